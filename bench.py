@@ -15,8 +15,13 @@ size ("weak"); batch64_1080p splits a fixed batch ("strong").
 
 Prints ONE JSON line on rank 0; see the task contract for the fields.  `roofline` is on the resource that binds -- VALU issue:
 the tile lives in registers for all sweeps, HBM is idle -- with the 17 B/pixel-sweep HBM-equivalent
-rate beside it.  Outside the timed region, on rank 0 at N = 1, the line also carries `estimate` (ms to a depth map: the whole
-1080p cascade), `sweep_4k` (the 4K sweep rate) and `effects` (the per-pixel passes), and `cpu_baseline` (the oracle on the host).
+rate beside it.  A plain run does nothing else: set-up, warm-up, the timed steps, the line.  With --full, outside the timed region
+on rank 0 at N = 1, the line also carries `estimate` (ms to a depth map: the whole 1080p cascade), `sweep_4k` (the 4K sweep rate),
+`effects` (the per-pixel passes), `sustained` and the other legs DESIGN.md section 5 lists, and `cpu_baseline` (the oracle on the host).
+
+--dump-outputs DIR writes what the last timed step computed -- every depth map of this rank's images (estimate workloads: the finest
+level and the u8 map) -- as DIR/<name>.npy in float32 (float64 for the residual-stopped solves' counts), at most 64 MB in all: beyond
+that, a fixed seeded sample of rows.  The inputs are seeded, so two builds run with the same arguments can be compared file by file.
 """
 import argparse
 import json
@@ -89,6 +94,7 @@ def jacobi_valu_ops():
 # CU busy: the chip clocks down under load) -- clamp, compare and select forms run at half rate -- against the 2 cycles `peak` assumes.
 # Reported beside `frac`, never instead of it.
 VALU_MIX_CYCLES = 2.66
+DUMP_BUDGET_BYTES = 64 * 10**6              # --dump-outputs: what all ranks write together
 
 
 def free_port():
@@ -135,6 +141,34 @@ def launch_ranks(n, argv, timeout_s=1500.0):
     sys.stdout.write(out0.read())
     sys.stdout.flush()
     return failed
+
+
+def pristine_copies(view, n):
+    """n more pitched device images holding what `view` (an rt.device_image) holds, padding included: device-to-device copies, so that
+    the set-up of a run with many steps does not pay one host upload per step."""
+    import torch
+    rows, pitch = view.shape[0], view.stride(0)
+    whole = view.as_strided((rows, pitch), (pitch, 1))
+    out = []
+    for _ in range(n):
+        b = torch.empty((rows, pitch), dtype=view.dtype, device=view.device)
+        b.copy_(whole)
+        out.append(b[:, :view.shape[1]])
+    return out
+
+
+def dump_outputs(out_dir, arrays, budget):
+    """Writes every named array as <out_dir>/<name>.npy.  If together they hold more than `budget` bytes, every image keeps the same
+    fraction of its rows, the rows drawn with a fixed seed: the same arguments give the same sample on any build."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    frac = min(1.0, budget / total) if total else 1.0
+    for name, a in arrays.items():
+        if frac < 1.0 and a.ndim >= 2:
+            keep = max(1, int(a.shape[0] * frac))
+            a = a[np.sort(np.random.default_rng(2024).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def cpu_baseline(rows, cols, method="jacobi", seconds_target=12.0):
@@ -619,9 +653,12 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="1080p_jacobi1000", help="one of %s, or ROWSxCOLSxITERS" % ", ".join(sorted(WORKLOADS)))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run the legs outside the timed region (sustained, whole-cascade estimates, "
+                    "photographs, drop-in frame, 4K / 8K sweeps, effects, batched estimates, photograph-like solves) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's results as DIR/<name>.npy (float32 / float64, 64 MB at most)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-clock-ramp", action="store_true", help="skip the untimed ~0.15 s of solves in front of the warm-up steps")
-    ap.add_argument("--no-estimate", action="store_true", help="skip the legs outside the timed region (whole-cascade estimate, 4K sweep, effects): profiling runs")
+    ap.add_argument("--no-estimate", action="store_true", help="with --full: skip the legs outside the timed region (whole-cascade estimate, 4K sweep, effects)")
     ap.add_argument("--sweep-kernel", type=int, default=0)
     ap.add_argument("--temporal-depth", type=int, default=0)
     ap.add_argument("--rows-per-wave", type=int, default=0)
@@ -633,6 +670,8 @@ def main():
                     "the line then carries `verified` (checker only: outside the timed region)")
     ap.add_argument("--dry-run", action="store_true", help="everything but the GPU work (launcher, rendezvous, sharding, aggregation): the N > 1 path on a CPU-only box")
     args = ap.parse_args()
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs the GPU work that --dry-run leaves out")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:        # plain `python3 bench.py --gpus N`: be the launcher
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -728,8 +767,9 @@ def main():
             masks = grays = []; depths = [[] for _ in range(args.steps + args.warmup)]
         else:
             masks = [rt.device_image(p["mask"], dev) for p in problems]; grays = [rt.device_image(p["gray"], dev) for p in problems]
-            # one pristine initial-depth image per image and step, uploaded before the clock starts
-            depths = [[rt.device_image(p["depth"], dev) for p in problems] for _ in range(args.steps + args.warmup)]
+            # one pristine initial-depth image per image and step, in place before the clock starts
+            firsts = [rt.device_image(p["depth"], dev) for p in problems]
+            depths = [firsts] + [list(c) for c in zip(*(pristine_copies(d, args.steps + args.warmup - 1) for d in firsts))]
 
         def step(i):
             if w.get("estimate"):
@@ -778,6 +818,22 @@ def main():
     if ctx:
         pr = ctx.profile(); sweep_ms = pr.sweep_ms; launches = pr.launches; sweeps = pr.sweeps   # events recorded inside the timed region (last <= 64 solves)
         info = ctx.last_solve_info()
+    if ctx and args.dump_outputs:             # what the last timed step computed, before --verify touches anything
+        n_all = batch if batch else world
+        dump = {}
+        for k, g in enumerate(my_images):
+            tag = f"_{g}" if n_all > 1 else ""
+            if w.get("estimate"):
+                ctx.pyramid_select(k)
+                dump["depth" + tag] = ctx.pyramid_download(rt.IMG_DEPTH, 0)
+                dump["depth_u8" + tag] = ctx.pyramid_download(rt.IMG_DEPTH_U8).astype(np.float32)
+            else:
+                dump["depth" + tag] = rt.to_host(depths[args.warmup + args.steps - 1][k])
+        if executed:                          # residual-stopped solves: the counts and residuals the last step's calls returned
+            last = executed[-len(my_images):]
+            for j, what in enumerate(("iterations", "residual", "cycles")[:len(last[0])]):
+                dump[f"solve_{what}" + (f"_rank{rank}" if world > 1 else "")] = np.array([e[j] for e in last], np.float64)
+        dump_outputs(args.dump_outputs, dump, DUMP_BUDGET_BYTES // world)
     if executed:                              # residual-stopped: count what actually ran (a V-cycle = its level-0 sweeps)
         per = MG_SWEEPS_PER_CYCLE if method == "multigrid" else 1
         px_iter_per_image = rows * cols * per * sum(e[0] for e in executed) / len(executed)
@@ -882,22 +938,22 @@ def main():
             dist.all_reduce(flag, op=dist.ReduceOp.SUM, group=tgroup)
         out["verified"] = {"against": "oracle.solve, bit for bit" if method == "jacobi" else "(hash only: no fixed-count oracle for this method)", "images_differing_all_ranks": int(flag.item()),
                            "rank0_images": [my_images[k] for k in range(len(problems))], "rank0_sha256_16": shas}
-    if not dry and rank == 0 and world == 1 and method in ("multigrid", "auto") and not args.no_estimate:
+    if not dry and rank == 0 and world == 1 and method in ("multigrid", "auto") and args.full and not args.no_estimate:
         out["photograph_like"] = photo_record(rt, dev, rows, cols)             # outside the timed region
     if executed:
         out["config"]["converged"] = {"tolerance": tolerance, "iterations": [e[0] for e in executed], "unit": "cycles" if method == "multigrid" else "sweeps",
                                       "residual": max(e[1] for e in executed), "start": "cold (depth 255 + labels)"}
-    if ctx and rank == 0 and world == 1 and default_line and not args.no_estimate:          # outside the timed region: the same solve for >= 3 s
+    if ctx and rank == 0 and world == 1 and default_line and args.full and not args.no_estimate:          # outside the timed region: the same solve for >= 3 s
         scratch_i = len(depths); depths.append([rt.device_image(p["depth"], dev) for p in problems])
         out["sustained"] = sustained(lambda: step(scratch_i), ctx.synchronize, len(my_images) * px_iter_per_image)
         depths.pop()
     # which numbers of this line were measured by THIS run and which are recordings read from committed files
-    out["measured_live"] = ["value", "ms_per_step", "roofline.launch_us (HIP events on the launch stream)", "roofline.achieved / frac (launch_us x the VALU count of the built object)",
-                            "sustained", "estimate*", "batch64_1080p_estimate", "sweep_4k / sweep_8k value and launch_us", "effects", "cpu_baseline"]
+    out["measured_live"] = ["value", "ms_per_step", "roofline.launch_us (HIP events on the launch stream)", "roofline.achieved / frac (launch_us x the VALU count of the built object)"] + (
+                           ["sustained", "estimate*", "batch64_1080p_estimate", "sweep_4k / sweep_8k value and launch_us", "effects", "cpu_baseline"] if args.full else [])
     out["recorded"] = ["roofline.traffic", "roofline.hbm_counter_frac", "roofline.valu_issue_frac_counted", "sweep_4k.traffic", "sweep_8k.traffic (rocprofv3 --pmc passes of the same command: counters_source)",
                        "roofline.mix_issue_cycles_measured (profiles/r03_block_replay.txt)"]
     if ctx: ctx.close()
-    if not dry and rank == 0 and world == 1 and default_line and not args.no_estimate:      # outside the timed region
+    if not dry and rank == 0 and world == 1 and default_line and args.full and not args.no_estimate:      # outside the timed region
         c2 = rt.Context(local); c2.set_stream(torch.cuda.current_stream().cuda_stream); c2.GPULoadWeights(0.4)
         out["estimate"] = estimate_ms(rt, c2, problems[0], rows, cols, dev)      # second half of BASELINE's metric
         out["estimate_4k"] = estimate_ms(rt, c2, make_problem(2160, 3840, seed=1234), 2160, 3840, dev, n=10)   # the 6-level 4K cascade (src/main.cpp:95,261-288)
@@ -910,7 +966,7 @@ def main():
         out["sweep_8k"] = sweep_4k(rt, dev, steps=5, rows=4320, cols=7680, iters=200, name="8k_jacobi200")   # HBM-resident (564 MB working set)
         out["effects"] = effects(rt, dev)
         out["batch64_1080p_estimate"] = batch_estimates(rt, dev)                 # BASELINE configs[3] at N = 1, as whole estimates
-    if not dry and rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if not dry and rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(rows, cols, method)
     if dist is not None:
         dist.destroy_process_group()

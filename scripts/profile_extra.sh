@@ -16,5 +16,5 @@ python3 scripts/prof_live_report.py /tmp/lvfx > $P/${RD}_live_frame_defocus_time
 find /tmp/df -name '*kernel_stats.csv' | head -1 | xargs -I{} sh -c "cut -c1-200 {} | head -12" > $P/${RD}_defocus_kernel_stats.csv
 python3 bench.py --gpus 1 --workload batch64_1080p --steps 2 --warmup 1 --no-cpu-baseline --verify > $P/${RD}_batch64_1080p_n1.json 2>/dev/null || exit 1
 python3 bench.py --gpus 1 --workload batch64_1080p_estimate --steps 3 --warmup 1 --no-cpu-baseline --verify > $P/${RD}_batch64_1080p_estimate_n1.json 2>/dev/null || exit 1
-python3 bench.py > $P/${RD}_bench_default.json 2>/dev/null || exit 1
+python3 bench.py --full > $P/${RD}_bench_default.json 2>/dev/null || exit 1
 tail -c 400 $P/${RD}_bench_default.json

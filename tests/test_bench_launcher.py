@@ -126,3 +126,67 @@ def test_the_batched_estimate_workload_the_bench_line_quotes_is_verified():
     assert v["images_differing_all_ranks"] == 0 and v["rank0_images_checked"] == [0, 1, 7, 8, 31, 32, 62, 63] and v["levels"] == 5, v
     assert v["rank0_level_choices"]["0"]["images_per_launch"] == 1 and v["rank0_level_choices"]["4"]["images_per_launch"] == 64
     assert d["estimates_per_s"] > 0
+
+
+def test_dump_outputs_keep_to_the_budget_with_a_fixed_sample(tmp_path):
+    """--dump-outputs: arrays that fit are written whole; beyond the budget every image keeps the same fraction of its rows, drawn
+    with a fixed seed, so two runs (two builds) with the same arguments write the same sample."""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(5)
+    small = {"depth": rng.random((40, 30), dtype=np.float32), "solve_iterations": np.array([3.0, 4.0])}
+    bench.dump_outputs(str(tmp_path / "whole"), small, 10**6)
+    for k, a in small.items():
+        assert np.array_equal(np.load(tmp_path / "whole" / f"{k}.npy"), a)
+    big = {f"depth_{i}": rng.random((1000, 250), dtype=np.float32) for i in range(4)}      # 4 MB
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), big, 10**6)
+    total = 0
+    for k, a in big.items():
+        got = np.load(tmp_path / "a" / f"{k}.npy")
+        assert got.dtype == np.float32 and got.shape[1] == 250 and 0 < got.shape[0] < 1000
+        assert np.array_equal(got, np.load(tmp_path / "b" / f"{k}.npy"))
+        assert all(any(np.array_equal(r, s) for s in a) for r in got[:5])          # the sample's rows are the image's rows
+        total += got.nbytes
+    assert total <= 10**6
+
+
+def test_pristine_copies_hold_the_pitched_image_padding_included():
+    import torch
+    import bench
+    base = torch.arange(6 * 16, dtype=torch.float32).reshape(6, 16)
+    view = base[:, :13]
+    copies = bench.pristine_copies(view, 3)
+    assert len(copies) == 3
+    for c in copies:
+        assert c.shape == view.shape and c.stride() == view.stride() and torch.equal(c, view)
+        assert torch.equal(c.as_strided((6, 16), (16, 1)), base) and c.data_ptr() != view.data_ptr()
+    copies[0][0, 0] = -1.0
+    assert view[0, 0] == 0.0 and copies[1][0, 0] == 0.0
+
+
+@pytest.mark.gpu
+def test_dumped_outputs_are_the_last_steps_depth_maps(tmp_path):
+    """bench.py --dump-outputs on a batch of two images: the files are the depth maps of the last timed step, equal to the oracle's bit
+    for bit; an estimate workload writes the finest depth and the u8 map of every image.  A plain run carries none of the --full legs."""
+    import numpy as np
+    import oracle
+    from realtimedepthdiffusion_amd.synth import make_problem
+    d = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "batch2_270x480x100", "--dump-outputs", str(tmp_path / "solve")])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    lut = oracle.load_weights(0.4)
+    for i in range(2):
+        p = make_problem(270, 480, seed=1234 + i)
+        want = oracle.solve(p["depth"].copy(), p["mask"], p["gray"], 100, 0, 0, lut, 1, threads=oracle.max_threads())
+        got = np.load(tmp_path / "solve" / f"depth_{i}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got.view(np.uint32), want.view(np.uint32)), i
+    _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "batch2_270x480x100_estimate", "--dump-outputs", str(tmp_path / "est")])
+    for i in range(2):
+        u8 = np.load(tmp_path / "est" / f"depth_u8_{i}.npy")
+        depth = np.load(tmp_path / "est" / f"depth_{i}.npy")
+        assert u8.shape == depth.shape == (270, 480) and u8.dtype == depth.dtype == np.float32
+        assert u8.min() >= 0 and u8.max() <= 255 and np.array_equal(u8, np.round(u8))
+    plain = _run(["--gpus", "1", "--steps", "2", "--warmup", "1"])
+    assert plain["value"] > 0 and plain["unit"] == "Mpixel-iterations/s" and plain["roofline"]["bound"] == "valu"
+    for leg in ("sustained", "estimate", "sweep_4k", "effects", "cpu_baseline"):
+        assert leg not in plain, leg
