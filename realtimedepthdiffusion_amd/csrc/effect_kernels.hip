@@ -562,9 +562,6 @@ __global__ __launch_bounds__(256) void k_defocus(const uint8_t *__restrict__ ori
 constexpr int kDtW = 64, kDtHM = 28, kDtRW = 124, kDtWorkers = 8;
 static_assert(kDtW + 2 * kDtHM + 3 <= kDtRW && kDtRW % 4 == 0 && kDtRW / 4 <= 32, "the region: tile + both margins + the alignment of its first column, one group of four per lane of a half-wave");
 
-#ifndef RTDD_DT_DIAG
-#define RTDD_DT_DIAG 0       // timing-only ablations of k_defocus_tile (results wrong): 1 no row scan, 2 no lookups, 4 no unpack
-#endif
 // inclusive prefix sum over the 32 lanes of each half of a wave (the wave scan without its last step)
 __device__ __forceinline__ u64 half_incl_scan64(u64 v) {
     u64 t = v + RTDD_DPP64(v, 0x111, 0xF, 0xF);
@@ -587,12 +584,7 @@ __global__ __launch_bounds__(256, 2) void k_defocus_tile(const uint8_t *__restri
     if (tile >= ntiles) return;
     // (loads and table build at a raised wave priority, the lookups at the normal one: of the two workgroups on a CU the one still
     // building gets ahead of the other's lookups -- 1080p 27.3 -> 26.5 us, 672 x 624 8.9 -> 8.5)
-#ifndef RTDD_DT_PRIO
-#define RTDD_DT_PRIO 2
-#endif
-#if RTDD_DT_PRIO
-    __builtin_amdgcn_s_setprio(RTDD_DT_PRIO);
-#endif
+    __builtin_amdgcn_s_setprio(2);
     const int tid = threadIdx.x, lane = tid & 63, wv = wave_id();
     const int tx0 = (tile % gx) * kDtW, ty0 = (tile / gx) * kDtH;
     const int R0 = ty0 - hm, C0 = (tx0 - hm) & ~3;                  // (a multiple of four, also when negative: groups of four never straddle column 0)
@@ -648,12 +640,11 @@ __global__ __launch_bounds__(256, 2) void k_defocus_tile(const uint8_t *__restri
 #pragma unroll
     for (int i = 0; i < kDtRowsPer; i++) {
         u64 px[4];
-        if (RTDD_DT_DIAG & 4) { px[0] = raw[i].w0; px[1] = raw[i].w1; px[2] = raw[i].w2; px[3] = raw[i].w0 ^ raw[i].w1; }
-        else unpack4(raw[i].w0, raw[i].w1, raw[i].w2, px);          // (zeros where nothing was loaded: outside the image or the region)
+        unpack4(raw[i].w0, raw[i].w1, raw[i].w2, px);          // (zeros where nothing was loaded: outside the image or the region)
 #pragma unroll
         for (int k = 0; k < 4; k++) col[k] += px[k];
         const u64 s0 = col[0], s1 = s0 + col[1], s2 = s1 + col[2], s3 = s2 + col[3];
-        const u64 excl = (RTDD_DT_DIAG & 1) ? s3 : half_incl_scan64(s3) - s3;
+        const u64 excl = half_incl_scan64(s3) - s3;
         v[i][0] = s0 + excl; v[i][1] = s1 + excl; v[i][2] = s2 + excl; v[i][3] = s3 + excl;
     }
     // each chunk's last row (its column totals, row-prefixed) goes through the table's own row `worker` -- LDS has no room for a
@@ -684,9 +675,7 @@ __global__ __launch_bounds__(256, 2) void k_defocus_tile(const uint8_t *__restri
     }
     __syncthreads();
 
-#if RTDD_DT_PRIO
     __builtin_amdgcn_s_setprio(0);
-#endif
     // ---- lookups (k_defocus with the corners in LDS) ----
     // The common case -- the window lies inside the region -- is straight-line code for the whole wave: clamped LDS addresses, selects
     // instead of branches, the quotients by quot3_u8 (count <= 56 x 56); what it computes for a lane whose window does not
@@ -702,7 +691,7 @@ __global__ __launch_bounds__(256, 2) void k_defocus_tile(const uint8_t *__restri
         const int ya = max(yc - h, 0), yb = min(yc + h, rows);
         const int xa = max(xc - h, 0), xb = min(xc + h, cols);
         const int wd = xb - xa, ht = yb - ya;
-        const bool has = !(RTDD_DT_DIAG & 2) && wd > 0 && ht > 0, local = h <= hm;
+        const bool has = wd > 0 && ht > 0, local = h <= hm;
         // T(r, c) of the region's table at the four corners; a row / column before the region sums to nothing
         const int r1 = min(max(yb - 1 - R0, 0), rh1), r0 = min(ya - 1 - R0, rh1), c1 = min(max(xb - 1 - C0, 0), kDtRW - 1), c0 = min(xa - 1 - C0, kDtRW - 1);
         const int r0c = max(r0, 0), c0c = max(c0, 0);
@@ -843,8 +832,7 @@ int launch_defocus(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const float *d
     const int trows_max = nslices == 1 ? rows : (slice_rows + 2 * reach < rows ? slice_rows + 2 * reach : rows);
     // band height: one workgroup per band builds the table, so enough bands to occupy the chip (270 / 135 / 135 workgroups of 8 / 16 / 16
     // waves at 1080p / 4K / 8K); a band costs 8 B per column three times over (colsum, its scan, the build's read)
-    static const int rb_env = getenv("RTDD_DEFOCUS_BAND") ? atoi(getenv("RTDD_DEFOCUS_BAND")) : 0;
-    const int RB = rb_env >= 4 && rb_env <= 32 && rb_env % 4 == 0 ? rb_env : trows_max <= 1536 ? 4 : trows_max <= 3072 ? 16 : 32;
+    const int RB = trows_max <= 1536 ? 4 : trows_max <= 3072 ? 16 : 32;
     const int nbands_max = (trows_max + RB - 1) / RB;
     const size_t table_entries = ((size_t)trows_max + 1) * tpitch;
     // k_defocus addresses the padded table with 32-bit BYTE offsets (one 24-bit multiply per corner row) through a buffer resource whose

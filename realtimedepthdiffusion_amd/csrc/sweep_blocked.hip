@@ -21,27 +21,12 @@
 // Outside-image pixels are held at x = 0 with all weights 0, which reproduces the reference's
 // "skip the missing neighbour" (src/GPUSolver.cu:79-101) exactly: fma(0, 0, s) == s up to the
 // sign of a zero sum, and that sign never reaches the output ("Zero-weight borders").
-#include <cstdlib>
 #include <type_traits>
 
 #include "rtdd_internal.hpp"
-#include <cstring>
 #include "persist_sync.hpp"
 #include "sweep_common.hpp"
 #include "sweep_diag.hpp"      // RTDD_STAMP / RTDD_TL / RTDD_XT: empty unless a diagnostic micro-benchmark asks for them
-
-// RTDD_MASKED_UPDATE (default 1): the update's last fma under an EXEC mask instead of a v_cndmask behind it, omega / gamma in VGPRs
-// (sweep_common.hpp masked_fmac4); 0 = the round-4 form, kept for A/B builds (scripts/build_variant.sh).
-#ifndef RTDD_MASKED_UPDATE
-#define RTDD_MASKED_UPDATE 1
-#endif
-
-// RTDD_OCC_G2 (A/B builds; default 4 = no change): waves per SIMD asked of the compiler for the 64 x 64 tile of 8 pixels per thread (tile 10):
-// 6 would put three of its workgroups on a CU (85 registers per thread) -- round 6's question whether more workgroups per CU hide the
-// tile loads at 4K better than the 64 x 96 tile's two (EXPERIMENTS.md)
-#ifndef RTDD_OCC_G2
-#define RTDD_OCC_G2 4
-#endif
 
 namespace rtdd {
 
@@ -75,7 +60,7 @@ __device__ __forceinline__ float relax(float xl, float xr, float xu, float xd, f
 // sweep loop (measured 25 % slower), so G = 4 tiles ask for 3 waves/SIMD (168 VGPRs) unless the
 // workgroup is 1024 threads (which needs 4 waves/SIMD to be launchable at all).  G <= 3 fits 128.
 template <int LX, int NT, int G, bool CONTRACT, bool PERSIST>
-__global__ __launch_bounds__(NT, (G == 2 && NT == 512 ? RTDD_OCC_G2 : NT >= 1024 || G <= 3 ? 4 : G <= 4 ? 3 : 2)) void k_sweep_blocked(float *Xk, float *Xm, float *Yk, float *Ym,
+__global__ __launch_bounds__(NT, (NT >= 1024 || G <= 3 ? 4 : G <= 4 ? 3 : 2)) void k_sweep_blocked(float *Xk, float *Xm, float *Yk, float *Ym,
                                                       const uint32_t *__restrict__ M, const float *__restrict__ lut_g,
                                                       const float *__restrict__ omegas, int ip, int rows, int cols,
                                                       int hx, int hy, int nsweeps, float gamma,
@@ -395,16 +380,8 @@ __global__ __launch_bounds__(1024) void k_sweep_col(const float *__restrict__ Xk
         rcp[g] = rcp_rn(cnt[g]);
         unsafe |= cnt[g] < 0x1p-126f;
     }
-#ifdef RTDD_TIMING_ASSUME_SAFE
-    const bool wave_unsafe = false; (void)unsafe;      // (timing-only diagnostic build: sweep_tile_setup.inc)
-#else
     const bool wave_unsafe = __builtin_amdgcn_ballot_w64(unsafe) != 0;
-#endif
-#ifdef RTDD_TIMING_NO_TINY
-    constexpr uint32_t kTinyT = 0u;
-#else
     constexpr uint32_t kTinyT = 2u * 0x0D800000u - 1u;
-#endif
     const int up_w = wv > 0 ? wv - 1 : wv, dn_w = wv < nwv - 1 ? wv + 1 : wv;
     // (the first / last wave reads its own row instead of a missing neighbour: weighted 0 at the image border, discarded halo elsewhere)
     const int up_half = wv > 0 ? 1 : 0, dn_half = wv < nwv - 1 ? 0 : 1;        // which (value, tag) pair of the entry: 0 = top, 1 = bottom
@@ -450,7 +427,7 @@ __global__ __launch_bounds__(1024) void k_sweep_col(const float *__restrict__ Xk
             }
         }
         RTDD_TL_ROWS_IN_HAND(s);
-        const float omega = omegas[s], gamma_v = gamma;     // (scalar operands: the vector form measured no faster, see k_sweep_blocked)
+        const float omega = omegas[s], gamma_v = gamma;     // (scalar operands: k_sweep_blocked's masked, vector form measured 2 % slower here -- EXPERIMENTS.md round 5)
         // (the lane shifts stay DPP here: through the LDS crossbar -- 8 ds_bpermute_b32 per thread and sweep, as k_sweep_blocked does with
         // its 2 per row -- the coarse levels measured 20 % SLOWER, and with no shifts at all (timing only) no faster: EXPERIMENTS.md)
         auto wsum = [&](int g) {
@@ -636,7 +613,7 @@ static double config_cost(const rtdd_ctx *ctx, int rows, int cols, int n, int ti
         const double rounds = ceil(nwg / (cus * k));
         const double m_eff = rounds <= 3 ? rounds * k : m;     // few rounds: the last, partly filled one costs a whole round
         // (1.45: what the single-image choices of rounds 1-3 were calibrated with; the kernels have become faster since, and the batch
-        // measurements of round 5 -- scripts/batch_level_ab.py: 64 x 480x270 tile 6 depth 8 7.8 us per sweep, 64 x 960x540 29, 64 x 1080p 110; tiles
+        // measurements of round 5 -- profiles/r05_batch_level_ab.txt: 64 x 480x270 tile 6 depth 8 7.8 us per sweep, 64 x 960x540 29, 64 x 1080p 110; tiles
         // 5 and 7 alike -- fit 0.95 for the tiles of three rows per thread; tile 9 (one row per thread: 13 us where 0.95 says 8) keeps 1.45)
         const double comp = (images > 1 && G >= 3 ? 0.95 : 1.45) * T * thr1, mem = load1 + store1;
         t = boundary + load1 + m_eff * (comp > mem ? comp : mem);
@@ -668,8 +645,6 @@ static double choose_config(const rtdd_ctx *ctx, int rows, int cols, int n, int 
     }
     if (fixed_tile && best >= 1e30) *tile = fixed_tile;
     if (fixed_T && best >= 1e30) *T = fixed_T;
-    if (getenv("RTDD_DEBUG_CONFIG"))
-        fprintf(stderr, "[rtdd] %dx%d x %d image(s) n=%d -> tile %d depth %d persistent %d (model %.3f us/sweep)\n", cols, rows, images, n, *tile, *T, (int)*persist, best);
     return best;
 }
 
@@ -687,35 +662,12 @@ static int launch_sweeps_blocked_impl(rtdd_ctx *ctx, const Level &L, size_t ip, 
 // single solve gets, which the model prices lower than a launch per block over the whole batch.
 int launch_sweeps_blocked(rtdd_ctx *ctx, const Level &L, size_t ip, int rows, int cols, const float *omegas_dev, int n,
                           int *pk, int *pm, int *launches, int images) {
-#ifdef RTDD_FORCE_CFG_HOOK
-    {   // developer's hook (A/B builds only): RTDD_FORCE_CFG="cols,rows,tile,depth,persistent,per_image;..." pins the choice for a level size
-        static const char *env = getenv("RTDD_FORCE_CFG");
-        for (const char *q = env; q && *q;) {
-            int c = 0, r = 0, ti = 0, d = 0, pe = 0, pi = 0;
-            if (sscanf(q, "%d,%d,%d,%d,%d,%d", &c, &r, &ti, &d, &pe, &pi) == 6 && c == cols && r == rows) {
-                const Options saved_opt = ctx->opt;
-                ctx->opt.tile = ti; ctx->opt.temporal_depth = d; ctx->opt.persistent = pe;
-                int rc = RTDD_OK, a = *pk, b = *pm, total = 0;
-                if (pi) {
-                    for (int i = 0; i < images && rc == RTDD_OK; i++) {
-                        a = *pk; b = *pm; int ln = 0;
-                        rc = launch_sweeps_blocked_impl(ctx, L.view(i), ip, rows, cols, omegas_dev, n, &a, &b, &ln, 1); total += ln;
-                    }
-                } else rc = launch_sweeps_blocked_impl(ctx, L, ip, rows, cols, omegas_dev, n, &a, &b, &total, images);
-                ctx->opt = saved_opt;
-                *pk = a; *pm = b; *launches = total;
-                return rc;
-            }
-            q = strchr(q, ';'); if (q) q++;
-        }
-    }
-#endif
     if (images > 1 && ctx->opt.tile == 0 && ctx->opt.temporal_depth == 0 && !(cols <= 128 && rows <= 96)) {
         int t1, T1, tb, Tb; bool p1, pb;
         const double c1 = choose_config(ctx, rows, cols, n, 0, 0, &t1, &T1, &p1, 1);
         const double cb = choose_config(ctx, rows, cols, n, 0, 0, &tb, &Tb, &pb, images);
         // (the model prices a persistent 1080p launch at 2.5 us per sweep; it runs at 1.5 -- profiles/r05_1080p_jacobi1000_* -- and 64 images
-        // one after the other take 5.96 ms where one launch per block over the batch takes 6.83: scripts/batch_level_ab.py)
+        // one after the other take 5.96 ms where one launch per block over the batch takes 6.83: profiles/r05_batch_level_ab.txt, measured with scripts/batch_level_ab.py of commit eb70ff4)
         if (p1 && 0.6 * c1 * images < cb) {
             int rc = RTDD_OK, a = *pk, b = *pm, total = 0;
             for (int i = 0; i < images && rc == RTDD_OK; i++) {
@@ -792,10 +744,9 @@ static int launch_sweeps_blocked_impl(rtdd_ctx *ctx, const Level &L, size_t ip, 
             { const int rc_ = prepare_persistent_launch(ctx, (m + T - 1) / T, &flag_base); if (rc_ != RTDD_OK) return rc_; }   // this launch's flag values, debug words
             note_status_writer(ctx);
         }
-        // XCD-aware tile placement (RTDD_XCD_REMAP=0 turns it off): +1.5-4 % persistent (strips traded inside one L2), +8 % at 4K
-        // launch-per-block (a tile's halo is its neighbours' centre: the same XCD reads both)
-        static const bool xcd_remap = !(getenv("RTDD_XCD_REMAP") && atoi(getenv("RTDD_XCD_REMAP")) == 0);
-        const int xcd_tiles = (!single && xcd_remap) ? ((int)(grid.x * grid.y) + 7) / 8 : 0;   // (filling one XCD before the next measured the same)
+        // XCD-aware tile placement: +1.5-4 % persistent (strips traded inside one L2), +8 % at 4K launch-per-block (a tile's halo is its
+        // neighbours' centre: the same XCD reads both)
+        const int xcd_tiles = !single ? ((int)(grid.x * grid.y) + 7) / 8 : 0;   // (filling one XCD before the next measured the same)
         // outputs go to the two spare planes, then the pairs swap
         int free0 = -1, free1 = -1;
         for (int i = 0; i < 4; i++) if (i != *pk && i != *pm) { if (free0 < 0) free0 = i; else free1 = i; }

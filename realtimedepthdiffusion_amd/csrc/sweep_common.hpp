@@ -31,13 +31,6 @@ __device__ __forceinline__ float lds_from_next(int prev4, float v) { return __in
 __device__ __forceinline__ void store_sc1(float4 *p, float4 v) {
     typedef float f4v __attribute__((ext_vector_type(4)));
     const f4v t = {v.x, v.y, v.z, v.w};
-#ifdef RTDD_TIMING_PLAIN_STRIPS
-    // TIMING-ONLY diagnostic build (scripts/build_variant.sh; never the product: cross-XCD neighbours read stale strips): what the exchange
-    // would cost if EVERY strip could be stored plain -- kept in the storing XCD's L2 -- i.e. the upper bound of storing same-XCD strips
-    // without write-through (EXPERIMENTS.md round 6)
-    asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" ::"v"(p), "v"(t) : "memory");
-    return;
-#endif
     asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(t) : "memory");
 }
 

@@ -88,14 +88,7 @@
         }
         finish_setup();
     }
-#ifdef RTDD_TIMING_ASSUME_SAFE
-    // TIMING-ONLY diagnostic build (never the product: pixels with a denormal divisor come out wrong): what the waves that meet such a pixel
-    // would cost on the 3-operation divide -- the bound of any finer-grained treatment of them (EXPERIMENTS.md round 6)
-    const bool wave_unsafe = false; (void)unsafe;
-#else
     const bool wave_unsafe = __builtin_amdgcn_ballot_w64(unsafe) != 0;
-#endif
-#if RTDD_MASKED_UPDATE
     // the update's last operation runs under an EXEC mask of the FREE pixels (sweep_common.hpp masked_fmac4): one lane mask per pixel
     // of the thread, in SGPR pairs (where the v_cndmask form kept its masks), and a Dirichlet pixel's value in BOTH iterates
     unsigned long long free_mask[G][4];
@@ -107,4 +100,3 @@
             free_mask[g][i] = __builtin_amdgcn_ballot_w64(!dir);
             b[g][i] = dir ? a[g][i] : b[g][i];
         }
-#endif

@@ -2,11 +2,7 @@
 // through LDS and ONE sweep of the register-resident tile, as lambdas over the tile's registers.
 // Expects in scope: PERSIST (constexpr bool), CONTRACT, G, LX, edge[], published[], dead_s, sync_words, omegas, gamma, tid, lx, tr, ntr,
 // bx, by, gx and the tile registers of sweep_tile_setup.inc.
-#ifdef RTDD_TIMING_NO_TINY
-    constexpr uint32_t kTinyT = 0u;                             // (timing-only diagnostic build: the tiny-numerator redo never taken; wrong results where it would be)
-#else
     constexpr uint32_t kTinyT = 2u * 0x0D800000u - 1u;          // bits(2^-100) = 27 << 23
-#endif
     const int prev4 = (((int)threadIdx.x + 63) & 63) * 4;       // horizontal neighbours across lanes by ds_bpermute_b32, issued a group ahead (sweep_common.hpp: why not DPP)
     const int wv = tid >> 6, nwv = (int)blockDim.x >> 6;
     const int tile_id_tl = by * gx + bx; (void)tile_id_tl;
@@ -71,17 +67,10 @@
         const float4 dn4 = edge[buf][tr < ntr - 1 ? tr + 1 : tr][G == 1 || tr < ntr - 1 ? 0 : 1][lx];
         const float up[4] = {up4.x, up4.y, up4.z, up4.w}, dn[4] = {dn4.x, dn4.y, dn4.z, dn4.w};
         RTDD_TL_ROWS_IN_HAND(s);
-        // omega and gamma stay SCALAR operands: in isolation v_fma_f32 with an SGPR operand issues at 4.8 cycles per wave-instruction and
-        // SIMD and with three VGPRs at 3.2 (scripts/ubench/valu_mix.hip, profiles/r03_valu_mix.txt), but inside this loop the vector form
-        // measured 0.5-1.5 % SLOWER (1080p, 4K: EXPERIMENTS.md)
-#if RTDD_MASKED_UPDATE
         // omega and gamma in VGPRs: an fma with an SGPR operand issues at 4.3 cycles per wave-instruction, with three VGPRs at 3.1
         // (profiles/r05_excp_probe.txt); one v_mov per wave and sweep
         float omega_v = omegas[s], gamma_v = gamma;
         asm volatile("" : "+v"(omega_v), "+v"(gamma_v));
-#else
-        const float omega = omegas[s], gamma_v = gamma;
-#endif
         // weighted sum of pixel (g, i): solveDiffusion, src/GPUSolver.cu:73-106, absent neighbours carried as (w = 0, x = 0)
         auto wsum = [&](int g, int i) {
             const float xl = i == 0 ? xl0[g] : cur[g][i - 1];
@@ -123,7 +112,6 @@
 #pragma unroll
             for (int g = 0; g < G; g++) {
                 if (!pick(g)) continue;
-#if RTDD_MASKED_UPDATE
                 float t[4], o[4];
 #pragma unroll
                 for (int i = 0; i < 4; i++) {
@@ -138,17 +126,6 @@
                 else masked_add4(o[0], o[1], o[2], o[3], t[0], t[1], t[2], t[3], free_mask[g][0], free_mask[g][1], free_mask[g][2], free_mask[g][3]);
 #pragma unroll
                 for (int i = 0; i < 4; i++) oth[g][i] = o[i];
-#else
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    // :104 min(max(r,0),255): v_med3_f32 returns min3 when an operand is NaN, i.e. 0 here, like fmax/fmin
-                    const float r = __builtin_amdgcn_fmed3f(q[g][i], 0.0f, 255.0f);        // cnt == 0 was replaced by 1 (sum is 0 there): r = 0 (:103)
-                    const float x = cur[g][i], prev = oth[g][i];
-                    const float v = CONTRACT ? __builtin_fmaf(omega, __builtin_fmaf(gamma_v, r - x, x) - prev, prev)      // src/GPUSolver.cu:259
-                                             : (omega * (gamma_v * (r - x) + x - prev)) + prev;
-                    oth[g][i] = (dirichlet >> (g * 4 + i)) & 1u ? x : v;                    // x_{k+1} replaces x_{k-1}
-                }
-#endif
             }
         };
         // The rows the neighbouring waves wait for (first and last) are computed at a raised wave priority, the interior rows at the normal

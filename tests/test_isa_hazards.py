@@ -123,10 +123,9 @@ def test_acquire_fallback_of_the_hand_off_builds(tmp_path):
     """RTDD_EXCHANGE_ACQUIRE=1 is the documented fallback of the no-acquire hand-off (agent-scope acquire + plain loads), in both
     persistent kernels.  It must keep compiling, contain the cache invalidate and no sc1 load; tests/test_gpu_parity.py runs it on the GPU
     (test_acquire_variant_of_the_hand_off_is_bit_exact) when the variant library has been built (scripts/build_variant.sh acq ...)."""
-    flags = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize",
-             "-fvisibility=hidden", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-DRTDD_EXCHANGE_ACQUIRE=1"]
+    flags = subprocess.check_output(["make", "-s", "--no-print-directory", "-C", CSRC, "print-cxxflags"], text=True).split()     # the product's flags (-I. included: run in csrc)
     obj = str(tmp_path / "rbgs_acq.o")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950"] + flags + ["-c", os.path.join(CSRC, "rbgs_blocked.hip"), "-o", obj])
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950"] + flags + ["-DRTDD_EXCHANGE_ACQUIRE=1", "-c", "rbgs_blocked.hip", "-o", obj], cwd=CSRC)
     asm = _disassembly(tmp_path, "rbgs_acq2.o", src=obj)
     persistent = [f for f in re.split(r"\n(?=[0-9a-f]+ <[^>]+>:)", asm) if "k_rbgs_blocked" in f.split("\n", 1)[0] and "buffer_inv sc1" in f]
     assert len(persistent) >= 4, "the acquire variant must invalidate at agent scope (buffer_inv sc1) in every persistent instantiation"
