@@ -2,7 +2,7 @@
 
 TEST INFRASTRUCTURE ONLY.  Importable from tests/, __graft_entry__.smoke() and the
 cpu_baseline leg of bench.py -- never from realtimedepthdiffusion_amd/.  See the header of
-rtdd_oracle.c for what pins it (the reference has no golden vectors: "parity unpinned").
+rtdd_oracle.c for what pins it (oracle/ref.py loads the reference's own GPU code, built by build_ref()).
 
 All image arguments are numpy arrays whose last axis is contiguous; the row pitch handed to
 C is ``arr.strides[0]`` so pitched (padded-row) views work exactly like the reference's
@@ -23,6 +23,32 @@ def build(force=False):
     if force or not os.path.exists(_SO) or any(os.path.getmtime(s) > os.path.getmtime(_SO) for s in srcs):
         subprocess.check_call(["make", "-C", _HERE, "-B", "liboracle.so"], stdout=subprocess.DEVNULL)
     return _SO
+
+
+REF_DIR = os.path.join(_HERE, "_ref")
+REF_SOURCES = ("GPUSolver", "GPUImageProcessing", "GPUDepthEffect")
+
+
+def reference_dir():
+    """The reference tree the recipe reads: $RTDD_REFERENCE_DIR, else a `reference` directory next to the repository."""
+    return os.environ.get("RTDD_REFERENCE_DIR") or os.path.join(os.path.dirname(os.path.dirname(_HERE)), "reference")
+
+
+def build_ref():
+    """Build the reference's own GPU code into oracle/_ref/libref_c{0,1}.so by the recipe oracle/ref.mk (loaded by oracle/ref.py).
+
+    Without the reference tree this prints one line and keeps whatever oracle/_ref/ already holds; a failed build prints one line
+    too (tests/test_reference_build.py is what fails then).  Never raises, never deletes.  Returns the directory, or None."""
+    ref = reference_dir()
+    if not all(os.path.isfile(os.path.join(ref, "src", n + ".cu")) for n in REF_SOURCES):
+        print(f"[oracle] no reference tree at {ref} (set RTDD_REFERENCE_DIR): oracle/_ref/ left as it is")
+        return None
+    try:
+        subprocess.check_call(["make", "-C", _HERE, "-f", "ref.mk", "-j2", f"REF={os.path.abspath(ref)}"], stdout=subprocess.DEVNULL)
+    except (OSError, subprocess.CalledProcessError) as e:
+        print(f"[oracle] building the reference's GPU code failed ({e}): oracle/_ref/ left as it is")
+        return None
+    return REF_DIR
 
 
 _lib = None

@@ -5,12 +5,13 @@
  * and bench.py's cpu_baseline leg may load it.  The product path (realtimedepthdiffusion_amd/)
  * never links, imports or falls back to anything in oracle/.
  *
- * PARITY UNPINNED BY THE REFERENCE: the reference ships no tests, golden vectors or
- * known-answer fixtures for this path, and its CUDA/OpenCV sources cannot be built here
- * (no nvcc, no OpenCV).  This file is pinned instead by (1) hand-computable known-answer
- * cases, (2) an independent numpy restatement (tests/np_restatement.py) that must agree
- * bit-for-bit in both FP-contraction variants, (3) scipy spsolve of the underlying linear
- * system, and (4) committed goldens produced by this file (tests/golden/).
+ * The reference ships no tests, golden vectors or known-answer fixtures for this path.
+ * This file is pinned by (1) hand-computable known-answer cases, (2) an independent numpy
+ * restatement (tests/np_restatement.py) that must agree bit-for-bit in both FP-contraction
+ * variants, (3) scipy spsolve of the underlying linear system, (4) committed goldens
+ * produced by this file (tests/golden/), and (5) the reference's own GPU code, hipified
+ * and built for gfx950 (oracle/ref.mk), which reproduces those goldens and the product
+ * (tests/test_gpu_reference.py).
  *
  * Every function cites the reference lines it follows (paths relative to /root/reference).
  * Arithmetic is IEEE binary32 with denormals preserved; build with
