@@ -7,6 +7,8 @@
 //     key 'd'  -> one depth estimate        (main.cpp:232-295)  -> <out>DepthMap.pgm     (main.cpp:306-310)
 //     key 's'  -> also the annotated image   (main.cpp:298-303)  -> <out>AnnotatedImage.ppm: the image with the scribbles painted in
 //     key 'b'/'g'/'h' -> --effect defocus|desaturation|haze     -> <out>ArtisticEffect.ppm (main.cpp:190-230, 312-316)
+//     extensions: --effect refocus [--focus D | --focus-at X,Y] [--aperture A]   (rtdd_simulate_refocus; default: focus depth 0,
+//                 aperture 0.025 = the defocus), --effect haze [--haze-beta B] [--airlight b,g,r]   (rtdd_simulate_haze_ex when either is given)
 //     key 't'  -> prints "Processing Time"  (main.cpp:320-322; wall clock here, the reference uses clock()); the process's one-time costs
 //                 (~20 ms: code objects, first allocations) are paid by a warm-up on a context of its own first -- --cold leaves it out
 //     --paint x,y,label,radius  = a mouse drag sample (main.cpp:46-62), repeatable; --paint-at F:x,y,label,radius = the same while --live
@@ -173,6 +175,12 @@ struct Job {
     int iters = 1000;
     std::string refine;           // "" | "sor" | "mg": rtdd_refine_depth after every estimate
     float tolerance = 1e-4f;
+    double aperture = 0.025;      // --effect refocus: --aperture, --focus / --focus-at (focus_x < 0: the depth focus_depth)
+    float focus_depth = 0.0f;
+    int focus_x = -1, focus_y = -1;
+    bool haze_ex = false;         // --haze-beta / --airlight given: rtdd_simulate_haze_ex
+    float haze_beta = 2.0f;
+    int air[3] = {255, 255, 255}; // b, g, r
     bool sequential = false;      // --sequential: a --batch as one estimate after the other (default: rtdd_estimate_depth_batch, all images in the same launches)
     bool cold = false;            // --cold: no warm-up: the first (and, without --live, only) estimate pays the one-time costs
 };
@@ -364,7 +372,13 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
         }
         if (job.effect == "defocus") CK(rtdd_simulate_defocus(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols));
         else if (job.effect == "desaturation") CK(rtdd_simulate_desaturation(ctx, (uint8_t *)p_orig, pi_orig, (uint8_t *)p_gray, pi_gray, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols));
+        else if (job.effect == "haze" && job.haze_ex)
+            CK(rtdd_simulate_haze_ex(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols, job.haze_beta,
+                                     (uint8_t)job.air[0], (uint8_t)job.air[1], (uint8_t)job.air[2]));
         else if (job.effect == "haze") CK(rtdd_simulate_haze(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols));
+        else if (job.effect == "refocus")
+            CK(rtdd_simulate_refocus(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols, job.aperture,
+                                     job.focus_depth, job.focus_x, job.focus_y));
         depth_u8->resize((size_t)rows * cols);
         CK(rtdd_download(ctx, depth_u8->data(), cols, p_u8, pi_u8, cols, rows));   // main.cpp:291 (synchronises)
         if (!job.effect.empty()) { art->resize((size_t)rows * cols * 3); CK(rtdd_download(ctx, art->data(), (size_t)cols * 3, p_art, pi_art, (size_t)cols * 3, rows)); }
@@ -377,7 +391,8 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
 }
 
 int main(int argc, const char *argv[]) {
-    if (argc == 1) { std::printf("Usage: rtdd_harness -i image.(jpg|png|ppm) [-a annotation.(png|pgm)] [-o prefix] [--effect defocus|desaturation|haze] [--iters N] [--refine sor|mg|auto [--tolerance T]]\n"
+    if (argc == 1) { std::printf("Usage: rtdd_harness -i image.(jpg|png|ppm) [-a annotation.(png|pgm)] [-o prefix] [--effect defocus|desaturation|haze|refocus] [--iters N] [--refine sor|mg|auto [--tolerance T]]\n"
+                                 "                    [--focus D | --focus-at X,Y] [--aperture A] (refocus)  [--haze-beta B] [--airlight b,g,r] (haze)\n"
                                  "                    [--paint x,y,label,radius]... [--live N [--paint-at frame:x,y,label,radius]...] [--devices D --batch B [--sequential] [--write-all]] [--png] [--cold]\n"
                                  "       rtdd_harness --convert in.(jpg|png|ppm|pgm) out.(png|ppm|pgm)   (JPEG / 8-bit PNG / PNM -> PNG / PNM, no GPU)\n"); return 0; }
     if (argc == 4 && !std::strcmp(argv[1], "--convert")) {               // file format conversion only (no GPU): JPEG / PNG / PNM -> PNG / PNM
@@ -407,7 +422,21 @@ int main(int argc, const char *argv[]) {
         else if (!std::strcmp(argv[i], "--png")) png = true;                       // DepthMap.png / ArtisticEffect.png like the reference
         else if (!std::strcmp(argv[i], "--paint")) { Paint p{0, 0, 0, 0, -1}; if (std::sscanf(next(), "%d,%d,%d,%d", &p.x, &p.y, &p.label, &p.radius) == 4) job.paints.push_back(p); }
         else if (!std::strcmp(argv[i], "--paint-at")) { Paint p{0, 0, 0, 0, 0}; if (std::sscanf(next(), "%d:%d,%d,%d,%d", &p.frame, &p.x, &p.y, &p.label, &p.radius) == 5) job.live_paints.push_back(p); }
+        else if (!std::strcmp(argv[i], "--focus")) { job.focus_depth = (float)std::atof(next()); job.focus_x = -1; }
+        else if (!std::strcmp(argv[i], "--focus-at")) { if (std::sscanf(next(), "%d,%d", &job.focus_x, &job.focus_y) != 2) { std::printf("--focus-at wants X,Y\n"); return 1; } }
+        else if (!std::strcmp(argv[i], "--aperture")) job.aperture = std::atof(next());
+        else if (!std::strcmp(argv[i], "--haze-beta")) { job.haze_beta = (float)std::atof(next()); job.haze_ex = true; }
+        else if (!std::strcmp(argv[i], "--airlight")) {
+            if (std::sscanf(next(), "%d,%d,%d", &job.air[0], &job.air[1], &job.air[2]) != 3) { std::printf("--airlight wants b,g,r\n"); return 1; }
+            for (int c = 0; c < 3; c++) if (job.air[c] < 0 || job.air[c] > 255) { std::printf("--airlight: each of b,g,r must be 0..255\n"); return 1; }
+            job.haze_ex = true;
+        }
         else if (!std::strcmp(argv[i], "-h")) std::printf("Usage:\n -i input image (JPEG, 8-bit PNG, binary PPM)\n -a annotated image (8-bit PNG, binary PGM)\n");
+    }
+    // a live frame's sticky effect is an effect code without parameters (rtdd_live_submit_ex): the aimed effects are not available there
+    if (live > 0 && (job.effect == "refocus" || (job.effect == "haze" && job.haze_ex))) {
+        std::printf("--live renders the reference's three effects only: --effect refocus and --haze-beta / --airlight are not supported with --live\n");
+        return 1;
     }
     Pnm rgb;
     if (!read_image(in, rgb)) { std::printf("cannot read %s as a binary PPM / PGM, an 8-bit PNG or a JPEG\n", in.c_str()); return 2; }

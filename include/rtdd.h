@@ -272,6 +272,38 @@ int rtdd_simulate_haze(rtdd_ctx *ctx, const uint8_t *original, size_t originalPi
                        const float *depth, size_t depthPitch, uint8_t *artistic, size_t artisticPitch,
                        int rows, int cols);
 
+/* ---- aimed depth effects (extensions; no reference behaviour) --------------------------------
+ * Added after ABI version 230 without a version bump: a host finds them by symbol (dlsym).  The next bump of RTDD_VERSION
+ * should cover them, together with a parameterised live effect (rtdd_live_submit_ex takes an effect code only and knows neither). */
+
+/* Refocus: the defocus effect sharp at a chosen depth instead of at depth 0.
+ *   K = (int)(aperture * sqrtf(rows*rows + cols*cols))   -- double times float, truncated, as GPUDepthEffect.cu:42; aperture 0.025 gives
+ *                                                           the reference's K.  Computed on the host.
+ *   f = focusDepth when focusX < 0; otherwise the depth map's value at (focusX, focusY), READ BY THE KERNEL ON THE DEVICE when it runs
+ *       (no host synchronisation: the call may sit behind an asynchronous estimate, and "focus on what I clicked" follows the map).
+ *   per pixel: dist = fabsf(d - f) in f32, k = (int)(K * dist / 255.0), half-width k/2, the box [y - k/2, y + k/2) x [x - k/2, x + k/2)
+ *   clipped to the image, (uchar)(sum / count) per channel in f32, the original pixel when count == 0 -- GPUDepthEffect.cu:43-70
+ *   with dist in place of depth.
+ * Identity: refocus(orig, d, f, aperture 0.025) == rtdd_simulate_defocus on the map fabsf(d - f), bit for bit; f = 0 on a map with
+ * every d in [0, 255] is rtdd_simulate_defocus itself.  Same paths, options and fall-backs as rtdd_simulate_defocus
+ * (RTDD_OPT_DEFOCUS_PATH / _STRIPS / _SLICE_MB; RTDD_OPT_DEFOCUS_LAST_PATH reports the path).
+ * Refused on the host (RTDD_ERR_INVALID), before any launch: the rules of the three effects (null pointers, pitches, image size, in
+ * place); a negative or non-finite aperture; K > 255 (then every window of a depth map has count <= 254^2 < 2^16 and channel sums
+ * < 2^24: the domains the exact integer sums and quotients are proven on -- the default K is 220 at 8K, and at 1080p the cap allows
+ * about 4.6 x the default blur); a non-finite focusDepth when it is used; a focus pixel outside the image when focusX >= 0. */
+int rtdd_simulate_refocus(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch,
+                          const float *depth, size_t depthPitch, uint8_t *artistic, size_t artisticPitch,
+                          int rows, int cols, double aperture, float focusDepth, int focusX, int focusY);
+
+/* Haze with a density and an airlight colour (GPUDepthEffect.cu:74-93 with its constants as parameters):
+ *   t = exp((float)((double)(-beta * d) / 255.0)) by the same deterministic exp as rtdd_simulate_haze,
+ *   per channel c of B, G, R: out = (uchar)(t * o + (1 - t) * air_c) in f32, fused or not per RTDD_OPT_FP_CONTRACT as in
+ *   rtdd_simulate_haze.  beta = 2 with air (255, 255, 255) gives rtdd_simulate_haze's bytes.
+ * beta must be finite and in [0, 64] (else RTDD_ERR_INVALID); the other rules are the three effects'. */
+int rtdd_simulate_haze_ex(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch,
+                          const float *depth, size_t depthPitch, uint8_t *artistic, size_t artisticPitch,
+                          int rows, int cols, float beta, uint8_t airB, uint8_t airG, uint8_t airR);
+
 /* ---- whole-estimate driver ------------------------------------------------
  * One depth estimate = the loop body of src/main.cpp:232-295, run as a single stream-ordered launch
  * sequence with the gray pyramid, f32 pyrUp and u8 conversion ON THE DEVICE (the reference round-trips

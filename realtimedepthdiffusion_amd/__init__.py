@@ -51,6 +51,7 @@ C_ABI_SYMBOLS = [
     "rtdd_pyrup_depth", "rtdd_depth_to_u8", "rtdd_upload", "rtdd_download",
     "rtdd_live_submit", "rtdd_live_wait", "rtdd_live_pending", "rtdd_host_alloc", "rtdd_host_free",
     "rtdd_pyramid_create_batch", "rtdd_pyramid_select", "rtdd_pyramid_batch", "rtdd_estimate_depth_batch", "rtdd_pyramid_level_info", "rtdd_live_submit_ex",
+    "rtdd_simulate_refocus", "rtdd_simulate_haze_ex",
 ]
 IMG_ORIGINAL, IMG_GRAY, IMG_SCRIBBLE, IMG_EDITED, IMG_DEPTH, IMG_DEPTH_U8, IMG_ARTISTIC = range(7)
 EFFECT_NONE, EFFECT_DEFOCUS, EFFECT_DESATURATION, EFFECT_HAZE = range(4)
@@ -298,6 +299,20 @@ class Context:
     def GPUSimulateHaze(self, originalImage, depthImage, artisticImage, rows, cols):
         o, op = _img(originalImage); d, dp = _img(depthImage); a, ap = _img(artisticImage)
         self._check(lib().rtdd_simulate_haze(self._h, o, op, d, dp, a, ap, C.c_int(rows), C.c_int(cols)))
+
+    # ---- aimed depth effects (extensions, include/rtdd.h)
+    def simulate_refocus(self, originalImage, depthImage, artisticImage, rows, cols, aperture=0.025, focusDepth=0.0, focusX=-1, focusY=-1):
+        """Defocus sharp at depth `focusDepth`, or (focusX >= 0) at the depth map's value at (focusX, focusY), read on the device."""
+        o, op = _img(originalImage); d, dp = _img(depthImage); a, ap = _img(artisticImage)
+        self._check(lib().rtdd_simulate_refocus(self._h, o, op, d, dp, a, ap, C.c_int(rows), C.c_int(cols), C.c_double(aperture),
+                                                C.c_float(focusDepth), C.c_int(focusX), C.c_int(focusY)))
+
+    def simulate_haze_ex(self, originalImage, depthImage, artisticImage, rows, cols, beta=2.0, air=(255, 255, 255)):
+        """Haze with density `beta` and airlight `air` = (b, g, r)."""
+        o, op = _img(originalImage); d, dp = _img(depthImage); a, ap = _img(artisticImage)
+        b, g, r = air
+        self._check(lib().rtdd_simulate_haze_ex(self._h, o, op, d, dp, a, ap, C.c_int(rows), C.c_int(cols), C.c_float(beta),
+                                                C.c_uint8(b), C.c_uint8(g), C.c_uint8(r)))
 
 
     # ---- whole-estimate driver (src/main.cpp:92-155, 232-295)

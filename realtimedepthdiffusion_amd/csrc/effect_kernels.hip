@@ -55,17 +55,23 @@ template <bool CONTRACT>
 __device__ __forceinline__ uint32_t haze_px(float t, float w, float o) {
     return store_u8(CONTRACT ? __builtin_fmaf(t, o, w) : t * o + w);
 }
+// rtdd_simulate_haze_ex: :88 with the density beta a parameter; the airlight replaces the 255 of :89-91 per channel
+__device__ __forceinline__ float haze_t_beta(float d, float beta) {
+    return expf_det((float)((double)(-beta * d) / 255.0));
+}
 
-// MODE 0 = desaturation, 1 = haze.  VEC: 4 pixels per thread with dword accesses (needs 4-byte aligned rows).
+// MODE 0 = desaturation, 1 = haze, 2 = haze with density `beta` and airlight `air` (b | g << 8 | r << 16; modes 0 and 1 ignore both).
+// VEC: 4 pixels per thread with dword accesses (needs 4-byte aligned rows).
 template <int MODE, bool CONTRACT, bool VEC>
 __global__ __launch_bounds__(256) void k_blend(const uint8_t *__restrict__ orig, size_t op, const uint8_t *__restrict__ gray, size_t gp,
                                                const float *__restrict__ depth, size_t dp, uint8_t *__restrict__ art, size_t ap,
-                                               int rows, int cols) {
+                                               int rows, int cols, float beta, uint32_t air) {
     const int y = blockIdx.y * 4 + wave_id();
     if (y >= rows) return;
     const float *drow = (const float *)((const char *)depth + (size_t)y * dp);
     const uint8_t *orow = orig + (size_t)y * op;
     uint8_t *arow = art + (size_t)y * ap;
+    const float airf[3] = {(float)(air & 255), (float)((air >> 8) & 255), (float)((air >> 16) & 255)};
     if (VEC) {
         const int x = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4;
         if (x + 3 < cols) {
@@ -84,11 +90,15 @@ __global__ __launch_bounds__(256) void k_blend(const uint8_t *__restrict__ orig,
                     const float g = (float)((g4 >> (8 * i)) & 255);
 #pragma unroll
                     for (int c = 0; c < 3; c++) rb[3 * i + c] = desat_px<CONTRACT>(dv[i], g, (float)ob[3 * i + c]);
-                } else {
+                } else if (MODE == 1) {
                     const float t = haze_t(dv[i]);
                     const float w = (1 - t) * 255;
 #pragma unroll
                     for (int c = 0; c < 3; c++) rb[3 * i + c] = haze_px<CONTRACT>(t, w, (float)ob[3 * i + c]);
+                } else {
+                    const float t = haze_t_beta(dv[i], beta), u = 1 - t;
+#pragma unroll
+                    for (int c = 0; c < 3; c++) rb[3 * i + c] = haze_px<CONTRACT>(t, u * airf[c], (float)ob[3 * i + c]);
                 }
             }
             uint32_t *a3 = (uint32_t *)(arow + 3 * x);
@@ -102,8 +112,10 @@ __global__ __launch_bounds__(256) void k_blend(const uint8_t *__restrict__ orig,
             const float d = drow[xx];
             if (MODE == 0) { const float g = (float)gray[(size_t)y * gp + xx];
                 for (int c = 0; c < 3; c++) arow[3 * xx + c] = (uint8_t)desat_px<CONTRACT>(d, g, (float)orow[3 * xx + c]); }
-            else { const float t = haze_t(d); const float w = (1 - t) * 255;
+            else if (MODE == 1) { const float t = haze_t(d); const float w = (1 - t) * 255;
                 for (int c = 0; c < 3; c++) arow[3 * xx + c] = (uint8_t)haze_px<CONTRACT>(t, w, (float)orow[3 * xx + c]); }
+            else { const float t = haze_t_beta(d, beta), u = 1 - t;
+                for (int c = 0; c < 3; c++) arow[3 * xx + c] = (uint8_t)haze_px<CONTRACT>(t, u * airf[c], (float)orow[3 * xx + c]); }
         }
     } else {
         const int x = blockIdx.x * 64 + (threadIdx.x & 63);
@@ -112,9 +124,12 @@ __global__ __launch_bounds__(256) void k_blend(const uint8_t *__restrict__ orig,
         if (MODE == 0) { const float g = (float)gray[(size_t)y * gp + x];
 #pragma unroll
             for (int c = 0; c < 3; c++) arow[3 * x + c] = (uint8_t)desat_px<CONTRACT>(d, g, (float)orow[3 * x + c]); }
-        else { const float t = haze_t(d); const float w = (1 - t) * 255;
+        else if (MODE == 1) { const float t = haze_t(d); const float w = (1 - t) * 255;
 #pragma unroll
             for (int c = 0; c < 3; c++) arow[3 * x + c] = (uint8_t)haze_px<CONTRACT>(t, w, (float)orow[3 * x + c]); }
+        else { const float t = haze_t_beta(d, beta), u = 1 - t;
+#pragma unroll
+            for (int c = 0; c < 3; c++) arow[3 * x + c] = (uint8_t)haze_px<CONTRACT>(t, u * airf[c], (float)orow[3 * x + c]); }
     }
 }
 
@@ -379,12 +394,19 @@ __device__ __forceinline__ u64 tab_load(__amdgpu_buffer_rsrc_t rsrc, uint32_t by
     return ((u64)v.y << 32) | v.x;
 }
 
+// FOCUS (rtdd_simulate_refocus): the window is sized by |depth - f| instead of depth, f = *focus_px (one uniform load per wave: the
+// depth map's value at the focus pixel, read when the kernel runs) or, focus_px == nullptr, the value `focus`.  Nothing else changes.
+__device__ __forceinline__ float focal_depth(float focus, const float *__restrict__ focus_px) {
+    return focus_px ? *focus_px : focus;
+}
+
 constexpr int kLk2Rows = 2;                                         // rows per wave
-template <bool VEC>
+template <bool VEC, bool FOCUS>
 __global__ __launch_bounds__(256) void k_defocus(const uint8_t *__restrict__ orig, size_t op, const float *__restrict__ depth, size_t dp,
                                                   const u64 *__restrict__ Tpad, int tpitch, uint8_t *__restrict__ art, size_t ap,
                                                   int rows, int cols, int kernelSize, int gx, int ntiles, int xcd_tiles,
-                                                  int row0, int row1, int trow0, int trows, int *__restrict__ nonlocal_word, int strip_w) {
+                                                  int row0, int row1, int trow0, int trows, int *__restrict__ nonlocal_word, int strip_w,
+                                                  float focus, const float *__restrict__ focus_px) {
     // Round 6, BANDED tables (launch_defocus): this launch writes output rows [row0, row1) and the table holds image rows
     // [trow0, trow0 + trows) with its origin at row trow0 -- rectangle sums are differences, so any origin above the window serves.  The
     // whole image in one launch: row0 = trow0 = 0, row1 = trows = rows.
@@ -412,6 +434,11 @@ __global__ __launch_bounds__(256) void k_defocus(const uint8_t *__restrict__ ori
     float d[kLk2Rows];
 #pragma unroll
     for (int i = 0; i < kLk2Rows; i++) d[i] = ((const float *)((const char *)depth + (size_t)min(yw + i, rows - 1) * dp))[xc];
+    if (FOCUS) {
+        const float f = focal_depth(focus, focus_px);
+#pragma unroll
+        for (int i = 0; i < kLk2Rows; i++) d[i] = fabsf(d[i] - f);
+    }
     uint32_t cnt[kLk2Rows];
     u64 C[kLk2Rows][4];
     int ya[kLk2Rows], yb[kLk2Rows], xa[kLk2Rows], xb[kLk2Rows];
@@ -573,10 +600,11 @@ __device__ __forceinline__ u64 half_incl_scan64(u64 v) {
     return t;
 }
 
-template <bool VEC, int kDtH>
+template <bool VEC, int kDtH, bool FOCUS>
 __global__ __launch_bounds__(256, 2) void k_defocus_tile(const uint8_t *__restrict__ orig, size_t op, const float *__restrict__ depth, size_t dp,
                                                          uint8_t *__restrict__ art, size_t ap, int rows, int cols, int kernelSize, int hm,
-                                                         int gx, int ntiles, int xcd_tiles, int *__restrict__ nonlocal_word) {
+                                                         int gx, int ntiles, int xcd_tiles, int *__restrict__ nonlocal_word,
+                                                         float focus, const float *__restrict__ focus_px) {
     constexpr int kDtRH = kDtH + 2 * kDtHM, kDtRowsPer = (kDtRH + kDtWorkers - 1) / kDtWorkers;
     __shared__ u64 S[kDtRH][kDtRW];                                 // the region's summed-area table, S[r - R0][c - C0]: <= 79 360 B, two workgroups per CU
     const int p = blockIdx.x;
@@ -620,10 +648,12 @@ __global__ __launch_bounds__(256, 2) void k_defocus_tile(const uint8_t *__restri
     constexpr int NR = kDtH / 4;                                    // output rows per wave
     float d[NR];
     uint32_t opx[NR];
+    const float f = FOCUS ? focal_depth(focus, focus_px) : 0.0f;   // (FOCUS: k_defocus; |d - f| <= 255 while both are depths: the region still holds)
 #pragma unroll
     for (int i = 0; i < NR; i++) {
         const int y = min(ty0 + wv * NR + i, rows - 1);
         d[i] = ((const float *)((const char *)depth + (size_t)y * dp))[xc];
+        if (FOCUS) d[i] = fabsf(d[i] - f);
         const uint8_t *orow = orig + (size_t)y * op;
         if (whole) {
             const uint32_t L = j < 3 ? ((const uint32_t *)(orow + 3 * (size_t)tx0))[3 * (lane >> 2) + j] : 0u;
@@ -755,17 +785,17 @@ static inline dim3 grid64x4(int rows, int cols) { return dim3((cols + 63) / 64, 
 
 template <int MODE>
 static int launch_blend(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const uint8_t *gray, size_t gp, const float *depth, size_t dp,
-                        uint8_t *art, size_t ap, int rows, int cols) {
+                        uint8_t *art, size_t ap, int rows, int cols, float beta = 2.0f, uint32_t air = 0xFFFFFFu) {
     const bool aligned = ((uintptr_t)orig % 4 == 0) && ((uintptr_t)art % 4 == 0) && op % 4 == 0 && ap % 4 == 0 &&
-                         ((uintptr_t)depth % 16 == 0) && dp % 16 == 0 && (MODE == 1 || (((uintptr_t)gray % 4 == 0) && gp % 4 == 0));
+                         ((uintptr_t)depth % 16 == 0) && dp % 16 == 0 && (MODE != 0 || (((uintptr_t)gray % 4 == 0) && gp % 4 == 0));
     const bool c = ctx->opt.fp_contract != 0;
     if (aligned) {
         const dim3 grid((cols + 255) / 256, (rows + 3) / 4);
-        if (c) hipLaunchKernelGGL((k_blend<MODE, true, true>), grid, dim3(256), 0, ctx->stream, orig, op, gray, gp, depth, dp, art, ap, rows, cols);
-        else hipLaunchKernelGGL((k_blend<MODE, false, true>), grid, dim3(256), 0, ctx->stream, orig, op, gray, gp, depth, dp, art, ap, rows, cols);
+        if (c) hipLaunchKernelGGL((k_blend<MODE, true, true>), grid, dim3(256), 0, ctx->stream, orig, op, gray, gp, depth, dp, art, ap, rows, cols, beta, air);
+        else hipLaunchKernelGGL((k_blend<MODE, false, true>), grid, dim3(256), 0, ctx->stream, orig, op, gray, gp, depth, dp, art, ap, rows, cols, beta, air);
     } else {
-        if (c) hipLaunchKernelGGL((k_blend<MODE, true, false>), grid64x4(rows, cols), dim3(256), 0, ctx->stream, orig, op, gray, gp, depth, dp, art, ap, rows, cols);
-        else hipLaunchKernelGGL((k_blend<MODE, false, false>), grid64x4(rows, cols), dim3(256), 0, ctx->stream, orig, op, gray, gp, depth, dp, art, ap, rows, cols);
+        if (c) hipLaunchKernelGGL((k_blend<MODE, true, false>), grid64x4(rows, cols), dim3(256), 0, ctx->stream, orig, op, gray, gp, depth, dp, art, ap, rows, cols, beta, air);
+        else hipLaunchKernelGGL((k_blend<MODE, false, false>), grid64x4(rows, cols), dim3(256), 0, ctx->stream, orig, op, gray, gp, depth, dp, art, ap, rows, cols, beta, air);
     }
     RTDD_LAUNCH_CHECK(ctx, "k_blend");
     return RTDD_OK;
@@ -780,8 +810,18 @@ int launch_haze(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const float *dept
     return launch_blend<1>(ctx, orig, op, nullptr, 0, depth, dp, art, ap, rows, cols);
 }
 
-int launch_defocus(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const float *depth, size_t dp, uint8_t *art, size_t ap, int rows, int cols) {
-    const int kernelSize = 0.025 * sqrtf(rows * rows + cols * cols);    // :42, evaluated once on the host (sqrtf is correctly rounded on both)
+int launch_haze_ex(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const float *depth, size_t dp, uint8_t *art, size_t ap, int rows, int cols,
+                   float beta, uint32_t air) {
+    return launch_blend<2>(ctx, orig, op, nullptr, 0, depth, dp, art, ap, rows, cols, beta, air);
+}
+
+// The body of rtdd_simulate_defocus (FOCUS false) and rtdd_simulate_refocus (FOCUS true: the kernels size each window by
+// |depth - f|, f = *focus_px or `focus`).  kernelSize <= 255 for a refocus (api.cpp): every window of a depth map stays within the
+// domains the packed fields and the quotients are proven on, and the reach kernelSize / 2 that the tile region and the slices are sized
+// for still bounds it (|d - f| <= 255 while both lie in [0, 255]; anything else takes the same fall-backs as an out-of-range depth).
+template <bool FOCUS>
+static int defocus_body(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const float *depth, size_t dp, uint8_t *art, size_t ap, int rows, int cols,
+                        int kernelSize, float focus, const float *focus_px) {
     // small nominal windows (up to ~1080p): one launch, per-tile tables in LDS (k_defocus_tile).  RTDD_OPT_DEFOCUS_PATH: 0 automatic, 1 the
     // global table always, 2 the tile kernel wherever its region fits.
     if (ctx->opt.defocus_path != 1 && !(ctx->opt.defocus_path == 0 && ctx->defocus_table_sticky) && kernelSize / 2 <= kDtHM && (size_t)rows * cols < (1ull << 32) / 255) {
@@ -791,7 +831,7 @@ int launch_defocus(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const float *d
         const int th = low ? 16 : 24, gy = (rows + th - 1) / th, ntiles = gx * gy;
         const int xcd_tiles = ntiles >= 64 ? (ntiles + 7) / 8 : 0;
         const dim3 g(xcd_tiles > 0 ? 8 * xcd_tiles : ntiles);
-#define RTDD_DT_LAUNCH(V, H) hipLaunchKernelGGL((k_defocus_tile<V, H>), g, dim3(256), 0, ctx->stream, orig, op, depth, dp, art, ap, rows, cols, kernelSize, kernelSize / 2, gx, ntiles, xcd_tiles, ctx->sync_words + kSyncNonLocal)
+#define RTDD_DT_LAUNCH(V, H) hipLaunchKernelGGL((k_defocus_tile<V, H, FOCUS>), g, dim3(256), 0, ctx->stream, orig, op, depth, dp, art, ap, rows, cols, kernelSize, kernelSize / 2, gx, ntiles, xcd_tiles, ctx->sync_words + kSyncNonLocal, focus, focus_px)
         if (vio) { if (low) RTDD_DT_LAUNCH(true, 16); else RTDD_DT_LAUNCH(true, 24); }
         else { if (low) RTDD_DT_LAUNCH(false, 16); else RTDD_DT_LAUNCH(false, 24); }
 #undef RTDD_DT_LAUNCH
@@ -877,14 +917,26 @@ int launch_defocus(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const float *d
         const int strip_w = strips ? (gx2 + 7) / 8 : 0;
         const dim3 g5(strip_w > 0 ? 8 * strip_w * gy2 : xt2 > 0 ? 8 * xt2 : nt2);
         int *nlw = nslices > 1 ? ctx->sync_words + kSyncNonLocal : nullptr;
-        if (vout) hipLaunchKernelGGL(k_defocus<true>, g5, dim3(256), 0, ctx->stream, orig, op, depth, dp, Tpad, tpitch, art, ap, rows, cols, kernelSize, gx2, nt2, xt2, row0, row1, trow0, trows, nlw, strip_w);
-        else hipLaunchKernelGGL(k_defocus<false>, g5, dim3(256), 0, ctx->stream, orig, op, depth, dp, Tpad, tpitch, art, ap, rows, cols, kernelSize, gx2, nt2, xt2, row0, row1, trow0, trows, nlw, strip_w);
+        if (vout) hipLaunchKernelGGL((k_defocus<true, FOCUS>), g5, dim3(256), 0, ctx->stream, orig, op, depth, dp, Tpad, tpitch, art, ap, rows, cols, kernelSize, gx2, nt2, xt2, row0, row1, trow0, trows, nlw, strip_w, focus, focus_px);
+        else hipLaunchKernelGGL((k_defocus<false, FOCUS>), g5, dim3(256), 0, ctx->stream, orig, op, depth, dp, Tpad, tpitch, art, ap, rows, cols, kernelSize, gx2, nt2, xt2, row0, row1, trow0, trows, nlw, strip_w, focus, focus_px);
     }
     if (nslices > 1) note_status_writer(ctx);                           // (kSyncNonLocal: a window beyond a slice -> the whole-image table from the next synchronisation on)
     RTDD_LAUNCH_CHECK(ctx, "k_defocus");
     ctx->defocus_last_path = 1;
     ctx->defocus_last_slices = nslices;
     return RTDD_OK;
+}
+
+int launch_defocus(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const float *depth, size_t dp, uint8_t *art, size_t ap, int rows, int cols) {
+    const int kernelSize = 0.025 * sqrtf(rows * rows + cols * cols);    // :42, evaluated once on the host (sqrtf is correctly rounded on both)
+    return defocus_body<false>(ctx, orig, op, depth, dp, art, ap, rows, cols, kernelSize, 0.0f, nullptr);
+}
+
+int launch_refocus(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const float *depth, size_t dp, uint8_t *art, size_t ap, int rows, int cols,
+                   int kernelSize, float focusDepth, int focusX, int focusY) {
+    // the pixel form: the kernels read the focal depth from the map when they run (no host synchronisation; a heal's replay reads it again)
+    const float *focus_px = focusX >= 0 ? (const float *)((const char *)depth + (size_t)focusY * dp) + focusX : nullptr;
+    return defocus_body<true>(ctx, orig, op, depth, dp, art, ap, rows, cols, kernelSize, focusDepth, focus_px);
 }
 
 }  // namespace rtdd

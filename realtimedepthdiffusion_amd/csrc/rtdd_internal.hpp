@@ -110,7 +110,7 @@ struct Options {
 // needs to run it again when a persistent launch gave up (api.cpp, "self-healing").  A solve is one sequence number (handed to the
 // kernel that publishes its result: k_finish, or k_pyrup_inject inside an estimate); an estimate is one per pyramid level.
 struct PendingOp {
-    enum Kind { kSolve = 0, kEstimate = 1, kDefocus = 2, kDesaturate = 3, kHaze = 4 } kind = kSolve;
+    enum Kind { kSolve = 0, kEstimate = 1, kDefocus = 2, kDesaturate = 3, kHaze = 4, kRefocus = 5, kHazeEx = 6 } kind = kSolve;
     Options opt;                          // the options in force when the call was made
     // kSolve: the arguments of rtdd_solve_ex (+ the optional u8 copy of the result, rtdd_refine_depth)
     float *depth = nullptr; size_t depthPitch = 0;
@@ -125,10 +125,14 @@ struct PendingOp {
     int batch_first = 0, batch_n = 1;     // the images of the context's batched pyramid the estimate covers
     LiveTargets live;                     // a live frame: its annotation pair, its map's second target, its effect (scribble == nullptr: not one)
     unsigned long long id = 0;            // position in the context's call order (live mode drops the confirmed prefix of the log)
-    // kDefocus / kDesaturate / kHaze: a depth effect queued BEHIND an unconfirmed solve (it may have read that solve's input instead of
-    // its result); `depth` / `depthPitch` / `gray` / `grayPitch` / `rows` / `cols` above, and:
+    // kDefocus / kDesaturate / kHaze / kRefocus / kHazeEx: a depth effect queued BEHIND an unconfirmed solve (it may have read that solve's
+    // input instead of its result); `depth` / `depthPitch` / `gray` / `grayPitch` / `rows` / `cols` above, and:
     const uint8_t *original = nullptr; size_t originalPitch = 0;
     uint8_t *artistic = nullptr; size_t artisticPitch = 0;
+    // kRefocus: the window scale and the focus (focusX >= 0: the map's pixel, read again by the replay); kHazeEx: density and airlight
+    int kernelSize = 0, focusX = -1, focusY = -1;
+    float focusDepth = 0.0f, beta = 0.0f;
+    uint32_t air = 0;
 };
 constexpr int kRestartSolve = -1000;      // internal status: the pending calls were healed inside a solve's residual check; that solve starts over
 constexpr size_t kMaxPendingOps = 4096;
@@ -297,6 +301,11 @@ int launch_desaturate(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const uint8
                       uint8_t *art, size_t ap, int rows, int cols);
 int launch_haze(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const float *depth, size_t dp, uint8_t *art, size_t ap, int rows, int cols);
 int launch_defocus(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const float *depth, size_t dp, uint8_t *art, size_t ap, int rows, int cols);
+// rtdd_simulate_refocus / rtdd_simulate_haze_ex, arguments checked (api.cpp): kernelSize <= 255; air = b | g << 8 | r << 16
+int launch_refocus(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const float *depth, size_t dp, uint8_t *art, size_t ap, int rows, int cols,
+                   int kernelSize, float focusDepth, int focusX, int focusY);
+int launch_haze_ex(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const float *depth, size_t dp, uint8_t *art, size_t ap, int rows, int cols,
+                   float beta, uint32_t air);
 
 // ---- cascade.hip -------------------------------------------------------------------------------
 int launch_bgr2gray(rtdd_ctx *ctx, const uint8_t *bgr, size_t bp, uint8_t *gray, size_t gp, int rows, int cols);
