@@ -74,24 +74,14 @@ static int replay(rtdd_ctx *ctx, const PendingOp &op, int failed_seq) {
     ctx->opt.persistent = 0;
     ctx->opt.debug_force_status = op.opt.debug_force_status == 3 ? 1 : 0;      // (3: the testing aid that makes the REPLAY fail as well)
     int rc = RTDD_OK;
-    if (op.kind == PendingOp::kSolve) {
-        rc = solve_with(ctx, op.depth, op.depthPitch, op.scribble, op.scribblePitch, op.gray, op.grayPitch, op.rows, op.cols, op.level,
-                        &op.params, nullptr, op.targets, nullptr);
-    } else if (op.kind == PendingOp::kEstimate) {
-        rc = estimate_replay(ctx, op, failed_seq);
-    } else if (op.kind == PendingOp::kDefocus) {
-        rc = launch_defocus(ctx, op.original, op.originalPitch, op.depth, op.depthPitch, op.artistic, op.artisticPitch, op.rows, op.cols);
-    } else if (op.kind == PendingOp::kRefocus) {
-        rc = launch_refocus(ctx, op.original, op.originalPitch, op.depth, op.depthPitch, op.artistic, op.artisticPitch, op.rows, op.cols,
-                            op.kernelSize, op.focusDepth, op.focusX, op.focusY);
-    } else if (op.kind == PendingOp::kHazeEx) {
-        rc = launch_haze_ex(ctx, op.original, op.originalPitch, op.depth, op.depthPitch, op.artistic, op.artisticPitch, op.rows, op.cols,
-                            op.beta, op.air);
-    } else if (op.kind == PendingOp::kDesaturate) {
-        rc = launch_desaturate(ctx, op.original, op.originalPitch, op.gray, op.grayPitch, op.depth, op.depthPitch, op.artistic,
-            op.artisticPitch, op.rows, op.cols);
-    } else {
-        rc = launch_haze(ctx, op.original, op.originalPitch, op.depth, op.depthPitch, op.artistic, op.artisticPitch, op.rows, op.cols);
+    switch (op.kind) {
+        case PendingOp::kSolve:
+            rc = solve_with(ctx, op.depth, op.depthPitch, op.scribble, op.scribblePitch, op.gray, op.grayPitch, op.rows, op.cols, op.level,
+                            &op.params, nullptr, op.targets, nullptr);
+            break;
+        case PendingOp::kEstimate: rc = estimate_replay(ctx, op, failed_seq); break;
+        case PendingOp::kEffect: rc = launch_effect(ctx, op.effect); break;
+        default: rc = fail(ctx, RTDD_ERR_TIMEOUT, "unknown call in the pending log; the results since the last synchronisation are invalid");
     }
     ctx->opt = now;
     return rc;
@@ -99,20 +89,13 @@ static int replay(rtdd_ctx *ctx, const PendingOp &op, int failed_seq) {
 
 // A depth effect queued behind solves that no synchronising call has confirmed yet is logged with them: should one of those solves turn
 // out to have timed out, the effect ran on its INPUT and is run again behind the replayed solve.  (Nothing unconfirmed: nothing to log.)
-// Returns the logged entry (nullptr: nothing logged), so that a call with parameters can add them.
-static PendingOp *log_effect(rtdd_ctx *ctx, PendingOp::Kind kind, const uint8_t *original, size_t originalPitch, const uint8_t *gray,
-    size_t grayPitch,
-                       const float *depth, size_t depthPitch, uint8_t *artistic, size_t artisticPitch, int rows, int cols) {
-    if (ctx->healing || ctx->pending.empty()) return nullptr;
+static void log_effect(rtdd_ctx *ctx, const Effect &e) {
+    if (ctx->healing || ctx->pending.empty()) return;
     prune_confirmed(ctx);
-    if (ctx->pending.empty() || ctx->pending.size() >= kMaxPendingOps) return nullptr;
+    if (ctx->pending.empty() || ctx->pending.size() >= kMaxPendingOps) return;
     PendingOp op;
-    op.kind = kind; op.opt = ctx->opt; op.id = ++ctx->op_counter;
-    op.original = original; op.originalPitch = originalPitch; op.gray = gray; op.grayPitch = grayPitch;
-    op.depth = const_cast<float *>(depth); op.depthPitch = depthPitch; op.artistic = artistic; op.artisticPitch = artisticPitch;
-    op.rows = rows; op.cols = cols;
+    op.kind = PendingOp::kEffect; op.opt = ctx->opt; op.id = ++ctx->op_counter; op.effect = e;
     ctx->pending.push_back(op);
-    return &ctx->pending.back();
 }
 
 // Sequence number of the kernel that publishes the LAST result of a logged call (0: the call publishes no solve).
@@ -887,17 +870,21 @@ static int check_effect(rtdd_ctx *ctx, const void *a, const void *b, const void 
     return RTDD_OK;
 }
 
+// What every rtdd_simulate_* does once its arguments are checked: launch, and log the effect if it sits behind unconfirmed solves.
+static int simulate(rtdd_ctx *ctx, const Effect &e) {
+    DeviceGuard g(ctx->device);
+    const int rc = launch_effect(ctx, e);
+    if (rc == RTDD_OK) log_effect(ctx, e);
+    return rc;
+}
+
 int rtdd_simulate_defocus(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
                           uint8_t *artistic, size_t artisticPitch, int rows, int cols) {
     if (!ctx) return RTDD_ERR_INVALID;
     int rc = check_effect(ctx, original, depth, artistic, originalPitch, depthPitch, artisticPitch, rows, cols);
     if (rc != RTDD_OK || rows == 0 || cols == 0) return rc;
     REQUIRE(ctx, original != artistic, "defocus cannot run in place");
-    DeviceGuard g(ctx->device);
-    rc = launch_defocus(ctx, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols);
-    if (rc == RTDD_OK) log_effect(ctx, PendingOp::kDefocus, original, originalPitch, nullptr, 0, depth, depthPitch, artistic, artisticPitch,
-        rows, cols);
-    return rc;
+    return simulate(ctx, {RTDD_EFFECT_DEFOCUS, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols});
 }
 
 int rtdd_simulate_desaturation(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const uint8_t *gray, size_t grayPitch,
@@ -906,11 +893,8 @@ int rtdd_simulate_desaturation(rtdd_ctx *ctx, const uint8_t *original, size_t or
     int rc = check_effect(ctx, original, depth, artistic, originalPitch, depthPitch, artisticPitch, rows, cols);
     if (rc != RTDD_OK || rows == 0 || cols == 0) return rc;
     REQUIRE(ctx, gray && grayPitch >= (size_t)cols, "bad gray image");
-    DeviceGuard g(ctx->device);
-    rc = launch_desaturate(ctx, original, originalPitch, gray, grayPitch, depth, depthPitch, artistic, artisticPitch, rows, cols);
-    if (rc == RTDD_OK) log_effect(ctx, PendingOp::kDesaturate, original, originalPitch, gray, grayPitch, depth, depthPitch, artistic,
-        artisticPitch, rows, cols);
-    return rc;
+    return simulate(ctx, {RTDD_EFFECT_DESATURATION, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols, gray,
+                          grayPitch});
 }
 
 int rtdd_simulate_haze(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
@@ -918,11 +902,7 @@ int rtdd_simulate_haze(rtdd_ctx *ctx, const uint8_t *original, size_t originalPi
     if (!ctx) return RTDD_ERR_INVALID;
     int rc = check_effect(ctx, original, depth, artistic, originalPitch, depthPitch, artisticPitch, rows, cols);
     if (rc != RTDD_OK || rows == 0 || cols == 0) return rc;
-    DeviceGuard g(ctx->device);
-    rc = launch_haze(ctx, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols);
-    if (rc == RTDD_OK) log_effect(ctx, PendingOp::kHaze, original, originalPitch, nullptr, 0, depth, depthPitch, artistic, artisticPitch,
-        rows, cols);
-    return rc;
+    return simulate(ctx, {RTDD_EFFECT_HAZE, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols});
 }
 
 int rtdd_simulate_refocus(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
@@ -931,21 +911,15 @@ int rtdd_simulate_refocus(rtdd_ctx *ctx, const uint8_t *original, size_t origina
     int rc = check_effect(ctx, original, depth, artistic, originalPitch, depthPitch, artisticPitch, rows, cols);
     if (rc != RTDD_OK) return rc;
     REQUIRE(ctx, std::isfinite(aperture) && aperture >= 0.0, "aperture must be finite and >= 0");
-    const double k = aperture * sqrtf(rows * rows + cols * cols);     // (double * float, as the reference's :42)
-    REQUIRE(ctx, k < 256.0, "aperture too large: the window scale (int)(aperture * diagonal) must be <= 255");
+    const int kernelSize = window_scale(aperture, rows, cols);
+    REQUIRE(ctx, kernelSize <= 255, "aperture too large: the window scale (int)(aperture * diagonal) must be <= 255");
     if (focusX < 0) REQUIRE(ctx, std::isfinite(focusDepth), "focusDepth must be finite");
     else REQUIRE(ctx, focusX < cols && focusY >= 0 && focusY < rows, "focus pixel outside the image");
     if (rows == 0 || cols == 0) return RTDD_OK;
     REQUIRE(ctx, original != artistic, "refocus cannot run in place");
-    DeviceGuard g(ctx->device);
-    const int kernelSize = (int)k;
-    rc = launch_refocus(ctx, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols, kernelSize, focusDepth, focusX, focusY);
-    if (rc == RTDD_OK) {
-        if (PendingOp *op = log_effect(ctx, PendingOp::kRefocus, original, originalPitch, nullptr, 0, depth, depthPitch, artistic, artisticPitch, rows, cols)) {
-            op->kernelSize = kernelSize; op->focusDepth = focusDepth; op->focusX = focusX; op->focusY = focusY;
-        }
-    }
-    return rc;
+    Effect e{Effect::kRefocus, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols};
+    e.kernelSize = kernelSize; e.focusDepth = focusDepth; e.focusX = focusX; e.focusY = focusY;
+    return simulate(ctx, e);
 }
 
 int rtdd_simulate_haze_ex(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
@@ -955,15 +929,9 @@ int rtdd_simulate_haze_ex(rtdd_ctx *ctx, const uint8_t *original, size_t origina
     if (rc != RTDD_OK) return rc;
     REQUIRE(ctx, std::isfinite(beta) && beta >= 0.0f && beta <= 64.0f, "beta must be finite and in [0, 64]");
     if (rows == 0 || cols == 0) return RTDD_OK;
-    DeviceGuard g(ctx->device);
-    const uint32_t air = (uint32_t)airB | ((uint32_t)airG << 8) | ((uint32_t)airR << 16);
-    rc = launch_haze_ex(ctx, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols, beta, air);
-    if (rc == RTDD_OK) {
-        if (PendingOp *op = log_effect(ctx, PendingOp::kHazeEx, original, originalPitch, nullptr, 0, depth, depthPitch, artistic, artisticPitch, rows, cols)) {
-            op->beta = beta; op->air = air;
-        }
-    }
-    return rc;
+    Effect e{Effect::kHazeEx, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols};
+    e.beta = beta; e.air = (uint32_t)airB | ((uint32_t)airG << 8) | ((uint32_t)airR << 16);
+    return simulate(ctx, e);
 }
 
 }  // extern "C"

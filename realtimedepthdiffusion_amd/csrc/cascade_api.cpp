@@ -742,20 +742,9 @@ int live_effect(rtdd_ctx *ctx, const LiveTargets &live) {
     if (!p) return fail(ctx, RTDD_ERR_STATE, "the pyramid is gone");
     if (p->rows <= 0 || p->cols <= 0 || !live.artistic) return RTDD_OK;
     DeviceGuard g(ctx->device);
-    const uint8_t *orig = (const uint8_t *)p->original.ptr; const float *depth = (const float *)p->depth[0].ptr;
-    switch (live.effect) {
-        case RTDD_EFFECT_DEFOCUS:
-            return launch_defocus(ctx, orig, p->original.pitch, depth, p->depth[0].pitch, live.artistic, live.artistic_pitch, p->rows,
-                p->cols);
-        case RTDD_EFFECT_DESATURATION:
-            return launch_desaturate(ctx, orig, p->original.pitch, (const uint8_t *)p->gray[0].ptr, p->gray[0].pitch, depth,
-                p->depth[0].pitch,
-                                     live.artistic, live.artistic_pitch, p->rows, p->cols);
-        case RTDD_EFFECT_HAZE:
-            return launch_haze(ctx, orig, p->original.pitch, depth, p->depth[0].pitch, live.artistic, live.artistic_pitch, p->rows,
-                p->cols);
-        default: return RTDD_OK;
-    }
+    return launch_effect(ctx, {live.effect, (const uint8_t *)p->original.ptr, p->original.pitch, (const float *)p->depth[0].ptr,
+                               p->depth[0].pitch, live.artistic, live.artistic_pitch, p->rows, p->cols, (const uint8_t *)p->gray[0].ptr,
+                               p->gray[0].pitch});
 }
 
 int estimate_replay(rtdd_ctx *ctx, const PendingOp &op, int failed_seq) {

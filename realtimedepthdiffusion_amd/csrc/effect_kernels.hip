@@ -407,7 +407,7 @@ __global__ __launch_bounds__(256) void k_defocus(const uint8_t *__restrict__ ori
                                                   int rows, int cols, int kernelSize, int gx, int ntiles, int xcd_tiles,
                                                   int row0, int row1, int trow0, int trows, int *__restrict__ nonlocal_word, int strip_w,
                                                   float focus, const float *__restrict__ focus_px) {
-    // Round 6, BANDED tables (launch_defocus): this launch writes output rows [row0, row1) and the table holds image rows
+    // Round 6, BANDED tables (defocus_body): this launch writes output rows [row0, row1) and the table holds image rows
     // [trow0, trow0 + trows) with its origin at row trow0 -- rectangle sums are differences, so any origin above the window serves.  The
     // whole image in one launch: row0 = trow0 = 0, row1 = trows = rows.
     // Which tile: workgroup p is dispatched to XCD p % 8.  strip_w == 0: each XCD takes a contiguous band of tile ROWS.  strip_w > 0
@@ -449,7 +449,7 @@ __global__ __launch_bounds__(256) void k_defocus(const uint8_t *__restrict__ ori
         ya[i] = max(y - h, 0); yb[i] = min(y + h, rows);
         xa[i] = max(xc - h, 0); xb[i] = min(xc + h, cols);
         // T(ya - 1, xa - 1) = T'[ya][xa + 3], ...: byte offsets row * pitch8 + 8 * col + 24 (rows counted from the table's origin row)
-        const uint32_t ra = (uint32_t)__umul24(ya[i] - trow0, pitch8), rb = (uint32_t)__umul24(yb[i] - trow0, pitch8);       // both factors < 2^24 and (rows + 1) * pitch8 < 2^32: launch_defocus refuses any larger table
+        const uint32_t ra = (uint32_t)__umul24(ya[i] - trow0, pitch8), rb = (uint32_t)__umul24(yb[i] - trow0, pitch8);       // both factors < 2^24 and (rows + 1) * pitch8 < 2^32: defocus_body refuses any larger table
         const uint32_t ca = 8u * (uint32_t)xa[i] + 24u, cb = 8u * (uint32_t)xb[i] + 24u;
         C[i][0] = tab_load(rsrc, ra + ca); C[i][1] = tab_load(rsrc, ra + cb); C[i][2] = tab_load(rsrc, rb + ca); C[i][3] = tab_load(rsrc, rb + cb);
         const int wd = xb[i] - xa[i], ht = yb[i] - ya[i];
@@ -801,20 +801,6 @@ static int launch_blend(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const uin
     return RTDD_OK;
 }
 
-int launch_desaturate(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const uint8_t *gray, size_t gp, const float *depth, size_t dp,
-                      uint8_t *art, size_t ap, int rows, int cols) {
-    return launch_blend<0>(ctx, orig, op, gray, gp, depth, dp, art, ap, rows, cols);
-}
-
-int launch_haze(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const float *depth, size_t dp, uint8_t *art, size_t ap, int rows, int cols) {
-    return launch_blend<1>(ctx, orig, op, nullptr, 0, depth, dp, art, ap, rows, cols);
-}
-
-int launch_haze_ex(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const float *depth, size_t dp, uint8_t *art, size_t ap, int rows, int cols,
-                   float beta, uint32_t air) {
-    return launch_blend<2>(ctx, orig, op, nullptr, 0, depth, dp, art, ap, rows, cols, beta, air);
-}
-
 // The body of rtdd_simulate_defocus (FOCUS false) and rtdd_simulate_refocus (FOCUS true: the kernels size each window by
 // |depth - f|, f = *focus_px or `focus`).  kernelSize <= 255 for a refocus (api.cpp): every window of a depth map stays within the
 // domains the packed fields and the quotients are proven on, and the reach kernelSize / 2 that the tile region and the slices are sized
@@ -857,7 +843,7 @@ static int defocus_body(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const flo
     // smooth, 522 -> 399 with a real depth map, 2888 -> 1342 random.  The slices stay as an option: they are what lets an image whose
     // whole table would pass 4 GiB (rows x cols > 2^29) be processed at all.
     const int reach = kernelSize / 2;
-    const size_t slice_budget = (size_t)ctx->opt.defocus_slice_mb << 20;          // RTDD_OPT_DEFOCUS_SLICE_MB (default 64; 0: never band)
+    const size_t slice_budget = (size_t)ctx->opt.defocus_slice_mb << 20;          // RTDD_OPT_DEFOCUS_SLICE_MB (default 0: never band)
     const size_t row_bytes = (size_t)tpitch * sizeof(u64);
     int slice_rows = rows;                                              // output rows per slice
     const bool want_bands = slice_budget > 0 && !ctx->defocus_band_sticky && ctx->opt.defocus_path != 1 &&
@@ -927,16 +913,28 @@ static int defocus_body(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const flo
     return RTDD_OK;
 }
 
-int launch_defocus(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const float *depth, size_t dp, uint8_t *art, size_t ap, int rows, int cols) {
-    const int kernelSize = 0.025 * sqrtf(rows * rows + cols * cols);    // :42, evaluated once on the host (sqrtf is correctly rounded on both)
-    return defocus_body<false>(ctx, orig, op, depth, dp, art, ap, rows, cols, kernelSize, 0.0f, nullptr);
-}
-
-int launch_refocus(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const float *depth, size_t dp, uint8_t *art, size_t ap, int rows, int cols,
-                   int kernelSize, float focusDepth, int focusX, int focusY) {
-    // the pixel form: the kernels read the focal depth from the map when they run (no host synchronisation; a heal's replay reads it again)
-    const float *focus_px = focusX >= 0 ? (const float *)((const char *)depth + (size_t)focusY * dp) + focusX : nullptr;
-    return defocus_body<true>(ctx, orig, op, depth, dp, art, ap, rows, cols, kernelSize, focusDepth, focus_px);
+// Every depth effect (arguments checked by api.cpp or cascade_api.cpp): k_blend's three modes and the two defocus bodies.
+int launch_effect(rtdd_ctx *ctx, const Effect &e) {
+    switch (e.kind) {
+        case RTDD_EFFECT_DEFOCUS:
+            return defocus_body<false>(ctx, e.original, e.originalPitch, e.depth, e.depthPitch, e.artistic, e.artisticPitch, e.rows, e.cols,
+                                       window_scale(0.025, e.rows, e.cols), 0.0f, nullptr);     // :42, evaluated once on the host
+        case Effect::kRefocus: {
+            // the pixel form: the kernels read the focal depth from the map when they run (no host synchronisation; a heal's replay reads it again)
+            const float *focus_px = e.focusX >= 0 ? (const float *)((const char *)e.depth + (size_t)e.focusY * e.depthPitch) + e.focusX : nullptr;
+            return defocus_body<true>(ctx, e.original, e.originalPitch, e.depth, e.depthPitch, e.artistic, e.artisticPitch, e.rows, e.cols,
+                                      e.kernelSize, e.focusDepth, focus_px);
+        }
+        case RTDD_EFFECT_DESATURATION:
+            return launch_blend<0>(ctx, e.original, e.originalPitch, e.gray, e.grayPitch, e.depth, e.depthPitch, e.artistic, e.artisticPitch,
+                                   e.rows, e.cols);
+        case RTDD_EFFECT_HAZE:
+            return launch_blend<1>(ctx, e.original, e.originalPitch, nullptr, 0, e.depth, e.depthPitch, e.artistic, e.artisticPitch, e.rows, e.cols);
+        case Effect::kHazeEx:
+            return launch_blend<2>(ctx, e.original, e.originalPitch, nullptr, 0, e.depth, e.depthPitch, e.artistic, e.artisticPitch, e.rows, e.cols,
+                                   e.beta, e.air);
+        default: return fail(ctx, RTDD_ERR_INVALID, "unknown depth effect");
+    }
 }
 
 }  // namespace rtdd

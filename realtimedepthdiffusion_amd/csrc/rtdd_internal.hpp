@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <string>
@@ -61,7 +62,7 @@ struct Batch {
 
 // What a solve is told BESIDES the reference's own arguments (GPUMatrixFreeSolver's, src/GPUSolver.cu:274-275).  Passed down the call
 // chain by value or const reference -- estimate_levels -> solve_with -> the launchers -- and stored by value in the pending-call log
-// (PendingOp): nothing is parked in the context around a call, so a replay restores nothing by hand.
+// (PendingOp, next to the solve's own arguments): nothing is parked in the context around a call, so a replay restores nothing by hand.
 struct SolveTargets {
     Batch batch;                                    // the images the launches cover (n = 1, first = 0: one image)
     bool defer_finish = false;                      // leave the result in its plane: the next level's pyrUp kernel reads it there
@@ -80,6 +81,30 @@ struct LiveTargets {
     int effect = 0;                                 // RTDD_EFFECT_*
     uint8_t *artistic = nullptr; size_t artistic_pitch = 0;     // device image the effect writes (the frame's staging slot)
 };
+
+// One depth effect, arguments checked: what to render, on which images, with which parameters.  Built by the rtdd_simulate_* entry
+// points (api.cpp) and by a live frame (live_effect), launched by launch_effect, and logged by value (PendingOp) to be launched again.
+struct Effect {
+    enum : int { kRefocus = RTDD_EFFECT_HAZE + 1, kHazeEx };        // the extensions, after the public kinds
+    int kind = RTDD_EFFECT_NONE;                    // RTDD_EFFECT_DEFOCUS / _DESATURATION / _HAZE, kRefocus, kHazeEx
+    const uint8_t *original = nullptr; size_t originalPitch = 0;
+    const float *depth = nullptr; size_t depthPitch = 0;
+    uint8_t *artistic = nullptr; size_t artisticPitch = 0;
+    int rows = 0, cols = 0;
+    const uint8_t *gray = nullptr; size_t grayPitch = 0;            // desaturation
+    // refocus: the window scale (<= 255) and the focus (focusX >= 0: the map's pixel (focusX, focusY), read by the kernels when they run)
+    int kernelSize = 0, focusX = -1, focusY = -1;
+    float focusDepth = 0.0f;
+    float beta = 2.0f; uint32_t air = 0xFFFFFFu;                    // haze_ex: density and airlight b | g << 8 | r << 16
+};
+
+// The defocus window scale K of src/GPUDepthEffect.cu:42, (int)(aperture * diagonal) -- double * float and the int products as there,
+// evaluated on the host (sqrtf is correctly rounded on the host as on the device).  INT_MAX where the product does not fit an int (an
+// aperture a refocus refuses).
+inline int window_scale(double aperture, int rows, int cols) {
+    const double k = aperture * sqrtf(rows * rows + cols * cols);
+    return k < 2147483647.0 ? (int)k : 2147483647;
+}
 
 struct Options {
     int fp_contract = 1;
@@ -108,9 +133,10 @@ struct Options {
 
 // One asynchronous call whose results the caller has not yet seen confirmed by a synchronising call: what check_persistent_status
 // needs to run it again when a persistent launch gave up (api.cpp, "self-healing").  A solve is one sequence number (handed to the
-// kernel that publishes its result: k_finish, or k_pyrup_inject inside an estimate); an estimate is one per pyramid level.
+// kernel that publishes its result: k_finish, or k_pyrup_inject inside an estimate); an estimate is one per pyramid level; an effect
+// publishes none.
 struct PendingOp {
-    enum Kind { kSolve = 0, kEstimate = 1, kDefocus = 2, kDesaturate = 3, kHaze = 4, kRefocus = 5, kHazeEx = 6 } kind = kSolve;
+    enum Kind { kSolve = 0, kEstimate = 1, kEffect = 2 } kind = kSolve;
     Options opt;                          // the options in force when the call was made
     // kSolve: the arguments of rtdd_solve_ex (+ the optional u8 copy of the result, rtdd_refine_depth)
     float *depth = nullptr; size_t depthPitch = 0;
@@ -125,14 +151,8 @@ struct PendingOp {
     int batch_first = 0, batch_n = 1;     // the images of the context's batched pyramid the estimate covers
     LiveTargets live;                     // a live frame: its annotation pair, its map's second target, its effect (scribble == nullptr: not one)
     unsigned long long id = 0;            // position in the context's call order (live mode drops the confirmed prefix of the log)
-    // kDefocus / kDesaturate / kHaze / kRefocus / kHazeEx: a depth effect queued BEHIND an unconfirmed solve (it may have read that solve's
-    // input instead of its result); `depth` / `depthPitch` / `gray` / `grayPitch` / `rows` / `cols` above, and:
-    const uint8_t *original = nullptr; size_t originalPitch = 0;
-    uint8_t *artistic = nullptr; size_t artisticPitch = 0;
-    // kRefocus: the window scale and the focus (focusX >= 0: the map's pixel, read again by the replay); kHazeEx: density and airlight
-    int kernelSize = 0, focusX = -1, focusY = -1;
-    float focusDepth = 0.0f, beta = 0.0f;
-    uint32_t air = 0;
+    // kEffect: a depth effect queued BEHIND an unconfirmed solve (it may have read that solve's input instead of its result)
+    Effect effect;
 };
 constexpr int kRestartSolve = -1000;      // internal status: the pending calls were healed inside a solve's residual check; that solve starts over
 constexpr size_t kMaxPendingOps = 4096;
@@ -297,15 +317,7 @@ int launch_paint(rtdd_ctx *ctx, int x, int y, int color, int radius, uint8_t *ed
                  uint8_t *scribble, size_t scribblePitch, int rows, int cols);
 
 // ---- effect_kernels.hip -------------------------------------------------------------------------
-int launch_desaturate(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const uint8_t *gray, size_t gp, const float *depth, size_t dp,
-                      uint8_t *art, size_t ap, int rows, int cols);
-int launch_haze(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const float *depth, size_t dp, uint8_t *art, size_t ap, int rows, int cols);
-int launch_defocus(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const float *depth, size_t dp, uint8_t *art, size_t ap, int rows, int cols);
-// rtdd_simulate_refocus / rtdd_simulate_haze_ex, arguments checked (api.cpp): kernelSize <= 255; air = b | g << 8 | r << 16
-int launch_refocus(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const float *depth, size_t dp, uint8_t *art, size_t ap, int rows, int cols,
-                   int kernelSize, float focusDepth, int focusX, int focusY);
-int launch_haze_ex(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const float *depth, size_t dp, uint8_t *art, size_t ap, int rows, int cols,
-                   float beta, uint32_t air);
+int launch_effect(rtdd_ctx *ctx, const Effect &e);
 
 // ---- cascade.hip -------------------------------------------------------------------------------
 int launch_bgr2gray(rtdd_ctx *ctx, const uint8_t *bgr, size_t bp, uint8_t *gray, size_t gp, int rows, int cols);

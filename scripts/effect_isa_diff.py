@@ -1,21 +1,22 @@
-"""Per-kernel instruction diff of the effect kernels between two gfx950 device objects of effect_kernels.hip -- the check that the
-instantiations rtdd_simulate_defocus / _desaturation / _haze launch are unchanged by a later edit (e.g. the FOCUS flag of k_defocus /
-k_defocus_tile, k_blend's third mode).  Kernels are matched by demangled name without their parameter lists; for the defocus kernels
-of the NEW object a trailing `, false>` template argument (FOCUS off) is dropped.  Branch targets and addresses are normalised.
+"""Per-kernel instruction diff between two gfx950 device objects of one csrc/*.hip file -- the check that an edit left every kernel of
+that file instruction for instruction as it was (a host-side refactor; a new template flag that must not touch the old instantiations).
+Every function of both objects is compared, matched by its demangled name on both sides alike.  Branch targets and addresses are
+normalised: raw code-object bundles differ between two compiles of the same source, the disassembly does not.
 
-    F=$(make -s -C realtimedepthdiffusion_amd/csrc print-cxxflags)
-    hipcc --offload-arch=gfx950 $F --cuda-device-only -save-temps=obj -o OLD/effect.co -c effect_kernels.hip   # at the parent commit
-    hipcc --offload-arch=gfx950 $F --cuda-device-only -save-temps=obj -o NEW/effect.co -c effect_kernels.hip   # at this one
-    python scripts/effect_isa_diff.py OLD/effect_kernels-hip-amdgcn-amd-amdhsa-gfx950.out NEW/effect_kernels-hip-amdgcn-amd-amdhsa-gfx950.out
+    cd realtimedepthdiffusion_amd/csrc                 # the flags hold -I.
+    F=$(make -s print-cxxflags)
+    hipcc --offload-arch=gfx950 $F --cuda-device-only -c X.hip -o OUT/X.co                # at the parent commit into OLD, here into NEW
+    clang-offload-bundler --unbundle --type=o --input=OUT/X.co --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --output=OUT/X.dev.o
+    python scripts/effect_isa_diff.py OLD/X.dev.o NEW/X.dev.o                              # from the repository root
 
-Prints nothing but the count on stderr when every old kernel has its new counterpart with the same instructions; exit status 1 otherwise."""
+(clang-offload-bundler is /opt/rocm/lib/llvm/bin's.)  Prints "compared N kernels, M differ" on stderr, and for every kernel that differs
+or exists in one object only a line and the start of its instruction diff; exit status 1 unless M is 0."""
 import difflib
 import re
 import subprocess
 import sys
 
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
-PICK = re.compile(r"k_defocus|k_blend|k_sat")
 
 
 def kernels(path):
@@ -33,25 +34,19 @@ def kernels(path):
     return ks
 
 
-def key(name, newer):
-    name = name.split("(")[0]
-    if newer and "k_defocus" in name:
-        name = name.replace(", false>", ">")
-    return name
-
-
 def main(old_path, new_path):
-    old = {key(n, False): v for n, v in kernels(old_path).items() if PICK.search(n)}
-    new = {key(n, True): v for n, v in kernels(new_path).items() if PICK.search(n)}
+    old, new = kernels(old_path), kernels(new_path)
     bad = 0
-    for n in sorted(old):
+    for n in sorted(old.keys() | new.keys()):
         if n not in new:
             print("missing in the new object:", n); bad += 1
+        elif n not in old:
+            print("missing in the old object:", n); bad += 1
         elif old[n] != new[n]:
             print("differs:", n); bad += 1
             for line in list(difflib.unified_diff(old[n], new[n], lineterm=""))[:40]:
                 print("  ", line)
-    print(f"compared {len(old)} kernels, {bad} differ", file=sys.stderr)
+    print(f"compared {len(old.keys() | new.keys())} kernels, {bad} differ", file=sys.stderr)
     return 1 if bad else 0
 
 
