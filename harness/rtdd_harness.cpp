@@ -8,7 +8,9 @@
 //     key 's'  -> also the annotated image   (main.cpp:298-303)  -> <out>AnnotatedImage.ppm: the image with the scribbles painted in
 //     key 'b'/'g'/'h' -> --effect defocus|desaturation|haze     -> <out>ArtisticEffect.ppm (main.cpp:190-230, 312-316)
 //     extensions: --effect refocus [--focus D | --focus-at X,Y] [--aperture A]   (rtdd_simulate_refocus; default: focus depth 0,
-//                 aperture 0.025 = the defocus), --effect haze [--haze-beta B] [--airlight b,g,r]   (rtdd_simulate_haze_ex when either is given)
+//                 aperture 0.025 = the defocus), --effect haze [--haze-beta B] [--airlight b,g,r]   (rtdd_simulate_haze_ex when either is given),
+//                 --effect stereo --disparity D [--zero-parallax Z | --zero-parallax-at X,Y] [--anaglyph]   (rtdd_simulate_stereo; default:
+//                 zero parallax at depth 0, the view)
 //     key 't'  -> prints "Processing Time"  (main.cpp:320-322; wall clock here, the reference uses clock()); the process's one-time costs
 //                 (~20 ms: code objects, first allocations) are paid by a warm-up on a context of its own first -- --cold leaves it out
 //     --paint x,y,label,radius  = a mouse drag sample (main.cpp:46-62), repeatable; --paint-at F:x,y,label,radius = the same while --live
@@ -181,6 +183,10 @@ struct Job {
     bool haze_ex = false;         // --haze-beta / --airlight given: rtdd_simulate_haze_ex
     float haze_beta = 2.0f;
     int air[3] = {255, 255, 255}; // b, g, r
+    int disparity = 0;            // --effect stereo: --disparity, --zero-parallax / --zero-parallax-at (zero_x < 0: the depth zero_depth), --anaglyph
+    float zero_depth = 0.0f;
+    int zero_x = -1, zero_y = -1;
+    bool anaglyph = false;
     bool sequential = false;      // --sequential: a --batch as one estimate after the other (default: rtdd_estimate_depth_batch, all images in the same launches)
     bool cold = false;            // --cold: no warm-up: the first (and, without --live, only) estimate pays the one-time costs
 };
@@ -379,6 +385,9 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
         else if (job.effect == "refocus")
             CK(rtdd_simulate_refocus(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols, job.aperture,
                                      job.focus_depth, job.focus_x, job.focus_y));
+        else if (job.effect == "stereo")
+            CK(rtdd_simulate_stereo(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols, job.disparity,
+                                    job.zero_depth, job.zero_x, job.zero_y, job.anaglyph ? RTDD_STEREO_ANAGLYPH : RTDD_STEREO_VIEW));
         depth_u8->resize((size_t)rows * cols);
         CK(rtdd_download(ctx, depth_u8->data(), cols, p_u8, pi_u8, cols, rows));   // main.cpp:291 (synchronises)
         if (!job.effect.empty()) { art->resize((size_t)rows * cols * 3); CK(rtdd_download(ctx, art->data(), (size_t)cols * 3, p_art, pi_art, (size_t)cols * 3, rows)); }
@@ -391,8 +400,9 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
 }
 
 int main(int argc, const char *argv[]) {
-    if (argc == 1) { std::printf("Usage: rtdd_harness -i image.(jpg|png|ppm) [-a annotation.(png|pgm)] [-o prefix] [--effect defocus|desaturation|haze|refocus] [--iters N] [--refine sor|mg|auto [--tolerance T]]\n"
+    if (argc == 1) { std::printf("Usage: rtdd_harness -i image.(jpg|png|ppm) [-a annotation.(png|pgm)] [-o prefix] [--effect defocus|desaturation|haze|refocus|stereo] [--iters N] [--refine sor|mg|auto [--tolerance T]]\n"
                                  "                    [--focus D | --focus-at X,Y] [--aperture A] (refocus)  [--haze-beta B] [--airlight b,g,r] (haze)\n"
+                                 "                    [--disparity D] [--zero-parallax Z | --zero-parallax-at X,Y] [--anaglyph] (stereo)\n"
                                  "                    [--paint x,y,label,radius]... [--live N [--paint-at frame:x,y,label,radius]...] [--devices D --batch B [--sequential] [--write-all]] [--png] [--cold]\n"
                                  "       rtdd_harness --convert in.(jpg|png|ppm|pgm) out.(png|ppm|pgm)   (JPEG / 8-bit PNG / PNM -> PNG / PNM, no GPU)\n"); return 0; }
     if (argc == 4 && !std::strcmp(argv[1], "--convert")) {               // file format conversion only (no GPU): JPEG / PNG / PNM -> PNG / PNM
@@ -425,6 +435,10 @@ int main(int argc, const char *argv[]) {
         else if (!std::strcmp(argv[i], "--focus")) { job.focus_depth = (float)std::atof(next()); job.focus_x = -1; }
         else if (!std::strcmp(argv[i], "--focus-at")) { if (std::sscanf(next(), "%d,%d", &job.focus_x, &job.focus_y) != 2) { std::printf("--focus-at wants X,Y\n"); return 1; } }
         else if (!std::strcmp(argv[i], "--aperture")) job.aperture = std::atof(next());
+        else if (!std::strcmp(argv[i], "--disparity")) job.disparity = std::atoi(next());
+        else if (!std::strcmp(argv[i], "--zero-parallax")) { job.zero_depth = (float)std::atof(next()); job.zero_x = -1; }
+        else if (!std::strcmp(argv[i], "--zero-parallax-at")) { if (std::sscanf(next(), "%d,%d", &job.zero_x, &job.zero_y) != 2) { std::printf("--zero-parallax-at wants X,Y\n"); return 1; } }
+        else if (!std::strcmp(argv[i], "--anaglyph")) job.anaglyph = true;
         else if (!std::strcmp(argv[i], "--haze-beta")) { job.haze_beta = (float)std::atof(next()); job.haze_ex = true; }
         else if (!std::strcmp(argv[i], "--airlight")) {
             if (std::sscanf(next(), "%d,%d,%d", &job.air[0], &job.air[1], &job.air[2]) != 3) { std::printf("--airlight wants b,g,r\n"); return 1; }
@@ -434,8 +448,8 @@ int main(int argc, const char *argv[]) {
         else if (!std::strcmp(argv[i], "-h")) std::printf("Usage:\n -i input image (JPEG, 8-bit PNG, binary PPM)\n -a annotated image (8-bit PNG, binary PGM)\n");
     }
     // a live frame's sticky effect is an effect code without parameters (rtdd_live_submit_ex): the aimed effects are not available there
-    if (live > 0 && (job.effect == "refocus" || (job.effect == "haze" && job.haze_ex))) {
-        std::printf("--live renders the reference's three effects only: --effect refocus and --haze-beta / --airlight are not supported with --live\n");
+    if (live > 0 && (job.effect == "refocus" || job.effect == "stereo" || (job.effect == "haze" && job.haze_ex))) {
+        std::printf("--live renders the reference's three effects only: --effect refocus, --effect stereo and --haze-beta / --airlight are not supported with --live\n");
         return 1;
     }
     Pnm rgb;

@@ -274,7 +274,8 @@ int rtdd_simulate_haze(rtdd_ctx *ctx, const uint8_t *original, size_t originalPi
 
 /* ---- aimed depth effects (extensions; no reference behaviour) --------------------------------
  * Added after ABI version 230 without a version bump: a host finds them by symbol (dlsym).  The next bump of RTDD_VERSION
- * should cover them, together with a parameterised live effect (rtdd_live_submit_ex takes an effect code only and knows neither). */
+ * should cover them (rtdd_simulate_refocus, rtdd_simulate_haze_ex, rtdd_simulate_stereo), together with a parameterised live effect
+ * (rtdd_live_submit_ex takes an effect code only and knows none of them). */
 
 /* Refocus: the defocus effect sharp at a chosen depth instead of at depth 0.
  *   K = (int)(aperture * sqrtf(rows*rows + cols*cols))   -- double times float, truncated, as GPUDepthEffect.cu:42; aperture 0.025 gives
@@ -303,6 +304,27 @@ int rtdd_simulate_refocus(rtdd_ctx *ctx, const uint8_t *original, size_t origina
 int rtdd_simulate_haze_ex(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch,
                           const float *depth, size_t depthPitch, uint8_t *artistic, size_t artisticPitch,
                           int rows, int cols, float beta, uint8_t airB, uint8_t airG, uint8_t airR);
+
+/* Stereo: a second eye's view rendered from the depth map (0 near, 255 far, as haze reads it), or a red-cyan anaglyph.  Each row on
+ * its own; D = disparity:
+ *   d' = fminf(fmaxf(d, 0), 255) (a NaN depth is 0);  z0 = zeroParallaxDepth when zeroX < 0, otherwise the depth map's value at
+ *       (zeroX, zeroY), clamped alike and READ BY THE KERNEL ON THE DEVICE when it runs (no host synchronisation, as refocus's focus);
+ *   s(x) = (int)rintf(((float)D * (d' - z0)) / 255.0f), each operation rounded in f32, none fused, rintf half to even: |s| <= |D|;
+ *   source x lands on t = x + s(x), dropped unless 0 <= t < cols; of several sources on one target the NEAREST wins (the smallest
+ *   s * sign(D); equal shifts never share a target); a filled target is view[t] = original[winner], no interpolation;
+ *   a hole (no source) copies the view of the nearest filled target on the BACKGROUND side (right when D > 0, left when D < 0), else
+ *   of the nearest on the other side, else (no filled target in the row) original[t].
+ *   mode RTDD_STEREO_VIEW: artistic = view.  RTDD_STEREO_ANAGLYPH: BGR (view.b, view.g, orig.r) when D >= 0 (the view is the right
+ *   eye), (orig.b, orig.g, view.r) when D < 0.
+ * D > 0 renders a camera moved to the right: pixels nearer than z0 move left, farther ones right.  D = 0 gives the original in both
+ * modes.  The output does not depend on RTDD_OPT_FP_CONTRACT.  One kernel launch, deterministic.
+ * Refused on the host (RTDD_ERR_INVALID), before any launch: the rules of the three effects (null pointers, pitches, image size);
+ * |D| > 256; a mode other than the two; a zeroParallaxDepth that is non-finite or outside [0, 255] when it is used; a zero-parallax
+ * pixel outside the image when zeroX >= 0; original == artistic (not in place). */
+enum rtdd_stereo_mode { RTDD_STEREO_VIEW = 0, RTDD_STEREO_ANAGLYPH = 1 };
+int rtdd_simulate_stereo(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch,
+                         const float *depth, size_t depthPitch, uint8_t *artistic, size_t artisticPitch,
+                         int rows, int cols, int disparity, float zeroParallaxDepth, int zeroX, int zeroY, int mode);
 
 /* ---- whole-estimate driver ------------------------------------------------
  * One depth estimate = the loop body of src/main.cpp:232-295, run as a single stream-ordered launch

@@ -51,10 +51,11 @@ C_ABI_SYMBOLS = [
     "rtdd_pyrup_depth", "rtdd_depth_to_u8", "rtdd_upload", "rtdd_download",
     "rtdd_live_submit", "rtdd_live_wait", "rtdd_live_pending", "rtdd_host_alloc", "rtdd_host_free",
     "rtdd_pyramid_create_batch", "rtdd_pyramid_select", "rtdd_pyramid_batch", "rtdd_estimate_depth_batch", "rtdd_pyramid_level_info", "rtdd_live_submit_ex",
-    "rtdd_simulate_refocus", "rtdd_simulate_haze_ex",
+    "rtdd_simulate_refocus", "rtdd_simulate_haze_ex", "rtdd_simulate_stereo",
 ]
 IMG_ORIGINAL, IMG_GRAY, IMG_SCRIBBLE, IMG_EDITED, IMG_DEPTH, IMG_DEPTH_U8, IMG_ARTISTIC = range(7)
 EFFECT_NONE, EFFECT_DEFOCUS, EFFECT_DESATURATION, EFFECT_HAZE = range(4)
+STEREO_VIEW, STEREO_ANAGLYPH = 0, 1           # rtdd_simulate_stereo's modes
 # Itanium-mangled names of the reference's ten free functions
 DROPIN_SYMBOLS = [
     "_Z23GPUAllocateDeviceMemoryiii", "_Z19GPUFreeDeviceMemoryi", "_Z14GPULoadWeightsf",
@@ -313,6 +314,14 @@ class Context:
         b, g, r = air
         self._check(lib().rtdd_simulate_haze_ex(self._h, o, op, d, dp, a, ap, C.c_int(rows), C.c_int(cols), C.c_float(beta),
                                                 C.c_uint8(b), C.c_uint8(g), C.c_uint8(r)))
+
+    def simulate_stereo(self, originalImage, depthImage, artisticImage, rows, cols, disparity, zeroParallaxDepth=0.0, zeroX=-1, zeroY=-1,
+                        mode=STEREO_VIEW):
+        """A second eye's view with `disparity` pixels between depths 0 and 255, zero parallax at `zeroParallaxDepth` or (zeroX >= 0) at
+        the depth map's value at (zeroX, zeroY), read on the device; mode STEREO_ANAGLYPH: a red-cyan anaglyph of it with the original."""
+        o, op = _img(originalImage); d, dp = _img(depthImage); a, ap = _img(artisticImage)
+        self._check(lib().rtdd_simulate_stereo(self._h, o, op, d, dp, a, ap, C.c_int(rows), C.c_int(cols), C.c_int(disparity),
+                                               C.c_float(zeroParallaxDepth), C.c_int(zeroX), C.c_int(zeroY), C.c_int(mode)))
 
 
     # ---- whole-estimate driver (src/main.cpp:92-155, 232-295)

@@ -934,5 +934,23 @@ int rtdd_simulate_haze_ex(rtdd_ctx *ctx, const uint8_t *original, size_t origina
     return simulate(ctx, e);
 }
 
+int rtdd_simulate_stereo(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
+                         uint8_t *artistic, size_t artisticPitch, int rows, int cols, int disparity, float zeroParallaxDepth, int zeroX, int zeroY,
+                         int mode) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    int rc = check_effect(ctx, original, depth, artistic, originalPitch, depthPitch, artisticPitch, rows, cols);
+    if (rc != RTDD_OK) return rc;
+    REQUIRE(ctx, disparity >= -256 && disparity <= 256, "|disparity| must be <= 256");
+    REQUIRE(ctx, mode == RTDD_STEREO_VIEW || mode == RTDD_STEREO_ANAGLYPH, "mode must be RTDD_STEREO_VIEW or RTDD_STEREO_ANAGLYPH");
+    if (zeroX < 0) REQUIRE(ctx, std::isfinite(zeroParallaxDepth) && zeroParallaxDepth >= 0.0f && zeroParallaxDepth <= 255.0f,
+                           "zeroParallaxDepth must be finite and in [0, 255]");
+    else REQUIRE(ctx, zeroX < cols && zeroY >= 0 && zeroY < rows, "zero-parallax pixel outside the image");
+    if (rows == 0 || cols == 0) return RTDD_OK;
+    REQUIRE(ctx, original != artistic, "stereo cannot run in place");
+    Effect e{Effect::kStereo, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols};
+    e.disparity = disparity; e.zeroDepth = zeroParallaxDepth; e.zeroX = zeroX; e.zeroY = zeroY; e.stereoMode = mode;
+    return simulate(ctx, e);
+}
+
 }  // extern "C"
 #pragma GCC visibility pop

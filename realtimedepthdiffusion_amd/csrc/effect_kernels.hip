@@ -133,6 +133,134 @@ __global__ __launch_bounds__(256) void k_blend(const uint8_t *__restrict__ orig,
     }
 }
 
+// ---- stereo: a per-row forward warp (rtdd_simulate_stereo, include/rtdd.h) -----------------------------------------------------
+// Source x lands on target x + s(x), s = (int)rintf((D * (d' - z0)) / 255) in f32 with no fused operation (|s| <= |D| <= 256); the
+// nearest source (smallest s * sign(D)) wins a target; a hole copies the view of the nearest filled target on the background side, else
+// of the other side, else original[t].  One workgroup per (row, segment of kStW targets); no global atomics, no communication between
+// workgroups.  Halo (DESIGN.md "Stereo"): every hole run that is not the whole row is at most |D| + 1 long, so a hole's filled
+// neighbours on both sides lie within H = |D| + 1 of it -- the workgroup resolves the targets [t0 - H, t1 + H) (E), and those are
+// reached only from the sources [t0 - H - |D|, t1 + H + |D|).  A row with no filled target has cols <= |D| + 1 <= H: E is the whole row.
+constexpr int kStMaxD = 256, kStW = 1024, kStMaxE = kStW + 2 * (kStMaxD + 1), kStC = (kStMaxE + 255) / 256;
+constexpr uint32_t kStEmpty = 0xFFFFFFFFu;
+
+__device__ __forceinline__ int stereo_shift(float d, float z0, float D) {
+    const float dc = fminf(fmaxf(d, 0.0f), 255.0f);                 // a NaN depth is 0
+    return (int)rintf((D * (dc - z0)) / 255.0f);                    // (-ffp-contract=off, IEEE divide: three roundings)
+}
+// pixel x of an interleaved BGR row as b | g << 8 | r << 16
+__device__ __forceinline__ uint32_t bgr_at(const uint8_t *row, int x) {
+    const uint8_t *p = row + 3 * (size_t)x;
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+}
+
+// VEC: 4 targets per thread with dword accesses (needs 4-byte aligned rows of the original and the artistic image).  zp: the depth
+// map's zero-parallax pixel (the pixel form, read here when the kernel runs), else z0 is the value `zval`.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_stereo(const uint8_t *__restrict__ orig, size_t op, const float *__restrict__ depth, size_t dp,
+                                                uint8_t *__restrict__ art, size_t ap, int rows, int cols, int D, float zval,
+                                                const float *__restrict__ zp, int anaglyph) {
+    __shared__ uint32_t key[kStMaxE];                               // per target of E: sign(D) * s + 256 of the winner (kStEmpty: a hole)
+    __shared__ int res[kStW];                                       // per target of the segment: the source whose colour it takes (-1: original[t])
+    __shared__ int wl[4], wr[4];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int y = blockIdx.y, t0 = blockIdx.x * kStW, t1 = min(cols, t0 + kStW);
+    const int aD = D < 0 ? -D : D, sg = D < 0 ? -1 : 1, H = aD + 1;
+    const int e0 = max(0, t0 - H), e1 = min(cols, t1 + H), nE = e1 - e0;
+    const float z0 = zp ? fminf(fmaxf(*zp, 0.0f), 255.0f) : zval;
+    const float Df = (float)D;
+    const float *drow = (const float *)((const char *)depth + (size_t)y * dp);
+    const uint8_t *orow = orig + (size_t)y * op;
+    uint8_t *arow = art + (size_t)y * ap;
+
+    for (int i = tid; i < nE; i += 256) key[i] = kStEmpty;
+    __syncthreads();
+    // every source that can land in E; the minimum key picks the nearest (equal shifts never share a target: no ties)
+    for (int x = max(0, e0 - aD) + tid, xe = min(cols, e1 + aD); x < xe; x += 256) {
+        const int s = stereo_shift(drow[x], z0, Df), t = x + s;
+        if (t >= e0 && t < e1) atomicMin(&key[t - e0], (uint32_t)(sg * s + 256));
+    }
+    __syncthreads();
+
+    // nearest filled slot at or left of (lf) and at or right of (rf) every slot: thread chunks of kStC slots, a max / min scan over them
+    const int c0 = tid * kStC;
+    int last = -1, first = 0x7FFFFFFF;
+#pragma unroll
+    for (int i = 0; i < kStC; i++) {
+        const int j = c0 + i;
+        if (j < nE && key[j] != kStEmpty) { last = j; if (first == 0x7FFFFFFF) first = j; }
+    }
+    int a = last, b = first;                                        // inclusive scans within the wave: max from the left, min from the right
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int u = __shfl_up(a, o), v = __shfl_down(b, o);
+        if (lane >= o) a = max(a, u);
+        if (lane + o < 64) b = min(b, v);
+    }
+    if (lane == 63) wl[w] = a;
+    if (lane == 0) wr[w] = b;
+    int exl = __shfl_up(a, 1), exr = __shfl_down(b, 1);
+    if (lane == 0) exl = -1;
+    if (lane == 63) exr = 0x7FFFFFFF;
+    __syncthreads();
+    for (int k = 0; k < w; k++) exl = max(exl, wl[k]);
+    for (int k = w + 1; k < 4; k++) exr = min(exr, wr[k]);
+    int lf[kStC];
+#pragma unroll
+    for (int i = 0; i < kStC; i++) {
+        const int j = c0 + i;
+        if (j < nE && key[j] != kStEmpty) exl = j;
+        lf[i] = exl;
+    }
+#pragma unroll
+    for (int i = kStC - 1; i >= 0; i--) {
+        const int j = c0 + i;
+        if (j >= nE) continue;
+        if (key[j] != kStEmpty) exr = j;
+        const int t = e0 + j;
+        if (t < t0 || t >= t1) continue;
+        const int rf = exr == 0x7FFFFFFF ? -1 : exr;
+        const int pick = D > 0 ? (rf >= 0 ? rf : lf[i]) : (lf[i] >= 0 ? lf[i] : rf);     // the background side first (filled: itself)
+        res[t - t0] = pick < 0 ? -1 : (e0 + pick) - sg * ((int)key[pick] - 256);
+    }
+    __syncthreads();
+
+    const int tb = t0 + 4 * tid;
+    if (tb >= t1) return;
+    uint32_t out[4];
+    const bool whole = VEC && tb + 3 < t1;
+    uint32_t ow[3] = {0, 0, 0};
+    if (whole && anaglyph) { const uint32_t *o3 = (const uint32_t *)(orow + 3 * (size_t)tb); ow[0] = o3[0]; ow[1] = o3[1]; ow[2] = o3[2]; }
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int t = tb + i;
+        if (t >= t1) break;
+        const int x = res[t - t0];
+        uint32_t v = bgr_at(orow, x >= 0 ? x : t);
+        if (anaglyph) {
+            uint32_t o;
+            if (whole) {
+                const uint32_t lo = i == 0 ? ow[0] : i == 1 ? (ow[0] >> 24) | (ow[1] << 8) : i == 2 ? (ow[1] >> 16) | (ow[2] << 16) : ow[2] >> 8;
+                o = lo & 0xFFFFFFu;
+            } else {
+                o = bgr_at(orow, t);
+            }
+            v = D >= 0 ? (v & 0x00FFFFu) | (o & 0xFF0000u) : (o & 0x00FFFFu) | (v & 0xFF0000u);   // (view.b, view.g, orig.r) | (orig.b, orig.g, view.r)
+        }
+        out[i] = v;
+    }
+    if (whole) {
+        uint32_t *a3 = (uint32_t *)(arow + 3 * (size_t)tb);
+        a3[0] = out[0] | (out[1] << 24);
+        a3[1] = (out[1] >> 8) | (out[2] << 16);
+        a3[2] = (out[2] >> 16) | (out[3] << 8);
+    } else {
+        for (int i = 0; i < 4 && tb + i < t1; i++) {
+            uint8_t *p = arow + 3 * (size_t)(tb + i);
+            p[0] = (uint8_t)out[i]; p[1] = (uint8_t)(out[i] >> 8); p[2] = (uint8_t)(out[i] >> 16);
+        }
+    }
+}
+
 // ---- defocus: packed summed-area table ---------------------------------------------------------------
 // The reference gathers up to (2*(K/2))^2 taps per pixel (src/GPUDepthEffect.cu:47-60: 2 916 at 1080p, 12 100 at 4K, 48 400 at 8K).
 // Here: an exact O(1) lookup.  A pixel is packed into ONE 64-bit integer  p = B + G * 2^21 + R * 2^42  and
@@ -933,6 +1061,18 @@ int launch_effect(rtdd_ctx *ctx, const Effect &e) {
         case Effect::kHazeEx:
             return launch_blend<2>(ctx, e.original, e.originalPitch, nullptr, 0, e.depth, e.depthPitch, e.artistic, e.artisticPitch, e.rows, e.cols,
                                    e.beta, e.air);
+        case Effect::kStereo: {
+            // the pixel form: the kernel reads z0 from the map when it runs (as refocus's focus)
+            const float *zp = e.zeroX >= 0 ? (const float *)((const char *)e.depth + (size_t)e.zeroY * e.depthPitch) + e.zeroX : nullptr;
+            const bool vec = (uintptr_t)e.original % 4 == 0 && e.originalPitch % 4 == 0 && (uintptr_t)e.artistic % 4 == 0 && e.artisticPitch % 4 == 0;
+            const dim3 g((e.cols + kStW - 1) / kStW, e.rows);
+            if (vec) hipLaunchKernelGGL(k_stereo<true>, g, dim3(256), 0, ctx->stream, e.original, e.originalPitch, e.depth, e.depthPitch, e.artistic,
+                                        e.artisticPitch, e.rows, e.cols, e.disparity, e.zeroDepth, zp, e.stereoMode);
+            else hipLaunchKernelGGL(k_stereo<false>, g, dim3(256), 0, ctx->stream, e.original, e.originalPitch, e.depth, e.depthPitch, e.artistic,
+                                    e.artisticPitch, e.rows, e.cols, e.disparity, e.zeroDepth, zp, e.stereoMode);
+            RTDD_LAUNCH_CHECK(ctx, "k_stereo");
+            return RTDD_OK;
+        }
         default: return fail(ctx, RTDD_ERR_INVALID, "unknown depth effect");
     }
 }

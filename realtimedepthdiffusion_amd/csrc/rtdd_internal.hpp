@@ -85,8 +85,8 @@ struct LiveTargets {
 // One depth effect, arguments checked: what to render, on which images, with which parameters.  Built by the rtdd_simulate_* entry
 // points (api.cpp) and by a live frame (live_effect), launched by launch_effect, and logged by value (PendingOp) to be launched again.
 struct Effect {
-    enum : int { kRefocus = RTDD_EFFECT_HAZE + 1, kHazeEx };        // the extensions, after the public kinds
-    int kind = RTDD_EFFECT_NONE;                    // RTDD_EFFECT_DEFOCUS / _DESATURATION / _HAZE, kRefocus, kHazeEx
+    enum : int { kRefocus = RTDD_EFFECT_HAZE + 1, kHazeEx, kStereo };   // the extensions, after the public kinds
+    int kind = RTDD_EFFECT_NONE;                    // RTDD_EFFECT_DEFOCUS / _DESATURATION / _HAZE, kRefocus, kHazeEx, kStereo
     const uint8_t *original = nullptr; size_t originalPitch = 0;
     const float *depth = nullptr; size_t depthPitch = 0;
     uint8_t *artistic = nullptr; size_t artisticPitch = 0;
@@ -96,6 +96,9 @@ struct Effect {
     int kernelSize = 0, focusX = -1, focusY = -1;
     float focusDepth = 0.0f;
     float beta = 2.0f; uint32_t air = 0xFFFFFFu;                    // haze_ex: density and airlight b | g << 8 | r << 16
+    // stereo: disparity (|D| <= 256), zero parallax (zeroX >= 0: the map's pixel (zeroX, zeroY), read by the kernel), rtdd_stereo_mode
+    int disparity = 0, zeroX = -1, zeroY = -1, stereoMode = 0;
+    float zeroDepth = 0.0f;
 };
 
 // The defocus window scale K of src/GPUDepthEffect.cu:42, (int)(aperture * diagonal) -- double * float and the int products as there,
