@@ -20,6 +20,7 @@
 // round-robin over N GPUs, one host thread + one HIP stream + one rtdd_ctx per GPU, no collective.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -169,10 +170,13 @@ static bool write_image(const std::string &path, int w, int h, int ch, const uns
 #define CK(call) do { int rc_ = (call); if (rc_ != RTDD_OK) { std::printf("%s: %s (%s)\n", #call, rtdd_status_string(rc_), rtdd_last_error(ctx)); return rc_; } } while (0)
 
 struct Paint { int x, y, label, radius, frame; };      // frame: --paint-at (live mode: in front of that frame); --paint: before the first estimate
+struct LiveStroke { rtdd_stroke s; int frame; };        // --stroke-at / --erase-at: in front of live frame `frame`
 struct Job {
     Pnm bgr, ann;                 // bgr is BGR-interleaved like cv::imread's Mat
     bool has_ann = false;
     std::vector<Paint> paints, live_paints;
+    std::vector<rtdd_stroke> strokes;         // --stroke / --erase, in command-line order: ONE rtdd_paint_strokes call, after the --paint stamps
+    std::vector<LiveStroke> live_strokes;
     std::string effect;
     int iters = 1000;
     std::string refine;           // "" | "sor" | "mg": rtdd_refine_depth after every estimate
@@ -190,6 +194,55 @@ struct Job {
     bool sequential = false;      // --sequential: a --batch as one estimate after the other (default: rtdd_estimate_depth_batch, all images in the same launches)
     bool cold = false;            // --cold: no warm-up: the first (and, without --live, only) estimate pays the one-time costs
 };
+
+// --stroke / --erase: the job's strokes on a device image pair, one call
+static int paint_strokes(rtdd_ctx *ctx, const std::vector<rtdd_stroke> &strokes, void *ed, size_t ed_pitch, void *scr, size_t scr_pitch, const void *orig, size_t orig_pitch,
+                         int rows, int cols) {
+    if (strokes.empty()) return RTDD_OK;
+    CK(rtdd_paint_strokes(ctx, strokes.data(), (int)strokes.size(), (uint8_t *)ed, ed_pitch, (uint8_t *)scr, scr_pitch, (const uint8_t *)orig, orig_pitch, rows, cols));
+    return RTDD_OK;
+}
+
+// rtdd_paint_strokes restated for the host's own image pair (--live: the host owns the pair every frame uploads; include/rtdd.h has the
+// rules).  Dense images; `orig` is the BGR image.  Returns whether a stroke erased.
+static bool host_strokes(const std::vector<rtdd_stroke> &strokes, unsigned char *scr, unsigned char *ed, const unsigned char *orig, int rows, int cols) {
+    typedef long long i64; typedef unsigned long long u64;
+    bool erased = false;
+    for (const rtdd_stroke &q : strokes) {
+        const int h = q.radius / 2;
+        const int xa = std::max(std::min(q.x0, q.x1) - h, 0), xb = std::min(std::max(q.x0, q.x1) + h, cols - 1);
+        const int ya = std::max(std::min(q.y0, q.y1) - h, 0), yb = std::min(std::max(q.y0, q.y1) + h, rows - 1);
+        const i64 dx = q.x1 - q.x0, dy = q.y1 - q.y0, dd = dx * dx + dy * dy, r2 = (i64)q.radius * q.radius;
+        erased = erased || q.label == RTDD_STROKE_ERASE;
+        for (int y = ya; y <= yb; y++)
+            for (int x = xa; x <= xb; x++) {
+                const i64 vx = x - q.x0, vy = y - q.y0, cross = dx * vy - dy * vx, t = vx * dx + vy * dy;
+                const u64 ac = (u64)(cross < 0 ? -cross : cross);
+                bool in;
+                if (q.brush == RTDD_BRUSH_SQUARE) in = ac <= (u64)h * (u64)((dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy));
+                else if (t <= 0) in = 4 * (vx * vx + vy * vy) <= r2;
+                else if (t >= dd) in = 4 * ((i64)(x - q.x1) * (x - q.x1) + (i64)(y - q.y1) * (y - q.y1)) <= r2;
+                else in = 2 * ac < (1ull << 32) && (2 * ac) * (2 * ac) <= (u64)r2 * (u64)dd;      // (beyond 2^32 the square exceeds radius^2 |d|^2 <= 2^54)
+                if (!in) continue;
+                const size_t i = (size_t)y * cols + x;
+                if (q.label == RTDD_STROKE_ERASE) { scr[i] = 0; for (int c = 0; c < 3; c++) ed[3 * i + c] = orig[3 * i + c]; }
+                else { scr[i] = 255; for (int c = 0; c < 3; c++) ed[3 * i + c] = (unsigned char)q.label; }
+            }
+    }
+    return erased;
+}
+
+// "x0,y0,x1,y1,label,radius[,round]" (erase: no label), with "F:" in front when `frame` is asked for
+static bool parse_stroke(const char *arg, bool erase, rtdd_stroke *q, int *frame) {
+    int n = 0;
+    if (frame) { if (std::sscanf(arg, "%d:%n", frame, &n) != 1 || n == 0) return false; arg += n; n = 0; }
+    q->label = RTDD_STROKE_ERASE; q->brush = RTDD_BRUSH_SQUARE;
+    if (erase ? std::sscanf(arg, "%d,%d,%d,%d,%d%n", &q->x0, &q->y0, &q->x1, &q->y1, &q->radius, &n) != 5
+              : std::sscanf(arg, "%d,%d,%d,%d,%d,%d%n", &q->x0, &q->y0, &q->x1, &q->y1, &q->label, &q->radius, &n) != 6) return false;
+    if (!std::strcmp(arg + n, ",round")) q->brush = RTDD_BRUSH_ROUND;
+    else if (arg[n] != 0 && std::strcmp(arg + n, ",square")) return false;
+    return true;
+}
 
 // What a process pays ONCE on a device -- the runtime's first stream and allocations, every kernel's code object on its first launch,
 // ~20 ms together -- and what "Processing Time" is not about (the reference's first key press pays CUDA's likewise): a 96 x 128 estimate
@@ -262,6 +315,9 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
             CK(rtdd_pyramid_image(ctx, RTDD_IMG_SCRIBBLE, 0, &ps, &pis, nullptr, nullptr));
             CK(rtdd_pyramid_image(ctx, RTDD_IMG_EDITED, 0, &pe, &pie, nullptr, nullptr));
             for (const Paint &p : job.paints) CK(rtdd_paint_image(ctx, p.x, p.y, p.label, p.radius, (uint8_t *)pe, pie, (uint8_t *)ps, pis, rows, cols));
+            void *po; size_t pio;
+            CK(rtdd_pyramid_image(ctx, RTDD_IMG_ORIGINAL, 0, &po, &pio, nullptr, nullptr));
+            CK(paint_strokes(ctx, job.strokes, pe, pie, ps, pis, po, pio, rows, cols));
         }
         CK(rtdd_estimate_depth_batch(ctx, job.iters));                  // main.cpp:239-291, for every image
         depth_u8->resize((size_t)rows * cols);
@@ -311,6 +367,7 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
         }
         for (const Paint &p : job.paints)
             CK(rtdd_paint_image(ctx, p.x, p.y, p.label, p.radius, (uint8_t *)p_ed, pi_ed, (uint8_t *)p_scr, pi_scr, rows, cols));
+        CK(paint_strokes(ctx, job.strokes, p_ed, pi_ed, p_scr, pi_scr, p_orig, pi_orig, rows, cols));
         CK(rtdd_host_alloc(&h_scr.p, (size_t)rows * cols)); CK(rtdd_host_alloc(&h_ed.p, (size_t)rows * cols * 3));
         CK(rtdd_host_alloc(&h_u8[0].p, (size_t)rows * cols)); CK(rtdd_host_alloc(&h_u8[1].p, (size_t)rows * cols));
         CK(rtdd_download(ctx, h_scr.p, cols, p_scr, pi_scr, cols, rows));            // the host's Mats (main.cpp:160-168: decoded on the host there)
@@ -341,6 +398,14 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
                 CK(rtdd_download(ctx, h_scr.p, cols, p_scr, pi_scr, cols, rows));
                 CK(rtdd_download(ctx, h_ed.p, (size_t)cols * 3, p_ed, pi_ed, (size_t)cols * 3, rows));
             }
+            // --stroke-at / --erase-at: the host owns the pair every frame uploads, so the strokes go onto the HOST images (the frames in
+            // flight, which are still being uploaded from them, land first); after an erase the coarse levels are built afresh
+            std::vector<rtdd_stroke> now;
+            for (const LiveStroke &q : job.live_strokes) if (q.frame == n) now.push_back(q.s);
+            if (!now.empty()) {
+                while (rtdd_live_pending(ctx) > 0) { const int f = n - rtdd_live_pending(ctx); CK(rtdd_live_wait(ctx)); landed(f); }
+                if (host_strokes(now, (unsigned char *)h_scr.p, (unsigned char *)h_ed.p, job.bgr.px.data(), rows, cols)) CK(rtdd_pyramid_annotation_rebuild(ctx));
+            }
             if (rtdd_live_pending(ctx) >= 2) { const int f = n - 2; CK(rtdd_live_wait(ctx)); landed(f); }              // frame n-2's buffer is about to be reused
             CK(rtdd_live_submit_ex(ctx, (const uint8_t *)h_scr.p, cols, (const uint8_t *)h_ed.p, (size_t)cols * 3, job.iters, (uint8_t *)h_u8[n % 2].p, cols,
                                    fx, (uint8_t *)h_art[n % 2].p, (size_t)cols * 3));
@@ -365,6 +430,7 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
             }
             for (const Paint &p : job.paints)                           // main.cpp:55-57
                 CK(rtdd_paint_image(ctx, p.x, p.y, p.label, p.radius, (uint8_t *)p_ed, pi_ed, (uint8_t *)p_scr, pi_scr, rows, cols));
+            CK(paint_strokes(ctx, job.strokes, p_ed, pi_ed, p_scr, pi_scr, p_orig, pi_orig, rows, cols));
         }
         CK(rtdd_estimate_depth(ctx, job.iters));                        // main.cpp:239-291
         if (!job.refine.empty()) {                                      // extension: converge the finest level
@@ -404,6 +470,8 @@ int main(int argc, const char *argv[]) {
                                  "                    [--focus D | --focus-at X,Y] [--aperture A] (refocus)  [--haze-beta B] [--airlight b,g,r] (haze)\n"
                                  "                    [--disparity D] [--zero-parallax Z | --zero-parallax-at X,Y] [--anaglyph] (stereo)\n"
                                  "                    [--paint x,y,label,radius]... [--live N [--paint-at frame:x,y,label,radius]...] [--devices D --batch B [--sequential] [--write-all]] [--png] [--cold]\n"
+                                 "                    [--stroke x0,y0,x1,y1,label,radius[,round]]... [--erase x0,y0,x1,y1,radius[,round]]...   (segments, in command-line order, one rtdd_paint_strokes call after --paint)\n"
+                                 "                    [--stroke-at frame:x0,y0,x1,y1,label,radius[,round]]... [--erase-at frame:x0,y0,x1,y1,radius[,round]]...   (--live: in front of that frame)\n"
                                  "       rtdd_harness --convert in.(jpg|png|ppm|pgm) out.(png|ppm|pgm)   (JPEG / 8-bit PNG / PNM -> PNG / PNM, no GPU)\n"); return 0; }
     if (argc == 4 && !std::strcmp(argv[1], "--convert")) {               // file format conversion only (no GPU): JPEG / PNG / PNM -> PNG / PNM
         Pnm im;
@@ -432,6 +500,16 @@ int main(int argc, const char *argv[]) {
         else if (!std::strcmp(argv[i], "--png")) png = true;                       // DepthMap.png / ArtisticEffect.png like the reference
         else if (!std::strcmp(argv[i], "--paint")) { Paint p{0, 0, 0, 0, -1}; if (std::sscanf(next(), "%d,%d,%d,%d", &p.x, &p.y, &p.label, &p.radius) == 4) job.paints.push_back(p); }
         else if (!std::strcmp(argv[i], "--paint-at")) { Paint p{0, 0, 0, 0, 0}; if (std::sscanf(next(), "%d:%d,%d,%d,%d", &p.frame, &p.x, &p.y, &p.label, &p.radius) == 5) job.live_paints.push_back(p); }
+        else if (!std::strcmp(argv[i], "--stroke") || !std::strcmp(argv[i], "--erase")) {
+            const bool erase = argv[i][2] == 'e'; rtdd_stroke q;
+            if (!parse_stroke(next(), erase, &q, nullptr)) { std::printf("%s\n", erase ? "--erase wants x0,y0,x1,y1,radius[,round]" : "--stroke wants x0,y0,x1,y1,label,radius[,round]"); return 1; }
+            job.strokes.push_back(q);
+        }
+        else if (!std::strcmp(argv[i], "--stroke-at") || !std::strcmp(argv[i], "--erase-at")) {
+            const bool erase = argv[i][2] == 'e'; LiveStroke q;
+            if (!parse_stroke(next(), erase, &q.s, &q.frame)) { std::printf("%s\n", erase ? "--erase-at wants frame:x0,y0,x1,y1,radius[,round]" : "--stroke-at wants frame:x0,y0,x1,y1,label,radius[,round]"); return 1; }
+            job.live_strokes.push_back(q);
+        }
         else if (!std::strcmp(argv[i], "--focus")) { job.focus_depth = (float)std::atof(next()); job.focus_x = -1; }
         else if (!std::strcmp(argv[i], "--focus-at")) { if (std::sscanf(next(), "%d,%d", &job.focus_x, &job.focus_y) != 2) { std::printf("--focus-at wants X,Y\n"); return 1; } }
         else if (!std::strcmp(argv[i], "--aperture")) job.aperture = std::atof(next());

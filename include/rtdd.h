@@ -251,9 +251,45 @@ int rtdd_pyrdown_annotation(rtdd_ctx *ctx, const uint8_t *prevScribble, size_t p
                             uint8_t *currScribble, size_t currScribblePitch,
                             uint8_t *currEdited, size_t currEditedPitch, int currentRows, int currentCols);
 
-/* GPUPaintImage -- src/GPUImageProcessing.cu:51-70,93-101 (square brush, integer radius/2). */
+/* GPUPaintImage -- src/GPUImageProcessing.cu:51-70,93-101 (square brush, integer radius/2).  A NEGATIVE scribbleRadius paints nothing
+ * and returns RTDD_OK: the brush's bounding box [x - r/2, x + r/2] is then empty (an accident of the arithmetic, kept because callers may
+ * rely on it; the reference's kernel tests the same empty interval).  rtdd_paint_strokes below refuses one instead. */
 int rtdd_paint_image(rtdd_ctx *ctx, int x, int y, int scribbleColor, int scribbleRadius,
                      uint8_t *edited, size_t editedPitch, uint8_t *scribble, size_t scribblePitch, int rows, int cols);
+
+/* Brush strokes and an eraser (extension; no reference behaviour).  Added after ABI version 230 without a version bump, like the aimed
+ * depth effects below: a host finds rtdd_paint_strokes and rtdd_pyramid_annotation_rebuild by symbol.
+ * `count` segments in ONE call, applied IN ARRAY ORDER: the last stroke that covers a pixel decides it, as `count` calls one after the
+ * other would.  A mouse drag event maps onto one call: the positions since the previous event as a polyline of segments.
+ * Coverage of pixel p by a stroke, in exact integer arithmetic, with d = p1 - p0, v = p - p0, h = radius / 2 (C division; `radius` is the
+ * reference's scribbleRadius, a DIAMETER):
+ *   square: p lies in the Minkowski sum of the segment and [-h, h]^2:  min(x0,x1) - h <= px <= max(x0,x1) + h, the same in y, and
+ *           |dx vy - dy vx| <= h (|dx| + |dy|).  For p0 == p1 this is GPUPaintImage's test (src/GPUImageProcessing.cu:59-60).
+ *   round:  4 dist^2(p, segment) <= radius^2, without a division: with t = v.d, dd = d.d -- t <= 0: 4 |v|^2 <= radius^2;
+ *           t >= dd: 4 |p - p1|^2 <= radius^2; otherwise (2 (dx vy - dy vx))^2 <= radius^2 dd.
+ * A painted pixel (label 0..255) gets edited = (label, label, label), scribble = 255, as GPUPaintImage; an erased pixel
+ * (label RTDD_STROKE_ERASE) gets edited = original at that pixel, scribble = 0.  Pixels no stroke covers are not written.
+ * `strokes` is a HOST array, read before the call returns (the host may reuse it at once); the call is otherwise stream-ordered and
+ * asynchronous like rtdd_paint_image.  The kernel runs over the strokes' bounding box only, 256 strokes per launch.
+ * Refused on the host (RTDD_ERR_INVALID), before any launch: null strokes with count > 0; count < 0 or count > 4096; the null / pitch /
+ * size rules of rtdd_paint_image; rows or cols above 32768; a radius outside [0, 1024]; an unknown brush; a label outside [-1, 255]; an
+ * erasing stroke with original == NULL (or an original pitch smaller than a row); an endpoint coordinate outside [-32768, 32767] (the
+ * domain the coverage test is exact on).  count == 0 is RTDD_OK and launches nothing.  A retired level-0 pointer of live mode:
+ * RTDD_ERR_STATE, as for rtdd_paint_image.
+ * On the pyramid's own level-0 RTDD_IMG_SCRIBBLE / RTDD_IMG_EDITED pair the call notes the change itself, and asks for
+ * rtdd_pyramid_annotation_rebuild when at least one stroke erases. */
+enum rtdd_brush { RTDD_BRUSH_SQUARE = 0, RTDD_BRUSH_ROUND = 1 };
+#define RTDD_STROKE_ERASE (-1)
+typedef struct rtdd_stroke {
+    int x0, y0, x1, y1;             /* the segment, pixel coordinates; may lie outside the image; x0 == x1 && y0 == y1: a stamp */
+    int radius;                     /* the reference's scribbleRadius (a DIAMETER: half-width radius / 2, C division) */
+    int brush;                      /* enum rtdd_brush */
+    int label;                      /* 0..255: paint that depth label; RTDD_STROKE_ERASE: remove the annotation */
+} rtdd_stroke;
+int rtdd_paint_strokes(rtdd_ctx *ctx, const rtdd_stroke *strokes /* HOST array */, int count,
+                       uint8_t *edited, size_t editedPitch, uint8_t *scribble, size_t scribblePitch,
+                       const uint8_t *original, size_t originalPitch, /* may be NULL when no stroke erases */
+                       int rows, int cols);
 
 /* ---- depth effects (include/GPUDepthEffect.h:4-9) ------------------------------------------ */
 
@@ -369,10 +405,26 @@ int rtdd_pyramid_image(rtdd_ctx *ctx, int kind, int level, void **ptr, size_t *p
 /* The coarse annotation levels (GPUPyrDownAnnotation, src/main.cpp:249-253) and the coarsest level's injection (:257-259) are brought up
  * to date by the first rtdd_estimate_depth after the annotation changed, not by every estimate (they depend on nothing else, the
  * down-sampling only ever adds and the solver never moves a Dirichlet pixel: same images, same bits).  Every entry point of this
- * library that writes RTDD_IMG_SCRIBBLE / RTDD_IMG_EDITED (set_image, set_annotation, rtdd_paint_image, rtdd_pyrdown_annotation,
- * rtdd_upload) notes the change itself; a caller that writes those images, or the coarsest RTDD_IMG_DEPTH, through the raw
+ * library that writes RTDD_IMG_SCRIBBLE / RTDD_IMG_EDITED (set_image, set_annotation, rtdd_paint_image, rtdd_paint_strokes,
+ * rtdd_pyrdown_annotation, rtdd_upload) notes the change itself; a caller that writes those images, or the coarsest RTDD_IMG_DEPTH, through the raw
  * pointers by other means says so with this call. */
 int rtdd_pyramid_annotation_changed(rtdd_ctx *ctx);
+/* rtdd_pyramid_annotation_changed, and in addition: labels were REMOVED.  The coarse levels only ever accumulate (above), so a level-0
+ * pixel cleared through the raw pointers, or a live frame that uploads a pair with fewer labels than the frame before, would leave its old
+ * label as a Dirichlet value on every coarse level.  After this call the next estimate builds the coarse RTDD_IMG_SCRIBBLE /
+ * RTDD_IMG_EDITED levels AS IF THEY HAD BEEN ALL ZERO (their state after rtdd_pyramid_create / _set_image) before the down-sampling of
+ * src/main.cpp:249-253 and the coarsest injection (:257): one launch that stores every coarse pixel, every image of a batched pyramid,
+ * anything written into the coarse levels by other means included.  RTDD_IMG_DEPTH is left alone: the coarsest level keeps its last result
+ * as the warm start (the reference's behaviour between frames), erased pixels are simply free again.  A live host that erased on its side
+ * calls this before the rtdd_live_submit that uploads the reduced pair; an erasing rtdd_paint_strokes on the pyramid's own images calls
+ * it itself.  Every other call accumulates, as before.
+ * Healing (RTDD_ERR_TIMEOUT): an estimate or live frame that rebuilt is run again WITH the rebuild, from the annotation pair it ran on, and
+ * the accumulating frames run again behind it add their levels again -- a rebuilt frame's Dirichlet pixels are its own on every level,
+ * whatever a newer frame in flight has added since, and with one frame in flight the replayed bits are the first run's.  (With a newer
+ * frame in flight, that frame's labels may still sit in the coarsest RTDD_IMG_DEPTH as the warm-start values of pixels the older frame
+ * leaves free; accumulating frames that are run again with no rebuilt frame in front of them may see a newer frame's coarse strokes, as
+ * noted at rtdd_live_submit.) */
+int rtdd_pyramid_annotation_rebuild(rtdd_ctx *ctx);
 /* src/main.cpp:239-291; asynchronous; results in RTDD_IMG_DEPTH (all levels) and RTDD_IMG_DEPTH_U8 */
 int rtdd_estimate_depth(rtdd_ctx *ctx, int maxIterations);
 /* Live mode: one frame of src/main.cpp:232-295 as the reference clocks it -- upload of the host's scribble and edited images
@@ -389,7 +441,7 @@ int rtdd_estimate_depth(rtdd_ctx *ctx, int maxIterations);
  * RTDD_IMG_DEPTH_U8 on the device as after rtdd_estimate_depth.  No staging copies: an uploaded annotation pair BECOMES the pyramid's
  * level-0 RTDD_IMG_SCRIBBLE / RTDD_IMG_EDITED -- pointers obtained from rtdd_pyramid_image for those two images are good until the
  * next rtdd_live_submit that uploads: ask again after it (every other image keeps its address; a library call handed such a retired
- * pointer -- rtdd_paint_image, rtdd_upload, rtdd_convert_to_float, rtdd_pyrdown_annotation -- fails with RTDD_ERR_STATE instead of
+ * pointer -- rtdd_paint_image, rtdd_paint_strokes, rtdd_upload, rtdd_convert_to_float, rtdd_pyrdown_annotation -- fails with RTDD_ERR_STATE instead of
  * writing a buffer no estimate reads). */
 int rtdd_live_submit(rtdd_ctx *ctx, const uint8_t *hostScribble, size_t scribblePitch, const uint8_t *hostEdited, size_t editedPitch,
                      int maxIterations, uint8_t *hostDepthU8, size_t depthPitch);

@@ -52,10 +52,13 @@ C_ABI_SYMBOLS = [
     "rtdd_live_submit", "rtdd_live_wait", "rtdd_live_pending", "rtdd_host_alloc", "rtdd_host_free",
     "rtdd_pyramid_create_batch", "rtdd_pyramid_select", "rtdd_pyramid_batch", "rtdd_estimate_depth_batch", "rtdd_pyramid_level_info", "rtdd_live_submit_ex",
     "rtdd_simulate_refocus", "rtdd_simulate_haze_ex", "rtdd_simulate_stereo",
+    "rtdd_paint_strokes", "rtdd_pyramid_annotation_rebuild",
 ]
 IMG_ORIGINAL, IMG_GRAY, IMG_SCRIBBLE, IMG_EDITED, IMG_DEPTH, IMG_DEPTH_U8, IMG_ARTISTIC = range(7)
 EFFECT_NONE, EFFECT_DEFOCUS, EFFECT_DESATURATION, EFFECT_HAZE = range(4)
 STEREO_VIEW, STEREO_ANAGLYPH = 0, 1           # rtdd_simulate_stereo's modes
+BRUSH_SQUARE, BRUSH_ROUND = 0, 1              # rtdd_stroke.brush
+STROKE_ERASE = -1                             # rtdd_stroke.label: remove the annotation
 # Itanium-mangled names of the reference's ten free functions
 DROPIN_SYMBOLS = [
     "_Z23GPUAllocateDeviceMemoryiii", "_Z19GPUFreeDeviceMemoryi", "_Z14GPULoadWeightsf",
@@ -82,6 +85,11 @@ class SolveInfo(C.Structure):
     def describe(self):
         return (f"kernel {self.kernel} tile {self.tile} depth {self.temporal_depth} persistent {self.persistent} contract {self.fp_contract} "
                 f"launches {self.launches} iterations {self.iterations} cycles {self.cycles} residual {self.residual:.3g}")
+
+
+class Stroke(C.Structure):
+    """rtdd_stroke: the segment (x0, y0)-(x1, y1), `radius` (the reference's scribbleRadius: a diameter), BRUSH_*, label 0..255 or STROKE_ERASE."""
+    _fields_ = [("x0", C.c_int), ("y0", C.c_int), ("x1", C.c_int), ("y1", C.c_int), ("radius", C.c_int), ("brush", C.c_int), ("label", C.c_int)]
 
 
 class Profile(C.Structure):
@@ -288,6 +296,14 @@ class Context:
         self._check(lib().rtdd_paint_image(self._h, C.c_int(x), C.c_int(y), C.c_int(scribbleColor), C.c_int(scribbleRadius),
                                            e, ep, s, sp, C.c_int(rows), C.c_int(cols)))
 
+    def paint_strokes(self, strokes, edited, scribble, rows, cols, original=None):
+        """rtdd_paint_strokes: `strokes` (Stroke objects or 7-tuples x0, y0, x1, y1, radius, brush, label) in order, one call; `original`
+        is needed when a stroke erases."""
+        arr = (Stroke * max(len(strokes), 1))(*[q if isinstance(q, Stroke) else Stroke(*q) for q in strokes])
+        e, ep = _img(edited); s, sp = _img(scribble)
+        o, op = _img(original) if original is not None else (None, C.c_size_t(0))
+        self._check(lib().rtdd_paint_strokes(self._h, arr, C.c_int(len(strokes)), e, ep, s, sp, o, op, C.c_int(rows), C.c_int(cols)))
+
     # ---- include/GPUDepthEffect.h
     def GPUSimulateDefocus(self, originalImage, depthImage, artisticImage, rows, cols):
         o, op = _img(originalImage); d, dp = _img(depthImage); a, ap = _img(artisticImage)
@@ -359,6 +375,10 @@ class Context:
 
     def pyramid_annotation_changed(self):
         self._check(lib().rtdd_pyramid_annotation_changed(self._h))
+
+    def pyramid_annotation_rebuild(self):
+        """Labels were removed from the level-0 annotation: the next estimate builds the coarse levels afresh instead of adding to them."""
+        self._check(lib().rtdd_pyramid_annotation_rebuild(self._h))
 
     def pyramid_image(self, kind, level=0):
         """(ptr, pitch_bytes, rows, cols) of a context-owned pyramid image."""

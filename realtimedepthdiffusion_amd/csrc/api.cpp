@@ -208,6 +208,7 @@ int check_persistent_status(rtdd_ctx *ctx, bool in_solve) {
             "synchronisation are invalid");
     }
     ctx->healing = true;
+    ctx->heal_rebuilt = false;
     int rc = RTDD_OK;
     for (size_t i = first; i < ops.size() && rc == RTDD_OK; i++) rc = replay(ctx, ops[i], i == first ? failed_seq : 0);
     if (rc == RTDD_OK) {
@@ -858,6 +859,33 @@ int rtdd_paint_image(rtdd_ctx *ctx, int x, int y, int scribbleColor, int scribbl
     DeviceGuard g(ctx->device);
     { const int rc_ = pyramid_note_write(ctx, scribble, edited); if (rc_ != RTDD_OK) return rc_; }
     return launch_paint(ctx, x, y, scribbleColor, scribbleRadius, edited, editedPitch, scribble, scribblePitch, rows, cols);
+}
+
+int rtdd_paint_strokes(rtdd_ctx *ctx, const rtdd_stroke *strokes, int count, uint8_t *edited, size_t editedPitch, uint8_t *scribble,
+                       size_t scribblePitch, const uint8_t *original, size_t originalPitch, int rows, int cols) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    REQUIRE(ctx, edited && scribble, "null image pointer");
+    REQUIRE(ctx, rows >= 0 && cols >= 0, "negative size");
+    REQUIRE(ctx, rows <= 32768 && cols <= 32768, "image larger than 32768 pixels in a direction");
+    REQUIRE(ctx, count >= 0 && count <= 4096, "count outside [0, 4096]");
+    REQUIRE(ctx, strokes || count == 0, "null stroke array");
+    bool erases = false;
+    for (int i = 0; i < count; i++) {
+        const rtdd_stroke &q = strokes[i];
+        for (int v : {q.x0, q.y0, q.x1, q.y1}) REQUIRE(ctx, v >= -32768 && v <= 32767, "stroke endpoint outside [-32768, 32767]");
+        REQUIRE(ctx, q.radius >= 0 && q.radius <= 1024, "stroke radius outside [0, 1024]");
+        REQUIRE(ctx, q.brush == RTDD_BRUSH_SQUARE || q.brush == RTDD_BRUSH_ROUND, "unknown brush");
+        REQUIRE(ctx, q.label >= RTDD_STROKE_ERASE && q.label <= 255, "stroke label outside [-1, 255]");
+        erases = erases || q.label == RTDD_STROKE_ERASE;
+    }
+    REQUIRE(ctx, !erases || original, "an erasing stroke needs the original image");
+    if (rows == 0 || cols == 0 || count == 0) return RTDD_OK;
+    REQUIRE(ctx, editedPitch >= (size_t)cols * 3 && scribblePitch >= (size_t)cols && (!erases || originalPitch >= (size_t)cols * 3),
+        "pitch smaller than a row");
+    DeviceGuard g(ctx->device);
+    // (an eraser on the pyramid's own level-0 pair: the coarse levels, which otherwise only accumulate, are built afresh by the next estimate)
+    { const int rc_ = pyramid_note_write(ctx, scribble, edited, erases); if (rc_ != RTDD_OK) return rc_; }
+    return launch_paint_strokes(ctx, strokes, count, edited, editedPitch, scribble, scribblePitch, original, originalPitch, rows, cols);
 }
 
 // ---- depth effects -------------------------------------------------------------------------------

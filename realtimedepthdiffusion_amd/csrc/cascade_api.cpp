@@ -27,6 +27,9 @@ struct Pyramid {
     // GPUPyrDownAnnotation only ever adds, SURVEY A.8, and the solver never moves a Dirichlet pixel): they are brought up to date
     // by the first estimate after the annotation changed, not by every estimate.
     bool annotation_dirty = true;         // (of ANY image of a batch: bringing an up-to-date image up to date again changes nothing)
+    // rtdd_pyramid_annotation_rebuild / an erasing rtdd_paint_strokes: labels were removed, so the next estimate builds the coarse levels
+    // as if they had been all zero instead of adding to them (every image of a batch: a rebuilt image that lost nothing is what it was)
+    bool annotation_rebuild = false;
     int images = 1, sel = 0;              // batch size; the image the single-image entry points address (rtdd_pyramid_select)
     std::vector<rtdd_solve_info> level_info;      // what the most recent estimate ran per level (rtdd_pyramid_level_info)
     std::vector<int> level_launch_images;
@@ -145,10 +148,11 @@ int pyramid_check_read(rtdd_ctx *ctx, const void *a, const void *b) {
     if (ctx->pyr && (stale_live_pointer(ctx->pyr, a) || stale_live_pointer(ctx->pyr, b))) return fail(ctx, RTDD_ERR_STATE, kStaleText);
     return RTDD_OK;
 }
-int pyramid_note_write(rtdd_ctx *ctx, const void *scribble, const void *edited) {
+int pyramid_note_write(rtdd_ctx *ctx, const void *scribble, const void *edited, bool erases) {
     Pyramid *p = ctx->pyr;
     if (!p) return RTDD_OK;
     if (stale_live_pointer(p, scribble) || stale_live_pointer(p, edited)) return fail(ctx, RTDD_ERR_STATE, kStaleText);
+    if (erases && p->levels > 0 && (inside(p->scribble[0], scribble) || inside(p->edited[0], edited))) p->annotation_rebuild = true;
     for (int l = 0; l < p->levels; l++)
         if (inside(p->scribble[l], scribble) || inside(p->edited[l], edited) || inside(p->scribble[l], edited)
             || inside(p->edited[l], scribble))
@@ -158,6 +162,23 @@ int pyramid_note_write(rtdd_ctx *ctx, const void *scribble, const void *edited) 
     // estimate inject again
     if (p->levels > 0 && (inside(p->depth[p->levels - 1], scribble) || inside(p->depth[p->levels - 1], edited))) p->annotation_dirty = true;
     return RTDD_OK;
+}
+
+// src/main.cpp:249-259: the P - 1 coarse annotation levels and the coarsest level's injection, one launch (image_kernels.hip), for every
+// image of the batch whatever the estimate covers: the flags are one per batch, the down-sampling only ever adds (an up-to-date image
+// stays as it is) and a rebuild of an image that lost no label gives what it held.
+static int annotation_pyramid(rtdd_ctx *ctx, Pyramid *p, bool rebuild) {
+    const int P = p->levels;
+    DeviceGuard g(ctx->device);
+    uint8_t *sc[32], *ed[32]; size_t sp[32], ep[32], zs[32], ze[32]; int lr[32], lc[32];
+    if (P > 12) return fail(ctx, RTDD_ERR_INVALID, "more than 12 pyramid levels");
+    for (int l = 0; l < P; l++) {
+        sc[l] = (uint8_t *)p->scribble[l].ptr; ed[l] = (uint8_t *)p->edited[l].ptr; sp[l] = p->scribble[l].pitch;
+        ep[l] = p->edited[l].pitch;
+        zs[l] = p->scribble[l].stride; ze[l] = p->edited[l].stride; lr[l] = p->edited[l].rows; lc[l] = p->edited[l].cols;
+    }
+    return launch_annotation_pyramid(ctx, P, sc, sp, zs, ed, ep, ze, lr, lc, (float *)p->depth[P - 1].ptr, p->depth[P - 1].pitch,
+                                     p->depth[P - 1].stride, p->images, rebuild);
 }
 
 static int alloc_image(rtdd_ctx *ctx, Image &im, int rows, int cols, int elem, int fill, int images = 1) {
@@ -360,6 +381,13 @@ int rtdd_pyramid_level_info(rtdd_ctx *ctx, int level, rtdd_solve_info *info, int
     return RTDD_OK;
 }
 
+int rtdd_pyramid_annotation_rebuild(rtdd_ctx *ctx) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    if (!ctx->pyr) return fail(ctx, RTDD_ERR_STATE, "rtdd_pyramid_create has not been called");
+    ctx->pyr->annotation_dirty = true; ctx->pyr->annotation_rebuild = true;
+    return RTDD_OK;
+}
+
 int rtdd_pyramid_annotation_changed(rtdd_ctx *ctx) {
     if (!ctx) return RTDD_ERR_INVALID;
     if (!ctx->pyr) return fail(ctx, RTDD_ERR_STATE, "rtdd_pyramid_create has not been called");
@@ -376,24 +404,15 @@ static int estimate_submit(rtdd_ctx *ctx, int maxIterations, unsigned long long 
     const int P = p->levels;
     const int first = whole_batch ? 0 : p->sel, n = whole_batch ? p->images : 1;
     int rc = RTDD_OK;
+    int annotation = PendingOp::kAnnotationNone;
     if (p->annotation_dirty) {
-        // every image of the batch in one launch per step, whatever the estimate covers: the flag is one for the whole batch, and the
-        // down-sampling only ever adds (an up-to-date image stays as it is)
-        DeviceGuard g(ctx->device);
-        uint8_t *sc[32], *ed[32]; size_t sp[32], ep[32], zs[32], ze[32]; int lr[32], lc[32];
-        if (P > 12) return fail(ctx, RTDD_ERR_INVALID, "more than 12 pyramid levels");
-        for (int l = 0; l < P; l++) {
-            sc[l] = (uint8_t *)p->scribble[l].ptr; ed[l] = (uint8_t *)p->edited[l].ptr; sp[l] = p->scribble[l].pitch;
-            ep[l] = p->edited[l].pitch;
-            zs[l] = p->scribble[l].stride; ze[l] = p->edited[l].stride; lr[l] = p->edited[l].rows; lc[l] = p->edited[l].cols;
-        }
-        // src/main.cpp:249-259: the P - 1 annotation levels and the coarsest level's injection, one launch (image_kernels.hip)
-        rc = launch_annotation_pyramid(ctx, P, sc, sp, zs, ed, ep, ze, lr, lc, (float *)p->depth[P - 1].ptr, p->depth[P - 1].pitch,
-                                       p->depth[P - 1].stride, p->images);
+        rc = annotation_pyramid(ctx, p, p->annotation_rebuild);
         if (rc != RTDD_OK) return rc;
-        p->annotation_dirty = false;
+        annotation = p->annotation_rebuild ? PendingOp::kAnnotationRebuilt : PendingOp::kAnnotationAccumulated;
+        p->annotation_dirty = false; p->annotation_rebuild = false;
     }
     PendingOp op;
+    op.annotation = annotation;
     op.kind = PendingOp::kEstimate; op.opt = ctx->opt; op.maxIterations = maxIterations;
     op.batch_first = first; op.batch_n = n; op.live = live;
     rc = estimate_levels(ctx, maxIterations, P - 1, op.level_seq, first, n, live);
@@ -757,6 +776,13 @@ int estimate_replay(rtdd_ctx *ctx, const PendingOp &op, int failed_seq) {
     // pyramid ends up naming its images)
     if (op.live.scribble) { p->scribble[0].ptr = op.live.scribble; p->edited[0].ptr = op.live.edited; }
     if (op.live.effect && op.live.artistic) p->artistic.ptr = op.live.artistic;
+    // an estimate that rebuilt the coarse annotation levels rebuilds them again, from the pair set just above: a newer frame in flight
+    // has added its strokes to them since.  The accumulating estimates run again behind it then add theirs again.
+    if (op.annotation == PendingOp::kAnnotationRebuilt || (op.annotation == PendingOp::kAnnotationAccumulated && ctx->heal_rebuilt)) {
+        const int rc_ = annotation_pyramid(ctx, p, op.annotation == PendingOp::kAnnotationRebuilt);
+        if (rc_ != RTDD_OK) return rc_;
+        ctx->heal_rebuilt = true;
+    }
     int rc = from >= 0 ? estimate_levels(ctx, op.maxIterations, from, nullptr, op.batch_first, op.batch_n, op.live) : RTDD_OK;
     if (rc == RTDD_OK && op.live.effect) rc = live_effect(ctx, op.live);
     return rc;

@@ -1,6 +1,8 @@
 // image_kernels.hip -- annotation-side passes: Dirichlet injection, 2x annotation downsample,
 // square brush.  All three are tiny, HBM-latency-bound byte kernels; one wave covers 64
 // consecutive pixels of a row so mask/depth accesses coalesce.
+#include <algorithm>
+
 #include "rtdd_internal.hpp"
 
 namespace rtdd {
@@ -180,6 +182,113 @@ __global__ __launch_bounds__(256) void k_annotation_pyramid_lds(AnnotationPyrami
     }
 }
 
+// The annotation pyramid REBUILT (rtdd_pyramid_annotation_rebuild, an erasing rtdd_paint_strokes): the coarse levels as if they had been
+// all zero before the down-sampling.  Same ownership as k_annotation_pyramid -- a workgroup owns the footprint of its kApB x kApB coarsest
+// pixels on every level, and the footprints tile every level completely and disjointly -- so each workgroup simply stores EVERY pixel of
+// its footprint, hit or not (scribble 255 / 0; edited (winner, 0, 0) / (0, 0, 0): channels 1 and 2 of a coarse edited image are never
+// written by GPUPyrDownAnnotation and are zero after creation), and never reads the old coarse contents: no memsets in front, one launch.
+__global__ __launch_bounds__(256) void k_annotation_rebuild(AnnotationPyramid A) {
+    const int P = A.levels, top = P - 1;
+    const size_t z = blockIdx.z;
+    for (int l = 1; l <= top; l++) {
+        const int f = 1 << (top - l);
+        const int xa = max((int)blockIdx.x * kApB * f - (f - 1), 0), xb = min(((int)blockIdx.x * kApB + kApB - 1) * f, A.cols[l] - 1);
+        const int ya = max((int)blockIdx.y * kApB * f - (f - 1), 0), yb = min(((int)blockIdx.y * kApB + kApB - 1) * f, A.rows[l] - 1);
+        const int w = xb - xa + 1, h = yb - ya + 1;
+        if (w > 0 && h > 0) {
+            const uint8_t *ps = A.scribble[l - 1] + z * A.zs[l - 1], *pe = A.edited[l - 1] + z * A.ze[l - 1];
+            uint8_t *cs = A.scribble[l] + z * A.zs[l], *ce = A.edited[l] + z * A.ze[l];
+            const int prows = A.rows[l - 1], pcols = A.cols[l - 1];
+            for (int i = threadIdx.x; i < w * h; i += 256) {
+                const int x = xa + i % w, y = ya + i / w;
+                int hit = -1;
+#pragma unroll
+                for (int jj = -1; jj <= 0; jj++)
+#pragma unroll
+                    for (int ii = -1; ii <= 0; ii++) {
+                        const int px = 2 * x + ii, py = 2 * y + jj;
+                        if (px >= 0 && py >= 0 && px < pcols && py < prows && ps[(size_t)py * A.sp[l - 1] + px] == 255)
+                            hit = pe[(size_t)py * A.ep[l - 1] + 3 * px];
+                    }
+                cs[(size_t)y * A.sp[l] + x] = hit >= 0 ? 255 : 0;
+                uint8_t *e = ce + (size_t)y * A.ep[l] + 3 * x;
+                e[0] = (uint8_t)(hit >= 0 ? hit : 0); e[1] = 0; e[2] = 0;
+            }
+        }
+        __syncthreads();                                             // the level is read back by this workgroup only
+    }
+    const int x = (int)blockIdx.x * kApB + (int)(threadIdx.x % kApB), y = (int)blockIdx.y * kApB + (int)(threadIdx.x / kApB);
+    if (threadIdx.x < kApB * kApB && A.depth && x < A.cols[top] && y < A.rows[top]) {
+        const uint8_t *m = A.scribble[top] + z * A.zs[top], *e = A.edited[top] + z * A.ze[top];
+        if (m[(size_t)y * A.sp[top] + x] == 255)
+            ((float *)((char *)A.depth + z * A.zd + (size_t)y * A.dp))[x] = (float)e[(size_t)y * A.ep[top] + 3 * x];
+    }
+}
+
+// ... and with the chain in LDS: only the level-0 footprint is loaded (one memory round trip, a fifth of the accumulating kernel's
+// loads: the old coarse state is not wanted), the levels are walked in LDS and every pixel of every coarse footprint is stored.
+template <int TOP>
+__global__ __launch_bounds__(256) void k_annotation_rebuild_lds(AnnotationPyramid A) {
+    constexpr int kN0 = kApB << TOP, kE0 = (kN0 * kN0 + 255) / 256;
+    constexpr int kTotal = (4 * kN0 * kN0 - kApB * kApB) / 3;
+    __shared__ short map[kTotal];
+    const int tid = threadIdx.x;
+    const size_t z = blockIdx.z;
+    {
+        const int x0 = (int)blockIdx.x * kN0 - ((1 << TOP) - 1), y0 = (int)blockIdx.y * kN0 - ((1 << TOP) - 1);
+        const uint8_t *ps = A.scribble[0] + z * A.zs[0], *pe = A.edited[0] + z * A.ze[0];
+        int flag[kE0], val[kE0];
+#pragma unroll
+        for (int k = 0; k < kE0; k++) {
+            const int i = tid + 256 * k, lx = i & (kN0 - 1), ly = i / kN0, x = x0 + lx, y = y0 + ly;
+            const bool in = i < kN0 * kN0 && x >= 0 && y >= 0 && x < A.cols[0] && y < A.rows[0];
+            const int xc = in ? x : 0, yc = in ? y : 0;
+            flag[k] = in ? ps[(size_t)yc * A.sp[0] + xc] : 0; val[k] = pe[(size_t)yc * A.ep[0] + 3 * xc];
+        }
+#pragma unroll
+        for (int k = 0; k < kE0; k++) {
+            const int i = tid + 256 * k;
+            if (i < kN0 * kN0) map[i] = (short)(flag[k] == 255 ? val[k] : -1);
+        }
+    }
+    __syncthreads();
+    int poff = 0;
+#pragma unroll
+    for (int l = 1; l <= TOP; l++) {
+        const int f = 1 << (TOP - l), n = kApB * f, pn = 2 * n, coff = poff + pn * pn;
+        const int x0 = (int)blockIdx.x * kApB * f - (f - 1), y0 = (int)blockIdx.y * kApB * f - (f - 1);
+        uint8_t *cs = A.scribble[l] + z * A.zs[l], *ce = A.edited[l] + z * A.ze[l];
+#pragma unroll
+        for (int k = 0; k < kE0; k++) {
+            if (k * 256 >= n * n) continue;
+            const int i = tid + 256 * k;
+            if (i < n * n) {
+                const int lx = i & (n - 1), ly = i / n, x = x0 + lx, y = y0 + ly;
+                const short *q = map + poff + (2 * ly) * pn + 2 * lx;
+                int hit = -1;                                        // scan order py outer, px inner, the last hit wins (k_pyrdown_annotation)
+                if (q[0] >= 0) hit = q[0];
+                if (q[1] >= 0) hit = q[1];
+                if (q[pn] >= 0) hit = q[pn];
+                if (q[pn + 1] >= 0) hit = q[pn + 1];
+                const bool in = x >= 0 && y >= 0 && x < A.cols[l] && y < A.rows[l];
+                map[coff + i] = (short)(in ? hit : -1);              // (a pixel outside the level hands nothing on, as in the global chain)
+                if (in) {
+                    cs[(size_t)y * A.sp[l] + x] = hit >= 0 ? 255 : 0;
+                    uint8_t *e = ce + (size_t)y * A.ep[l] + 3 * x;
+                    e[0] = (uint8_t)(hit >= 0 ? hit : 0); e[1] = 0; e[2] = 0;
+                }
+            }
+        }
+        __syncthreads();
+        poff = coff;
+    }
+    const int x = (int)blockIdx.x * kApB + (tid % kApB), y = (int)blockIdx.y * kApB + (tid / kApB);
+    if (tid < kApB * kApB && A.depth && x < A.cols[TOP] && y < A.rows[TOP]) {
+        const int v = map[poff + tid];
+        if (v >= 0) ((float *)((char *)A.depth + z * A.zd + (size_t)y * A.dp))[x] = (float)v;
+    }
+}
+
 // paintImage (K7) -- src/GPUImageProcessing.cu:51-70.  Launched over the brush's bounding box only
 // (the reference launches the whole image and discards all but the brush).
 __global__ __launch_bounds__(256) void k_paint(int x0, int y0, int x1, int y1, int color, uint8_t *__restrict__ edited, size_t editedPitch,
@@ -190,6 +299,88 @@ __global__ __launch_bounds__(256) void k_paint(int x0, int y0, int x1, int y1, i
     uint8_t *e = edited + (size_t)y * editedPitch + 3 * x;
     e[0] = (uint8_t)color; e[1] = (uint8_t)color; e[2] = (uint8_t)color;
     scribble[(size_t)y * scribblePitch + x] = 255;
+}
+
+// rtdd_paint_strokes (extension, include/rtdd.h): up to kStrokeChunk segments per launch, painted or erased in array order.  The records
+// travel as kernel arguments (12 bytes each: no device buffer, no staging area to keep alive, nothing of the caller's read after the call
+// returns); a longer array is a sequence of launches, whose stream order is the array's order.  A workgroup owns a 64 x 16 tile of the
+// chunk's bounding box (4 pixels per thread, one wave per row as everywhere here): thread i tests stroke i's own bounding box, grown by
+// its half-width, against the tile; the survivors are compacted IN ORDER into LDS (a ballot per wave, a four-entry prefix), and every
+// pixel walks them from the last to the first and stops at the first that covers it.  All integer, exact on the whole documented domain:
+// endpoints in [-32768, 32767], pixels in [0, 32767], radius <= 1024, so inside a stroke's grown box |v| and |d| stay below 2^17, every
+// product below 2^35, and the one square that can pass 2^63 -- (2 cross)^2 -- is compared only after 2 |cross| < 2^32 (at or beyond that
+// it exceeds radius^2 * |d|^2 <= 2^54 anyway).
+constexpr int kStrokeChunk = 256, kStrokeTileW = 64, kStrokeTileH = 16;
+struct PackedStroke { uint32_t p0, p1, meta; };  // x | y << 16 (two's complement halves); radius | brush << 11 | (label + 1) << 12
+struct StrokeChunk {
+    int count, x0, y0, x1, y1;                    // strokes in this chunk; its bounding box, clipped to the image (inclusive)
+    PackedStroke s[kStrokeChunk];
+};
+
+__device__ __forceinline__ bool stroke_covers(int px, int py, int x0, int y0, int x1, int y1, int radius, int brush) {
+    const int h = radius / 2;
+    if (px < min(x0, x1) - h || px > max(x0, x1) + h || py < min(y0, y1) - h || py > max(y0, y1) + h) return false;
+    const long long dx = x1 - x0, dy = y1 - y0, vx = px - x0, vy = py - y0;
+    const long long cross = dx * vy - dy * vx;
+    const unsigned long long ac = (unsigned long long)(cross < 0 ? -cross : cross);
+    if (brush == RTDD_BRUSH_SQUARE) return ac <= (unsigned long long)h * (unsigned long long)((dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy));
+    const long long t = vx * dx + vy * dy, dd = dx * dx + dy * dy, r2 = (long long)radius * radius;
+    if (t <= 0) return 4 * (vx * vx + vy * vy) <= r2;
+    if (t >= dd) { const long long wx = px - x1, wy = py - y1; return 4 * (wx * wx + wy * wy) <= r2; }
+    const unsigned long long c2 = 2 * ac;
+    return c2 < (1ull << 32) && c2 * c2 <= (unsigned long long)r2 * (unsigned long long)dd;
+}
+
+__global__ __launch_bounds__(256) void k_paint_strokes(const StrokeChunk C, uint8_t *__restrict__ edited, size_t editedPitch,
+                                                       uint8_t *__restrict__ scribble, size_t scribblePitch,
+                                                       const uint8_t *__restrict__ original, size_t originalPitch) {
+    __shared__ int4 live[kStrokeChunk];           // the surviving strokes, unpacked: (x0 | y0 << 16, x1 | y1 << 16, radius, brush | (label + 1) << 1)
+    __shared__ int wave_count[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
+    const int tx0 = C.x0 + (int)blockIdx.x * kStrokeTileW, ty0 = C.y0 + (int)blockIdx.y * kStrokeTileH;
+    const int tx1 = min(tx0 + kStrokeTileW - 1, C.x1), ty1 = min(ty0 + kStrokeTileH - 1, C.y1);
+    // cull: stroke `tid` against this tile
+    bool keep = false;
+    int4 rec = make_int4(0, 0, 0, 0);
+    if (tid < C.count) {
+        const PackedStroke q = C.s[tid];
+        const int x0 = (int16_t)(q.p0 & 0xFFFF), y0 = (int16_t)(q.p0 >> 16), x1 = (int16_t)(q.p1 & 0xFFFF), y1 = (int16_t)(q.p1 >> 16);
+        const int radius = (int)(q.meta & 0x7FF), h = radius / 2;
+        keep = min(x0, x1) - h <= tx1 && max(x0, x1) + h >= tx0 && min(y0, y1) - h <= ty1 && max(y0, y1) + h >= ty0;
+        rec = make_int4((int)q.p0, (int)q.p1, radius, (int)(q.meta >> 11));
+    }
+    const unsigned long long mask = __ballot(keep);
+    if (lane == 0) wave_count[wave] = __popcll(mask);
+    __syncthreads();
+    int base = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; w++) { const int n = wave_count[w]; if (w < wave) base += n; total += n; }
+    if (keep) live[base + __popcll(mask & ((1ull << lane) - 1))] = rec;
+    __syncthreads();
+    if (total == 0) return;
+    const int x = tx0 + lane;
+    if (x > tx1) return;
+#pragma unroll
+    for (int k = 0; k < kStrokeTileH / 4; k++) {
+        const int y = ty0 + wave + 4 * k;
+        if (y > ty1) break;
+        for (int i = total - 1; i >= 0; i--) {
+            const int4 r = live[i];                                  // (one address for the whole wave: an LDS broadcast)
+            if (!stroke_covers(x, y, (int16_t)(r.x & 0xFFFF), (int16_t)((uint32_t)r.x >> 16), (int16_t)(r.y & 0xFFFF), (int16_t)((uint32_t)r.y >> 16),
+                               r.z, r.w & 1)) continue;
+            const int label = (r.w >> 1) - 1;                        // RTDD_STROKE_ERASE = -1
+            uint8_t *e = edited + (size_t)y * editedPitch + 3 * x;
+            if (label >= 0) {
+                e[0] = (uint8_t)label; e[1] = (uint8_t)label; e[2] = (uint8_t)label;
+                scribble[(size_t)y * scribblePitch + x] = 255;
+            } else {
+                const uint8_t *o = original + (size_t)y * originalPitch + 3 * x;
+                e[0] = o[0]; e[1] = o[1]; e[2] = o[2];
+                scribble[(size_t)y * scribblePitch + x] = 0;
+            }
+            break;                                                   // the LAST stroke covering a pixel decides it
+        }
+    }
 }
 
 // rows of `width` bytes from one pitch to another (copy_h2d / copy_d2h, rtdd_live_submit: one side is a contiguous buffer whose row length is
@@ -234,7 +425,7 @@ int launch_pyrdown_annotation(rtdd_ctx *ctx, const uint8_t *ps, size_t psp, cons
 }
 
 int launch_annotation_pyramid(rtdd_ctx *ctx, int levels, uint8_t *const *scribble, const size_t *sp, const size_t *zs, uint8_t *const *edited, const size_t *ep, const size_t *ze,
-                              const int *rows, const int *cols, float *depth, size_t dp, size_t zd, int images) {
+                              const int *rows, const int *cols, float *depth, size_t dp, size_t zd, int images, bool rebuild) {
     if (levels < 1 || levels > kApMaxLevels) return fail(ctx, RTDD_ERR_INVALID, "annotation pyramid: too many levels");
     AnnotationPyramid A{};
     A.levels = levels;
@@ -254,6 +445,16 @@ int launch_annotation_pyramid(rtdd_ctx *ctx, int levels, uint8_t *const *scribbl
     if (gx < 1 || gy < 1) return RTDD_OK;
     const dim3 grid(gx, gy, images);
     const int lds = ctx->opt.annotation_lds;
+    if (rebuild) {
+        if (lds && top == 1) hipLaunchKernelGGL(k_annotation_rebuild_lds<1>, grid, dim3(256), 0, ctx->stream, A);
+        else if (lds && top == 2) hipLaunchKernelGGL(k_annotation_rebuild_lds<2>, grid, dim3(256), 0, ctx->stream, A);
+        else if (lds && top == 3) hipLaunchKernelGGL(k_annotation_rebuild_lds<3>, grid, dim3(256), 0, ctx->stream, A);
+        else if (lds && top == 4) hipLaunchKernelGGL(k_annotation_rebuild_lds<4>, grid, dim3(256), 0, ctx->stream, A);
+        else if (lds && top == 5) hipLaunchKernelGGL(k_annotation_rebuild_lds<5>, grid, dim3(256), 0, ctx->stream, A);
+        else hipLaunchKernelGGL(k_annotation_rebuild, grid, dim3(256), 0, ctx->stream, A);
+        RTDD_LAUNCH_CHECK(ctx, "k_annotation_rebuild");
+        return RTDD_OK;
+    }
     if (lds && top == 1) hipLaunchKernelGGL(k_annotation_pyramid_lds<1>, grid, dim3(256), 0, ctx->stream, A);
     else if (lds && top == 2) hipLaunchKernelGGL(k_annotation_pyramid_lds<2>, grid, dim3(256), 0, ctx->stream, A);
     else if (lds && top == 3) hipLaunchKernelGGL(k_annotation_pyramid_lds<3>, grid, dim3(256), 0, ctx->stream, A);
@@ -272,6 +473,34 @@ int launch_paint(rtdd_ctx *ctx, int x, int y, int color, int radius, uint8_t *ed
     if (x1 < x0 || y1 < y0) return RTDD_OK;            // brush entirely outside the image (or negative radius)
     hipLaunchKernelGGL(k_paint, grid64x4(y1 - y0 + 1, x1 - x0 + 1), dim3(256), 0, ctx->stream, x0, y0, x1, y1, color, edited, editedPitch, scribble, scribblePitch);
     RTDD_LAUNCH_CHECK(ctx, "k_paint");
+    return RTDD_OK;
+}
+
+// strokes: checked by rtdd_paint_strokes (api.cpp) -- coordinates, radius, brush and label inside the packed fields' ranges
+int launch_paint_strokes(rtdd_ctx *ctx, const rtdd_stroke *strokes, int count, uint8_t *edited, size_t editedPitch, uint8_t *scribble,
+                         size_t scribblePitch, const uint8_t *original, size_t originalPitch, int rows, int cols) {
+    for (int first = 0; first < count; first += kStrokeChunk) {
+        StrokeChunk C;
+        C.count = count - first < kStrokeChunk ? count - first : kStrokeChunk;
+        int bx0 = cols, by0 = rows, bx1 = -1, by1 = -1;              // union of the strokes' boxes, clipped to the image
+        for (int i = 0; i < C.count; i++) {
+            const rtdd_stroke &q = strokes[first + i];
+            const int h = q.radius / 2;
+            const int x0 = std::max(std::min(q.x0, q.x1) - h, 0), x1 = std::min(std::max(q.x0, q.x1) + h, cols - 1);
+            const int y0 = std::max(std::min(q.y0, q.y1) - h, 0), y1 = std::min(std::max(q.y0, q.y1) + h, rows - 1);
+            if (x0 <= x1 && y0 <= y1) { bx0 = std::min(bx0, x0); bx1 = std::max(bx1, x1); by0 = std::min(by0, y0); by1 = std::max(by1, y1); }
+            C.s[i].p0 = ((uint32_t)q.x0 & 0xFFFFu) | ((uint32_t)q.y0 << 16);
+            C.s[i].p1 = ((uint32_t)q.x1 & 0xFFFFu) | ((uint32_t)q.y1 << 16);
+            C.s[i].meta = (uint32_t)q.radius | ((uint32_t)q.brush << 11) | ((uint32_t)(q.label + 1) << 12);
+        }
+        for (int i = C.count; i < kStrokeChunk; i++) C.s[i] = PackedStroke{0, 0, 0};
+        if (bx1 < bx0 || by1 < by0) continue;                        // every stroke of the chunk lies outside the image
+        bx0 &= ~63;                                                  // (a wave's 64 pixels start on a 64-pixel boundary of the row)
+        C.x0 = bx0; C.y0 = by0; C.x1 = bx1; C.y1 = by1;
+        const dim3 grid((bx1 - bx0) / kStrokeTileW + 1, (by1 - by0) / kStrokeTileH + 1);
+        hipLaunchKernelGGL(k_paint_strokes, grid, dim3(256), 0, ctx->stream, C, edited, editedPitch, scribble, scribblePitch, original, originalPitch);
+        RTDD_LAUNCH_CHECK(ctx, "k_paint_strokes");
+    }
     return RTDD_OK;
 }
 

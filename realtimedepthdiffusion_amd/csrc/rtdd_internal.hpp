@@ -153,6 +153,12 @@ struct PendingOp {
     int level_seq[32] = {};               // sequence number of level l's solve (0: the level is empty)
     int batch_first = 0, batch_n = 1;     // the images of the context's batched pyramid the estimate covers
     LiveTargets live;                     // a live frame: its annotation pair, its map's second target, its effect (scribble == nullptr: not one)
+    // what the estimate did to the coarse annotation levels in front of its solves: kAnnotationNone (they were up to date),
+    // kAnnotationAccumulated (GPUPyrDownAnnotation: only ever adds) or kAnnotationRebuilt (as if they had been all zero).  A replay of a
+    // rebuilt estimate rebuilds them again from the annotation pair it ran on, and the accumulating estimates replayed behind it add
+    // theirs again: a newer live frame's strokes, accumulated in the meantime, are gone from the older frame's Dirichlet set
+    enum : int { kAnnotationNone = 0, kAnnotationAccumulated = 1, kAnnotationRebuilt = 2 };
+    int annotation = kAnnotationNone;
     unsigned long long id = 0;            // position in the context's call order (live mode drops the confirmed prefix of the log)
     // kEffect: a depth effect queued BEHIND an unconfirmed solve (it may have read that solve's input instead of its result)
     Effect effect;
@@ -201,6 +207,7 @@ struct rtdd_ctx {
     std::vector<rtdd::PendingOp> pending;
     bool pending_overflow = false;  // more than kMaxPendingOps calls without a synchronisation: a timeout among them is reported, not healed
     bool healing = false;           // a replay is running: nothing is logged, a second timeout is final
+    bool heal_rebuilt = false;      // ... and one of the estimates run again so far has rebuilt the coarse annotation levels (PendingOp::annotation)
     bool heal_warned = false;
     int heals = 0;                  // RTDD_OPT_TIMEOUT_HEALS
     // opt.persistent is what the launchers read; persistent_wanted is what the caller asked for.  A heal switches opt.persistent off and
@@ -312,12 +319,15 @@ int launch_pyrdown_annotation(rtdd_ctx *ctx, const uint8_t *ps, size_t psp, cons
                               int images = 1, size_t zPs = 0, size_t zPe = 0, size_t zCs = 0, size_t zCe = 0);
 // the annotation pyramid of an estimate (levels 1 .. levels-1 from level 0) and the coarsest level's injection, one launch (image_kernels.hip)
 int launch_annotation_pyramid(rtdd_ctx *ctx, int levels, uint8_t *const *scribble, const size_t *sp, const size_t *zs, uint8_t *const *edited, const size_t *ep, const size_t *ze,
-                              const int *rows, const int *cols, float *depth, size_t dp, size_t zd, int images);
+                              const int *rows, const int *cols, float *depth, size_t dp, size_t zd, int images, bool rebuild = false);
 int launch_repitch(rtdd_ctx *ctx, hipStream_t stream, const void *src, size_t srcPitch, void *dst, size_t dstPitch, size_t widthBytes, int rows);
 int copy_h2d(rtdd_ctx *ctx, Bounce &b, void *dev, size_t devPitch, const void *host, size_t hostPitch, size_t widthBytes, int rows, hipStream_t stream);
 int copy_d2h(rtdd_ctx *ctx, Bounce &b, void *host, size_t hostPitch, const void *dev, size_t devPitch, size_t widthBytes, int rows, hipStream_t stream);
 int launch_paint(rtdd_ctx *ctx, int x, int y, int color, int radius, uint8_t *edited, size_t editedPitch,
                  uint8_t *scribble, size_t scribblePitch, int rows, int cols);
+// rtdd_paint_strokes: `count` checked strokes in array order, kStrokeChunk per launch (the records are kernel arguments)
+int launch_paint_strokes(rtdd_ctx *ctx, const rtdd_stroke *strokes, int count, uint8_t *edited, size_t editedPitch, uint8_t *scribble,
+                         size_t scribblePitch, const uint8_t *original, size_t originalPitch, int rows, int cols);
 
 // ---- effect_kernels.hip -------------------------------------------------------------------------
 int launch_effect(rtdd_ctx *ctx, const Effect &e);
@@ -335,7 +345,8 @@ int launch_decode_annotation(rtdd_ctx *ctx, const uint8_t *bgr, size_t bp, const
 int launch_fill_f32(rtdd_ctx *ctx, float *dst, size_t dp, int rows, int cols, float v);
 void pyramid_free(rtdd_ctx *ctx);
 // an annotation image is about to be written: one of the pyramid's?  RTDD_ERR_STATE for a level-0 pointer a live frame has retired
-int pyramid_note_write(rtdd_ctx *ctx, const void *scribble, const void *edited);
+// (erases: labels were REMOVED -- when the images are the pyramid's level-0 pair the next estimate rebuilds the coarse levels)
+int pyramid_note_write(rtdd_ctx *ctx, const void *scribble, const void *edited, bool erases = false);
 int pyramid_check_read(rtdd_ctx *ctx, const void *a, const void *b);     // ... about to be read
 
 // persistent kernels (persist_sync.hpp): reserve the launch's flag values and refresh the debug words before a persistent launch;
