@@ -7,8 +7,8 @@
 //     key 'd'  -> one depth estimate        (main.cpp:232-295)  -> <out>DepthMap.pgm     (main.cpp:306-310)
 //     key 's'  -> also the annotated image   (main.cpp:298-303)  -> <out>AnnotatedImage.ppm: the image with the scribbles painted in
 //     key 'b'/'g'/'h' -> --effect defocus|desaturation|haze     -> <out>ArtisticEffect.ppm (main.cpp:190-230, 312-316)
-//     extensions: --effect refocus [--focus D | --focus-at X,Y] [--aperture A]   (rtdd_simulate_refocus; default: focus depth 0,
-//                 aperture 0.025 = the defocus), --effect haze [--haze-beta B] [--airlight b,g,r]   (rtdd_simulate_haze_ex when either is given),
+//     extensions: --effect refocus [--focus D | --focus-at X,Y] [--aperture A] [--bokeh box|disc]   (rtdd_simulate_refocus; default: focus depth 0,
+//                 aperture 0.025 = the defocus; --bokeh disc: rtdd_simulate_lens_blur's round aperture), --effect haze [--haze-beta B] [--airlight b,g,r]   (rtdd_simulate_haze_ex when either is given),
 //                 --effect stereo --disparity D [--zero-parallax Z | --zero-parallax-at X,Y] [--anaglyph]   (rtdd_simulate_stereo; default:
 //                 zero parallax at depth 0, the view)
 //     key 't'  -> prints "Processing Time"  (main.cpp:320-322; wall clock here, the reference uses clock()); the process's one-time costs
@@ -184,6 +184,7 @@ struct Job {
     double aperture = 0.025;      // --effect refocus: --aperture, --focus / --focus-at (focus_x < 0: the depth focus_depth)
     float focus_depth = 0.0f;
     int focus_x = -1, focus_y = -1;
+    bool disc = false;            // --bokeh disc: rtdd_simulate_lens_blur with the round aperture (box, the default: rtdd_simulate_refocus)
     bool haze_ex = false;         // --haze-beta / --airlight given: rtdd_simulate_haze_ex
     float haze_beta = 2.0f;
     int air[3] = {255, 255, 255}; // b, g, r
@@ -448,6 +449,9 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
             CK(rtdd_simulate_haze_ex(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols, job.haze_beta,
                                      (uint8_t)job.air[0], (uint8_t)job.air[1], (uint8_t)job.air[2]));
         else if (job.effect == "haze") CK(rtdd_simulate_haze(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols));
+        else if (job.effect == "refocus" && job.disc)
+            CK(rtdd_simulate_lens_blur(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols, job.aperture,
+                                       job.focus_depth, job.focus_x, job.focus_y, RTDD_APERTURE_DISC));
         else if (job.effect == "refocus")
             CK(rtdd_simulate_refocus(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols, job.aperture,
                                      job.focus_depth, job.focus_x, job.focus_y));
@@ -467,7 +471,7 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
 
 int main(int argc, const char *argv[]) {
     if (argc == 1) { std::printf("Usage: rtdd_harness -i image.(jpg|png|ppm) [-a annotation.(png|pgm)] [-o prefix] [--effect defocus|desaturation|haze|refocus|stereo] [--iters N] [--refine sor|mg|auto [--tolerance T]]\n"
-                                 "                    [--focus D | --focus-at X,Y] [--aperture A] (refocus)  [--haze-beta B] [--airlight b,g,r] (haze)\n"
+                                 "                    [--focus D | --focus-at X,Y] [--aperture A] [--bokeh box|disc] (refocus)  [--haze-beta B] [--airlight b,g,r] (haze)\n"
                                  "                    [--disparity D] [--zero-parallax Z | --zero-parallax-at X,Y] [--anaglyph] (stereo)\n"
                                  "                    [--paint x,y,label,radius]... [--live N [--paint-at frame:x,y,label,radius]...] [--devices D --batch B [--sequential] [--write-all]] [--png] [--cold]\n"
                                  "                    [--stroke x0,y0,x1,y1,label,radius[,round]]... [--erase x0,y0,x1,y1,radius[,round]]...   (segments, in command-line order, one rtdd_paint_strokes call after --paint)\n"
@@ -513,6 +517,11 @@ int main(int argc, const char *argv[]) {
         else if (!std::strcmp(argv[i], "--focus")) { job.focus_depth = (float)std::atof(next()); job.focus_x = -1; }
         else if (!std::strcmp(argv[i], "--focus-at")) { if (std::sscanf(next(), "%d,%d", &job.focus_x, &job.focus_y) != 2) { std::printf("--focus-at wants X,Y\n"); return 1; } }
         else if (!std::strcmp(argv[i], "--aperture")) job.aperture = std::atof(next());
+        else if (!std::strcmp(argv[i], "--bokeh")) {
+            const std::string b = next();
+            if (b != "box" && b != "disc") { std::printf("--bokeh wants box or disc\n"); return 1; }
+            job.disc = b == "disc";
+        }
         else if (!std::strcmp(argv[i], "--disparity")) job.disparity = std::atoi(next());
         else if (!std::strcmp(argv[i], "--zero-parallax")) { job.zero_depth = (float)std::atof(next()); job.zero_x = -1; }
         else if (!std::strcmp(argv[i], "--zero-parallax-at")) { if (std::sscanf(next(), "%d,%d", &job.zero_x, &job.zero_y) != 2) { std::printf("--zero-parallax-at wants X,Y\n"); return 1; } }

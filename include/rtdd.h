@@ -310,7 +310,7 @@ int rtdd_simulate_haze(rtdd_ctx *ctx, const uint8_t *original, size_t originalPi
 
 /* ---- aimed depth effects (extensions; no reference behaviour) --------------------------------
  * Added after ABI version 230 without a version bump: a host finds them by symbol (dlsym).  The next bump of RTDD_VERSION
- * should cover them (rtdd_simulate_refocus, rtdd_simulate_haze_ex, rtdd_simulate_stereo), together with a parameterised live effect
+ * should cover them (rtdd_simulate_refocus, rtdd_simulate_lens_blur, rtdd_simulate_haze_ex, rtdd_simulate_stereo), together with a parameterised live effect
  * (rtdd_live_submit_ex takes an effect code only and knows none of them). */
 
 /* Refocus: the defocus effect sharp at a chosen depth instead of at depth 0.
@@ -331,6 +331,24 @@ int rtdd_simulate_haze(rtdd_ctx *ctx, const uint8_t *original, size_t originalPi
 int rtdd_simulate_refocus(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch,
                           const float *depth, size_t depthPitch, uint8_t *artistic, size_t artisticPitch,
                           int rows, int cols, double aperture, float focusDepth, int focusX, int focusY);
+
+/* Lens blur: refocus through a round aperture -- the window is a disc instead of a box, so out-of-focus highlights come out round.
+ *   K, f and the focus-pixel form are rtdd_simulate_refocus's, K computed on the host, the focus pixel read by the kernel when it runs.
+ *   shape RTDD_APERTURE_BOX: rtdd_simulate_refocus itself, bit for bit (the same kernels).
+ *   shape RTDD_APERTURE_DISC, per pixel (x, y): dist = fabsf(d - f) in f32, kf = (double)((float)K * dist) / 255.0, k = 0 when kf is NaN or
+ *   <= 0, 255 when kf >= 255, else (int)kf (for a depth map in [0, 255] the clamp never acts: it makes the effect total and bounded --
+ *   the disc has no fall-back path and sets no sticky state); the window is the image's pixels (px, py) with
+ *   4 * ((px - x)^2 + (py - y)^2) <= k * k, a disc of diameter k inscribed in the box's k x k -- rows dy with 4 dy^2 <= k^2, in each the
+ *   span x - w .. x + w, w = isqrt((k*k - 4*dy*dy) / 4), clipped to the image.  The centre always belongs (count >= 1); per channel
+ *   out = (uchar)(sum / count) in f32; k <= 1 gives the original pixel.  count <= 51 101 < 2^16 and the sums are < 2^24: exact.
+ * RTDD_OPT_DEFOCUS_PATH selects the disc's path as the box's (0 automatic, 1 a global table of row prefixes, 2 the tile kernel where its
+ * region fits: K / 2 <= 28); RTDD_OPT_DEFOCUS_LAST_PATH reports it.  The output does not depend on RTDD_OPT_FP_CONTRACT.  Deterministic.
+ * Refused on the host (RTDD_ERR_INVALID), before any launch: everything rtdd_simulate_refocus refuses (K > 255 included); a shape
+ * other than the two; original == artistic (not in place). */
+enum rtdd_aperture_shape { RTDD_APERTURE_BOX = 0, RTDD_APERTURE_DISC = 1 };
+int rtdd_simulate_lens_blur(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch,
+                            const float *depth, size_t depthPitch, uint8_t *artistic, size_t artisticPitch,
+                            int rows, int cols, double aperture, float focusDepth, int focusX, int focusY, int shape);
 
 /* Haze with a density and an airlight colour (GPUDepthEffect.cu:74-93 with its constants as parameters):
  *   t = exp((float)((double)(-beta * d) / 255.0)) by the same deterministic exp as rtdd_simulate_haze,

@@ -51,12 +51,13 @@ C_ABI_SYMBOLS = [
     "rtdd_pyrup_depth", "rtdd_depth_to_u8", "rtdd_upload", "rtdd_download",
     "rtdd_live_submit", "rtdd_live_wait", "rtdd_live_pending", "rtdd_host_alloc", "rtdd_host_free",
     "rtdd_pyramid_create_batch", "rtdd_pyramid_select", "rtdd_pyramid_batch", "rtdd_estimate_depth_batch", "rtdd_pyramid_level_info", "rtdd_live_submit_ex",
-    "rtdd_simulate_refocus", "rtdd_simulate_haze_ex", "rtdd_simulate_stereo",
+    "rtdd_simulate_refocus", "rtdd_simulate_haze_ex", "rtdd_simulate_stereo", "rtdd_simulate_lens_blur",
     "rtdd_paint_strokes", "rtdd_pyramid_annotation_rebuild",
 ]
 IMG_ORIGINAL, IMG_GRAY, IMG_SCRIBBLE, IMG_EDITED, IMG_DEPTH, IMG_DEPTH_U8, IMG_ARTISTIC = range(7)
 EFFECT_NONE, EFFECT_DEFOCUS, EFFECT_DESATURATION, EFFECT_HAZE = range(4)
 STEREO_VIEW, STEREO_ANAGLYPH = 0, 1           # rtdd_simulate_stereo's modes
+APERTURE_BOX, APERTURE_DISC = 0, 1            # rtdd_simulate_lens_blur's shapes
 BRUSH_SQUARE, BRUSH_ROUND = 0, 1              # rtdd_stroke.brush
 STROKE_ERASE = -1                             # rtdd_stroke.label: remove the annotation
 # Itanium-mangled names of the reference's ten free functions
@@ -323,6 +324,13 @@ class Context:
         o, op = _img(originalImage); d, dp = _img(depthImage); a, ap = _img(artisticImage)
         self._check(lib().rtdd_simulate_refocus(self._h, o, op, d, dp, a, ap, C.c_int(rows), C.c_int(cols), C.c_double(aperture),
                                                 C.c_float(focusDepth), C.c_int(focusX), C.c_int(focusY)))
+
+    def simulate_lens_blur(self, originalImage, depthImage, artisticImage, rows, cols, aperture=0.025, focusDepth=0.0, focusX=-1, focusY=-1,
+                           shape=APERTURE_DISC):
+        """Refocus through a round aperture (shape APERTURE_DISC: disc windows) or a square one (APERTURE_BOX: simulate_refocus itself)."""
+        o, op = _img(originalImage); d, dp = _img(depthImage); a, ap = _img(artisticImage)
+        self._check(lib().rtdd_simulate_lens_blur(self._h, o, op, d, dp, a, ap, C.c_int(rows), C.c_int(cols), C.c_double(aperture),
+                                                  C.c_float(focusDepth), C.c_int(focusX), C.c_int(focusY), C.c_int(shape)))
 
     def simulate_haze_ex(self, originalImage, depthImage, artisticImage, rows, cols, beta=2.0, air=(255, 255, 255)):
         """Haze with density `beta` and airlight `air` = (b, g, r)."""

@@ -10,7 +10,7 @@ cd "$(dirname "$0")/../realtimedepthdiffusion_amd/csrc"
 make -j4 >/dev/null
 FLAGS=$(make -s --no-print-directory print-cxxflags)
 OBJS=""
-for f in solver_kernels sweep_blocked rbgs_blocked multigrid image_kernels effect_kernels cascade api cascade_api dropin; do
+for f in solver_kernels sweep_blocked rbgs_blocked multigrid image_kernels effect_kernels lens_blur cascade api cascade_api dropin; do
     ext=hip; [ -f $f.cpp ] && ext=cpp
     if echo " $FILES " | grep -q " $f.$ext "; then
         /opt/rocm/bin/hipcc --offload-arch=gfx950 $FLAGS $DEFS -c $f.$ext -o $f.$NAME.o
