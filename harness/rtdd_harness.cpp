@@ -10,7 +10,10 @@
 //     extensions: --effect refocus [--focus D | --focus-at X,Y] [--aperture A] [--bokeh box|disc]   (rtdd_simulate_refocus; default: focus depth 0,
 //                 aperture 0.025 = the defocus; --bokeh disc: rtdd_simulate_lens_blur's round aperture), --effect haze [--haze-beta B] [--airlight b,g,r]   (rtdd_simulate_haze_ex when either is given),
 //                 --effect stereo --disparity D [--zero-parallax Z | --zero-parallax-at X,Y] [--anaglyph]   (rtdd_simulate_stereo; default:
-//                 zero parallax at depth 0, the view)
+//                 zero parallax at depth 0, the view),
+//                 --effect relight [--light-dir x,y,z | --light-at X,Y [--light-height H] [--light-radius R]] [--relief S] [--ambient A] [--diffuse D]
+//                 [--light-color b,g,r]   (rtdd_simulate_relight; default: a white directional light from the upper left, (-1, -1, 1), relief 2,
+//                 ambient 0.25, diffuse 1; --light-at: a point light over that pixel, anchored at its depth, height 100, radius 200)
 //     key 't'  -> prints "Processing Time"  (main.cpp:320-322; wall clock here, the reference uses clock()); the process's one-time costs
 //                 (~20 ms: code objects, first allocations) are paid by a warm-up on a context of its own first -- --cold leaves it out
 //     --paint x,y,label,radius  = a mouse drag sample (main.cpp:46-62), repeatable; --paint-at F:x,y,label,radius = the same while --live
@@ -192,6 +195,10 @@ struct Job {
     float zero_depth = 0.0f;
     int zero_x = -1, zero_y = -1;
     bool anaglyph = false;
+    // --effect relight: --light-dir (directional) or --light-at (a point light over that pixel, anchored at its depth), --light-height, --light-radius,
+    // --relief, --ambient, --diffuse, --light-color
+    rtdd_light light = {RTDD_LIGHT_DIRECTIONAL, -1.0f, -1.0f, 1.0f, 0.0f, -1, -1, 200.0f, 2.0f, 0.25f, 1.0f, 255, 255, 255};
+    float light_height = 100.0f;
     bool sequential = false;      // --sequential: a --batch as one estimate after the other (default: rtdd_estimate_depth_batch, all images in the same launches)
     bool cold = false;            // --cold: no warm-up: the first (and, without --live, only) estimate pays the one-time costs
 };
@@ -458,6 +465,11 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
         else if (job.effect == "stereo")
             CK(rtdd_simulate_stereo(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols, job.disparity,
                                     job.zero_depth, job.zero_x, job.zero_y, job.anaglyph ? RTDD_STEREO_ANAGLYPH : RTDD_STEREO_VIEW));
+        else if (job.effect == "relight") {
+            rtdd_light light = job.light;
+            if (light.kind == RTDD_LIGHT_POINT) light.z = job.light_height;
+            CK(rtdd_simulate_relight(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols, &light));
+        }
         depth_u8->resize((size_t)rows * cols);
         CK(rtdd_download(ctx, depth_u8->data(), cols, p_u8, pi_u8, cols, rows));   // main.cpp:291 (synchronises)
         if (!job.effect.empty()) { art->resize((size_t)rows * cols * 3); CK(rtdd_download(ctx, art->data(), (size_t)cols * 3, p_art, pi_art, (size_t)cols * 3, rows)); }
@@ -470,9 +482,10 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
 }
 
 int main(int argc, const char *argv[]) {
-    if (argc == 1) { std::printf("Usage: rtdd_harness -i image.(jpg|png|ppm) [-a annotation.(png|pgm)] [-o prefix] [--effect defocus|desaturation|haze|refocus|stereo] [--iters N] [--refine sor|mg|auto [--tolerance T]]\n"
+    if (argc == 1) { std::printf("Usage: rtdd_harness -i image.(jpg|png|ppm) [-a annotation.(png|pgm)] [-o prefix] [--effect defocus|desaturation|haze|refocus|stereo|relight] [--iters N] [--refine sor|mg|auto [--tolerance T]]\n"
                                  "                    [--focus D | --focus-at X,Y] [--aperture A] [--bokeh box|disc] (refocus)  [--haze-beta B] [--airlight b,g,r] (haze)\n"
                                  "                    [--disparity D] [--zero-parallax Z | --zero-parallax-at X,Y] [--anaglyph] (stereo)\n"
+                                 "                    [--light-dir x,y,z | --light-at X,Y [--light-height H] [--light-radius R]] [--relief S] [--ambient A] [--diffuse D] [--light-color b,g,r] (relight)\n"
                                  "                    [--paint x,y,label,radius]... [--live N [--paint-at frame:x,y,label,radius]...] [--devices D --batch B [--sequential] [--write-all]] [--png] [--cold]\n"
                                  "                    [--stroke x0,y0,x1,y1,label,radius[,round]]... [--erase x0,y0,x1,y1,radius[,round]]...   (segments, in command-line order, one rtdd_paint_strokes call after --paint)\n"
                                  "                    [--stroke-at frame:x0,y0,x1,y1,label,radius[,round]]... [--erase-at frame:x0,y0,x1,y1,radius[,round]]...   (--live: in front of that frame)\n"
@@ -526,6 +539,25 @@ int main(int argc, const char *argv[]) {
         else if (!std::strcmp(argv[i], "--zero-parallax")) { job.zero_depth = (float)std::atof(next()); job.zero_x = -1; }
         else if (!std::strcmp(argv[i], "--zero-parallax-at")) { if (std::sscanf(next(), "%d,%d", &job.zero_x, &job.zero_y) != 2) { std::printf("--zero-parallax-at wants X,Y\n"); return 1; } }
         else if (!std::strcmp(argv[i], "--anaglyph")) job.anaglyph = true;
+        else if (!std::strcmp(argv[i], "--light-dir")) {
+            if (std::sscanf(next(), "%f,%f,%f", &job.light.x, &job.light.y, &job.light.z) != 3) { std::printf("--light-dir wants x,y,z\n"); return 1; }
+            job.light.kind = RTDD_LIGHT_DIRECTIONAL;
+        }
+        else if (!std::strcmp(argv[i], "--light-at")) {
+            if (std::sscanf(next(), "%d,%d", &job.light.anchorX, &job.light.anchorY) != 2) { std::printf("--light-at wants X,Y\n"); return 1; }
+            job.light.kind = RTDD_LIGHT_POINT; job.light.x = (float)job.light.anchorX; job.light.y = (float)job.light.anchorY;
+        }
+        else if (!std::strcmp(argv[i], "--light-height")) job.light_height = (float)std::atof(next());
+        else if (!std::strcmp(argv[i], "--light-radius")) job.light.radius = (float)std::atof(next());
+        else if (!std::strcmp(argv[i], "--relief")) job.light.relief = (float)std::atof(next());
+        else if (!std::strcmp(argv[i], "--ambient")) job.light.ambient = (float)std::atof(next());
+        else if (!std::strcmp(argv[i], "--diffuse")) job.light.diffuse = (float)std::atof(next());
+        else if (!std::strcmp(argv[i], "--light-color")) {
+            int c[3];
+            if (std::sscanf(next(), "%d,%d,%d", &c[0], &c[1], &c[2]) != 3) { std::printf("--light-color wants b,g,r\n"); return 1; }
+            for (int k = 0; k < 3; k++) if (c[k] < 0 || c[k] > 255) { std::printf("--light-color: each of b,g,r must be 0..255\n"); return 1; }
+            job.light.colorB = (uint8_t)c[0]; job.light.colorG = (uint8_t)c[1]; job.light.colorR = (uint8_t)c[2];
+        }
         else if (!std::strcmp(argv[i], "--haze-beta")) { job.haze_beta = (float)std::atof(next()); job.haze_ex = true; }
         else if (!std::strcmp(argv[i], "--airlight")) {
             if (std::sscanf(next(), "%d,%d,%d", &job.air[0], &job.air[1], &job.air[2]) != 3) { std::printf("--airlight wants b,g,r\n"); return 1; }
@@ -535,8 +567,8 @@ int main(int argc, const char *argv[]) {
         else if (!std::strcmp(argv[i], "-h")) std::printf("Usage:\n -i input image (JPEG, 8-bit PNG, binary PPM)\n -a annotated image (8-bit PNG, binary PGM)\n");
     }
     // a live frame's sticky effect is an effect code without parameters (rtdd_live_submit_ex): the aimed effects are not available there
-    if (live > 0 && (job.effect == "refocus" || job.effect == "stereo" || (job.effect == "haze" && job.haze_ex))) {
-        std::printf("--live renders the reference's three effects only: --effect refocus, --effect stereo and --haze-beta / --airlight are not supported with --live\n");
+    if (live > 0 && (job.effect == "refocus" || job.effect == "stereo" || job.effect == "relight" || (job.effect == "haze" && job.haze_ex))) {
+        std::printf("--live renders the reference's three effects only: --effect refocus, --effect stereo, --effect relight and --haze-beta / --airlight are not supported with --live\n");
         return 1;
     }
     Pnm rgb;

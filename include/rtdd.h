@@ -310,7 +310,7 @@ int rtdd_simulate_haze(rtdd_ctx *ctx, const uint8_t *original, size_t originalPi
 
 /* ---- aimed depth effects (extensions; no reference behaviour) --------------------------------
  * Added after ABI version 230 without a version bump: a host finds them by symbol (dlsym).  The next bump of RTDD_VERSION
- * should cover them (rtdd_simulate_refocus, rtdd_simulate_lens_blur, rtdd_simulate_haze_ex, rtdd_simulate_stereo), together with a parameterised live effect
+ * should cover them (rtdd_simulate_refocus, rtdd_simulate_lens_blur, rtdd_simulate_haze_ex, rtdd_simulate_stereo, rtdd_simulate_relight), together with a parameterised live effect
  * (rtdd_live_submit_ex takes an effect code only and knows none of them). */
 
 /* Refocus: the defocus effect sharp at a chosen depth instead of at depth 0.
@@ -379,6 +379,56 @@ enum rtdd_stereo_mode { RTDD_STEREO_VIEW = 0, RTDD_STEREO_ANAGLYPH = 1 };
 int rtdd_simulate_stereo(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch,
                          const float *depth, size_t depthPitch, uint8_t *artistic, size_t artisticPitch,
                          int rows, int cols, int disparity, float zeroParallaxDepth, int zeroX, int zeroY, int mode);
+
+/* Relight: the depth map read as a SURFACE and lit by one light -- a directional one, or a point light anchored to the surface
+ * ("light this object") that falls off with distance.  Coordinates: x right, y down, z towards the viewer; the surface is
+ * z(x, y) = relief * (255 - d'), depth 0 near, 255 far as haze and stereo read it.  Every operation below is one f32 operation, rounded
+ * once, NONE fused, in the order written; sqrtf and / are IEEE correctly rounded; f32 denormals are kept.
+ *   d'(x, y) = fminf(fmaxf(d, 0), 255), a NaN depth is 0                    (stereo's clamp)
+ *   gx = d'(min(x+1, cols-1), y) - d'(max(x-1, 0), y)     gy likewise in y  (central difference, replicated border)
+ *   nx = relief * gx;  ny = relief * gy;  nz = 2                            (the unnormalised normal 2 * (-dz/dx, -dz/dy, 1))
+ *   nn = ((nx*nx) + (ny*ny)) + 4
+ *   DIRECTIONAL: (lx, ly, lz) = the unit vector of (x, y, z), normalised on the host in double (length sqrt(x*x + y*y + z*z)), each
+ *                component rounded to f32
+ *                dot = ((nx*lx) + (ny*ly)) + (2*lz)
+ *                shade = fmaxf(dot, 0) / sqrtf(nn)
+ *   POINT:       dA = anchorDepth when anchorX < 0, otherwise d' at (anchorX, anchorY), READ BY THE KERNEL ON THE DEVICE when it runs
+ *                Lz = (relief * (255 - dA)) + z                             (the light's height in scene units)
+ *                vx = light.x - (float)x;  vy = light.y - (float)y;  vz = Lz - (relief * (255 - d'))
+ *                vv = ((vx*vx) + (vy*vy)) + (vz*vz)
+ *                dot = ((nx*vx) + (ny*vy)) + (2*vz)
+ *                shade = (fmaxf(dot, 0) / sqrtf(nn * vv)) / (1 + (vv * invR2)),  invR2 = (float)(1.0 / ((double)radius * radius)) on the
+ *                host;  vv == 0: shade = 0
+ *   per channel c of B, G, R:  k_c = (float)((double)diffuse * color_c / 255.0) on the host
+ *                out_c = (uchar) fminf(o_c * (ambient + (k_c * shade)), 255)   (truncation, as the reference's effects)
+ * Sign: the normal is (-dz/dx, -dz/dy, 1) = (relief * dd'/dx, relief * dd'/dy, 1) and the central difference is twice the derivative,
+ * hence nz = 2.  A surface that gets NEARER towards the right (gx < 0) rises towards the right and faces LEFT: it is lit by a light
+ * from the left and dark under one from the right.  A constant map under DIRECTIONAL (0, 0, 1), ambient 0, diffuse 1, white, gives the
+ * original; relief 0 shades by distance only; diffuse 0 gives (uchar) fminf(o * ambient, 255) whatever the map.
+ * The output does not depend on RTDD_OPT_FP_CONTRACT.  One kernel launch, stream-ordered, deterministic.
+ * Refused on the host (RTDD_ERR_INVALID), before any launch: the rules of the three effects (null pointers, pitches, image size); a
+ * null light; an unknown kind; any non-finite float; z <= 0; a directional (x, y, z) whose length in double is zero or not finite;
+ * relief outside [0, 64]; ambient or diffuse outside [0, 8]; of a POINT light (a directional light's anchor and radius need only be
+ * finite: it does not use them): x or y outside [-32768, 32767], z above 65536, radius outside (0, 65536] (with these bounds nn * vv
+ * stays below 2^70: no overflow, no NaN but the stated vv == 0), an anchor pixel outside the image when anchorX >= 0, an anchorDepth
+ * outside [0, 255] when it is used; original == artistic (not in place). */
+enum rtdd_light_kind { RTDD_LIGHT_DIRECTIONAL = 0, RTDD_LIGHT_POINT = 1 };
+typedef struct rtdd_light {
+    int   kind;                 /* enum rtdd_light_kind */
+    float x, y, z;              /* DIRECTIONAL: the direction TOWARDS the light (any length; z > 0).
+                                   POINT: (x, y) the light's position in pixels (may lie outside the image), z its height in
+                                   pixels above the surface point it is anchored to (z > 0) */
+    float anchorDepth;          /* POINT: the depth of that surface point when anchorX < 0 */
+    int   anchorX, anchorY;     /* POINT: anchorX >= 0: the depth map's value at this pixel instead, READ BY THE KERNEL ON THE
+                                   DEVICE when it runs (no host synchronisation; the call may sit behind an asynchronous estimate) */
+    float radius;               /* POINT: distance in pixels at which the light has fallen to one half (> 0) */
+    float relief;               /* pixels of height per unit of depth, in [0, 64]; 0: a flat surface (no shading by orientation) */
+    float ambient, diffuse;     /* each in [0, 8]: gain = ambient + diffuse * colour * shade */
+    uint8_t colorB, colorG, colorR;   /* the light's colour; 255, 255, 255: white */
+} rtdd_light;
+int rtdd_simulate_relight(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch,
+                          const float *depth, size_t depthPitch, uint8_t *artistic, size_t artisticPitch,
+                          int rows, int cols, const rtdd_light *light /* HOST, read before the call returns */);
 
 /* ---- whole-estimate driver ------------------------------------------------
  * One depth estimate = the loop body of src/main.cpp:232-295, run as a single stream-ordered launch

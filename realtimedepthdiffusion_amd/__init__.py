@@ -53,11 +53,13 @@ C_ABI_SYMBOLS = [
     "rtdd_pyramid_create_batch", "rtdd_pyramid_select", "rtdd_pyramid_batch", "rtdd_estimate_depth_batch", "rtdd_pyramid_level_info", "rtdd_live_submit_ex",
     "rtdd_simulate_refocus", "rtdd_simulate_haze_ex", "rtdd_simulate_stereo", "rtdd_simulate_lens_blur",
     "rtdd_paint_strokes", "rtdd_pyramid_annotation_rebuild",
+    "rtdd_simulate_relight",
 ]
 IMG_ORIGINAL, IMG_GRAY, IMG_SCRIBBLE, IMG_EDITED, IMG_DEPTH, IMG_DEPTH_U8, IMG_ARTISTIC = range(7)
 EFFECT_NONE, EFFECT_DEFOCUS, EFFECT_DESATURATION, EFFECT_HAZE = range(4)
 STEREO_VIEW, STEREO_ANAGLYPH = 0, 1           # rtdd_simulate_stereo's modes
 APERTURE_BOX, APERTURE_DISC = 0, 1            # rtdd_simulate_lens_blur's shapes
+LIGHT_DIRECTIONAL, LIGHT_POINT = 0, 1         # rtdd_light.kind
 BRUSH_SQUARE, BRUSH_ROUND = 0, 1              # rtdd_stroke.brush
 STROKE_ERASE = -1                             # rtdd_stroke.label: remove the annotation
 # Itanium-mangled names of the reference's ten free functions
@@ -91,6 +93,20 @@ class SolveInfo(C.Structure):
 class Stroke(C.Structure):
     """rtdd_stroke: the segment (x0, y0)-(x1, y1), `radius` (the reference's scribbleRadius: a diameter), BRUSH_*, label 0..255 or STROKE_ERASE."""
     _fields_ = [("x0", C.c_int), ("y0", C.c_int), ("x1", C.c_int), ("y1", C.c_int), ("radius", C.c_int), ("brush", C.c_int), ("label", C.c_int)]
+
+
+class Light(C.Structure):
+    """rtdd_light: LIGHT_DIRECTIONAL with (x, y, z) the direction towards the light, or LIGHT_POINT at pixel (x, y), z pixels above the
+    surface point of depth `anchorDepth` or (anchorX >= 0) of the depth map's value at (anchorX, anchorY), read on the device; `radius`
+    the distance of half intensity; `relief` pixels of height per unit of depth; gain = ambient + diffuse * colour * shade."""
+    _fields_ = [("kind", C.c_int), ("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("anchorDepth", C.c_float),
+                ("anchorX", C.c_int), ("anchorY", C.c_int), ("radius", C.c_float), ("relief", C.c_float), ("ambient", C.c_float),
+                ("diffuse", C.c_float), ("colorB", C.c_uint8), ("colorG", C.c_uint8), ("colorR", C.c_uint8)]
+
+    def __init__(self, kind=LIGHT_DIRECTIONAL, x=0.0, y=0.0, z=1.0, anchorDepth=0.0, anchorX=-1, anchorY=-1, radius=1.0, relief=1.0,
+                 ambient=0.0, diffuse=1.0, color=(255, 255, 255)):
+        b, g, r = color
+        super().__init__(kind, x, y, z, anchorDepth, anchorX, anchorY, radius, relief, ambient, diffuse, b, g, r)
 
 
 class Profile(C.Structure):
@@ -346,6 +362,13 @@ class Context:
         o, op = _img(originalImage); d, dp = _img(depthImage); a, ap = _img(artisticImage)
         self._check(lib().rtdd_simulate_stereo(self._h, o, op, d, dp, a, ap, C.c_int(rows), C.c_int(cols), C.c_int(disparity),
                                                C.c_float(zeroParallaxDepth), C.c_int(zeroX), C.c_int(zeroY), C.c_int(mode)))
+
+    def simulate_relight(self, originalImage, depthImage, artisticImage, rows, cols, light):
+        """The depth map as a surface under `light` (a Light, or None for the C call's null pointer): a directional light, or a point
+        light anchored to the surface that falls off with distance."""
+        o, op = _img(originalImage); d, dp = _img(depthImage); a, ap = _img(artisticImage)
+        self._check(lib().rtdd_simulate_relight(self._h, o, op, d, dp, a, ap, C.c_int(rows), C.c_int(cols),
+                                                C.byref(light) if light is not None else None))
 
 
     # ---- whole-estimate driver (src/main.cpp:92-155, 232-295)

@@ -1006,5 +1006,43 @@ int rtdd_simulate_stereo(rtdd_ctx *ctx, const uint8_t *original, size_t original
     return simulate(ctx, e);
 }
 
+int rtdd_simulate_relight(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
+                          uint8_t *artistic, size_t artisticPitch, int rows, int cols, const rtdd_light *light) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    int rc = check_effect(ctx, original, depth, artistic, originalPitch, depthPitch, artisticPitch, rows, cols);
+    if (rc != RTDD_OK) return rc;
+    REQUIRE(ctx, light, "null light");
+    const rtdd_light &q = *light;
+    const bool point = q.kind == RTDD_LIGHT_POINT;
+    REQUIRE(ctx, point || q.kind == RTDD_LIGHT_DIRECTIONAL, "kind must be RTDD_LIGHT_DIRECTIONAL or RTDD_LIGHT_POINT");
+    for (float v : {q.x, q.y, q.z, q.anchorDepth, q.radius, q.relief, q.ambient, q.diffuse}) REQUIRE(ctx, std::isfinite(v), "a non-finite value in the light");
+    REQUIRE(ctx, q.z > 0.0f, "the light's z must be > 0");
+    REQUIRE(ctx, q.relief >= 0.0f && q.relief <= 64.0f, "relief outside [0, 64]");
+    REQUIRE(ctx, q.ambient >= 0.0f && q.ambient <= 8.0f && q.diffuse >= 0.0f && q.diffuse <= 8.0f, "ambient or diffuse outside [0, 8]");
+    Effect e{Effect::kRelight, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols};
+    Effect::Light &L = e.light;
+    L.kind = q.kind;
+    if (point) {
+        REQUIRE(ctx, q.x >= -32768.0f && q.x <= 32767.0f && q.y >= -32768.0f && q.y <= 32767.0f, "a point light's x or y outside [-32768, 32767]");
+        REQUIRE(ctx, q.z <= 65536.0f, "a point light's z above 65536");
+        REQUIRE(ctx, q.radius > 0.0f && q.radius <= 65536.0f, "radius outside (0, 65536]");
+        if (q.anchorX < 0) REQUIRE(ctx, q.anchorDepth >= 0.0f && q.anchorDepth <= 255.0f, "anchorDepth outside [0, 255]");
+        else REQUIRE(ctx, q.anchorX < cols && q.anchorY >= 0 && q.anchorY < rows, "anchor pixel outside the image");
+        L.x = q.x; L.y = q.y; L.z = q.z;
+        L.anchorDepth = q.anchorDepth; L.anchorX = q.anchorX; L.anchorY = q.anchorY;
+        L.invR2 = (float)(1.0 / ((double)q.radius * q.radius));
+    } else {
+        const double len = std::sqrt((((double)q.x * q.x) + ((double)q.y * q.y)) + ((double)q.z * q.z));
+        REQUIRE(ctx, std::isfinite(len) && len > 0.0, "the light's direction has no length");
+        L.x = (float)(q.x / len); L.y = (float)(q.y / len); L.z = (float)(q.z / len);
+    }
+    L.relief = q.relief; L.ambient = q.ambient;
+    const uint8_t color[3] = {q.colorB, q.colorG, q.colorR};
+    for (int c = 0; c < 3; c++) L.k[c] = (float)((double)q.diffuse * color[c] / 255.0);
+    if (rows == 0 || cols == 0) return RTDD_OK;
+    REQUIRE(ctx, original != artistic, "relight cannot run in place");
+    return simulate(ctx, e);
+}
+
 }  // extern "C"
 #pragma GCC visibility pop

@@ -947,6 +947,7 @@ int launch_effect(rtdd_ctx *ctx, const Effect &e) {
                                       e.kernelSize, e.focusDepth, focus_px);
         }
         case Effect::kLensBlur: return launch_lens_blur(ctx, e);       // lens_blur.hip
+        case Effect::kRelight: return launch_relight(ctx, e);          // relight.hip
         case RTDD_EFFECT_DESATURATION:
             return launch_blend<0>(ctx, e.original, e.originalPitch, e.gray, e.grayPitch, e.depth, e.depthPitch, e.artistic, e.artisticPitch,
                                    e.rows, e.cols);

@@ -1,0 +1,130 @@
+// relight.hip -- depth-aware relighting (rtdd_simulate_relight, include/rtdd.h): the depth map read as a surface, shaded by a
+// directional or a point light.  The first effect here that needs a depth NEIGHBOURHOOD: the central difference of the clamped depth.
+//
+// A stream like haze_ex (3 B + 4 B read, 3 B written per pixel): a lane takes FOUR pixels of a row -- the image as three dwords in and
+// out, the depth as one float4 -- a wave 256 pixels of one row, a workgroup four rows.  The left / right depth neighbours of a lane's
+// four pixels are its neighbour lanes' outer depths (ds_bpermute; lanes 0 and 63 load theirs), the rows above and below are read again
+// as float4 (the workgroup's own rows and its neighbours': cache hits).  Rows that are not aligned for that take one pixel per lane
+// with the same arithmetic.  No LDS, no atomics.
+//
+// The arithmetic is the header's, operation by operation: this translation unit is compiled with -ffp-contract=off and holds no fmaf,
+// `/` and sqrtf are the correctly rounded ones (-fhip-fp32-correctly-rounded-divide-sqrt), denormals are kept -- the bytes are those of
+// tests/relight_ref.py and do not depend on RTDD_OPT_FP_CONTRACT.
+#include "rtdd_internal.hpp"
+#include "effect_common.hpp"
+
+namespace rtdd {
+
+typedef Effect::Light Light;
+
+__device__ __forceinline__ float clamp_depth(float d) { return fminf(fmaxf(d, 0.0f), 255.0f); }     // a NaN depth is 0 (stereo's clamp)
+
+// The shade of pixel (x, y): dc its clamped depth, dl / dr / du / dd its left / right / upper / lower neighbours' (replicated border).
+// Lz: the point light's height in scene units (wave-uniform).
+template <bool POINT>
+__device__ __forceinline__ float relight_shade(const Light &L, float Lz, float dc, float dl, float dr, float du, float dd, int x, int y) {
+    const float gx = dr - dl, gy = dd - du;
+    const float nx = L.relief * gx, ny = L.relief * gy;
+    const float nn = ((nx * nx) + (ny * ny)) + 4.0f;
+    if (!POINT) {
+        const float dot = ((nx * L.x) + (ny * L.y)) + (2.0f * L.z);
+        return fmaxf(dot, 0.0f) / sqrtf(nn);
+    }
+    const float vx = L.x - (float)x, vy = L.y - (float)y, vz = Lz - (L.relief * (255.0f - dc));
+    const float vv = ((vx * vx) + (vy * vy)) + (vz * vz);
+    const float dot = ((nx * vx) + (ny * vy)) + (2.0f * vz);
+    const float s = (fmaxf(dot, 0.0f) / sqrtf(nn * vv)) / (1.0f + (vv * L.invR2));
+    return vv == 0.0f ? 0.0f : s;
+}
+
+// (uchar) fminf(o * (ambient + (k_c * shade)), 255): the gain is finite and >= 0, so the truncation is defined
+__device__ __forceinline__ uint32_t relight_u8(const Light &L, int c, float shade, uint32_t o) {
+    return (uint32_t)(int)fminf((float)o * (L.ambient + (L.k[c] * shade)), 255.0f);
+}
+
+// VEC: four pixels per lane (rows of both images 4-byte aligned, rows of the depth map 16-byte aligned).
+template <bool POINT, bool VEC>
+__global__ __launch_bounds__(256) void k_relight(const uint8_t *__restrict__ orig, size_t op, const float *__restrict__ depth, size_t dp,
+                                                 uint8_t *__restrict__ art, size_t ap, int rows, int cols, Light L,
+                                                 const float *__restrict__ anchor_px) {
+    const int y = blockIdx.y * 4 + wave_id();
+    if (y >= rows) return;                                           // wave-uniform: a wave is one row
+    const int lane = threadIdx.x & 63;
+    const float *drow = (const float *)((const char *)depth + (size_t)y * dp);
+    const float *urow = (const float *)((const char *)depth + (size_t)max(y - 1, 0) * dp);
+    const float *lrow = (const float *)((const char *)depth + (size_t)min(y + 1, rows - 1) * dp);
+    const uint8_t *orow = orig + (size_t)y * op;
+    uint8_t *arow = art + (size_t)y * ap;
+    float Lz = 0.0f;
+    if (POINT) {
+        // the anchor: one uniform load per wave (the pixel form reads the map when the kernel runs, as refocus's focus)
+        const float dA = anchor_px ? clamp_depth(*anchor_px) : L.anchorDepth;
+        Lz = (L.relief * (255.0f - dA)) + L.z;
+    }
+    // one pixel, every neighbour from memory: the one-pixel-per-lane path and the ragged end of a vectorised row
+    auto pixel = [&](int x) {
+        const float dc = clamp_depth(drow[x]);
+        const float dl = clamp_depth(drow[max(x - 1, 0)]), dr = clamp_depth(drow[min(x + 1, cols - 1)]);
+        const float s = relight_shade<POINT>(L, Lz, dc, dl, dr, clamp_depth(urow[x]), clamp_depth(lrow[x]), x, y);
+#pragma unroll
+        for (int c = 0; c < 3; c++) arow[3 * (size_t)x + c] = (uint8_t)relight_u8(L, c, s, orow[3 * (size_t)x + c]);
+    };
+    if (!VEC) {
+        const int x = blockIdx.x * 64 + lane;
+        if (x < cols) pixel(x);
+        return;
+    }
+    const int x = (blockIdx.x * 64 + lane) * 4;
+    const bool whole = x + 3 < cols;
+    // the lane's own depths; a lane at or beyond the ragged end holds the row's last depth in .x: what its left neighbour lane wants
+    float4 c4 = {0.0f, 0.0f, 0.0f, 0.0f}, u4 = c4, l4 = c4;
+    raw12 o = {0u, 0u, 0u};
+    if (whole) {
+        c4 = *(const float4 *)(drow + x); u4 = *(const float4 *)(urow + x); l4 = *(const float4 *)(lrow + x);
+        o = load_raw<true>(orow, x, cols);
+    } else {
+        c4.x = drow[min(x, cols - 1)];
+    }
+    // d(x - 1) and d(x + 4), replicated at the borders: the neighbour lanes' outer depths; the wave's two edge lanes load theirs
+    float left = __shfl_up(c4.w, 1), right = __shfl_down(c4.x, 1);
+    if (lane == 0) left = drow[min(max(x - 1, 0), cols - 1)];
+    if (lane == 63) right = drow[min(x + 4, cols - 1)];
+    if (!whole) {
+        for (int xx = x; xx < cols; xx++) pixel(xx);
+        return;
+    }
+    const float dv[6] = {clamp_depth(left), clamp_depth(c4.x), clamp_depth(c4.y), clamp_depth(c4.z), clamp_depth(c4.w), clamp_depth(right)};
+    const float uv[4] = {u4.x, u4.y, u4.z, u4.w}, lv[4] = {l4.x, l4.y, l4.z, l4.w};
+    uint32_t ob[12], rb[12];
+#pragma unroll
+    for (int i = 0; i < 4; i++) { ob[i] = (o.w0 >> (8 * i)) & 255; ob[4 + i] = (o.w1 >> (8 * i)) & 255; ob[8 + i] = (o.w2 >> (8 * i)) & 255; }
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const float s = relight_shade<POINT>(L, Lz, dv[i + 1], dv[i], dv[i + 2], clamp_depth(uv[i]), clamp_depth(lv[i]), x + i, y);
+#pragma unroll
+        for (int c = 0; c < 3; c++) rb[3 * i + c] = relight_u8(L, c, s, ob[3 * i + c]);
+    }
+    uint32_t *a3 = (uint32_t *)(arow + 3 * (size_t)x);
+    a3[0] = rb[0] | (rb[1] << 8) | (rb[2] << 16) | (rb[3] << 24);
+    a3[1] = rb[4] | (rb[5] << 8) | (rb[6] << 16) | (rb[7] << 24);
+    a3[2] = rb[8] | (rb[9] << 8) | (rb[10] << 16) | (rb[11] << 24);
+}
+
+// rtdd_simulate_relight (arguments checked and the light prepared by api.cpp): one launch.
+int launch_relight(rtdd_ctx *ctx, const Effect &e) {
+    const Light &L = e.light;
+    const bool point = L.kind == RTDD_LIGHT_POINT;
+    // the pixel form: the kernel reads the anchor's depth from the map when it runs (no host synchronisation; a heal's replay reads it again)
+    const float *anchor_px = point && L.anchorX >= 0 ? (const float *)((const char *)e.depth + (size_t)L.anchorY * e.depthPitch) + L.anchorX : nullptr;
+    const bool vec = (uintptr_t)e.original % 4 == 0 && e.originalPitch % 4 == 0 && (uintptr_t)e.artistic % 4 == 0 && e.artisticPitch % 4 == 0 &&
+                     (uintptr_t)e.depth % 16 == 0 && e.depthPitch % 16 == 0;
+    const dim3 g((e.cols + (vec ? 255 : 63)) / (vec ? 256 : 64), (e.rows + 3) / 4);
+#define RTDD_RL_LAUNCH(P, V) hipLaunchKernelGGL((k_relight<P, V>), g, dim3(256), 0, ctx->stream, e.original, e.originalPitch, e.depth, e.depthPitch, e.artistic, e.artisticPitch, e.rows, e.cols, L, anchor_px)
+    if (point) { if (vec) RTDD_RL_LAUNCH(true, true); else RTDD_RL_LAUNCH(true, false); }
+    else { if (vec) RTDD_RL_LAUNCH(false, true); else RTDD_RL_LAUNCH(false, false); }
+#undef RTDD_RL_LAUNCH
+    RTDD_LAUNCH_CHECK(ctx, "k_relight");
+    return RTDD_OK;
+}
+
+}  // namespace rtdd

@@ -85,8 +85,8 @@ struct LiveTargets {
 // One depth effect, arguments checked: what to render, on which images, with which parameters.  Built by the rtdd_simulate_* entry
 // points (api.cpp) and by a live frame (live_effect), launched by launch_effect, and logged by value (PendingOp) to be launched again.
 struct Effect {
-    enum : int { kRefocus = RTDD_EFFECT_HAZE + 1, kHazeEx, kStereo, kLensBlur };   // the extensions, after the public kinds
-    int kind = RTDD_EFFECT_NONE;                    // RTDD_EFFECT_DEFOCUS / _DESATURATION / _HAZE, kRefocus, kHazeEx, kStereo, kLensBlur
+    enum : int { kRefocus = RTDD_EFFECT_HAZE + 1, kHazeEx, kStereo, kLensBlur, kRelight };   // the extensions, after the public kinds
+    int kind = RTDD_EFFECT_NONE;                    // RTDD_EFFECT_DEFOCUS / _DESATURATION / _HAZE, kRefocus, kHazeEx, kStereo, kLensBlur, kRelight
     const uint8_t *original = nullptr; size_t originalPitch = 0;
     const float *depth = nullptr; size_t depthPitch = 0;
     uint8_t *artistic = nullptr; size_t artisticPitch = 0;
@@ -99,6 +99,13 @@ struct Effect {
     // stereo: disparity (|D| <= 256), zero parallax (zeroX >= 0: the map's pixel (zeroX, zeroY), read by the kernel), rtdd_stereo_mode
     int disparity = 0, zeroX = -1, zeroY = -1, stereoMode = 0;
     float zeroDepth = 0.0f;
+    // relight: the light as the host prepared it (include/rtdd.h rtdd_simulate_relight), by value -- a replay needs no rtdd_light
+    struct Light {
+        int kind = 0, anchorX = -1, anchorY = -1;   // rtdd_light_kind; anchorX >= 0: the map's pixel (anchorX, anchorY), read by the kernel
+        float x = 0.0f, y = 0.0f, z = 1.0f;         // directional: the unit vector towards the light; point: position (pixels) and height above the anchor
+        float anchorDepth = 0.0f, invR2 = 0.0f;     // point
+        float relief = 0.0f, ambient = 0.0f, k[3] = {0.0f, 0.0f, 0.0f};   // k[c] = diffuse * colour_c / 255 for c of B, G, R
+    } light = {};
 };
 
 // The defocus window scale K of src/GPUDepthEffect.cu:42, (int)(aperture * diagonal) -- double * float and the int products as there,
@@ -333,6 +340,8 @@ int launch_paint_strokes(rtdd_ctx *ctx, const rtdd_stroke *strokes, int count, u
 int launch_effect(rtdd_ctx *ctx, const Effect &e);
 // ---- lens_blur.hip: Effect::kLensBlur (called by launch_effect) ------------------------------------
 int launch_lens_blur(rtdd_ctx *ctx, const Effect &e);
+// ---- relight.hip: Effect::kRelight (called by launch_effect) ---------------------------------------
+int launch_relight(rtdd_ctx *ctx, const Effect &e);
 
 // ---- cascade.hip -------------------------------------------------------------------------------
 int launch_bgr2gray(rtdd_ctx *ctx, const uint8_t *bgr, size_t bp, uint8_t *gray, size_t gp, int rows, int cols);

@@ -10,8 +10,9 @@ cd "$(dirname "$0")/../realtimedepthdiffusion_amd/csrc"
 make -j4 >/dev/null
 FLAGS=$(make -s --no-print-directory print-cxxflags)
 OBJS=""
-for f in solver_kernels sweep_blocked rbgs_blocked multigrid image_kernels effect_kernels lens_blur cascade api cascade_api dropin; do
-    ext=hip; [ -f $f.cpp ] && ext=cpp
+# the library's sources are the Makefile's own list: a new translation unit is linked into every variant too
+for src in $(make -s --no-print-directory print-srcs); do
+    f=${src%.*}; ext=${src##*.}
     if echo " $FILES " | grep -q " $f.$ext "; then
         /opt/rocm/bin/hipcc --offload-arch=gfx950 $FLAGS $DEFS -c $f.$ext -o $f.$NAME.o
         OBJS="$OBJS $f.$NAME.o"
@@ -19,5 +20,5 @@ for f in solver_kernels sweep_blocked rbgs_blocked multigrid image_kernels effec
         OBJS="$OBJS $f.o"
     fi
 done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../librtdd_$NAME.so $OBJS
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -Wl,-z,defs -o ../librtdd_$NAME.so $OBJS
 echo built librtdd_$NAME.so
