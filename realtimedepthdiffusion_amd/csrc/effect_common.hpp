@@ -1,5 +1,7 @@
-// effect_common.hpp -- device helpers shared by the depth-effect translation units (effect_kernels.hip, lens_blur.hip): the packed
-// 3 x 21-bit pixel sums of the defocus tables, the 64-bit DPP scans, the exact integer quotients, the focus read, the tile geometry.
+// effect_common.hpp -- what the depth-effect translation units (effect_kernels.hip, lens_blur.hip, relight.hip) share.  Device: the
+// packed 3 x 21-bit pixel sums of the defocus tables, the 64-bit DPP scans, the quotients, the focus read, the workgroup -> tile decode,
+// the tile geometry.  Host: the pixel form, row alignment, the launch grids of the two tile kernels and the two table lookups, the
+// table buffer.
 // Included inside no namespace; everything here is in namespace rtdd.
 #pragma once
 
@@ -41,29 +43,44 @@ __device__ __forceinline__ raw12 load_raw(const uint8_t *__restrict__ row, int x
     return v;
 }
 
+// the same twelve bytes one per word, b[3 * i + c] = channel c of pixel i, and back: the three dwords stored at px, the first of the
+// four pixels (4-byte aligned)
+__device__ __forceinline__ void bytes12(const raw12 &v, uint32_t b[12]) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) { b[i] = (v.w0 >> (8 * i)) & 255; b[4 + i] = (v.w1 >> (8 * i)) & 255; b[8 + i] = (v.w2 >> (8 * i)) & 255; }
+}
+__device__ __forceinline__ void store_bytes12(uint8_t *__restrict__ px, const uint32_t b[12]) {              // (every b[i] <= 255)
+    uint32_t *a3 = (uint32_t *)px;
+#pragma unroll
+    for (int i = 0; i < 3; i++) a3[i] = b[4 * i] | (b[4 * i + 1] << 8) | (b[4 * i + 2] << 16) | (b[4 * i + 3] << 24);
+}
+
+// the three fields of a packed sum X (each < 2^21: at most kSatMaxArea pixels) added to running channel sums
+__device__ __forceinline__ void add_fields(u64 X, uint32_t &sb, uint32_t &sg, uint32_t &sr) {
+    sb += (uint32_t)(X & kSatFieldMask); sg += (uint32_t)((X >> 21) & kSatFieldMask); sr += (uint32_t)(X >> 42);
+}
+
 #define RTDD_DPP64(src, ctrl, rows, banks)                                                                       \
     (((u64)(uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)((src) >> 32), ctrl, rows, banks, true) << 32) | \
      (u64)(uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(src), ctrl, rows, banks, true))
 
-// inclusive prefix sum of a 64-bit value over the 64 lanes of a wave (the 7-step DPP scan: VALU only)
-__device__ __forceinline__ u64 wave_incl_scan64(u64 v) {
+// inclusive prefix sums of a 64-bit value by DPP (VALU only), each scan the one before plus a step: over the 16 lanes of each DPP row
+// (the wave totals of a workgroup: at most 16), over the 32 lanes of each half of a wave, over the 64 lanes of a wave
+__device__ __forceinline__ u64 row16_incl_scan64(u64 v) {
     u64 t = v + RTDD_DPP64(v, 0x111, 0xF, 0xF);         // row_shr:1
     t += RTDD_DPP64(v, 0x112, 0xF, 0xF);                // row_shr:2
     t += RTDD_DPP64(v, 0x113, 0xF, 0xF);                // row_shr:3   -> v[i-3..i] within a row of 16
     t += RTDD_DPP64(t, 0x114, 0xF, 0xE);                // row_shr:4, banks 1-3
     t += RTDD_DPP64(t, 0x118, 0xF, 0xC);                // row_shr:8, banks 2-3  -> prefix within each row of 16
-    t += RTDD_DPP64(t, 0x142, 0xA, 0xF);                // row_bcast:15 into rows 1 and 3
-    t += RTDD_DPP64(t, 0x143, 0xC, 0xF);                // row_bcast:31 into rows 2 and 3
     return t;
 }
-// ... over the 16 lanes of each DPP row only (the wave totals of a workgroup: at most 16)
-__device__ __forceinline__ u64 row16_incl_scan64(u64 v) {
-    u64 t = v + RTDD_DPP64(v, 0x111, 0xF, 0xF);
-    t += RTDD_DPP64(v, 0x112, 0xF, 0xF);
-    t += RTDD_DPP64(v, 0x113, 0xF, 0xF);
-    t += RTDD_DPP64(t, 0x114, 0xF, 0xE);
-    t += RTDD_DPP64(t, 0x118, 0xF, 0xC);
-    return t;
+__device__ __forceinline__ u64 half_incl_scan64(u64 v) {
+    const u64 t = row16_incl_scan64(v);
+    return t + RTDD_DPP64(t, 0x142, 0xA, 0xF);          // row_bcast:15 into rows 1 and 3
+}
+__device__ __forceinline__ u64 wave_incl_scan64(u64 v) {
+    const u64 t = half_incl_scan64(v);
+    return t + RTDD_DPP64(t, 0x143, 0xC, 0xF);          // row_bcast:31 into rows 2 and 3
 }
 __device__ __forceinline__ u64 readlane64(u64 v, int lane) {
     return ((u64)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), lane) << 32) | (u64)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, lane);
@@ -96,24 +113,101 @@ __device__ __forceinline__ uint32_t quot3_u8(uint32_t sb, uint32_t sg, uint32_t 
     return __builtin_amdgcn_cvt_pk_u8_f32(q1(sr), 2, out);
 }
 
+// the reference's float -> uchar cast with its out-of-range cases defined: saturate, then truncate
+__device__ __forceinline__ uint32_t store_u8(float v) {
+    if (!(v >= 0.0f)) return 0;
+    if (v >= 255.0f) return 255;
+    return (uint32_t)(int)v;
+}
+
+// The three quotients b | g << 8 | r << 16 of channel sums that a wave took from the image (cnt >= 1 pixels): exact integer quotients on
+// quot_u8's domain, cnt < 2^16 and sums < 2^24 -- every window of a depth map -- and beyond it (an out-of-range depth) the reference's
+// own f32 divide of its f32 sums, which round there.
+__device__ __forceinline__ uint32_t quot3_exact_or_f32(uint32_t sb, uint32_t sg, uint32_t sr, uint32_t cnt) {
+    if (cnt < 65536u && (sb | sg | sr) < (1u << 24)) {
+        const float rc = __builtin_amdgcn_rcpf((float)cnt);
+        return quot_u8(sb, cnt, rc) | (quot_u8(sg, cnt, rc) << 8) | (quot_u8(sr, cnt, rc) << 16);
+    }
+    const float count = (float)cnt;
+    return store_u8((float)sb / count) | (store_u8((float)sg / count) << 8) | (store_u8((float)sr / count) << 16);
+}
+
 // FOCUS (rtdd_simulate_refocus): the window is sized by |depth - f| instead of depth, f = *focus_px (one uniform load per wave: the
 // depth map's value at the focus pixel, read when the kernel runs) or, focus_px == nullptr, the value `focus`.  Nothing else changes.
 __device__ __forceinline__ float focal_depth(float focus, const float *__restrict__ focus_px) {
     return focus_px ? *focus_px : focus;
 }
 
+// ---- workgroup -> tile (k_defocus, k_lens_gather and the two LDS kernels) ----
+// The tile of workgroup p, which the dispatcher places on XCD p % 8: each XCD takes xcd_tiles consecutive tiles, a band of tile ROWS
+// (xcd_tiles == 0: tile p).  The caller leaves if it is >= ntiles, before it divides anything.
+__device__ __forceinline__ int band_tile(int p, int xcd_tiles) { return xcd_tiles > 0 ? (p & 7) * xcd_tiles + (p >> 3) : p; }
+// Tile (tx, ty) of workgroup p of a table lookup: band_tile, or (strip_w > 0) each XCD takes a COLUMN strip strip_w tiles wide and walks
+// it row by row.  false: a workgroup beyond the tiles (workgroup-uniform).
+__device__ __forceinline__ bool tile_of_workgroup(int p, int gx, int ntiles, int xcd_tiles, int strip_w, int &tx, int &ty) {
+    if (strip_w > 0) {
+        const int q = p >> 3;
+        tx = (p & 7) * strip_w + q % strip_w; ty = q / strip_w;
+        if (tx >= gx || ty * gx >= ntiles) return false;
+    } else {
+        const int tile = band_tile(p, xcd_tiles);
+        if (tile >= ntiles) return false;
+        tx = tile % gx; ty = tile / gx;
+    }
+    return true;
+}
+
 // ---- the tile of the LDS kernels (k_defocus_tile, k_lens_tile) ----
 constexpr int kDtW = 64, kDtHM = 28, kDtRW = 124, kDtWorkers = 8;
 static_assert(kDtW + 2 * kDtHM + 3 <= kDtRW && kDtRW % 4 == 0 && kDtRW / 4 <= 32, "the region: tile + both margins + the alignment of its first column, one group of four per lane of a half-wave");
 
-// inclusive prefix sum over the 32 lanes of each half of a wave (the wave scan without its last step)
-__device__ __forceinline__ u64 half_incl_scan64(u64 v) {
-    u64 t = v + RTDD_DPP64(v, 0x111, 0xF, 0xF);
-    t += RTDD_DPP64(v, 0x112, 0xF, 0xF);
-    t += RTDD_DPP64(v, 0x113, 0xF, 0xF);
-    t += RTDD_DPP64(t, 0x114, 0xF, 0xE);
-    t += RTDD_DPP64(t, 0x118, 0xF, 0xC);
-    t += RTDD_DPP64(t, 0x142, 0xA, 0xF);                // row_bcast:15 into rows 1 and 3
+// ---- host: what the launchers share ----
+// The pixel form of a depth-valued argument: the address of depth(x, y), which the kernel reads when it runs (no host synchronisation; a
+// heal's replay reads it again).  x < 0: the value form, nullptr.
+inline const float *pixel_ptr(const float *depth, size_t pitch, int x, int y) {
+    return x >= 0 ? (const float *)((const char *)depth + (size_t)y * pitch) + x : nullptr;
+}
+// every row of an image starts at a multiple of `a` bytes -- what the kernels' VEC paths ask for: 4 for dword accesses to the u8 images,
+// 16 for a float4 of depth
+inline bool rows_aligned(const void *p, size_t pitch, size_t a = 4) { return (uintptr_t)p % a == 0 && pitch % a == 0; }
+
+// the context's table buffer (ctx->sat), grown to `words` u32 words; a new buffer holds no table geometry
+inline int ensure_sat(rtdd_ctx *ctx, size_t words) {
+    if (ctx->sat_elems < words) {
+        if (ctx->sat) { RTDD_HIP(ctx, hipStreamSynchronize(ctx->stream)); RTDD_HIP(ctx, hipFree(ctx->sat)); ctx->sat = nullptr; ctx->sat_elems = 0; }
+        RTDD_HIP(ctx, hipMalloc((void **)&ctx->sat, words * sizeof(uint32_t)));
+        ctx->sat_elems = words; ctx->sat_rows = ctx->sat_cols = 0;
+    }
+    return RTDD_OK;
+}
+
+// The launch of an LDS-tile kernel: tiles of 64 x 16 where all of those are resident at once (`low`), else of 64 x 24; from 64 tiles on
+// each XCD takes xcd_tiles consecutive ones (tile_of_workgroup).
+struct DtGrid { int gx, ntiles, xcd_tiles; bool low; dim3 grid; };
+inline DtGrid dt_grid(const rtdd_ctx *ctx, int rows, int cols) {
+    DtGrid t;
+    t.gx = (cols + kDtW - 1) / kDtW;
+    t.low = t.gx * ((rows + 15) / 16) <= 2 * ctx->num_cus;
+    const int th = t.low ? 16 : 24;
+    t.ntiles = t.gx * ((rows + th - 1) / th);
+    t.xcd_tiles = t.ntiles >= 64 ? (t.ntiles + 7) / 8 : 0;
+    t.grid = dim3(t.xcd_tiles > 0 ? 8 * t.xcd_tiles : t.ntiles);
+    return t;
+}
+
+// The launch of a table lookup (k_defocus, k_lens_gather) over out_rows rows: workgroups of 64 columns x wg_rows rows.  Column strips
+// per XCD where the table rows between a window's bottom and top edge (2 * reach rows of row_bytes), over the whole image width, outgrow
+// an XCD's L2 (RTDD_OPT_DEFOCUS_STRIPS: 0 this rule, 1 never, 2 always; measured in profiles/r06_defocus_strips.txt).
+struct LookupGrid { int gx, ntiles, xcd_tiles, strip_w; dim3 grid; };
+inline LookupGrid lookup_grid(const rtdd_ctx *ctx, int out_rows, int cols, int wg_rows, int reach, size_t row_bytes) {
+    LookupGrid t;
+    t.gx = (cols + 63) / 64;
+    const int gy = (out_rows + wg_rows - 1) / wg_rows;
+    t.ntiles = t.gx * gy;
+    t.xcd_tiles = t.ntiles >= 64 ? (t.ntiles + 7) / 8 : 0;
+    const bool strips = ctx->opt.defocus_strips == 2 || (ctx->opt.defocus_strips == 0 && (size_t)2 * reach * row_bytes > ((size_t)3 << 20) && t.gx >= 16);
+    t.strip_w = strips ? (t.gx + 7) / 8 : 0;
+    t.grid = dim3(t.strip_w > 0 ? 8 * t.strip_w * gy : t.xcd_tiles > 0 ? 8 * t.xcd_tiles : t.ntiles);
     return t;
 }
 

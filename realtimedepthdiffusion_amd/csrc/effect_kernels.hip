@@ -14,13 +14,6 @@
 
 namespace rtdd {
 
-__device__ __forceinline__ uint32_t store_u8(float v) {
-    // defined behaviour for the reference's out-of-range float->uchar cast: saturate, then truncate
-    if (!(v >= 0.0f)) return 0;
-    if (v >= 255.0f) return 255;
-    return (uint32_t)(int)v;
-}
-
 // simulateDesaturation (K8) -- src/GPUDepthEffect.cu:8-27
 template <bool CONTRACT>
 __device__ __forceinline__ uint32_t desat_px(float d, float g, float o) {
@@ -78,13 +71,12 @@ __global__ __launch_bounds__(256) void k_blend(const uint8_t *__restrict__ orig,
         if (x + 3 < cols) {
             const float4 d4 = *(const float4 *)(drow + x);
             const uint32_t *o3 = (const uint32_t *)(orow + 3 * x);
-            const uint32_t w0 = o3[0], w1 = o3[1], w2 = o3[2];
+            const raw12 o = {o3[0], o3[1], o3[2]};
             uint32_t g4 = 0;
             if (MODE == 0) g4 = *(const uint32_t *)(gray + (size_t)y * gp + x);
             const float dv[4] = {d4.x, d4.y, d4.z, d4.w};
             uint32_t ob[12], rb[12];
-#pragma unroll
-            for (int i = 0; i < 4; i++) { ob[i] = (w0 >> (8 * i)) & 255; ob[4 + i] = (w1 >> (8 * i)) & 255; ob[8 + i] = (w2 >> (8 * i)) & 255; }
+            bytes12(o, ob);
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 if (MODE == 0) {
@@ -102,10 +94,7 @@ __global__ __launch_bounds__(256) void k_blend(const uint8_t *__restrict__ orig,
                     for (int c = 0; c < 3; c++) rb[3 * i + c] = haze_px<CONTRACT>(t, u * airf[c], (float)ob[3 * i + c]);
                 }
             }
-            uint32_t *a3 = (uint32_t *)(arow + 3 * x);
-            a3[0] = rb[0] | (rb[1] << 8) | (rb[2] << 16) | (rb[3] << 24);
-            a3[1] = rb[4] | (rb[5] << 8) | (rb[6] << 16) | (rb[7] << 24);
-            a3[2] = rb[8] | (rb[9] << 8) | (rb[10] << 16) | (rb[11] << 24);
+            store_bytes12(arow + 3 * x, rb);
             return;
         }
         // ragged tail of a vectorised row: fall through to the scalar body for the remaining pixels
@@ -449,17 +438,8 @@ __global__ __launch_bounds__(256) void k_defocus(const uint8_t *__restrict__ ori
     // (round 6, wide images): each XCD takes a COLUMN strip strip_w tiles wide and walks it row by row -- a table line read as a window's
     // bottom edge is read again as a top edge 2 h rows later, and only a strip's 2 h rows (8K: 220 x 960 px x 8 B = 1.7 MB), not the
     // whole image width's (13.5 MB), fit the XCD's 4 MB L2 in between.
-    const int p = blockIdx.x;
     int tx, ty;
-    if (strip_w > 0) {
-        const int q = p >> 3;
-        tx = (p & 7) * strip_w + q % strip_w; ty = q / strip_w;
-        if (tx >= gx || ty * gx >= ntiles) return;
-    } else {
-        const int tile = xcd_tiles > 0 ? (p & 7) * xcd_tiles + (p >> 3) : p;
-        if (tile >= ntiles) return;
-        tx = tile % gx; ty = tile / gx;
-    }
+    if (!tile_of_workgroup(blockIdx.x, gx, ntiles, xcd_tiles, strip_w, tx, ty)) return;
     const int lane = threadIdx.x & 63, wv = wave_id();
     const int x0 = tx * 64, yw = row0 + ty * (4 * kLk2Rows) + wv * kLk2Rows;
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)Tpad, 0, (int)((uint32_t)(trows + 1) * (uint32_t)tpitch * 8u), 0x00020000);
@@ -512,7 +492,6 @@ __global__ __launch_bounds__(256) void k_defocus(const uint8_t *__restrict__ ori
             if (cnt[i] > (uint32_t)kSatMaxArea) {
                 uint32_t sb = 0, sg = 0, sr = 0;
                 const int wd = xb[i] - xa[i];
-                auto add = [&](u64 Xs) { sb += (uint32_t)(Xs & kSatFieldMask); sg += (uint32_t)((Xs >> 21) & kSatFieldMask); sr += (uint32_t)(Xs >> 42); };
                 if (wd <= kSatMaxArea) {                            // every nominal window: strips of whole rows
                     const int rh = max(kSatMaxArea / wd, 1);
                     const uint32_t cs = 8u * (uint32_t)xa[i] + 24u, ce = 8u * (uint32_t)xb[i] + 24u;
@@ -520,10 +499,10 @@ __global__ __launch_bounds__(256) void k_defocus(const uint8_t *__restrict__ ori
                     for (int ys = ya[i] + rh; ys < yb[i]; ys += rh) {            // the rows between the strips
                         const uint32_t r1 = (uint32_t)(ys - trow0) * pitch8;
                         const u64 D1 = tab_load(rsrc, r1 + ce) - tab_load(rsrc, r1 + cs);
-                        add(D1 - Dp);
+                        add_fields(D1 - Dp, sb, sg, sr);
                         Dp = D1;
                     }
-                    add((C[i][3] - C[i][2]) - Dp);                  // the strip that ends at the last corner row
+                    add_fields((C[i][3] - C[i][2]) - Dp, sb, sg, sr);                  // the strip that ends at the last corner row
                 } else {                                            // a row wider than a strip may be (depths far above 255 only): strips in columns too
                     const int cw = kSatMaxArea, rh = 1;
                     for (int xs = xa[i]; xs < xb[i]; xs += cw) {
@@ -535,18 +514,12 @@ __global__ __launch_bounds__(256) void k_defocus(const uint8_t *__restrict__ ori
                             const int ye = min(ys + rh, yb[i]);
                             const uint32_t r1 = (uint32_t)(ye - trow0) * pitch8;
                             const u64 D1 = tab_load(rsrc, r1 + ce) - tab_load(rsrc, r1 + cs);
-                            add(D1 - D0);
+                            add_fields(D1 - D0, sb, sg, sr);
                             D0 = D1;
                         }
                     }
                 }
-                if (cnt[i] < 65536u && (sb | sg | sr) < (1u << 24)) {           // nominal: exact sums, exact integer quotients
-                    const float rc = __builtin_amdgcn_rcpf((float)cnt[i]);
-                    res = quot_u8(sb, cnt[i], rc) | (quot_u8(sg, cnt[i], rc) << 8) | (quot_u8(sr, cnt[i], rc) << 16);
-                } else {                                            // (an out-of-range depth: the reference's own f32 sums round here)
-                    const float count = (float)cnt[i];
-                    res = store_u8((float)sb / count) | (store_u8((float)sg / count) << 8) | (store_u8((float)sr / count) << 16);
-                }
+                res = quot3_exact_or_f32(sb, sg, sr, cnt[i]);
             }
         }
         // (a banded table) a window that reaches beyond the slice's rows -- a depth above 255: no depth map -- is summed by its wave from
@@ -572,15 +545,7 @@ __global__ __launch_bounds__(256) void k_defocus(const uint8_t *__restrict__ ori
                     for (int m = 32; m >= 1; m >>= 1) { tb += __shfl_xor(tb, m); tg += __shfl_xor(tg, m); tr += __shfl_xor(tr, m); }
                     if (lane == L) { sb = tb; sg = tg; sr = tr; }
                 }
-                if (mine) {
-                    if (cnt[i] < 65536u && (sb | sg | sr) < (1u << 24)) {       // exact sums, exact integer quotients
-                        const float rc = __builtin_amdgcn_rcpf((float)cnt[i]);
-                        res = quot_u8(sb, cnt[i], rc) | (quot_u8(sg, cnt[i], rc) << 8) | (quot_u8(sr, cnt[i], rc) << 16);
-                    } else {                                                    // (as the strips above: the reference's own f32 sums round here)
-                        const float count = (float)cnt[i];
-                        res = store_u8((float)sb / count) | (store_u8((float)sg / count) << 8) | (store_u8((float)sr / count) << 16);
-                    }
-                }
+                if (mine) res = quot3_exact_or_f32(sb, sg, sr, cnt[i]);
             }
         }
         if (__builtin_expect(__builtin_amdgcn_ballot_w64(cnt[i] == 0u) != 0, 0)) {   // count == 0 (src/GPUDepthEffect.cu:62-66): the pixel itself
@@ -599,7 +564,7 @@ __global__ __launch_bounds__(256) void k_defocus(const uint8_t *__restrict__ ori
                 uint8_t *a = arow + 3 * (size_t)x;
                 a[0] = (uint8_t)res; a[1] = (uint8_t)(res >> 8); a[2] = (uint8_t)(res >> 16);
             }
-        }
+        }     // wave-uniform (row1 <= rows: this launch's last output row + 1)
     }
 }
 
@@ -628,24 +593,21 @@ __global__ __launch_bounds__(256, 2) void k_defocus_tile(const uint8_t *__restri
                                                          float focus, const float *__restrict__ focus_px) {
     constexpr int kDtRH = kDtH + 2 * kDtHM, kDtRowsPer = (kDtRH + kDtWorkers - 1) / kDtWorkers;
     __shared__ u64 S[kDtRH][kDtRW];                                 // the region's summed-area table, S[r - R0][c - C0]: <= 79 360 B, two workgroups per CU
-    const int p = blockIdx.x;
-    const int tile = xcd_tiles > 0 ? (p & 7) * xcd_tiles + (p >> 3) : p;
+    const int tile = band_tile(blockIdx.x, xcd_tiles);
     if (tile >= ntiles) return;
     // (loads and table build at a raised wave priority, the lookups at the normal one: of the two workgroups on a CU the one still
     // building gets ahead of the other's lookups -- 1080p 27.3 -> 26.5 us, 672 x 624 8.9 -> 8.5)
     __builtin_amdgcn_s_setprio(2);
     const int tid = threadIdx.x, lane = tid & 63, wv = wave_id();
     const int tx0 = (tile % gx) * kDtW, ty0 = (tile / gx) * kDtH;
-    const int R0 = ty0 - hm, C0 = (tx0 - hm) & ~3;                  // (a multiple of four, also when negative: groups of four never straddle column 0)
-    const int rh = kDtH + 2 * hm, rpw = (rh + kDtWorkers - 1) / kDtWorkers;      // region rows, rows per worker
 
     // ---- every load of the tile first: the region's pixels (this thread: 4 columns x <= 9 rows) and the output pixels' depth / colour ----
+    const int R0 = ty0 - hm, C0 = (tx0 - hm) & ~3;                  // (a multiple of four, also when negative: groups of four never straddle column 0)
+    const int rh = kDtH + 2 * hm, rpw = (rh + kDtWorkers - 1) / kDtWorkers;      // region rows, rows per worker
     const int worker = tid >> 5, wl = tid & 31, gcol = C0 + 4 * wl;
     const bool group_ok = wl < kDtRW / 4 && gcol >= 0 && gcol < cols;
     raw12 raw[kDtRowsPer];
     if (VEC && C0 >= 0 && C0 + kDtRW <= cols) {
-        // the region lies between the image's left and right borders (workgroup-uniform; all but the outermost tile columns): three dword
-        // loads per row from a clamped, always valid address, rows outside the image or the chunk zeroed afterwards -- no branches
         const int gc = wl < kDtRW / 4 ? gcol : C0;
 #pragma unroll
         for (int i = 0; i < kDtRowsPer; i++) {
@@ -777,16 +739,7 @@ __global__ __launch_bounds__(256, 2) void k_defocus_tile(const uint8_t *__restri
                 }
                 if (lane == L) { sb = tb; sg = tg; sr = tr; }
             }
-            if (has && !local) {
-                const uint32_t n = (uint32_t)ht * (uint32_t)wd;
-                if (n < 65536u && (sb | sg | sr) < (1u << 24)) {    // exact sums, exact integer quotients (quot_u8)
-                    const float rn = __builtin_amdgcn_rcpf((float)n);
-                    res = quot_u8(sb, n, rn) | (quot_u8(sg, n, rn) << 8) | (quot_u8(sr, n, rn) << 16);
-                } else {                                            // (as the table path: the reference's own f32 sums round here)
-                    const float count = (float)n;
-                    res = store_u8((float)sb / count) | (store_u8((float)sg / count) << 8) | (store_u8((float)sr / count) << 16);
-                }
-            }
+            if (has && !local) res = quot3_exact_or_f32(sb, sg, sr, (uint32_t)ht * (uint32_t)wd);
         }
         if (y < rows) {                                             // wave-uniform
             uint8_t *arow = art + (size_t)y * ap;
@@ -798,7 +751,7 @@ __global__ __launch_bounds__(256, 2) void k_defocus_tile(const uint8_t *__restri
                 uint8_t *a = arow + 3 * (size_t)x;
                 a[0] = (uint8_t)res; a[1] = (uint8_t)(res >> 8); a[2] = (uint8_t)(res >> 16);
             }
-        }
+        }    // wave-uniform
     }
 }
 
@@ -807,17 +760,12 @@ static inline dim3 grid64x4(int rows, int cols) { return dim3((cols + 63) / 64, 
 template <int MODE>
 static int launch_blend(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const uint8_t *gray, size_t gp, const float *depth, size_t dp,
                         uint8_t *art, size_t ap, int rows, int cols, float beta = 2.0f, uint32_t air = 0xFFFFFFu) {
-    const bool aligned = ((uintptr_t)orig % 4 == 0) && ((uintptr_t)art % 4 == 0) && op % 4 == 0 && ap % 4 == 0 &&
-                         ((uintptr_t)depth % 16 == 0) && dp % 16 == 0 && (MODE != 0 || (((uintptr_t)gray % 4 == 0) && gp % 4 == 0));
-    const bool c = ctx->opt.fp_contract != 0;
-    if (aligned) {
-        const dim3 grid((cols + 255) / 256, (rows + 3) / 4);
-        if (c) hipLaunchKernelGGL((k_blend<MODE, true, true>), grid, dim3(256), 0, ctx->stream, orig, op, gray, gp, depth, dp, art, ap, rows, cols, beta, air);
-        else hipLaunchKernelGGL((k_blend<MODE, false, true>), grid, dim3(256), 0, ctx->stream, orig, op, gray, gp, depth, dp, art, ap, rows, cols, beta, air);
-    } else {
-        if (c) hipLaunchKernelGGL((k_blend<MODE, true, false>), grid64x4(rows, cols), dim3(256), 0, ctx->stream, orig, op, gray, gp, depth, dp, art, ap, rows, cols, beta, air);
-        else hipLaunchKernelGGL((k_blend<MODE, false, false>), grid64x4(rows, cols), dim3(256), 0, ctx->stream, orig, op, gray, gp, depth, dp, art, ap, rows, cols, beta, air);
-    }
+    const bool aligned = rows_aligned(orig, op) && rows_aligned(art, ap) && rows_aligned(depth, dp, 16) && (MODE != 0 || rows_aligned(gray, gp));
+    const dim3 grid = aligned ? dim3((cols + 255) / 256, (rows + 3) / 4) : grid64x4(rows, cols);
+#define RTDD_BL_LAUNCH(C, V) hipLaunchKernelGGL((k_blend<MODE, C, V>), grid, dim3(256), 0, ctx->stream, orig, op, gray, gp, depth, dp, art, ap, rows, cols, beta, air)
+    if (ctx->opt.fp_contract != 0) { if (aligned) RTDD_BL_LAUNCH(true, true); else RTDD_BL_LAUNCH(true, false); }
+    else { if (aligned) RTDD_BL_LAUNCH(false, true); else RTDD_BL_LAUNCH(false, false); }
+#undef RTDD_BL_LAUNCH
     RTDD_LAUNCH_CHECK(ctx, "k_blend");
     return RTDD_OK;
 }
@@ -832,15 +780,10 @@ static int defocus_body(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const flo
     // small nominal windows (up to ~1080p): one launch, per-tile tables in LDS (k_defocus_tile).  RTDD_OPT_DEFOCUS_PATH: 0 automatic, 1 the
     // global table always, 2 the tile kernel wherever its region fits.
     if (ctx->opt.defocus_path != 1 && !(ctx->opt.defocus_path == 0 && ctx->defocus_table_sticky) && kernelSize / 2 <= kDtHM && (size_t)rows * cols < (1ull << 32) / 255) {
-        const bool vio = (uintptr_t)orig % 4 == 0 && op % 4 == 0 && (uintptr_t)art % 4 == 0 && ap % 4 == 0;
-        const int gx = (cols + kDtW - 1) / kDtW;
-        const bool low = gx * ((rows + 15) / 16) <= 2 * ctx->num_cus;    // every 16-row tile resident at once
-        const int th = low ? 16 : 24, gy = (rows + th - 1) / th, ntiles = gx * gy;
-        const int xcd_tiles = ntiles >= 64 ? (ntiles + 7) / 8 : 0;
-        const dim3 g(xcd_tiles > 0 ? 8 * xcd_tiles : ntiles);
-#define RTDD_DT_LAUNCH(V, H) hipLaunchKernelGGL((k_defocus_tile<V, H, FOCUS>), g, dim3(256), 0, ctx->stream, orig, op, depth, dp, art, ap, rows, cols, kernelSize, kernelSize / 2, gx, ntiles, xcd_tiles, ctx->sync_words + kSyncNonLocal, focus, focus_px)
-        if (vio) { if (low) RTDD_DT_LAUNCH(true, 16); else RTDD_DT_LAUNCH(true, 24); }
-        else { if (low) RTDD_DT_LAUNCH(false, 16); else RTDD_DT_LAUNCH(false, 24); }
+        const DtGrid t = dt_grid(ctx, rows, cols);
+#define RTDD_DT_LAUNCH(V, H) hipLaunchKernelGGL((k_defocus_tile<V, H, FOCUS>), t.grid, dim3(256), 0, ctx->stream, orig, op, depth, dp, art, ap, rows, cols, kernelSize, kernelSize / 2, t.gx, t.ntiles, t.xcd_tiles, ctx->sync_words + kSyncNonLocal, focus, focus_px)
+        if (rows_aligned(orig, op) && rows_aligned(art, ap)) { if (t.low) RTDD_DT_LAUNCH(true, 16); else RTDD_DT_LAUNCH(true, 24); }
+        else { if (t.low) RTDD_DT_LAUNCH(false, 16); else RTDD_DT_LAUNCH(false, 24); }
 #undef RTDD_DT_LAUNCH
         RTDD_LAUNCH_CHECK(ctx, "k_defocus_tile");
         ctx->defocus_last_path = 2;
@@ -888,17 +831,13 @@ static int defocus_body(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const flo
     if (table_entries * sizeof(u64) >= (1ull << 32) || (size_t)tpitch * sizeof(u64) >= (1u << 24) || (size_t)trows_max + 1 >= (1u << 24))
         return fail(ctx, RTDD_ERR_INVALID, "image too large for the defocus table (its 8 bytes per pixel must stay below 4 GiB: about 536 million pixels)");
     const size_t need = ((table_entries + (size_t)nbands_max * tp) * sizeof(u64) + 256) / sizeof(uint32_t);   // padded table + band bases, in u32 words
-    if (ctx->sat_elems < need) {
-        if (ctx->sat) { RTDD_HIP(ctx, hipStreamSynchronize(ctx->stream)); RTDD_HIP(ctx, hipFree(ctx->sat)); ctx->sat = nullptr; ctx->sat_elems = 0; }
-        RTDD_HIP(ctx, hipMalloc((void **)&ctx->sat, need * sizeof(uint32_t)));
-        ctx->sat_elems = need; ctx->sat_rows = ctx->sat_cols = 0;
-    }
+    if (const int st = ensure_sat(ctx, need)) return st;
     u64 *Tpad = (u64 *)ctx->sat, *T = Tpad + tpitch + 4, *base = Tpad + table_entries;
     if (ctx->sat_rows != trows_max || ctx->sat_cols != cols) {          // another geometry: the padding lies elsewhere -- zero the table once (the build never writes the padding)
         RTDD_HIP(ctx, hipMemsetAsync(Tpad, 0, table_entries * sizeof(u64), ctx->stream));
         ctx->sat_rows = trows_max; ctx->sat_cols = cols;
     }
-    const bool vin = (uintptr_t)orig % 4 == 0 && op % 4 == 0, vout = vin && (uintptr_t)art % 4 == 0 && ap % 4 == 0;
+    const bool vin = rows_aligned(orig, op), vout = vin && rows_aligned(art, ap);
     for (int sl = 0; sl < nslices; sl++) {
         const int row0 = sl * slice_rows, row1 = row0 + slice_rows < rows ? row0 + slice_rows : rows;
         const int trow0 = nslices == 1 ? 0 : (row0 - reach > 0 ? row0 - reach : 0);
@@ -916,16 +855,10 @@ static int defocus_body(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const flo
         if (vin) hipLaunchKernelGGL(k_sat_build<true>, dim3(nbands), dim3(64 * build_waves), 0, ctx->stream, o_sl, op, base, T, tp, trows, cols, RB, tpitch);
         else hipLaunchKernelGGL(k_sat_build<false>, dim3(nbands), dim3(64 * build_waves), 0, ctx->stream, o_sl, op, base, T, tp, trows, cols, RB, tpitch);
         RTDD_LAUNCH_CHECK(ctx, "k_sat_build");
-        const int gx2 = (cols + 63) / 64, gy2 = (row1 - row0 + 4 * kLk2Rows - 1) / (4 * kLk2Rows), nt2 = gx2 * gy2;
-        const int xt2 = nt2 >= 64 ? (nt2 + 7) / 8 : 0;
-        // column strips per XCD where the rows between a window's bottom and top edge, over the whole image width, outgrow an XCD's L2
-        // (RTDD_OPT_DEFOCUS_STRIPS: 0 this rule, 1 never, 2 always; measured in profiles/r06_defocus_strips.txt)
-        const bool strips = ctx->opt.defocus_strips == 2 || (ctx->opt.defocus_strips == 0 && (size_t)2 * reach * row_bytes > ((size_t)3 << 20) && gx2 >= 16);
-        const int strip_w = strips ? (gx2 + 7) / 8 : 0;
-        const dim3 g5(strip_w > 0 ? 8 * strip_w * gy2 : xt2 > 0 ? 8 * xt2 : nt2);
+        const LookupGrid t = lookup_grid(ctx, row1 - row0, cols, 4 * kLk2Rows, reach, row_bytes);
         int *nlw = nslices > 1 ? ctx->sync_words + kSyncNonLocal : nullptr;
-        if (vout) hipLaunchKernelGGL((k_defocus<true, FOCUS>), g5, dim3(256), 0, ctx->stream, orig, op, depth, dp, Tpad, tpitch, art, ap, rows, cols, kernelSize, gx2, nt2, xt2, row0, row1, trow0, trows, nlw, strip_w, focus, focus_px);
-        else hipLaunchKernelGGL((k_defocus<false, FOCUS>), g5, dim3(256), 0, ctx->stream, orig, op, depth, dp, Tpad, tpitch, art, ap, rows, cols, kernelSize, gx2, nt2, xt2, row0, row1, trow0, trows, nlw, strip_w, focus, focus_px);
+        if (vout) hipLaunchKernelGGL((k_defocus<true, FOCUS>), t.grid, dim3(256), 0, ctx->stream, orig, op, depth, dp, Tpad, tpitch, art, ap, rows, cols, kernelSize, t.gx, t.ntiles, t.xcd_tiles, row0, row1, trow0, trows, nlw, t.strip_w, focus, focus_px);
+        else hipLaunchKernelGGL((k_defocus<false, FOCUS>), t.grid, dim3(256), 0, ctx->stream, orig, op, depth, dp, Tpad, tpitch, art, ap, rows, cols, kernelSize, t.gx, t.ntiles, t.xcd_tiles, row0, row1, trow0, trows, nlw, t.strip_w, focus, focus_px);
     }
     if (nslices > 1) note_status_writer(ctx);                           // (kSyncNonLocal: a window beyond a slice -> the whole-image table from the next synchronisation on)
     RTDD_LAUNCH_CHECK(ctx, "k_defocus");
@@ -940,12 +873,9 @@ int launch_effect(rtdd_ctx *ctx, const Effect &e) {
         case RTDD_EFFECT_DEFOCUS:
             return defocus_body<false>(ctx, e.original, e.originalPitch, e.depth, e.depthPitch, e.artistic, e.artisticPitch, e.rows, e.cols,
                                        window_scale(0.025, e.rows, e.cols), 0.0f, nullptr);     // :42, evaluated once on the host
-        case Effect::kRefocus: {
-            // the pixel form: the kernels read the focal depth from the map when they run (no host synchronisation; a heal's replay reads it again)
-            const float *focus_px = e.focusX >= 0 ? (const float *)((const char *)e.depth + (size_t)e.focusY * e.depthPitch) + e.focusX : nullptr;
+        case Effect::kRefocus:
             return defocus_body<true>(ctx, e.original, e.originalPitch, e.depth, e.depthPitch, e.artistic, e.artisticPitch, e.rows, e.cols,
-                                      e.kernelSize, e.focusDepth, focus_px);
-        }
+                                      e.kernelSize, e.focusDepth, pixel_ptr(e.depth, e.depthPitch, e.focusX, e.focusY));
         case Effect::kLensBlur: return launch_lens_blur(ctx, e);       // lens_blur.hip
         case Effect::kRelight: return launch_relight(ctx, e);          // relight.hip
         case RTDD_EFFECT_DESATURATION:
@@ -957,12 +887,11 @@ int launch_effect(rtdd_ctx *ctx, const Effect &e) {
             return launch_blend<2>(ctx, e.original, e.originalPitch, nullptr, 0, e.depth, e.depthPitch, e.artistic, e.artisticPitch, e.rows, e.cols,
                                    e.beta, e.air);
         case Effect::kStereo: {
-            // the pixel form: the kernel reads z0 from the map when it runs (as refocus's focus)
-            const float *zp = e.zeroX >= 0 ? (const float *)((const char *)e.depth + (size_t)e.zeroY * e.depthPitch) + e.zeroX : nullptr;
-            const bool vec = (uintptr_t)e.original % 4 == 0 && e.originalPitch % 4 == 0 && (uintptr_t)e.artistic % 4 == 0 && e.artisticPitch % 4 == 0;
+            const float *zp = pixel_ptr(e.depth, e.depthPitch, e.zeroX, e.zeroY);      // the pixel form of z0
             const dim3 g((e.cols + kStW - 1) / kStW, e.rows);
-            if (vec) hipLaunchKernelGGL(k_stereo<true>, g, dim3(256), 0, ctx->stream, e.original, e.originalPitch, e.depth, e.depthPitch, e.artistic,
-                                        e.artisticPitch, e.rows, e.cols, e.disparity, e.zeroDepth, zp, e.stereoMode);
+            if (rows_aligned(e.original, e.originalPitch) && rows_aligned(e.artistic, e.artisticPitch))
+                hipLaunchKernelGGL(k_stereo<true>, g, dim3(256), 0, ctx->stream, e.original, e.originalPitch, e.depth, e.depthPitch, e.artistic,
+                                   e.artisticPitch, e.rows, e.cols, e.disparity, e.zeroDepth, zp, e.stereoMode);
             else hipLaunchKernelGGL(k_stereo<false>, g, dim3(256), 0, ctx->stream, e.original, e.originalPitch, e.depth, e.depthPitch, e.artistic,
                                     e.artisticPitch, e.rows, e.cols, e.disparity, e.zeroDepth, zp, e.stereoMode);
             RTDD_LAUNCH_CHECK(ctx, "k_stereo");

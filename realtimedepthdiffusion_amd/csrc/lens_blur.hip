@@ -44,11 +44,13 @@ __device__ __forceinline__ void disc_span(int q4, int dy, int x, int cols, int &
 }
 
 __device__ __forceinline__ uint32_t disc_quot(u64 X, uint32_t sb, uint32_t sg, uint32_t sr, uint32_t cnt) {
-    sb += (uint32_t)(X & kSatFieldMask); sg += (uint32_t)((X >> 21) & kSatFieldMask); sr += (uint32_t)(X >> 42);
+    add_fields(X, sb, sg, sr);
     return quot3_u8(sb, sg, sr, cnt, __builtin_amdgcn_rcpf((float)cnt));
 }
 
-// a wave's 64 results b | g << 8 | r << 16 of row y, columns x0 .. x0 + 63, to the image (k_defocus's store: three dwords per quad of pixels)
+// a wave's 64 results b | g << 8 | r << 16 of row y, columns x0 .. x0 + 63, to the image.  whole (wave-uniform: 4-byte aligned rows and
+// all 64 columns inside the image): `art` moves as dwords, the three dwords of a quad of pixels stored by its first three lanes after
+// one quad permute; else bytes, column by column
 __device__ __forceinline__ void store_row(uint8_t *__restrict__ art, size_t ap, int y, int x0, int lane, int cols, bool whole, uint32_t res) {
     uint8_t *arow = art + (size_t)y * ap;
     const int j = lane & 3, x = x0 + lane;
@@ -95,7 +97,7 @@ __global__ __launch_bounds__(1024) void k_lens_rowprefix(const uint8_t *__restri
 }
 
 // The lookup: lane = pixel, wave = 64 pixels of one row, workgroup = 64 x 4 pixels; workgroup p runs on XCD p % 8 and the tiles are dealt
-// as k_defocus deals them -- a band of tile rows per XCD, or (strip_w > 0: wide images) a column strip per XCD walked row by row, so that
+// by tile_of_workgroup -- a band of tile rows per XCD, or (strip_w > 0: wide images) a column strip per XCD walked row by row, so that
 // the table rows a tile reads are still in that XCD's L2 from the tile above.  A wave's row is uniform: the two table rows of a step
 // are scalar addresses and lanes with equal k read adjacent entries.  The loop runs to the largest h of the wave; a lane beyond its
 // own disc adds empty spans.  Packed sums are unpacked every 32 rows (<= 32 x 255 pixels <= kSatMaxArea).
@@ -104,17 +106,8 @@ __global__ __launch_bounds__(256) void k_lens_gather(const uint8_t *__restrict__
                                                       const u64 *__restrict__ E, int tpitch, uint8_t *__restrict__ art, size_t ap,
                                                       int rows, int cols, int kernelSize, int gx, int ntiles, int xcd_tiles, int strip_w,
                                                       float focus, const float *__restrict__ focus_px) {
-    const int p = blockIdx.x;
     int tx, ty;
-    if (strip_w > 0) {
-        const int q = p >> 3;
-        tx = (p & 7) * strip_w + q % strip_w; ty = q / strip_w;
-        if (tx >= gx || ty * gx >= ntiles) return;
-    } else {
-        const int tile = xcd_tiles > 0 ? (p & 7) * xcd_tiles + (p >> 3) : p;
-        if (tile >= ntiles) return;
-        tx = tile % gx; ty = tile / gx;
-    }
+    if (!tile_of_workgroup(blockIdx.x, gx, ntiles, xcd_tiles, strip_w, tx, ty)) return;
     const int lane = threadIdx.x & 63, x0 = tx * 64, y = ty * 4 + wave_id();
     if (y >= rows) return;                                          // wave-uniform
     const int x = x0 + lane, xc = min(x, cols - 1);
@@ -144,7 +137,7 @@ __global__ __launch_bounds__(256) void k_lens_gather(const uint8_t *__restrict__
             X += e[xb1] - e[xa]; cnt += (uint32_t)n;
         }
         if ((dy & 15) == 15) {                                      // 31 rows, then 32 at a time
-            sb += (uint32_t)(X & kSatFieldMask); sg += (uint32_t)((X >> 21) & kSatFieldMask); sr += (uint32_t)(X >> 42);
+            add_fields(X, sb, sg, sr);
             X = 0;
         }
     }
@@ -167,19 +160,18 @@ __global__ __launch_bounds__(256, 2) void k_lens_tile(const uint8_t *__restrict_
                                                       int gx, int ntiles, int xcd_tiles, float focus, const float *__restrict__ focus_px) {
     constexpr int kDtRH = kDtH + 2 * kDtHM, kDtRowsPer = (kDtRH + kDtWorkers - 1) / kDtWorkers;
     __shared__ u64 S[kDtRH][kDtRW];                                 // <= 79 360 B: two workgroups per CU
-    const int p = blockIdx.x;
-    const int tile = xcd_tiles > 0 ? (p & 7) * xcd_tiles + (p >> 3) : p;
+    const int tile = band_tile(blockIdx.x, xcd_tiles);
     if (tile >= ntiles) return;
     const int tid = threadIdx.x, lane = tid & 63, wv = wave_id();
     const int tx0 = (tile % gx) * kDtW, ty0 = (tile / gx) * kDtH;
-    const int R0 = ty0 - hm, C0 = (tx0 - hm) & ~3;                  // (a multiple of four, also when negative)
-    const int rh = kDtH + 2 * hm, rpw = (rh + kDtWorkers - 1) / kDtWorkers;      // region rows, rows per worker
 
     // ---- every load first: the region's pixels (this thread: 4 columns x <= 10 rows), then the output pixels' depth ----
+    const int R0 = ty0 - hm, C0 = (tx0 - hm) & ~3;                  // (a multiple of four, also when negative: groups of four never straddle column 0)
+    const int rh = kDtH + 2 * hm, rpw = (rh + kDtWorkers - 1) / kDtWorkers;      // region rows, rows per worker
     const int worker = tid >> 5, wl = tid & 31, gcol = C0 + 4 * wl;
     const bool group_ok = wl < kDtRW / 4 && gcol >= 0 && gcol < cols;
     raw12 raw[kDtRowsPer];
-    if (VEC && C0 >= 0 && C0 + kDtRW <= cols) {                     // workgroup-uniform: clamped, always valid addresses and no branches
+    if (VEC && C0 >= 0 && C0 + kDtRW <= cols) {
         const int gc = wl < kDtRW / 4 ? gcol : C0;
 #pragma unroll
         for (int i = 0; i < kDtRowsPer; i++) {
@@ -288,47 +280,32 @@ int launch_lens_blur(rtdd_ctx *ctx, const Effect &e) {
     const uint8_t *orig = e.original; const size_t op = e.originalPitch;
     uint8_t *art = e.artistic; const size_t ap = e.artisticPitch;
     const int rows = e.rows, cols = e.cols, kernelSize = e.kernelSize;
-    // the pixel form: the kernels read the focal depth from the map when they run (as refocus)
-    const float *focus_px = e.focusX >= 0 ? (const float *)((const char *)e.depth + (size_t)e.focusY * e.depthPitch) + e.focusX : nullptr;
-    const bool vin = (uintptr_t)orig % 4 == 0 && op % 4 == 0, vout = vin && (uintptr_t)art % 4 == 0 && ap % 4 == 0;
+    const float *focus_px = pixel_ptr(e.depth, e.depthPitch, e.focusX, e.focusY);      // the pixel form of the focus
+    const bool vin = rows_aligned(orig, op), vout = vin && rows_aligned(art, ap);
     if (ctx->opt.defocus_path != 1 && kernelSize / 2 <= kDtHM) {
-        const int gx = (cols + kDtW - 1) / kDtW;
-        const bool low = gx * ((rows + 15) / 16) <= 2 * ctx->num_cus;    // every 16-row tile resident at once
-        const int th = low ? 16 : 24, gy = (rows + th - 1) / th, ntiles = gx * gy;
-        const int xcd_tiles = ntiles >= 64 ? (ntiles + 7) / 8 : 0;
-        const dim3 g(xcd_tiles > 0 ? 8 * xcd_tiles : ntiles);
-#define RTDD_LT_LAUNCH(V, H) hipLaunchKernelGGL((k_lens_tile<V, H>), g, dim3(256), 0, ctx->stream, orig, op, e.depth, e.depthPitch, art, ap, rows, cols, kernelSize, kernelSize / 2, gx, ntiles, xcd_tiles, e.focusDepth, focus_px)
-        if (vout) { if (low) RTDD_LT_LAUNCH(true, 16); else RTDD_LT_LAUNCH(true, 24); }
-        else { if (low) RTDD_LT_LAUNCH(false, 16); else RTDD_LT_LAUNCH(false, 24); }
+        const DtGrid t = dt_grid(ctx, rows, cols);
+#define RTDD_LT_LAUNCH(V, H) hipLaunchKernelGGL((k_lens_tile<V, H>), t.grid, dim3(256), 0, ctx->stream, orig, op, e.depth, e.depthPitch, art, ap, rows, cols, kernelSize, kernelSize / 2, t.gx, t.ntiles, t.xcd_tiles, e.focusDepth, focus_px)
+        if (vout) { if (t.low) RTDD_LT_LAUNCH(true, 16); else RTDD_LT_LAUNCH(true, 24); }
+        else { if (t.low) RTDD_LT_LAUNCH(false, 16); else RTDD_LT_LAUNCH(false, 24); }
 #undef RTDD_LT_LAUNCH
         RTDD_LAUNCH_CHECK(ctx, "k_lens_tile");
         ctx->defocus_last_path = 2;
         return RTDD_OK;
     }
-    // The row prefixes live in the defocus table's buffer, grown by its rule.  Their layout is another, and they overwrite what the
+    // The row prefixes live in the defocus table's buffer.  Their layout is another, and they overwrite what the
     // defocus table keeps zero: its cached geometry is dropped, so the next defocus lays its padding out again.
     const int tpitch = (cols + 1 + 3) / 4 * 4;
     const size_t need = ((size_t)rows * tpitch * sizeof(u64) + 256) / sizeof(uint32_t);
-    if (ctx->sat_elems < need) {
-        if (ctx->sat) { RTDD_HIP(ctx, hipStreamSynchronize(ctx->stream)); RTDD_HIP(ctx, hipFree(ctx->sat)); ctx->sat = nullptr; ctx->sat_elems = 0; }
-        RTDD_HIP(ctx, hipMalloc((void **)&ctx->sat, need * sizeof(uint32_t)));
-        ctx->sat_elems = need;
-    }
+    if (const int st = ensure_sat(ctx, need)) return st;
     ctx->sat_rows = ctx->sat_cols = 0;
     u64 *E = (u64 *)ctx->sat;
     int waves = (tpitch / 4 + 63) / 64; if (waves > 16) waves = 16;
     if (vin) hipLaunchKernelGGL(k_lens_rowprefix<true>, dim3(rows), dim3(64 * waves), 0, ctx->stream, orig, op, E, tpitch, cols);
     else hipLaunchKernelGGL(k_lens_rowprefix<false>, dim3(rows), dim3(64 * waves), 0, ctx->stream, orig, op, E, tpitch, cols);
     RTDD_LAUNCH_CHECK(ctx, "k_lens_rowprefix");
-    const int gx = (cols + 63) / 64, gy = (rows + 3) / 4, ntiles = gx * gy;
-    const int xcd_tiles = ntiles >= 64 ? (ntiles + 7) / 8 : 0;
-    // column strips per XCD where the table rows a disc spans, over the whole image width, outgrow an XCD's L2 (the box's rule and option)
-    const bool strips = ctx->opt.defocus_strips == 2 ||
-                        (ctx->opt.defocus_strips == 0 && (size_t)2 * (kernelSize / 2) * tpitch * sizeof(u64) > ((size_t)3 << 20) && gx >= 16);
-    const int strip_w = strips ? (gx + 7) / 8 : 0;
-    const dim3 g(strip_w > 0 ? 8 * strip_w * gy : xcd_tiles > 0 ? 8 * xcd_tiles : ntiles);
-    if (vout) hipLaunchKernelGGL(k_lens_gather<true>, g, dim3(256), 0, ctx->stream, orig, op, e.depth, e.depthPitch, E, tpitch, art, ap, rows, cols, kernelSize, gx, ntiles, xcd_tiles, strip_w, e.focusDepth, focus_px);
-    else hipLaunchKernelGGL(k_lens_gather<false>, g, dim3(256), 0, ctx->stream, orig, op, e.depth, e.depthPitch, E, tpitch, art, ap, rows, cols, kernelSize, gx, ntiles, xcd_tiles, strip_w, e.focusDepth, focus_px);
+    const LookupGrid t = lookup_grid(ctx, rows, cols, 4, kernelSize / 2, tpitch * sizeof(u64));
+    if (vout) hipLaunchKernelGGL(k_lens_gather<true>, t.grid, dim3(256), 0, ctx->stream, orig, op, e.depth, e.depthPitch, E, tpitch, art, ap, rows, cols, kernelSize, t.gx, t.ntiles, t.xcd_tiles, t.strip_w, e.focusDepth, focus_px);
+    else hipLaunchKernelGGL(k_lens_gather<false>, t.grid, dim3(256), 0, ctx->stream, orig, op, e.depth, e.depthPitch, E, tpitch, art, ap, rows, cols, kernelSize, t.gx, t.ntiles, t.xcd_tiles, t.strip_w, e.focusDepth, focus_px);
     RTDD_LAUNCH_CHECK(ctx, "k_lens_gather");
     ctx->defocus_last_path = 1;
     ctx->defocus_last_slices = 1;

@@ -96,28 +96,22 @@ __global__ __launch_bounds__(256) void k_relight(const uint8_t *__restrict__ ori
     const float dv[6] = {clamp_depth(left), clamp_depth(c4.x), clamp_depth(c4.y), clamp_depth(c4.z), clamp_depth(c4.w), clamp_depth(right)};
     const float uv[4] = {u4.x, u4.y, u4.z, u4.w}, lv[4] = {l4.x, l4.y, l4.z, l4.w};
     uint32_t ob[12], rb[12];
-#pragma unroll
-    for (int i = 0; i < 4; i++) { ob[i] = (o.w0 >> (8 * i)) & 255; ob[4 + i] = (o.w1 >> (8 * i)) & 255; ob[8 + i] = (o.w2 >> (8 * i)) & 255; }
+    bytes12(o, ob);
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         const float s = relight_shade<POINT>(L, Lz, dv[i + 1], dv[i], dv[i + 2], clamp_depth(uv[i]), clamp_depth(lv[i]), x + i, y);
 #pragma unroll
         for (int c = 0; c < 3; c++) rb[3 * i + c] = relight_u8(L, c, s, ob[3 * i + c]);
     }
-    uint32_t *a3 = (uint32_t *)(arow + 3 * (size_t)x);
-    a3[0] = rb[0] | (rb[1] << 8) | (rb[2] << 16) | (rb[3] << 24);
-    a3[1] = rb[4] | (rb[5] << 8) | (rb[6] << 16) | (rb[7] << 24);
-    a3[2] = rb[8] | (rb[9] << 8) | (rb[10] << 16) | (rb[11] << 24);
+    store_bytes12(arow + 3 * (size_t)x, rb);
 }
 
 // rtdd_simulate_relight (arguments checked and the light prepared by api.cpp): one launch.
 int launch_relight(rtdd_ctx *ctx, const Effect &e) {
     const Light &L = e.light;
     const bool point = L.kind == RTDD_LIGHT_POINT;
-    // the pixel form: the kernel reads the anchor's depth from the map when it runs (no host synchronisation; a heal's replay reads it again)
-    const float *anchor_px = point && L.anchorX >= 0 ? (const float *)((const char *)e.depth + (size_t)L.anchorY * e.depthPitch) + L.anchorX : nullptr;
-    const bool vec = (uintptr_t)e.original % 4 == 0 && e.originalPitch % 4 == 0 && (uintptr_t)e.artistic % 4 == 0 && e.artisticPitch % 4 == 0 &&
-                     (uintptr_t)e.depth % 16 == 0 && e.depthPitch % 16 == 0;
+    const float *anchor_px = point ? pixel_ptr(e.depth, e.depthPitch, L.anchorX, L.anchorY) : nullptr;     // the pixel form of the anchor's depth
+    const bool vec = rows_aligned(e.original, e.originalPitch) && rows_aligned(e.artistic, e.artisticPitch) && rows_aligned(e.depth, e.depthPitch, 16);
     const dim3 g((e.cols + (vec ? 255 : 63)) / (vec ? 256 : 64), (e.rows + 3) / 4);
 #define RTDD_RL_LAUNCH(P, V) hipLaunchKernelGGL((k_relight<P, V>), g, dim3(256), 0, ctx->stream, e.original, e.originalPitch, e.depth, e.depthPitch, e.artistic, e.artisticPitch, e.rows, e.cols, L, anchor_px)
     if (point) { if (vec) RTDD_RL_LAUNCH(true, true); else RTDD_RL_LAUNCH(true, false); }
