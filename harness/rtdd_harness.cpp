@@ -14,6 +14,8 @@
 //                 --effect relight [--light-dir x,y,z | --light-at X,Y [--light-height H] [--light-radius R]] [--relief S] [--ambient A] [--diffuse D]
 //                 [--light-color b,g,r]   (rtdd_simulate_relight; default: a white directional light from the upper left, (-1, -1, 1), relief 2,
 //                 ambient 0.25, diffuse 1; --light-at: a point light over that pixel, anchored at its depth, height 100, radius 200)
+//                 --effect relight --shadows N [--shadow-bias B] [--shadow-softness S] [--shadow-strength T]   (rtdd_simulate_relight_shadowed: cast
+//                 shadows, N steps of the march; default bias 0, softness 0 = hard, strength 1)
 //     key 't'  -> prints "Processing Time"  (main.cpp:320-322; wall clock here, the reference uses clock()); the process's one-time costs
 //                 (~20 ms: code objects, first allocations) are paid by a warm-up on a context of its own first -- --cold leaves it out
 //     --paint x,y,label,radius  = a mouse drag sample (main.cpp:46-62), repeatable; --paint-at F:x,y,label,radius = the same while --live
@@ -199,6 +201,9 @@ struct Job {
     // --relief, --ambient, --diffuse, --light-color
     rtdd_light light = {RTDD_LIGHT_DIRECTIONAL, -1.0f, -1.0f, 1.0f, 0.0f, -1, -1, 200.0f, 2.0f, 0.25f, 1.0f, 255, 255, 255};
     float light_height = 100.0f;
+    // --shadows N (given: rtdd_simulate_relight_shadowed), --shadow-bias, --shadow-softness, --shadow-strength
+    bool shadows = false;
+    rtdd_shadow shadow = {0, 0.0f, 0.0f, 1.0f};
     bool sequential = false;      // --sequential: a --batch as one estimate after the other (default: rtdd_estimate_depth_batch, all images in the same launches)
     bool cold = false;            // --cold: no warm-up: the first (and, without --live, only) estimate pays the one-time costs
 };
@@ -468,7 +473,8 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
         else if (job.effect == "relight") {
             rtdd_light light = job.light;
             if (light.kind == RTDD_LIGHT_POINT) light.z = job.light_height;
-            CK(rtdd_simulate_relight(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols, &light));
+            if (job.shadows) CK(rtdd_simulate_relight_shadowed(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols, &light, &job.shadow));
+            else CK(rtdd_simulate_relight(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols, &light));
         }
         depth_u8->resize((size_t)rows * cols);
         CK(rtdd_download(ctx, depth_u8->data(), cols, p_u8, pi_u8, cols, rows));   // main.cpp:291 (synchronises)
@@ -486,6 +492,7 @@ int main(int argc, const char *argv[]) {
                                  "                    [--focus D | --focus-at X,Y] [--aperture A] [--bokeh box|disc] (refocus)  [--haze-beta B] [--airlight b,g,r] (haze)\n"
                                  "                    [--disparity D] [--zero-parallax Z | --zero-parallax-at X,Y] [--anaglyph] (stereo)\n"
                                  "                    [--light-dir x,y,z | --light-at X,Y [--light-height H] [--light-radius R]] [--relief S] [--ambient A] [--diffuse D] [--light-color b,g,r] (relight)\n"
+                                 "                    [--shadows N [--shadow-bias B] [--shadow-softness S] [--shadow-strength T]] (relight with cast shadows)\n"
                                  "                    [--paint x,y,label,radius]... [--live N [--paint-at frame:x,y,label,radius]...] [--devices D --batch B [--sequential] [--write-all]] [--png] [--cold]\n"
                                  "                    [--stroke x0,y0,x1,y1,label,radius[,round]]... [--erase x0,y0,x1,y1,radius[,round]]...   (segments, in command-line order, one rtdd_paint_strokes call after --paint)\n"
                                  "                    [--stroke-at frame:x0,y0,x1,y1,label,radius[,round]]... [--erase-at frame:x0,y0,x1,y1,radius[,round]]...   (--live: in front of that frame)\n"
@@ -497,7 +504,7 @@ int main(int argc, const char *argv[]) {
     }
     Job job;
     std::string in, an, out = "";
-    bool png = false, write_all = false;
+    bool png = false, write_all = false, shadow_opt = false;
     int devices = 1, batch = 1, live = 0;
     for (int i = 1; i < argc; i++) {
         auto next = [&]() -> const char * { return i + 1 < argc ? argv[++i] : ""; };
@@ -550,6 +557,10 @@ int main(int argc, const char *argv[]) {
         else if (!std::strcmp(argv[i], "--light-height")) job.light_height = (float)std::atof(next());
         else if (!std::strcmp(argv[i], "--light-radius")) job.light.radius = (float)std::atof(next());
         else if (!std::strcmp(argv[i], "--relief")) job.light.relief = (float)std::atof(next());
+        else if (!std::strcmp(argv[i], "--shadows")) { job.shadow.maxSteps = std::atoi(next()); job.shadows = true; }
+        else if (!std::strcmp(argv[i], "--shadow-bias")) { job.shadow.bias = (float)std::atof(next()); shadow_opt = true; }
+        else if (!std::strcmp(argv[i], "--shadow-softness")) { job.shadow.softness = (float)std::atof(next()); shadow_opt = true; }
+        else if (!std::strcmp(argv[i], "--shadow-strength")) { job.shadow.strength = (float)std::atof(next()); shadow_opt = true; }
         else if (!std::strcmp(argv[i], "--ambient")) job.light.ambient = (float)std::atof(next());
         else if (!std::strcmp(argv[i], "--diffuse")) job.light.diffuse = (float)std::atof(next());
         else if (!std::strcmp(argv[i], "--light-color")) {
@@ -566,6 +577,9 @@ int main(int argc, const char *argv[]) {
         }
         else if (!std::strcmp(argv[i], "-h")) std::printf("Usage:\n -i input image (JPEG, 8-bit PNG, binary PPM)\n -a annotated image (8-bit PNG, binary PGM)\n");
     }
+    // cast shadows belong to relight, and their parameters to --shadows: a stray one is refused, not dropped
+    if (job.shadows && job.effect != "relight") { std::printf("--shadows needs --effect relight\n"); return 1; }
+    if (shadow_opt && !job.shadows) { std::printf("--shadow-bias, --shadow-softness and --shadow-strength need --shadows N\n"); return 1; }
     // a live frame's sticky effect is an effect code without parameters (rtdd_live_submit_ex): the aimed effects are not available there
     if (live > 0 && (job.effect == "refocus" || job.effect == "stereo" || job.effect == "relight" || (job.effect == "haze" && job.haze_ex))) {
         std::printf("--live renders the reference's three effects only: --effect refocus, --effect stereo, --effect relight and --haze-beta / --airlight are not supported with --live\n");

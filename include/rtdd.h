@@ -310,7 +310,8 @@ int rtdd_simulate_haze(rtdd_ctx *ctx, const uint8_t *original, size_t originalPi
 
 /* ---- aimed depth effects (extensions; no reference behaviour) --------------------------------
  * Added after ABI version 230 without a version bump: a host finds them by symbol (dlsym).  The next bump of RTDD_VERSION
- * should cover them (rtdd_simulate_refocus, rtdd_simulate_lens_blur, rtdd_simulate_haze_ex, rtdd_simulate_stereo, rtdd_simulate_relight), together with a parameterised live effect
+ * should cover them (rtdd_simulate_refocus, rtdd_simulate_lens_blur, rtdd_simulate_haze_ex, rtdd_simulate_stereo, rtdd_simulate_relight,
+ * rtdd_simulate_relight_shadowed), together with a parameterised live effect
  * (rtdd_live_submit_ex takes an effect code only and knows none of them). */
 
 /* Refocus: the defocus effect sharp at a chosen depth instead of at depth 0.
@@ -429,6 +430,42 @@ typedef struct rtdd_light {
 int rtdd_simulate_relight(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch,
                           const float *depth, size_t depthPitch, uint8_t *artistic, size_t artisticPitch,
                           int rows, int cols, const rtdd_light *light /* HOST, read before the call returns */);
+
+/* Relight with CAST SHADOWS: rtdd_simulate_relight, and in addition every pixel marches over the height field H(x, y) = relief * (255 - d'(x, y))
+ * towards the light and is darkened where the surface rises above its ray.  The rules of rtdd_simulate_relight carry over: every
+ * operation is one f32 operation, rounded once, NONE fused; / is IEEE correctly rounded; denormals are kept; rintf rounds half to even;
+ * d', shade, k_c, Lz, vx, vy, vz and the unit vector (lx, ly, lz) are exactly rtdd_simulate_relight's.
+ * The direction of the march -- it steps along the MAJOR axis of the projected direction towards the light:
+ *   DIRECTIONAL: m = fmaxf(fabsf(lx), fabsf(ly));  sx = lx / m;  sy = ly / m;  rise = lz / m;  n = maxSteps      (f32, on the host;
+ *                m == 0: every pixel is lit)
+ *   POINT, per pixel: m = fmaxf(fabsf(vx), fabsf(vy));  m < 1: the pixel is lit;  otherwise sx = vx / m;  sy = vy / m;  rise = vz / m;
+ *                n = min(maxSteps, (int)m)                        (the march ends at the light's column or row)
+ * The march, for k = 1 .. n, kf = (float)k:
+ *   px = x + (int)rintf(kf * sx);  py = y + (int)rintf(kf * sy);  the first k whose (px, py) lies outside the image ends the march
+ *   ray = (H(x, y) + bias) + (kf * rise)
+ *   occ = H(px, py) - ray
+ *   q_k = 0 when !(occ > 0);  otherwise 1 when softness == 0, and fminf(occ / (kf * softness), 1) when softness > 0   (a blocker
+ *         farther away gives a wider penumbra)
+ *   q = max over k of q_k  (0 over no steps);  vis = 1 - (strength * q)
+ * per channel c of B, G, R:  out_c = (uchar) fminf(o_c * (ambient + (k_c * (shade * vis))), 255)
+ * q is a maximum of values in [0, 1]: the order of the steps does not matter.  An implementation may stop a march as soon as q == 1,
+ * and for rise >= 0 as soon as ray > relief * 255 (no height reaches the ray from there on: rounding is monotonic); these are its
+ * freedoms, not part of the rule.  maxSteps == 0 or strength == 0 gives rtdd_simulate_relight's bytes.  A constant map is never
+ * shadowed by a light that does not stand below it (rise >= 0, so ray >= H: every directional light, a point light with Lz >= H); a
+ * point light below the surface does shadow it.
+ * With the stated bounds nothing produces a NaN: occ > 0 is divided by a positive kf * softness, an infinite rise gives occ = -inf.
+ * The output does not depend on RTDD_OPT_FP_CONTRACT; one kernel launch, stream-ordered, deterministic, not in place.
+ * Refused on the host (RTDD_ERR_INVALID), before any launch: everything rtdd_simulate_relight refuses; a null shadow; any non-finite
+ * field; any field outside the ranges below. */
+typedef struct rtdd_shadow {
+    int   maxSteps;    /* [0, 1024]: pixels marched towards the light along the major axis; 0: no shadows */
+    float bias;        /* [0, 65536]: height (scene units = pixels) the ray starts above the surface: against self-shadowing */
+    float softness;    /* [0, 65536]: 0 hard shadows; > 0: penumbra -- see q_k */
+    float strength;    /* [0, 1]: the share of the diffuse term a full shadow removes */
+} rtdd_shadow;
+int rtdd_simulate_relight_shadowed(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch,
+                                   const float *depth, size_t depthPitch, uint8_t *artistic, size_t artisticPitch,
+                                   int rows, int cols, const rtdd_light *light, const rtdd_shadow *shadow /* both HOST, read before the call returns */);
 
 /* ---- whole-estimate driver ------------------------------------------------
  * One depth estimate = the loop body of src/main.cpp:232-295, run as a single stream-ordered launch

@@ -53,7 +53,7 @@ C_ABI_SYMBOLS = [
     "rtdd_pyramid_create_batch", "rtdd_pyramid_select", "rtdd_pyramid_batch", "rtdd_estimate_depth_batch", "rtdd_pyramid_level_info", "rtdd_live_submit_ex",
     "rtdd_simulate_refocus", "rtdd_simulate_haze_ex", "rtdd_simulate_stereo", "rtdd_simulate_lens_blur",
     "rtdd_paint_strokes", "rtdd_pyramid_annotation_rebuild",
-    "rtdd_simulate_relight",
+    "rtdd_simulate_relight", "rtdd_simulate_relight_shadowed",
 ]
 IMG_ORIGINAL, IMG_GRAY, IMG_SCRIBBLE, IMG_EDITED, IMG_DEPTH, IMG_DEPTH_U8, IMG_ARTISTIC = range(7)
 EFFECT_NONE, EFFECT_DEFOCUS, EFFECT_DESATURATION, EFFECT_HAZE = range(4)
@@ -107,6 +107,16 @@ class Light(C.Structure):
                  ambient=0.0, diffuse=1.0, color=(255, 255, 255)):
         b, g, r = color
         super().__init__(kind, x, y, z, anchorDepth, anchorX, anchorY, radius, relief, ambient, diffuse, b, g, r)
+
+
+class Shadow(C.Structure):
+    """rtdd_shadow: every pixel marches up to `maxSteps` pixels towards the light (0: no shadows) from `bias` above the surface;
+    `softness` 0 gives hard shadows, > 0 a penumbra that widens with the blocker's distance; `strength` is the share of the diffuse
+    term a full shadow removes."""
+    _fields_ = [("maxSteps", C.c_int), ("bias", C.c_float), ("softness", C.c_float), ("strength", C.c_float)]
+
+    def __init__(self, maxSteps=256, bias=0.0, softness=0.0, strength=1.0):
+        super().__init__(maxSteps, bias, softness, strength)
 
 
 class Profile(C.Structure):
@@ -370,6 +380,13 @@ class Context:
         self._check(lib().rtdd_simulate_relight(self._h, o, op, d, dp, a, ap, C.c_int(rows), C.c_int(cols),
                                                 C.byref(light) if light is not None else None))
 
+    def simulate_relight_shadowed(self, originalImage, depthImage, artisticImage, rows, cols, light, shadow):
+        """simulate_relight with cast shadows: a height-field march per pixel towards `light`, as `shadow` (a Shadow, or None for the C
+        call's null pointer) says."""
+        o, op = _img(originalImage); d, dp = _img(depthImage); a, ap = _img(artisticImage)
+        self._check(lib().rtdd_simulate_relight_shadowed(self._h, o, op, d, dp, a, ap, C.c_int(rows), C.c_int(cols),
+                                                         C.byref(light) if light is not None else None,
+                                                         C.byref(shadow) if shadow is not None else None))
 
     # ---- whole-estimate driver (src/main.cpp:92-155, 232-295)
     def pyramid_create(self, rows, cols):

@@ -1006,10 +1006,10 @@ int rtdd_simulate_stereo(rtdd_ctx *ctx, const uint8_t *original, size_t original
     return simulate(ctx, e);
 }
 
-int rtdd_simulate_relight(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
-                          uint8_t *artistic, size_t artisticPitch, int rows, int cols, const rtdd_light *light) {
-    if (!ctx) return RTDD_ERR_INVALID;
-    int rc = check_effect(ctx, original, depth, artistic, originalPitch, depthPitch, artisticPitch, rows, cols);
+// The checks of rtdd_simulate_relight up to the empty image, and the light as the kernels take it (e.light), for the two relight calls.
+static int prepare_relight(rtdd_ctx *ctx, Effect &e, const rtdd_light *light) {
+    const int rows = e.rows, cols = e.cols;
+    int rc = check_effect(ctx, e.original, e.depth, e.artistic, e.originalPitch, e.depthPitch, e.artisticPitch, rows, cols);
     if (rc != RTDD_OK) return rc;
     REQUIRE(ctx, light, "null light");
     const rtdd_light &q = *light;
@@ -1019,7 +1019,6 @@ int rtdd_simulate_relight(rtdd_ctx *ctx, const uint8_t *original, size_t origina
     REQUIRE(ctx, q.z > 0.0f, "the light's z must be > 0");
     REQUIRE(ctx, q.relief >= 0.0f && q.relief <= 64.0f, "relief outside [0, 64]");
     REQUIRE(ctx, q.ambient >= 0.0f && q.ambient <= 8.0f && q.diffuse >= 0.0f && q.diffuse <= 8.0f, "ambient or diffuse outside [0, 8]");
-    Effect e{Effect::kRelight, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols};
     Effect::Light &L = e.light;
     L.kind = q.kind;
     if (point) {
@@ -1039,6 +1038,40 @@ int rtdd_simulate_relight(rtdd_ctx *ctx, const uint8_t *original, size_t origina
     L.relief = q.relief; L.ambient = q.ambient;
     const uint8_t color[3] = {q.colorB, q.colorG, q.colorR};
     for (int c = 0; c < 3; c++) L.k[c] = (float)((double)q.diffuse * color[c] / 255.0);
+    return RTDD_OK;
+}
+
+int rtdd_simulate_relight(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
+                          uint8_t *artistic, size_t artisticPitch, int rows, int cols, const rtdd_light *light) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    Effect e{Effect::kRelight, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols};
+    const int rc = prepare_relight(ctx, e, light);
+    if (rc != RTDD_OK) return rc;
+    if (rows == 0 || cols == 0) return RTDD_OK;
+    REQUIRE(ctx, original != artistic, "relight cannot run in place");
+    return simulate(ctx, e);
+}
+
+int rtdd_simulate_relight_shadowed(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
+                                   uint8_t *artistic, size_t artisticPitch, int rows, int cols, const rtdd_light *light,
+                                   const rtdd_shadow *shadow) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    Effect e{Effect::kRelightShadow, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols};
+    const int rc = prepare_relight(ctx, e, light);
+    if (rc != RTDD_OK) return rc;
+    REQUIRE(ctx, shadow, "null shadow");
+    const rtdd_shadow &q = *shadow;
+    for (float v : {q.bias, q.softness, q.strength}) REQUIRE(ctx, std::isfinite(v), "a non-finite value in the shadow");
+    REQUIRE(ctx, q.maxSteps >= 0 && q.maxSteps <= 1024, "maxSteps outside [0, 1024]");
+    REQUIRE(ctx, q.bias >= 0.0f && q.bias <= 65536.0f && q.softness >= 0.0f && q.softness <= 65536.0f, "bias or softness outside [0, 65536]");
+    REQUIRE(ctx, q.strength >= 0.0f && q.strength <= 1.0f, "strength outside [0, 1]");
+    Effect::Shadow &S = e.shadow;
+    S.maxSteps = q.maxSteps; S.bias = q.bias; S.softness = q.softness; S.strength = q.strength;
+    if (e.light.kind == RTDD_LIGHT_DIRECTIONAL) {
+        // the step along the major axis of the projected direction, in f32; m == 0 (the light straight above) leaves sx == sy == 0
+        const float m = fmaxf(fabsf(e.light.x), fabsf(e.light.y));
+        if (m != 0.0f) { S.sx = e.light.x / m; S.sy = e.light.y / m; S.rise = e.light.z / m; }
+    }
     if (rows == 0 || cols == 0) return RTDD_OK;
     REQUIRE(ctx, original != artistic, "relight cannot run in place");
     return simulate(ctx, e);

@@ -12,35 +12,9 @@
 // tests/relight_ref.py and do not depend on RTDD_OPT_FP_CONTRACT.
 #include "rtdd_internal.hpp"
 #include "effect_common.hpp"
+#include "relight_common.hpp"       // clamp_depth, relight_shade, relight_u8: shared with relight_shadow.hip
 
 namespace rtdd {
-
-typedef Effect::Light Light;
-
-__device__ __forceinline__ float clamp_depth(float d) { return fminf(fmaxf(d, 0.0f), 255.0f); }     // a NaN depth is 0 (stereo's clamp)
-
-// The shade of pixel (x, y): dc its clamped depth, dl / dr / du / dd its left / right / upper / lower neighbours' (replicated border).
-// Lz: the point light's height in scene units (wave-uniform).
-template <bool POINT>
-__device__ __forceinline__ float relight_shade(const Light &L, float Lz, float dc, float dl, float dr, float du, float dd, int x, int y) {
-    const float gx = dr - dl, gy = dd - du;
-    const float nx = L.relief * gx, ny = L.relief * gy;
-    const float nn = ((nx * nx) + (ny * ny)) + 4.0f;
-    if (!POINT) {
-        const float dot = ((nx * L.x) + (ny * L.y)) + (2.0f * L.z);
-        return fmaxf(dot, 0.0f) / sqrtf(nn);
-    }
-    const float vx = L.x - (float)x, vy = L.y - (float)y, vz = Lz - (L.relief * (255.0f - dc));
-    const float vv = ((vx * vx) + (vy * vy)) + (vz * vz);
-    const float dot = ((nx * vx) + (ny * vy)) + (2.0f * vz);
-    const float s = (fmaxf(dot, 0.0f) / sqrtf(nn * vv)) / (1.0f + (vv * L.invR2));
-    return vv == 0.0f ? 0.0f : s;
-}
-
-// (uchar) fminf(o * (ambient + (k_c * shade)), 255): the gain is finite and >= 0, so the truncation is defined
-__device__ __forceinline__ uint32_t relight_u8(const Light &L, int c, float shade, uint32_t o) {
-    return (uint32_t)(int)fminf((float)o * (L.ambient + (L.k[c] * shade)), 255.0f);
-}
 
 // VEC: four pixels per lane (rows of both images 4-byte aligned, rows of the depth map 16-byte aligned).
 template <bool POINT, bool VEC>

@@ -85,8 +85,8 @@ struct LiveTargets {
 // One depth effect, arguments checked: what to render, on which images, with which parameters.  Built by the rtdd_simulate_* entry
 // points (api.cpp) and by a live frame (live_effect), launched by launch_effect, and logged by value (PendingOp) to be launched again.
 struct Effect {
-    enum : int { kRefocus = RTDD_EFFECT_HAZE + 1, kHazeEx, kStereo, kLensBlur, kRelight };   // the extensions, after the public kinds
-    int kind = RTDD_EFFECT_NONE;                    // RTDD_EFFECT_DEFOCUS / _DESATURATION / _HAZE, kRefocus, kHazeEx, kStereo, kLensBlur, kRelight
+    enum : int { kRefocus = RTDD_EFFECT_HAZE + 1, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow };   // the extensions, after the public kinds
+    int kind = RTDD_EFFECT_NONE;                    // RTDD_EFFECT_DEFOCUS / _DESATURATION / _HAZE, kRefocus, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow
     const uint8_t *original = nullptr; size_t originalPitch = 0;
     const float *depth = nullptr; size_t depthPitch = 0;
     uint8_t *artistic = nullptr; size_t artisticPitch = 0;
@@ -106,6 +106,14 @@ struct Effect {
         float anchorDepth = 0.0f, invR2 = 0.0f;     // point
         float relief = 0.0f, ambient = 0.0f, k[3] = {0.0f, 0.0f, 0.0f};   // k[c] = diffuse * colour_c / 255 for c of B, G, R
     } light = {};
+    // relight with cast shadows (kRelightShadow: `light` too): the march as the host prepared it (include/rtdd.h
+    // rtdd_simulate_relight_shadowed), by value.  sx, sy, rise: a directional light's step along the major axis (sx == sy == 0: the
+    // light stands straight above, m == 0, every pixel is lit); a point light's are per pixel, the kernel's.
+    struct Shadow {
+        float sx = 0.0f, sy = 0.0f, rise = 0.0f;
+        int maxSteps = 0;
+        float bias = 0.0f, softness = 0.0f, strength = 0.0f;
+    } shadow = {};
 };
 
 // The defocus window scale K of src/GPUDepthEffect.cu:42, (int)(aperture * diagonal) -- double * float and the int products as there,
@@ -342,6 +350,8 @@ int launch_effect(rtdd_ctx *ctx, const Effect &e);
 int launch_lens_blur(rtdd_ctx *ctx, const Effect &e);
 // ---- relight.hip: Effect::kRelight (called by launch_effect) ---------------------------------------
 int launch_relight(rtdd_ctx *ctx, const Effect &e);
+// ---- relight_shadow.hip: Effect::kRelightShadow (called by launch_effect) --------------------------
+int launch_relight_shadow(rtdd_ctx *ctx, const Effect &e);
 
 // ---- cascade.hip -------------------------------------------------------------------------------
 int launch_bgr2gray(rtdd_ctx *ctx, const uint8_t *bgr, size_t bp, uint8_t *gray, size_t gp, int rows, int cols);
