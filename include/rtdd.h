@@ -17,7 +17,12 @@
  *
  * Pointer semantics are the reference's: every image pointer is a DEVICE pointer to pitched
  * row-major memory, pitch in BYTES next to it, rows/cols in pixels; u8x3 images are
- * interleaved (x*3+c); depth is f32, nominally in [0,255].  The library never allocates
+ * interleaved (x*3+c); depth is f32, nominally in [0,255].  A u8 image may start at any address
+ * and have any pitch that holds a row -- a region of interest of a larger image is a legal
+ * argument.  An f32 image (every depth map, and the f32 source and destination of
+ * rtdd_convert_to_float, rtdd_pyrup_depth, rtdd_depth_to_u8 and rtdd_index_to_weight) needs a
+ * pointer AND a pitch that are multiples of 4: every entry point that takes one returns
+ * RTDD_ERR_INVALID otherwise, before anything is launched.  The library never allocates
  * caller-visible memory.  No torch, no C++ types in any signature.
  */
 #ifndef RTDD_H

@@ -515,8 +515,8 @@ static int check_solve_args(rtdd_ctx *ctx, const float *depth, size_t depthPitch
                             const uint8_t *gray, size_t grayPitch, int rows, int cols, int level) {
     REQUIRE(ctx, depth && scribble && gray, "null image pointer");
     REQUIRE(ctx, rows > 0 && cols > 0, "rows and cols must be positive");
-    REQUIRE(ctx, depthPitch >= (size_t)cols * sizeof(float) && depthPitch % sizeof(float) == 0,
-        "depth pitch too small or not a multiple of 4");
+    REQUIRE(ctx, f32_image_aligned(depth, depthPitch), kF32AlignText);
+    REQUIRE(ctx, depthPitch >= (size_t)cols * sizeof(float), "depth pitch smaller than a row");
     REQUIRE(ctx, scribblePitch >= (size_t)cols && grayPitch >= (size_t)cols, "u8 pitch smaller than a row");
     if (ctx->levels.empty()) return fail(ctx, RTDD_ERR_STATE, "rtdd_allocate has not been called");
     if (!ctx->weights_loaded) return fail(ctx, RTDD_ERR_STATE, "rtdd_load_weights has not been called");
@@ -809,6 +809,7 @@ int rtdd_index_to_weight(rtdd_ctx *ctx, const uint8_t *gray, size_t grayPitch, c
     if (!ctx) return RTDD_ERR_INVALID;
     REQUIRE(ctx, gray && depth && index2, "null pointer");
     REQUIRE(ctx, rows > 0 && cols > 0 && grayPitch >= (size_t)cols && depthPitch >= (size_t)cols * 4, "bad size or pitch");
+    REQUIRE(ctx, f32_image_aligned(depth, depthPitch), kF32AlignText);
     if (ctx->maxLevel < 0) return fail(ctx, RTDD_ERR_STATE, "rtdd_allocate has not been called (maxLevel unknown)");
     DeviceGuard g(ctx->device);
     // reads a depth image a logged, unconfirmed solve may not have written (its copy-back stores nothing after a time-out) and is not
@@ -824,6 +825,7 @@ int rtdd_convert_to_float(rtdd_ctx *ctx, const uint8_t *src, size_t srcPitch, fl
     if (!ctx) return RTDD_ERR_INVALID;
     REQUIRE(ctx, src && dst && mask, "null image pointer");
     REQUIRE(ctx, rows >= 0 && cols >= 0, "negative size");
+    REQUIRE(ctx, f32_image_aligned(dst, dstPitch), kF32AlignText);
     if (rows == 0 || cols == 0) return RTDD_OK;
     REQUIRE(ctx, srcPitch >= (size_t)cols * 3 && dstPitch >= (size_t)cols * 4 && maskPitch >= (size_t)cols, "pitch smaller than a row");
     DeviceGuard g(ctx->device);
@@ -895,6 +897,7 @@ static int check_effect(rtdd_ctx *ctx, const void *a, const void *b, const void 
     REQUIRE(ctx, rows >= 0 && cols >= 0, "negative size");
     REQUIRE(ctx, (long long)rows * rows + (long long)cols * cols < 2147483647LL, "image too large");
     REQUIRE(ctx, op >= (size_t)cols * 3 && ap >= (size_t)cols * 3 && dp >= (size_t)cols * 4, "pitch smaller than a row");
+    REQUIRE(ctx, f32_image_aligned(b, dp), kF32AlignText);         // (b: the depth map)
     return RTDD_OK;
 }
 

@@ -826,6 +826,7 @@ int rtdd_pyrup_depth(rtdd_ctx *ctx, const float *src, size_t srcPitch, int rows,
     if (!ctx) return RTDD_ERR_INVALID;
     REQUIRE(ctx, src && dst && rows > 0 && cols > 0 && dstRows > 0 && dstCols > 0 && srcPitch >= (size_t)cols * 4
         && dstPitch >= (size_t)dstCols * 4, "bad argument");
+    REQUIRE(ctx, f32_image_aligned(src, srcPitch) && f32_image_aligned(dst, dstPitch), kF32AlignText);
     DeviceGuard g(ctx->device);
     // (as rtdd_index_to_weight: `src` may be the output of a logged solve whose persistent launch gave up -- the spelt-out cascade,
     // solve -> pyrUp -> inject -> solve, queued asynchronously)
@@ -837,6 +838,7 @@ int rtdd_pyrup_depth(rtdd_ctx *ctx, const float *src, size_t srcPitch, int rows,
 int rtdd_depth_to_u8(rtdd_ctx *ctx, const float *src, size_t srcPitch, uint8_t *dst, size_t dstPitch, int rows, int cols) {
     if (!ctx) return RTDD_ERR_INVALID;
     REQUIRE(ctx, src && dst && rows > 0 && cols > 0 && srcPitch >= (size_t)cols * 4 && dstPitch >= (size_t)cols, "bad argument");
+    REQUIRE(ctx, f32_image_aligned(src, srcPitch), kF32AlignText);
     DeviceGuard g(ctx->device);
     { const int rc_ = settle_pending(ctx); if (rc_ != RTDD_OK) return rc_; }     // (as rtdd_pyrup_depth)
     return launch_depth_to_u8(ctx, src, srcPitch, dst, dstPitch, rows, cols);

@@ -267,6 +267,10 @@ __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane
 #endif
 
 int fail(rtdd_ctx *ctx, int status, const char *what, hipError_t e = hipSuccess);
+// The f32 alignment contract of include/rtdd.h: every entry point that takes an f32 image refuses one whose pointer or pitch is no
+// multiple of 4 (the kernels read and write it as floats; u8 images are legal at any pointer and pitch).
+inline bool f32_image_aligned(const void *p, size_t pitch) { return (uintptr_t)p % sizeof(float) == 0 && pitch % sizeof(float) == 0; }
+constexpr const char *kF32AlignText = "an f32 image needs a pointer and a pitch that are multiples of 4";
 // a launch that can set one of the control words (sync_words) has been queued: the next synchronising call must look at them
 inline void note_status_writer(rtdd_ctx *ctx) { ctx->persistent_used = true; ctx->status_writer_behind = true; }
 // a guarded copy-back kernel (k_finish, k_pyrup_inject) for solve `seq` has been queued: it reports `seq` if it finds the words clear
