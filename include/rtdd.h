@@ -17,7 +17,11 @@
  *
  * Pointer semantics are the reference's: every image pointer is a DEVICE pointer to pitched
  * row-major memory, pitch in BYTES next to it, rows/cols in pixels; u8x3 images are
- * interleaved (x*3+c); depth is f32, nominally in [0,255].  A u8 image may start at any address
+ * interleaved (x*3+c); depth is f32, nominally in [0,255] -- but the solvers' results are the
+ * reference's arithmetic, bit for bit, for EVERY f32 depth: negative, huge, infinite or NaN, on
+ * free and on Dirichlet pixels (a buffer whose free pixels were never initialised is a legal
+ * input).  Only a NaN's sign and payload are left out of that promise, and for such inputs too
+ * the result depends on neither the sweep kernel nor the tile.  A u8 image may start at any address
  * and have any pitch that holds a row -- a region of interest of a larger image is a legal
  * argument.  An f32 image (every depth map, and the f32 source and destination of
  * rtdd_convert_to_float, rtdd_pyrup_depth, rtdd_depth_to_u8 and rtdd_index_to_weight) needs a
@@ -185,7 +189,10 @@ int rtdd_load_weights(rtdd_ctx *ctx, float beta);
 /* GPUMatrixFreeSolver(...) -- src/GPUSolver.cu:274-316.  Exactly maxIterations Chebyshev-Jacobi
  * sweeps on level `level`; depth is read (initial guess + Dirichlet values where scribble==255)
  * and overwritten with the result.  beta and tolerance are accepted and ignored, as in the
- * reference (src/GPUSolver.cu:274-275).  rows/cols must not exceed the level's allocation. */
+ * reference (src/GPUSolver.cu:274-275).  rows/cols must not exceed the level's allocation.
+ * The bits are the reference's arithmetic for every f32 depth, in range or not (a NaN's sign and
+ * payload excepted), whatever RTDD_OPT_SWEEP_KERNEL, RTDD_OPT_TILE and RTDD_OPT_TEMPORAL_DEPTH say:
+ * a mean whose weighted sum is +inf or overflows is +inf, clamped to 255, never a NaN clamped to 0. */
 int rtdd_matrix_free_solver(rtdd_ctx *ctx, float *depth, size_t depthPitch,
                             const uint8_t *scribble, size_t scribblePitch,
                             const uint8_t *gray, size_t grayPitch,
@@ -197,7 +204,8 @@ int rtdd_matrix_free_solver(rtdd_ctx *ctx, float *depth, size_t depthPitch,
 typedef struct rtdd_solve_params {
     int method;                     /* enum rtdd_method */
     int maxIterations;              /* upper bound on sweeps */
-    float tolerance;                /* stop when max|J(x)-x| over free pixels <= tolerance; <= 0: never */
+    float tolerance;                /* stop when max|J(x)-x| over free pixels <= tolerance; <= 0: never.  A free pixel whose
+                                     * |J(x)-x| is NaN counts as +inf: a map with a NaN in it never passes for converged */
     int checkEvery;                 /* residual is evaluated every checkEvery sweeps (0 = 16) */
     float relaxation;               /* RED_BLACK_GS only: SOR factor in (0,2), x <- clamp(x + relaxation (gs - x));
                                      * 0 or 1 = plain Gauss-Seidel; RTDD_RELAXATION_AUTO = SOR cycles.  Cycle c (e = min(c,6)),

@@ -407,6 +407,7 @@ ORC_API float orc_residual(const float *in, const int32_t *index2, const uint8_t
             float r = mean4(index2[2 * p] / 1000, index2[2 * p] % 1000, index2[2 * p + 1] / 1000,
                             index2[2 * p + 1] % 1000, lut, in, x, y, cols, contract);
             float d = fabsf(r - in[p]);
+            if (!(d >= 0.0f)) d = INFINITY;                              /* a NaN difference must not hide: it counts as +inf, as in k_residual */
             if (d > worst) worst = d;
         }
     return worst;
@@ -468,6 +469,7 @@ ORC_API float orc_residual_mt(const float *in, const int32_t *index2, const uint
             float r = mean4(index2[2 * p] / 1000, index2[2 * p] % 1000, index2[2 * p + 1] / 1000,
                             index2[2 * p + 1] % 1000, lut, in, x, y, cols, contract);
             float d = fabsf(r - in[p]);
+            if (!(d >= 0.0f)) d = INFINITY;                              /* a NaN difference must not hide: it counts as +inf, as in k_residual */
             if (d > worst) worst = d;
         }
     return worst;

@@ -668,6 +668,7 @@ static int solve_once(rtdd_ctx *ctx, float *depth, size_t depthPitch, const uint
     hipEvent_t *ev = ctx->ev + 4 * (ctx->prof_pending % rtdd_ctx::kProfSlots);
 
     if (prof) RTDD_HIP(ctx, hipEventRecord(ev[0], ctx->stream));
+    ctx->wild_seq = seq;                           // k_prepare tags depths outside the fast divide's domain with it; the sweep kernels compare (persist_sync.hpp kSyncWild)
     int rc = launch_prepare(ctx, L, ip, depth, depthPitch, scribble, scribblePitch, gray, grayPitch, rows, cols, level, t.batch);
     if (rc != RTDD_OK) return rc;
     if (prof) RTDD_HIP(ctx, hipEventRecord(ev[1], ctx->stream));
@@ -742,6 +743,7 @@ int rtdd::solve_with(rtdd_ctx *ctx, float *depth, size_t depthPitch, const uint8
         if (!ctx->healing) { const int rc_ = settle_pending(ctx); if (rc_ != RTDD_OK) return rc_; }
         RTDD_HIP(ctx, hipStreamSynchronize(ctx->stream));
         *(volatile int *)ctx->confirm_host = 0;
+        RTDD_HIP(ctx, hipMemset(ctx->sync_words + kSyncWild, 0, sizeof(int)));
         ctx->solve_seq = 0; ctx->publish_seq = 0;
     }
     const int seq = ++ctx->solve_seq;

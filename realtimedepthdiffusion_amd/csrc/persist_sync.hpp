@@ -17,6 +17,10 @@
 //   [kSyncConfirmPtr] (two ints, an address) where the copy-back kernels report the sequence number of a solve whose result they DID publish:
 //                    a word in page-locked host memory, so that the host can drop confirmed calls from its log without synchronising
 //                    (api.cpp prune_confirmed).  Written by one lane, only while the status word is clear.
+//   [kSyncWild]      sequence number of the most recent solve whose k_prepare met a depth that is not finite or is 2^100 or larger in
+//                    magnitude (solver_kernels.hip; a plain vector store, made only when such a value is found).  The register-blocked
+//                    sweep kernels compare it with their own solve's number and, when equal, run the variant with the full IEEE divide
+//                    and explicit absent neighbours (sweep_common.hpp div_tail).  Never cleared: sequence numbers do not repeat.
 //   [kSyncFlags ..]  one block counter per tile.  Monotonic over the life of the context: launch L's workgroups publish base_L + block
 //                    number, base_L handed in by the host (api.cpp prepare_persistent_launch), so nothing is zeroed between launches.
 #pragma once
@@ -27,7 +31,7 @@ namespace rtdd {
 // kSyncFlagStride: ints between the flags of consecutive tiles.  64 = one flag per 256 bytes (its own line, and neighbouring tiles on different memory channels): a tile's flag is stored once and polled
 // by up to 8 neighbours, all through memory (sc1); packed 32 to a line (round 2) every store and poll of 32 tiles met on one line: 1080p 1.17 -> 1.24 Tpx-it/s with one line each, +1.5 % more at 256 bytes.
 constexpr int kSyncStatus = 0, kSyncWithhold = 1, kSyncLimit = 2, kSyncNonLocal = 3 /* k_defocus_tile met windows beyond its region (effect_kernels.hip) */, kSyncFailedSeq = 4,
-              kSyncConfirmPtr = 6 /* two ints: the device address of the context's page-locked `confirmed sequence number` word */, kSyncFlags = 32, kSyncMaxTiles = 1024, kSyncFlagStride = 64;
+              kSyncConfirmPtr = 6 /* two ints: the device address of the context's page-locked `confirmed sequence number` word */, kSyncWild = 8, kSyncFlags = 32, kSyncMaxTiles = 1024, kSyncFlagStride = 64;
 constexpr int kSyncWords = kSyncFlags + kSyncMaxTiles * kSyncFlagStride;              // size of sync_words in ints
 constexpr unsigned long long kDefaultPollLimit = 20000000ull;      // 200 ms: legitimate waits are microseconds
 // Round 6: the FIRST thing a persistent workgroup does is announce itself (its flag := the launch's base value) and wait for its
@@ -37,7 +41,21 @@ constexpr unsigned long long kDefaultPollLimit = 20000000ull;      // 200 ms: le
 // exchanges behind the first keep the long bound: once every workgroup has been seen running, a long wait is no scheduling accident.
 constexpr unsigned long long kArrivalPollLimit = 150000ull;        // 1.5 ms
 
+// A depth of this magnitude or more (or a NaN) makes k_prepare raise kSyncWild.  An iterate that starts below it cannot reach an
+// overflowing numerator: the mean r is clamped to [0, 255], so x_{k+1} = 0.01 omega x_k + (1 - omega) x_{k-1} + 0.99 omega r is a
+// bounded forcing on a recurrence whose characteristic roots have modulus sqrt(omega - 1) < 1 for the schedule's omega in [1, 2) --
+// the iterates stay within a small multiple of the start, while a sum of four of them (weights <= 1) overflows only from 2^125 on,
+// and the 3-operation divide's q0 = n * y is within an ulp of a weighted mean, no larger than the largest of them.  Red-black: the
+// update is clamped to [0, 255] outright.  (tests/wild_depth.py: `magnitudes` runs just below the threshold, `huge` above it.)
+constexpr float kWildDepth = 0x1p100f;
+
 #ifdef __HIPCC__
+// true when depth value d must send its solve to the sweep kernels' full-divide variant (NaN compares false)
+__device__ __forceinline__ bool depth_is_wild(float d) { return !(__builtin_fabsf(d) < kWildDepth); }
+// The word a sweep kernel compares with its solve's number (k_prepare ran in an earlier launch of the same stream).  Read at the TOP
+// of the kernel, next to the tile loads: read where it is used, behind the setup, the load sits alone on every launch's critical
+// path while the chip's tile loads are in flight (4K, 125 launches per solve: 5 % slower; EXPERIMENTS.md).
+__device__ __forceinline__ int load_wild_word(const int *sync_words) { return sync_words[kSyncWild]; }
 // The kernels that publish a solve's result into the caller's buffers call this first (every thread; `first` = one thread of the
 // grid): true = a sweep launch in front of them gave up, store nothing.  The reference's solver always leaves a valid depth map
 // (src/GPUSolver.cu:311-314); here a failed solve leaves its INPUT in place so that the host can run it again.

@@ -25,7 +25,7 @@ __device__ __forceinline__ float from_prev_lane(float v) {          // (bound_ct
 __device__ __forceinline__ float from_next_lane(float v) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130, 0xF, 0xF, true));
 }
-__device__ __forceinline__ float div3(float n, float d, float y) {     // see sweep_blocked.hip: == RN(n/d) for normal d, n = 0 or |n| >= 2^-100
+__device__ __forceinline__ float div3(float n, float d, float y) {     // see sweep_common.hpp div_tail: == RN(n/d) for normal d, n = 0 or 2^-100 <= |n|, n and n*y finite (else: the full divide, persist_sync.hpp kSyncWild)
     const float q0 = n * y;
     const float r = __builtin_fmaf(-d, q0, n);
     return __builtin_fmaf(r, y, q0);
@@ -54,7 +54,7 @@ __device__ __forceinline__ void store_sc1(float4 *p, float4 v) {
 template <int LX, int NT, int G, bool CONTRACT, bool SOR, bool PERSIST>
 __global__ __launch_bounds__(NT, 4) void k_rbgs_blocked(float *X, float *Y, const uint32_t *__restrict__ M,
                                                         const float *__restrict__ lut_g, int ip, int rows, int cols, int hx, int hy, int nsweeps, float omega, int gx, int gy, int xcd_tiles,
-                                                        int block_sweeps, int *sync_words, int flag_base) {
+                                                        int block_sweeps, int *sync_words, int flag_base, int wild_seq) {
     static_assert(G % 2 == 0, "the compile-time colour pattern needs an even number of rows per thread");
     constexpr int EW = 4 * LX, NTR = NT / LX;
     typedef float f4r __attribute__((ext_vector_type(4)));
@@ -92,6 +92,7 @@ __global__ __launch_bounds__(NT, 4) void k_rbgs_blocked(float *X, float *Y, cons
     float wr[G][4], wd[G][4], wl0[G], wu0[4], cnt[G][4], rcp[G][4];
     uint32_t dirichlet = 0;
     bool unsafe = false;
+    const int wild_word = load_wild_word(sync_words);     // (persist_sync.hpp kSyncWild: in flight with the tile)
 #pragma unroll
     for (int g = 0; g < G; g++) {
         const int y = y0 + g;
@@ -133,7 +134,8 @@ __global__ __launch_bounds__(NT, 4) void k_rbgs_blocked(float *X, float *Y, cons
             rcp[g][i] = rcp_rn(cnt[g][i]);
             unsafe |= cnt[g][i] < 0x1p-126f;
         }
-    const bool wave_unsafe = __builtin_amdgcn_ballot_w64(unsafe) != 0;
+    // (or the solve's input holds depths outside the 3-operation divide's domain: persist_sync.hpp kSyncWild)
+    const bool wave_unsafe = __builtin_amdgcn_ballot_w64(unsafe) != 0 || wild_word == wild_seq;
 
     // One half-sweep, written like sweep_blocked.hip's sweep body (see the comments there): the pixels of the colour in two GROUPS
     // of rows -- the thread's first and last row, whose new values the neighbouring thread rows need, then the interior rows --,
@@ -159,8 +161,12 @@ __global__ __launch_bounds__(NT, 4) void k_rbgs_blocked(float *X, float *Y, cons
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         // the first / last thread row reads its OWN published row instead of a row above / below (finite, and either weighted 0 or discarded halo)
-        const float4 up4 = edge[C][tr > 0 ? tr - 1 : 0][tr > 0 ? 1 : 0][lx];
-        const float4 dn4 = edge[C][tr < ntr - 1 ? tr + 1 : tr][tr < ntr - 1 ? 0 : 1][lx];
+        float4 up4 = edge[C][tr > 0 ? tr - 1 : 0][tr > 0 ? 1 : 0][lx];
+        float4 dn4 = edge[C][tr < ntr - 1 ? tr + 1 : tr][tr < ntr - 1 ? 0 : 1][lx];
+        // The full-divide variant also runs on infinities and NaNs, where 0 * x is no longer 0, and a Gauss-Seidel update REPLACES such a
+        // pixel, so its own row read as the "row above" would poison it: the stand-ins for absent neighbours are 0 there (here and in
+        // the lane shifts below) -- each is a neighbour the reference skips at the image border, or discarded halo.
+        if (!FAST) { if (tr == 0) up4 = make_float4(0, 0, 0, 0); if (tr == ntr - 1) dn4 = make_float4(0, 0, 0, 0); }
         const float up[4] = {up4.x, up4.y, up4.z, up4.w}, dn[4] = {dn4.x, dn4.y, dn4.z, dn4.w};
         float xl0[G], xr3[G];
         auto wsum = [&](int g, int i) {
@@ -184,8 +190,8 @@ __global__ __launch_bounds__(NT, 4) void k_rbgs_blocked(float *X, float *Y, cons
             for (int g = 0; g < G; g++) {
                 if (!pick(g)) continue;
                 // a pixel of colour C in column 0 / 3 needs the neighbouring lane's value (of the other colour: not touched by this half-sweep)
-                if (((g + 0) & 1) == C) xl0[g] = from_prev_lane(a[g][3]);
-                if (((g + 3) & 1) == C) xr3[g] = from_next_lane(a[g][0]);
+                if (((g + 0) & 1) == C) { xl0[g] = from_prev_lane(a[g][3]); if (!FAST && lx == 0) xl0[g] = 0.0f; }
+                if (((g + 3) & 1) == C) { xr3[g] = from_next_lane(a[g][0]); if (!FAST && lx == LX - 1) xr3[g] = 0.0f; }
 #pragma unroll
                 for (int i = 0; i < 4; i++) {
                     if (((g + i) & 1) != C) continue;
@@ -363,8 +369,8 @@ int launch_rbgs_blocked(rtdd_ctx *ctx, const Level &L, size_t ip, int rows, int 
         const bool sor = omega != 1.0f;
         const int xcd_tiles = single ? 0 : ((int)(grid.x * grid.y) + 7) / 8;
         const dim3 launch_grid = xcd_tiles > 0 ? dim3(8 * xcd_tiles) : grid;
-#define RTDD_RBGS_GO(NT_, C_, S_) do { if (persistent) hipLaunchKernelGGL((k_rbgs_blocked<32, NT_, 4, C_, S_, true>), launch_grid, dim3(nthreads), 0, ctx->stream, X, Y, L.M(ip), ctx->lut_dev, (int)ip, rows, cols, hx, hy, m, omega, (int)grid.x, (int)grid.y, xcd_tiles, block_sweeps, ctx->sync_words, flag_base); \
-        else hipLaunchKernelGGL((k_rbgs_blocked<32, NT_, 4, C_, S_, false>), launch_grid, dim3(nthreads), 0, ctx->stream, X, Y, L.M(ip), ctx->lut_dev, (int)ip, rows, cols, hx, hy, m, omega, (int)grid.x, (int)grid.y, xcd_tiles, block_sweeps, ctx->sync_words, flag_base); } while (0)
+#define RTDD_RBGS_GO(NT_, C_, S_) do { if (persistent) hipLaunchKernelGGL((k_rbgs_blocked<32, NT_, 4, C_, S_, true>), launch_grid, dim3(nthreads), 0, ctx->stream, X, Y, L.M(ip), ctx->lut_dev, (int)ip, rows, cols, hx, hy, m, omega, (int)grid.x, (int)grid.y, xcd_tiles, block_sweeps, ctx->sync_words, flag_base, ctx->wild_seq); \
+        else hipLaunchKernelGGL((k_rbgs_blocked<32, NT_, 4, C_, S_, false>), launch_grid, dim3(nthreads), 0, ctx->stream, X, Y, L.M(ip), ctx->lut_dev, (int)ip, rows, cols, hx, hy, m, omega, (int)grid.x, (int)grid.y, xcd_tiles, block_sweeps, ctx->sync_words, flag_base, ctx->wild_seq); } while (0)
         const int variant = (big ? 4 : 0) | (ctx->opt.fp_contract ? 2 : 0) | (sor ? 1 : 0);
         switch (variant) {
             case 0: RTDD_RBGS_GO(512, false, false); break;

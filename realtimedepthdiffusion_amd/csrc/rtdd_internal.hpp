@@ -219,6 +219,8 @@ struct rtdd_ctx {
     rtdd_solve_info last_info{};    // of the most recent solve; kernel/tile/temporal_depth/persistent are filled in by the sweep launchers
     // Self-healing after RTDD_ERR_TIMEOUT (api.cpp heal_pending): every solve / estimate since the last status check, in call order
     int solve_seq = 0;              // sequence number of the most recent rtdd_solve_ex (1 .. 2^30, never 0)
+    int wild_seq = -1;              // the number the solve being queued hands k_prepare and its sweep kernels (persist_sync.hpp kSyncWild);
+                                    // -1 outside a solve (the diagnostics of scripts/ubench launch sweeps directly): never the word's value
     std::vector<rtdd::PendingOp> pending;
     bool pending_overflow = false;  // more than kMaxPendingOps calls without a synchronisation: a timeout among them is reported, not healed
     bool healing = false;           // a replay is running: nothing is logged, a second timeout is final

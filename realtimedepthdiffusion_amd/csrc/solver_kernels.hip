@@ -41,7 +41,7 @@ __global__ __launch_bounds__(256) void k_prepare(const float *__restrict__ depth
                                                  const uint8_t *__restrict__ gray, size_t grayPitch,
                                                  float *__restrict__ X0, float *__restrict__ X1,
                                                  uint32_t *__restrict__ M, int ip, int rows, int cols, int gated, int thr,
-                                                 size_t zDepth, size_t zScribble, size_t zGray, size_t zPlane) {
+                                                 size_t zDepth, size_t zScribble, size_t zGray, size_t zPlane, int *sync_words, int wild_seq) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     const int y = blockIdx.y * 4 + wave_id();
     if (x >= cols || y >= rows) return;
@@ -64,6 +64,7 @@ __global__ __launch_bounds__(256) void k_prepare(const float *__restrict__ depth
         }
     }
     const size_t p = (size_t)y * ip + x;
+    if (depth_is_wild(d)) sync_words[kSyncWild] = wild_seq;      // (persist_sync.hpp: the blocked sweeps then take their full-divide variant)
     X0[p] = d;
     X1[p] = dirichlet ? d : 0.0f;     // x_{-1} = 0 on free pixels (cudaMemset, :290); Dirichlet value in both planes (:291-292)
     M[p] = (uint32_t)right | ((uint32_t)down << 8) | (dirichlet ? kMetaDirichlet : 0u);
@@ -77,7 +78,7 @@ __global__ __launch_bounds__(256) void k_prepare4(const float *__restrict__ dept
                                                   const uint8_t *__restrict__ gray, size_t grayPitch,
                                                   float *__restrict__ X0, float *__restrict__ X1,
                                                   uint32_t *__restrict__ M, int ip, int rows, int cols, int gated, int thr,
-                                                  size_t zDepth, size_t zScribble, size_t zGray, size_t zPlane) {
+                                                  size_t zDepth, size_t zScribble, size_t zGray, size_t zPlane, int *sync_words, int wild_seq) {
     const int x0 = 4 * (blockIdx.x * 64 + (threadIdx.x & 63));
     const int y = blockIdx.y * 4 + wave_id();
     if (x0 >= cols || y >= rows) return;
@@ -130,6 +131,8 @@ __global__ __launch_bounds__(256) void k_prepare4(const float *__restrict__ dept
         x1v[i] = dirichlet ? d[i] : 0.0f;
         mv[i] = (uint32_t)right | ((uint32_t)down << 8) | (dirichlet ? kMetaDirichlet : 0u);
     }
+    // (pixels past the end of a ragged row were loaded as 0)
+    if (depth_is_wild(d[0]) || depth_is_wild(d[1]) || depth_is_wild(d[2]) || depth_is_wild(d[3])) sync_words[kSyncWild] = wild_seq;
     const size_t p = (size_t)y * ip + x0;          // the planes' rows are 256-byte aligned and padded: whole 16-byte stores always fit; columns >= cols are never read as pixels
     *(float4 *)(X0 + p) = make_float4(x0v[0], x0v[1], x0v[2], x0v[3]);
     *(float4 *)(X1 + p) = make_float4(x1v[0], x1v[1], x1v[2], x1v[3]);
@@ -410,10 +413,10 @@ int launch_prepare(rtdd_ctx *ctx, const Level &L, size_t ip, const float *depth,
                          ((uintptr_t)scribble % 4 == 0) && scribblePitch % 4 == 0 && B.depth % 16 == 0 && B.gray % 4 == 0 && B.scribble % 4 == 0;
     if (aligned)
         hipLaunchKernelGGL(k_prepare4, grid64x4(rows, (cols + 3) / 4, B.n), dim3(256), 0, ctx->stream, depth, depthPitch, scribble, scribblePitch,
-                           gray, grayPitch, L.P(0, ip), L.P(1, ip), L.M(ip), (int)ip, rows, cols, gated, thr, B.depth, B.scribble, B.gray, zP);
+                           gray, grayPitch, L.P(0, ip), L.P(1, ip), L.M(ip), (int)ip, rows, cols, gated, thr, B.depth, B.scribble, B.gray, zP, ctx->sync_words, ctx->wild_seq);
     else
         hipLaunchKernelGGL(k_prepare, grid64x4(rows, cols, B.n), dim3(256), 0, ctx->stream, depth, depthPitch, scribble, scribblePitch,
-                           gray, grayPitch, L.P(0, ip), L.P(1, ip), L.M(ip), (int)ip, rows, cols, gated, thr, B.depth, B.scribble, B.gray, zP);
+                           gray, grayPitch, L.P(0, ip), L.P(1, ip), L.M(ip), (int)ip, rows, cols, gated, thr, B.depth, B.scribble, B.gray, zP, ctx->sync_words, ctx->wild_seq);
     RTDD_LAUNCH_CHECK(ctx, "k_prepare");
     return RTDD_OK;
 }

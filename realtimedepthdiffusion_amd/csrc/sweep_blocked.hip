@@ -64,7 +64,7 @@ __global__ __launch_bounds__(NT, (NT >= 1024 || G <= 3 ? 4 : G <= 4 ? 3 : 2)) vo
                                                       const uint32_t *__restrict__ M, const float *__restrict__ lut_g,
                                                       const float *__restrict__ omegas, int ip, int rows, int cols,
                                                       int hx, int hy, int nsweeps, float gamma,
-                                                      int block_sweeps, int *sync_words, int gx, int gy, int xcd_tiles, int flag_base, size_t zPlane) {
+                                                      int block_sweeps, int *sync_words, int gx, int gy, int xcd_tiles, int flag_base, size_t zPlane, int wild_seq) {
     // block_sweeps == nsweeps: the plain time-blocked launch (results -> Yk/Ym).
     // block_sweeps <  nsweeps: PERSISTENT mode -- the workgroup keeps its tile in registers for the whole solve and,
     // every block_sweeps (= halo width, even) sweeps, trades halo strips with its 8 neighbours through memory instead
@@ -111,6 +111,7 @@ __global__ __launch_bounds__(NT, (NT >= 1024 || G <= 3 ? 4 : G <= 4 ? 3 : 2)) vo
 
     // ---- load the extended tile once: every load is issued BEFORE the weight table is staged in LDS and the barrier behind it, so
     // that a launch pays one memory round trip, not two in a row (launch-per-block: 125 launches per 1000 sweeps at 4K) ------------
+    const int wild_word = load_wild_word(sync_words);     // (persist_sync.hpp kSyncWild: in flight with the tile)
     float4 vxr[G], vpr[G];
     uint4 mr[G], mup = make_uint4(0, 0, 0, 0);
 #pragma unroll
@@ -317,7 +318,7 @@ __global__ __launch_bounds__(NT, (NT >= 1024 || G <= 3 ? 4 : G <= 4 ? 3 : 2)) vo
 template <bool CONTRACT>
 __global__ __launch_bounds__(1024) void k_sweep_col(const float *__restrict__ Xk, const float *__restrict__ Xm, float *__restrict__ Yk, float *__restrict__ Ym,
                                                     const uint32_t *__restrict__ M, const float *__restrict__ lut_g, const float *__restrict__ omegas,
-                                                    int ip, int rows, int cols, int hx, int hy, int nsweeps, float gamma, int gx, int gy, int xcd_tiles, int *sync_words, size_t zPlane) {
+                                                    int ip, int rows, int cols, int hx, int hy, int nsweeps, float gamma, int gx, int gy, int xcd_tiles, int *sync_words, size_t zPlane, int wild_seq) {
     constexpr int R = 4;
     RTDD_Z(Xk, zPlane); RTDD_Z(Xm, zPlane); RTDD_Z(Yk, zPlane); RTDD_Z(Ym, zPlane); RTDD_Z(M, zPlane);
     __shared__ float lut[257];
@@ -340,6 +341,7 @@ __global__ __launch_bounds__(1024) void k_sweep_col(const float *__restrict__ Xk
     bool dir[R], unsafe = false;
     // The tile's loads are issued BEFORE the weight table is staged in LDS, so that the launch pays one memory round trip, not two in a
     // row (these levels are 36 + 21 launches of ~13.6 us: -0.7 us each).
+    const int wild_word = load_wild_word(sync_words);     // (persist_sync.hpp kSyncWild: in flight with the tile)
     uint32_t mraw[R], mup = 0;
 #pragma unroll
     for (int g = 0; g < R; g++) {
@@ -380,7 +382,7 @@ __global__ __launch_bounds__(1024) void k_sweep_col(const float *__restrict__ Xk
         rcp[g] = rcp_rn(cnt[g]);
         unsafe |= cnt[g] < 0x1p-126f;
     }
-    const bool wave_unsafe = __builtin_amdgcn_ballot_w64(unsafe) != 0;
+    const bool wave_unsafe = __builtin_amdgcn_ballot_w64(unsafe) != 0 || wild_word == wild_seq;     // (as k_sweep_blocked)
     constexpr uint32_t kTinyT = 2u * 0x0D800000u - 1u;
     const int up_w = wv > 0 ? wv - 1 : wv, dn_w = wv < nwv - 1 ? wv + 1 : wv;
     // (the first / last wave reads its own row instead of a missing neighbour: weighted 0 at the image border, discarded halo elsewhere)
@@ -560,7 +562,7 @@ static void launch_cfg(rtdd_ctx *ctx, dim3 grid, int xcd_tiles, int nthreads, fl
                        const float *omegas, int ip, int rows, int cols, int hx, int hy, int n, float gamma, int block_sweeps, int flag_base, size_t zPlane, int images) {
     const bool persist = block_sweeps < n;
     const dim3 launch_grid = xcd_tiles > 0 ? dim3(8 * xcd_tiles, 1, images) : dim3(grid.x, grid.y, images);
-#define RTDD_LAUNCH(C, P) hipLaunchKernelGGL((k_sweep_blocked<LX, NT, G, C, P>), launch_grid, dim3(nthreads), 0, ctx->stream, Xk, Xm, Yk, Ym, M, ctx->lut_dev, omegas, ip, rows, cols, hx, hy, n, gamma, block_sweeps, ctx->sync_words, (int)grid.x, (int)grid.y, xcd_tiles, flag_base, zPlane)
+#define RTDD_LAUNCH(C, P) hipLaunchKernelGGL((k_sweep_blocked<LX, NT, G, C, P>), launch_grid, dim3(nthreads), 0, ctx->stream, Xk, Xm, Yk, Ym, M, ctx->lut_dev, omegas, ip, rows, cols, hx, hy, n, gamma, block_sweeps, ctx->sync_words, (int)grid.x, (int)grid.y, xcd_tiles, flag_base, zPlane, ctx->wild_seq)
     if (ctx->opt.fp_contract) { if (persist) RTDD_LAUNCH(true, true); else RTDD_LAUNCH(true, false); }
     else { if (persist) RTDD_LAUNCH(false, true); else RTDD_LAUNCH(false, false); }
 #undef RTDD_LAUNCH
@@ -757,8 +759,8 @@ static int launch_sweeps_blocked_impl(rtdd_ctx *ctx, const Level &L, size_t ip, 
     case id: launch_cfg<LX_, NT_, G_>(ctx, grid, xcd_tiles, nthreads, Xk, Xm, Yk, Ym, L.M(ip), omegas_dev + done, (int)ip, rows, cols, hx, hy, m, gamma, block_sweeps, flag_base, zPlane, images); break;
         if (is_col_tile(tile)) {
             const dim3 launch_grid = xcd_tiles > 0 ? dim3(8 * xcd_tiles, 1, images) : dim3(grid.x, grid.y, images);
-            if (ctx->opt.fp_contract) hipLaunchKernelGGL(k_sweep_col<true>, launch_grid, dim3(nthreads), 0, ctx->stream, Xk, Xm, Yk, Ym, L.M(ip), ctx->lut_dev, omegas_dev + done, (int)ip, rows, cols, hx, hy, m, gamma, (int)grid.x, (int)grid.y, xcd_tiles, ctx->sync_words, zPlane);
-            else hipLaunchKernelGGL(k_sweep_col<false>, launch_grid, dim3(nthreads), 0, ctx->stream, Xk, Xm, Yk, Ym, L.M(ip), ctx->lut_dev, omegas_dev + done, (int)ip, rows, cols, hx, hy, m, gamma, (int)grid.x, (int)grid.y, xcd_tiles, ctx->sync_words, zPlane);
+            if (ctx->opt.fp_contract) hipLaunchKernelGGL(k_sweep_col<true>, launch_grid, dim3(nthreads), 0, ctx->stream, Xk, Xm, Yk, Ym, L.M(ip), ctx->lut_dev, omegas_dev + done, (int)ip, rows, cols, hx, hy, m, gamma, (int)grid.x, (int)grid.y, xcd_tiles, ctx->sync_words, zPlane, ctx->wild_seq);
+            else hipLaunchKernelGGL(k_sweep_col<false>, launch_grid, dim3(nthreads), 0, ctx->stream, Xk, Xm, Yk, Ym, L.M(ip), ctx->lut_dev, omegas_dev + done, (int)ip, rows, cols, hx, hy, m, gamma, (int)grid.x, (int)grid.y, xcd_tiles, ctx->sync_words, zPlane, ctx->wild_seq);
         } else
         switch (tile) { RTDD_ALL_TILES }
 #undef RTDD_TILE_CASE

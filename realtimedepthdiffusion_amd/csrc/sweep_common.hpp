@@ -59,8 +59,14 @@ __device__ __forceinline__ void store_result(float4 *p, float4 v) { *p = v; }
 // numerator significands (scripts/ubench/div_exhaustive.hip, 1.4e14 pairs, 0 mismatches, 71 s; log in
 // profiles/).  Powers of two scale every intermediate exactly, so that covers all operands for which no
 // intermediate under/overflows: d normal (<= 4 here), n == 0 or |n| >= 2^-100 (then q0 is normal and the
-// remainder, a multiple of 2^(e_n - 47), is exactly representable), n/d bounded (a weighted mean).
-// Anything else takes the full divide under a wave-uniform branch.
+// remainder, a multiple of 2^(e_n - 47), is exactly representable), n/d bounded (a weighted mean) and n finite: with n = +-inf, or a
+// sum or n*y that overflows, fma(-d, inf, inf) is NaN where the IEEE quotient is +-inf, and the clamp behind it turns that NaN into 0
+// and +inf into 255.
+// Anything else takes the full divide under a wave-uniform branch.  Three guards send a wave there: a divisor below 2^-126 (tested per
+// launch), a numerator below 2^-100 (tested per group of rows, sweep_tile_sweeps.inc), and -- the upper end of the domain -- a solve
+// whose INPUT holds a depth that is not finite or is 2^100 or more in magnitude: k_prepare reads every depth anyway and raises a
+// launch-wide flag that every wave of the sweep kernels ORs into its choice (persist_sync.hpp kSyncWild, where it is also shown that
+// an iterate that starts below that threshold never reaches an overflowing numerator).  Nothing per sweep.
 __device__ __forceinline__ float div_tail(float n, float d, float y) {
     const float q0 = n * y;
     const float r = __builtin_fmaf(-d, q0, n);

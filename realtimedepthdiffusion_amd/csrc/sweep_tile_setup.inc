@@ -88,7 +88,8 @@
         }
         finish_setup();
     }
-    const bool wave_unsafe = __builtin_amdgcn_ballot_w64(unsafe) != 0;
+    // (or the solve's input holds depths outside the 3-operation divide's domain: persist_sync.hpp kSyncWild)
+    const bool wave_unsafe = __builtin_amdgcn_ballot_w64(unsafe) != 0 || wild_word == wild_seq;
     // the update's last operation runs under an EXEC mask of the FREE pixels (sweep_common.hpp masked_fmac4): one lane mask per pixel
     // of the thread, in SGPR pairs (where the v_cndmask form kept its masks), and a Dirichlet pixel's value in BOTH iterates
     unsigned long long free_mask[G][4];

@@ -56,15 +56,23 @@
         RTDD_TL(0, s);
         // The first / last thread row of the tile has no row above / below in LDS: it reads its OWN published row instead (any
         // finite value will do -- the weight towards it is 0 at the image border, and elsewhere that row is discarded halo), which
-        // keeps the two loads unconditional: no lane masks, no zero-filling moves.
+        // keeps the two loads unconditional: no lane masks, no zero-filling moves.  (Not finite: the full-divide variant, below.)
         float xl0[G], xr3[G];                    // filled per group (each costs a register until its row is done)
         // the values a row needs from the neighbouring lanes: the previous lane's wr[g][3] * cur[g][3] (the whole left term of pixel 0)
         // and the next lane's cur[g][0].  They depend on x_k only, so they are requested before the rows that use them are started.
-        auto shifts = [&](int g) { xl0[g] = lds_from_prev(prev4, wr[g][3] * cur[g][3]); xr3[g] = lds_from_next(prev4, cur[g][0]); };
+        // The full-divide variant also runs on inputs with infinities and NaNs (persist_sync.hpp kSyncWild), where 0 * x is no longer 0:
+        // what a tile row's first lane receives from the lane before it and its last lane from the lane behind it, and (below) the rows
+        // the first / last thread row reads in place of a row above / below, are 0 there -- each is an absent neighbour at the image
+        // border, which the reference skips, or discarded halo.
+        auto shifts = [&](int g) {
+            xl0[g] = lds_from_prev(prev4, wr[g][3] * cur[g][3]); xr3[g] = lds_from_next(prev4, cur[g][0]);
+            if (!FAST) { xl0[g] = lx == 0 ? 0.0f : xl0[g]; xr3[g] = lx == LX - 1 ? 0.0f : xr3[g]; }
+        };
         shifts(0); if (G > 1) shifts(G - 1);                 // in flight during the wait for the neighbouring waves' rows
         await(s);
-        const float4 up4 = edge[buf][tr > 0 ? tr - 1 : 0][G > 1 && tr > 0 ? 1 : 0][lx];
-        const float4 dn4 = edge[buf][tr < ntr - 1 ? tr + 1 : tr][G == 1 || tr < ntr - 1 ? 0 : 1][lx];
+        float4 up4 = edge[buf][tr > 0 ? tr - 1 : 0][G > 1 && tr > 0 ? 1 : 0][lx];
+        float4 dn4 = edge[buf][tr < ntr - 1 ? tr + 1 : tr][G == 1 || tr < ntr - 1 ? 0 : 1][lx];
+        if (!FAST) { if (tr == 0) up4 = make_float4(0, 0, 0, 0); if (tr == ntr - 1) dn4 = make_float4(0, 0, 0, 0); }
         const float up[4] = {up4.x, up4.y, up4.z, up4.w}, dn[4] = {dn4.x, dn4.y, dn4.z, dn4.w};
         RTDD_TL_ROWS_IN_HAND(s);
         // omega and gamma in VGPRs: an fma with an SGPR operand issues at 4.3 cycles per wave-instruction, with three VGPRs at 3.1
