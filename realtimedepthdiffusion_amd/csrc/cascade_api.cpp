@@ -229,9 +229,6 @@ void pyramid_free(rtdd_ctx *ctx) {
 
 using namespace rtdd;
 
-#define REQUIRE(ctx, cond, msg) \
-    do { if (!(cond)) return fail((ctx), RTDD_ERR_INVALID, msg); } while (0)
-
 #pragma GCC visibility push(default)
 extern "C" {
 
@@ -259,7 +256,7 @@ int rtdd_pyramid_create_batch(rtdd_ctx *ctx, int rows, int cols, int images) {
     REQUIRE(ctx, rows > 0 && cols > 0, "rows and cols must be positive");
     REQUIRE(ctx, images >= 1 && images <= 4096, "the batch must hold 1..4096 images");
     DeviceGuard g(ctx->device);
-    { const int rc_ = settle_pending(ctx); if (rc_ != RTDD_OK) return rc_; }
+    RTDD_TRY(settle_pending(ctx));
     RTDD_HIP(ctx, hipStreamSynchronize(ctx->stream));
     pyramid_free(ctx);
     Pyramid *p = new (std::nothrow) Pyramid();
@@ -293,7 +290,7 @@ int rtdd_pyramid_create_batch(rtdd_ctx *ctx, int rows, int cols, int images) {
 int rtdd_pyramid_destroy(rtdd_ctx *ctx) {
     if (!ctx) return RTDD_ERR_INVALID;
     DeviceGuard g(ctx->device);
-    { const int rc_ = settle_pending(ctx); if (rc_ != RTDD_OK) return rc_; }
+    RTDD_TRY(settle_pending(ctx));
     RTDD_HIP(ctx, hipStreamSynchronize(ctx->stream));
     pyramid_free(ctx);
     return RTDD_OK;
@@ -306,7 +303,7 @@ int rtdd_pyramid_set_image(rtdd_ctx *ctx, const uint8_t *bgr, size_t pitch) {
     REQUIRE(ctx, bgr && pitch >= (size_t)p->cols * 3, "bad image");
     DeviceGuard g(ctx->device);
     // (a new image resets the warm-start state a logged estimate ran on)
-    { const int rc_ = settle_pending(ctx); if (rc_ != RTDD_OK) return rc_; }
+    RTDD_TRY(settle_pending(ctx));
     const int b = p->sel;                          // (a batched pyramid: the selected image)
     RTDD_HIP(ctx, hipMemcpy2DAsync(p->original.at(b), p->original.pitch, bgr, pitch, (size_t)p->cols * 3, p->rows, hipMemcpyDeviceToDevice,
         ctx->stream));
@@ -322,10 +319,8 @@ int rtdd_pyramid_set_image(rtdd_ctx *ctx, const uint8_t *bgr, size_t pitch) {
             hipMemsetAsync(p->scribble[l].at(b), 0, p->scribble[l].pitch * p->scribble[l].rows, ctx->stream));
         if (l > 0 && p->edited[l].ptr) RTDD_HIP(ctx,
             hipMemsetAsync(p->edited[l].at(b), 0, p->edited[l].pitch * p->edited[l].rows, ctx->stream));
-        if (p->depth[l].rows > 0 && p->depth[l].cols > 0) {
-            const int rc_ = launch_fill_f32(ctx, (float *)p->depth[l].at(b), p->depth[l].pitch, p->depth[l].rows, p->depth[l].cols, 255.0f);
-            if (rc_ != RTDD_OK) return rc_;
-        }
+        if (p->depth[l].rows > 0 && p->depth[l].cols > 0)
+            RTDD_TRY(launch_fill_f32(ctx, (float *)p->depth[l].at(b), p->depth[l].pitch, p->depth[l].rows, p->depth[l].cols, 255.0f));
     }
     int rc = launch_bgr2gray(ctx, (const uint8_t *)p->original.at(b), p->original.pitch, (uint8_t *)p->gray[0].at(b), p->gray[0].pitch,
         p->rows, p->cols);
@@ -412,18 +407,13 @@ static int estimate_submit(rtdd_ctx *ctx, int maxIterations, unsigned long long 
         p->annotation_dirty = false; p->annotation_rebuild = false;
     }
     PendingOp op;
-    op.annotation = annotation;
-    op.kind = PendingOp::kEstimate; op.opt = ctx->opt; op.maxIterations = maxIterations;
-    op.batch_first = first; op.batch_n = n; op.live = live;
-    rc = estimate_levels(ctx, maxIterations, P - 1, op.level_seq, first, n, live);
+    op.kind = PendingOp::kEstimate; op.opt = ctx->opt;
+    PendingOp::Estimate &e = op.estimate;
+    e.annotation = annotation; e.maxIterations = maxIterations;
+    e.batch_first = first; e.batch_n = n; e.live = live;
+    rc = estimate_levels(ctx, maxIterations, P - 1, e.level_seq, first, n, live);
     if (rc == RTDD_OK && live.effect) rc = live_effect(ctx, live);      // src/main.cpp:190-230: the sticky effect, on this frame's map
-    if (rc == RTDD_OK && !ctx->healing && ctx->opt.timeout_heal) {
-        prune_confirmed(ctx);
-        if (ctx->pending.size() >= kMaxPendingOps) { ctx->pending.clear(); ctx->pending_overflow = true; }
-        op.id = ++ctx->op_counter;
-        if (op_id) *op_id = op.id;
-        ctx->pending.push_back(op);
-    }
+    if (rc == RTDD_OK && log_call(ctx, op) && op_id) *op_id = op.id;
     return rc;
 }
 
@@ -531,7 +521,7 @@ int rtdd_live_wait(rtdd_ctx *ctx) {
     else {
         // (a frame with one part stored / queued on the compute stream and the other staged: the one event behind both was recorded there)
         RTDD_HIP(ctx, hipEventSynchronize(fr.direct ? v->d2h_done[k] : v->est_done[k]));
-        { const int rc_ = live_fetch(ctx, v, k, fetch_map, fetch_art); if (rc_ != RTDD_OK) return rc_; }
+        RTDD_TRY(live_fetch(ctx, v, k, fetch_map, fetch_art));
     }
     // the usual case: the frame is good, and so is everything logged before it
     if (v->status_host[8 * k + kSyncStatus] == 0) {
@@ -554,7 +544,7 @@ int rtdd_live_wait(rtdd_ctx *ctx) {
         const int j = (int)(f % 2);
         // (a frame whose map the copy-back kernel stores in the host's buffer itself has just been run again into that buffer; an
         // artistic image is always rendered into its staging slot)
-        { const int rc_ = live_fetch(ctx, v, j, !v->frame[j].direct, true); if (rc_ != RTDD_OK) return rc_; }
+        RTDD_TRY(live_fetch(ctx, v, j, !v->frame[j].direct, true));
         v->status_host[8 * j + kSyncStatus] = 0;
     }
     v->frame[k].in_flight = false; v->waited++;
@@ -711,10 +701,9 @@ int estimate_levels(rtdd_ctx *ctx, int maxIterations, int from_level, int *level
             rtdd_solve_params sp;
             sp.method = RTDD_METHOD_CHEBYSHEV_JACOBI; sp.maxIterations = iters; sp.tolerance = 0.0f; sp.checkEvery = 0;
             sp.relaxation = 0.0f;
-            rc = solve_with(ctx, (float *)p->depth[l].at(first), p->depth[l].pitch, (const uint8_t *)p->scribble[l].at(first),
-                p->scribble[l].pitch,
-                            (const uint8_t *)p->gray[l].at(first), p->gray[l].pitch, p->depth[l].rows, p->depth[l].cols, l, &sp, nullptr, t,
-                                &done);
+            rc = solve_with(ctx, {(float *)p->depth[l].at(first), p->depth[l].pitch, (const uint8_t *)p->scribble[l].at(first),
+                                  p->scribble[l].pitch, (const uint8_t *)p->gray[l].at(first), p->gray[l].pitch, p->depth[l].rows,
+                                  p->depth[l].cols, l, sp, t}, nullptr, &done);
             if (level_seq && l < 32) level_seq[l] = done.seq;
             if (rc == RTDD_OK) {
                 p->level_info[l] = ctx->last_info; p->level_launch_images[l] = ctx->last_launch_images;
@@ -766,25 +755,24 @@ int live_effect(rtdd_ctx *ctx, const LiveTargets &live) {
                                p->gray[0].pitch});
 }
 
-int estimate_replay(rtdd_ctx *ctx, const PendingOp &op, int failed_seq) {
+int estimate_replay(rtdd_ctx *ctx, const PendingOp::Estimate &e, int failed_seq) {
     Pyramid *p = ctx->pyr;
     if (!p) return fail(ctx, RTDD_ERR_STATE, "the pyramid is gone");
     int from = -1;                                  // the level whose solve gave up; an estimate queued behind the failed call: every level
-    for (int l = 0; l < 32; l++) if (failed_seq != 0 && op.level_seq[l] == failed_seq) from = l;
-    if (from < 0) for (int l = 31; l >= 0 && from < 0; l--) if (op.level_seq[l] != 0) from = l;
+    for (int l = 0; l < 32; l++) if (failed_seq != 0 && e.level_seq[l] == failed_seq) from = l;
+    if (from < 0) for (int l = 31; l >= 0 && from < 0; l--) if (e.level_seq[l] != 0) from = l;
     // a live frame is run again on ITS annotation pair into ITS u8 slot and ITS artistic image (the newest frame's replay comes last: the
     // pyramid ends up naming its images)
-    if (op.live.scribble) { p->scribble[0].ptr = op.live.scribble; p->edited[0].ptr = op.live.edited; }
-    if (op.live.effect && op.live.artistic) p->artistic.ptr = op.live.artistic;
+    if (e.live.scribble) { p->scribble[0].ptr = e.live.scribble; p->edited[0].ptr = e.live.edited; }
+    if (e.live.effect && e.live.artistic) p->artistic.ptr = e.live.artistic;
     // an estimate that rebuilt the coarse annotation levels rebuilds them again, from the pair set just above: a newer frame in flight
     // has added its strokes to them since.  The accumulating estimates run again behind it then add theirs again.
-    if (op.annotation == PendingOp::kAnnotationRebuilt || (op.annotation == PendingOp::kAnnotationAccumulated && ctx->heal_rebuilt)) {
-        const int rc_ = annotation_pyramid(ctx, p, op.annotation == PendingOp::kAnnotationRebuilt);
-        if (rc_ != RTDD_OK) return rc_;
+    if (e.annotation == PendingOp::kAnnotationRebuilt || (e.annotation == PendingOp::kAnnotationAccumulated && ctx->heal_rebuilt)) {
+        RTDD_TRY(annotation_pyramid(ctx, p, e.annotation == PendingOp::kAnnotationRebuilt));
         ctx->heal_rebuilt = true;
     }
-    int rc = from >= 0 ? estimate_levels(ctx, op.maxIterations, from, nullptr, op.batch_first, op.batch_n, op.live) : RTDD_OK;
-    if (rc == RTDD_OK && op.live.effect) rc = live_effect(ctx, op.live);
+    int rc = from >= 0 ? estimate_levels(ctx, e.maxIterations, from, nullptr, e.batch_first, e.batch_n, e.live) : RTDD_OK;
+    if (rc == RTDD_OK && e.live.effect) rc = live_effect(ctx, e.live);
     return rc;
 }
 
@@ -797,14 +785,15 @@ int rtdd_refine_depth(rtdd_ctx *ctx, const rtdd_solve_params *params, rtdd_solve
     if (!ctx) return RTDD_ERR_INVALID;
     if (!ctx->pyr) return fail(ctx, RTDD_ERR_STATE, "rtdd_pyramid_create has not been called");
     Pyramid *p = ctx->pyr;
+    REQUIRE(ctx, params != nullptr, "null params");
     // the u8 map is written by the solve's own copy-back (k_finish: the same rounding as k_depth_to_u8), so that a solve that has to be
     // run again after a timed-out persistent launch brings the map with it
     const int b = p->sel;
     SolveTargets t;
     t.u8 = (uint8_t *)p->depth_u8.at(b); t.u8_pitch = p->depth_u8.pitch;
     t.batch.first = b;
-    return solve_with(ctx, (float *)p->depth[0].at(b), p->depth[0].pitch, (const uint8_t *)p->scribble[0].at(b), p->scribble[0].pitch,
-                      (const uint8_t *)p->gray[0].at(b), p->gray[0].pitch, p->rows, p->cols, 0, params, info, t, nullptr);
+    return solve_with(ctx, {(float *)p->depth[0].at(b), p->depth[0].pitch, (const uint8_t *)p->scribble[0].at(b), p->scribble[0].pitch,
+                            (const uint8_t *)p->gray[0].at(b), p->gray[0].pitch, p->rows, p->cols, 0, *params, t}, info, nullptr);
 }
 
 int rtdd_bgr2gray(rtdd_ctx *ctx, const uint8_t *bgr, size_t bgrPitch, uint8_t *gray, size_t grayPitch, int rows, int cols) {
@@ -830,8 +819,8 @@ int rtdd_pyrup_depth(rtdd_ctx *ctx, const float *src, size_t srcPitch, int rows,
     DeviceGuard g(ctx->device);
     // (as rtdd_index_to_weight: `src` may be the output of a logged solve whose persistent launch gave up -- the spelt-out cascade,
     // solve -> pyrUp -> inject -> solve, queued asynchronously)
-    { const int rc_ = settle_pending(ctx); if (rc_ != RTDD_OK) return rc_; }
-    { const int rc_ = pyramid_note_write(ctx, dst, dst); if (rc_ != RTDD_OK) return rc_; }
+    RTDD_TRY(settle_pending(ctx));
+    RTDD_TRY(pyramid_note_write(ctx, dst, dst));
     return launch_pyrup_inject(ctx, src, srcPitch, rows, cols, dst, dstPitch, dstRows, dstCols, nullptr, 0, nullptr, 0);
 }
 
@@ -840,7 +829,7 @@ int rtdd_depth_to_u8(rtdd_ctx *ctx, const float *src, size_t srcPitch, uint8_t *
     REQUIRE(ctx, src && dst && rows > 0 && cols > 0 && srcPitch >= (size_t)cols * 4 && dstPitch >= (size_t)cols, "bad argument");
     REQUIRE(ctx, f32_image_aligned(src, srcPitch), kF32AlignText);
     DeviceGuard g(ctx->device);
-    { const int rc_ = settle_pending(ctx); if (rc_ != RTDD_OK) return rc_; }     // (as rtdd_pyrup_depth)
+    RTDD_TRY(settle_pending(ctx));     // (as rtdd_pyrup_depth)
     return launch_depth_to_u8(ctx, src, srcPitch, dst, dstPitch, rows, cols);
 }
 
@@ -849,10 +838,9 @@ int rtdd_upload(rtdd_ctx *ctx, void *dev, size_t devPitch, const void *host, siz
     REQUIRE(ctx, dev && host && rows >= 0 && devPitch >= widthBytes && hostPitch >= widthBytes, "bad argument");
     DeviceGuard g(ctx->device);
     // the destination may be an input of a logged call that still has to be run again: settle first (this call synchronises anyway)
-    { const int rc_ = settle_pending(ctx); if (rc_ != RTDD_OK) return rc_; }
-    { const int rc_ = pyramid_note_write(ctx, dev, dev); if (rc_ != RTDD_OK) return rc_; }
-    { const int rc_ = copy_h2d(ctx, ctx->bounce, dev, devPitch, host, hostPitch, widthBytes, rows,
-        ctx->stream); if (rc_ != RTDD_OK) return rc_; }
+    RTDD_TRY(settle_pending(ctx));
+    RTDD_TRY(pyramid_note_write(ctx, dev, dev));
+    RTDD_TRY(copy_h2d(ctx, ctx->bounce, dev, devPitch, host, hostPitch, widthBytes, rows, ctx->stream));
     RTDD_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return RTDD_OK;
 }
@@ -861,15 +849,13 @@ int rtdd_download(rtdd_ctx *ctx, void *host, size_t hostPitch, const void *dev, 
     if (!ctx) return RTDD_ERR_INVALID;
     REQUIRE(ctx, dev && host && rows >= 0 && devPitch >= widthBytes && hostPitch >= widthBytes, "bad argument");
     DeviceGuard g(ctx->device);
-    { const int rc_ = copy_d2h(ctx, ctx->bounce, host, hostPitch, dev, devPitch, widthBytes, rows,
-        ctx->stream); if (rc_ != RTDD_OK) return rc_; }
+    RTDD_TRY(copy_d2h(ctx, ctx->bounce, host, hostPitch, dev, devPitch, widthBytes, rows, ctx->stream));
     RTDD_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const int heals = ctx->heals;
     const int rc = check_persistent_status(ctx);  // what was just downloaded may come from a persistent launch that gave up ...
     if (rc != RTDD_OK || ctx->heals == heals) return rc;
     // ... and has been run again since
-    { const int rc_ = copy_d2h(ctx, ctx->bounce, host, hostPitch, dev, devPitch, widthBytes, rows,
-        ctx->stream); if (rc_ != RTDD_OK) return rc_; }
+    RTDD_TRY(copy_d2h(ctx, ctx->bounce, host, hostPitch, dev, devPitch, widthBytes, rows, ctx->stream));
     RTDD_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return RTDD_OK;
 }

@@ -57,7 +57,7 @@ RTDD_EXPORT void GPUMatrixFreeSolver(float *depthImage, size_t depthPitch, unsig
     report("GPUMatrixFreeSolver", rtdd_matrix_free_solver(g_ctx, depthImage, depthPitch, scribbleImage, scribblePitch, grayImage,
                                                           grayPitch, rows, cols, beta, maxIterations, tolerance, level));
     // src/GPUSolver.cu:314.  A persistent launch that timed out (shared GPU) is healed in here: the solve has run again, one launch per
-    // block of sweeps, by the time this returns (api.cpp check_persistent_status) -- the caller's depth map is valid either way
+    // block of sweeps, by the time this returns (heal.cpp check_persistent_status) -- the caller's depth map is valid either way
     sync("GPUMatrixFreeSolver");
 }
 

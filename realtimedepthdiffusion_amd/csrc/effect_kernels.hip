@@ -771,7 +771,7 @@ static int launch_blend(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const uin
 }
 
 // The body of rtdd_simulate_defocus (FOCUS false) and rtdd_simulate_refocus (FOCUS true: the kernels size each window by
-// |depth - f|, f = *focus_px or `focus`).  kernelSize <= 255 for a refocus (api.cpp): every window of a depth map stays within the
+// |depth - f|, f = *focus_px or `focus`).  kernelSize <= 255 for a refocus (effects_api.cpp): every window of a depth map stays within the
 // domains the packed fields and the quotients are proven on, and the reach kernelSize / 2 that the tile region and the slices are sized
 // for still bounds it (|d - f| <= 255 while both lie in [0, 255]; anything else takes the same fall-backs as an out-of-range depth).
 template <bool FOCUS>
@@ -867,7 +867,7 @@ static int defocus_body(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const flo
     return RTDD_OK;
 }
 
-// Every depth effect (arguments checked by api.cpp or cascade_api.cpp): k_blend's three modes and the two defocus bodies.
+// Every depth effect (arguments checked by effects_api.cpp or cascade_api.cpp): k_blend's three modes and the two defocus bodies.
 int launch_effect(rtdd_ctx *ctx, const Effect &e) {
     switch (e.kind) {
         case RTDD_EFFECT_DEFOCUS:

@@ -1,0 +1,203 @@
+// effects_api.cpp -- the rtdd_simulate_* entry points (include/rtdd.h): arguments checked, one Effect record built, handed to
+// launch_effect (effect_kernels.hip) and, behind unconfirmed solves, to the pending-call log (heal.cpp).  Host code only.
+#include <cmath>
+
+#include "rtdd_internal.hpp"
+
+using namespace rtdd;
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+static int check_effect(rtdd_ctx *ctx, const void *a, const void *b, const void *c, size_t op, size_t dp, size_t ap, int rows, int cols) {
+    REQUIRE(ctx, a && b && c, "null image pointer");
+    REQUIRE(ctx, rows >= 0 && cols >= 0, "negative size");
+    REQUIRE(ctx, (long long)rows * rows + (long long)cols * cols < 2147483647LL, "image too large");
+    REQUIRE(ctx, op >= (size_t)cols * 3 && ap >= (size_t)cols * 3 && dp >= (size_t)cols * 4, "pitch smaller than a row");
+    REQUIRE(ctx, f32_image_aligned(b, dp), kF32AlignText);         // (b: the depth map)
+    return RTDD_OK;
+}
+
+// What every rtdd_simulate_* does once its arguments are checked: launch, and log the effect if it sits behind unconfirmed solves.
+static int simulate(rtdd_ctx *ctx, const Effect &e) {
+    DeviceGuard g(ctx->device);
+    RTDD_TRY(launch_effect(ctx, e));
+    PendingOp op;
+    op.kind = PendingOp::kEffect; op.opt = ctx->opt; op.effect = e;
+    log_call(ctx, op);
+    return RTDD_OK;
+}
+
+int rtdd_simulate_defocus(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
+                          uint8_t *artistic, size_t artisticPitch, int rows, int cols) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    int rc = check_effect(ctx, original, depth, artistic, originalPitch, depthPitch, artisticPitch, rows, cols);
+    if (rc != RTDD_OK || rows == 0 || cols == 0) return rc;
+    REQUIRE(ctx, original != artistic, "defocus cannot run in place");
+    return simulate(ctx, {RTDD_EFFECT_DEFOCUS, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols});
+}
+
+int rtdd_simulate_desaturation(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const uint8_t *gray, size_t grayPitch,
+                               const float *depth, size_t depthPitch, uint8_t *artistic, size_t artisticPitch, int rows, int cols) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    int rc = check_effect(ctx, original, depth, artistic, originalPitch, depthPitch, artisticPitch, rows, cols);
+    if (rc != RTDD_OK || rows == 0 || cols == 0) return rc;
+    REQUIRE(ctx, gray && grayPitch >= (size_t)cols, "bad gray image");
+    return simulate(ctx, {RTDD_EFFECT_DESATURATION, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols, gray,
+                          grayPitch});
+}
+
+int rtdd_simulate_haze(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
+                       uint8_t *artistic, size_t artisticPitch, int rows, int cols) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    int rc = check_effect(ctx, original, depth, artistic, originalPitch, depthPitch, artisticPitch, rows, cols);
+    if (rc != RTDD_OK || rows == 0 || cols == 0) return rc;
+    return simulate(ctx, {RTDD_EFFECT_HAZE, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols});
+}
+
+// the aperture (the K rule) and the focus of rtdd_simulate_refocus and rtdd_simulate_lens_blur
+static int check_focus(rtdd_ctx *ctx, int rows, int cols, double aperture, float focusDepth, int focusX, int focusY) {
+    REQUIRE(ctx, std::isfinite(aperture) && aperture >= 0.0, "aperture must be finite and >= 0");
+    REQUIRE(ctx, window_scale(aperture, rows, cols) <= 255, "aperture too large: the window scale (int)(aperture * diagonal) must be <= 255");
+    if (focusX < 0) REQUIRE(ctx, std::isfinite(focusDepth), "focusDepth must be finite");
+    else REQUIRE(ctx, focusX < cols && focusY >= 0 && focusY < rows, "focus pixel outside the image");
+    return RTDD_OK;
+}
+
+int rtdd_simulate_refocus(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
+                          uint8_t *artistic, size_t artisticPitch, int rows, int cols, double aperture, float focusDepth, int focusX, int focusY) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    int rc = check_effect(ctx, original, depth, artistic, originalPitch, depthPitch, artisticPitch, rows, cols);
+    if (rc != RTDD_OK) return rc;
+    rc = check_focus(ctx, rows, cols, aperture, focusDepth, focusX, focusY);
+    if (rc != RTDD_OK) return rc;
+    const int kernelSize = window_scale(aperture, rows, cols);
+    if (rows == 0 || cols == 0) return RTDD_OK;
+    REQUIRE(ctx, original != artistic, "refocus cannot run in place");
+    Effect e{Effect::kRefocus, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols};
+    e.kernelSize = kernelSize; e.focusDepth = focusDepth; e.focusX = focusX; e.focusY = focusY;
+    return simulate(ctx, e);
+}
+
+int rtdd_simulate_lens_blur(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
+                            uint8_t *artistic, size_t artisticPitch, int rows, int cols, double aperture, float focusDepth, int focusX, int focusY,
+                            int shape) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    REQUIRE(ctx, shape == RTDD_APERTURE_BOX || shape == RTDD_APERTURE_DISC, "shape must be RTDD_APERTURE_BOX or RTDD_APERTURE_DISC");
+    // the square aperture IS a refocus: the same checks, the same Effect, the same kernels
+    if (shape == RTDD_APERTURE_BOX)
+        return rtdd_simulate_refocus(ctx, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols, aperture, focusDepth, focusX, focusY);
+    int rc = check_effect(ctx, original, depth, artistic, originalPitch, depthPitch, artisticPitch, rows, cols);
+    if (rc != RTDD_OK) return rc;
+    rc = check_focus(ctx, rows, cols, aperture, focusDepth, focusX, focusY);
+    if (rc != RTDD_OK) return rc;
+    REQUIRE(ctx, original != artistic, "lens blur cannot run in place");
+    if (rows == 0 || cols == 0) return RTDD_OK;
+    Effect e{Effect::kLensBlur, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols};
+    e.kernelSize = window_scale(aperture, rows, cols); e.focusDepth = focusDepth; e.focusX = focusX; e.focusY = focusY;
+    return simulate(ctx, e);
+}
+
+int rtdd_simulate_haze_ex(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
+                          uint8_t *artistic, size_t artisticPitch, int rows, int cols, float beta, uint8_t airB, uint8_t airG, uint8_t airR) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    int rc = check_effect(ctx, original, depth, artistic, originalPitch, depthPitch, artisticPitch, rows, cols);
+    if (rc != RTDD_OK) return rc;
+    REQUIRE(ctx, std::isfinite(beta) && beta >= 0.0f && beta <= 64.0f, "beta must be finite and in [0, 64]");
+    if (rows == 0 || cols == 0) return RTDD_OK;
+    Effect e{Effect::kHazeEx, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols};
+    e.beta = beta; e.air = (uint32_t)airB | ((uint32_t)airG << 8) | ((uint32_t)airR << 16);
+    return simulate(ctx, e);
+}
+
+int rtdd_simulate_stereo(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
+                         uint8_t *artistic, size_t artisticPitch, int rows, int cols, int disparity, float zeroParallaxDepth, int zeroX, int zeroY,
+                         int mode) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    int rc = check_effect(ctx, original, depth, artistic, originalPitch, depthPitch, artisticPitch, rows, cols);
+    if (rc != RTDD_OK) return rc;
+    REQUIRE(ctx, disparity >= -256 && disparity <= 256, "|disparity| must be <= 256");
+    REQUIRE(ctx, mode == RTDD_STEREO_VIEW || mode == RTDD_STEREO_ANAGLYPH, "mode must be RTDD_STEREO_VIEW or RTDD_STEREO_ANAGLYPH");
+    if (zeroX < 0) REQUIRE(ctx, std::isfinite(zeroParallaxDepth) && zeroParallaxDepth >= 0.0f && zeroParallaxDepth <= 255.0f,
+                           "zeroParallaxDepth must be finite and in [0, 255]");
+    else REQUIRE(ctx, zeroX < cols && zeroY >= 0 && zeroY < rows, "zero-parallax pixel outside the image");
+    if (rows == 0 || cols == 0) return RTDD_OK;
+    REQUIRE(ctx, original != artistic, "stereo cannot run in place");
+    Effect e{Effect::kStereo, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols};
+    e.disparity = disparity; e.zeroDepth = zeroParallaxDepth; e.zeroX = zeroX; e.zeroY = zeroY; e.stereoMode = mode;
+    return simulate(ctx, e);
+}
+
+// The checks of rtdd_simulate_relight up to the empty image, and the light as the kernels take it (e.light), for the two relight calls.
+static int prepare_relight(rtdd_ctx *ctx, Effect &e, const rtdd_light *light) {
+    const int rows = e.rows, cols = e.cols;
+    int rc = check_effect(ctx, e.original, e.depth, e.artistic, e.originalPitch, e.depthPitch, e.artisticPitch, rows, cols);
+    if (rc != RTDD_OK) return rc;
+    REQUIRE(ctx, light, "null light");
+    const rtdd_light &q = *light;
+    const bool point = q.kind == RTDD_LIGHT_POINT;
+    REQUIRE(ctx, point || q.kind == RTDD_LIGHT_DIRECTIONAL, "kind must be RTDD_LIGHT_DIRECTIONAL or RTDD_LIGHT_POINT");
+    for (float v : {q.x, q.y, q.z, q.anchorDepth, q.radius, q.relief, q.ambient, q.diffuse}) REQUIRE(ctx, std::isfinite(v), "a non-finite value in the light");
+    REQUIRE(ctx, q.z > 0.0f, "the light's z must be > 0");
+    REQUIRE(ctx, q.relief >= 0.0f && q.relief <= 64.0f, "relief outside [0, 64]");
+    REQUIRE(ctx, q.ambient >= 0.0f && q.ambient <= 8.0f && q.diffuse >= 0.0f && q.diffuse <= 8.0f, "ambient or diffuse outside [0, 8]");
+    Effect::Light &L = e.light;
+    L.kind = q.kind;
+    if (point) {
+        REQUIRE(ctx, q.x >= -32768.0f && q.x <= 32767.0f && q.y >= -32768.0f && q.y <= 32767.0f, "a point light's x or y outside [-32768, 32767]");
+        REQUIRE(ctx, q.z <= 65536.0f, "a point light's z above 65536");
+        REQUIRE(ctx, q.radius > 0.0f && q.radius <= 65536.0f, "radius outside (0, 65536]");
+        if (q.anchorX < 0) REQUIRE(ctx, q.anchorDepth >= 0.0f && q.anchorDepth <= 255.0f, "anchorDepth outside [0, 255]");
+        else REQUIRE(ctx, q.anchorX < cols && q.anchorY >= 0 && q.anchorY < rows, "anchor pixel outside the image");
+        L.x = q.x; L.y = q.y; L.z = q.z;
+        L.anchorDepth = q.anchorDepth; L.anchorX = q.anchorX; L.anchorY = q.anchorY;
+        L.invR2 = (float)(1.0 / ((double)q.radius * q.radius));
+    } else {
+        const double len = std::sqrt((((double)q.x * q.x) + ((double)q.y * q.y)) + ((double)q.z * q.z));
+        REQUIRE(ctx, std::isfinite(len) && len > 0.0, "the light's direction has no length");
+        L.x = (float)(q.x / len); L.y = (float)(q.y / len); L.z = (float)(q.z / len);
+    }
+    L.relief = q.relief; L.ambient = q.ambient;
+    const uint8_t color[3] = {q.colorB, q.colorG, q.colorR};
+    for (int c = 0; c < 3; c++) L.k[c] = (float)((double)q.diffuse * color[c] / 255.0);
+    return RTDD_OK;
+}
+
+int rtdd_simulate_relight(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
+                          uint8_t *artistic, size_t artisticPitch, int rows, int cols, const rtdd_light *light) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    Effect e{Effect::kRelight, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols};
+    const int rc = prepare_relight(ctx, e, light);
+    if (rc != RTDD_OK) return rc;
+    if (rows == 0 || cols == 0) return RTDD_OK;
+    REQUIRE(ctx, original != artistic, "relight cannot run in place");
+    return simulate(ctx, e);
+}
+
+int rtdd_simulate_relight_shadowed(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
+                                   uint8_t *artistic, size_t artisticPitch, int rows, int cols, const rtdd_light *light,
+                                   const rtdd_shadow *shadow) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    Effect e{Effect::kRelightShadow, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols};
+    const int rc = prepare_relight(ctx, e, light);
+    if (rc != RTDD_OK) return rc;
+    REQUIRE(ctx, shadow, "null shadow");
+    const rtdd_shadow &q = *shadow;
+    for (float v : {q.bias, q.softness, q.strength}) REQUIRE(ctx, std::isfinite(v), "a non-finite value in the shadow");
+    REQUIRE(ctx, q.maxSteps >= 0 && q.maxSteps <= 1024, "maxSteps outside [0, 1024]");
+    REQUIRE(ctx, q.bias >= 0.0f && q.bias <= 65536.0f && q.softness >= 0.0f && q.softness <= 65536.0f, "bias or softness outside [0, 65536]");
+    REQUIRE(ctx, q.strength >= 0.0f && q.strength <= 1.0f, "strength outside [0, 1]");
+    Effect::Shadow &S = e.shadow;
+    S.maxSteps = q.maxSteps; S.bias = q.bias; S.softness = q.softness; S.strength = q.strength;
+    if (e.light.kind == RTDD_LIGHT_DIRECTIONAL) {
+        // the step along the major axis of the projected direction, in f32; m == 0 (the light straight above) leaves sx == sy == 0
+        const float m = fmaxf(fabsf(e.light.x), fabsf(e.light.y));
+        if (m != 0.0f) { S.sx = e.light.x / m; S.sy = e.light.y / m; S.rise = e.light.z / m; }
+    }
+    if (rows == 0 || cols == 0) return RTDD_OK;
+    REQUIRE(ctx, original != artistic, "relight cannot run in place");
+    return simulate(ctx, e);
+}
+
+}  // extern "C"
+#pragma GCC visibility pop

@@ -274,7 +274,7 @@ __global__ __launch_bounds__(256, 2) void k_lens_tile(const uint8_t *__restrict_
     }
 }
 
-// rtdd_simulate_lens_blur with RTDD_APERTURE_DISC (kernelSize <= 255: api.cpp).  RTDD_OPT_DEFOCUS_PATH as for the box: 0 automatic
+// rtdd_simulate_lens_blur with RTDD_APERTURE_DISC (kernelSize <= 255: effects_api.cpp).  RTDD_OPT_DEFOCUS_PATH as for the box: 0 automatic
 // (the tile kernel where its region holds every disc of a depth map), 1 the global table, 2 the tile kernel wherever it fits.
 int launch_lens_blur(rtdd_ctx *ctx, const Effect &e) {
     const uint8_t *orig = e.original; const size_t op = e.originalPitch;

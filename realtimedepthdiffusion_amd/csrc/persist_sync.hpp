@@ -1,5 +1,5 @@
 // persist_sync.hpp -- the inter-workgroup hand-off of the persistent kernels (sweep_blocked.hip, rbgs_blocked.hip), device side,
-// and the host helpers around it (api.cpp).
+// and the host helpers around it (heal.cpp).
 //
 // Control words (rtdd_ctx::sync_words, device memory, one set per context):
 //   [kSyncStatus]    0 = fine; 1 = a workgroup gave up waiting for a neighbouring TILE (the launch was not fully co-resident:
@@ -13,16 +13,16 @@
 //                    timeout path testable.
 //   [kSyncLimit]     poll limit in 10 ns ticks of s_memrealtime (0 = kDefaultPollLimit).
 //   [kSyncFailedSeq] sequence number of the first solve whose copy-back kernel (k_finish / k_pyrup_inject) found the status word set and
-//                    therefore stored nothing: the host re-runs the pending calls from that one on (api.cpp heal_pending).  0 = none.
+//                    therefore stored nothing: the host re-runs the pending calls from that one on (heal.cpp check_persistent_status).  0 = none.
 //   [kSyncConfirmPtr] (two ints, an address) where the copy-back kernels report the sequence number of a solve whose result they DID publish:
 //                    a word in page-locked host memory, so that the host can drop confirmed calls from its log without synchronising
-//                    (api.cpp prune_confirmed).  Written by one lane, only while the status word is clear.
+//                    (heal.cpp prune_confirmed).  Written by one lane, only while the status word is clear.
 //   [kSyncWild]      sequence number of the most recent solve whose k_prepare met a depth that is not finite or is 2^100 or larger in
 //                    magnitude (solver_kernels.hip; a plain vector store, made only when such a value is found).  The register-blocked
 //                    sweep kernels compare it with their own solve's number and, when equal, run the variant with the full IEEE divide
 //                    and explicit absent neighbours (sweep_common.hpp div_tail).  Never cleared: sequence numbers do not repeat.
 //   [kSyncFlags ..]  one block counter per tile.  Monotonic over the life of the context: launch L's workgroups publish base_L + block
-//                    number, base_L handed in by the host (api.cpp prepare_persistent_launch), so nothing is zeroed between launches.
+//                    number, base_L handed in by the host (heal.cpp prepare_persistent_launch), so nothing is zeroed between launches.
 #pragma once
 #include <hip/hip_runtime.h>
 

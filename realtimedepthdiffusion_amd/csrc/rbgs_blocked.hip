@@ -359,7 +359,7 @@ int launch_rbgs_blocked(rtdd_ctx *ctx, const Level &L, size_t ip, int rows, int 
         int block_sweeps = m, flag_base = 0;
         if (persistent) {
             m = n - done;
-            { const int rc_ = prepare_persistent_launch(ctx, (m + block_sweeps - 1) / block_sweeps, &flag_base); if (rc_ != RTDD_OK) return rc_; }   // this launch's flag values, debug words
+            RTDD_TRY(prepare_persistent_launch(ctx, (m + block_sweeps - 1) / block_sweeps, &flag_base));   // this launch's flag values, debug words
             note_status_writer(ctx);
         }
         int out = -1;

@@ -80,7 +80,7 @@ __global__ __launch_bounds__(256) void k_relight(const uint8_t *__restrict__ ori
     store_bytes12(arow + 3 * (size_t)x, rb);
 }
 
-// rtdd_simulate_relight (arguments checked and the light prepared by api.cpp): one launch.
+// rtdd_simulate_relight (arguments checked and the light prepared by effects_api.cpp): one launch.
 int launch_relight(rtdd_ctx *ctx, const Effect &e) {
     const Light &L = e.light;
     const bool point = L.kind == RTDD_LIGHT_POINT;

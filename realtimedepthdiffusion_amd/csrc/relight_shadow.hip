@@ -98,7 +98,7 @@ __global__ __launch_bounds__(256) void k_relight_shadow(const uint8_t *__restric
     for (int c = 0; c < 3; c++) a[c] = (uint8_t)relight_u8(L, c, lit, o[c]);
 }
 
-// rtdd_simulate_relight_shadowed (arguments checked, the light and the direction prepared by api.cpp): one launch.  Where no pixel can
+// rtdd_simulate_relight_shadowed (arguments checked, the light and the direction prepared by effects_api.cpp): one launch.  Where no pixel can
 // be shadowed -- no steps, no strength, a directional light straight above (m == 0: sx == sy == 0) -- the launch is k_relight's own.
 int launch_relight_shadow(rtdd_ctx *ctx, const Effect &e) {
     const Light &L = e.light;

@@ -60,9 +60,7 @@ struct Batch {
 };
 #define RTDD_Z(ptr, stride) ptr = (decltype(ptr))((const char *)(ptr) + (size_t)blockIdx.z * (size_t)(stride))
 
-// What a solve is told BESIDES the reference's own arguments (GPUMatrixFreeSolver's, src/GPUSolver.cu:274-275).  Passed down the call
-// chain by value or const reference -- estimate_levels -> solve_with -> the launchers -- and stored by value in the pending-call log
-// (PendingOp, next to the solve's own arguments): nothing is parked in the context around a call, so a replay restores nothing by hand.
+// What a solve is told BESIDES the reference's own arguments (GPUMatrixFreeSolver's, src/GPUSolver.cu:274-275): part of its SolveCall.
 struct SolveTargets {
     Batch batch;                                    // the images the launches cover (n = 1, first = 0: one image)
     bool defer_finish = false;                      // leave the result in its plane: the next level's pyrUp kernel reads it there
@@ -73,6 +71,18 @@ struct SolveTargets {
 // What a solve hands back to a caller inside the library: its sequence number (what the guarded copy-back kernels report) and the
 // plane its result is in (defer_finish).
 struct SolveOutcome { int seq = 0, plane = -1; };
+// One solve: what rtdd_solve_ex is given plus what the library's own callers add.  Built once per entry point (rtdd_solve_ex,
+// rtdd_matrix_free_solver, estimate_levels, rtdd_refine_depth), passed down by const reference -- solve_with -> solve_once -> the
+// launchers -- and stored by value in the pending-call log (PendingOp): nothing is parked in the context around a call, so a replay
+// hands the stored record straight back.  The sequence number and the SolveOutcome are per attempt, not per call, and travel beside it.
+struct SolveCall {
+    float *depth = nullptr; size_t depthPitch = 0;
+    const uint8_t *scribble = nullptr; size_t scribblePitch = 0;
+    const uint8_t *gray = nullptr; size_t grayPitch = 0;
+    int rows = 0, cols = 0, level = 0;
+    rtdd_solve_params params{};
+    SolveTargets targets;                           // (rtdd_refine_depth: the selected image of a batch, the u8 copy of the result)
+};
 // A live frame's own images (cascade_api.cpp): the level-0 annotation pair its estimate ran on, the second target of its u8 map
 // (u8_pitch 0: a staging slot with the pyramid's pitch), and the sticky depth effect behind it (src/main.cpp:190-230) with its target.
 struct LiveTargets {
@@ -83,7 +93,7 @@ struct LiveTargets {
 };
 
 // One depth effect, arguments checked: what to render, on which images, with which parameters.  Built by the rtdd_simulate_* entry
-// points (api.cpp) and by a live frame (live_effect), launched by launch_effect, and logged by value (PendingOp) to be launched again.
+// points (effects_api.cpp) and by a live frame (live_effect), launched by launch_effect, and logged by value (PendingOp) to be launched again.
 struct Effect {
     enum : int { kRefocus = RTDD_EFFECT_HAZE + 1, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow };   // the extensions, after the public kinds
     int kind = RTDD_EFFECT_NONE;                    // RTDD_EFFECT_DEFOCUS / _DESATURATION / _HAZE, kRefocus, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow
@@ -150,33 +160,29 @@ struct Options {
 };
 
 // One asynchronous call whose results the caller has not yet seen confirmed by a synchronising call: what check_persistent_status
-// needs to run it again when a persistent launch gave up (api.cpp, "self-healing").  A solve is one sequence number (handed to the
-// kernel that publishes its result: k_finish, or k_pyrup_inject inside an estimate); an estimate is one per pyramid level; an effect
-// publishes none.
+// needs to run it again when a persistent launch gave up (heal.cpp).  One record per kind, side by side (the log holds at most
+// kMaxPendingOps entries): `kind` says which one is meant, and replay hands it back to solve_with / estimate_replay / launch_effect as
+// it is.  A solve is one sequence number (handed to the kernel that publishes its result: k_finish, or k_pyrup_inject inside an
+// estimate); an estimate is one per pyramid level; an effect publishes none.
 struct PendingOp {
     enum Kind { kSolve = 0, kEstimate = 1, kEffect = 2 } kind = kSolve;
     Options opt;                          // the options in force when the call was made
-    // kSolve: the arguments of rtdd_solve_ex (+ the optional u8 copy of the result, rtdd_refine_depth)
-    float *depth = nullptr; size_t depthPitch = 0;
-    const uint8_t *scribble = nullptr; size_t scribblePitch = 0;
-    const uint8_t *gray = nullptr; size_t grayPitch = 0;
-    int rows = 0, cols = 0, level = 0, seq = 0;
-    rtdd_solve_params params{};
-    SolveTargets targets;                 // (rtdd_refine_depth: the selected image of a batch, the u8 copy of the result)
-    // kEstimate
-    int maxIterations = 0;
-    int level_seq[32] = {};               // sequence number of level l's solve (0: the level is empty)
-    int batch_first = 0, batch_n = 1;     // the images of the context's batched pyramid the estimate covers
-    LiveTargets live;                     // a live frame: its annotation pair, its map's second target, its effect (scribble == nullptr: not one)
-    // what the estimate did to the coarse annotation levels in front of its solves: kAnnotationNone (they were up to date),
-    // kAnnotationAccumulated (GPUPyrDownAnnotation: only ever adds) or kAnnotationRebuilt (as if they had been all zero).  A replay of a
-    // rebuilt estimate rebuilds them again from the annotation pair it ran on, and the accumulating estimates replayed behind it add
-    // theirs again: a newer live frame's strokes, accumulated in the meantime, are gone from the older frame's Dirichlet set
-    enum : int { kAnnotationNone = 0, kAnnotationAccumulated = 1, kAnnotationRebuilt = 2 };
-    int annotation = kAnnotationNone;
     unsigned long long id = 0;            // position in the context's call order (live mode drops the confirmed prefix of the log)
-    // kEffect: a depth effect queued BEHIND an unconfirmed solve (it may have read that solve's input instead of its result)
-    Effect effect;
+    SolveCall solve;                      // kSolve ...
+    int seq = 0;                          // ... and its sequence number
+    struct Estimate {                     // kEstimate
+        int maxIterations = 0;
+        int level_seq[32] = {};           // sequence number of level l's solve (0: the level is empty)
+        int batch_first = 0, batch_n = 1; // the images of the context's batched pyramid the estimate covers
+        LiveTargets live;                 // a live frame: its annotation pair, its map's second target, its effect (scribble == nullptr: not one)
+        // what the estimate did to the coarse annotation levels in front of its solves: kAnnotationNone (they were up to date),
+        // kAnnotationAccumulated (GPUPyrDownAnnotation: only ever adds) or kAnnotationRebuilt (as if they had been all zero).  A replay
+        // of a rebuilt estimate rebuilds them again from the annotation pair it ran on, and the accumulating estimates replayed behind
+        // it add theirs again: a newer live frame's strokes, accumulated in the meantime, are gone from the older frame's Dirichlet set
+        int annotation = 0;
+    } estimate;
+    enum : int { kAnnotationNone = 0, kAnnotationAccumulated = 1, kAnnotationRebuilt = 2 };
+    Effect effect;                        // kEffect: queued BEHIND an unconfirmed solve (it may have read that solve's input, not its result)
 };
 constexpr int kRestartSolve = -1000;      // internal status: the pending calls were healed inside a solve's residual check; that solve starts over
 constexpr size_t kMaxPendingOps = 4096;
@@ -212,12 +218,12 @@ struct rtdd_ctx {
     int defocus_last_slices = 0;         // ... and, on the table path, how many horizontal slices it built a table for (1: one whole-image table)
     bool defocus_band_sticky = false;    // a banded-table defocus met windows beyond a slice (depths above 255): one whole-image table from then on
     bool defocus_table_sticky = false;   // a tile-kernel defocus met out-of-range depths (seen at a synchronisation): automatic choice = the table from then on
-    int flag_epoch = 0;             // the per-tile flags of the persistent kernels only ever grow: base value of the next persistent launch (api.cpp)
+    int flag_epoch = 0;             // the per-tile flags of the persistent kernels only ever grow: base value of the next persistent launch (heal.cpp)
     int sync_header[2] = {0, 0};    // what sync_words[kSyncWithhold], [kSyncLimit] currently hold on the device
     int last_nominal_depth = 0;     // sweeps per launch / exchange the most recent blocked solve was configured with (its last launch may be shorter)
     int last_launch_images = 1;     // images each sweep launch of the most recent solve covered (sweep_blocked.hip: a batch in the same launches, or image after image)
     rtdd_solve_info last_info{};    // of the most recent solve; kernel/tile/temporal_depth/persistent are filled in by the sweep launchers
-    // Self-healing after RTDD_ERR_TIMEOUT (api.cpp heal_pending): every solve / estimate since the last status check, in call order
+    // Self-healing after RTDD_ERR_TIMEOUT (heal.cpp): every solve / estimate since the last status check, in call order
     int solve_seq = 0;              // sequence number of the most recent rtdd_solve_ex (1 .. 2^30, never 0)
     int wild_seq = -1;              // the number the solve being queued hands k_prepare and its sweep kernels (persist_sync.hpp kSyncWild);
                                     // -1 outside a solve (the diagnostics of scripts/ubench launch sweeps directly): never the word's value
@@ -284,6 +290,12 @@ inline void note_publisher(rtdd_ctx *ctx, int seq) { ctx->persistent_used = true
         if (e_ != hipSuccess) return ::rtdd::fail((ctx), RTDD_ERR_HIP, #call, e_); \
     } while (0)
 
+#define REQUIRE(ctx, cond, msg) \
+    do { if (!(cond)) return ::rtdd::fail((ctx), RTDD_ERR_INVALID, msg); } while (0)
+// evaluate a call that returns an rtdd status; leave the function with it unless it is RTDD_OK
+#define RTDD_TRY(call) \
+    do { const int rc_ = (call); if (rc_ != RTDD_OK) return rc_; } while (0)
+
 #define RTDD_LAUNCH_CHECK(ctx, name)                                                     \
     do {                                                                                 \
         hipError_t e_ = hipGetLastError();                                               \
@@ -303,10 +315,8 @@ struct DeviceGuard {
 };
 
 // ---- solver_kernels.hip -------------------------------------------------------------------------
-// (B: the images a batched launch covers; L is image B.first's view of the level)
-int launch_prepare(rtdd_ctx *ctx, const Level &L, size_t ip, const float *depth, size_t depthPitch,
-                   const uint8_t *scribble, size_t scribblePitch, const uint8_t *gray, size_t grayPitch,
-                   int rows, int cols, int level, const Batch &B);
+// (c.targets.batch: the images a batched launch covers; L is its first image's view of the level)
+int launch_prepare(rtdd_ctx *ctx, const Level &L, size_t ip, const SolveCall &c);
 // Both sweep launchers advance n sweeps from (plane *pk = x_k, plane *pm = x_{k-1}) and update *pk / *pm to
 // the planes holding x_{k+n} / x_{k+n-1}.
 int launch_sweeps(rtdd_ctx *ctx, const Level &L, size_t ip, int rows, int cols, const float *omegas_host, int n,
@@ -316,9 +326,8 @@ int launch_sweeps_blocked(rtdd_ctx *ctx, const Level &L, size_t ip, int rows, in
                           int *pk, int *pm, int *launches, int images = 1);
 // (k_finish and k_pyrup_inject store NOTHING when the status word is set: a timed-out solve leaves the caller's buffers as they were;
 // the first of them to find it set records ctx->guard_seq in sync_words[kSyncFailedSeq])
-// (seq: the solve's sequence number, reported by the kernel either as confirmed or as the first failed one; t: the batch and the u8 targets)
-int launch_finish(rtdd_ctx *ctx, const Level &L, size_t ip, int src_plane, float *depth, size_t depthPitch, int rows, int cols,
-                  const SolveTargets &t, int seq);
+// (seq: the solve's sequence number, reported by the kernel either as confirmed or as the first failed one; c.targets: the batch and the u8 targets)
+int launch_finish(rtdd_ctx *ctx, const Level &L, size_t ip, int src_plane, const SolveCall &c, int seq);
 int launch_index_to_weight(rtdd_ctx *ctx, const uint8_t *gray, size_t grayPitch, const float *depth, size_t depthPitch,
                            int32_t *index2, int level, int rows, int cols);
 int launch_residual(rtdd_ctx *ctx, const Level &L, size_t ip, int plane, int rows, int cols, float *host_out);
@@ -376,6 +385,7 @@ void pyramid_free(rtdd_ctx *ctx);
 int pyramid_note_write(rtdd_ctx *ctx, const void *scribble, const void *edited, bool erases = false);
 int pyramid_check_read(rtdd_ctx *ctx, const void *a, const void *b);     // ... about to be read
 
+// ---- heal.cpp ----------------------------------------------------------------------------------
 // persistent kernels (persist_sync.hpp): reserve the launch's flag values and refresh the debug words before a persistent launch;
 // read the status word where the stream has just been synchronised (-> RTDD_ERR_TIMEOUT, status cleared)
 int prepare_persistent_launch(rtdd_ctx *ctx, int nblocks, int *flag_base);
@@ -383,15 +393,16 @@ int prepare_persistent_launch(rtdd_ctx *ctx, int nblocks, int *flag_base);
 int check_persistent_status(rtdd_ctx *ctx, bool in_solve = false);
 void prune_confirmed(rtdd_ctx *ctx);    // drop the logged calls a copy-back kernel has confirmed (no synchronisation)
 int settle_pending(rtdd_ctx *ctx);      // before a call changes what the logged calls ran on: synchronise + check (+ heal) while that state still exists
+// the one place a call enters the log: kind, opt and the kind's record filled in by the caller, id assigned here; false: not logged
+bool log_call(rtdd_ctx *ctx, PendingOp &op);
 // cascade_api.cpp: levels from_level .. 0 of an estimate (src/main.cpp:261-291); level_seq (optional) receives each level's solve sequence number
 int estimate_levels(rtdd_ctx *ctx, int maxIterations, int from_level, int *level_seq, int first, int n, const LiveTargets &live);
-// api.cpp: rtdd_solve_ex with everything the library's own callers add to it
-int solve_with(rtdd_ctx *ctx, float *depth, size_t depthPitch, const uint8_t *scribble, size_t scribblePitch, const uint8_t *gray, size_t grayPitch,
-               int rows, int cols, int level, const rtdd_solve_params *params, rtdd_solve_info *info, const SolveTargets &t, SolveOutcome *out);
+// api.cpp: rtdd_solve_ex with everything the library's own callers add to it (c.targets)
+int solve_with(rtdd_ctx *ctx, const SolveCall &c, rtdd_solve_info *info, SolveOutcome *out);
 // cascade_api.cpp: a live frame's effect (again, on a replay): RTDD_EFFECT_* on the pyramid's level-0 images into live.artistic
 int live_effect(rtdd_ctx *ctx, const LiveTargets &live);
 // an estimate of the pending log again, from the level whose solve has sequence number failed_seq (0: every level)
-int estimate_replay(rtdd_ctx *ctx, const PendingOp &op, int failed_seq);
+int estimate_replay(rtdd_ctx *ctx, const PendingOp::Estimate &e, int failed_seq);
 
 // the reference's host-side omega recurrence (src/GPUSolver.cu:282-299)
 void omega_schedule(int n, std::vector<float> &out);

@@ -402,21 +402,20 @@ __global__ __launch_bounds__(256) void k_rbgs_half(float *__restrict__ X, const 
 // ================================================================================================
 static inline dim3 grid64x4(int rows, int cols, int images = 1) { return dim3((cols + 63) / 64, (rows + 3) / 4, images); }
 
-int launch_prepare(rtdd_ctx *ctx, const Level &L, size_t ip, const float *depth, size_t depthPitch,
-                   const uint8_t *scribble, size_t scribblePitch, const uint8_t *gray, size_t grayPitch,
-                   int rows, int cols, int level, const Batch &B) {
-    const int gated = level != ctx->maxLevel;
-    const int thr = level == 0 ? 0 : 4;
+int launch_prepare(rtdd_ctx *ctx, const Level &L, size_t ip, const SolveCall &c) {
+    const Batch &B = c.targets.batch;
+    const int gated = c.level != ctx->maxLevel;
+    const int thr = c.level == 0 ? 0 : 4;
     // (B.n = 1: one image, strides unused; L is already image B.first's view)
     const size_t zP = L.elems * sizeof(float);
-    const bool aligned = ((uintptr_t)depth % 16 == 0) && depthPitch % 16 == 0 && ((uintptr_t)gray % 4 == 0) && grayPitch % 4 == 0 &&
-                         ((uintptr_t)scribble % 4 == 0) && scribblePitch % 4 == 0 && B.depth % 16 == 0 && B.gray % 4 == 0 && B.scribble % 4 == 0;
+    const bool aligned = ((uintptr_t)c.depth % 16 == 0) && c.depthPitch % 16 == 0 && ((uintptr_t)c.gray % 4 == 0) && c.grayPitch % 4 == 0 &&
+                         ((uintptr_t)c.scribble % 4 == 0) && c.scribblePitch % 4 == 0 && B.depth % 16 == 0 && B.gray % 4 == 0 && B.scribble % 4 == 0;
     if (aligned)
-        hipLaunchKernelGGL(k_prepare4, grid64x4(rows, (cols + 3) / 4, B.n), dim3(256), 0, ctx->stream, depth, depthPitch, scribble, scribblePitch,
-                           gray, grayPitch, L.P(0, ip), L.P(1, ip), L.M(ip), (int)ip, rows, cols, gated, thr, B.depth, B.scribble, B.gray, zP, ctx->sync_words, ctx->wild_seq);
+        hipLaunchKernelGGL(k_prepare4, grid64x4(c.rows, (c.cols + 3) / 4, B.n), dim3(256), 0, ctx->stream, c.depth, c.depthPitch, c.scribble, c.scribblePitch,
+                           c.gray, c.grayPitch, L.P(0, ip), L.P(1, ip), L.M(ip), (int)ip, c.rows, c.cols, gated, thr, B.depth, B.scribble, B.gray, zP, ctx->sync_words, ctx->wild_seq);
     else
-        hipLaunchKernelGGL(k_prepare, grid64x4(rows, cols, B.n), dim3(256), 0, ctx->stream, depth, depthPitch, scribble, scribblePitch,
-                           gray, grayPitch, L.P(0, ip), L.P(1, ip), L.M(ip), (int)ip, rows, cols, gated, thr, B.depth, B.scribble, B.gray, zP, ctx->sync_words, ctx->wild_seq);
+        hipLaunchKernelGGL(k_prepare, grid64x4(c.rows, c.cols, B.n), dim3(256), 0, ctx->stream, c.depth, c.depthPitch, c.scribble, c.scribblePitch,
+                           c.gray, c.grayPitch, L.P(0, ip), L.P(1, ip), L.M(ip), (int)ip, c.rows, c.cols, gated, thr, B.depth, B.scribble, B.gray, zP, ctx->sync_words, ctx->wild_seq);
     RTDD_LAUNCH_CHECK(ctx, "k_prepare");
     return RTDD_OK;
 }
@@ -465,16 +464,16 @@ int launch_sweeps(rtdd_ctx *ctx, const Level &L, size_t ip, int rows, int cols, 
     return RTDD_OK;
 }
 
-int launch_finish(rtdd_ctx *ctx, const Level &L, size_t ip, int src_plane, float *depth, size_t depthPitch, int rows, int cols,
-                  const SolveTargets &t, int seq) {
+int launch_finish(rtdd_ctx *ctx, const Level &L, size_t ip, int src_plane, const SolveCall &c, int seq) {
+    const SolveTargets &t = c.targets;
     const Batch &B = t.batch;
     const size_t zP = L.elems * sizeof(float);
-    if ((uintptr_t)depth % 16 == 0 && depthPitch % 16 == 0 && B.depth % 16 == 0 && B.u8 % 4 == 0)
-        hipLaunchKernelGGL(k_finish4, grid64x4(rows, (cols + 3) / 4, B.n), dim3(256), 0, ctx->stream, L.P(src_plane, ip), (int)ip, depth, depthPitch,
-                           rows, cols, t.u8, t.u8_pitch, ctx->sync_words, seq, zP, B.depth, B.u8, t.u8b, t.u8b_pitch);
+    if ((uintptr_t)c.depth % 16 == 0 && c.depthPitch % 16 == 0 && B.depth % 16 == 0 && B.u8 % 4 == 0)
+        hipLaunchKernelGGL(k_finish4, grid64x4(c.rows, (c.cols + 3) / 4, B.n), dim3(256), 0, ctx->stream, L.P(src_plane, ip), (int)ip, c.depth, c.depthPitch,
+                           c.rows, c.cols, t.u8, t.u8_pitch, ctx->sync_words, seq, zP, B.depth, B.u8, t.u8b, t.u8b_pitch);
     else
-        hipLaunchKernelGGL(k_finish, grid64x4(rows, cols, B.n), dim3(256), 0, ctx->stream, L.P(src_plane, ip), (int)ip, depth, depthPitch,
-                           rows, cols, t.u8, t.u8_pitch, ctx->sync_words, seq, zP, B.depth, B.u8, t.u8b, t.u8b_pitch);
+        hipLaunchKernelGGL(k_finish, grid64x4(c.rows, c.cols, B.n), dim3(256), 0, ctx->stream, L.P(src_plane, ip), (int)ip, c.depth, c.depthPitch,
+                           c.rows, c.cols, t.u8, t.u8_pitch, ctx->sync_words, seq, zP, B.depth, B.u8, t.u8b, t.u8b_pitch);
     note_publisher(ctx, seq);                     // (the guard may have recorded a failed solve: the next synchronising call looks)
     RTDD_LAUNCH_CHECK(ctx, "k_finish");
     return RTDD_OK;

@@ -743,7 +743,7 @@ static int launch_sweeps_blocked_impl(rtdd_ctx *ctx, const Level &L, size_t ip, 
         if (persistent) {
             block_sweeps = T;
             m = n - done;
-            { const int rc_ = prepare_persistent_launch(ctx, (m + T - 1) / T, &flag_base); if (rc_ != RTDD_OK) return rc_; }   // this launch's flag values, debug words
+            RTDD_TRY(prepare_persistent_launch(ctx, (m + T - 1) / T, &flag_base));   // this launch's flag values, debug words
             note_status_writer(ctx);
         }
         // XCD-aware tile placement: +1.5-4 % persistent (strips traded inside one L2), +8 % at 4K launch-per-block (a tile's halo is its
