@@ -11,6 +11,8 @@
 //                 aperture 0.025 = the defocus; --bokeh disc: rtdd_simulate_lens_blur's round aperture), --effect haze [--haze-beta B] [--airlight b,g,r]   (rtdd_simulate_haze_ex when either is given),
 //                 --effect stereo --disparity D [--zero-parallax Z | --zero-parallax-at X,Y] [--anaglyph]   (rtdd_simulate_stereo; default:
 //                 zero parallax at depth 0, the view),
+//                 --effect parallax --shift dx,dy [--dolly z] [--zero-parallax Z | --zero-parallax-at X,Y]   (rtdd_simulate_parallax: the camera moved
+//                 sideways, up or forward; default: no dolly, zero parallax at depth 0),
 //                 --effect relight [--light-dir x,y,z | --light-at X,Y [--light-height H] [--light-radius R]] [--relief S] [--ambient A] [--diffuse D]
 //                 [--light-color b,g,r]   (rtdd_simulate_relight; default: a white directional light from the upper left, (-1, -1, 1), relief 2,
 //                 ambient 0.25, diffuse 1; --light-at: a point light over that pixel, anchored at its depth, height 100, radius 200)
@@ -197,6 +199,8 @@ struct Job {
     float zero_depth = 0.0f;
     int zero_x = -1, zero_y = -1;
     bool anaglyph = false;
+    int shift_x = 0, shift_y = 0; // --effect parallax: --shift, --dolly, and stereo's --zero-parallax / --zero-parallax-at
+    float dolly = 0.0f;
     // --effect relight: --light-dir (directional) or --light-at (a point light over that pixel, anchored at its depth), --light-height, --light-radius,
     // --relief, --ambient, --diffuse, --light-color
     rtdd_light light = {RTDD_LIGHT_DIRECTIONAL, -1.0f, -1.0f, 1.0f, 0.0f, -1, -1, 200.0f, 2.0f, 0.25f, 1.0f, 255, 255, 255};
@@ -470,6 +474,10 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
         else if (job.effect == "stereo")
             CK(rtdd_simulate_stereo(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols, job.disparity,
                                     job.zero_depth, job.zero_x, job.zero_y, job.anaglyph ? RTDD_STEREO_ANAGLYPH : RTDD_STEREO_VIEW));
+        else if (job.effect == "parallax") {
+            const rtdd_parallax view = {job.shift_x, job.shift_y, job.dolly, job.zero_depth, job.zero_x, job.zero_y};
+            CK(rtdd_simulate_parallax(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols, &view));
+        }
         else if (job.effect == "relight") {
             rtdd_light light = job.light;
             if (light.kind == RTDD_LIGHT_POINT) light.z = job.light_height;
@@ -488,9 +496,10 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
 }
 
 int main(int argc, const char *argv[]) {
-    if (argc == 1) { std::printf("Usage: rtdd_harness -i image.(jpg|png|ppm) [-a annotation.(png|pgm)] [-o prefix] [--effect defocus|desaturation|haze|refocus|stereo|relight] [--iters N] [--refine sor|mg|auto [--tolerance T]]\n"
+    if (argc == 1) { std::printf("Usage: rtdd_harness -i image.(jpg|png|ppm) [-a annotation.(png|pgm)] [-o prefix] [--effect defocus|desaturation|haze|refocus|stereo|parallax|relight] [--iters N] [--refine sor|mg|auto [--tolerance T]]\n"
                                  "                    [--focus D | --focus-at X,Y] [--aperture A] [--bokeh box|disc] (refocus)  [--haze-beta B] [--airlight b,g,r] (haze)\n"
                                  "                    [--disparity D] [--zero-parallax Z | --zero-parallax-at X,Y] [--anaglyph] (stereo)\n"
+                                 "                    --shift dx,dy [--dolly z] [--zero-parallax Z | --zero-parallax-at X,Y] (parallax)\n"
                                  "                    [--light-dir x,y,z | --light-at X,Y [--light-height H] [--light-radius R]] [--relief S] [--ambient A] [--diffuse D] [--light-color b,g,r] (relight)\n"
                                  "                    [--shadows N [--shadow-bias B] [--shadow-softness S] [--shadow-strength T]] (relight with cast shadows)\n"
                                  "                    [--paint x,y,label,radius]... [--live N [--paint-at frame:x,y,label,radius]...] [--devices D --batch B [--sequential] [--write-all]] [--png] [--cold]\n"
@@ -546,6 +555,8 @@ int main(int argc, const char *argv[]) {
         else if (!std::strcmp(argv[i], "--zero-parallax")) { job.zero_depth = (float)std::atof(next()); job.zero_x = -1; }
         else if (!std::strcmp(argv[i], "--zero-parallax-at")) { if (std::sscanf(next(), "%d,%d", &job.zero_x, &job.zero_y) != 2) { std::printf("--zero-parallax-at wants X,Y\n"); return 1; } }
         else if (!std::strcmp(argv[i], "--anaglyph")) job.anaglyph = true;
+        else if (!std::strcmp(argv[i], "--shift")) { if (std::sscanf(next(), "%d,%d", &job.shift_x, &job.shift_y) != 2) { std::printf("--shift wants dx,dy\n"); return 1; } }
+        else if (!std::strcmp(argv[i], "--dolly")) job.dolly = (float)std::atof(next());
         else if (!std::strcmp(argv[i], "--light-dir")) {
             if (std::sscanf(next(), "%f,%f,%f", &job.light.x, &job.light.y, &job.light.z) != 3) { std::printf("--light-dir wants x,y,z\n"); return 1; }
             job.light.kind = RTDD_LIGHT_DIRECTIONAL;
@@ -581,8 +592,8 @@ int main(int argc, const char *argv[]) {
     if (job.shadows && job.effect != "relight") { std::printf("--shadows needs --effect relight\n"); return 1; }
     if (shadow_opt && !job.shadows) { std::printf("--shadow-bias, --shadow-softness and --shadow-strength need --shadows N\n"); return 1; }
     // a live frame's sticky effect is an effect code without parameters (rtdd_live_submit_ex): the aimed effects are not available there
-    if (live > 0 && (job.effect == "refocus" || job.effect == "stereo" || job.effect == "relight" || (job.effect == "haze" && job.haze_ex))) {
-        std::printf("--live renders the reference's three effects only: --effect refocus, --effect stereo, --effect relight and --haze-beta / --airlight are not supported with --live\n");
+    if (live > 0 && (job.effect == "refocus" || job.effect == "stereo" || job.effect == "parallax" || job.effect == "relight" || (job.effect == "haze" && job.haze_ex))) {
+        std::printf("--live renders the reference's three effects only: --effect refocus, --effect stereo, --effect parallax, --effect relight and --haze-beta / --airlight are not supported with --live\n");
         return 1;
     }
     Pnm rgb;

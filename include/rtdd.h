@@ -324,7 +324,7 @@ int rtdd_simulate_haze(rtdd_ctx *ctx, const uint8_t *original, size_t originalPi
 /* ---- aimed depth effects (extensions; no reference behaviour) --------------------------------
  * Added after ABI version 230 without a version bump: a host finds them by symbol (dlsym).  The next bump of RTDD_VERSION
  * should cover them (rtdd_simulate_refocus, rtdd_simulate_lens_blur, rtdd_simulate_haze_ex, rtdd_simulate_stereo, rtdd_simulate_relight,
- * rtdd_simulate_relight_shadowed), together with a parameterised live effect
+ * rtdd_simulate_relight_shadowed, rtdd_simulate_parallax), together with a parameterised live effect
  * (rtdd_live_submit_ex takes an effect code only and knows none of them). */
 
 /* Refocus: the defocus effect sharp at a chosen depth instead of at depth 0.
@@ -479,6 +479,51 @@ typedef struct rtdd_shadow {
 int rtdd_simulate_relight_shadowed(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch,
                                    const float *depth, size_t depthPitch, uint8_t *artistic, size_t artisticPitch,
                                    int rows, int cols, const rtdd_light *light, const rtdd_shadow *shadow /* both HOST, read before the call returns */);
+
+/* Parallax: the view of a camera that moved sideways, up or down, forward or back, rendered from the depth map (0 near, 255 far, as
+ * stereo reads it) -- stereo's forward warp with a shift in x AND y that may vary over the image, so sources cross rows, the nearest
+ * source wins over the whole image and holes are filled in every direction.  Every operation below is one f32 operation, rounded once,
+ * NONE fused, in the order written; / is IEEE correctly rounded; rintf rounds half to even.
+ *   d' = fminf(fmaxf(d, 0), 255), a NaN depth is 0, -0 counts as +0 (stereo's clamp);  z0 = zeroParallaxDepth when zeroX < 0, otherwise
+ *       the depth map's value at (zeroX, zeroY), clamped alike and READ BY THE KERNEL ON THE DEVICE when it runs (no host
+ *       synchronisation; the call may sit behind an asynchronous estimate)
+ *   cx = (float)(cols - 1) * 0.5f;  cy = (float)(rows - 1) * 0.5f                              (the image centre, on the host)
+ *   per pixel (x, y):  ax = (float)shiftX - (dolly * ((float)x - cx));  ay = (float)shiftY - (dolly * ((float)y - cy))
+ *       (the shift of a point 255 depth units behind z0; with the bounds below |ax|, |ay| <= 512)
+ *   SOURCE (x, y):  sx = (int)rintf((ax * (d' - z0)) / 255.0f);  sy = (int)rintf((ay * (d' - z0)) / 255.0f)     (|sx|, |sy| <= 512)
+ *       it lands on the target t = (x + sx, y + sy) and is dropped when t lies outside the image
+ *   WINNER:  of several sources on one target the NEAREST wins: the smallest d'; among equal d' the smallest y * cols + x.  A filled
+ *       target is view[t] = original[winner], no interpolation.
+ *   HOLE (a target t = (x, y) no source lands on):  ax, ay as above AT THE HOLE'S OWN POSITION;  m = fmaxf(fabsf(ax), fabsf(ay))
+ *       m == 0: view[t] = original[t].  Otherwise stx = ax / m;  sty = ay / m, and the hole marches along the major axis of (ax, ay)
+ *       towards the BACKGROUND side, the direction +a, the way far points move: for k = 1, 2, ...
+ *           p = (x + (int)rintf((float)k * stx), y + (int)rintf((float)k * sty))
+ *       the first p outside the image ends the march; the first FILLED p gives view[t] = view[p] (= original[p's winner]).  A march
+ *       that ends without one is run again with both offsets negated (p = (x - (int)rintf(..), y - (int)rintf(..))); if that ends
+ *       too, view[t] = original[t].
+ *   artistic = view.
+ * shiftX > 0 renders a camera moved to the right (stereo's D), shiftY > 0 one moved down, dolly > 0 one moved forward: points nearer
+ * than z0 spread away from the image centre, farther ones move towards it.
+ * Identities: shiftY == 0 and dolly == 0 gives rtdd_simulate_stereo(..., disparity = shiftX, ..., RTDD_STEREO_VIEW) byte for byte
+ * (there the smallest d' IS the smallest s * sign(D), and the march is stereo's nearest filled target on the background side, then
+ * on the other); shiftX == shiftY == 0 with dolly == 0, or a constant map equal to z0, gives the original.
+ * The outcome never depends on the order in which sources reach a target; the output does not depend on RTDD_OPT_FP_CONTRACT.
+ * Stream-ordered (a fill, a scatter and a resolve pass over 8 bytes of context-owned scratch per pixel), deterministic, not in place.
+ * Refused on the host (RTDD_ERR_INVALID), before any launch: the rules of the three effects (null pointers, pitches, image size); a
+ * null view; a shift outside [-256, 256]; a dolly that is non-finite or too large (see the field); a zeroParallaxDepth that is
+ * non-finite or outside [0, 255] when it is used; a zero-parallax pixel outside the image when zeroX >= 0; original == artistic.
+ * RTDD_ERR_NOMEM, before any launch, when the scratch cannot be allocated. */
+typedef struct rtdd_parallax {
+    int   shiftX, shiftY;       /* each in [-256, 256]: the shift in pixels of a point 255 depth units behind the zero-parallax depth;
+                                   shiftX > 0: the camera moved to the right (stereo's D), shiftY > 0: the camera moved down */
+    float dolly;                /* > 0: the camera moved forward (near points spread away from the image centre), < 0: back.  Finite,
+                                   |dolly| * max(cols - 1, rows - 1) / 2 <= 256 evaluated in double */
+    float zeroParallaxDepth;    /* used when zeroX < 0: finite, in [0, 255] */
+    int   zeroX, zeroY;         /* zeroX >= 0: the depth map's value at this pixel instead, READ BY THE KERNEL ON THE DEVICE when it runs */
+} rtdd_parallax;
+int rtdd_simulate_parallax(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch,
+                           const float *depth, size_t depthPitch, uint8_t *artistic, size_t artisticPitch,
+                           int rows, int cols, const rtdd_parallax *view /* HOST, read before the call returns */);
 
 /* ---- whole-estimate driver ------------------------------------------------
  * One depth estimate = the loop body of src/main.cpp:232-295, run as a single stream-ordered launch

@@ -53,7 +53,7 @@ C_ABI_SYMBOLS = [
     "rtdd_pyramid_create_batch", "rtdd_pyramid_select", "rtdd_pyramid_batch", "rtdd_estimate_depth_batch", "rtdd_pyramid_level_info", "rtdd_live_submit_ex",
     "rtdd_simulate_refocus", "rtdd_simulate_haze_ex", "rtdd_simulate_stereo", "rtdd_simulate_lens_blur",
     "rtdd_paint_strokes", "rtdd_pyramid_annotation_rebuild",
-    "rtdd_simulate_relight", "rtdd_simulate_relight_shadowed",
+    "rtdd_simulate_relight", "rtdd_simulate_relight_shadowed", "rtdd_simulate_parallax",
 ]
 IMG_ORIGINAL, IMG_GRAY, IMG_SCRIBBLE, IMG_EDITED, IMG_DEPTH, IMG_DEPTH_U8, IMG_ARTISTIC = range(7)
 EFFECT_NONE, EFFECT_DEFOCUS, EFFECT_DESATURATION, EFFECT_HAZE = range(4)
@@ -117,6 +117,17 @@ class Shadow(C.Structure):
 
     def __init__(self, maxSteps=256, bias=0.0, softness=0.0, strength=1.0):
         super().__init__(maxSteps, bias, softness, strength)
+
+
+class Parallax(C.Structure):
+    """rtdd_parallax: the camera moved by (shiftX, shiftY) -- pixels of shift of a point 255 depth units behind the zero-parallax depth --
+    and forward by `dolly` (< 0: back); zero parallax at `zeroParallaxDepth` or (zeroX >= 0) at the depth map's value at (zeroX, zeroY),
+    read on the device."""
+    _fields_ = [("shiftX", C.c_int), ("shiftY", C.c_int), ("dolly", C.c_float), ("zeroParallaxDepth", C.c_float), ("zeroX", C.c_int),
+                ("zeroY", C.c_int)]
+
+    def __init__(self, shiftX=0, shiftY=0, dolly=0.0, zeroParallaxDepth=0.0, zeroX=-1, zeroY=-1):
+        super().__init__(shiftX, shiftY, dolly, zeroParallaxDepth, zeroX, zeroY)
 
 
 class Profile(C.Structure):
@@ -387,6 +398,13 @@ class Context:
         self._check(lib().rtdd_simulate_relight_shadowed(self._h, o, op, d, dp, a, ap, C.c_int(rows), C.c_int(cols),
                                                          C.byref(light) if light is not None else None,
                                                          C.byref(shadow) if shadow is not None else None))
+
+    def simulate_parallax(self, originalImage, depthImage, artisticImage, rows, cols, view):
+        """The view of a camera moved sideways, up or forward as `view` (a Parallax, or None for the C call's null pointer) says: a
+        forward warp over the whole image, the nearest source wins, holes filled from the background side."""
+        o, op = _img(originalImage); d, dp = _img(depthImage); a, ap = _img(artisticImage)
+        self._check(lib().rtdd_simulate_parallax(self._h, o, op, d, dp, a, ap, C.c_int(rows), C.c_int(cols),
+                                                 C.byref(view) if view is not None else None))
 
     # ---- whole-estimate driver (src/main.cpp:92-155, 232-295)
     def pyramid_create(self, rows, cols):

@@ -879,6 +879,7 @@ int launch_effect(rtdd_ctx *ctx, const Effect &e) {
         case Effect::kLensBlur: return launch_lens_blur(ctx, e);       // lens_blur.hip
         case Effect::kRelight: return launch_relight(ctx, e);          // relight.hip
         case Effect::kRelightShadow: return launch_relight_shadow(ctx, e);     // relight_shadow.hip
+        case Effect::kParallax: return launch_parallax(ctx, e);        // parallax.hip
         case RTDD_EFFECT_DESATURATION:
             return launch_blend<0>(ctx, e.original, e.originalPitch, e.gray, e.grayPitch, e.depth, e.depthPitch, e.artistic, e.artisticPitch,
                                    e.rows, e.cols);

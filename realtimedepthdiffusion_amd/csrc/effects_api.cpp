@@ -1,5 +1,6 @@
 // effects_api.cpp -- the rtdd_simulate_* entry points (include/rtdd.h): arguments checked, one Effect record built, handed to
 // launch_effect (effect_kernels.hip) and, behind unconfirmed solves, to the pending-call log (heal.cpp).  Host code only.
+#include <algorithm>
 #include <cmath>
 
 #include "rtdd_internal.hpp"
@@ -196,6 +197,30 @@ int rtdd_simulate_relight_shadowed(rtdd_ctx *ctx, const uint8_t *original, size_
     }
     if (rows == 0 || cols == 0) return RTDD_OK;
     REQUIRE(ctx, original != artistic, "relight cannot run in place");
+    return simulate(ctx, e);
+}
+
+int rtdd_simulate_parallax(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
+                           uint8_t *artistic, size_t artisticPitch, int rows, int cols, const rtdd_parallax *view) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    int rc = check_effect(ctx, original, depth, artistic, originalPitch, depthPitch, artisticPitch, rows, cols);
+    if (rc != RTDD_OK) return rc;
+    REQUIRE(ctx, view, "null view");
+    const rtdd_parallax &q = *view;
+    REQUIRE(ctx, q.shiftX >= -256 && q.shiftX <= 256 && q.shiftY >= -256 && q.shiftY <= 256, "|shiftX| and |shiftY| must be <= 256");
+    const int span = std::max(std::max(cols - 1, rows - 1), 0);
+    REQUIRE(ctx, std::isfinite(q.dolly) && std::fabs((double)q.dolly) * span / 2.0 <= 256.0,
+            "dolly must be finite with |dolly| * max(cols - 1, rows - 1) / 2 <= 256");
+    if (q.zeroX < 0) REQUIRE(ctx, std::isfinite(q.zeroParallaxDepth) && q.zeroParallaxDepth >= 0.0f && q.zeroParallaxDepth <= 255.0f,
+                             "zeroParallaxDepth must be finite and in [0, 255]");
+    else REQUIRE(ctx, q.zeroX < cols && q.zeroY >= 0 && q.zeroY < rows, "zero-parallax pixel outside the image");
+    if (rows == 0 || cols == 0) return RTDD_OK;
+    REQUIRE(ctx, original != artistic, "parallax cannot run in place");
+    Effect e{Effect::kParallax, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols};
+    Effect::Parallax &P = e.parallax;
+    P.shiftX = q.shiftX; P.shiftY = q.shiftY; P.dolly = q.dolly; P.zeroX = q.zeroX; P.zeroY = q.zeroY;
+    P.zeroDepth = q.zeroParallaxDepth;
+    P.cx = (float)(cols - 1) * 0.5f; P.cy = (float)(rows - 1) * 0.5f;
     return simulate(ctx, e);
 }
 

@@ -1,0 +1,149 @@
+// parallax.hip -- the 2-D parallax view (rtdd_simulate_parallax, include/rtdd.h): the camera moved sideways, up or forward.  Stereo's
+// forward warp with a shift in x AND y that may vary over the image (the dolly): sources cross rows, so the occlusion is resolved over
+// the whole image, in a z-buffer in global memory, and holes open -- and are filled -- in every direction.
+//
+// Three stream-ordered passes over one 64-bit key per target (ctx->sat, 8 bytes per pixel):
+//   hipMemsetAsync 0xFF    every key all ones: empty
+//   k_parallax_scatter     one lane per source: key[t] = min(key[t], bits(d') << 32 | y * cols + x), one no-return 64-bit atomic.  d' is
+//                          in [+0, 255]: its bit pattern is non-negative, so unsigned order is depth order; the low word breaks ties
+//                          towards the smallest source index and stays below 2^30 (check_effect: rows^2 + cols^2 < 2^31).  The minimum
+//                          does not depend on the order of arrival: deterministic.
+//   k_parallax_resolve     one lane per target (four where the artistic rows take dword stores): a filled key copies
+//                          original[low word]; an empty one marches over the KEYS along the major axis of its own (ax, ay).
+// The launch boundary between scatter and resolve is what completes every atomic before a key is read.
+//
+// Shape.  A wave takes 64 consecutive sources of one row: one 256-byte read of the depth row, and -- neighbouring sources mostly land on
+// neighbouring targets -- an atomic wave-instruction that is mostly one or two runs of consecutive 8-byte keys.  The atomics execute
+// behind L2, nothing is fetched and nothing returns, so a wave holds no register for them and the kernel keeps full occupancy; what
+// bounds it is the rate of atomic requests, not the waves in flight.  No LDS pre-pass (DESIGN.md "Parallax").
+//
+// The arithmetic is the header's, operation by operation: -ffp-contract=off, no fmaf in this translation unit, `/` correctly rounded
+// (-fhip-fp32-correctly-rounded-divide-sqrt): the bytes are those of tests/parallax_ref.py and do not depend on RTDD_OPT_FP_CONTRACT.
+#include "rtdd_internal.hpp"
+#include "effect_common.hpp"
+
+namespace rtdd {
+
+typedef Effect::Parallax Parallax;
+constexpr u64 kPxEmpty = ~0ull;
+
+// (ax, ay) of the header at pixel (x, y): the shift of a point 255 depth units behind z0
+__device__ __forceinline__ void parallax_a(const Parallax &v, int x, int y, float &ax, float &ay) {
+    ax = (float)v.shiftX - (v.dolly * ((float)x - v.cx));
+    ay = (float)v.shiftY - (v.dolly * ((float)y - v.cy));
+}
+// d' with -0 folded into +0 (fmaxf may return either zero): the key's high word is then a non-negative integer
+__device__ __forceinline__ float parallax_depth(float d) { return fminf(fmaxf(d, 0.0f), 255.0f) + 0.0f; }
+
+__global__ __launch_bounds__(256) void k_parallax_scatter(const float *__restrict__ depth, size_t dp, u64 *__restrict__ keys, int rows, int cols,
+                                                          Parallax v, const float *__restrict__ zp) {
+    const int y = blockIdx.y * 4 + wave_id();
+    if (y >= rows) return;                                           // wave-uniform: a wave is 64 sources of one row
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    if (x >= cols) return;
+    const float z0 = zp ? parallax_depth(*zp) : v.zeroDepth;        // the pixel form: one uniform load per wave, when the kernel runs
+    const float dc = parallax_depth(((const float *)((const char *)depth + (size_t)y * dp))[x]);
+    const float dz = dc - z0;
+    float ax, ay;
+    parallax_a(v, x, y, ax, ay);
+    const int tx = x + (int)rintf((ax * dz) / 255.0f), ty = y + (int)rintf((ay * dz) / 255.0f);
+    if (tx < 0 || tx >= cols || ty < 0 || ty >= rows) return;       // the only store of this kernel: inside the rows * cols keys
+    const u64 key = ((u64)__float_as_uint(dc) << 32) | (uint32_t)(y * cols + x);
+    (void)__hip_atomic_fetch_min(&keys[(size_t)ty * cols + tx], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// pixel `i` (= y * cols + x) of an interleaved BGR image as b | g << 8 | r << 16
+__device__ __forceinline__ uint32_t bgr_of_index(const uint8_t *__restrict__ orig, size_t op, uint32_t i, int cols) {
+    const uint32_t sy = i / (uint32_t)cols, sx = i - sy * (uint32_t)cols;
+    const uint8_t *p = orig + (size_t)sy * op + 3 * (size_t)sx;
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+}
+
+// The march of a hole at (x, y) with the step (stx, sty): the key of the first filled target on it, kPxEmpty when it leaves the image first.
+// One of |stx|, |sty| is 1: step k is k pixels along the major axis, so at most max(rows, cols) - 1 steps stay inside the image.
+__device__ __forceinline__ u64 parallax_march(const u64 *__restrict__ keys, int rows, int cols, int x, int y, float stx, float sty, int sign) {
+    for (int k = 1;; k++) {
+        const float kf = (float)k;
+        const int px = x + sign * (int)rintf(kf * stx), py = y + sign * (int)rintf(kf * sty);
+        if (px < 0 || px >= cols || py < 0 || py >= rows) return kPxEmpty;
+        const u64 key = keys[(size_t)py * cols + px];
+        if (key != kPxEmpty) return key;
+    }
+}
+
+// VEC: four targets per lane, the artistic row written as dwords (its rows 4-byte aligned); else one target per lane, written as bytes.
+// The original is gathered pixel by pixel either way.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_parallax_resolve(const uint8_t *__restrict__ orig, size_t op, const u64 *__restrict__ keys,
+                                                          uint8_t *__restrict__ art, size_t ap, int rows, int cols, Parallax v) {
+    const int y = blockIdx.y * 4 + wave_id();
+    if (y >= rows) return;                                           // wave-uniform
+    const int lane = threadIdx.x & 63;
+    uint8_t *arow = art + (size_t)y * ap;
+    auto pixel = [&](int x) -> uint32_t {                            // view[(x, y)]
+        const uint32_t self = (uint32_t)(y * cols + x);
+        u64 key = keys[self];
+        if (key == kPxEmpty) {                                       // a hole: towards the background side (+a), then the other one
+            float ax, ay;
+            parallax_a(v, x, y, ax, ay);
+            const float m = fmaxf(fabsf(ax), fabsf(ay));
+            if (m != 0.0f) {
+                const float stx = ax / m, sty = ay / m;
+                key = parallax_march(keys, rows, cols, x, y, stx, sty, 1);
+                if (key == kPxEmpty) key = parallax_march(keys, rows, cols, x, y, stx, sty, -1);
+            }
+        }
+        return bgr_of_index(orig, op, key == kPxEmpty ? self : (uint32_t)key, cols);
+    };
+    if (!VEC) {
+        const int x = blockIdx.x * 64 + lane;
+        if (x >= cols) return;
+        const uint32_t o = pixel(x);
+        uint8_t *p = arow + 3 * (size_t)x;
+        p[0] = (uint8_t)o; p[1] = (uint8_t)(o >> 8); p[2] = (uint8_t)(o >> 16);
+        return;
+    }
+    const int x = (blockIdx.x * 64 + lane) * 4;
+    if (x >= cols) return;
+    if (x + 3 < cols) {
+        const uint32_t o0 = pixel(x), o1 = pixel(x + 1), o2 = pixel(x + 2), o3 = pixel(x + 3);
+        uint32_t *a3 = (uint32_t *)(arow + 3 * (size_t)x);
+        a3[0] = o0 | (o1 << 24);
+        a3[1] = (o1 >> 8) | (o2 << 16);
+        a3[2] = (o2 >> 16) | (o3 << 8);
+    } else {
+        for (int xx = x; xx < cols; xx++) {                          // the ragged end of a row
+            const uint32_t o = pixel(xx);
+            uint8_t *p = arow + 3 * (size_t)xx;
+            p[0] = (uint8_t)o; p[1] = (uint8_t)(o >> 8); p[2] = (uint8_t)(o >> 16);
+        }
+    }
+}
+
+// rtdd_simulate_parallax (arguments checked by effects_api.cpp): the keys emptied, scattered, resolved.
+int launch_parallax(rtdd_ctx *ctx, const Effect &e) {
+    const Parallax &v = e.parallax;
+    // The keys live in the context's table buffer.  rows * cols < 2^30 (check_effect), so the buffer stays below 8 GiB and every key
+    // index fits the kernels' size_t arithmetic: what can fail is the allocation.
+    const size_t npx = (size_t)e.rows * e.cols;
+    if (ensure_sat(ctx, npx * 2) != RTDD_OK) {
+        (void)hipGetLastError();
+        return fail(ctx, RTDD_ERR_NOMEM, "parallax: the key buffer (8 bytes per pixel) could not be allocated");
+    }
+    ctx->sat_rows = ctx->sat_cols = 0;                               // whatever table lay here is gone: the next table-path defocus zeroes its padding again
+    u64 *keys = (u64 *)ctx->sat;
+    RTDD_HIP(ctx, hipMemsetAsync(keys, 0xFF, npx * sizeof(u64), ctx->stream));
+    const float *zp = pixel_ptr(e.depth, e.depthPitch, v.zeroX, v.zeroY);     // the pixel form of z0
+    const dim3 g((e.cols + 63) / 64, (e.rows + 3) / 4);
+    hipLaunchKernelGGL(k_parallax_scatter, g, dim3(256), 0, ctx->stream, e.depth, e.depthPitch, keys, e.rows, e.cols, v, zp);
+    RTDD_LAUNCH_CHECK(ctx, "k_parallax_scatter");
+    if (rows_aligned(e.artistic, e.artisticPitch))
+        hipLaunchKernelGGL(k_parallax_resolve<true>, dim3((e.cols + 255) / 256, g.y), dim3(256), 0, ctx->stream, e.original, e.originalPitch, keys,
+                           e.artistic, e.artisticPitch, e.rows, e.cols, v);
+    else hipLaunchKernelGGL(k_parallax_resolve<false>, g, dim3(256), 0, ctx->stream, e.original, e.originalPitch, keys, e.artistic, e.artisticPitch,
+                            e.rows, e.cols, v);
+    RTDD_LAUNCH_CHECK(ctx, "k_parallax_resolve");
+    return RTDD_OK;
+}
+
+}  // namespace rtdd

@@ -95,8 +95,8 @@ struct LiveTargets {
 // One depth effect, arguments checked: what to render, on which images, with which parameters.  Built by the rtdd_simulate_* entry
 // points (effects_api.cpp) and by a live frame (live_effect), launched by launch_effect, and logged by value (PendingOp) to be launched again.
 struct Effect {
-    enum : int { kRefocus = RTDD_EFFECT_HAZE + 1, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow };   // the extensions, after the public kinds
-    int kind = RTDD_EFFECT_NONE;                    // RTDD_EFFECT_DEFOCUS / _DESATURATION / _HAZE, kRefocus, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow
+    enum : int { kRefocus = RTDD_EFFECT_HAZE + 1, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow, kParallax };   // the extensions, after the public kinds
+    int kind = RTDD_EFFECT_NONE;                    // RTDD_EFFECT_DEFOCUS / _DESATURATION / _HAZE, kRefocus, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow, kParallax
     const uint8_t *original = nullptr; size_t originalPitch = 0;
     const float *depth = nullptr; size_t depthPitch = 0;
     uint8_t *artistic = nullptr; size_t artisticPitch = 0;
@@ -124,6 +124,13 @@ struct Effect {
         int maxSteps = 0;
         float bias = 0.0f, softness = 0.0f, strength = 0.0f;
     } shadow = {};
+    // parallax (kParallax): the view as rtdd_parallax states it (include/rtdd.h rtdd_simulate_parallax) and the image centre the host
+    // computed, by value -- a replay needs no rtdd_parallax.  zeroX >= 0: the map's pixel (zeroX, zeroY), read by the kernel
+    struct Parallax {
+        int shiftX = 0, shiftY = 0, zeroX = -1, zeroY = -1;
+        float dolly = 0.0f, zeroDepth = 0.0f;
+        float cx = 0.0f, cy = 0.0f;                 // (float)(cols - 1) * 0.5f, (float)(rows - 1) * 0.5f
+    } parallax = {};
 };
 
 // The defocus window scale K of src/GPUDepthEffect.cu:42, (int)(aperture * diagonal) -- double * float and the int products as there,
@@ -248,7 +255,7 @@ struct rtdd_ctx {
     bool status_writer_behind = false;
     signed char persist_fit[17][2];  // per (tile id, contraction): does one workgroup of the persistent kernel fit a CU of THIS device (-1 = not asked yet)
     rtdd::Bounce bounce;            // host <-> device 2-D copies with an unaligned host pitch, on ctx->stream (copy_h2d / copy_d2h, cascade_api.cpp)
-    uint32_t *sat = nullptr;        // defocus summed-area table scratch
+    uint32_t *sat = nullptr;        // defocus summed-area table scratch; the parallax view's keys
     size_t sat_elems = 0;
     int sat_rows = 0, sat_cols = 0;     // the geometry the table's zero padding was laid out for (effect_kernels.hip)
     int num_cus = 256;
@@ -367,6 +374,8 @@ int launch_lens_blur(rtdd_ctx *ctx, const Effect &e);
 int launch_relight(rtdd_ctx *ctx, const Effect &e);
 // ---- relight_shadow.hip: Effect::kRelightShadow (called by launch_effect) --------------------------
 int launch_relight_shadow(rtdd_ctx *ctx, const Effect &e);
+// ---- parallax.hip: Effect::kParallax (called by launch_effect) -------------------------------------
+int launch_parallax(rtdd_ctx *ctx, const Effect &e);
 
 // ---- cascade.hip -------------------------------------------------------------------------------
 int launch_bgr2gray(rtdd_ctx *ctx, const uint8_t *bgr, size_t bp, uint8_t *gray, size_t gp, int rows, int cols);
