@@ -18,6 +18,10 @@
 //                 ambient 0.25, diffuse 1; --light-at: a point light over that pixel, anchored at its depth, height 100, radius 200)
 //                 --effect relight --shadows N [--shadow-bias B] [--shadow-softness S] [--shadow-strength T]   (rtdd_simulate_relight_shadowed: cast
 //                 shadows, N steps of the march; default bias 0, softness 0 = hard, strength 1)
+//                 --effect ao [--ao-radius R] [--ao-directions 4|8] [--ao-bias B] [--ao-strength T] [--relief S] [--ao-map]   (rtdd_simulate_ambient_occlusion
+//                 without a light: the original darkened in creases, or --ao-map: the occlusion as a gray map; default radius 16, 8 directions,
+//                 bias 0, strength 1, relief 2), --effect relight --ao R [--ao-directions ..] [--ao-bias ..] [--ao-strength ..]   (the same call
+//                 under relight's light: its ambient term occluded; not together with --shadows)
 //     key 't'  -> prints "Processing Time"  (main.cpp:320-322; wall clock here, the reference uses clock()); the process's one-time costs
 //                 (~20 ms: code objects, first allocations) are paid by a warm-up on a context of its own first -- --cold leaves it out
 //     --paint x,y,label,radius  = a mouse drag sample (main.cpp:46-62), repeatable; --paint-at F:x,y,label,radius = the same while --live
@@ -208,6 +212,10 @@ struct Job {
     // --shadows N (given: rtdd_simulate_relight_shadowed), --shadow-bias, --shadow-softness, --shadow-strength
     bool shadows = false;
     rtdd_shadow shadow = {0, 0.0f, 0.0f, 1.0f};
+    // --effect ao, or --effect relight --ao R (ao_lit): rtdd_simulate_ambient_occlusion; --ao-radius / --ao R, --ao-directions, --ao-bias, --ao-strength,
+    // --ao-map; the relief is --relief's (the light's)
+    bool ao_lit = false;
+    rtdd_ambient_occlusion ao = {RTDD_AO_SHADE, 8, 16, 2.0f, 0.0f, 1.0f};
     bool sequential = false;      // --sequential: a --batch as one estimate after the other (default: rtdd_estimate_depth_batch, all images in the same launches)
     bool cold = false;            // --cold: no warm-up: the first (and, without --live, only) estimate pays the one-time costs
 };
@@ -481,8 +489,16 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
         else if (job.effect == "relight") {
             rtdd_light light = job.light;
             if (light.kind == RTDD_LIGHT_POINT) light.z = job.light_height;
-            if (job.shadows) CK(rtdd_simulate_relight_shadowed(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols, &light, &job.shadow));
+            rtdd_ambient_occlusion ao = job.ao;
+            ao.relief = light.relief;
+            if (job.ao_lit) CK(rtdd_simulate_ambient_occlusion(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols, &ao, &light));
+            else if (job.shadows) CK(rtdd_simulate_relight_shadowed(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols, &light, &job.shadow));
             else CK(rtdd_simulate_relight(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols, &light));
+        }
+        else if (job.effect == "ao") {
+            rtdd_ambient_occlusion ao = job.ao;
+            ao.relief = job.light.relief;
+            CK(rtdd_simulate_ambient_occlusion(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols, &ao, nullptr));
         }
         depth_u8->resize((size_t)rows * cols);
         CK(rtdd_download(ctx, depth_u8->data(), cols, p_u8, pi_u8, cols, rows));   // main.cpp:291 (synchronises)
@@ -496,12 +512,13 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
 }
 
 int main(int argc, const char *argv[]) {
-    if (argc == 1) { std::printf("Usage: rtdd_harness -i image.(jpg|png|ppm) [-a annotation.(png|pgm)] [-o prefix] [--effect defocus|desaturation|haze|refocus|stereo|parallax|relight] [--iters N] [--refine sor|mg|auto [--tolerance T]]\n"
+    if (argc == 1) { std::printf("Usage: rtdd_harness -i image.(jpg|png|ppm) [-a annotation.(png|pgm)] [-o prefix] [--effect defocus|desaturation|haze|refocus|stereo|parallax|relight|ao] [--iters N] [--refine sor|mg|auto [--tolerance T]]\n"
                                  "                    [--focus D | --focus-at X,Y] [--aperture A] [--bokeh box|disc] (refocus)  [--haze-beta B] [--airlight b,g,r] (haze)\n"
                                  "                    [--disparity D] [--zero-parallax Z | --zero-parallax-at X,Y] [--anaglyph] (stereo)\n"
                                  "                    --shift dx,dy [--dolly z] [--zero-parallax Z | --zero-parallax-at X,Y] (parallax)\n"
                                  "                    [--light-dir x,y,z | --light-at X,Y [--light-height H] [--light-radius R]] [--relief S] [--ambient A] [--diffuse D] [--light-color b,g,r] (relight)\n"
                                  "                    [--shadows N [--shadow-bias B] [--shadow-softness S] [--shadow-strength T]] (relight with cast shadows)\n"
+                                 "                    [--ao-radius R] [--ao-directions 4|8] [--ao-bias B] [--ao-strength T] [--relief S] [--ao-map] (ao)  [--ao R [--ao-directions ..] [--ao-bias ..] [--ao-strength ..]] (relight with its ambient term occluded)\n"
                                  "                    [--paint x,y,label,radius]... [--live N [--paint-at frame:x,y,label,radius]...] [--devices D --batch B [--sequential] [--write-all]] [--png] [--cold]\n"
                                  "                    [--stroke x0,y0,x1,y1,label,radius[,round]]... [--erase x0,y0,x1,y1,radius[,round]]...   (segments, in command-line order, one rtdd_paint_strokes call after --paint)\n"
                                  "                    [--stroke-at frame:x0,y0,x1,y1,label,radius[,round]]... [--erase-at frame:x0,y0,x1,y1,radius[,round]]...   (--live: in front of that frame)\n"
@@ -513,7 +530,7 @@ int main(int argc, const char *argv[]) {
     }
     Job job;
     std::string in, an, out = "";
-    bool png = false, write_all = false, shadow_opt = false;
+    bool png = false, write_all = false, shadow_opt = false, ao_opt = false, ao_radius_opt = false;
     int devices = 1, batch = 1, live = 0;
     for (int i = 1; i < argc; i++) {
         auto next = [&]() -> const char * { return i + 1 < argc ? argv[++i] : ""; };
@@ -572,6 +589,12 @@ int main(int argc, const char *argv[]) {
         else if (!std::strcmp(argv[i], "--shadow-bias")) { job.shadow.bias = (float)std::atof(next()); shadow_opt = true; }
         else if (!std::strcmp(argv[i], "--shadow-softness")) { job.shadow.softness = (float)std::atof(next()); shadow_opt = true; }
         else if (!std::strcmp(argv[i], "--shadow-strength")) { job.shadow.strength = (float)std::atof(next()); shadow_opt = true; }
+        else if (!std::strcmp(argv[i], "--ao")) { job.ao.radius = std::atoi(next()); job.ao_lit = true; }
+        else if (!std::strcmp(argv[i], "--ao-radius")) { job.ao.radius = std::atoi(next()); ao_radius_opt = true; }
+        else if (!std::strcmp(argv[i], "--ao-directions")) { job.ao.directions = std::atoi(next()); ao_opt = true; }
+        else if (!std::strcmp(argv[i], "--ao-bias")) { job.ao.bias = (float)std::atof(next()); ao_opt = true; }
+        else if (!std::strcmp(argv[i], "--ao-strength")) { job.ao.strength = (float)std::atof(next()); ao_opt = true; }
+        else if (!std::strcmp(argv[i], "--ao-map")) { job.ao.mode = RTDD_AO_MAP; ao_radius_opt = true; }
         else if (!std::strcmp(argv[i], "--ambient")) job.light.ambient = (float)std::atof(next());
         else if (!std::strcmp(argv[i], "--diffuse")) job.light.diffuse = (float)std::atof(next());
         else if (!std::strcmp(argv[i], "--light-color")) {
@@ -591,9 +614,15 @@ int main(int argc, const char *argv[]) {
     // cast shadows belong to relight, and their parameters to --shadows: a stray one is refused, not dropped
     if (job.shadows && job.effect != "relight") { std::printf("--shadows needs --effect relight\n"); return 1; }
     if (shadow_opt && !job.shadows) { std::printf("--shadow-bias, --shadow-softness and --shadow-strength need --shadows N\n"); return 1; }
+    // ambient occlusion is --effect ao, or --ao R under --effect relight (without cast shadows: one call renders one or the other); its
+    // parameters belong to one of the two: a stray one is refused, not dropped
+    if (job.ao_lit && job.effect != "relight") { std::printf("--ao needs --effect relight (without a light: --effect ao --ao-radius R)\n"); return 1; }
+    if (job.ao_lit && job.shadows) { std::printf("--ao and --shadows cannot be combined: ambient occlusion and cast shadows are separate calls\n"); return 1; }
+    if (ao_radius_opt && job.effect != "ao") { std::printf("--ao-radius and --ao-map need --effect ao (under --effect relight: --ao R)\n"); return 1; }
+    if (ao_opt && !job.ao_lit && job.effect != "ao") { std::printf("--ao-directions, --ao-bias and --ao-strength need --ao R or --effect ao\n"); return 1; }
     // a live frame's sticky effect is an effect code without parameters (rtdd_live_submit_ex): the aimed effects are not available there
-    if (live > 0 && (job.effect == "refocus" || job.effect == "stereo" || job.effect == "parallax" || job.effect == "relight" || (job.effect == "haze" && job.haze_ex))) {
-        std::printf("--live renders the reference's three effects only: --effect refocus, --effect stereo, --effect parallax, --effect relight and --haze-beta / --airlight are not supported with --live\n");
+    if (live > 0 && (job.effect == "refocus" || job.effect == "stereo" || job.effect == "parallax" || job.effect == "relight" || job.effect == "ao" || (job.effect == "haze" && job.haze_ex))) {
+        std::printf("--live renders the reference's three effects only: --effect refocus, --effect stereo, --effect parallax, --effect relight, --effect ao and --haze-beta / --airlight are not supported with --live\n");
         return 1;
     }
     Pnm rgb;

@@ -324,7 +324,7 @@ int rtdd_simulate_haze(rtdd_ctx *ctx, const uint8_t *original, size_t originalPi
 /* ---- aimed depth effects (extensions; no reference behaviour) --------------------------------
  * Added after ABI version 230 without a version bump: a host finds them by symbol (dlsym).  The next bump of RTDD_VERSION
  * should cover them (rtdd_simulate_refocus, rtdd_simulate_lens_blur, rtdd_simulate_haze_ex, rtdd_simulate_stereo, rtdd_simulate_relight,
- * rtdd_simulate_relight_shadowed, rtdd_simulate_parallax), together with a parameterised live effect
+ * rtdd_simulate_relight_shadowed, rtdd_simulate_parallax, rtdd_simulate_ambient_occlusion), together with a parameterised live effect
  * (rtdd_live_submit_ex takes an effect code only and knows none of them). */
 
 /* Refocus: the defocus effect sharp at a chosen depth instead of at depth 0.
@@ -524,6 +524,56 @@ typedef struct rtdd_parallax {
 int rtdd_simulate_parallax(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch,
                            const float *depth, size_t depthPitch, uint8_t *artistic, size_t artisticPitch,
                            int rows, int cols, const rtdd_parallax *view /* HOST, read before the call returns */);
+
+/* Ambient occlusion: the third term of relight's lighting model.  The height field H(x, y) = relief * (255 - d'(x, y)) of
+ * rtdd_simulate_relight_shadowed is searched, from every pixel, along 4 or 8 fixed compass directions over `radius` pixels for its
+ * HORIZON; a pixel whose horizons stand high -- a crease, the foot of an object against a wall, the inside of a fold -- loses its
+ * ambient light.  Alone it darkens the original or renders the occlusion as a gray map; under a light it is rtdd_simulate_relight
+ * with the ambient term occluded.  The rules of rtdd_simulate_relight carry over: every operation is one f32 operation, rounded once,
+ * NONE fused, in the order written; sqrtf and / are IEEE correctly rounded; denormals are kept; d', shade, k_c and every quantity of
+ * the light are exactly rtdd_simulate_relight's.
+ *   H(x, y) = relief * (255 - d'(x, y))          relief: ao.relief when light == NULL, light->relief otherwise (the two must agree)
+ *   directions j = 0 .. 7:  (ux, uy) = (1,0) (1,1) (0,1) (-1,1) (-1,0) (-1,-1) (0,-1) (1,-1);  directions == 4 uses j = 0, 2, 4, 6 only
+ *   inv_j[k], k = 1 .. radius, on the host in double, rounded to f32 once:
+ *       axis directions (j even):  (float)(1.0 / (double)k)
+ *       diagonals       (j odd):   (float)(1.0 / ((double)k * sqrt(2.0)))
+ *   per pixel and direction, for k = 1 .. radius:
+ *       p = (x + k*ux, y + k*uy);  the first p outside the image ends this direction's march
+ *       rise = (H(p) - H(x, y)) - bias
+ *       t_k  = rise * inv_j[k]                                   (the tangent of the elevation of p seen from the pixel)
+ *   tmax_j = max(0, max over k of t_k)                           (a horizon below the pixel's own plane counts as 0)
+ *   occ_j  = tmax_j / sqrtf(1 + (tmax_j * tmax_j))               (the sine of the horizon angle)
+ *   s    = the occ_j added in ascending j, left to right: ((occ_0 + occ_1) + occ_2) + ...   (4 directions: ((occ_0 + occ_2) + occ_4) + occ_6)
+ *   mean = s * (1 / directions)                                  (0.25f or 0.125f: exact)
+ *   ao   = 1 - (strength * mean)                                 (in [0, 1] up to the last rounding; the bytes below truncate towards zero)
+ * per channel c of B, G, R:
+ *   RTDD_AO_SHADE, light == NULL:  out_c = (uchar)(o_c * ao)
+ *   RTDD_AO_SHADE, light != NULL:  out_c = (uchar) fminf(o_c * ((ambient * ao) + (k_c * shade)), 255)     (relight, its ambient term occluded)
+ *   RTDD_AO_MAP:                   out_B = out_G = out_R = (uchar)(255 * ao);  `original` is validated but not read; light must be NULL
+ * The maximum over k does not depend on the order of the steps.  No height exceeds relief * 255 and rounding is monotonic, so once
+ * ((relief * 255 - H(x, y)) - bias) * inv_j[k] <= tmax_j no later step can win: an implementation may stop a direction there, and it may
+ * treat positions outside the image as a height of minus infinity.  Both are its freedoms, not part of the rule.
+ * Identities: radius == 0, strength == 0, relief == 0 or a constant map give the original (light == NULL) or rtdd_simulate_relight's
+ * bytes (light != NULL); RTDD_AO_MAP gives 255 everywhere in those cases.  Nothing produces a NaN: rise is finite and inv_j[k] is
+ * finite and positive.
+ * The output does not depend on RTDD_OPT_FP_CONTRACT; one kernel launch, stream-ordered, deterministic, not in place.  A point light's
+ * anchor pixel is read by the kernel on the device, as in rtdd_simulate_relight.  Cast shadows are not combined with it.
+ * Refused on the host (RTDD_ERR_INVALID), before any launch: the rules of the three effects (null pointers, pitches, image size); a
+ * null ao; an unknown mode; directions other than 4 or 8; any non-finite field; any field outside the ranges below; RTDD_AO_MAP with a
+ * light; with a light, everything rtdd_simulate_relight refuses of it, and ao->relief != light->relief; original == artistic. */
+enum rtdd_ao_mode { RTDD_AO_SHADE = 0, RTDD_AO_MAP = 1 };
+typedef struct rtdd_ambient_occlusion {
+    int   mode;        /* enum rtdd_ao_mode */
+    int   directions;  /* 4 or 8 */
+    int   radius;      /* [0, 64]: pixels marched in every direction; 0: no occlusion */
+    float relief;      /* [0, 64]: used when light == NULL; otherwise it must equal light->relief bit for bit */
+    float bias;        /* [0, 65536]: height the horizon must clear before it counts: against noise in the map */
+    float strength;    /* [0, 1] */
+} rtdd_ambient_occlusion;
+int rtdd_simulate_ambient_occlusion(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch,
+                                    const float *depth, size_t depthPitch, uint8_t *artistic, size_t artisticPitch,
+                                    int rows, int cols, const rtdd_ambient_occlusion *ao,
+                                    const rtdd_light *light /* may be NULL */);   /* both HOST, read before the call returns */
 
 /* ---- whole-estimate driver ------------------------------------------------
  * One depth estimate = the loop body of src/main.cpp:232-295, run as a single stream-ordered launch

@@ -53,13 +53,14 @@ C_ABI_SYMBOLS = [
     "rtdd_pyramid_create_batch", "rtdd_pyramid_select", "rtdd_pyramid_batch", "rtdd_estimate_depth_batch", "rtdd_pyramid_level_info", "rtdd_live_submit_ex",
     "rtdd_simulate_refocus", "rtdd_simulate_haze_ex", "rtdd_simulate_stereo", "rtdd_simulate_lens_blur",
     "rtdd_paint_strokes", "rtdd_pyramid_annotation_rebuild",
-    "rtdd_simulate_relight", "rtdd_simulate_relight_shadowed", "rtdd_simulate_parallax",
+    "rtdd_simulate_relight", "rtdd_simulate_relight_shadowed", "rtdd_simulate_parallax", "rtdd_simulate_ambient_occlusion",
 ]
 IMG_ORIGINAL, IMG_GRAY, IMG_SCRIBBLE, IMG_EDITED, IMG_DEPTH, IMG_DEPTH_U8, IMG_ARTISTIC = range(7)
 EFFECT_NONE, EFFECT_DEFOCUS, EFFECT_DESATURATION, EFFECT_HAZE = range(4)
 STEREO_VIEW, STEREO_ANAGLYPH = 0, 1           # rtdd_simulate_stereo's modes
 APERTURE_BOX, APERTURE_DISC = 0, 1            # rtdd_simulate_lens_blur's shapes
 LIGHT_DIRECTIONAL, LIGHT_POINT = 0, 1         # rtdd_light.kind
+AO_SHADE, AO_MAP = 0, 1                       # rtdd_ambient_occlusion.mode
 BRUSH_SQUARE, BRUSH_ROUND = 0, 1              # rtdd_stroke.brush
 STROKE_ERASE = -1                             # rtdd_stroke.label: remove the annotation
 # Itanium-mangled names of the reference's ten free functions
@@ -128,6 +129,18 @@ class Parallax(C.Structure):
 
     def __init__(self, shiftX=0, shiftY=0, dolly=0.0, zeroParallaxDepth=0.0, zeroX=-1, zeroY=-1):
         super().__init__(shiftX, shiftY, dolly, zeroParallaxDepth, zeroX, zeroY)
+
+
+class AmbientOcclusion(C.Structure):
+    """rtdd_ambient_occlusion: the horizon of the height field relief * (255 - depth) along `directions` (4 or 8) compass directions
+    over `radius` pixels (0: no occlusion); a horizon counts once it clears `bias`; `strength` is the share of the ambient light a fully
+    occluded pixel loses.  mode AO_SHADE darkens the original (or, under a light, relight's ambient term), AO_MAP renders the occlusion
+    itself as a gray image.  Under a light `relief` must be the light's."""
+    _fields_ = [("mode", C.c_int), ("directions", C.c_int), ("radius", C.c_int), ("relief", C.c_float), ("bias", C.c_float),
+                ("strength", C.c_float)]
+
+    def __init__(self, mode=AO_SHADE, directions=8, radius=16, relief=1.0, bias=0.0, strength=1.0):
+        super().__init__(mode, directions, radius, relief, bias, strength)
 
 
 class Profile(C.Structure):
@@ -405,6 +418,14 @@ class Context:
         o, op = _img(originalImage); d, dp = _img(depthImage); a, ap = _img(artisticImage)
         self._check(lib().rtdd_simulate_parallax(self._h, o, op, d, dp, a, ap, C.c_int(rows), C.c_int(cols),
                                                  C.byref(view) if view is not None else None))
+
+    def simulate_ambient_occlusion(self, originalImage, depthImage, artisticImage, rows, cols, ao, light=None):
+        """Ambient occlusion from the depth map as `ao` (an AmbientOcclusion, or None for the C call's null pointer) says: alone
+        (light None: the original darkened, or AO_MAP's gray map), or as the ambient term of simulate_relight under `light`."""
+        o, op = _img(originalImage); d, dp = _img(depthImage); a, ap = _img(artisticImage)
+        self._check(lib().rtdd_simulate_ambient_occlusion(self._h, o, op, d, dp, a, ap, C.c_int(rows), C.c_int(cols),
+                                                          C.byref(ao) if ao is not None else None,
+                                                          C.byref(light) if light is not None else None))
 
     # ---- whole-estimate driver (src/main.cpp:92-155, 232-295)
     def pyramid_create(self, rows, cols):

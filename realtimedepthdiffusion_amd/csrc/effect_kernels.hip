@@ -880,6 +880,7 @@ int launch_effect(rtdd_ctx *ctx, const Effect &e) {
         case Effect::kRelight: return launch_relight(ctx, e);          // relight.hip
         case Effect::kRelightShadow: return launch_relight_shadow(ctx, e);     // relight_shadow.hip
         case Effect::kParallax: return launch_parallax(ctx, e);        // parallax.hip
+        case Effect::kAmbientOcclusion: return launch_ambient_occlusion(ctx, e);   // ambient_occlusion.hip
         case RTDD_EFFECT_DESATURATION:
             return launch_blend<0>(ctx, e.original, e.originalPitch, e.gray, e.grayPitch, e.depth, e.depthPitch, e.artistic, e.artisticPitch,
                                    e.rows, e.cols);

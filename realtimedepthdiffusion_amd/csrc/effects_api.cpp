@@ -2,6 +2,7 @@
 // launch_effect (effect_kernels.hip) and, behind unconfirmed solves, to the pending-call log (heal.cpp).  Host code only.
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 
 #include "rtdd_internal.hpp"
 
@@ -221,6 +222,37 @@ int rtdd_simulate_parallax(rtdd_ctx *ctx, const uint8_t *original, size_t origin
     P.shiftX = q.shiftX; P.shiftY = q.shiftY; P.dolly = q.dolly; P.zeroX = q.zeroX; P.zeroY = q.zeroY;
     P.zeroDepth = q.zeroParallaxDepth;
     P.cx = (float)(cols - 1) * 0.5f; P.cy = (float)(rows - 1) * 0.5f;
+    return simulate(ctx, e);
+}
+
+int rtdd_simulate_ambient_occlusion(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
+                                    uint8_t *artistic, size_t artisticPitch, int rows, int cols, const rtdd_ambient_occlusion *ao,
+                                    const rtdd_light *light) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    Effect e{Effect::kAmbientOcclusion, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols};
+    // the images first, as every effect; then the occlusion; then the light, checked as rtdd_simulate_relight checks it
+    int rc = check_effect(ctx, original, depth, artistic, originalPitch, depthPitch, artisticPitch, rows, cols);
+    if (rc != RTDD_OK) return rc;
+    REQUIRE(ctx, ao, "null ao");
+    const rtdd_ambient_occlusion &q = *ao;
+    REQUIRE(ctx, q.mode == RTDD_AO_SHADE || q.mode == RTDD_AO_MAP, "mode must be RTDD_AO_SHADE or RTDD_AO_MAP");
+    REQUIRE(ctx, q.directions == 4 || q.directions == 8, "directions must be 4 or 8");
+    REQUIRE(ctx, q.radius >= 0 && q.radius <= 64, "radius outside [0, 64]");
+    for (float v : {q.relief, q.bias, q.strength}) REQUIRE(ctx, std::isfinite(v), "a non-finite value in the ambient occlusion");
+    REQUIRE(ctx, q.relief >= 0.0f && q.relief <= 64.0f, "relief outside [0, 64]");
+    REQUIRE(ctx, q.bias >= 0.0f && q.bias <= 65536.0f, "bias outside [0, 65536]");
+    REQUIRE(ctx, q.strength >= 0.0f && q.strength <= 1.0f, "strength outside [0, 1]");
+    Effect::Occlusion &A = e.occlusion;
+    A.mode = q.mode; A.directions = q.directions; A.radius = q.radius; A.relief = q.relief; A.bias = q.bias; A.strength = q.strength;
+    A.lit = light != nullptr;
+    if (light) {
+        REQUIRE(ctx, q.mode != RTDD_AO_MAP, "RTDD_AO_MAP takes no light");
+        rc = prepare_relight(ctx, e, light);
+        if (rc != RTDD_OK) return rc;
+        REQUIRE(ctx, std::memcmp(&q.relief, &light->relief, sizeof(float)) == 0, "ao->relief must equal light->relief bit for bit");
+    }
+    if (rows == 0 || cols == 0) return RTDD_OK;
+    REQUIRE(ctx, original != artistic, "ambient occlusion cannot run in place");
     return simulate(ctx, e);
 }
 

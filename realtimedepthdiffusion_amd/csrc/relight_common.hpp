@@ -1,5 +1,5 @@
-// relight_common.hpp -- the shading arithmetic that relight.hip (k_relight) and relight_shadow.hip (k_relight_shadow) share: the depth
-// clamp, the shade of one pixel, the byte of one channel.  The header's lines (include/rtdd.h rtdd_simulate_relight), operation by
+// relight_common.hpp -- the shading arithmetic that relight.hip (k_relight), relight_shadow.hip (k_relight_shadow) and
+// ambient_occlusion.hip (k_ambient_occlusion) share: the depth clamp, the shade of one pixel, the byte of one channel.  The header's lines (include/rtdd.h rtdd_simulate_relight), operation by
 // operation; both translation units are compiled with -ffp-contract=off and hold no fmaf.
 // Included inside no namespace; everything here is in namespace rtdd.
 #pragma once
@@ -33,6 +33,11 @@ __device__ __forceinline__ float relight_shade(const Light &L, float Lz, float d
 // (uchar) fminf(o * (ambient + (k_c * shade)), 255): the gain is finite and >= 0, so the truncation is defined
 __device__ __forceinline__ uint32_t relight_u8(const Light &L, int c, float shade, uint32_t o) {
     return (uint32_t)(int)fminf((float)o * (L.ambient + (L.k[c] * shade)), 255.0f);
+}
+
+// the same byte with the ambient term the caller occluded, amb = ambient * ao (rtdd_simulate_ambient_occlusion under a light)
+__device__ __forceinline__ uint32_t relight_u8_ambient(const Light &L, int c, float amb, float shade, uint32_t o) {
+    return (uint32_t)(int)fminf((float)o * (amb + (L.k[c] * shade)), 255.0f);
 }
 
 }  // namespace rtdd
