@@ -5,41 +5,24 @@ and out-of-range depths; the bounds of the parameters; the identities; the known
 padding bytes; sub-image views; FP contraction; the anchor pixel read on the device behind an estimate; the heal log; the host-side
 refusals; the harness.  No tolerance anywhere: every operation of the header is a correctly rounded IEEE one."""
 import ctypes as C
-import os
 import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
-import torch
 
 import realtimedepthdiffusion_amd as rt
 import wild_depth
 from ao_ref import MAP, SHADE, ambient, apply_ao, occluded, occlusion
-from dataset_util import load_pair
+from effect_gpu import ctx, dog_depth  # noqa: F401
+from effect_gpu import (FILL, assert_bad_images_refused, assert_padding_untouched, assert_same_image, clean_and_healed, estimate, harness_bin,
+                        harness_files, harness_pair, padded_artistic, pixel_form_behind_estimate, random_inputs, run_harness, tile_mirrored)
 from gpu_util import down, up
 from relight_ref import DIRECTIONAL, POINT, light, relight, shade
 from roi_util import FILL_INPUT, FILL_OUTPUT, LAYOUTS_F32, LAYOUTS_U8, Roi, covering, pitch_for
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "harness", "rtdd_harness")
 F = np.float32
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = rt.Context(0)
-    yield c
-    c.close()
-
-
-def _inputs(rows, cols, seed):
-    rng = np.random.default_rng(seed)
-    orig = rng.integers(0, 256, (rows, cols, 3), dtype=np.uint8)
-    depth = rng.uniform(-20, 275, (rows, cols)).astype(np.float32)
-    depth[rng.random((rows, cols)) < 0.03] = np.nan
-    return orig, depth
 
 
 def _ao(A):
@@ -47,7 +30,7 @@ def _ao(A):
 
 
 def _run(c, o, d, rows, cols, A, L=None, align=512):
-    art = up(np.full((rows, cols, 3), 0x5A, np.uint8), align)
+    art = up(np.full((rows, cols, 3), FILL, np.uint8), align)
     c.simulate_ambient_occlusion(o, d, art, rows, cols, _ao(A), rt.Light(**L) if L is not None else None)
     c.synchronize()
     return down(art)
@@ -58,10 +41,6 @@ def _relight(c, o, d, rows, cols, L):
     c.simulate_relight(o, d, art, rows, cols, rt.Light(**L))
     c.synchronize()
     return down(art)
-
-
-def _check(got, want, what):
-    assert np.array_equal(got, want), f"{what}: {int((got != want).any(-1).sum())} of {got.shape[0] * got.shape[1]} pixels differ"
 
 
 def _lights(rows, cols, relief):
@@ -76,11 +55,11 @@ def _lights(rows, cols, relief):
 def _all_forms(c, o, d, orig, depth, rows, cols, A, align, what):
     """Every output of one occlusion: the shade, the map, and the three lights -- the restatement's ao computed once."""
     ao = ambient(depth, A)
-    _check(_run(c, o, d, rows, cols, A, None, align), apply_ao(orig, ao, A), (what, A, "shade"))
+    assert_same_image(_run(c, o, d, rows, cols, A, None, align), apply_ao(orig, ao, A), (what, A, "shade"))
     M = dict(A, mode=MAP)
-    _check(_run(c, o, d, rows, cols, M, None, align), apply_ao(orig, ao, M), (what, M))
+    assert_same_image(_run(c, o, d, rows, cols, M, None, align), apply_ao(orig, ao, M), (what, M))
     for L in _lights(rows, cols, A["relief"]):
-        _check(_run(c, o, d, rows, cols, A, L, align), apply_ao(orig, ao, A, L, shade(depth, L)), (what, A, L))
+        assert_same_image(_run(c, o, d, rows, cols, A, L, align), apply_ao(orig, ao, A, L, shade(depth, L)), (what, A, L))
     return ao
 
 
@@ -90,7 +69,7 @@ def _all_forms(c, o, d, orig, depth, rows, cols, A, align, what):
                                          ((130, 200), 512), ((33, 70), 4)])
 def test_small_shapes_bit_exact(ctx, shape, align):
     rows, cols = shape
-    orig, depth = _inputs(rows, cols, rows * 1000 + cols)
+    orig, depth = random_inputs(rows, cols, rows * 1000 + cols)
     o, d = up(orig, align), up(depth, align)
     occluding = 0
     for radius in (1, 5, 64):
@@ -103,7 +82,7 @@ def test_small_shapes_bit_exact(ctx, shape, align):
 def test_every_radius_class_and_its_neighbours(ctx):
     """The launcher chooses the LDS array by the radius: both sides of every threshold, on a smooth map whose creases are occluded."""
     rows, cols = 70, 150
-    orig = _inputs(rows, cols, 5)[0]
+    orig = random_inputs(rows, cols, 5)[0]
     yy, xx = np.mgrid[0:rows, 0:cols].astype(np.float32)
     depth = (127.5 + 120 * np.sin(xx / 17.0) * np.cos(yy / 11.0)).astype(np.float32)
     o, d = up(orig, 1), up(depth, 1)
@@ -112,8 +91,8 @@ def test_every_radius_class_and_its_neighbours(ctx):
     for radius in (2, 8, 9, 16, 17, 32, 33, 63, 64):
         A = occlusion(SHADE, 8 if radius % 2 else 4, radius, 2.0, 0.125, 1.0)
         ao = ambient(depth, A)
-        _check(_run(ctx, o, d, rows, cols, A, L, 1), apply_ao(orig, ao, A, L, shade(depth, L)), A)
-        _check(_run(ctx, o, d, rows, cols, dict(A, mode=MAP), None, 1), apply_ao(orig, ao, dict(A, mode=MAP)), A)
+        assert_same_image(_run(ctx, o, d, rows, cols, A, L, 1), apply_ao(orig, ao, A, L, shade(depth, L)), A)
+        assert_same_image(_run(ctx, o, d, rows, cols, dict(A, mode=MAP), None, 1), apply_ao(orig, ao, dict(A, mode=MAP)), A)
         shares.append(float((ao < 1).mean()))
     assert 0.2 < min(shares) and max(shares) < 1.0
 
@@ -122,7 +101,7 @@ def test_every_radius_class_and_its_neighbours(ctx):
 def test_out_of_range_and_non_finite_depths(ctx, name):
     rows, cols = 70, 133
     depth = wild_depth.make(name, rows, cols)["depth"]
-    orig = _inputs(rows, cols, 21)[0]
+    orig = random_inputs(rows, cols, 21)[0]
     o, d = up(orig), up(depth)
     for A in (occlusion(SHADE, 8, 5, 2.0, 0.0, 1.0), occlusion(SHADE, 4, 64, 0.25, 1.0, 0.5)):
         _all_forms(ctx, o, d, orig, depth, rows, cols, A, 512, name)
@@ -131,7 +110,7 @@ def test_out_of_range_and_non_finite_depths(ctx, name):
 def test_extreme_parameters(ctx):
     """The bounds of the ranges: relief 64, bias 0 and 65536, strength 1, radius 64; a tiny relief whose rises are denormal."""
     rows, cols = 20, 140
-    orig, depth = _inputs(rows, cols, 23)
+    orig, depth = random_inputs(rows, cols, 23)
     o, d = up(orig), up(depth)
     for A in (occlusion(SHADE, 8, 64, 64.0, 0.0, 1.0), occlusion(SHADE, 8, 64, 64.0, 65536.0, 1.0), occlusion(SHADE, 4, 64, 64.0, 16000.0, 1.0),
               occlusion(SHADE, 8, 7, 1e-40, 0.0, 1.0), occlusion(SHADE, 4, 1, 64.0, 1e-30, 1.0)):
@@ -143,18 +122,18 @@ def test_extreme_parameters(ctx):
 
 def test_identities_on_the_device(ctx):
     rows, cols = 33, 300
-    orig, depth = _inputs(rows, cols, 22)
+    orig, depth = random_inputs(rows, cols, 22)
     const = np.full((rows, cols), 93.5, np.float32)
     o, d, dc = up(orig), up(depth), up(const)
     cases = [(d, occlusion(SHADE, 8, 0, 1.5, 0.0, 1.0)), (d, occlusion(SHADE, 4, 16, 1.5, 0.0, 0.0)), (d, occlusion(SHADE, 8, 64, 0.0, 0.0, 1.0)),
              (dc, occlusion(SHADE, 8, 16, 1.5, 0.0, 1.0)), (dc, occlusion(SHADE, 4, 64, 64.0, 0.0, 1.0))]
     for dev, A in cases:
-        _check(_run(ctx, o, dev, rows, cols, A), orig, ("the original", A))
+        assert_same_image(_run(ctx, o, dev, rows, cols, A), orig, ("the original", A))
         assert (_run(ctx, o, dev, rows, cols, dict(A, mode=MAP)) == 255).all(), A
         for L in _lights(rows, cols, A["relief"]):
             want = _relight(ctx, o, dev, rows, cols, L)                 # rtdd_simulate_relight's own output, on the same context
-            _check(_run(ctx, o, dev, rows, cols, A, L), want, ("relight", A, L))
-    _check(_relight(ctx, o, d, rows, cols, _lights(rows, cols, 1.5)[0]), relight(orig, depth, _lights(rows, cols, 1.5)[0]), "relight")
+            assert_same_image(_run(ctx, o, dev, rows, cols, A, L), want, ("relight", A, L))
+    assert_same_image(_relight(ctx, o, d, rows, cols, _lights(rows, cols, 1.5)[0]), relight(orig, depth, _lights(rows, cols, 1.5)[0]), "relight")
     A = occlusion(SHADE, 8, 16, 1.5, 0.0, 1.0)                          # ... and a rough map under the same settings is occluded
     assert not np.array_equal(_run(ctx, o, d, rows, cols, A), orig)
     L = _lights(rows, cols, 1.5)[0]
@@ -178,30 +157,7 @@ def test_known_answer_on_the_device(ctx, radius):
         assert (out[2, x0 - 1] == int(F(200) * ao)).all() and (out[:, x0:] == 200).all() and (out[:, :x0 - radius] == 200).all()
         m = _run(ctx, o, d, rows, cols, dict(A, mode=MAP))
         assert (m[2, x0 - 1] == int(F(255) * ao)).all() and (m[:, x0:] == 255).all()
-        _check(out, occluded(orig, depth, A), A)
-
-
-def _estimate(c, bgr, ann):
-    rows, cols = bgr.shape[:2]
-    c.pyramid_create(rows, cols)
-    c.pyramid_set_image(up(bgr)); c.pyramid_set_annotation(up(ann))
-    c.estimate_depth(1000)
-    return c.pyramid_image(rt.IMG_DEPTH, 0)
-
-
-def _tile(a, rows, cols):
-    a2 = np.concatenate([a, a[:, ::-1]], 1); a4 = np.concatenate([a2, a2[::-1]], 0)
-    return np.ascontiguousarray(np.tile(a4, (-(-rows // a4.shape[0]), -(-cols // a4.shape[1])))[:rows, :cols])
-
-
-@pytest.fixture(scope="module")
-def dog_depth():
-    bgr, ann, _ = load_pair("Dog")
-    with rt.Context(0) as c:
-        c.GPULoadWeights(0.4)
-        _estimate(c, bgr, ann)
-        c.synchronize()
-        return c.pyramid_download(rt.IMG_DEPTH, 0)
+        assert_same_image(out, occluded(orig, depth, A), A)
 
 
 def _restate_rows(depth, A, y0, y1, workers=16):
@@ -216,7 +172,7 @@ def _restate_rows(depth, A, y0, y1, workers=16):
 def test_full_size(ctx, dog_depth, rows, cols, band):
     rng = np.random.default_rng(rows)
     orig = rng.integers(0, 256, (rows, cols, 3), dtype=np.uint8)
-    depth = _tile(dog_depth, rows, cols)
+    depth = tile_mirrored(dog_depth, rows, cols)
     o, d = up(orig), up(depth)
     L = light(DIRECTIONAL, -1, -1, 1, relief=2, ambient=0.5, diffuse=1.0)
     y0, y1 = band
@@ -224,32 +180,29 @@ def test_full_size(ctx, dog_depth, rows, cols, band):
     for radius in (16, 64):
         A = occlusion(SHADE, 8, radius, 2.0, 0.5, 1.0)
         pitch = cols * 3 + 512
-        base = torch.full((rows, pitch), 0x5A, dtype=torch.uint8, device="cuda:0")
-        art = base[:, :cols * 3].unflatten(1, (cols, 3))
+        base, art = padded_artistic(rows, cols, pitch)
         ctx.simulate_ambient_occlusion(o, d, art, rows, cols, _ao(A), rt.Light(**L))
         ctx.synchronize()
-        assert bool((base[:, cols * 3:] == 0x5A).all()), "padding bytes written"
+        assert_padding_untouched(base, cols)
         ao = _restate_rows(depth, A, y0, y1)
         share = float((ao < 1).mean())
         print(f"{rows} x {cols} rows {y0}-{y1} radius {radius}: {share:.3f} of the pixels occluded, mean ao {float(ao.mean()):.4f}")
         assert 0.0 < share < 1.0
-        _check(down(art)[y0:y1], apply_ao(orig[y0:y1], ao, A, L, s), (rows, radius))
+        assert_same_image(down(art)[y0:y1], apply_ao(orig[y0:y1], ao, A, L, s), (rows, radius))
 
 
 @pytest.mark.parametrize("cols", [37, 1030])
 def test_padding_bytes_stay_untouched(ctx, cols):
     rows, pitch = 19, cols * 3 + 13
-    orig, depth = _inputs(rows, cols, 8)
+    orig, depth = random_inputs(rows, cols, 8)
     o, d = up(orig), up(depth)
     for A, L in ((occlusion(SHADE, 8, 5, 1.0, 0.0, 1.0), None), (occlusion(MAP, 4, 64, 1.0, 0.0, 1.0), None),
                  (occlusion(SHADE, 8, 20, 1.0, 0.5, 0.5), _lights(rows, cols, 1.0)[0]), (occlusion(SHADE, 4, 9, 1.0, 0.5, 0.5), _lights(rows, cols, 1.0)[2])):
-        base = torch.full((rows, pitch), 0x5A, dtype=torch.uint8, device="cuda:0")
-        art = base[:, :cols * 3].unflatten(1, (cols, 3))
+        base, art = padded_artistic(rows, cols, pitch)
         ctx.simulate_ambient_occlusion(o, d, art, rows, cols, _ao(A), rt.Light(**L) if L else None)
         ctx.synchronize()
-        b = base.cpu().numpy()
-        assert (b[:, cols * 3:] == 0x5A).all()
-        _check(b[:, :cols * 3].reshape(rows, cols, 3), occluded(orig, depth, A, L), (A, L))
+        assert_padding_untouched(base, cols)
+        assert_same_image(down(art), occluded(orig, depth, A, L), (A, L))
 
 
 @pytest.mark.parametrize("shape", [(9, 67), (13, 131), (1, 7), (7, 1)], ids=lambda s: f"{s[0]}x{s[1]}")
@@ -257,7 +210,7 @@ def test_sub_image_views(ctx, shape):
     """Input and output are views into larger allocations (tests/roi_util.py), every layout of each image and every pair of layouts of
     any two: the pixels are the restatement's, every byte around the output still holds its fill, and the inputs' parents are unchanged."""
     rows, cols = shape
-    orig, depth = _inputs(rows, cols, 31 + rows)
+    orig, depth = random_inputs(rows, cols, 31 + rows)
     lay = [[(lead, pitch_for(cols * 3, lead, res)) for lead, res in LAYOUTS_U8], [(lead, pitch_for(cols * 4, lead, res)) for lead, res in LAYOUTS_F32],
            [(lead, pitch_for(cols * 3, lead, res)) for lead, res in LAYOUTS_U8]]
     ins_o = [Roi(orig, lead, pitch, FILL_INPUT, what=f"original (lead {lead}, pitch {pitch})") for lead, pitch in lay[0]]
@@ -272,13 +225,13 @@ def test_sub_image_views(ctx, shape):
         out = Roi(np.zeros_like(orig), *lay[2][ia], FILL_OUTPUT, seed=k, what=f"artistic (lead {lay[2][ia][0]}, pitch {lay[2][ia][1]})")
         ctx.simulate_ambient_occlusion(ins_o[io].img, ins_d[idp].img, out.img, rows, cols, _ao(A), rt.Light(**Lf) if Lf else None)
         ctx.synchronize()
-        _check(out.result(), wants[k % 3], (shape, lay[0][io], lay[1][idp], lay[2][ia], A))
+        assert_same_image(out.result(), wants[k % 3], (shape, lay[0][io], lay[1][idp], lay[2][ia], A))
         ins_o[io].assert_unchanged(); ins_d[idp].assert_unchanged()
 
 
 def test_fp_contraction_does_not_change_the_bytes(ctx):
     rows, cols = 40, 500
-    orig, depth = _inputs(rows, cols, 9)
+    orig, depth = random_inputs(rows, cols, 9)
     o, d = up(orig), up(depth)
     for A, L in ((occlusion(SHADE, 8, 12, 3.0, 0.5, 1.0), None), (occlusion(MAP, 4, 40, 3.0, 0.0, 0.75), None),
                  (occlusion(SHADE, 8, 64, 3.0, 0.5, 1.0), _lights(rows, cols, 3.0)[0]), (occlusion(SHADE, 4, 7, 3.0, 0.5, 1.0), _lights(rows, cols, 3.0)[1])):
@@ -290,79 +243,49 @@ def test_fp_contraction_does_not_change_the_bytes(ctx):
         finally:
             ctx.set_option(rt.OPT_FP_CONTRACT, 1)
         assert np.array_equal(outs[0], outs[1])
-        _check(outs[0], occluded(orig, depth, A, L), "contraction")
+        assert_same_image(outs[0], occluded(orig, depth, A, L), "contraction")
 
 
 def test_anchor_pixel_is_read_behind_an_unsynchronised_estimate():
-    bgr, ann, _ = load_pair("Dog")
-    rows, cols = bgr.shape[:2]
-    with rt.Context(0) as c:
-        c.GPULoadWeights(0.4)
-        _estimate(c, bgr, ann)
-        first = c.pyramid_download(rt.IMG_DEPTH, 0)
-        ys, xs = np.nonzero((first > 60) & (first < 200))
-        y, x = int(ys[len(ys) // 2]), int(xs[len(xs) // 2])
-        d = _estimate(c, bgr, ann)                                          # a new image: the same estimate again, from a cold start
-        o = up(bgr)
-        a1, a2 = up(np.zeros_like(bgr)), up(np.zeros_like(bgr))
-        L = light(POINT, x, y, 60, anchorX=x, anchorY=y, radius=150, relief=2, ambient=0.6, diffuse=2.0)
-        A = occlusion(SHADE, 8, 24, 2.0, 0.5, 1.0)
-        c.simulate_ambient_occlusion(o, d, a1, rows, cols, _ao(A), rt.Light(**L))     # no synchronisation since the estimate was queued
-        c.synchronize()
-        depth = c.pyramid_download(rt.IMG_DEPTH, 0)
-        fv = float(depth[y, x])
-        assert 60.0 < fv < 200.0
-        L2 = dict(L, anchorX=-1, anchorY=-1, anchorDepth=fv)
-        c.simulate_ambient_occlusion(o, d, a2, rows, cols, _ao(A), rt.Light(**L2))
-        c.synchronize()
-        assert np.array_equal(down(a1), down(a2))
-        _check(down(a1), occluded(bgr, depth, A, L), "pixel form")
-        assert not np.array_equal(down(a1), relight(bgr, depth, L))
+    A = occlusion(SHADE, 8, 24, 2.0, 0.5, 1.0)
+
+    def over(x, y):
+        return light(POINT, x, y, 60, anchorX=x, anchorY=y, radius=150, relief=2, ambient=0.6, diffuse=2.0)
+
+    def call(c, o, d, art, x, y, value=None):
+        rows, cols = o.shape[:2]
+        L = over(x, y) if value is None else dict(over(x, y), anchorX=-1, anchorY=-1, anchorDepth=value)
+        c.simulate_ambient_occlusion(o, d, art, rows, cols, _ao(A), rt.Light(**L))
+
+    bgr, depth, x, y, _, image = pixel_form_behind_estimate(call)
+    assert_same_image(image, occluded(bgr, depth, A, over(x, y)), "pixel form")
+    assert not np.array_equal(image, relight(bgr, depth, over(x, y)))
 
 
 def test_ambient_occlusion_is_replayed_after_a_healed_solve():
-    from realtimedepthdiffusion_amd.synth import make_problem
     rows, cols = 270, 480
-    p = make_problem(rows, cols, seed=6)
-    orig = _inputs(rows, cols, 2)[0]
+    orig = random_inputs(rows, cols, 2)[0]
     L1 = light(POINT, 100, 200, 40, anchorX=100, anchorY=200, radius=120, relief=2, ambient=0.6, diffuse=2.0, color=(255, 220, 180))
     A1, A2, A3 = occlusion(SHADE, 8, 20, 2.0, 0.5, 0.875), occlusion(SHADE, 4, 64, 3.0, 0.0, 1.0), occlusion(MAP, 8, 7, 1.0, 0.25, 1.0)
 
-    def run(force):
-        c = rt.Context(0)
-        try:
-            c.GPUAllocateDeviceMemory(rows, cols, 1); c.GPULoadWeights(0.4)
-            d, m, g = up(p["depth"]), up(p["mask"]), up(p["gray"])
-            o = up(orig)
-            a1, a2, a3 = up(np.zeros_like(orig)), up(np.zeros_like(orig)), up(np.zeros_like(orig))
-            if force:
-                c.set_option(rt.OPT_DEBUG_FORCE_STATUS, 1)
-            c.GPUMatrixFreeSolver(d, m, g, rows, cols, 0.4, 24, 0.0, 0)
-            light1, ao1 = rt.Light(**L1), _ao(A1)
-            c.simulate_ambient_occlusion(o, d, a1, rows, cols, ao1, light1)
-            light1.kind, light1.relief, light1.x = 7, -1.0, float("nan")   # the call has read both: the record holds them by value
-            ao1.radius, ao1.directions, ao1.bias, ao1.strength = -5, 3, float("nan"), 9.0
-            c.simulate_ambient_occlusion(o, d, a2, rows, cols, _ao(A2), None)
-            c.simulate_ambient_occlusion(o, d, a3, rows, cols, _ao(A3), None)
-            c.synchronize()
-            assert c.get_option(rt.OPT_TIMEOUT_HEALS) == (1 if force else 0)
-            return down(d), down(a1), down(a2), down(a3)
-        finally:
-            c.close()
+    def queue(c, o, d, arts):
+        light1, ao1 = rt.Light(**L1), _ao(A1)
+        c.simulate_ambient_occlusion(o, d, arts[0], rows, cols, ao1, light1)
+        light1.kind, light1.relief, light1.x = 7, -1.0, float("nan")   # the call has read both: the record holds them by value
+        ao1.radius, ao1.directions, ao1.bias, ao1.strength = -5, 3, float("nan"), 9.0
+        c.simulate_ambient_occlusion(o, d, arts[1], rows, cols, _ao(A2), None)
+        c.simulate_ambient_occlusion(o, d, arts[2], rows, cols, _ao(A3), None)
 
-    clean, healed = run(False), run(True)
-    assert not np.array_equal(clean[0], p["depth"])
-    for w, g in zip(clean, healed):
-        assert np.array_equal(g, w)
-    _check(healed[1], occluded(orig, clean[0], A1, L1), "healed, under a point light")
-    _check(healed[2], occluded(orig, clean[0], A2), "healed, no light")
-    _check(healed[3], occluded(orig, clean[0], A3), "healed, the map")
-    assert not np.array_equal(healed[1], relight(orig, clean[0], L1)) and not np.array_equal(healed[2], orig)
+    solved, healed = clean_and_healed(queue, 3, orig)
+    assert_same_image(healed[0], occluded(orig, solved, A1, L1), "healed, under a point light")
+    assert_same_image(healed[1], occluded(orig, solved, A2), "healed, no light")
+    assert_same_image(healed[2], occluded(orig, solved, A3), "healed, the map")
+    assert not np.array_equal(healed[0], relight(orig, solved, L1)) and not np.array_equal(healed[1], orig)
 
 
 def test_invalid_arguments_are_refused_on_the_host():
     rows, cols = 40, 60
-    orig, depth = _inputs(rows, cols, 1)
+    orig, depth = random_inputs(rows, cols, 1)
     sentinel = np.full_like(orig, 77)
     nan, inf = float("nan"), float("inf")
     AO, Li = rt.AmbientOcclusion, rt.Light
@@ -394,21 +317,9 @@ def test_invalid_arguments_are_refused_on_the_host():
         refused(AO(mode=rt.AO_MAP), None, src=o, dst=o)
         refused(AO(radius=100), None, rows=0)                                   # the parameters are checked before the empty return
         c.simulate_ambient_occlusion(o, d, o, 0, cols, AO(), None)              # ... and the in-place rule after it
-        lib = rt.lib()
-        op, dp, ap = C.c_size_t(o.stride(0)), C.c_size_t(d.stride(0) * 4), C.c_size_t(art.stride(0))
-        po, pd, pa = C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()), C.c_void_p(art.data_ptr())
-        f = lib.rtdd_simulate_ambient_occlusion
+        f = rt.lib().rtdd_simulate_ambient_occlusion
         for ao, li in ((C.byref(AO()), None), (C.byref(AO()), C.byref(Li())), (C.byref(AO(mode=rt.AO_MAP)), None)):
-            assert f(c._h, None, op, pd, dp, pa, ap, rows, cols, ao, li) == 1   # (the map does not read `original`, and still wants one)
-            assert f(c._h, po, op, None, dp, pa, ap, rows, cols, ao, li) == 1
-            assert f(c._h, po, op, pd, dp, None, ap, rows, cols, ao, li) == 1
-            assert f(c._h, po, op, pd, dp, pa, C.c_size_t(cols * 3 - 1), rows, cols, ao, li) == 1
-            assert f(c._h, po, C.c_size_t(cols * 3 - 1), pd, dp, pa, ap, rows, cols, ao, li) == 1
-            assert f(c._h, po, op, pd, C.c_size_t(cols * 4 - 4), pa, ap, rows, cols, ao, li) == 1
-            assert f(c._h, po, op, pd, C.c_size_t(d.stride(0) * 4 + 2), pa, ap, rows, cols, ao, li) == 1      # an f32 pitch that is no multiple of 4
-            assert f(c._h, po, op, pd, dp, pa, ap, 40000, 40000, ao, li) == 1
-            assert f(c._h, po, op, pd, dp, pa, ap, -1, cols, ao, li) == 1
-            assert f(None, po, op, pd, dp, pa, ap, rows, cols, ao, li) == 1
+            assert_bad_images_refused(c, f, o, d, art, rows, cols, (ao, li))    # (the map does not read `original`, and still wants one)
         c.synchronize()
         assert np.array_equal(down(art), sentinel)                             # nothing was launched
         for kw in (dict(radius=64, relief=64.0, bias=65536.0, strength=1.0), dict(radius=0, relief=0.0, bias=0.0, strength=0.0, directions=4)):
@@ -417,22 +328,11 @@ def test_invalid_arguments_are_refused_on_the_host():
         assert not np.array_equal(down(art), sentinel)
 
 
-def _harness_files(tmp_path):
-    from PIL import Image
-    if not os.path.exists(BIN):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "harness")])
-    bgr, ann, _ = load_pair("WomanParasol")
-    Image.fromarray(np.ascontiguousarray(bgr[..., ::-1]), "RGB").save(tmp_path / "img.png")
-    Image.fromarray(ann, "L").save(tmp_path / "ann.png")
-    return bgr, ann
-
-
 def test_harness_writes_the_restatements_image(tmp_path):
-    from PIL import Image
-    bgr, ann = _harness_files(tmp_path)
+    bgr, ann = harness_pair(tmp_path, "png")
     with rt.Context(0) as c:                                                   # the harness's own depth map: the same estimate
         c.GPULoadWeights(0.4)
-        _estimate(c, bgr, ann)
+        estimate(c, bgr, ann)
         c.synchronize()
         depth = c.pyramid_download(rt.IMG_DEPTH, 0)
     x, y = 300, 200
@@ -447,21 +347,15 @@ def test_harness_writes_the_restatements_image(tmp_path):
               occlusion(SHADE, 4, 12, 2.0, 1.0, 0.5), point),
              (["--effect", "relight", "--ao", "0"], occlusion(SHADE, 8, 0, 2.0, 0.0, 1.0), directional)]
     for args, A, L in cases:
-        out = subprocess.check_output([BIN, "-i", str(tmp_path / "img.png"), "-a", str(tmp_path / "ann.png"), "-o", str(tmp_path) + "/", "--png"] + args,
-                                      text=True)
-        assert "Saving images" in out
-        got = np.array(Image.open(tmp_path / "ArtisticEffect.png"))[..., ::-1]
-        _check(got, occluded(bgr, depth, A, L), args)
+        got = run_harness(tmp_path, "png", args)[1]
+        assert_same_image(got, occluded(bgr, depth, A, L), args)
         plain = relight(bgr, depth, L) if L is not None else bgr
         assert np.array_equal(got, plain) == (A["radius"] == 0)                 # the occlusion is visible, and --ao 0 is relight
-    r = subprocess.run([BIN, "-i", str(tmp_path / "img.png"), "-a", str(tmp_path / "ann.png"), "-o", str(tmp_path) + "/", "--effect", "ao",
-                        "--ao-radius", "65"], capture_output=True, text=True)
+    r = subprocess.run([harness_bin()] + harness_files(tmp_path, "png") + ["--effect", "ao", "--ao-radius", "65"], capture_output=True, text=True)
     assert r.returncode != 0                                                   # refused by the library
 
 
 def test_harness_refuses_the_misuses():
-    if not os.path.exists(BIN):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "harness")])
     for args, said in ((["--effect", "relight", "--ao", "16", "--shadows", "64"], "--ao and --shadows cannot be combined"),
                        (["--effect", "relight", "--ao-bias", "0.5"], "need --ao R or --effect ao"),
                        (["--effect", "defocus", "--ao-strength", "0.5"], "need --ao R or --effect ao"),
@@ -470,8 +364,8 @@ def test_harness_refuses_the_misuses():
                        (["--effect", "haze", "--ao-map"], "need --effect ao"),
                        (["--effect", "ao", "--ao", "16"], "--ao needs --effect relight"),
                        (["--ao", "16"], "--ao needs --effect relight")):
-        r = subprocess.run([BIN, "-i", "unused.ppm"] + args, capture_output=True, text=True)
+        r = subprocess.run([harness_bin(), "-i", "unused.ppm"] + args, capture_output=True, text=True)
         assert r.returncode == 1 and said in r.stdout, (args, r.returncode, r.stdout)
     for args in (["--effect", "ao"], ["--effect", "relight", "--ao", "16"]):
-        r = subprocess.run([BIN, "-i", "unused.ppm", "--live", "3"] + args, capture_output=True, text=True)
+        r = subprocess.run([harness_bin(), "-i", "unused.ppm", "--live", "3"] + args, capture_output=True, text=True)
         assert r.returncode != 0 and "not supported with --live" in r.stdout, (args, r.stdout)

@@ -2,8 +2,8 @@
 tests/lens_blur_ref.py on both paths (per-tile row prefixes in LDS, a global row-prefix table), at every size up to 8K; the square aperture
 against rtdd_simulate_refocus; out-of-range depths; the table buffer shared with the defocus; the focus pixel read on the device behind
 an estimate; the heal log; the host-side refusals; the dataset; the harness."""
+import ctypes as C
 import functools
-import os
 import subprocess
 
 import numpy as np
@@ -11,22 +11,16 @@ import pytest
 
 import realtimedepthdiffusion_amd as rt
 from dataset_util import PAIRS, load_pair
+from effect_gpu import ctx  # noqa: F401
+from effect_gpu import (assert_bad_images_refused, assert_same_image, clean_and_healed, estimate, harness_bin, harness_pair,
+                        pixel_form_behind_estimate, run_harness)
 from effects_ref import defocus_by_summed_area_table, effect_inputs
 from gpu_util import down, up
 from lens_blur_ref import lens_blur_by_row_prefixes, lens_blur_literal
 from refocus_ref import kernel_size, largest_aperture
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "harness", "rtdd_harness")
 FOCI = [0.0, 37.5, 128.0, 255.0]
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = rt.Context(0)
-    yield c
-    c.close()
 
 
 def _blur(c, o, d, rows, cols, aperture=0.025, f=0.0, at=None, path=0, shape=rt.APERTURE_DISC):
@@ -66,10 +60,6 @@ def _want(rows, cols, seed, f, aperture):
     return lens_blur_by_row_prefixes(orig, depth, f, aperture)
 
 
-def _differ(got, want):
-    return f"{int((got != want).any(-1).sum())} of {want.shape[0] * want.shape[1]} pixels differ"
-
-
 SMALL = [((6, 8), 512), ((23, 37), 1), ((67, 121), 1), ((131, 259), 4), ((270, 480), 512)]
 
 
@@ -87,7 +77,7 @@ def test_disc_small_shapes_bit_exact(ctx, shape, align, path):
             # (K = 255 never fits the tile region: both settings take the table there)
             assert ctx.get_option(rt.OPT_DEFOCUS_LAST_PATH) == (2 if path == 2 and kernel_size(rows, cols, aperture) // 2 <= 28 else 1)
             want = lens_blur_by_row_prefixes(orig, depth, fv, aperture)
-            assert np.array_equal(got, want), (aperture, f, _differ(got, want))
+            assert_same_image(got, want, (aperture, f))
             if rows <= 67 and (aperture == 0.025 or f == 37.5):
                 assert np.array_equal(got, lens_blur_literal(orig, depth, fv, aperture)), (aperture, f, "literal")
 
@@ -116,17 +106,17 @@ def test_disc_1080p_every_pixel(ctx, path):
     got = _blur(ctx, o, d, rows, cols, f=128.0, path=path)
     assert ctx.get_option(rt.OPT_DEFOCUS_LAST_PATH) == (2 if path == 0 else 1)
     want = _want(rows, cols, 9, 128.0, 0.025)
-    assert np.array_equal(got, want), _differ(got, want)
+    assert_same_image(got, want, (path, "f = 128"))
     at = (1500, 900)
     got = _blur(ctx, o, d, rows, cols, at=at, path=path)
     assert ctx.get_option(rt.OPT_DEFOCUS_LAST_PATH) == (2 if path == 0 else 1)
     want = _want(rows, cols, 9, float(depth[at[1], at[0]]), 0.025)
-    assert np.array_equal(got, want), _differ(got, want)
+    assert_same_image(got, want, (path, "pixel form"))
     a = largest_aperture(rows, cols)
     got = _blur(ctx, o, d, rows, cols, a, 37.5, path=path)
     assert ctx.get_option(rt.OPT_DEFOCUS_LAST_PATH) == 1
     want = _want(rows, cols, 9, 37.5, a)
-    assert np.array_equal(got, want), _differ(got, want)
+    assert_same_image(got, want, (path, "largest aperture"))
 
 
 def test_box_is_refocus_at_1080p(ctx):
@@ -150,11 +140,11 @@ def test_disc_4k_every_pixel(ctx):
     got = _blur(ctx, o, up(depth), rows, cols, f=37.5)
     assert ctx.get_option(rt.OPT_DEFOCUS_LAST_PATH) == 1
     want = _want(rows, cols, 21, 37.5, 0.025)
-    assert np.array_equal(got, want), _differ(got, want)
+    assert_same_image(got, want, "4K")
     smooth = _smooth(rows, cols)
     got = _blur(ctx, o, up(smooth), rows, cols, f=128.0)
     want = lens_blur_by_row_prefixes(orig, smooth, 128.0)
-    assert np.array_equal(got, want), _differ(got, want)
+    assert_same_image(got, want, "4K, smooth map")
 
 
 # 512 full-width rows of the 8K image: the first and the last 64, 128 across the middle, and four bands in between
@@ -169,7 +159,7 @@ def test_disc_8k_bands(ctx):
     assert ctx.get_option(rt.OPT_DEFOCUS_LAST_PATH) == 1
     for band in BANDS_8K:
         want = lens_blur_by_row_prefixes(orig, depth, 128.0, band=band)
-        assert np.array_equal(got[band[0]:band[1]], want), (band, _differ(got[band[0]:band[1]], want))
+        assert_same_image(got[band[0]:band[1]], want, band)
 
 
 def test_out_of_range_depths_are_clamped_and_nothing_sticks():
@@ -185,7 +175,7 @@ def test_out_of_range_depths_are_clamped_and_nothing_sticks():
         for path, last in ((0, 2), (1, 1)):
             got = _blur(c, o, w, rows, cols, f=20.0, path=path)            # (returns RTDD_OK: anything else raises)
             assert c.get_option(rt.OPT_DEFOCUS_LAST_PATH) == last
-            assert np.array_equal(got, want), (path, _differ(got, want))
+            assert_same_image(got, want, path)
         art = up(np.zeros_like(orig))
         c.GPUSimulateDefocus(o, up(np.clip(depth, 0, 255)), art, rows, cols)
         c.synchronize()
@@ -210,75 +200,36 @@ def test_defocus_and_lens_blur_share_the_table_buffer():
         assert np.array_equal(down(a1), want_defocus)
         assert np.array_equal(down(a3), want_defocus)
         want = _want(rows, cols, 21, 37.5, 0.025)
-        assert np.array_equal(down(a2), want), _differ(down(a2), want)
-
-
-def _estimate(c, bgr, ann):
-    rows, cols = bgr.shape[:2]
-    c.pyramid_create(rows, cols)
-    c.pyramid_set_image(up(bgr)); c.pyramid_set_annotation(up(ann))
-    c.estimate_depth(1000)
-    return c.pyramid_image(rt.IMG_DEPTH, 0)
+        assert_same_image(down(a2), want, "between the two defocus calls")
 
 
 def test_pixel_form_reads_the_map_behind_an_unsynchronised_estimate():
-    bgr, ann, _ = load_pair("Dog")
-    rows, cols = bgr.shape[:2]
-    with rt.Context(0) as c:
-        c.GPULoadWeights(0.4)
-        _estimate(c, bgr, ann)
-        first = c.pyramid_download(rt.IMG_DEPTH, 0)
-        ys, xs = np.nonzero((first > 60) & (first < 200))                 # a pixel in the middle of the depth range
-        y, x = int(ys[len(ys) // 2]), int(xs[len(xs) // 2])
-        d = _estimate(c, bgr, ann)                                          # a new image: the same estimate again, from a cold start
-        o = up(bgr)
-        a1, a2 = up(np.zeros_like(bgr)), up(np.zeros_like(bgr))
-        c.simulate_lens_blur(o, d, a1, rows, cols, 0.025, 0.0, x, y)        # no synchronisation since the estimate was queued
-        c.synchronize()
-        fv = float(c.pyramid_download(rt.IMG_DEPTH, 0)[y, x])
-        assert 60.0 < fv < 200.0
-        c.simulate_lens_blur(o, d, a2, rows, cols, 0.025, fv, -1, -1)
-        c.synchronize()
-        assert np.array_equal(down(a1), down(a2))
-        assert not np.array_equal(down(a1), bgr)
+    def call(c, o, d, art, x, y, value=None):
+        rows, cols = o.shape[:2]
+        if value is None:
+            c.simulate_lens_blur(o, d, art, rows, cols, 0.025, 0.0, x, y)
+        else:
+            c.simulate_lens_blur(o, d, art, rows, cols, 0.025, value, -1, -1)
+
+    bgr, _, _, _, _, image = pixel_form_behind_estimate(call)
+    assert not np.array_equal(image, bgr)
 
 
 def test_lens_blur_is_replayed_after_a_healed_solve():
     """A solve with a (simulated) time-out status and two lens blurs (pixel form: tile kernel and global table) queued behind it: the
     synchronisation heals the solve and renders both again from the healed depth -- the images of a clean run."""
-    from realtimedepthdiffusion_amd.synth import make_problem
     rows, cols = 270, 480
-    p = make_problem(rows, cols, seed=6)
     orig = effect_inputs(rows, cols, 2)[0]
 
-    def run(force):
-        c = rt.Context(0)
-        try:
-            c.GPUAllocateDeviceMemory(rows, cols, 1); c.GPULoadWeights(0.4)
-            d, m, g = up(p["depth"]), up(p["mask"]), up(p["gray"])
-            o = up(orig)
-            a1, a2 = up(np.zeros_like(orig)), up(np.zeros_like(orig))
-            if force:
-                c.set_option(rt.OPT_DEBUG_FORCE_STATUS, 1)
-            c.GPUMatrixFreeSolver(d, m, g, rows, cols, 0.4, 24, 0.0, 0)
-            c.simulate_lens_blur(o, d, a1, rows, cols, 0.025, 0.0, 100, 200)
-            c.simulate_lens_blur(o, d, a2, rows, cols, 0.2, 0.0, 100, 200)
-            c.synchronize()
-            assert c.get_option(rt.OPT_TIMEOUT_HEALS) == (1 if force else 0)
-            solved = down(d)
-            assert np.array_equal(down(a1), lens_blur_by_row_prefixes(orig, solved, float(solved[200, 100])))
-            return solved, down(a1), down(a2)
-        finally:
-            c.close()
+    def queue(c, o, d, arts):
+        c.simulate_lens_blur(o, d, arts[0], rows, cols, 0.025, 0.0, 100, 200)
+        c.simulate_lens_blur(o, d, arts[1], rows, cols, 0.2, 0.0, 100, 200)
 
-    clean, healed = run(False), run(True)
-    assert not np.array_equal(clean[0], p["depth"])
-    for w, g in zip(clean, healed):
-        assert np.array_equal(g, w)
+    solved, healed = clean_and_healed(queue, 2, orig)
+    assert np.array_equal(healed[0], lens_blur_by_row_prefixes(orig, solved, float(solved[200, 100])))
 
 
 def test_invalid_arguments_are_refused_on_the_host():
-    import ctypes as C
     rows, cols = 40, 60
     orig, depth = effect_inputs(rows, cols, 1)
     sentinel = np.full_like(orig, 77)
@@ -300,19 +251,8 @@ def test_invalid_arguments_are_refused_on_the_host():
             with pytest.raises(rt.RtddError) as e:
                 c.simulate_lens_blur(o, d, o, rows, cols, 0.025, 0.0, -1, -1, shape)      # in place
             assert e.value.status == 1
-        L = rt.lib()
-        op, dp, ap = C.c_size_t(o.stride(0)), C.c_size_t(d.stride(0) * 4), C.c_size_t(art.stride(0))
-        po, pd, pa = C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()), C.c_void_p(art.data_ptr())
-        f0, a0 = C.c_float(0.0), C.c_double(0.025)
         for shape in (rt.APERTURE_DISC, rt.APERTURE_BOX):
-            assert L.rtdd_simulate_lens_blur(c._h, None, op, pd, dp, pa, ap, rows, cols, a0, f0, -1, -1, shape) == 1
-            assert L.rtdd_simulate_lens_blur(c._h, po, op, None, dp, pa, ap, rows, cols, a0, f0, -1, -1, shape) == 1
-            assert L.rtdd_simulate_lens_blur(c._h, po, op, pd, dp, None, ap, rows, cols, a0, f0, -1, -1, shape) == 1
-            assert L.rtdd_simulate_lens_blur(c._h, po, op, pd, dp, pa, C.c_size_t(cols * 3 - 1), rows, cols, a0, f0, -1, -1, shape) == 1
-            assert L.rtdd_simulate_lens_blur(c._h, po, C.c_size_t(cols * 3 - 1), pd, dp, pa, ap, rows, cols, a0, f0, -1, -1, shape) == 1
-            assert L.rtdd_simulate_lens_blur(c._h, po, op, pd, C.c_size_t(cols * 4 - 4), pa, ap, rows, cols, a0, f0, -1, -1, shape) == 1
-            assert L.rtdd_simulate_lens_blur(c._h, po, op, pd, dp, pa, ap, -1, cols, a0, f0, -1, -1, shape) == 1
-            assert L.rtdd_simulate_lens_blur(None, po, op, pd, dp, pa, ap, rows, cols, a0, f0, -1, -1, shape) == 1
+            assert_bad_images_refused(c, rt.lib().rtdd_simulate_lens_blur, o, d, art, rows, cols, (C.c_double(0.025), C.c_float(0.0), -1, -1, shape))
         c.synchronize()
         assert np.array_equal(down(art), sentinel)                            # nothing was launched
         # the limits themselves are accepted
@@ -329,7 +269,7 @@ def test_disc_at_the_clicked_pixel_on_the_dataset(name):
     x, y = (2 * cols) // 5, (3 * rows) // 5
     with rt.Context(0) as c:
         c.GPULoadWeights(0.4)
-        d = _estimate(c, bgr, ann)
+        d = estimate(c, bgr, ann)
         o, art = up(bgr), up(np.zeros_like(bgr))
         c.simulate_lens_blur(o, d, art, rows, cols, 0.025, 0.0, x, y)
         c.synchronize()
@@ -337,41 +277,19 @@ def test_disc_at_the_clicked_pixel_on_the_dataset(name):
         depth = c.pyramid_download(rt.IMG_DEPTH, 0)
         got = down(art)
     want = lens_blur_by_row_prefixes(bgr, depth, float(depth[y, x]))
-    assert np.array_equal(got, want), _differ(got, want)
-
-
-def _write_pnm(path, a):
-    with open(path, "wb") as f:
-        f.write(b"%s\n%d %d\n255\n" % (b"P6" if a.ndim == 3 else b"P5", a.shape[1], a.shape[0]))
-        f.write(np.ascontiguousarray(a).tobytes())
-
-
-def _read_pnm(path):
-    with open(path, "rb") as f:
-        magic = f.readline().strip(); w, h = map(int, f.readline().split()); f.readline()
-        a = np.frombuffer(f.read(), np.uint8)
-    return a.reshape(h, w, 3) if magic == b"P6" else a.reshape(h, w)
-
-
-def _harness(tmp_path, bgr, ann, args):
-    if not os.path.exists(BIN):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "harness")])
-    _write_pnm(tmp_path / "img.ppm", bgr[..., ::-1]); _write_pnm(tmp_path / "ann.pgm", ann)
-    out = subprocess.check_output([BIN, "-i", str(tmp_path / "img.ppm"), "-a", str(tmp_path / "ann.pgm"), "-o", str(tmp_path) + "/"] + args, text=True)
-    assert "Saving images" in out
-    return _read_pnm(tmp_path / "ArtisticEffect.ppm")[..., ::-1].copy()
+    assert_same_image(got, want, name)
 
 
 def test_harness_bokeh(tmp_path):
-    bgr, ann, _ = load_pair("WomanParasol")
+    bgr, ann = harness_pair(tmp_path, "pnm")
     rows, cols = bgr.shape[:2]
-    disc = _harness(tmp_path, bgr, ann, ["--effect", "refocus", "--bokeh", "disc", "--focus-at", "300,200"])
-    box = _harness(tmp_path, bgr, ann, ["--effect", "refocus", "--bokeh", "box", "--focus-at", "300,200"])
-    plain = _harness(tmp_path, bgr, ann, ["--effect", "refocus", "--focus-at", "300,200"])
+    disc = run_harness(tmp_path, "pnm", ["--effect", "refocus", "--bokeh", "disc", "--focus-at", "300,200"])[1]
+    box = run_harness(tmp_path, "pnm", ["--effect", "refocus", "--bokeh", "box", "--focus-at", "300,200"])[1]
+    plain = run_harness(tmp_path, "pnm", ["--effect", "refocus", "--focus-at", "300,200"])[1]
     assert np.array_equal(box, plain)
     with rt.Context(0) as c:
         c.GPULoadWeights(0.4)
-        d = _estimate(c, bgr, ann)
+        d = estimate(c, bgr, ann)
         o, a1, a2 = up(bgr), up(np.zeros_like(bgr)), up(np.zeros_like(bgr))
         c.simulate_lens_blur(o, d, a1, rows, cols, 0.025, 0.0, 300, 200, rt.APERTURE_DISC)
         c.simulate_refocus(o, d, a2, rows, cols, 0.025, 0.0, 300, 200)
@@ -382,9 +300,7 @@ def test_harness_bokeh(tmp_path):
 
 
 def test_harness_refuses_live_with_the_disc():
-    if not os.path.exists(BIN):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "harness")])
-    r = subprocess.run([BIN, "-i", "unused.ppm", "--live", "3", "--effect", "refocus", "--bokeh", "disc"], capture_output=True, text=True)
+    r = subprocess.run([harness_bin(), "-i", "unused.ppm", "--live", "3", "--effect", "refocus", "--bokeh", "disc"], capture_output=True, text=True)
     assert r.returncode != 0 and "not supported with --live" in r.stdout
-    r = subprocess.run([BIN, "-i", "unused.ppm", "--effect", "refocus", "--bokeh", "hexagon"], capture_output=True, text=True)
+    r = subprocess.run([harness_bin(), "-i", "unused.ppm", "--effect", "refocus", "--bokeh", "hexagon"], capture_output=True, text=True)
     assert r.returncode != 0 and "--bokeh wants box or disc" in r.stdout

@@ -4,32 +4,23 @@ both directions, rows wider than 1024 and whole rows of holes; adversarial maps;
 identity on the device; determinism and FP contraction; sub-image views; the shared scratch buffer; the zero-parallax pixel read on the
 device behind an estimate; the heal log; the host-side refusals; the harness."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
 import pytest
-import torch
 
 import realtimedepthdiffusion_amd as rt
-from dataset_util import load_pair
+from effect_gpu import ctx  # noqa: F401
+from effect_gpu import (assert_bad_images_refused, assert_padding_untouched, assert_same_image, clean_and_healed, estimate, harness_bin,
+                        harness_pair, padded_artistic, pixel_form_behind_estimate, raw_images, run_harness)
 from gpu_util import down, up
 from parallax_ref import parallax, scatter
 from roi_util import FILL_OUTPUT, LAYOUTS_F32, LAYOUTS_U8, Roi, covering, pitch_for
 from stereo_ref import stereo
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "harness", "rtdd_harness")
 SHAPES = [(1, 1), (1, 64), (5, 97), (61, 83), (257, 300), (4, 2100), (3, 500)]
 Z0 = [0.0, 127.5, 255.0]
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = rt.Context(0)
-    yield c
-    c.close()
 
 
 def _orig(rows, cols, seed=0):
@@ -77,10 +68,6 @@ def _run(c, o, d, rows, cols, view, z0=0.0, at=None, align=512):
     return down(art)
 
 
-def _check(got, want, what):
-    assert np.array_equal(got, want), f"{what}: {int((got != want).any(-1).sum())} of {got.shape[0] * got.shape[1]} pixels differ"
-
-
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_bit_exact(ctx, shape):
     rows, cols = shape
@@ -93,11 +80,11 @@ def test_bit_exact(ctx, shape):
             z0 = Z0[n % 3]; n += 1
             want = parallax(orig, depth, *view, z0)
             for align, o, d in images:
-                _check(_run(ctx, o, d, rows, cols, view, z0, align=align), want, (shape, name, align, view, z0))
+                assert_same_image(_run(ctx, o, d, rows, cols, view, z0, align=align), want, (shape, name, align, view, z0))
     at = (cols // 3, rows - 1)
     depth = _maps(rows, cols, 1)["random"]
     o, d = up(orig), up(depth)
-    _check(_run(ctx, o, d, rows, cols, (5, -7, 0.0), at=at), parallax(orig, depth, 5, -7, 0.0, zx=at[0], zy=at[1]), (shape, "pixel form"))
+    assert_same_image(_run(ctx, o, d, rows, cols, (5, -7, 0.0), at=at), parallax(orig, depth, 5, -7, 0.0, zx=at[0], zy=at[1]), (shape, "pixel form"))
 
 
 def test_a_whole_row_of_holes_marches_across_the_image(ctx):
@@ -112,7 +99,7 @@ def test_a_whole_row_of_holes_marches_across_the_image(ctx):
     assert (keys[1] == np.uint64(0xFFFFFFFFFFFFFFFF)).all()
     want = parallax(orig, far, *view, 0.0)
     assert np.array_equal(want[1], orig[1])
-    _check(_run(ctx, up(orig), up(far), rows, cols, view, 0.0), want, "whole row of holes")
+    assert_same_image(_run(ctx, up(orig), up(far), rows, cols, view, 0.0), want, "whole row of holes")
 
 
 def test_ties_go_to_the_smallest_source_index(ctx):
@@ -122,7 +109,7 @@ def test_ties_go_to_the_smallest_source_index(ctx):
     for view in ((0, 0, 1.0), (3, -2, 2.5), (0, 0, 0.5)):         # a contracting dolly on a plane behind z0
         _, same = scatter(const, *view, 0.0)
         assert (same >= 2).any(), view                  # at least one target with two or more candidates of equal d': the rule is exercised
-        _check(_run(ctx, up(orig), up(const), rows, cols, view, 0.0), parallax(orig, const, *view, 0.0), view)
+        assert_same_image(_run(ctx, up(orig), up(const), rows, cols, view, 0.0), parallax(orig, const, *view, 0.0), view)
 
 
 @pytest.mark.parametrize("shape", [(5, 97), (9, 300), (4, 2100)], ids=lambda s: f"{s[0]}x{s[1]}")
@@ -137,8 +124,8 @@ def test_horizontal_case_is_the_stereo_view_on_the_device(ctx, shape):
                 ctx.simulate_stereo(o, d, art, rows, cols, D, z0, -1, -1, rt.STEREO_VIEW)
                 ctx.synchronize()
                 sv = down(art)
-                _check(_run(ctx, o, d, rows, cols, (D, 0, 0.0), z0), sv, (shape, name, D, z0))
-                _check(sv, stereo(orig, depth, D, z0), "stereo itself")
+                assert_same_image(_run(ctx, o, d, rows, cols, (D, 0, 0.0), z0), sv, (shape, name, D, z0))
+                assert_same_image(sv, stereo(orig, depth, D, z0), "stereo itself")
 
 
 def test_identities(ctx):
@@ -146,12 +133,12 @@ def test_identities(ctx):
     orig = _orig(rows, cols, 4)
     depth = _maps(rows, cols, 4)["random"]
     o, d = up(orig), up(depth)
-    _check(_run(ctx, o, d, rows, cols, (0, 0, 0.0), 100.0), orig, "no motion")
+    assert_same_image(_run(ctx, o, d, rows, cols, (0, 0, 0.0), 100.0), orig, "no motion")
     const = np.full((rows, cols), 99.0, np.float32)
     dc = up(const)
     for view in _views(rows, cols):
-        _check(_run(ctx, o, dc, rows, cols, view, 99.0), orig, ("constant map at z0", view))
-        _check(_run(ctx, o, dc, rows, cols, view, at=(5, 6)), orig, ("constant map, pixel form", view))
+        assert_same_image(_run(ctx, o, dc, rows, cols, view, 99.0), orig, ("constant map at z0", view))
+        assert_same_image(_run(ctx, o, dc, rows, cols, view, at=(5, 6)), orig, ("constant map, pixel form", view))
 
 
 def test_deterministic_and_independent_of_fp_contraction(ctx):
@@ -169,7 +156,7 @@ def test_deterministic_and_independent_of_fp_contraction(ctx):
     finally:
         ctx.set_option(rt.OPT_FP_CONTRACT, 1)
     assert np.array_equal(outs[0], outs[1]) and np.array_equal(outs[1], outs[2])
-    _check(outs[0], parallax(orig, depth, *view, 127.5), "contraction")
+    assert_same_image(outs[0], parallax(orig, depth, *view, 127.5), "contraction")
 
 
 @pytest.mark.parametrize("shape", [(61, 83), (9, 300)], ids=lambda s: f"{s[0]}x{s[1]}")
@@ -189,7 +176,7 @@ def test_sub_image_views(ctx, shape):
         out = Roi(np.zeros_like(orig), *lay_u8[a], FILL_OUTPUT, seed=k, what=f"artistic {lay_u8[a]}")
         ctx.simulate_parallax(ins_o[i].img, ins_d[j].img, out.img, rows, cols, rt.Parallax(*view, 60.0))
         ctx.synchronize()
-        _check(out.result(), want, (shape, lay_u8[i], lay_f32[j], lay_u8[a]))
+        assert_same_image(out.result(), want, (shape, lay_u8[i], lay_f32[j], lay_u8[a]))
         ins_o[i].assert_unchanged(); ins_d[j].assert_unchanged()
 
 
@@ -198,13 +185,11 @@ def test_padding_bytes_stay_untouched(ctx):
     pitch = cols * 3 + 13
     orig = _orig(rows, cols, 8)
     depth = _maps(rows, cols, 8)["random"]
-    base = torch.full((rows, pitch), 0x5A, dtype=torch.uint8, device="cuda:0")
-    art = base[:, :cols * 3].unflatten(1, (cols, 3))
+    base, art = padded_artistic(rows, cols, pitch)
     ctx.simulate_parallax(up(orig), up(depth), art, rows, cols, rt.Parallax(*view, 60.0))
     ctx.synchronize()
-    b = base.cpu().numpy()
-    assert (b[:, cols * 3:] == 0x5A).all()
-    _check(b[:, :cols * 3].reshape(rows, cols, 3), parallax(orig, depth, *view, 60.0), "padded rows")
+    assert_padding_untouched(base, cols)
+    assert_same_image(down(art), parallax(orig, depth, *view, 60.0), "padded rows")
 
 
 def test_the_scratch_is_shared_with_the_defocus_table():
@@ -224,79 +209,39 @@ def test_the_scratch_is_shared_with_the_defocus_table():
             assert c.get_option(rt.OPT_DEFOCUS_LAST_PATH) == 1
             outs.append(down(art))
             if step == 0:
-                _check(_run(c, o, d, rows, cols, (40, -25, 0.5), 100.0), parallax(orig, depth, 40, -25, 0.5, 100.0), "between the two defocus calls")
+                assert_same_image(_run(c, o, d, rows, cols, (40, -25, 0.5), 100.0), parallax(orig, depth, 40, -25, 0.5, 100.0), "between the two defocus calls")
         assert np.array_equal(outs[0], outs[1])
         for r2, c2 in ((37, 91), (300, 260)):           # a smaller image in the same buffer, a larger one in a new one
             o2 = _orig(r2, c2, 10)
             d2 = _maps(r2, c2, 10)["random"]
-            _check(_run(c, up(o2), up(d2), r2, c2, (-11, 17, -0.3), 30.0), parallax(o2, d2, -11, 17, -0.3, 30.0), (r2, c2))
+            assert_same_image(_run(c, up(o2), up(d2), r2, c2, (-11, 17, -0.3), 30.0), parallax(o2, d2, -11, 17, -0.3, 30.0), (r2, c2))
         art = up(np.zeros_like(orig))
         c.GPUSimulateDefocus(o, d, art, rows, cols)
         c.synchronize()
         assert np.array_equal(down(art), outs[0])
 
 
-def _estimate(c, bgr, ann):
-    rows, cols = bgr.shape[:2]
-    c.pyramid_create(rows, cols)
-    c.pyramid_set_image(up(bgr)); c.pyramid_set_annotation(up(ann))
-    c.estimate_depth(1000)
-    return c.pyramid_image(rt.IMG_DEPTH, 0)
-
-
 def test_pixel_form_reads_the_map_behind_an_unsynchronised_estimate():
-    bgr, ann, _ = load_pair("Dog")
-    rows, cols = bgr.shape[:2]
-    with rt.Context(0) as c:
-        c.GPULoadWeights(0.4)
-        _estimate(c, bgr, ann)
-        first = c.pyramid_download(rt.IMG_DEPTH, 0)
-        ys, xs = np.nonzero((first > 60) & (first < 200))
-        y, x = int(ys[len(ys) // 2]), int(xs[len(xs) // 2])
-        d = _estimate(c, bgr, ann)                                          # a new image: the same estimate again, from a cold start
-        o = up(bgr)
-        a1, a2 = up(np.zeros_like(bgr)), up(np.zeros_like(bgr))
-        c.simulate_parallax(o, d, a1, rows, cols, rt.Parallax(30, -18, 0.05, 0.0, x, y))     # no synchronisation since the estimate was queued
-        c.synchronize()
-        depth = c.pyramid_download(rt.IMG_DEPTH, 0)
-        fv = float(depth[y, x])
-        assert 60.0 < fv < 200.0
-        c.simulate_parallax(o, d, a2, rows, cols, rt.Parallax(30, -18, 0.05, fv, -1, -1))
-        c.synchronize()
-        assert np.array_equal(down(a1), down(a2))
-        _check(down(a1), parallax(bgr, depth, 30, -18, 0.05, fv), "pixel form")
+    def call(c, o, d, art, x, y, value=None):
+        rows, cols = o.shape[:2]
+        view = rt.Parallax(30, -18, 0.05, 0.0, x, y) if value is None else rt.Parallax(30, -18, 0.05, value, -1, -1)
+        c.simulate_parallax(o, d, art, rows, cols, view)
+
+    bgr, depth, _, _, fv, image = pixel_form_behind_estimate(call)
+    assert_same_image(image, parallax(bgr, depth, 30, -18, 0.05, fv), "pixel form")
 
 
 def test_parallax_is_replayed_after_a_healed_solve():
-    from realtimedepthdiffusion_amd.synth import make_problem
     rows, cols = 270, 480
-    p = make_problem(rows, cols, seed=6)
     orig = _orig(rows, cols, 2)
 
-    def run(force):
-        c = rt.Context(0)
-        try:
-            c.GPUAllocateDeviceMemory(rows, cols, 1); c.GPULoadWeights(0.4)
-            d, m, g = up(p["depth"]), up(p["mask"]), up(p["gray"])
-            o = up(orig)
-            a1, a2 = up(np.zeros_like(orig)), up(np.zeros_like(orig))
-            if force:
-                c.set_option(rt.OPT_DEBUG_FORCE_STATUS, 1)
-            c.GPUMatrixFreeSolver(d, m, g, rows, cols, 0.4, 24, 0.0, 0)
-            c.simulate_parallax(o, d, a1, rows, cols, rt.Parallax(31, -14, 0.2, 0.0, 100, 200))
-            c.simulate_parallax(o, d, a2, rows, cols, rt.Parallax(-12, 0, -0.5, 90.0, -1, -1))
-            c.synchronize()
-            assert c.get_option(rt.OPT_TIMEOUT_HEALS) == (1 if force else 0)
-            return down(d), down(a1), down(a2)
-        finally:
-            c.close()
+    def queue(c, o, d, arts):
+        c.simulate_parallax(o, d, arts[0], rows, cols, rt.Parallax(31, -14, 0.2, 0.0, 100, 200))
+        c.simulate_parallax(o, d, arts[1], rows, cols, rt.Parallax(-12, 0, -0.5, 90.0, -1, -1))
 
-    clean, healed = run(False), run(True)
-    assert not np.array_equal(clean[0], p["depth"])
-    for w, g in zip(clean, healed):
-        assert np.array_equal(g, w)
-    _check(healed[1], parallax(orig, clean[0], 31, -14, 0.2, zx=100, zy=200), "healed view, pixel form")
-    _check(healed[2], parallax(orig, clean[0], -12, 0, -0.5, 90.0), "healed view")
+    solved, healed = clean_and_healed(queue, 2, orig)
+    assert_same_image(healed[0], parallax(orig, solved, 31, -14, 0.2, zx=100, zy=200), "healed view, pixel form")
+    assert_same_image(healed[1], parallax(orig, solved, -12, 0, -0.5, 90.0), "healed view")
 
 
 def test_invalid_arguments_are_refused_on_the_host():
@@ -329,23 +274,10 @@ def test_invalid_arguments_are_refused_on_the_host():
         assert e.value.status == 1
         c.simulate_parallax(o, d, o, 0, cols, rt.Parallax(10, 0))                   # ... and the in-place rule after it
         c.simulate_parallax(o, d, o, rows, 0, rt.Parallax(10, 0))
-        L = rt.lib()
-        f = L.rtdd_simulate_parallax
-        op, dp, ap = C.c_size_t(o.stride(0)), C.c_size_t(d.stride(0) * 4), C.c_size_t(art.stride(0))
-        po, pd, pa = C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()), C.c_void_p(art.data_ptr())
-        v = rt.Parallax(10, -4, 0.5, 20.0)
-        pv = C.byref(v)
-        assert f(c._h, None, op, pd, dp, pa, ap, rows, cols, pv) == 1
-        assert f(c._h, po, op, None, dp, pa, ap, rows, cols, pv) == 1
-        assert f(c._h, po, op, pd, dp, None, ap, rows, cols, pv) == 1
-        assert f(c._h, po, op, pd, dp, pa, ap, rows, cols, None) == 1
-        assert f(c._h, po, op, pd, dp, pa, ap, -1, cols, pv) == 1
-        assert f(c._h, po, C.c_size_t(cols * 3 - 1), pd, dp, pa, ap, rows, cols, pv) == 1       # a pitch one byte short of a row
-        assert f(c._h, po, op, pd, dp, pa, C.c_size_t(cols * 3 - 1), rows, cols, pv) == 1
-        assert f(c._h, po, op, pd, C.c_size_t(cols * 4 - 4), pa, ap, rows, cols, pv) == 1
-        assert f(c._h, po, op, C.c_void_p(d.data_ptr() + 2), dp, pa, ap, rows, cols, pv) == 1   # an unaligned f32 image
-        assert f(c._h, po, op, pd, dp, po, op, rows, cols, pv) == 1                             # in place
-        assert f(None, po, op, pd, dp, pa, ap, rows, cols, pv) == 1
+        f = rt.lib().rtdd_simulate_parallax
+        assert_bad_images_refused(c, f, o, d, art, rows, cols, (C.byref(rt.Parallax(10, -4, 0.5, 20.0)),))
+        po, op, pd, dp, pa, ap = raw_images(o, d, art)
+        assert f(c._h, po, op, pd, dp, pa, ap, rows, cols, None) == 1                           # a null view
         for kw in bad:
             w = rt.Parallax(**kw)
             assert f(c._h, po, op, pd, dp, pa, ap, rows, cols, C.byref(w)) == 1, kw
@@ -359,35 +291,16 @@ def test_invalid_arguments_are_refused_on_the_host():
         c.synchronize()
 
 
-def _write_pnm(path, a):
-    with open(path, "wb") as f:
-        f.write(b"%s\n%d %d\n255\n" % (b"P6" if a.ndim == 3 else b"P5", a.shape[1], a.shape[0]))
-        f.write(np.ascontiguousarray(a).tobytes())
-
-
-def _read_pnm(path):
-    with open(path, "rb") as f:
-        magic = f.readline().strip(); w, h = map(int, f.readline().split()); f.readline()
-        a = np.frombuffer(f.read(), np.uint8)
-    return a.reshape(h, w, 3) if magic == b"P6" else a.reshape(h, w)
-
-
 @pytest.mark.parametrize("args,call", [(["--shift", "19,-11", "--dolly", "0.125", "--zero-parallax", "128"], (19, -11, 0.125, 128.0, -1, -1)),
                                        (["--shift", "-25,0"], (-25, 0, 0.0, 0.0, -1, -1)),
                                        (["--shift", "0,30", "--dolly", "-0.25", "--zero-parallax-at", "300,200"], (0, 30, -0.25, 0.0, 300, 200))])
 def test_harness_writes_the_librarys_image(tmp_path, args, call):
-    if not os.path.exists(BIN):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "harness")])
-    bgr, ann, _ = load_pair("WomanParasol")
+    bgr, ann = harness_pair(tmp_path, "pnm")
     rows, cols = bgr.shape[:2]
-    _write_pnm(tmp_path / "img.ppm", bgr[..., ::-1]); _write_pnm(tmp_path / "ann.pgm", ann)
-    out = subprocess.check_output([BIN, "-i", str(tmp_path / "img.ppm"), "-a", str(tmp_path / "ann.pgm"), "-o", str(tmp_path) + "/",
-                                   "--effect", "parallax"] + args, text=True)
-    assert "Saving images" in out
-    got = _read_pnm(tmp_path / "ArtisticEffect.ppm")[..., ::-1]
+    got = run_harness(tmp_path, "pnm", ["--effect", "parallax"] + args)[1]
     with rt.Context(0) as c:
         c.GPULoadWeights(0.4)
-        d = _estimate(c, bgr, ann)
+        d = estimate(c, bgr, ann)
         o, art = up(bgr), up(np.zeros_like(bgr))
         c.simulate_parallax(o, d, art, rows, cols, rt.Parallax(*call))
         c.synchronize()
@@ -397,7 +310,5 @@ def test_harness_writes_the_librarys_image(tmp_path, args, call):
 
 
 def test_harness_refuses_live_with_parallax():
-    if not os.path.exists(BIN):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "harness")])
-    r = subprocess.run([BIN, "-i", "unused.ppm", "--live", "3", "--effect", "parallax", "--shift", "10,5"], capture_output=True, text=True)
+    r = subprocess.run([harness_bin(), "-i", "unused.ppm", "--live", "3", "--effect", "parallax", "--shift", "10,5"], capture_output=True, text=True)
     assert r.returncode != 0 and "not supported with --live" in r.stdout

@@ -1,7 +1,7 @@
 """Refocus at a chosen depth and haze with density and airlight (include/rtdd.h rtdd_simulate_refocus, rtdd_simulate_haze_ex) on the
 GPU (-m gpu): bit for bit against the restatements of tests/refocus_ref.py and the oracle's literal gather, on both defocus paths, with
 column strips and slices; the focus pixel read on the device behind an estimate; the heal log; the host-side refusals; the harness."""
-import os
+import ctypes as C
 import subprocess
 
 import numpy as np
@@ -9,21 +9,15 @@ import pytest
 
 import realtimedepthdiffusion_amd as rt
 from dataset_util import PAIRS, load_pair
+from effect_gpu import ctx  # noqa: F401
+from effect_gpu import (assert_bad_images_refused, clean_and_healed, estimate, harness_bin, harness_pair, pixel_form_behind_estimate, raw_images,
+                        run_harness)
 from effects_ref import effect_inputs
 from gpu_util import down, up
 from refocus_ref import focus_distance, haze_ex, kernel_size, largest_aperture, refocus_by_summed_area_table
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "harness", "rtdd_harness")
 FOCI = [0.0, 37.5, 128.0, 255.0]
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = rt.Context(0)
-    yield c
-    c.close()
 
 
 def _refocus(c, o, d, rows, cols, aperture=0.025, f=0.0, at=None, path=0):
@@ -100,14 +94,6 @@ def test_refocus_full_size(ctx, oracle, rows, cols, name):
             assert np.array_equal(got[ys, xs], oracle.defocus_at(orig, focus_distance(depth, fv), ys, xs))
 
 
-def _estimate(c, bgr, ann):
-    rows, cols = bgr.shape[:2]
-    c.pyramid_create(rows, cols)
-    c.pyramid_set_image(up(bgr)); c.pyramid_set_annotation(up(ann))
-    c.estimate_depth(1000)
-    return c.pyramid_image(rt.IMG_DEPTH, 0)
-
-
 @pytest.mark.parametrize("name", PAIRS)
 def test_defaults_equal_defocus_on_the_dataset(name):
     """f = 0, aperture 0.025 is rtdd_simulate_defocus on every pair's estimated depth."""
@@ -115,7 +101,7 @@ def test_defaults_equal_defocus_on_the_dataset(name):
     rows, cols = bgr.shape[:2]
     with rt.Context(0) as c:
         c.GPULoadWeights(0.4)
-        d = _estimate(c, bgr, ann)
+        d = estimate(c, bgr, ann)
         o = up(bgr)
         a1, a2 = up(np.zeros_like(bgr)), up(np.zeros_like(bgr))
         c.GPUSimulateDefocus(o, d, a1, rows, cols)
@@ -125,24 +111,14 @@ def test_defaults_equal_defocus_on_the_dataset(name):
 
 
 def test_pixel_form_reads_the_map_behind_an_unsynchronised_estimate():
-    bgr, ann, _ = load_pair("Dog")
-    rows, cols = bgr.shape[:2]
-    with rt.Context(0) as c:
-        c.GPULoadWeights(0.4)
-        _estimate(c, bgr, ann)
-        first = c.pyramid_download(rt.IMG_DEPTH, 0)
-        ys, xs = np.nonzero((first > 60) & (first < 200))                 # a pixel in the middle of the depth range
-        y, x = int(ys[len(ys) // 2]), int(xs[len(xs) // 2])
-        d = _estimate(c, bgr, ann)                                          # a new image: the same estimate again, from a cold start
-        o = up(bgr)
-        a1, a2 = up(np.zeros_like(bgr)), up(np.zeros_like(bgr))
-        c.simulate_refocus(o, d, a1, rows, cols, 0.025, 0.0, x, y)          # no synchronisation since the estimate was queued
-        c.synchronize()
-        fv = float(c.pyramid_download(rt.IMG_DEPTH, 0)[y, x])
-        assert 60.0 < fv < 200.0
-        c.simulate_refocus(o, d, a2, rows, cols, 0.025, fv, -1, -1)
-        c.synchronize()
-        assert np.array_equal(down(a1), down(a2))
+    def call(c, o, d, art, x, y, value=None):
+        rows, cols = o.shape[:2]
+        if value is None:
+            c.simulate_refocus(o, d, art, rows, cols, 0.025, 0.0, x, y)
+        else:
+            c.simulate_refocus(o, d, art, rows, cols, 0.025, value, -1, -1)
+
+    pixel_form_behind_estimate(call)
 
 
 @pytest.mark.parametrize("align", [512, 1])
@@ -181,38 +157,17 @@ def test_haze_ex_bit_exact_against_the_exact_restatement(ctx, oracle, align):
 def test_refocus_and_haze_ex_are_replayed_after_a_healed_solve():
     """A solve with a (simulated) time-out status, refocus (pixel form) and haze_ex queued behind it: the synchronisation heals the
     solve and renders both again from the healed depth -- the images of a clean run."""
-    from realtimedepthdiffusion_amd.synth import make_problem
     rows, cols = 270, 480
-    p = make_problem(rows, cols, seed=6)
-    orig = effect_inputs(rows, cols, 2)[0]
 
-    def run(force):
-        c = rt.Context(0)
-        try:
-            c.GPUAllocateDeviceMemory(rows, cols, 1); c.GPULoadWeights(0.4)
-            d, m, g = up(p["depth"]), up(p["mask"]), up(p["gray"])
-            o = up(orig)
-            a1, a2 = up(np.zeros_like(orig)), up(np.zeros_like(orig))
-            if force:
-                c.set_option(rt.OPT_DEBUG_FORCE_STATUS, 1)
-            c.GPUMatrixFreeSolver(d, m, g, rows, cols, 0.4, 24, 0.0, 0)
-            c.simulate_refocus(o, d, a1, rows, cols, 0.025, 0.0, 100, 200)
-            c.simulate_haze_ex(o, d, a2, rows, cols, 3.0, (40, 90, 200))
-            c.synchronize()
-            assert c.get_option(rt.OPT_TIMEOUT_HEALS) == (1 if force else 0)
-            return down(d), down(a1), down(a2)
-        finally:
-            c.close()
+    def queue(c, o, d, arts):
+        c.simulate_refocus(o, d, arts[0], rows, cols, 0.025, 0.0, 100, 200)
+        c.simulate_haze_ex(o, d, arts[1], rows, cols, 3.0, (40, 90, 200))
 
-    clean, healed = run(False), run(True)
-    assert not np.array_equal(clean[0], p["depth"])
-    for w, g in zip(clean, healed):
-        assert np.array_equal(g, w)
+    clean_and_healed(queue, 2, effect_inputs(rows, cols, 2)[0])
 
 
 def test_invalid_arguments_are_refused_on_the_host():
     """Every refusal with correctly sized buffers: a refusal that did not happen could never send the GPU through a wild pointer."""
-    import ctypes as C
     rows, cols = 40, 60
     orig, depth = effect_inputs(rows, cols, 1)
     sentinel = np.full_like(orig, 77)
@@ -236,14 +191,10 @@ def test_invalid_arguments_are_refused_on_the_host():
             c.simulate_refocus(o, d, o, rows, cols, 0.025, 0.0, -1, -1)            # in place
         assert e.value.status == 1
         L = rt.lib()
-        op, dp, ap = C.c_size_t(o.stride(0)), C.c_size_t(d.stride(0) * 4), C.c_size_t(art.stride(0))
-        po, pd, pa = C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()), C.c_void_p(art.data_ptr())
-        f0, a0 = C.c_float(0.0), C.c_double(0.025)
-        assert L.rtdd_simulate_refocus(c._h, None, op, pd, dp, pa, ap, rows, cols, a0, f0, -1, -1) == 1
-        assert L.rtdd_simulate_refocus(c._h, po, op, pd, dp, pa, C.c_size_t(cols * 3 - 1), rows, cols, a0, f0, -1, -1) == 1
+        assert_bad_images_refused(c, L.rtdd_simulate_refocus, o, d, art, rows, cols, (C.c_double(0.025), C.c_float(0.0), -1, -1))
+        po, op, pd, dp, pa, ap = raw_images(o, d, art)                        # (haze_ex may run in place: its own two cases)
         assert L.rtdd_simulate_haze_ex(c._h, po, op, None, dp, pa, ap, rows, cols, C.c_float(2.0), 1, 2, 3) == 1
         assert L.rtdd_simulate_haze_ex(c._h, po, op, pd, C.c_size_t(cols * 4 - 4), pa, ap, rows, cols, C.c_float(2.0), 1, 2, 3) == 1
-        assert L.rtdd_simulate_refocus(None, po, op, pd, dp, pa, ap, rows, cols, a0, f0, -1, -1) == 1
         c.synchronize()
         assert np.array_equal(down(art), sentinel)                            # nothing was launched
         # the limits themselves are accepted
@@ -254,34 +205,16 @@ def test_invalid_arguments_are_refused_on_the_host():
         c.synchronize()
 
 
-def _write_pnm(path, a):
-    with open(path, "wb") as f:
-        f.write(b"%s\n%d %d\n255\n" % (b"P6" if a.ndim == 3 else b"P5", a.shape[1], a.shape[0]))
-        f.write(np.ascontiguousarray(a).tobytes())
-
-
-def _read_pnm(path):
-    with open(path, "rb") as f:
-        magic = f.readline().strip(); w, h = map(int, f.readline().split()); f.readline()
-        a = np.frombuffer(f.read(), np.uint8)
-    return a.reshape(h, w, 3) if magic == b"P6" else a.reshape(h, w)
-
-
 @pytest.mark.parametrize("args", [["--effect", "refocus", "--focus-at", "300,200"],
                                   ["--effect", "refocus", "--focus", "180.5", "--aperture", "0.05"],
                                   ["--effect", "haze", "--haze-beta", "4", "--airlight", "200,180,160"]])
 def test_harness_writes_the_librarys_image(tmp_path, args):
-    if not os.path.exists(BIN):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "harness")])
-    bgr, ann, _ = load_pair("WomanParasol")
+    bgr, ann = harness_pair(tmp_path, "pnm")
     rows, cols = bgr.shape[:2]
-    _write_pnm(tmp_path / "img.ppm", bgr[..., ::-1]); _write_pnm(tmp_path / "ann.pgm", ann)
-    out = subprocess.check_output([BIN, "-i", str(tmp_path / "img.ppm"), "-a", str(tmp_path / "ann.pgm"), "-o", str(tmp_path) + "/"] + args, text=True)
-    assert "Saving images" in out
-    got = _read_pnm(tmp_path / "ArtisticEffect.ppm")[..., ::-1]
+    got = run_harness(tmp_path, "pnm", args)[1]
     with rt.Context(0) as c:
         c.GPULoadWeights(0.4)
-        d = _estimate(c, bgr, ann)
+        d = estimate(c, bgr, ann)
         o, art = up(bgr), up(np.zeros_like(bgr))
         if args[1] == "refocus":
             if args[2] == "--focus-at":
@@ -296,8 +229,6 @@ def test_harness_writes_the_librarys_image(tmp_path, args):
 
 
 def test_harness_refuses_live_with_the_aimed_effects(tmp_path):
-    if not os.path.exists(BIN):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "harness")])
     for extra in (["--effect", "refocus"], ["--effect", "haze", "--haze-beta", "3"]):
-        r = subprocess.run([BIN, "-i", "unused.ppm", "--live", "3"] + extra, capture_output=True, text=True)
+        r = subprocess.run([harness_bin(), "-i", "unused.ppm", "--live", "3"] + extra, capture_output=True, text=True)
         assert r.returncode != 0 and "not supported with --live" in r.stdout

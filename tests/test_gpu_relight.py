@@ -4,36 +4,19 @@ image and on the surface, denormal depth differences, NaN and out-of-range depth
 anchor pixel read on the device behind an estimate; the heal log; the host-side refusals; the harness.  No tolerance anywhere: every
 operation of the header is a correctly rounded IEEE one."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
 import pytest
-import torch
 
 import realtimedepthdiffusion_amd as rt
-from dataset_util import load_pair
+from effect_gpu import ctx, dog_depth  # noqa: F401
+from effect_gpu import (assert_bad_images_refused, assert_padding_untouched, assert_same_image, clean_and_healed, estimate, harness_bin,
+                        harness_pair, padded_artistic, pixel_form_behind_estimate, random_inputs, run_harness, tile_mirrored)
 from gpu_util import down, up
 from relight_ref import DIRECTIONAL, POINT, light, relight
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "harness", "rtdd_harness")
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = rt.Context(0)
-    yield c
-    c.close()
-
-
-def _inputs(rows, cols, seed):
-    rng = np.random.default_rng(seed)
-    orig = rng.integers(0, 256, (rows, cols, 3), dtype=np.uint8)
-    depth = rng.uniform(-20, 275, (rows, cols)).astype(np.float32)
-    depth[rng.random((rows, cols)) < 0.03] = np.nan
-    return orig, depth
 
 
 def _relight(c, o, d, rows, cols, L, align=512):
@@ -41,10 +24,6 @@ def _relight(c, o, d, rows, cols, L, align=512):
     c.simulate_relight(o, d, art, rows, cols, rt.Light(**L))
     c.synchronize()
     return down(art)
-
-
-def _check(got, want, what):
-    assert np.array_equal(got, want), f"{what}: {int((got != want).any(-1).sum())} of {got.shape[0] * got.shape[1]} pixels differ"
 
 
 def _lights(rows, cols, relief):
@@ -65,18 +44,18 @@ def _lights(rows, cols, relief):
                                          ((3, 2051), 512), ((6, 1024), 512), ((5, 255), 4), ((9, 1027), 512)])
 def test_small_shapes_bit_exact(ctx, shape, align):
     rows, cols = shape
-    orig, depth = _inputs(rows, cols, rows * 1000 + cols)
+    orig, depth = random_inputs(rows, cols, rows * 1000 + cols)
     o, d = up(orig, align), up(depth, align)
     for relief in (0.0, 0.5, 64.0):
         for L in _lights(rows, cols, relief):
-            _check(_relight(ctx, o, d, rows, cols, L, align), relight(orig, depth, L), (shape, align, L))
+            assert_same_image(_relight(ctx, o, d, rows, cols, L, align), relight(orig, depth, L), (shape, align, L))
 
 
 @pytest.mark.parametrize("align", [1, 512])
 def test_light_on_the_surface_and_tiny_distances(ctx, align):
     """A point light exactly over a pixel of the surface: vv == 0 there (shade 0), or tiny -- denormal squares under sqrtf and /."""
     rows, cols = 9, 261
-    orig, depth = _inputs(rows, cols, 77)
+    orig, depth = random_inputs(rows, cols, 77)
     orig[4, 100:104] = 255
     flat = np.full((rows, cols), 40.0, np.float32)
     o = up(orig, align)
@@ -86,7 +65,7 @@ def test_light_on_the_surface_and_tiny_distances(ctx, align):
             for relief in (0.0, 1.0):
                 for anchor in (dict(anchorX=101, anchorY=4), dict(anchorDepth=40.0)):
                     L = light(POINT, 101, 4, z, radius=0.5, relief=relief, ambient=0.0, diffuse=8.0, **anchor)
-                    _check(_relight(ctx, o, d, rows, cols, L, align), relight(orig, dm, L), (name, z, relief, anchor))
+                    assert_same_image(_relight(ctx, o, d, rows, cols, L, align), relight(orig, dm, L), (name, z, relief, anchor))
 
 
 @pytest.mark.parametrize("align", [4, 512])
@@ -100,27 +79,27 @@ def test_denormal_depth_differences(ctx, align):
     o, d = up(orig, align), up(depth, align)
     for relief in (0.5, 1.0, 64.0):
         for L in _lights(rows, cols, relief):
-            _check(_relight(ctx, o, d, rows, cols, L, align), relight(orig, depth, L), (relief, L))
+            assert_same_image(_relight(ctx, o, d, rows, cols, L, align), relight(orig, depth, L), (relief, L))
 
 
 def test_out_of_range_and_non_finite_depths(ctx):
     rows, cols = 6, 300
-    orig, depth = _inputs(rows, cols, 21)
+    orig, depth = random_inputs(rows, cols, 21)
     depth[1, ::7] = np.inf; depth[2, ::5] = -np.inf; depth[3, ::3] = 1e30; depth[4, ::2] = -1e30; depth[5] = np.nan
     o, d = up(orig), up(depth)
     for L in _lights(rows, cols, 2.0):
-        _check(_relight(ctx, o, d, rows, cols, L), relight(orig, depth, L), L)
+        assert_same_image(_relight(ctx, o, d, rows, cols, L), relight(orig, depth, L), L)
     L = light(DIRECTIONAL, 1, 2, 3, relief=64, ambient=1.75, diffuse=0)
     want = np.fmin(orig.astype(np.float32) * np.float32(1.75), np.float32(255)).astype(np.int32).astype(np.uint8)
-    _check(_relight(ctx, o, d, rows, cols, L), want, "diffuse 0")
+    assert_same_image(_relight(ctx, o, d, rows, cols, L), want, "diffuse 0")
 
 
 def test_identities_on_the_device(ctx):
     rows, cols = 33, 700
-    orig, depth = _inputs(rows, cols, 22)
+    orig, depth = random_inputs(rows, cols, 22)
     o = up(orig)
     const = up(np.full((rows, cols), 93.5, np.float32))
-    _check(_relight(ctx, o, const, rows, cols, light(DIRECTIONAL, 0, 0, 1, relief=7, ambient=0, diffuse=1)), orig, "the original")
+    assert_same_image(_relight(ctx, o, const, rows, cols, light(DIRECTIONAL, 0, 0, 1, relief=7, ambient=0, diffuse=1)), orig, "the original")
     ramp = np.tile((255 - 0.25 * np.arange(cols)).astype(np.float32), (rows, 1))
     r = up(ramp)
     lit = _relight(ctx, o, r, rows, cols, light(DIRECTIONAL, -1, 0, 1, relief=4, ambient=0, diffuse=1))
@@ -131,30 +110,7 @@ def test_identities_on_the_device(ctx):
     common = dict(relief=1.5, ambient=0.125, diffuse=1.0, color=(255, 200, 90))
     a = _relight(ctx, o, d, rows, cols, light(POINT, 40.5, 2.5, 30, anchorX=17, anchorY=3, radius=60, **common))
     b = _relight(ctx, of, df, rows, cols, light(POINT, cols - 1 - 40.5, 2.5, 30, anchorX=cols - 1 - 17, anchorY=3, radius=60, **common))
-    _check(b, a[:, ::-1], "mirror")
-
-
-def _estimate(c, bgr, ann):
-    rows, cols = bgr.shape[:2]
-    c.pyramid_create(rows, cols)
-    c.pyramid_set_image(up(bgr)); c.pyramid_set_annotation(up(ann))
-    c.estimate_depth(1000)
-    return c.pyramid_image(rt.IMG_DEPTH, 0)
-
-
-def _tile(a, rows, cols):
-    a2 = np.concatenate([a, a[:, ::-1]], 1); a4 = np.concatenate([a2, a2[::-1]], 0)
-    return np.ascontiguousarray(np.tile(a4, (-(-rows // a4.shape[0]), -(-cols // a4.shape[1])))[:rows, :cols])
-
-
-@pytest.fixture(scope="module")
-def dog_depth():
-    bgr, ann, _ = load_pair("Dog")
-    with rt.Context(0) as c:
-        c.GPULoadWeights(0.4)
-        _estimate(c, bgr, ann)
-        c.synchronize()
-        return c.pyramid_download(rt.IMG_DEPTH, 0)
+    assert_same_image(b, a[:, ::-1], "mirror")
 
 
 @pytest.mark.parametrize("rows,cols", [(1080, 1920), (2160, 3840), (4320, 7680)])
@@ -166,36 +122,33 @@ def test_full_size(ctx, dog_depth, rows, cols):
     lights = [light(DIRECTIONAL, -1, -1, 1, relief=2, ambient=0.25, diffuse=1.0),
               light(POINT, cols * 0.4, rows * 0.3, 120, anchorX=cols // 2, anchorY=rows // 2, radius=cols / 4, relief=1.5, ambient=0.1, diffuse=3.0,
                     color=(200, 230, 255))]
-    for name, depth in (("Dog tiled", _tile(dog_depth, rows, cols)), ("random", random)):
+    for name, depth in (("Dog tiled", tile_mirrored(dog_depth, rows, cols)), ("random", random)):
         d = up(depth)
         for L in lights:
             pitch = cols * 3 + 512
-            base = torch.full((rows, pitch), 0x5A, dtype=torch.uint8, device="cuda:0")
-            art = base[:, :cols * 3].unflatten(1, (cols, 3))
+            base, art = padded_artistic(rows, cols, pitch)
             ctx.simulate_relight(o, d, art, rows, cols, rt.Light(**L))
             ctx.synchronize()
-            assert bool((base[:, cols * 3:] == 0x5A).all()), "padding bytes written"
-            _check(down(art), relight(orig, depth, L), (rows, name, L["kind"]))
+            assert_padding_untouched(base, cols)
+            assert_same_image(down(art), relight(orig, depth, L), (rows, name, L["kind"]))
 
 
 @pytest.mark.parametrize("cols", [37, 1030])
 def test_padding_bytes_stay_untouched(ctx, cols):
     rows, pitch = 5, cols * 3 + 13
-    orig, depth = _inputs(rows, cols, 8)
+    orig, depth = random_inputs(rows, cols, 8)
     o, d = up(orig), up(depth)
     for L in _lights(rows, cols, 1.0)[1:4]:
-        base = torch.full((rows, pitch), 0x5A, dtype=torch.uint8, device="cuda:0")
-        art = base[:, :cols * 3].unflatten(1, (cols, 3))
+        base, art = padded_artistic(rows, cols, pitch)
         ctx.simulate_relight(o, d, art, rows, cols, rt.Light(**L))
         ctx.synchronize()
-        b = base.cpu().numpy()
-        assert (b[:, cols * 3:] == 0x5A).all()
-        _check(b[:, :cols * 3].reshape(rows, cols, 3), relight(orig, depth, L), L)
+        assert_padding_untouched(base, cols)
+        assert_same_image(down(art), relight(orig, depth, L), L)
 
 
 def test_fp_contraction_does_not_change_the_bytes(ctx):
     rows, cols = 16, 1500
-    orig, depth = _inputs(rows, cols, 9)
+    orig, depth = random_inputs(rows, cols, 9)
     o, d = up(orig), up(depth)
     for L in _lights(rows, cols, 3.0):
         try:
@@ -206,74 +159,43 @@ def test_fp_contraction_does_not_change_the_bytes(ctx):
         finally:
             ctx.set_option(rt.OPT_FP_CONTRACT, 1)
         assert np.array_equal(outs[0], outs[1])
-        _check(outs[0], relight(orig, depth, L), "contraction")
+        assert_same_image(outs[0], relight(orig, depth, L), "contraction")
 
 
 def test_anchor_pixel_is_read_behind_an_unsynchronised_estimate():
-    bgr, ann, _ = load_pair("Dog")
-    rows, cols = bgr.shape[:2]
-    with rt.Context(0) as c:
-        c.GPULoadWeights(0.4)
-        _estimate(c, bgr, ann)
-        first = c.pyramid_download(rt.IMG_DEPTH, 0)
-        ys, xs = np.nonzero((first > 60) & (first < 200))
-        y, x = int(ys[len(ys) // 2]), int(xs[len(xs) // 2])
-        d = _estimate(c, bgr, ann)                                          # a new image: the same estimate again, from a cold start
-        o = up(bgr)
-        a1, a2 = up(np.zeros_like(bgr)), up(np.zeros_like(bgr))
-        L = light(POINT, x, y, 60, anchorX=x, anchorY=y, radius=150, relief=2, ambient=0.2, diffuse=2.0)
-        c.simulate_relight(o, d, a1, rows, cols, rt.Light(**L))            # no synchronisation since the estimate was queued
-        c.synchronize()
-        depth = c.pyramid_download(rt.IMG_DEPTH, 0)
-        fv = float(depth[y, x])
-        assert 60.0 < fv < 200.0
-        L2 = dict(L, anchorX=-1, anchorY=-1, anchorDepth=fv)
-        c.simulate_relight(o, d, a2, rows, cols, rt.Light(**L2))
-        c.synchronize()
-        assert np.array_equal(down(a1), down(a2))
-        _check(down(a1), relight(bgr, depth, L), "pixel form")
-        assert not np.array_equal(down(a1), bgr)
+    def over(x, y):
+        return light(POINT, x, y, 60, anchorX=x, anchorY=y, radius=150, relief=2, ambient=0.2, diffuse=2.0)
+
+    def call(c, o, d, art, x, y, value=None):
+        rows, cols = o.shape[:2]
+        L = over(x, y) if value is None else dict(over(x, y), anchorX=-1, anchorY=-1, anchorDepth=value)
+        c.simulate_relight(o, d, art, rows, cols, rt.Light(**L))
+
+    bgr, depth, x, y, _, image = pixel_form_behind_estimate(call)
+    assert_same_image(image, relight(bgr, depth, over(x, y)), "pixel form")
+    assert not np.array_equal(image, bgr)
 
 
 def test_relight_is_replayed_after_a_healed_solve():
-    from realtimedepthdiffusion_amd.synth import make_problem
     rows, cols = 270, 480
-    p = make_problem(rows, cols, seed=6)
-    orig = _inputs(rows, cols, 2)[0]
+    orig = random_inputs(rows, cols, 2)[0]
     L1 = light(POINT, 100, 200, 40, anchorX=100, anchorY=200, radius=120, relief=2, ambient=0.2, diffuse=2.0, color=(255, 220, 180))
     L2 = light(DIRECTIONAL, 1, -2, 1.5, relief=3, ambient=0.1, diffuse=1.25)
 
-    def run(force):
-        c = rt.Context(0)
-        try:
-            c.GPUAllocateDeviceMemory(rows, cols, 1); c.GPULoadWeights(0.4)
-            d, m, g = up(p["depth"]), up(p["mask"]), up(p["gray"])
-            o = up(orig)
-            a1, a2 = up(np.zeros_like(orig)), up(np.zeros_like(orig))
-            if force:
-                c.set_option(rt.OPT_DEBUG_FORCE_STATUS, 1)
-            c.GPUMatrixFreeSolver(d, m, g, rows, cols, 0.4, 24, 0.0, 0)
-            light1 = rt.Light(**L1)
-            c.simulate_relight(o, d, a1, rows, cols, light1)
-            light1.kind, light1.relief, light1.x = 7, -1.0, float("nan")   # the call has read the light: the record holds it by value
-            c.simulate_relight(o, d, a2, rows, cols, rt.Light(**L2))
-            c.synchronize()
-            assert c.get_option(rt.OPT_TIMEOUT_HEALS) == (1 if force else 0)
-            return down(d), down(a1), down(a2)
-        finally:
-            c.close()
+    def queue(c, o, d, arts):
+        light1 = rt.Light(**L1)
+        c.simulate_relight(o, d, arts[0], rows, cols, light1)
+        light1.kind, light1.relief, light1.x = 7, -1.0, float("nan")   # the call has read the light: the record holds it by value
+        c.simulate_relight(o, d, arts[1], rows, cols, rt.Light(**L2))
 
-    clean, healed = run(False), run(True)
-    assert not np.array_equal(clean[0], p["depth"])
-    for w, g in zip(clean, healed):
-        assert np.array_equal(g, w)
-    _check(healed[1], relight(orig, clean[0], L1), "healed point light")
-    _check(healed[2], relight(orig, clean[0], L2), "healed directional light")
+    solved, healed = clean_and_healed(queue, 2, orig)
+    assert_same_image(healed[0], relight(orig, solved, L1), "healed point light")
+    assert_same_image(healed[1], relight(orig, solved, L2), "healed directional light")
 
 
 def test_invalid_arguments_are_refused_on_the_host():
     rows, cols = 40, 60
-    orig, depth = _inputs(rows, cols, 1)
+    orig, depth = random_inputs(rows, cols, 1)
     sentinel = np.full_like(orig, 77)
     nan, inf = float("nan"), float("inf")
     with rt.Context(0) as c:
@@ -301,18 +223,7 @@ def test_invalid_arguments_are_refused_on_the_host():
             c.simulate_relight(o, d, art, 0, cols, rt.Light(relief=100.0))      # the parameters are checked before the empty return
         assert e.value.status == 1
         c.simulate_relight(o, d, o, 0, cols, rt.Light())                        # ... and the in-place rule after it
-        L = rt.lib()
-        op, dp, ap = C.c_size_t(o.stride(0)), C.c_size_t(d.stride(0) * 4), C.c_size_t(art.stride(0))
-        po, pd, pa = C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()), C.c_void_p(art.data_ptr())
-        li = C.byref(rt.Light())
-        assert L.rtdd_simulate_relight(c._h, None, op, pd, dp, pa, ap, rows, cols, li) == 1
-        assert L.rtdd_simulate_relight(c._h, po, op, None, dp, pa, ap, rows, cols, li) == 1
-        assert L.rtdd_simulate_relight(c._h, po, op, pd, dp, None, ap, rows, cols, li) == 1
-        assert L.rtdd_simulate_relight(c._h, po, op, pd, dp, pa, C.c_size_t(cols * 3 - 1), rows, cols, li) == 1
-        assert L.rtdd_simulate_relight(c._h, po, C.c_size_t(cols * 3 - 1), pd, dp, pa, ap, rows, cols, li) == 1
-        assert L.rtdd_simulate_relight(c._h, po, op, pd, C.c_size_t(cols * 4 - 4), pa, ap, rows, cols, li) == 1
-        assert L.rtdd_simulate_relight(c._h, po, op, pd, dp, pa, ap, 40000, 40000, li) == 1
-        assert L.rtdd_simulate_relight(None, po, op, pd, dp, pa, ap, rows, cols, li) == 1
+        assert_bad_images_refused(c, rt.lib().rtdd_simulate_relight, o, d, art, rows, cols, (C.byref(rt.Light()),))
         c.synchronize()
         assert np.array_equal(down(art), sentinel)                             # nothing was launched
         # the bounds themselves are admitted; a directional light ignores the point light's fields but for their finiteness
@@ -324,16 +235,10 @@ def test_invalid_arguments_are_refused_on_the_host():
 
 
 def test_harness_writes_the_restatements_image(tmp_path):
-    from PIL import Image
-    if not os.path.exists(BIN):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "harness")])
-    bgr, ann, _ = load_pair("WomanParasol")
-    rows, cols = bgr.shape[:2]
-    Image.fromarray(np.ascontiguousarray(bgr[..., ::-1]), "RGB").save(tmp_path / "img.png")
-    Image.fromarray(ann, "L").save(tmp_path / "ann.png")
+    bgr, ann = harness_pair(tmp_path, "png")
     with rt.Context(0) as c:                                                   # the harness's own depth map: the same estimate
         c.GPULoadWeights(0.4)
-        _estimate(c, bgr, ann)
+        estimate(c, bgr, ann)
         c.synchronize()
         depth = c.pyramid_download(rt.IMG_DEPTH, 0)
         depth_u8 = c.pyramid_download(rt.IMG_DEPTH_U8, 0)
@@ -346,18 +251,13 @@ def test_harness_writes_the_restatements_image(tmp_path):
              ([], light(DIRECTIONAL, -1, -1, 1, relief=2, ambient=0.25, diffuse=1)),
              (["--light-dir", "2,0.5,1", "--relief", "1"], light(DIRECTIONAL, 2, 0.5, 1, relief=1, ambient=0.25, diffuse=1))]
     for args, L in cases:
-        out = subprocess.check_output([BIN, "-i", str(tmp_path / "img.png"), "-a", str(tmp_path / "ann.png"), "-o", str(tmp_path) + "/",
-                                       "--effect", "relight", "--png"] + args, text=True)
-        assert "Saving images" in out
-        assert np.array_equal(np.array(Image.open(tmp_path / "DepthMap.png")), depth_u8)
-        got = np.array(Image.open(tmp_path / "ArtisticEffect.png"))[..., ::-1]
+        _, got, depth_map = run_harness(tmp_path, "png", ["--effect", "relight"] + args)
+        assert np.array_equal(depth_map, depth_u8)
         want = relight(bgr, depth, L)
-        _check(got, want, args)
+        assert_same_image(got, want, args)
         assert (got != bgr).any(-1).mean() > 0.5                               # a visible result
 
 
 def test_harness_refuses_live_with_relight():
-    if not os.path.exists(BIN):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "harness")])
-    r = subprocess.run([BIN, "-i", "unused.ppm", "--live", "3", "--effect", "relight"], capture_output=True, text=True)
+    r = subprocess.run([harness_bin(), "-i", "unused.ppm", "--live", "3", "--effect", "relight"], capture_output=True, text=True)
     assert r.returncode != 0 and "not supported with --live" in r.stdout

@@ -4,39 +4,22 @@ forms of the anchor, hard and soft shadows, 1 to 1024 steps, NaN and out-of-rang
 bytes; FP contraction; the identities; the anchor pixel read on the device behind an estimate; the heal log; the host-side refusals; the
 harness.  No tolerance anywhere: every operation of the header is a correctly rounded IEEE one."""
 import ctypes as C
-import os
 import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
-import torch
 
 import realtimedepthdiffusion_amd as rt
-from dataset_util import load_pair
+from effect_gpu import ctx, dog_depth  # noqa: F401
+from effect_gpu import (assert_bad_images_refused, assert_padding_untouched, assert_same_image, clean_and_healed, estimate, harness_bin,
+                        harness_files, harness_pair, padded_artistic, pixel_form_behind_estimate, random_inputs, run_harness, tile_mirrored)
 from gpu_util import down, up
 from relight_ref import DIRECTIONAL, POINT, apply_gain, light, relight, shade
 from shadow_ref import relight_shadowed, shadow, shadow_q
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "harness", "rtdd_harness")
 F = np.float32
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    c = rt.Context(0)
-    yield c
-    c.close()
-
-
-def _inputs(rows, cols, seed):
-    rng = np.random.default_rng(seed)
-    orig = rng.integers(0, 256, (rows, cols, 3), dtype=np.uint8)
-    depth = rng.uniform(-20, 275, (rows, cols)).astype(np.float32)
-    depth[rng.random((rows, cols)) < 0.03] = np.nan
-    return orig, depth
 
 
 def _run(c, o, d, rows, cols, L, S, align=512):
@@ -51,10 +34,6 @@ def _relight(c, o, d, rows, cols, L):
     c.simulate_relight(o, d, art, rows, cols, rt.Light(**L))
     c.synchronize()
     return down(art)
-
-
-def _check(got, want, what):
-    assert np.array_equal(got, want), f"{what}: {int((got != want).any(-1).sum())} of {got.shape[0] * got.shape[1]} pixels differ"
 
 
 def _lights(rows, cols, relief):
@@ -79,43 +58,43 @@ def _shadows():
                                          ((3, 2051), 512), ((6, 1024), 512), ((5, 255), 4), ((9, 1027), 512)])
 def test_small_shapes_bit_exact(ctx, shape, align):
     rows, cols = shape
-    orig, depth = _inputs(rows, cols, rows * 1000 + cols)
+    orig, depth = random_inputs(rows, cols, rows * 1000 + cols)
     o, d = up(orig, align), up(depth, align)
     for relief in (0.5, 64.0):
         for L in _lights(rows, cols, relief):
             for S in _shadows():
-                _check(_run(ctx, o, d, rows, cols, L, S, align), relight_shadowed(orig, depth, L, S), (shape, align, L, S))
+                assert_same_image(_run(ctx, o, d, rows, cols, L, S, align), relight_shadowed(orig, depth, L, S), (shape, align, L, S))
 
 
 def test_tall_shapes_and_vertical_marches(ctx):
     """More rows than a workgroup holds, marches that cross many rows, a smooth map with long shadows."""
     rows, cols = 150, 203
-    orig = _inputs(rows, cols, 5)[0]
+    orig = random_inputs(rows, cols, 5)[0]
     yy, xx = np.mgrid[0:rows, 0:cols].astype(np.float32)
     depth = (127.5 + 120 * np.sin(xx / 17.0) * np.cos(yy / 11.0)).astype(np.float32)
     o, d = up(orig, 1), up(depth, 1)
     shadowed = 0.0
     for L in _lights(rows, cols, 1.0) + [light(DIRECTIONAL, 0, 1, 0.25, relief=2), light(DIRECTIONAL, 0.5, -1, 2, relief=4)]:
         for S in (shadow(1024, bias=0.125), shadow(200, softness=0.5, strength=0.75)):
-            _check(_run(ctx, o, d, rows, cols, L, S, 1), relight_shadowed(orig, depth, L, S), (L, S))
+            assert_same_image(_run(ctx, o, d, rows, cols, L, S, 1), relight_shadowed(orig, depth, L, S), (L, S))
             shadowed = max(shadowed, float((shadow_q(depth, L, S) > 0).mean()))
     assert 0.2 < shadowed < 1.0
 
 
 def test_out_of_range_and_non_finite_depths(ctx):
     rows, cols = 6, 300
-    orig, depth = _inputs(rows, cols, 21)
+    orig, depth = random_inputs(rows, cols, 21)
     depth[1, ::7] = np.inf; depth[2, ::5] = -np.inf; depth[3, ::3] = 1e30; depth[4, ::2] = -1e30; depth[5] = np.nan
     o, d = up(orig), up(depth)
     for L in _lights(rows, cols, 2.0):
         for S in (shadow(64), shadow(64, bias=1.0, softness=1e-3), shadow(1024, softness=65536.0)):
-            _check(_run(ctx, o, d, rows, cols, L, S), relight_shadowed(orig, depth, L, S), (L, S))
+            assert_same_image(_run(ctx, o, d, rows, cols, L, S), relight_shadowed(orig, depth, L, S), (L, S))
 
 
 def test_extreme_parameters(ctx):
     """The bounds of the ranges; a direction whose m is tiny (an infinite rise: nothing is shadowed); a denormal softness."""
     rows, cols = 12, 140
-    orig, depth = _inputs(rows, cols, 23)
+    orig, depth = random_inputs(rows, cols, 23)
     o, d = up(orig), up(depth)
     cases = [(light(DIRECTIONAL, 1e-30, 0, 1, relief=64), shadow(1024)),
              (light(DIRECTIONAL, 1e-42, -1e-43, 1, relief=64), shadow(1024, softness=1e-40)),
@@ -125,39 +104,39 @@ def test_extreme_parameters(ctx):
              (light(POINT, 32767, -32768, 65536, anchorDepth=0, radius=65536, relief=64), shadow(1024, softness=0.5)),
              (light(POINT, 70.0, 6.0, 1e-30, anchorDepth=255, radius=10, relief=64), shadow(1024, bias=1e-30))]
     for L, S in cases:
-        _check(_run(ctx, o, d, rows, cols, L, S), relight_shadowed(orig, depth, L, S), (L, S))
+        assert_same_image(_run(ctx, o, d, rows, cols, L, S), relight_shadowed(orig, depth, L, S), (L, S))
 
 
 def test_identities_on_the_device(ctx):
     rows, cols = 33, 700
-    orig, depth = _inputs(rows, cols, 22)
+    orig, depth = random_inputs(rows, cols, 22)
     o, d = up(orig), up(depth)
     for L in _lights(rows, cols, 1.5):
         want = _relight(ctx, o, d, rows, cols, L)                       # rtdd_simulate_relight's own output
-        _check(want, relight(orig, depth, L), "relight")
+        assert_same_image(want, relight(orig, depth, L), "relight")
         for S in (shadow(0), shadow(0, bias=3, softness=2, strength=0.5), shadow(64, strength=0.0)):
-            _check(_run(ctx, o, d, rows, cols, L, S), want, ("no shadow", L, S))
+            assert_same_image(_run(ctx, o, d, rows, cols, L, S), want, ("no shadow", L, S))
         if L["kind"] == DIRECTIONAL:
             assert not np.array_equal(_run(ctx, o, d, rows, cols, L, shadow(64)), want)
     # a light straight above: m == 0
     L = light(DIRECTIONAL, 0, 0, 3, relief=7, ambient=0.1, diffuse=1)
-    _check(_run(ctx, o, d, rows, cols, L, shadow(1024)), _relight(ctx, o, d, rows, cols, L), "m == 0")
+    assert_same_image(_run(ctx, o, d, rows, cols, L, shadow(1024)), _relight(ctx, o, d, rows, cols, L), "m == 0")
     # a constant map under lights that do not stand below it
     const = np.full((rows, cols), 93.5, np.float32)
     dc = up(const)
     for L in (light(DIRECTIONAL, -1, 0.25, 0.001, relief=64), light(POINT, 40.5, 2.5, 1e-3, anchorX=17, anchorY=3, radius=60, relief=64)):
         for S in (shadow(1024), shadow(1024, softness=1e-6)):
-            _check(_run(ctx, o, dc, rows, cols, L, S), _relight(ctx, o, dc, rows, cols, L), ("constant", L, S))
+            assert_same_image(_run(ctx, o, dc, rows, cols, L, S), _relight(ctx, o, dc, rows, cols, L), ("constant", L, S))
     # mirror
     of, df = up(np.ascontiguousarray(orig[:, ::-1])), up(np.ascontiguousarray(depth[:, ::-1]))
     common = dict(relief=1.5, ambient=0.125, diffuse=1.0, color=(255, 200, 90))
     S = shadow(100, bias=0.5, softness=0.5, strength=0.75)
     a = _run(ctx, o, d, rows, cols, light(POINT, 40.5, 2.5, 30, anchorX=17, anchorY=3, radius=60, **common), S)
     b = _run(ctx, of, df, rows, cols, light(POINT, cols - 1 - 40.5, 2.5, 30, anchorX=cols - 1 - 17, anchorY=3, radius=60, **common), S)
-    _check(b, a[:, ::-1], "mirror, point")
+    assert_same_image(b, a[:, ::-1], "mirror, point")
     a = _run(ctx, o, d, rows, cols, light(DIRECTIONAL, 1.25, -0.5, 0.75, **common), S)
     b = _run(ctx, of, df, rows, cols, light(DIRECTIONAL, -1.25, -0.5, 0.75, **common), S)
-    _check(b, a[:, ::-1], "mirror, directional")
+    assert_same_image(b, a[:, ::-1], "mirror, directional")
 
 
 def test_known_answer_on_the_device(ctx):
@@ -171,29 +150,6 @@ def test_known_answer_on_the_device(ctx):
     for steps, last in ((1024, 118), (50, 69)):
         out = _run(ctx, o, d, rows, cols, L, shadow(steps))
         assert (out[:, 20:last + 1] == 50).all() and np.array_equal(out[:, last + 1:], lit[:, last + 1:]) and np.array_equal(out[:, :20], lit[:, :20])
-
-
-def _estimate(c, bgr, ann):
-    rows, cols = bgr.shape[:2]
-    c.pyramid_create(rows, cols)
-    c.pyramid_set_image(up(bgr)); c.pyramid_set_annotation(up(ann))
-    c.estimate_depth(1000)
-    return c.pyramid_image(rt.IMG_DEPTH, 0)
-
-
-def _tile(a, rows, cols):
-    a2 = np.concatenate([a, a[:, ::-1]], 1); a4 = np.concatenate([a2, a2[::-1]], 0)
-    return np.ascontiguousarray(np.tile(a4, (-(-rows // a4.shape[0]), -(-cols // a4.shape[1])))[:rows, :cols])
-
-
-@pytest.fixture(scope="module")
-def dog_depth():
-    bgr, ann, _ = load_pair("Dog")
-    with rt.Context(0) as c:
-        c.GPULoadWeights(0.4)
-        _estimate(c, bgr, ann)
-        c.synchronize()
-        return c.pyramid_download(rt.IMG_DEPTH, 0)
 
 
 def _restate_rows(orig, depth, L, S, y0, y1, workers=16):
@@ -211,7 +167,7 @@ def _restate_rows(orig, depth, L, S, y0, y1, workers=16):
 def test_full_size(ctx, dog_depth, rows, cols, band):
     rng = np.random.default_rng(rows)
     orig = rng.integers(0, 256, (rows, cols, 3), dtype=np.uint8)
-    depth = _tile(dog_depth, rows, cols)
+    depth = tile_mirrored(dog_depth, rows, cols)
     o, d = up(orig), up(depth)
     cases = [(light(DIRECTIONAL, -1, -1, 1, relief=2, ambient=0.25, diffuse=1.0), shadow(256)),
              (light(POINT, cols * 0.4, rows * 0.3, 120, anchorX=cols // 2, anchorY=rows // 2, radius=cols / 4, relief=1.5, ambient=0.1, diffuse=3.0,
@@ -221,36 +177,33 @@ def test_full_size(ctx, dog_depth, rows, cols, band):
     y0, y1 = band
     for L, S in cases:
         pitch = cols * 3 + 512
-        base = torch.full((rows, pitch), 0x5A, dtype=torch.uint8, device="cuda:0")
-        art = base[:, :cols * 3].unflatten(1, (cols, 3))
+        base, art = padded_artistic(rows, cols, pitch)
         ctx.simulate_relight_shadowed(o, d, art, rows, cols, rt.Light(**L), rt.Shadow(**S))
         ctx.synchronize()
-        assert bool((base[:, cols * 3:] == 0x5A).all()), "padding bytes written"
+        assert_padding_untouched(base, cols)
         want, share = _restate_rows(orig, depth, L, S, y0, y1)
         print(f"{rows} x {cols} rows {y0}-{y1} kind {L['kind']} softness {S['softness']}: {share:.3f} of the pixels shadowed")
         assert 0.0 < share < 1.0
-        _check(down(art)[y0:y1], want, (rows, L["kind"], S))
+        assert_same_image(down(art)[y0:y1], want, (rows, L["kind"], S))
 
 
 @pytest.mark.parametrize("cols", [37, 1030])
 def test_padding_bytes_stay_untouched(ctx, cols):
     rows, pitch = 5, cols * 3 + 13
-    orig, depth = _inputs(rows, cols, 8)
+    orig, depth = random_inputs(rows, cols, 8)
     o, d = up(orig), up(depth)
     for L in _lights(rows, cols, 1.0)[1:5]:
         S = shadow(64, softness=0.5)
-        base = torch.full((rows, pitch), 0x5A, dtype=torch.uint8, device="cuda:0")
-        art = base[:, :cols * 3].unflatten(1, (cols, 3))
+        base, art = padded_artistic(rows, cols, pitch)
         ctx.simulate_relight_shadowed(o, d, art, rows, cols, rt.Light(**L), rt.Shadow(**S))
         ctx.synchronize()
-        b = base.cpu().numpy()
-        assert (b[:, cols * 3:] == 0x5A).all()
-        _check(b[:, :cols * 3].reshape(rows, cols, 3), relight_shadowed(orig, depth, L, S), L)
+        assert_padding_untouched(base, cols)
+        assert_same_image(down(art), relight_shadowed(orig, depth, L, S), L)
 
 
 def test_fp_contraction_does_not_change_the_bytes(ctx):
     rows, cols = 16, 1500
-    orig, depth = _inputs(rows, cols, 9)
+    orig, depth = random_inputs(rows, cols, 9)
     o, d = up(orig), up(depth)
     for L in _lights(rows, cols, 3.0):
         for S in (shadow(64, bias=0.5), shadow(64, softness=0.75, strength=0.5)):
@@ -262,78 +215,48 @@ def test_fp_contraction_does_not_change_the_bytes(ctx):
             finally:
                 ctx.set_option(rt.OPT_FP_CONTRACT, 1)
             assert np.array_equal(outs[0], outs[1])
-            _check(outs[0], relight_shadowed(orig, depth, L, S), "contraction")
+            assert_same_image(outs[0], relight_shadowed(orig, depth, L, S), "contraction")
 
 
 def test_anchor_pixel_is_read_behind_an_unsynchronised_estimate():
-    bgr, ann, _ = load_pair("Dog")
-    rows, cols = bgr.shape[:2]
-    with rt.Context(0) as c:
-        c.GPULoadWeights(0.4)
-        _estimate(c, bgr, ann)
-        first = c.pyramid_download(rt.IMG_DEPTH, 0)
-        ys, xs = np.nonzero((first > 60) & (first < 200))
-        y, x = int(ys[len(ys) // 2]), int(xs[len(xs) // 2])
-        d = _estimate(c, bgr, ann)                                          # a new image: the same estimate again, from a cold start
-        o = up(bgr)
-        a1, a2 = up(np.zeros_like(bgr)), up(np.zeros_like(bgr))
-        L = light(POINT, x, y, 60, anchorX=x, anchorY=y, radius=150, relief=2, ambient=0.2, diffuse=2.0)
-        S = shadow(128, bias=0.5, softness=0.5)
-        c.simulate_relight_shadowed(o, d, a1, rows, cols, rt.Light(**L), rt.Shadow(**S))     # no synchronisation since the estimate was queued
-        c.synchronize()
-        depth = c.pyramid_download(rt.IMG_DEPTH, 0)
-        fv = float(depth[y, x])
-        assert 60.0 < fv < 200.0
-        L2 = dict(L, anchorX=-1, anchorY=-1, anchorDepth=fv)
-        c.simulate_relight_shadowed(o, d, a2, rows, cols, rt.Light(**L2), rt.Shadow(**S))
-        c.synchronize()
-        assert np.array_equal(down(a1), down(a2))
-        _check(down(a1), relight_shadowed(bgr, depth, L, S), "pixel form")
-        assert not np.array_equal(down(a1), relight(bgr, depth, L))
+    S = shadow(128, bias=0.5, softness=0.5)
+
+    def over(x, y):
+        return light(POINT, x, y, 60, anchorX=x, anchorY=y, radius=150, relief=2, ambient=0.2, diffuse=2.0)
+
+    def call(c, o, d, art, x, y, value=None):
+        rows, cols = o.shape[:2]
+        L = over(x, y) if value is None else dict(over(x, y), anchorX=-1, anchorY=-1, anchorDepth=value)
+        c.simulate_relight_shadowed(o, d, art, rows, cols, rt.Light(**L), rt.Shadow(**S))
+
+    bgr, depth, x, y, _, image = pixel_form_behind_estimate(call)
+    assert_same_image(image, relight_shadowed(bgr, depth, over(x, y), S), "pixel form")
+    assert not np.array_equal(image, relight(bgr, depth, over(x, y)))
 
 
 def test_shadowed_relight_is_replayed_after_a_healed_solve():
-    from realtimedepthdiffusion_amd.synth import make_problem
     rows, cols = 270, 480
-    p = make_problem(rows, cols, seed=6)
-    orig = _inputs(rows, cols, 2)[0]
+    orig = random_inputs(rows, cols, 2)[0]
     L1 = light(POINT, 100, 200, 40, anchorX=100, anchorY=200, radius=120, relief=2, ambient=0.2, diffuse=2.0, color=(255, 220, 180))
     L2 = light(DIRECTIONAL, 1, -2, 1.5, relief=3, ambient=0.1, diffuse=1.25)
     S1, S2 = shadow(96, bias=0.5, softness=0.5, strength=0.875), shadow(200)
 
-    def run(force):
-        c = rt.Context(0)
-        try:
-            c.GPUAllocateDeviceMemory(rows, cols, 1); c.GPULoadWeights(0.4)
-            d, m, g = up(p["depth"]), up(p["mask"]), up(p["gray"])
-            o = up(orig)
-            a1, a2 = up(np.zeros_like(orig)), up(np.zeros_like(orig))
-            if force:
-                c.set_option(rt.OPT_DEBUG_FORCE_STATUS, 1)
-            c.GPUMatrixFreeSolver(d, m, g, rows, cols, 0.4, 24, 0.0, 0)
-            light1, shadow1 = rt.Light(**L1), rt.Shadow(**S1)
-            c.simulate_relight_shadowed(o, d, a1, rows, cols, light1, shadow1)
-            light1.kind, light1.relief, light1.x = 7, -1.0, float("nan")   # the call has read both: the record holds them by value
-            shadow1.maxSteps, shadow1.bias, shadow1.strength = -5, float("nan"), 9.0
-            c.simulate_relight_shadowed(o, d, a2, rows, cols, rt.Light(**L2), rt.Shadow(**S2))
-            c.synchronize()
-            assert c.get_option(rt.OPT_TIMEOUT_HEALS) == (1 if force else 0)
-            return down(d), down(a1), down(a2)
-        finally:
-            c.close()
+    def queue(c, o, d, arts):
+        light1, shadow1 = rt.Light(**L1), rt.Shadow(**S1)
+        c.simulate_relight_shadowed(o, d, arts[0], rows, cols, light1, shadow1)
+        light1.kind, light1.relief, light1.x = 7, -1.0, float("nan")   # the call has read both: the record holds them by value
+        shadow1.maxSteps, shadow1.bias, shadow1.strength = -5, float("nan"), 9.0
+        c.simulate_relight_shadowed(o, d, arts[1], rows, cols, rt.Light(**L2), rt.Shadow(**S2))
 
-    clean, healed = run(False), run(True)
-    assert not np.array_equal(clean[0], p["depth"])
-    for w, g in zip(clean, healed):
-        assert np.array_equal(g, w)
-    _check(healed[1], relight_shadowed(orig, clean[0], L1, S1), "healed point light")
-    _check(healed[2], relight_shadowed(orig, clean[0], L2, S2), "healed directional light")
-    assert not np.array_equal(healed[2], relight(orig, clean[0], L2))
+    solved, healed = clean_and_healed(queue, 2, orig)
+    assert_same_image(healed[0], relight_shadowed(orig, solved, L1, S1), "healed point light")
+    assert_same_image(healed[1], relight_shadowed(orig, solved, L2, S2), "healed directional light")
+    assert not np.array_equal(healed[1], relight(orig, solved, L2))
 
 
 def test_invalid_arguments_are_refused_on_the_host():
     rows, cols = 40, 60
-    orig, depth = _inputs(rows, cols, 1)
+    orig, depth = random_inputs(rows, cols, 1)
     sentinel = np.full_like(orig, 77)
     nan, inf = float("nan"), float("inf")
     with rt.Context(0) as c:
@@ -364,19 +287,7 @@ def test_invalid_arguments_are_refused_on_the_host():
             c.simulate_relight_shadowed(o, d, art, 0, cols, rt.Light(), rt.Shadow(maxSteps=2000))   # the parameters are checked before the empty return
         assert e.value.status == 1
         c.simulate_relight_shadowed(o, d, o, 0, cols, rt.Light(), rt.Shadow())  # ... and the in-place rule after it
-        lib = rt.lib()
-        op, dp, ap = C.c_size_t(o.stride(0)), C.c_size_t(d.stride(0) * 4), C.c_size_t(art.stride(0))
-        po, pd, pa = C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()), C.c_void_p(art.data_ptr())
-        li, sh = C.byref(rt.Light()), C.byref(rt.Shadow())
-        f = lib.rtdd_simulate_relight_shadowed
-        assert f(c._h, None, op, pd, dp, pa, ap, rows, cols, li, sh) == 1
-        assert f(c._h, po, op, None, dp, pa, ap, rows, cols, li, sh) == 1
-        assert f(c._h, po, op, pd, dp, None, ap, rows, cols, li, sh) == 1
-        assert f(c._h, po, op, pd, dp, pa, C.c_size_t(cols * 3 - 1), rows, cols, li, sh) == 1
-        assert f(c._h, po, C.c_size_t(cols * 3 - 1), pd, dp, pa, ap, rows, cols, li, sh) == 1
-        assert f(c._h, po, op, pd, C.c_size_t(cols * 4 - 4), pa, ap, rows, cols, li, sh) == 1
-        assert f(c._h, po, op, pd, dp, pa, ap, 40000, 40000, li, sh) == 1
-        assert f(None, po, op, pd, dp, pa, ap, rows, cols, li, sh) == 1
+        assert_bad_images_refused(c, rt.lib().rtdd_simulate_relight_shadowed, o, d, art, rows, cols, (C.byref(rt.Light()), C.byref(rt.Shadow())))
         c.synchronize()
         assert np.array_equal(down(art), sentinel)                             # nothing was launched
         for kw in (dict(maxSteps=1024, bias=65536.0, softness=65536.0, strength=1.0), dict(maxSteps=0, bias=0.0, softness=0.0, strength=0.0)):
@@ -386,15 +297,10 @@ def test_invalid_arguments_are_refused_on_the_host():
 
 
 def test_harness_writes_the_restatements_image(tmp_path):
-    from PIL import Image
-    if not os.path.exists(BIN):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "harness")])
-    bgr, ann, _ = load_pair("WomanParasol")
-    Image.fromarray(np.ascontiguousarray(bgr[..., ::-1]), "RGB").save(tmp_path / "img.png")
-    Image.fromarray(ann, "L").save(tmp_path / "ann.png")
+    bgr, ann = harness_pair(tmp_path, "png")
     with rt.Context(0) as c:                                                   # the harness's own depth map: the same estimate
         c.GPULoadWeights(0.4)
-        _estimate(c, bgr, ann)
+        estimate(c, bgr, ann)
         c.synchronize()
         depth = c.pyramid_download(rt.IMG_DEPTH, 0)
     x, y = 300, 200
@@ -406,29 +312,21 @@ def test_harness_writes_the_restatements_image(tmp_path):
              (["--light-at", f"{x},{y}", "--shadows", "64", "--shadow-softness", "0.25"], point, shadow(64, softness=0.25)),
              (["--shadows", "0"], directional, shadow(0))]
     for args, L, S in cases:
-        out = subprocess.check_output([BIN, "-i", str(tmp_path / "img.png"), "-a", str(tmp_path / "ann.png"), "-o", str(tmp_path) + "/",
-                                       "--effect", "relight", "--png"] + args, text=True)
-        assert "Saving images" in out
-        got = np.array(Image.open(tmp_path / "ArtisticEffect.png"))[..., ::-1]
-        _check(got, relight_shadowed(bgr, depth, L, S), args)
+        got = run_harness(tmp_path, "png", ["--effect", "relight"] + args)[1]
+        assert_same_image(got, relight_shadowed(bgr, depth, L, S), args)
         assert np.array_equal(got, relight(bgr, depth, L)) == (S["maxSteps"] == 0)      # shadows are visible, and --shadows 0 is relight
-    r = subprocess.run([BIN, "-i", str(tmp_path / "img.png"), "-a", str(tmp_path / "ann.png"), "-o", str(tmp_path) + "/", "--effect", "relight",
-                        "--shadows", "2000"], capture_output=True, text=True)
+    r = subprocess.run([harness_bin()] + harness_files(tmp_path, "png") + ["--effect", "relight", "--shadows", "2000"], capture_output=True, text=True)
     assert r.returncode != 0                                                   # refused by the library
 
 
 def test_harness_refuses_live_with_shadows():
-    if not os.path.exists(BIN):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "harness")])
-    r = subprocess.run([BIN, "-i", "unused.ppm", "--live", "3", "--effect", "relight", "--shadows", "64"], capture_output=True, text=True)
+    r = subprocess.run([harness_bin(), "-i", "unused.ppm", "--live", "3", "--effect", "relight", "--shadows", "64"], capture_output=True, text=True)
     assert r.returncode != 0 and "not supported with --live" in r.stdout
 
 
 def test_harness_refuses_stray_shadow_options():
-    if not os.path.exists(BIN):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "harness")])
     for args, said in ((["--effect", "defocus", "--shadows", "64"], "--shadows needs --effect relight"),
                        (["--shadows", "64"], "--shadows needs --effect relight"),
                        (["--effect", "relight", "--shadow-softness", "0.5"], "need --shadows N")):
-        r = subprocess.run([BIN, "-i", "unused.ppm"] + args, capture_output=True, text=True)
+        r = subprocess.run([harness_bin(), "-i", "unused.ppm"] + args, capture_output=True, text=True)
         assert r.returncode == 1 and said in r.stdout, (args, r.returncode, r.stdout)
