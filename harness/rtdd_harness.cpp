@@ -22,6 +22,9 @@
 //                 without a light: the original darkened in creases, or --ao-map: the occlusion as a gray map; default radius 16, 8 directions,
 //                 bias 0, strength 1, relief 2), --effect relight --ao R [--ao-directions ..] [--ao-bias ..] [--ao-strength ..]   (the same call
 //                 under relight's light: its ambient term occluded; not together with --shadows)
+//                 --effect lighting [relight's light flags] [--shadows N] [--shadow-bias ..] [--shadow-softness ..] [--shadow-strength ..] [--ao R]
+//                 [--ao-directions ..] [--ao-bias ..] [--ao-strength ..]   (rtdd_simulate_lighting: shade, cast shadows and the occluded ambient
+//                 term in one call; default 256 steps, radius 16)
 //     key 't'  -> prints "Processing Time"  (main.cpp:320-322; wall clock here, the reference uses clock()); the process's one-time costs
 //                 (~20 ms: code objects, first allocations) are paid by a warm-up on a context of its own first -- --cold leaves it out
 //     --paint x,y,label,radius  = a mouse drag sample (main.cpp:46-62), repeatable; --paint-at F:x,y,label,radius = the same while --live
@@ -209,7 +212,8 @@ struct Job {
     // --relief, --ambient, --diffuse, --light-color
     rtdd_light light = {RTDD_LIGHT_DIRECTIONAL, -1.0f, -1.0f, 1.0f, 0.0f, -1, -1, 200.0f, 2.0f, 0.25f, 1.0f, 255, 255, 255};
     float light_height = 100.0f;
-    // --shadows N (given: rtdd_simulate_relight_shadowed), --shadow-bias, --shadow-softness, --shadow-strength
+    // --shadows N (given: rtdd_simulate_relight_shadowed; --effect lighting: the steps of rtdd_simulate_lighting, 256 when not given), --shadow-bias,
+    // --shadow-softness, --shadow-strength
     bool shadows = false;
     rtdd_shadow shadow = {0, 0.0f, 0.0f, 1.0f};
     // --effect ao, or --effect relight --ao R (ao_lit): rtdd_simulate_ambient_occlusion; --ao-radius / --ao R, --ao-directions, --ao-bias, --ao-strength,
@@ -495,6 +499,15 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
             else if (job.shadows) CK(rtdd_simulate_relight_shadowed(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols, &light, &job.shadow));
             else CK(rtdd_simulate_relight(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols, &light));
         }
+        else if (job.effect == "lighting") {
+            rtdd_light light = job.light;
+            if (light.kind == RTDD_LIGHT_POINT) light.z = job.light_height;
+            rtdd_shadow shadow = job.shadow;
+            if (!job.shadows) shadow.maxSteps = 256;
+            rtdd_ambient_occlusion ao = job.ao;
+            ao.relief = light.relief;
+            CK(rtdd_simulate_lighting(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols, &light, &shadow, &ao));
+        }
         else if (job.effect == "ao") {
             rtdd_ambient_occlusion ao = job.ao;
             ao.relief = job.light.relief;
@@ -512,13 +525,14 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
 }
 
 int main(int argc, const char *argv[]) {
-    if (argc == 1) { std::printf("Usage: rtdd_harness -i image.(jpg|png|ppm) [-a annotation.(png|pgm)] [-o prefix] [--effect defocus|desaturation|haze|refocus|stereo|parallax|relight|ao] [--iters N] [--refine sor|mg|auto [--tolerance T]]\n"
+    if (argc == 1) { std::printf("Usage: rtdd_harness -i image.(jpg|png|ppm) [-a annotation.(png|pgm)] [-o prefix] [--effect defocus|desaturation|haze|refocus|stereo|parallax|relight|ao|lighting] [--iters N] [--refine sor|mg|auto [--tolerance T]]\n"
                                  "                    [--focus D | --focus-at X,Y] [--aperture A] [--bokeh box|disc] (refocus)  [--haze-beta B] [--airlight b,g,r] (haze)\n"
                                  "                    [--disparity D] [--zero-parallax Z | --zero-parallax-at X,Y] [--anaglyph] (stereo)\n"
                                  "                    --shift dx,dy [--dolly z] [--zero-parallax Z | --zero-parallax-at X,Y] (parallax)\n"
                                  "                    [--light-dir x,y,z | --light-at X,Y [--light-height H] [--light-radius R]] [--relief S] [--ambient A] [--diffuse D] [--light-color b,g,r] (relight)\n"
                                  "                    [--shadows N [--shadow-bias B] [--shadow-softness S] [--shadow-strength T]] (relight with cast shadows)\n"
                                  "                    [--ao-radius R] [--ao-directions 4|8] [--ao-bias B] [--ao-strength T] [--relief S] [--ao-map] (ao)  [--ao R [--ao-directions ..] [--ao-bias ..] [--ao-strength ..]] (relight with its ambient term occluded)\n"
+                                 "                    [relight's light flags] [--shadows N (256)] [--shadow-bias B] [--shadow-softness S] [--shadow-strength T] [--ao R (16)] [--ao-directions 4|8] [--ao-bias B] [--ao-strength T] (lighting: shade, cast shadows and occlusion in one call)\n"
                                  "                    [--paint x,y,label,radius]... [--live N [--paint-at frame:x,y,label,radius]...] [--devices D --batch B [--sequential] [--write-all]] [--png] [--cold]\n"
                                  "                    [--stroke x0,y0,x1,y1,label,radius[,round]]... [--erase x0,y0,x1,y1,radius[,round]]...   (segments, in command-line order, one rtdd_paint_strokes call after --paint)\n"
                                  "                    [--stroke-at frame:x0,y0,x1,y1,label,radius[,round]]... [--erase-at frame:x0,y0,x1,y1,radius[,round]]...   (--live: in front of that frame)\n"
@@ -612,17 +626,18 @@ int main(int argc, const char *argv[]) {
         else if (!std::strcmp(argv[i], "-h")) std::printf("Usage:\n -i input image (JPEG, 8-bit PNG, binary PPM)\n -a annotated image (8-bit PNG, binary PGM)\n");
     }
     // cast shadows belong to relight, and their parameters to --shadows: a stray one is refused, not dropped
-    if (job.shadows && job.effect != "relight") { std::printf("--shadows needs --effect relight\n"); return 1; }
-    if (shadow_opt && !job.shadows) { std::printf("--shadow-bias, --shadow-softness and --shadow-strength need --shadows N\n"); return 1; }
+    const bool lighting = job.effect == "lighting";                           // takes --shadows and --ao together, each with its parameters
+    if (job.shadows && job.effect != "relight" && !lighting) { std::printf("--shadows needs --effect relight\n"); return 1; }
+    if (shadow_opt && !job.shadows && !lighting) { std::printf("--shadow-bias, --shadow-softness and --shadow-strength need --shadows N\n"); return 1; }
     // ambient occlusion is --effect ao, or --ao R under --effect relight (without cast shadows: one call renders one or the other); its
     // parameters belong to one of the two: a stray one is refused, not dropped
-    if (job.ao_lit && job.effect != "relight") { std::printf("--ao needs --effect relight (without a light: --effect ao --ao-radius R)\n"); return 1; }
-    if (job.ao_lit && job.shadows) { std::printf("--ao and --shadows cannot be combined: ambient occlusion and cast shadows are separate calls\n"); return 1; }
+    if (job.ao_lit && job.effect != "relight" && !lighting) { std::printf("--ao needs --effect relight (without a light: --effect ao --ao-radius R)\n"); return 1; }
+    if (job.ao_lit && job.shadows && !lighting) { std::printf("--ao and --shadows cannot be combined: ambient occlusion and cast shadows are separate calls (both in one call: --effect lighting)\n"); return 1; }
     if (ao_radius_opt && job.effect != "ao") { std::printf("--ao-radius and --ao-map need --effect ao (under --effect relight: --ao R)\n"); return 1; }
-    if (ao_opt && !job.ao_lit && job.effect != "ao") { std::printf("--ao-directions, --ao-bias and --ao-strength need --ao R or --effect ao\n"); return 1; }
+    if (ao_opt && !job.ao_lit && job.effect != "ao" && !lighting) { std::printf("--ao-directions, --ao-bias and --ao-strength need --ao R or --effect ao\n"); return 1; }
     // a live frame's sticky effect is an effect code without parameters (rtdd_live_submit_ex): the aimed effects are not available there
-    if (live > 0 && (job.effect == "refocus" || job.effect == "stereo" || job.effect == "parallax" || job.effect == "relight" || job.effect == "ao" || (job.effect == "haze" && job.haze_ex))) {
-        std::printf("--live renders the reference's three effects only: --effect refocus, --effect stereo, --effect parallax, --effect relight, --effect ao and --haze-beta / --airlight are not supported with --live\n");
+    if (live > 0 && (job.effect == "refocus" || job.effect == "stereo" || job.effect == "parallax" || job.effect == "relight" || job.effect == "ao" || lighting || (job.effect == "haze" && job.haze_ex))) {
+        std::printf("--live renders the reference's three effects only: --effect refocus, --effect stereo, --effect parallax, --effect relight, --effect ao, --effect lighting and --haze-beta / --airlight are not supported with --live\n");
         return 1;
     }
     Pnm rgb;

@@ -324,7 +324,8 @@ int rtdd_simulate_haze(rtdd_ctx *ctx, const uint8_t *original, size_t originalPi
 /* ---- aimed depth effects (extensions; no reference behaviour) --------------------------------
  * Added after ABI version 230 without a version bump: a host finds them by symbol (dlsym).  The next bump of RTDD_VERSION
  * should cover them (rtdd_simulate_refocus, rtdd_simulate_lens_blur, rtdd_simulate_haze_ex, rtdd_simulate_stereo, rtdd_simulate_relight,
- * rtdd_simulate_relight_shadowed, rtdd_simulate_parallax, rtdd_simulate_ambient_occlusion), together with a parameterised live effect
+ * rtdd_simulate_relight_shadowed, rtdd_simulate_parallax, rtdd_simulate_ambient_occlusion, rtdd_simulate_lighting), together with a
+ * parameterised live effect
  * (rtdd_live_submit_ex takes an effect code only and knows none of them). */
 
 /* Refocus: the defocus effect sharp at a chosen depth instead of at depth 0.
@@ -557,7 +558,8 @@ int rtdd_simulate_parallax(rtdd_ctx *ctx, const uint8_t *original, size_t origin
  * bytes (light != NULL); RTDD_AO_MAP gives 255 everywhere in those cases.  Nothing produces a NaN: rise is finite and inv_j[k] is
  * finite and positive.
  * The output does not depend on RTDD_OPT_FP_CONTRACT; one kernel launch, stream-ordered, deterministic, not in place.  A point light's
- * anchor pixel is read by the kernel on the device, as in rtdd_simulate_relight.  Cast shadows are not combined with it.
+ * anchor pixel is read by the kernel on the device, as in rtdd_simulate_relight.  Cast shadows are not combined with it here:
+ * rtdd_simulate_lighting renders both.
  * Refused on the host (RTDD_ERR_INVALID), before any launch: the rules of the three effects (null pointers, pitches, image size); a
  * null ao; an unknown mode; directions other than 4 or 8; any non-finite field; any field outside the ranges below; RTDD_AO_MAP with a
  * light; with a light, everything rtdd_simulate_relight refuses of it, and ao->relief != light->relief; original == artistic. */
@@ -574,6 +576,35 @@ int rtdd_simulate_ambient_occlusion(rtdd_ctx *ctx, const uint8_t *original, size
                                     const float *depth, size_t depthPitch, uint8_t *artistic, size_t artisticPitch,
                                     int rows, int cols, const rtdd_ambient_occlusion *ao,
                                     const rtdd_light *light /* may be NULL */);   /* both HOST, read before the call returns */
+
+/* Lighting: the WHOLE lighting model in one call -- rtdd_simulate_relight's diffuse shade, rtdd_simulate_relight_shadowed's cast
+ * shadow on it and rtdd_simulate_ambient_occlusion's occlusion of the ambient term: an object that throws a shadow AND sits in a
+ * darkened crease where it meets the ground.  Every call ends in a truncated, clamped uchar, so two calls cannot be composed
+ * afterwards; this one renders the three terms per pixel.  Nothing here is new arithmetic -- every operation is one f32 operation,
+ * rounded once, NONE fused, in the order written; sqrtf and / are IEEE correctly rounded; denormals are kept:
+ *   d', shade, k_c, Lz and every quantity of the light:       exactly rtdd_simulate_relight's
+ *   H(x, y) = relief * (255 - d'(x, y)),  relief = light->relief = ao->relief (the two must agree bit for bit)
+ *   m, sx, sy, rise, n, the march for k = 1 .. n (px, py, ray, occ, q_k), q;  vis = 1 - (shadow->strength * q):
+ *                                                             exactly rtdd_simulate_relight_shadowed's, march included
+ *   inv_j[k], the marches p, rise, t_k, tmax_j, occ_j, s in ascending j, mean;  ao = 1 - (ao->strength * mean):
+ *                                                             exactly rtdd_simulate_ambient_occlusion's
+ * per channel c of B, G, R:
+ *   out_c = (uchar) fminf(o_c * ((ambient * ao) + (k_c * (shade * vis))), 255)          (truncation, as every effect)
+ * The freedoms of the two marches (their early exits, minus infinity outside the image) carry over; they are not part of the rule.
+ * Identities, byte for byte (vis is then exactly 1, ao exactly 1):
+ *   shadow->maxSteps == 0 or shadow->strength == 0:  rtdd_simulate_ambient_occlusion(..., ao, light)'s bytes
+ *   ao->radius == 0 or ao->strength == 0:            rtdd_simulate_relight_shadowed's bytes
+ *   both together:                                   rtdd_simulate_relight's bytes
+ * Nothing produces a NaN (see the two calls).  The output does not depend on RTDD_OPT_FP_CONTRACT; one kernel launch (a disabled term
+ * costs nothing: the launch is then the kernel of what is left), stream-ordered, deterministic, not in place.  A point light's anchor
+ * pixel is read by the kernel on the device, as in rtdd_simulate_relight.  RTDD_VERSION is unchanged: a host finds the symbol by name.
+ * Refused on the host (RTDD_ERR_INVALID), before any launch: everything rtdd_simulate_relight_shadowed refuses of the images, the light
+ * and the shadow; everything rtdd_simulate_ambient_occlusion refuses of ao under a light, ao->relief != light->relief included; a null
+ * light, shadow or ao; ao->mode other than RTDD_AO_SHADE; original == artistic. */
+int rtdd_simulate_lighting(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch,
+                           const float *depth, size_t depthPitch, uint8_t *artistic, size_t artisticPitch,
+                           int rows, int cols, const rtdd_light *light, const rtdd_shadow *shadow,
+                           const rtdd_ambient_occlusion *ao /* all three HOST, read before the call returns */);
 
 /* ---- whole-estimate driver ------------------------------------------------
  * One depth estimate = the loop body of src/main.cpp:232-295, run as a single stream-ordered launch

@@ -54,6 +54,7 @@ C_ABI_SYMBOLS = [
     "rtdd_simulate_refocus", "rtdd_simulate_haze_ex", "rtdd_simulate_stereo", "rtdd_simulate_lens_blur",
     "rtdd_paint_strokes", "rtdd_pyramid_annotation_rebuild",
     "rtdd_simulate_relight", "rtdd_simulate_relight_shadowed", "rtdd_simulate_parallax", "rtdd_simulate_ambient_occlusion",
+    "rtdd_simulate_lighting",
 ]
 IMG_ORIGINAL, IMG_GRAY, IMG_SCRIBBLE, IMG_EDITED, IMG_DEPTH, IMG_DEPTH_U8, IMG_ARTISTIC = range(7)
 EFFECT_NONE, EFFECT_DEFOCUS, EFFECT_DESATURATION, EFFECT_HAZE = range(4)
@@ -426,6 +427,16 @@ class Context:
         self._check(lib().rtdd_simulate_ambient_occlusion(self._h, o, op, d, dp, a, ap, C.c_int(rows), C.c_int(cols),
                                                           C.byref(ao) if ao is not None else None,
                                                           C.byref(light) if light is not None else None))
+
+    def simulate_lighting(self, originalImage, depthImage, artisticImage, rows, cols, light, shadow, ao):
+        """The whole lighting model in one call: simulate_relight's shade under `light`, simulate_relight_shadowed's cast shadows as
+        `shadow` says and simulate_ambient_occlusion's occlusion of the ambient term as `ao` (AO_SHADE, relief the light's) says.  Each
+        may be None for the C call's null pointer."""
+        o, op = _img(originalImage); d, dp = _img(depthImage); a, ap = _img(artisticImage)
+        self._check(lib().rtdd_simulate_lighting(self._h, o, op, d, dp, a, ap, C.c_int(rows), C.c_int(cols),
+                                                 C.byref(light) if light is not None else None,
+                                                 C.byref(shadow) if shadow is not None else None,
+                                                 C.byref(ao) if ao is not None else None))
 
     # ---- whole-estimate driver (src/main.cpp:92-155, 232-295)
     def pyramid_create(self, rows, cols):

@@ -26,12 +26,6 @@ namespace rtdd {
 
 typedef Effect::Occlusion Occlusion;
 
-constexpr int kAoW = 64, kAoH = 16;                                 // the tile: a wave's 64 lanes wide
-constexpr int kAoMaxRadius = 64;
-// inv_j[k] at [k - 1]: the axis directions' and the diagonals'.  They depend on k alone, so they are built once on the host and
-// travel to every launch by value, a replay's included.
-struct AoTables { float axis[kAoMaxRadius], diag[kAoMaxRadius]; };
-
 enum : int { kAoOutShade = 0, kAoOutMap = 1, kAoOutDirectional = 2, kAoOutPoint = 3 };     // the first two are rtdd_ao_mode's
 
 // RMAX: the largest radius the LDS array has a halo for; NW: waves per workgroup; DIRS: 4 or 8; OUT: what is written.
@@ -112,15 +106,6 @@ __global__ __launch_bounds__(64 * NW) void k_ambient_occlusion(const uint8_t *__
 #pragma unroll
         for (int c = 0; c < 3; c++) a[c] = (uint8_t)relight_u8_ambient(L, c, amb, shade, o[c]);
     }
-}
-
-static AoTables ao_tables() {
-    AoTables t;
-    for (int k = 1; k <= kAoMaxRadius; k++) {
-        t.axis[k - 1] = (float)(1.0 / (double)k);
-        t.diag[k - 1] = (float)(1.0 / ((double)k * std::sqrt(2.0)));
-    }
-    return t;
 }
 
 template <int RMAX, int NW>

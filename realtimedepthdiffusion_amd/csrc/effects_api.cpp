@@ -176,13 +176,8 @@ int rtdd_simulate_relight(rtdd_ctx *ctx, const uint8_t *original, size_t origina
     return simulate(ctx, e);
 }
 
-int rtdd_simulate_relight_shadowed(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
-                                   uint8_t *artistic, size_t artisticPitch, int rows, int cols, const rtdd_light *light,
-                                   const rtdd_shadow *shadow) {
-    if (!ctx) return RTDD_ERR_INVALID;
-    Effect e{Effect::kRelightShadow, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols};
-    const int rc = prepare_relight(ctx, e, light);
-    if (rc != RTDD_OK) return rc;
+// The checks of rtdd_simulate_relight_shadowed's shadow, and the march as the kernels take it (e.shadow); e.light is prepared.
+static int prepare_shadow(rtdd_ctx *ctx, Effect &e, const rtdd_shadow *shadow) {
     REQUIRE(ctx, shadow, "null shadow");
     const rtdd_shadow &q = *shadow;
     for (float v : {q.bias, q.softness, q.strength}) REQUIRE(ctx, std::isfinite(v), "a non-finite value in the shadow");
@@ -196,6 +191,18 @@ int rtdd_simulate_relight_shadowed(rtdd_ctx *ctx, const uint8_t *original, size_
         const float m = fmaxf(fabsf(e.light.x), fabsf(e.light.y));
         if (m != 0.0f) { S.sx = e.light.x / m; S.sy = e.light.y / m; S.rise = e.light.z / m; }
     }
+    return RTDD_OK;
+}
+
+int rtdd_simulate_relight_shadowed(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
+                                   uint8_t *artistic, size_t artisticPitch, int rows, int cols, const rtdd_light *light,
+                                   const rtdd_shadow *shadow) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    Effect e{Effect::kRelightShadow, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols};
+    int rc = prepare_relight(ctx, e, light);
+    if (rc != RTDD_OK) return rc;
+    rc = prepare_shadow(ctx, e, shadow);
+    if (rc != RTDD_OK) return rc;
     if (rows == 0 || cols == 0) return RTDD_OK;
     REQUIRE(ctx, original != artistic, "relight cannot run in place");
     return simulate(ctx, e);
@@ -225,14 +232,9 @@ int rtdd_simulate_parallax(rtdd_ctx *ctx, const uint8_t *original, size_t origin
     return simulate(ctx, e);
 }
 
-int rtdd_simulate_ambient_occlusion(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
-                                    uint8_t *artistic, size_t artisticPitch, int rows, int cols, const rtdd_ambient_occlusion *ao,
-                                    const rtdd_light *light) {
-    if (!ctx) return RTDD_ERR_INVALID;
-    Effect e{Effect::kAmbientOcclusion, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols};
-    // the images first, as every effect; then the occlusion; then the light, checked as rtdd_simulate_relight checks it
-    int rc = check_effect(ctx, original, depth, artistic, originalPitch, depthPitch, artisticPitch, rows, cols);
-    if (rc != RTDD_OK) return rc;
+// The checks of rtdd_simulate_ambient_occlusion behind the images', and the occlusion and the light as the kernels take them
+// (e.occlusion, e.light): the occlusion first; then the light, checked as rtdd_simulate_relight checks it.
+static int prepare_occlusion(rtdd_ctx *ctx, Effect &e, const rtdd_ambient_occlusion *ao, const rtdd_light *light) {
     REQUIRE(ctx, ao, "null ao");
     const rtdd_ambient_occlusion &q = *ao;
     REQUIRE(ctx, q.mode == RTDD_AO_SHADE || q.mode == RTDD_AO_MAP, "mode must be RTDD_AO_SHADE or RTDD_AO_MAP");
@@ -247,12 +249,43 @@ int rtdd_simulate_ambient_occlusion(rtdd_ctx *ctx, const uint8_t *original, size
     A.lit = light != nullptr;
     if (light) {
         REQUIRE(ctx, q.mode != RTDD_AO_MAP, "RTDD_AO_MAP takes no light");
-        rc = prepare_relight(ctx, e, light);
+        const int rc = prepare_relight(ctx, e, light);
         if (rc != RTDD_OK) return rc;
         REQUIRE(ctx, std::memcmp(&q.relief, &light->relief, sizeof(float)) == 0, "ao->relief must equal light->relief bit for bit");
     }
+    return RTDD_OK;
+}
+
+int rtdd_simulate_ambient_occlusion(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
+                                    uint8_t *artistic, size_t artisticPitch, int rows, int cols, const rtdd_ambient_occlusion *ao,
+                                    const rtdd_light *light) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    Effect e{Effect::kAmbientOcclusion, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols};
+    // the images first, as every effect
+    int rc = check_effect(ctx, original, depth, artistic, originalPitch, depthPitch, artisticPitch, rows, cols);
+    if (rc != RTDD_OK) return rc;
+    rc = prepare_occlusion(ctx, e, ao, light);
+    if (rc != RTDD_OK) return rc;
     if (rows == 0 || cols == 0) return RTDD_OK;
     REQUIRE(ctx, original != artistic, "ambient occlusion cannot run in place");
+    return simulate(ctx, e);
+}
+
+int rtdd_simulate_lighting(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
+                           uint8_t *artistic, size_t artisticPitch, int rows, int cols, const rtdd_light *light, const rtdd_shadow *shadow,
+                           const rtdd_ambient_occlusion *ao) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    Effect e{Effect::kLighting, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols};
+    // the checks of the two calls it fuses, each by its own function: the images and the light, the shadow, the occlusion under that light
+    int rc = prepare_relight(ctx, e, light);
+    if (rc != RTDD_OK) return rc;
+    rc = prepare_shadow(ctx, e, shadow);
+    if (rc != RTDD_OK) return rc;
+    rc = prepare_occlusion(ctx, e, ao, light);
+    if (rc != RTDD_OK) return rc;
+    REQUIRE(ctx, ao->mode == RTDD_AO_SHADE, "lighting takes RTDD_AO_SHADE only");
+    if (rows == 0 || cols == 0) return RTDD_OK;
+    REQUIRE(ctx, original != artistic, "lighting cannot run in place");
     return simulate(ctx, e);
 }
 

@@ -1,8 +1,10 @@
-// relight_common.hpp -- the shading arithmetic that relight.hip (k_relight), relight_shadow.hip (k_relight_shadow) and
-// ambient_occlusion.hip (k_ambient_occlusion) share: the depth clamp, the shade of one pixel, the byte of one channel.  The header's lines (include/rtdd.h rtdd_simulate_relight), operation by
+// relight_common.hpp -- the shading arithmetic that relight.hip (k_relight), relight_shadow.hip (k_relight_shadow),
+// ambient_occlusion.hip (k_ambient_occlusion) and lighting.hip (k_lighting) share: the depth clamp, the shade of one pixel, the byte of one channel.  The header's lines (include/rtdd.h rtdd_simulate_relight), operation by
 // operation; both translation units are compiled with -ffp-contract=off and hold no fmaf.
 // Included inside no namespace; everything here is in namespace rtdd.
 #pragma once
+
+#include <cmath>
 
 #include "rtdd_internal.hpp"
 
@@ -38,6 +40,22 @@ __device__ __forceinline__ uint32_t relight_u8(const Light &L, int c, float shad
 // the same byte with the ambient term the caller occluded, amb = ambient * ao (rtdd_simulate_ambient_occlusion under a light)
 __device__ __forceinline__ uint32_t relight_u8_ambient(const Light &L, int c, float amb, float shade, uint32_t o) {
     return (uint32_t)(int)fminf((float)o * (amb + (L.k[c] * shade)), 255.0f);
+}
+
+// What ambient_occlusion.hip (k_ambient_occlusion) and lighting.hip (k_lighting) share of the occlusion: the tile, and the tables.
+constexpr int kAoW = 64, kAoH = 16;                                 // the tile: a wave's 64 lanes wide
+constexpr int kAoMaxRadius = 64;
+// inv_j[k] at [k - 1]: the axis directions' and the diagonals'.  They depend on k alone, so they are built once on the host and
+// travel to every launch by value, a replay's included.
+struct AoTables { float axis[kAoMaxRadius], diag[kAoMaxRadius]; };
+
+inline AoTables ao_tables() {
+    AoTables t;
+    for (int k = 1; k <= kAoMaxRadius; k++) {
+        t.axis[k - 1] = (float)(1.0 / (double)k);
+        t.diag[k - 1] = (float)(1.0 / ((double)k * std::sqrt(2.0)));
+    }
+    return t;
 }
 
 }  // namespace rtdd

@@ -95,8 +95,8 @@ struct LiveTargets {
 // One depth effect, arguments checked: what to render, on which images, with which parameters.  Built by the rtdd_simulate_* entry
 // points (effects_api.cpp) and by a live frame (live_effect), launched by launch_effect, and logged by value (PendingOp) to be launched again.
 struct Effect {
-    enum : int { kRefocus = RTDD_EFFECT_HAZE + 1, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow, kParallax, kAmbientOcclusion };   // the extensions, after the public kinds
-    int kind = RTDD_EFFECT_NONE;                    // RTDD_EFFECT_DEFOCUS / _DESATURATION / _HAZE, kRefocus, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow, kParallax, kAmbientOcclusion
+    enum : int { kRefocus = RTDD_EFFECT_HAZE + 1, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow, kParallax, kAmbientOcclusion, kLighting };   // the extensions, after the public kinds
+    int kind = RTDD_EFFECT_NONE;                    // RTDD_EFFECT_DEFOCUS / _DESATURATION / _HAZE, kRefocus, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow, kParallax, kAmbientOcclusion, kLighting
     const uint8_t *original = nullptr; size_t originalPitch = 0;
     const float *depth = nullptr; size_t depthPitch = 0;
     uint8_t *artistic = nullptr; size_t artisticPitch = 0;
@@ -133,7 +133,9 @@ struct Effect {
     } parallax = {};
     // ambient occlusion (kAmbientOcclusion): rtdd_ambient_occlusion as the entry point checked it (include/rtdd.h
     // rtdd_simulate_ambient_occlusion), by value -- a replay needs no rtdd_ambient_occlusion.  lit: the call had a light, prepared in
-    // `light` as relight's (light.relief == relief bit for bit); the tables inv_j[k] depend on k alone and are the launcher's
+    // `light` as relight's (light.relief == relief bit for bit); the tables inv_j[k] depend on k alone and are the launcher's.
+    // The whole lighting model (kLighting, include/rtdd.h rtdd_simulate_lighting) has no fields of its own: `light`, `shadow` and
+    // `occlusion` (lit, RTDD_AO_SHADE) as the three calls prepare them
     struct Occlusion {
         int mode = 0, directions = 8, radius = 0;   // rtdd_ao_mode; 4 or 8; [0, 64]
         float relief = 0.0f, bias = 0.0f, strength = 0.0f;
@@ -386,6 +388,8 @@ int launch_relight_shadow(rtdd_ctx *ctx, const Effect &e);
 int launch_parallax(rtdd_ctx *ctx, const Effect &e);
 // ---- ambient_occlusion.hip: Effect::kAmbientOcclusion (called by launch_effect) --------------------
 int launch_ambient_occlusion(rtdd_ctx *ctx, const Effect &e);
+// ---- lighting.hip: Effect::kLighting (called by launch_effect) -------------------------------------
+int launch_lighting(rtdd_ctx *ctx, const Effect &e);
 
 // ---- cascade.hip -------------------------------------------------------------------------------
 int launch_bgr2gray(rtdd_ctx *ctx, const uint8_t *bgr, size_t bp, uint8_t *gray, size_t gp, int rows, int cols);
