@@ -120,7 +120,8 @@ def test_persistent_mode_bit_exact(ctx, oracle, lut, shape, iters, tile, depth):
 
 def test_randomised_shapes_and_options(ctx, oracle, lut):
     """60 random (shape, sweeps, level rule, kernel, tile, depth, persistence, contraction) draws, fixed seed: every
-    one bit-exact.  Catches geometry corner cases the hand-picked lists miss (ragged tiles, tiny centres, 1-pixel strips)."""
+    one bit-exact.  Catches geometry corner cases the hand-picked lists miss (ragged tiles, tiny centres, 1-pixel strips) where a draw
+    happens to land on one; tests/test_gpu_tile_geometry.py is where those are hit on purpose, on shapes derived from each tile's geometry."""
     rng = np.random.default_rng(20261003)
     for trial in range(60):
         rows = int(rng.integers(1, 420)); cols = int(rng.integers(1, 520))
