@@ -7,8 +7,8 @@
 //     key 'd'  -> one depth estimate        (main.cpp:232-295)  -> <out>DepthMap.pgm     (main.cpp:306-310)
 //     key 's'  -> also the annotated image   (main.cpp:298-303)  -> <out>AnnotatedImage.ppm: the image with the scribbles painted in
 //     key 'b'/'g'/'h' -> --effect defocus|desaturation|haze     -> <out>ArtisticEffect.ppm (main.cpp:190-230, 312-316)
-//     extensions: --effect refocus [--focus D | --focus-at X,Y] [--aperture A] [--bokeh box|disc]   (rtdd_simulate_refocus; default: focus depth 0,
-//                 aperture 0.025 = the defocus; --bokeh disc: rtdd_simulate_lens_blur's round aperture), --effect haze [--haze-beta B] [--airlight b,g,r]   (rtdd_simulate_haze_ex when either is given),
+//     extensions: --effect refocus [--focus D | --focus-at X,Y] [--aperture A] [--bokeh box|disc|spread]   (rtdd_simulate_refocus; default: focus depth 0,
+//                 aperture 0.025 = the defocus; --bokeh disc: rtdd_simulate_lens_blur's round aperture; --bokeh spread: rtdd_simulate_bokeh, the occlusion-aware blur), --effect haze [--haze-beta B] [--airlight b,g,r]   (rtdd_simulate_haze_ex when either is given),
 //                 --effect stereo --disparity D [--zero-parallax Z | --zero-parallax-at X,Y] [--anaglyph]   (rtdd_simulate_stereo; default:
 //                 zero parallax at depth 0, the view),
 //                 --effect parallax --shift dx,dy [--dolly z] [--zero-parallax Z | --zero-parallax-at X,Y]   (rtdd_simulate_parallax: the camera moved
@@ -199,6 +199,7 @@ struct Job {
     float focus_depth = 0.0f;
     int focus_x = -1, focus_y = -1;
     bool disc = false;            // --bokeh disc: rtdd_simulate_lens_blur with the round aperture (box, the default: rtdd_simulate_refocus)
+    bool spread = false;          // --bokeh spread: rtdd_simulate_bokeh, every pixel spread over its own disc
     bool haze_ex = false;         // --haze-beta / --airlight given: rtdd_simulate_haze_ex
     float haze_beta = 2.0f;
     int air[3] = {255, 255, 255}; // b, g, r
@@ -477,6 +478,9 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
             CK(rtdd_simulate_haze_ex(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols, job.haze_beta,
                                      (uint8_t)job.air[0], (uint8_t)job.air[1], (uint8_t)job.air[2]));
         else if (job.effect == "haze") CK(rtdd_simulate_haze(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols));
+        else if (job.effect == "refocus" && job.spread)
+            CK(rtdd_simulate_bokeh(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols, job.aperture,
+                                   job.focus_depth, job.focus_x, job.focus_y));
         else if (job.effect == "refocus" && job.disc)
             CK(rtdd_simulate_lens_blur(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols, job.aperture,
                                        job.focus_depth, job.focus_x, job.focus_y, RTDD_APERTURE_DISC));
@@ -526,7 +530,7 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
 
 int main(int argc, const char *argv[]) {
     if (argc == 1) { std::printf("Usage: rtdd_harness -i image.(jpg|png|ppm) [-a annotation.(png|pgm)] [-o prefix] [--effect defocus|desaturation|haze|refocus|stereo|parallax|relight|ao|lighting] [--iters N] [--refine sor|mg|auto [--tolerance T]]\n"
-                                 "                    [--focus D | --focus-at X,Y] [--aperture A] [--bokeh box|disc] (refocus)  [--haze-beta B] [--airlight b,g,r] (haze)\n"
+                                 "                    [--focus D | --focus-at X,Y] [--aperture A] [--bokeh box|disc|spread] (refocus)  [--haze-beta B] [--airlight b,g,r] (haze)\n"
                                  "                    [--disparity D] [--zero-parallax Z | --zero-parallax-at X,Y] [--anaglyph] (stereo)\n"
                                  "                    --shift dx,dy [--dolly z] [--zero-parallax Z | --zero-parallax-at X,Y] (parallax)\n"
                                  "                    [--light-dir x,y,z | --light-at X,Y [--light-height H] [--light-radius R]] [--relief S] [--ambient A] [--diffuse D] [--light-color b,g,r] (relight)\n"
@@ -579,8 +583,8 @@ int main(int argc, const char *argv[]) {
         else if (!std::strcmp(argv[i], "--aperture")) job.aperture = std::atof(next());
         else if (!std::strcmp(argv[i], "--bokeh")) {
             const std::string b = next();
-            if (b != "box" && b != "disc") { std::printf("--bokeh wants box or disc\n"); return 1; }
-            job.disc = b == "disc";
+            if (b != "box" && b != "disc" && b != "spread") { std::printf("--bokeh wants box or disc or spread\n"); return 1; }
+            job.disc = b == "disc"; job.spread = b == "spread";
         }
         else if (!std::strcmp(argv[i], "--disparity")) job.disparity = std::atoi(next());
         else if (!std::strcmp(argv[i], "--zero-parallax")) { job.zero_depth = (float)std::atof(next()); job.zero_x = -1; }

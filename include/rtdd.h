@@ -324,7 +324,8 @@ int rtdd_simulate_haze(rtdd_ctx *ctx, const uint8_t *original, size_t originalPi
 /* ---- aimed depth effects (extensions; no reference behaviour) --------------------------------
  * Added after ABI version 230 without a version bump: a host finds them by symbol (dlsym).  The next bump of RTDD_VERSION
  * should cover them (rtdd_simulate_refocus, rtdd_simulate_lens_blur, rtdd_simulate_haze_ex, rtdd_simulate_stereo, rtdd_simulate_relight,
- * rtdd_simulate_relight_shadowed, rtdd_simulate_parallax, rtdd_simulate_ambient_occlusion, rtdd_simulate_lighting), together with a
+ * rtdd_simulate_relight_shadowed, rtdd_simulate_parallax, rtdd_simulate_ambient_occlusion, rtdd_simulate_lighting, rtdd_simulate_bokeh),
+ * together with a
  * parameterised live effect
  * (rtdd_live_submit_ex takes an effect code only and knows none of them). */
 
@@ -364,6 +365,34 @@ enum rtdd_aperture_shape { RTDD_APERTURE_BOX = 0, RTDD_APERTURE_DISC = 1 };
 int rtdd_simulate_lens_blur(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch,
                             const float *depth, size_t depthPitch, uint8_t *artistic, size_t artisticPitch,
                             int rows, int cols, double aperture, float focusDepth, int focusX, int focusY, int shape);
+
+/* Bokeh: the occlusion-aware lens blur.  rtdd_simulate_lens_blur is a gather: the OUTPUT pixel sizes the window from its own depth, so a
+ * blurred background averages a sharp foreground subject's colours in (a halo), and a blurred foreground keeps a hard silhouette.  Here
+ * every SOURCE pixel spreads its colour over its own circle of confusion, and a source behind the target spreads no wider than the
+ * target's own circle.  Evaluated as a gather; all arithmetic after step 2 is integer, so the sums do not depend on their order.
+ *   1. K = (int)(aperture * sqrtf(rows*rows + cols*cols)) on the host, as rtdd_simulate_refocus's.  f0 = focusDepth when focusX < 0;
+ *      otherwise the depth map's value at (focusX, focusY), READ BY THE KERNEL ON THE DEVICE when it runs (no host synchronisation, as
+ *      refocus's focus).  f = fminf(fmaxf(f0, 0), 255), a NaN giving 0 (stereo's clamp).
+ *   2. per pixel q, the signed circle of confusion: d' = fminf(fmaxf(d, 0), 255) (a NaN depth is 0), t = d' - f in f32,
+ *      kf = (double)((float)K * fabsf(t)) / 255.0, k = (int)kf (in [0, K]: |t| <= 255), s = t < 0 ? -k : k.  For a map within [0, 255]
+ *      k is RTDD_APERTURE_DISC's diameter.
+ *   3. source q and target p, both inside the image: ke = (s_q > s_p) ? min(k_q, k_p) : k_q -- a source behind the target spreads no
+ *      wider than the target's own circle; q reaches p iff 4 * ((qx - px)^2 + (qy - py)^2) <= ke * ke, the disc test of
+ *      RTDD_APERTURE_DISC.  p always reaches itself.
+ *   4. wt[k] = floor(2^30 / N(k)) for k = 0 .. 127, N(k) the number of integer (dx, dy) with 4 (dx^2 + dy^2) <= k^2 (N(0) = N(1) = 1,
+ *      N(127) = 12645, wt[127] = 84914).  W = the sum of wt[ke] over the sources that reach p, S_c = the sum of wt[ke] * o_c(q) over the
+ *      same sources, out_c = floor(S_c / W) per channel c of B, G, R.  W >= wt[127] > 0; at most 127^2 sources reach p, so
+ *      S_c < 2^14 * 2^30 * 2^8 = 2^52: exact in 64 bits.
+ * Identities: on a map whose every pixel has the same s the output is rtdd_simulate_lens_blur(..., RTDD_APERTURE_DISC) byte for byte
+ * (floor(wt * sum / (wt * n)) = floor(sum / n), and with n <= 12645 the f32 (uchar)(sum / count) cannot round up to the next integer);
+ * where every k <= 1 the output is the original; a pixel with s_p = 0 on a map that has no s < 0 anywhere keeps its original bytes.
+ * Deterministic; the output does not depend on RTDD_OPT_FP_CONTRACT; no fall-back path, no sticky state.  One kernel launch.
+ * Refused on the host (RTDD_ERR_INVALID), before any launch: everything rtdd_simulate_lens_blur refuses (original == artistic
+ * included); K > 127, so that s fits 8 bits and a tile with its halo fits the LDS.  The default aperture gives K = 55 at 1080p and 110 at
+ * 4K; at 8K it gives 220, which is refused: 8K needs an aperture of 0.0144 or less (K = 126). */
+int rtdd_simulate_bokeh(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch,
+                        const float *depth, size_t depthPitch, uint8_t *artistic, size_t artisticPitch,
+                        int rows, int cols, double aperture, float focusDepth, int focusX, int focusY);
 
 /* Haze with a density and an airlight colour (GPUDepthEffect.cu:74-93 with its constants as parameters):
  *   t = exp((float)((double)(-beta * d) / 255.0)) by the same deterministic exp as rtdd_simulate_haze,

@@ -54,7 +54,7 @@ C_ABI_SYMBOLS = [
     "rtdd_simulate_refocus", "rtdd_simulate_haze_ex", "rtdd_simulate_stereo", "rtdd_simulate_lens_blur",
     "rtdd_paint_strokes", "rtdd_pyramid_annotation_rebuild",
     "rtdd_simulate_relight", "rtdd_simulate_relight_shadowed", "rtdd_simulate_parallax", "rtdd_simulate_ambient_occlusion",
-    "rtdd_simulate_lighting",
+    "rtdd_simulate_lighting", "rtdd_simulate_bokeh",
 ]
 IMG_ORIGINAL, IMG_GRAY, IMG_SCRIBBLE, IMG_EDITED, IMG_DEPTH, IMG_DEPTH_U8, IMG_ARTISTIC = range(7)
 EFFECT_NONE, EFFECT_DEFOCUS, EFFECT_DESATURATION, EFFECT_HAZE = range(4)
@@ -382,6 +382,14 @@ class Context:
         o, op = _img(originalImage); d, dp = _img(depthImage); a, ap = _img(artisticImage)
         self._check(lib().rtdd_simulate_lens_blur(self._h, o, op, d, dp, a, ap, C.c_int(rows), C.c_int(cols), C.c_double(aperture),
                                                   C.c_float(focusDepth), C.c_int(focusX), C.c_int(focusY), C.c_int(shape)))
+
+    def simulate_bokeh(self, originalImage, depthImage, artisticImage, rows, cols, aperture=0.025, focusDepth=0.0, focusX=-1, focusY=-1):
+        """The occlusion-aware lens blur: every pixel spreads its colour over its own circle of confusion (the disc of simulate_lens_blur),
+        and a pixel behind the target spreads no wider than the target's own circle -- a sharp subject gets no halo, a blurred one a soft
+        edge.  The focus as simulate_refocus's; the window scale (int)(aperture * diagonal) must be <= 127."""
+        o, op = _img(originalImage); d, dp = _img(depthImage); a, ap = _img(artisticImage)
+        self._check(lib().rtdd_simulate_bokeh(self._h, o, op, d, dp, a, ap, C.c_int(rows), C.c_int(cols), C.c_double(aperture),
+                                              C.c_float(focusDepth), C.c_int(focusX), C.c_int(focusY)))
 
     def simulate_haze_ex(self, originalImage, depthImage, artisticImage, rows, cols, beta=2.0, air=(255, 255, 255)):
         """Haze with density `beta` and airlight `air` = (b, g, r)."""

@@ -57,7 +57,7 @@ int rtdd_simulate_haze(rtdd_ctx *ctx, const uint8_t *original, size_t originalPi
     return simulate(ctx, {RTDD_EFFECT_HAZE, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols});
 }
 
-// the aperture (the K rule) and the focus of rtdd_simulate_refocus and rtdd_simulate_lens_blur
+// the aperture (the K rule) and the focus of rtdd_simulate_refocus, rtdd_simulate_lens_blur and rtdd_simulate_bokeh
 static int check_focus(rtdd_ctx *ctx, int rows, int cols, double aperture, float focusDepth, int focusX, int focusY) {
     REQUIRE(ctx, std::isfinite(aperture) && aperture >= 0.0, "aperture must be finite and >= 0");
     REQUIRE(ctx, window_scale(aperture, rows, cols) <= 255, "aperture too large: the window scale (int)(aperture * diagonal) must be <= 255");
@@ -97,6 +97,22 @@ int rtdd_simulate_lens_blur(rtdd_ctx *ctx, const uint8_t *original, size_t origi
     if (rows == 0 || cols == 0) return RTDD_OK;
     Effect e{Effect::kLensBlur, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols};
     e.kernelSize = window_scale(aperture, rows, cols); e.focusDepth = focusDepth; e.focusX = focusX; e.focusY = focusY;
+    return simulate(ctx, e);
+}
+
+int rtdd_simulate_bokeh(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
+                        uint8_t *artistic, size_t artisticPitch, int rows, int cols, double aperture, float focusDepth, int focusX, int focusY) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    int rc = check_effect(ctx, original, depth, artistic, originalPitch, depthPitch, artisticPitch, rows, cols);
+    if (rc != RTDD_OK) return rc;
+    rc = check_focus(ctx, rows, cols, aperture, focusDepth, focusX, focusY);
+    if (rc != RTDD_OK) return rc;
+    const int kernelSize = window_scale(aperture, rows, cols);
+    REQUIRE(ctx, kernelSize <= 127, "aperture too large for the bokeh: the window scale (int)(aperture * diagonal) must be <= 127");
+    REQUIRE(ctx, original != artistic, "bokeh cannot run in place");
+    if (rows == 0 || cols == 0) return RTDD_OK;
+    Effect e{Effect::kBokeh, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols};
+    e.kernelSize = kernelSize; e.focusDepth = focusDepth; e.focusX = focusX; e.focusY = focusY;
     return simulate(ctx, e);
 }
 

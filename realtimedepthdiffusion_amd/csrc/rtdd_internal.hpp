@@ -95,14 +95,14 @@ struct LiveTargets {
 // One depth effect, arguments checked: what to render, on which images, with which parameters.  Built by the rtdd_simulate_* entry
 // points (effects_api.cpp) and by a live frame (live_effect), launched by launch_effect, and logged by value (PendingOp) to be launched again.
 struct Effect {
-    enum : int { kRefocus = RTDD_EFFECT_HAZE + 1, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow, kParallax, kAmbientOcclusion, kLighting };   // the extensions, after the public kinds
-    int kind = RTDD_EFFECT_NONE;                    // RTDD_EFFECT_DEFOCUS / _DESATURATION / _HAZE, kRefocus, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow, kParallax, kAmbientOcclusion, kLighting
+    enum : int { kRefocus = RTDD_EFFECT_HAZE + 1, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow, kParallax, kAmbientOcclusion, kLighting, kBokeh };   // the extensions, after the public kinds
+    int kind = RTDD_EFFECT_NONE;                    // RTDD_EFFECT_DEFOCUS / _DESATURATION / _HAZE, kRefocus, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow, kParallax, kAmbientOcclusion, kLighting, kBokeh
     const uint8_t *original = nullptr; size_t originalPitch = 0;
     const float *depth = nullptr; size_t depthPitch = 0;
     uint8_t *artistic = nullptr; size_t artisticPitch = 0;
     int rows = 0, cols = 0;
     const uint8_t *gray = nullptr; size_t grayPitch = 0;            // desaturation
-    // refocus, lens blur (the round aperture; the square one IS a refocus): the window scale (<= 255) and the focus (focusX >= 0: the map's pixel (focusX, focusY), read by the kernels when they run)
+    // refocus, lens blur (the round aperture; the square one IS a refocus), bokeh (<= 127): the window scale (<= 255) and the focus (focusX >= 0: the map's pixel (focusX, focusY), read by the kernels when they run)
     int kernelSize = 0, focusX = -1, focusY = -1;
     float focusDepth = 0.0f;
     float beta = 2.0f; uint32_t air = 0xFFFFFFu;                    // haze_ex: density and airlight b | g << 8 | r << 16
@@ -390,6 +390,8 @@ int launch_parallax(rtdd_ctx *ctx, const Effect &e);
 int launch_ambient_occlusion(rtdd_ctx *ctx, const Effect &e);
 // ---- lighting.hip: Effect::kLighting (called by launch_effect) -------------------------------------
 int launch_lighting(rtdd_ctx *ctx, const Effect &e);
+// ---- bokeh.hip: Effect::kBokeh (called by launch_effect) -------------------------------------------
+int launch_bokeh(rtdd_ctx *ctx, const Effect &e);
 
 // ---- cascade.hip -------------------------------------------------------------------------------
 int launch_bgr2gray(rtdd_ctx *ctx, const uint8_t *bgr, size_t bp, uint8_t *gray, size_t gp, int rows, int cols);
