@@ -30,6 +30,7 @@
 //     --paint x,y,label,radius  = a mouse drag sample (main.cpp:46-62), repeatable; --paint-at F:x,y,label,radius = the same while --live
 //                                 runs, in front of frame F (the user painting into a live view)
 //     --refine sor|mg|auto [--tolerance T] = extension: converge the finest level after the estimate (rtdd_refine_depth)
+//     --edges gray|color = extension: the estimates' edge weights from the gray image (default, the reference's) or from the BGR image (rtdd_pyramid_set_guide)
 // and adds what the reference cannot do: --devices N --batch B runs B independent estimates
 // round-robin over N GPUs, one host thread + one HIP stream + one rtdd_ctx per GPU, no collective.
 #include <hip/hip_runtime.h>
@@ -223,6 +224,7 @@ struct Job {
     rtdd_ambient_occlusion ao = {RTDD_AO_SHADE, 8, 16, 2.0f, 0.0f, 1.0f};
     bool sequential = false;      // --sequential: a --batch as one estimate after the other (default: rtdd_estimate_depth_batch, all images in the same launches)
     bool cold = false;            // --cold: no warm-up: the first (and, without --live, only) estimate pays the one-time costs
+    bool edges_color = false;     // --edges color: the estimates read their edge weights from the BGR image (rtdd_pyramid_set_guide); default gray: the reference's
 };
 
 // --stroke / --erase: the job's strokes on a device image pair, one call
@@ -331,6 +333,7 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
     const bool batched = !live && count > 1 && !job.sequential && job.effect.empty() && job.refine.empty();
     if (batched) {
         CK(rtdd_pyramid_create_batch(ctx, rows, cols, count));
+        if (job.edges_color) CK(rtdd_pyramid_set_guide(ctx, RTDD_GUIDE_BGR));
         if (hipMalloc((void **)&own.d_bgr, (size_t)rows * cols * 3) != hipSuccess || hipMalloc((void **)&own.d_ann, (size_t)rows * cols) != hipSuccess) { std::printf("device %d: out of memory\n", device); return RTDD_ERR_NOMEM; }
         auto t0 = std::chrono::steady_clock::now();
         for (int n = 0; n < count; n++) {                               // every image is independent: its own upload, annotation and strokes
@@ -369,6 +372,7 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
         return RTDD_OK;
     }
     CK(rtdd_pyramid_create(ctx, rows, cols));                           // main.cpp:92-149
+    if (job.edges_color) CK(rtdd_pyramid_set_guide(ctx, RTDD_GUIDE_BGR));  // (single estimates, --live and --sequential alike)
     if (hipMalloc((void **)&own.d_bgr, (size_t)rows * cols * 3) != hipSuccess || hipMalloc((void **)&own.d_ann, (size_t)rows * cols) != hipSuccess) { std::printf("device %d: out of memory\n", device); return RTDD_ERR_NOMEM; }
     unsigned char *d_bgr = own.d_bgr, *d_ann = own.d_ann;
     void *p_scr, *p_ed, *p_orig, *p_gray, *p_depth, *p_art, *p_u8;
@@ -537,7 +541,7 @@ int main(int argc, const char *argv[]) {
                                  "                    [--shadows N [--shadow-bias B] [--shadow-softness S] [--shadow-strength T]] (relight with cast shadows)\n"
                                  "                    [--ao-radius R] [--ao-directions 4|8] [--ao-bias B] [--ao-strength T] [--relief S] [--ao-map] (ao)  [--ao R [--ao-directions ..] [--ao-bias ..] [--ao-strength ..]] (relight with its ambient term occluded)\n"
                                  "                    [relight's light flags] [--shadows N (256)] [--shadow-bias B] [--shadow-softness S] [--shadow-strength T] [--ao R (16)] [--ao-directions 4|8] [--ao-bias B] [--ao-strength T] (lighting: shade, cast shadows and occlusion in one call)\n"
-                                 "                    [--paint x,y,label,radius]... [--live N [--paint-at frame:x,y,label,radius]...] [--devices D --batch B [--sequential] [--write-all]] [--png] [--cold]\n"
+                                 "                    [--paint x,y,label,radius]... [--live N [--paint-at frame:x,y,label,radius]...] [--devices D --batch B [--sequential] [--write-all]] [--png] [--cold] [--edges gray|color]\n"
                                  "                    [--stroke x0,y0,x1,y1,label,radius[,round]]... [--erase x0,y0,x1,y1,radius[,round]]...   (segments, in command-line order, one rtdd_paint_strokes call after --paint)\n"
                                  "                    [--stroke-at frame:x0,y0,x1,y1,label,radius[,round]]... [--erase-at frame:x0,y0,x1,y1,radius[,round]]...   (--live: in front of that frame)\n"
                                  "       rtdd_harness --convert in.(jpg|png|ppm|pgm) out.(png|ppm|pgm)   (JPEG / 8-bit PNG / PNM -> PNG / PNM, no GPU)\n"); return 0; }
@@ -557,6 +561,11 @@ int main(int argc, const char *argv[]) {
         else if (!std::strcmp(argv[i], "-o")) out = next();
         else if (!std::strcmp(argv[i], "--effect")) job.effect = next();
         else if (!std::strcmp(argv[i], "--cold")) job.cold = true;
+        else if (!std::strcmp(argv[i], "--edges")) {
+            const char *v = next();
+            if (!std::strcmp(v, "color")) job.edges_color = true;
+            else if (std::strcmp(v, "gray")) { std::printf("--edges wants gray or color\n"); return 1; }
+        }
         else if (!std::strcmp(argv[i], "--iters")) job.iters = std::atoi(next());
         else if (!std::strcmp(argv[i], "--refine")) job.refine = next();          // sor | mg | auto
         else if (!std::strcmp(argv[i], "--tolerance")) job.tolerance = (float)std::atof(next());

@@ -252,6 +252,35 @@ int rtdd_index_to_weight(rtdd_ctx *ctx, const uint8_t *gray, size_t grayPitch,
                          const float *depth, size_t depthPitch,
                          int32_t *index2, int level, int rows, int cols);
 
+/* Colour-guided edge weights (extension; no reference behaviour).  Added after ABI version 230 without a version bump: a host finds
+ * rtdd_solve_guided, rtdd_index_to_weight_guided, rtdd_pyrdown_bgr, rtdd_pyramid_set_guide and rtdd_pyramid_guide by symbol, and the next
+ * bump of RTDD_VERSION should cover them.
+ * The reference reads the photograph through ONE gray channel: the LUT index of the edge between two 4-neighbours p, q is
+ * |gray_p - gray_q| (src/GPUSolver.cu:183-222), so a boundary between two colours of equal luminance does not exist for the diffusion.
+ * With a BGR guide (interleaved u8x3, pitch >= 3 * cols, any address and any pitch: a region of interest is legal) the index is
+ *     index(p, q) = max(|B_p - B_q|, |G_p - G_q|, |R_p - R_q|)
+ * an integer in [0, 255] -- a LUT index as it stands, no clamp.  Everything else is loadIndexToWeight's: 256 outside the image, the
+ * depth gate of level != maxLevel with its threshold (0 on level 0, 4 otherwise: the index is 0 unless the saturated u8 depths of p and
+ * q differ by MORE than it), the saturating u8 cast of the depth.  A BGR guide with B = G = R = v gives the gray guide's indices on v,
+ * byte for byte, so such a solve has the reference's bits.  The sweeps never see the guide, only the indices: every method, sweep kernel,
+ * tile and launch mode is guided alike.
+ * NOTE (a consequence of the reference's gate, not of the guide): on level 0 an edge whose two pixels START at the same u8 depth has index
+ * 0 under either guide -- the gate zeroes it before the guide is asked.  A colour edge is found at the coarsest level of an estimate,
+ * which is not gated, and inherited by the finer ones through the depth they start from.
+ * rtdd_solve_guided with RTDD_GUIDE_GRAY IS rtdd_solve_ex: the same record, the same launches, the same bits.  Its refusals are
+ * rtdd_solve_ex's plus an unknown kind (with RTDD_GUIDE_BGR the pitch rule is guidePitch >= 3 * cols).  A healed time-out
+ * (RTDD_ERR_TIMEOUT) runs a guided solve again as guided. */
+enum rtdd_guide { RTDD_GUIDE_GRAY = 0, RTDD_GUIDE_BGR = 1 };
+int rtdd_solve_guided(rtdd_ctx *ctx, float *depth, size_t depthPitch,
+                      const uint8_t *scribble, size_t scribblePitch,
+                      const uint8_t *guide, size_t guidePitch, int guideKind,
+                      int rows, int cols, int level,
+                      const rtdd_solve_params *params, rtdd_solve_info *info);
+/* rtdd_index_to_weight for either guide: the index pass alone, in the reference's int2 format, for parity tests. */
+int rtdd_index_to_weight_guided(rtdd_ctx *ctx, const uint8_t *guide, size_t guidePitch, int guideKind,
+                                const float *depth, size_t depthPitch,
+                                int32_t *index2, int level, int rows, int cols);
+
 /* ---- image processing (include/GPUImageProcessing.h:4-10) ---------------------------------- */
 
 /* GPUConvertToFloat -- src/GPUImageProcessing.cu:8-21,72-79: dst[y][x] = src[y][3x] where mask==255. */
@@ -648,7 +677,9 @@ enum rtdd_pyramid_image_kind {
     RTDD_IMG_EDITED = 3,            /* u8x3 */
     RTDD_IMG_DEPTH = 4,             /* f32 */
     RTDD_IMG_DEPTH_U8 = 5,          /* u8, level 0 only */
-    RTDD_IMG_ARTISTIC = 6           /* u8x3, level 0 only: output of the effect calls */
+    RTDD_IMG_ARTISTIC = 6,          /* u8x3, level 0 only: output of the effect calls */
+    RTDD_IMG_GUIDE_BGR = 7          /* u8x3 on every level, ceil-sized chain like RTDD_IMG_GRAY; level 0 IS RTDD_IMG_ORIGINAL.  The levels above 0:
+                                       RTDD_ERR_STATE until a call of rtdd_pyramid_set_guide with RTDD_GUIDE_BGR has made them */
 };
 int rtdd_pyramid_levels(int rows, int cols);             /* src/main.cpp:95 */
 int rtdd_pyramid_create(rtdd_ctx *ctx, int rows, int cols);   /* main.cpp:92-155 minus I/O: images, depth := 255, rtdd_allocate */
@@ -672,6 +703,18 @@ int rtdd_estimate_depth_batch(rtdd_ctx *ctx, int maxIterations);   /* rtdd_estim
 int rtdd_pyramid_level_info(rtdd_ctx *ctx, int level, rtdd_solve_info *info, int *imagesPerLaunch);
 /* image: DEVICE pointer to an interleaved BGR u8 image; builds the gray pyramid, edited[0] := image, scribble[0] := 0 */
 int rtdd_pyramid_set_image(rtdd_ctx *ctx, const uint8_t *bgr, size_t pitch);
+/* The guide of the pyramid's estimates (enum rtdd_guide above; RTDD_GUIDE_GRAY after rtdd_pyramid_create / _create_batch: the reference's
+ * behaviour).  With RTDD_GUIDE_BGR every per-level solve of rtdd_estimate_depth, rtdd_estimate_depth_batch, rtdd_live_submit / _ex and
+ * rtdd_refine_depth takes level l of a COLOUR pyramid instead of RTDD_IMG_GRAY: level 0 is the original image, level l is cv::pyrDown of
+ * level l - 1 per channel (OpenCV filters channels independently) -- the arithmetic and the ceil-sized chain of rtdd_pyrdown_gray, channel by
+ * channel (RTDD_IMG_GUIDE_BGR).  The first request for BGR allocates the coarse colour levels (RTDD_ERR_NOMEM before anything is launched)
+ * and, if an image has been set, builds them for every image of a batch; while the guide is BGR rtdd_pyramid_set_image builds the selected
+ * image's chain behind the gray one.  Going back to RTDD_GUIDE_GRAY keeps the allocation (asking for BGR again builds the chains again
+ * from the images as they are).  A pyramid that never asks for BGR allocates nothing and launches nothing it did not launch before.
+ * A logged estimate remembers the guide it ran with: a healed time-out runs it again with that guide, whatever the pyramid's is by then.
+ * Refused: no pyramid (RTDD_ERR_STATE), an unknown kind.  rtdd_pyramid_guide: the guide in force (RTDD_GUIDE_GRAY without a pyramid). */
+int rtdd_pyramid_set_guide(rtdd_ctx *ctx, int guideKind);
+int rtdd_pyramid_guide(rtdd_ctx *ctx);
 /* annotation: DEVICE pointer to a 1-channel u8 map; decode rule of src/main.cpp:160-168 (value != 32 -> label, mask 255) */
 int rtdd_pyramid_set_annotation(rtdd_ctx *ctx, const uint8_t *annotation, size_t pitch);
 int rtdd_pyramid_image(rtdd_ctx *ctx, int kind, int level, void **ptr, size_t *pitch, int *rows, int *cols);
@@ -742,6 +785,8 @@ int rtdd_refine_depth(rtdd_ctx *ctx, const rtdd_solve_params *params, rtdd_solve
 /* the standalone third-party pieces, exposed for parity tests against the oracle's restatement */
 int rtdd_bgr2gray(rtdd_ctx *ctx, const uint8_t *bgr, size_t bgrPitch, uint8_t *gray, size_t grayPitch, int rows, int cols);
 int rtdd_pyrdown_gray(rtdd_ctx *ctx, const uint8_t *src, size_t srcPitch, int rows, int cols, uint8_t *dst, size_t dstPitch);
+/* rtdd_pyrdown_gray on each channel of an interleaved u8x3 image (dst: (rows + 1) / 2 x (cols + 1) / 2, dstPitch >= 3 * that width) */
+int rtdd_pyrdown_bgr(rtdd_ctx *ctx, const uint8_t *src, size_t srcPitch, int rows, int cols, uint8_t *dst, size_t dstPitch);
 int rtdd_pyrup_depth(rtdd_ctx *ctx, const float *src, size_t srcPitch, int rows, int cols,
                      float *dst, size_t dstPitch, int dstRows, int dstCols);
 int rtdd_depth_to_u8(rtdd_ctx *ctx, const float *src, size_t srcPitch, uint8_t *dst, size_t dstPitch, int rows, int cols);

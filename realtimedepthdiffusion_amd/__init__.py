@@ -55,8 +55,10 @@ C_ABI_SYMBOLS = [
     "rtdd_paint_strokes", "rtdd_pyramid_annotation_rebuild",
     "rtdd_simulate_relight", "rtdd_simulate_relight_shadowed", "rtdd_simulate_parallax", "rtdd_simulate_ambient_occlusion",
     "rtdd_simulate_lighting", "rtdd_simulate_bokeh",
+    "rtdd_solve_guided", "rtdd_index_to_weight_guided", "rtdd_pyrdown_bgr", "rtdd_pyramid_set_guide", "rtdd_pyramid_guide",
 ]
-IMG_ORIGINAL, IMG_GRAY, IMG_SCRIBBLE, IMG_EDITED, IMG_DEPTH, IMG_DEPTH_U8, IMG_ARTISTIC = range(7)
+IMG_ORIGINAL, IMG_GRAY, IMG_SCRIBBLE, IMG_EDITED, IMG_DEPTH, IMG_DEPTH_U8, IMG_ARTISTIC, IMG_GUIDE_BGR = range(8)
+GUIDE_GRAY, GUIDE_BGR = 0, 1                  # rtdd_guide: what the edge weights are read from (rtdd_solve_guided, rtdd_pyramid_set_guide)
 EFFECT_NONE, EFFECT_DEFOCUS, EFFECT_DESATURATION, EFFECT_HAZE = range(4)
 STEREO_VIEW, STEREO_ANAGLYPH = 0, 1           # rtdd_simulate_stereo's modes
 APERTURE_BOX, APERTURE_DISC = 0, 1            # rtdd_simulate_lens_blur's shapes
@@ -312,6 +314,18 @@ class Context:
         self.last_cycles = info.cycles          # V-cycles of the last solve (METHOD_MULTIGRID / METHOD_AUTO)
         return info.iterations, info.residual
 
+    def solve_guided(self, depthImage, scribbleImage, guideImage, guideKind, rows, cols, level, method=METHOD_CHEBYSHEV_JACOBI,
+                     maxIterations=1000, tolerance=0.0, checkEvery=0, relaxation=0.0):
+        """rtdd_solve_guided: solve_ex with the edge weights read from `guideImage` as `guideKind` says -- GUIDE_GRAY (solve_ex itself) or
+        GUIDE_BGR (an interleaved colour image: the index of an edge is the largest channel difference)."""
+        dp, dpitch = _img(depthImage); sp, spitch = _img(scribbleImage); gp, gpitch = _img(guideImage)
+        params = SolveParams(method, maxIterations, tolerance, checkEvery, relaxation)
+        info = SolveInfo()
+        self._check(lib().rtdd_solve_guided(self._h, dp, dpitch, sp, spitch, gp, gpitch, C.c_int(guideKind), C.c_int(rows), C.c_int(cols),
+                                            C.c_int(level), C.byref(params), C.byref(info)))
+        self.last_cycles = info.cycles
+        return info.iterations, info.residual
+
     def last_solve_info(self):
         """What the most recent solve on this context actually ran (kernel, tile, depth, persistence, contraction, counts)."""
         info = SolveInfo()
@@ -331,6 +345,11 @@ class Context:
         gp, gpitch = _img(grayImage); dp, dpitch = _img(depthImage)
         self._check(lib().rtdd_index_to_weight(self._h, gp, gpitch, dp, dpitch, C.c_void_p(index2.data_ptr()), C.c_int(level),
                                                C.c_int(rows), C.c_int(cols)))
+
+    def index_to_weight_guided(self, guideImage, guideKind, depthImage, index2, level, rows, cols):
+        gp, gpitch = _img(guideImage); dp, dpitch = _img(depthImage)
+        self._check(lib().rtdd_index_to_weight_guided(self._h, gp, gpitch, C.c_int(guideKind), dp, dpitch, C.c_void_p(index2.data_ptr()),
+                                                      C.c_int(level), C.c_int(rows), C.c_int(cols)))
 
     # ---- include/GPUImageProcessing.h
     def GPUConvertToFloat(self, src, dst, mask, rows, cols):
@@ -475,6 +494,13 @@ class Context:
         p, pitch = _img(bgr)
         self._check(lib().rtdd_pyramid_set_image(self._h, p, pitch))
 
+    def pyramid_set_guide(self, guideKind):
+        """GUIDE_GRAY (the default, the reference's behaviour) or GUIDE_BGR: the estimates' per-level solves read the colour pyramid."""
+        self._check(lib().rtdd_pyramid_set_guide(self._h, C.c_int(guideKind)))
+
+    def pyramid_guide(self):
+        return int(lib().rtdd_pyramid_guide(self._h))
+
     def pyramid_set_annotation(self, annotation):
         p, pitch = _img(annotation)
         self._check(lib().rtdd_pyramid_set_annotation(self._h, p, pitch))
@@ -495,7 +521,7 @@ class Context:
     def pyramid_download(self, kind, level=0):
         import numpy as np
         ptr, pitch, rows, cols = self.pyramid_image(kind, level)
-        dtype, ch = (np.float32, 1) if kind == IMG_DEPTH else (np.uint8, 3 if kind in (IMG_ORIGINAL, IMG_EDITED, IMG_ARTISTIC) else 1)
+        dtype, ch = (np.float32, 1) if kind == IMG_DEPTH else (np.uint8, 3 if kind in (IMG_ORIGINAL, IMG_EDITED, IMG_ARTISTIC, IMG_GUIDE_BGR) else 1)
         out = np.empty((rows, cols, ch) if ch == 3 else (rows, cols), dtype)
         if rows and cols:
             w = cols * ch * out.itemsize
@@ -541,6 +567,10 @@ class Context:
     def pyrdown_gray(self, src, rows, cols, dst):
         s, sp = _img(src); d, dp = _img(dst)
         self._check(lib().rtdd_pyrdown_gray(self._h, s, sp, C.c_int(rows), C.c_int(cols), d, dp))
+
+    def pyrdown_bgr(self, src, rows, cols, dst):
+        s, sp = _img(src); d, dp = _img(dst)
+        self._check(lib().rtdd_pyrdown_bgr(self._h, s, sp, C.c_int(rows), C.c_int(cols), d, dp))
 
     def pyrup_depth(self, src, rows, cols, dst, drows, dcols):
         s, sp = _img(src); d, dp = _img(dst)

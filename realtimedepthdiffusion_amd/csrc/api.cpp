@@ -314,7 +314,8 @@ static int check_solve_args(rtdd_ctx *ctx, const SolveCall &c) {
     REQUIRE(ctx, c.rows > 0 && c.cols > 0, "rows and cols must be positive");
     REQUIRE(ctx, f32_image_aligned(c.depth, c.depthPitch), kF32AlignText);
     REQUIRE(ctx, c.depthPitch >= (size_t)c.cols * sizeof(float), "depth pitch smaller than a row");
-    REQUIRE(ctx, c.scribblePitch >= (size_t)c.cols && c.grayPitch >= (size_t)c.cols, "u8 pitch smaller than a row");
+    REQUIRE(ctx, c.guide == RTDD_GUIDE_GRAY || c.guide == RTDD_GUIDE_BGR, "unknown guide kind");
+    REQUIRE(ctx, c.scribblePitch >= (size_t)c.cols && c.grayPitch >= (size_t)c.cols * (c.guide == RTDD_GUIDE_BGR ? 3 : 1), "u8 pitch smaller than a row");
     if (ctx->levels.empty()) return fail(ctx, RTDD_ERR_STATE, "rtdd_allocate has not been called");
     if (!ctx->weights_loaded) return fail(ctx, RTDD_ERR_STATE, "rtdd_load_weights has not been called");
     REQUIRE(ctx, c.level >= 0 && c.level < (int)ctx->levels.size(), "level out of range");
@@ -506,7 +507,15 @@ int rtdd_solve_ex(rtdd_ctx *ctx, float *depth, size_t depthPitch, const uint8_t 
                   const rtdd_solve_params *params, rtdd_solve_info *info) {
     if (!ctx) return RTDD_ERR_INVALID;
     REQUIRE(ctx, params != nullptr, "null params");
-    return solve_with(ctx, {depth, depthPitch, scribble, scribblePitch, gray, grayPitch, rows, cols, level, *params, {}}, info, nullptr);
+    return solve_with(ctx, {depth, depthPitch, scribble, scribblePitch, gray, grayPitch, RTDD_GUIDE_GRAY, rows, cols, level, *params, {}}, info, nullptr);
+}
+
+int rtdd_solve_guided(rtdd_ctx *ctx, float *depth, size_t depthPitch, const uint8_t *scribble, size_t scribblePitch,
+                      const uint8_t *guide, size_t guidePitch, int guideKind, int rows, int cols, int level,
+                      const rtdd_solve_params *params, rtdd_solve_info *info) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    REQUIRE(ctx, params != nullptr, "null params");
+    return solve_with(ctx, {depth, depthPitch, scribble, scribblePitch, guide, guidePitch, guideKind, rows, cols, level, *params, {}}, info, nullptr);
 }
 
 }  // extern "C"
@@ -583,12 +592,20 @@ int rtdd_matrix_free_solver(rtdd_ctx *ctx, float *depth, size_t depthPitch, cons
     if (!ctx) return RTDD_ERR_INVALID;
     if (maxIterations < 0) maxIterations = 0;      // the reference's loop simply does not run (:295)
     const rtdd_solve_params p{RTDD_METHOD_CHEBYSHEV_JACOBI, maxIterations, /*tolerance=*/0.0f, /*checkEvery=*/0, /*relaxation=*/0.0f};
-    return solve_with(ctx, {depth, depthPitch, scribble, scribblePitch, gray, grayPitch, rows, cols, level, p, {}}, nullptr, nullptr);
+    return solve_with(ctx, {depth, depthPitch, scribble, scribblePitch, gray, grayPitch, RTDD_GUIDE_GRAY, rows, cols, level, p, {}}, nullptr, nullptr);
 }
 
 int rtdd_index_to_weight(rtdd_ctx *ctx, const uint8_t *gray, size_t grayPitch, const float *depth, size_t depthPitch,
                          int32_t *index2, int level, int rows, int cols) {
+    return rtdd_index_to_weight_guided(ctx, gray, grayPitch, RTDD_GUIDE_GRAY, depth, depthPitch, index2, level, rows, cols);
+}
+
+int rtdd_index_to_weight_guided(rtdd_ctx *ctx, const uint8_t *guide, size_t guidePitch, int guideKind, const float *depth, size_t depthPitch,
+                                int32_t *index2, int level, int rows, int cols) {
     if (!ctx) return RTDD_ERR_INVALID;
+    const uint8_t *gray = guide;
+    REQUIRE(ctx, guideKind == RTDD_GUIDE_GRAY || guideKind == RTDD_GUIDE_BGR, "unknown guide kind");
+    const size_t grayPitch = guideKind == RTDD_GUIDE_BGR ? guidePitch / 3 : guidePitch;       // (compared with cols below: pitch >= 3 * cols)
     REQUIRE(ctx, gray && depth && index2, "null pointer");
     REQUIRE(ctx, rows > 0 && cols > 0 && grayPitch >= (size_t)cols && depthPitch >= (size_t)cols * 4, "bad size or pitch");
     REQUIRE(ctx, f32_image_aligned(depth, depthPitch), kF32AlignText);
@@ -597,7 +614,7 @@ int rtdd_index_to_weight(rtdd_ctx *ctx, const uint8_t *gray, size_t grayPitch, c
     // reads a depth image a logged, unconfirmed solve may not have written (its copy-back stores nothing after a time-out) and is not
     // logged itself: confirm or heal first.  Nothing logged: nothing to wait for.
     RTDD_TRY(settle_pending(ctx));
-    return launch_index_to_weight(ctx, gray, grayPitch, depth, depthPitch, index2, level, rows, cols);
+    return launch_index_to_weight(ctx, guide, guidePitch, depth, depthPitch, index2, level, rows, cols, guideKind);
 }
 
 // ---- image processing ---------------------------------------------------------------------------

@@ -48,6 +48,31 @@ __global__ __launch_bounds__(256) void k_pyrdown_u8(const uint8_t *__restrict__ 
     dst[(size_t)y * dp + x] = (uint8_t)((s + 128) >> 8);
 }
 
+// The same filter on the three channels of an interleaved image (cv::pyrDown filters channels independently): the colour guide's chain
+__global__ __launch_bounds__(256) void k_pyrdown_bgr(const uint8_t *__restrict__ src, size_t sp, int rows, int cols,
+                                                     uint8_t *__restrict__ dst, size_t dp, int drows, int dcols) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + wave_id();
+    if (x >= dcols || y >= drows) return;
+    const int k[5] = {1, 4, 6, 4, 1};
+    int cx[5];
+#pragma unroll
+    for (int i = 0; i < 5; i++) cx[i] = 3 * reflect101(2 * x + i - 2, cols);
+    int s[3] = {0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+        const uint8_t *row = src + (size_t)reflect101(2 * y + j - 2, rows) * sp;
+        int h[3] = {0, 0, 0};
+#pragma unroll
+        for (int i = 0; i < 5; i++) {
+            const uint8_t *q = row + cx[i];
+            h[0] += k[i] * q[0]; h[1] += k[i] * q[1]; h[2] += k[i] * q[2];
+        }
+        s[0] += k[j] * h[0]; s[1] += k[j] * h[1]; s[2] += k[j] * h[2];
+    }
+    uint8_t *o = dst + (size_t)y * dp + 3 * (size_t)x;
+    o[0] = (uint8_t)((s[0] + 128) >> 8); o[1] = (uint8_t)((s[1] + 128) >> 8); o[2] = (uint8_t)((s[2] + 128) >> 8);
+}
+
 // f32 pyrUp as src/main.cpp:272-279 calls it, with the Dirichlet re-injection of GPUConvertToFloat (src/main.cpp:281-283,
 // src/GPUImageProcessing.cu:19) fused in.  The reference uses TWO OpenCV routines: cv::cuda::pyrUp when the destination is exactly
 // twice the source (main.cpp:273), the host's cv::pyrUp with the explicit size otherwise (main.cpp:277).  Both mirror at the
@@ -243,6 +268,12 @@ int launch_pyrdown_u8(rtdd_ctx *ctx, const uint8_t *src, size_t sp, int rows, in
     const int drows = (rows + 1) / 2, dcols = (cols + 1) / 2;
     hipLaunchKernelGGL(k_pyrdown_u8, grid64x4(drows, dcols), dim3(256), 0, ctx->stream, src, sp, rows, cols, dst, dp, drows, dcols);
     RTDD_LAUNCH_CHECK(ctx, "k_pyrdown_u8");
+    return RTDD_OK;
+}
+int launch_pyrdown_bgr(rtdd_ctx *ctx, const uint8_t *src, size_t sp, int rows, int cols, uint8_t *dst, size_t dp) {
+    const int drows = (rows + 1) / 2, dcols = (cols + 1) / 2;
+    hipLaunchKernelGGL(k_pyrdown_bgr, grid64x4(drows, dcols), dim3(256), 0, ctx->stream, src, sp, rows, cols, dst, dp, drows, dcols);
+    RTDD_LAUNCH_CHECK(ctx, "k_pyrdown_bgr");
     return RTDD_OK;
 }
 int launch_pyrup_inject(rtdd_ctx *ctx, const float *src, size_t sp, int rows, int cols, float *dst, size_t dp, int drows, int dcols,

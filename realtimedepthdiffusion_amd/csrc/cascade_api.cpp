@@ -23,6 +23,13 @@ struct Pyramid {
     int levels = 0, rows = 0, cols = 0;
     Image original, depth_u8, artistic;
     std::vector<Image> gray, scribble, edited, depth;
+    // The colour guide (rtdd_pyramid_set_guide): while `guide` is RTDD_GUIDE_BGR the per-level solves read level l's colour image instead
+    // of gray[l].  color[l], l >= 1: cv::pyrDown per channel of level l - 1, the ceil-sized chain of gray[]; level 0 is `original` itself
+    // (color[0] stays empty).  Allocated by the first request for BGR, kept from then on; a pyramid that never asks has none.
+    int guide = RTDD_GUIDE_GRAY;
+    std::vector<Image> color;
+    bool image_set = false;               // rtdd_pyramid_set_image has been called: there is something to build the chain from
+    const Image &guide_image(int kind, int l) const { return kind != RTDD_GUIDE_BGR ? gray[l] : l == 0 ? original : color[l]; }
     // The coarse annotation levels and the coarsest level's injection depend on the annotation only (src/main.cpp:249-259;
     // GPUPyrDownAnnotation only ever adds, SURVEY A.8, and the solver never moves a Dirichlet pixel): they are brought up to date
     // by the first estimate after the annotation changed, not by every estimate.
@@ -214,12 +221,23 @@ static void live_free(Pyramid *p) {
     p->live = nullptr;
 }
 
+// image b's colour chain: level l from level l - 1, per channel, behind whatever wrote `original` on the context's stream
+static int color_chain(rtdd_ctx *ctx, Pyramid *p, int b) {
+    for (int l = 1; l < p->levels; l++) {
+        const Image &src = l == 1 ? p->original : p->color[l - 1];
+        // (level 0 has the image's own size; the levels above it the ceil chain's, as gray[])
+        RTDD_TRY(launch_pyrdown_bgr(ctx, (const uint8_t *)src.at(b), src.pitch, l == 1 ? p->rows : src.rows, l == 1 ? p->cols : src.cols,
+                                    (uint8_t *)p->color[l].at(b), p->color[l].pitch));
+    }
+    return RTDD_OK;
+}
+
 void pyramid_free(rtdd_ctx *ctx) {
     if (!ctx->pyr) return;
     Pyramid *p = ctx->pyr;
     live_free(p);
     free_image(p->original); free_image(p->depth_u8); free_image(p->artistic);
-    for (auto *v : {&p->gray, &p->scribble, &p->edited, &p->depth})
+    for (auto *v : {&p->gray, &p->scribble, &p->edited, &p->depth, &p->color})
         for (auto &im : *v) free_image(im);
     delete p;
     ctx->pyr = nullptr;
@@ -328,7 +346,41 @@ int rtdd_pyramid_set_image(rtdd_ctx *ctx, const uint8_t *bgr, size_t pitch) {
     for (int l = 1; l < p->levels && rc == RTDD_OK; l++)
         rc = launch_pyrdown_u8(ctx, (const uint8_t *)p->gray[l - 1].at(b), p->gray[l - 1].pitch, p->gray[l - 1].rows, p->gray[l - 1].cols,
                                (uint8_t *)p->gray[l].at(b), p->gray[l].pitch);
+    p->image_set = true;
+    if (rc == RTDD_OK && p->guide == RTDD_GUIDE_BGR) rc = color_chain(ctx, p, b);
     return rc;
+}
+
+int rtdd_pyramid_guide(rtdd_ctx *ctx) { return ctx && ctx->pyr ? ctx->pyr->guide : RTDD_GUIDE_GRAY; }
+
+int rtdd_pyramid_set_guide(rtdd_ctx *ctx, int guideKind) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    if (!ctx->pyr) return fail(ctx, RTDD_ERR_STATE, "rtdd_pyramid_create has not been called");
+    Pyramid *p = ctx->pyr;
+    REQUIRE(ctx, guideKind == RTDD_GUIDE_GRAY || guideKind == RTDD_GUIDE_BGR, "unknown guide kind");
+    if (guideKind == p->guide) return RTDD_OK;
+    if (guideKind == RTDD_GUIDE_GRAY) { p->guide = RTDD_GUIDE_GRAY; return RTDD_OK; }      // (the colour levels stay allocated)
+    DeviceGuard g(ctx->device);
+    if (p->color.empty() && p->levels > 1) {            // the first request: every coarse level, or none (nothing has been launched yet)
+        std::vector<Image> lv(p->levels);
+        for (int l = 1; l < p->levels; l++) {
+            Image &im = lv[l];
+            im.rows = p->gray[l].rows; im.cols = p->gray[l].cols; im.elem = 3; im.images = p->images;
+            im.pitch = ((size_t)im.cols * 3 + 511) / 512 * 512;
+            im.stride = im.pitch * (size_t)(im.rows > 0 ? im.rows : 1);
+            const hipError_t e = hipMalloc(&im.ptr, im.stride * (size_t)im.images);
+            if (e != hipSuccess) {
+                im.ptr = nullptr;
+                for (auto &q : lv) free_image(q);
+                return fail(ctx, e == hipErrorOutOfMemory ? RTDD_ERR_NOMEM : RTDD_ERR_HIP, "hipMalloc(colour guide levels)", e);
+            }
+        }
+        p->color.swap(lv);
+    }
+    // the chain of every image of a batch, from the images as they are now (set_image keeps it up to date only while the guide is BGR)
+    if (p->image_set) for (int b = 0; b < p->images; b++) RTDD_TRY(color_chain(ctx, p, b));
+    p->guide = RTDD_GUIDE_BGR;
+    return RTDD_OK;
 }
 
 int rtdd_pyramid_set_annotation(rtdd_ctx *ctx, const uint8_t *annotation, size_t pitch) {
@@ -357,6 +409,10 @@ int rtdd_pyramid_image(rtdd_ctx *ctx, int kind, int level, void **ptr, size_t *p
         case RTDD_IMG_SCRIBBLE: im = &p->scribble[level]; break;
         case RTDD_IMG_EDITED: im = &p->edited[level]; break;
         case RTDD_IMG_DEPTH: im = &p->depth[level]; break;
+        case RTDD_IMG_GUIDE_BGR:
+            if (level > 0 && p->color.empty()) return fail(ctx, RTDD_ERR_STATE, "the colour guide's coarse levels do not exist: rtdd_pyramid_set_guide(RTDD_GUIDE_BGR) first");
+            im = level == 0 ? &p->original : &p->color[level];
+            break;
         default: break;
     }
     REQUIRE(ctx, im != nullptr, "no such pyramid image");
@@ -410,8 +466,8 @@ static int estimate_submit(rtdd_ctx *ctx, int maxIterations, unsigned long long 
     op.kind = PendingOp::kEstimate; op.opt = ctx->opt;
     PendingOp::Estimate &e = op.estimate;
     e.annotation = annotation; e.maxIterations = maxIterations;
-    e.batch_first = first; e.batch_n = n; e.live = live;
-    rc = estimate_levels(ctx, maxIterations, P - 1, e.level_seq, first, n, live);
+    e.batch_first = first; e.batch_n = n; e.live = live; e.guide = p->guide;
+    rc = estimate_levels(ctx, maxIterations, P - 1, e.level_seq, first, n, live, e.guide);
     if (rc == RTDD_OK && live.effect) rc = live_effect(ctx, live);      // src/main.cpp:190-230: the sticky effect, on this frame's map
     if (rc == RTDD_OK && log_call(ctx, op) && op_id) *op_id = op.id;
     return rc;
@@ -670,11 +726,12 @@ int rtdd_live_submit_ex(rtdd_ctx *ctx, const uint8_t *hostScribble, size_t scrib
 
 namespace rtdd {
 
-int estimate_levels(rtdd_ctx *ctx, int maxIterations, int from_level, int *level_seq, int first, int n, const LiveTargets &live) {
+int estimate_levels(rtdd_ctx *ctx, int maxIterations, int from_level, int *level_seq, int first, int n, const LiveTargets &live, int guide) {
     Pyramid *p = ctx->pyr;
     if (!p) return fail(ctx, RTDD_ERR_STATE, "the pyramid is gone");
     if (first < 0 || n < 1 || first + n > p->images) return fail(ctx, RTDD_ERR_INVALID, "images outside the pyramid's batch");
     const int P = p->levels;
+    if (guide == RTDD_GUIDE_BGR && P > 1 && p->color.empty()) return fail(ctx, RTDD_ERR_STATE, "the colour guide's levels are gone");
     if (from_level > P - 1) from_level = P - 1;
     int rc = RTDD_OK;
     for (int l = from_level; l >= 0 && rc == RTDD_OK; l--) {                   // src/main.cpp:261-288
@@ -693,7 +750,8 @@ int estimate_levels(rtdd_ctx *ctx, int maxIterations, int from_level, int *level
         }
         // the level of images first .. first + n - 1 in the same launches (blockIdx.z = image: Batch, rtdd_internal.hpp)
         t.batch.n = n; t.batch.first = first;
-        t.batch.depth = p->depth[l].stride; t.batch.scribble = p->scribble[l].stride; t.batch.gray = p->gray[l].stride;
+        const Image &gd = p->guide_image(guide, l);                              // gray[l], or level l of the colour chain
+        t.batch.depth = p->depth[l].stride; t.batch.scribble = p->scribble[l].stride; t.batch.gray = gd.stride;
         t.batch.u8 = p->depth_u8.stride;
         SolveOutcome done;
         if (solved) {
@@ -702,7 +760,7 @@ int estimate_levels(rtdd_ctx *ctx, int maxIterations, int from_level, int *level
             sp.method = RTDD_METHOD_CHEBYSHEV_JACOBI; sp.maxIterations = iters; sp.tolerance = 0.0f; sp.checkEvery = 0;
             sp.relaxation = 0.0f;
             rc = solve_with(ctx, {(float *)p->depth[l].at(first), p->depth[l].pitch, (const uint8_t *)p->scribble[l].at(first),
-                                  p->scribble[l].pitch, (const uint8_t *)p->gray[l].at(first), p->gray[l].pitch, p->depth[l].rows,
+                                  p->scribble[l].pitch, (const uint8_t *)gd.at(first), gd.pitch, guide, p->depth[l].rows,
                                   p->depth[l].cols, l, sp, t}, nullptr, &done);
             if (level_seq && l < 32) level_seq[l] = done.seq;
             if (rc == RTDD_OK) {
@@ -771,7 +829,7 @@ int estimate_replay(rtdd_ctx *ctx, const PendingOp::Estimate &e, int failed_seq)
         RTDD_TRY(annotation_pyramid(ctx, p, e.annotation == PendingOp::kAnnotationRebuilt));
         ctx->heal_rebuilt = true;
     }
-    int rc = from >= 0 ? estimate_levels(ctx, e.maxIterations, from, nullptr, e.batch_first, e.batch_n, e.live) : RTDD_OK;
+    int rc = from >= 0 ? estimate_levels(ctx, e.maxIterations, from, nullptr, e.batch_first, e.batch_n, e.live, e.guide) : RTDD_OK;
     if (rc == RTDD_OK && e.live.effect) rc = live_effect(ctx, e.live);
     return rc;
 }
@@ -792,8 +850,9 @@ int rtdd_refine_depth(rtdd_ctx *ctx, const rtdd_solve_params *params, rtdd_solve
     SolveTargets t;
     t.u8 = (uint8_t *)p->depth_u8.at(b); t.u8_pitch = p->depth_u8.pitch;
     t.batch.first = b;
+    const Image &gd = p->guide_image(p->guide, 0);
     return solve_with(ctx, {(float *)p->depth[0].at(b), p->depth[0].pitch, (const uint8_t *)p->scribble[0].at(b), p->scribble[0].pitch,
-                            (const uint8_t *)p->gray[0].at(b), p->gray[0].pitch, p->rows, p->cols, 0, *params, t}, info, nullptr);
+                            (const uint8_t *)gd.at(b), gd.pitch, p->guide, p->rows, p->cols, 0, *params, t}, info, nullptr);
 }
 
 int rtdd_bgr2gray(rtdd_ctx *ctx, const uint8_t *bgr, size_t bgrPitch, uint8_t *gray, size_t grayPitch, int rows, int cols) {
@@ -808,6 +867,13 @@ int rtdd_pyrdown_gray(rtdd_ctx *ctx, const uint8_t *src, size_t srcPitch, int ro
     REQUIRE(ctx, src && dst && rows > 0 && cols > 0 && srcPitch >= (size_t)cols && dstPitch >= (size_t)((cols + 1) / 2), "bad argument");
     DeviceGuard g(ctx->device);
     return launch_pyrdown_u8(ctx, src, srcPitch, rows, cols, dst, dstPitch);
+}
+
+int rtdd_pyrdown_bgr(rtdd_ctx *ctx, const uint8_t *src, size_t srcPitch, int rows, int cols, uint8_t *dst, size_t dstPitch) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    REQUIRE(ctx, src && dst && rows > 0 && cols > 0 && srcPitch >= (size_t)cols * 3 && dstPitch >= (size_t)((cols + 1) / 2) * 3, "bad argument");
+    DeviceGuard g(ctx->device);
+    return launch_pyrdown_bgr(ctx, src, srcPitch, rows, cols, dst, dstPitch);
 }
 
 int rtdd_pyrup_depth(rtdd_ctx *ctx, const float *src, size_t srcPitch, int rows, int cols, float *dst, size_t dstPitch, int dstRows,

@@ -56,7 +56,7 @@ struct Level {
 struct Batch {
     int n = 1;                            // images per launch
     int first = 0;                        // the first one's index in the context's batched allocations
-    size_t depth = 0, scribble = 0, gray = 0, u8 = 0;     // byte strides of the caller-side arguments of the solve in progress
+    size_t depth = 0, scribble = 0, gray = 0, u8 = 0;     // byte strides of the caller-side arguments of the solve in progress (gray: the guide's, gray or colour)
 };
 #define RTDD_Z(ptr, stride) ptr = (decltype(ptr))((const char *)(ptr) + (size_t)blockIdx.z * (size_t)(stride))
 
@@ -79,6 +79,7 @@ struct SolveCall {
     float *depth = nullptr; size_t depthPitch = 0;
     const uint8_t *scribble = nullptr; size_t scribblePitch = 0;
     const uint8_t *gray = nullptr; size_t grayPitch = 0;
+    int guide = RTDD_GUIDE_GRAY;                    // rtdd_guide: what `gray` points at -- a gray image, or (RTDD_GUIDE_BGR) the interleaved colour image
     int rows = 0, cols = 0, level = 0;
     rtdd_solve_params params{};
     SolveTargets targets;                           // (rtdd_refine_depth: the selected image of a batch, the u8 copy of the result)
@@ -191,6 +192,7 @@ struct PendingOp {
         int maxIterations = 0;
         int level_seq[32] = {};           // sequence number of level l's solve (0: the level is empty)
         int batch_first = 0, batch_n = 1; // the images of the context's batched pyramid the estimate covers
+        int guide = RTDD_GUIDE_GRAY;      // the guide the estimate ran with (rtdd_pyramid_set_guide): a replay uses it, not the pyramid's current one
         LiveTargets live;                 // a live frame: its annotation pair, its map's second target, its effect (scribble == nullptr: not one)
         // what the estimate did to the coarse annotation levels in front of its solves: kAnnotationNone (they were up to date),
         // kAnnotationAccumulated (GPUPyrDownAnnotation: only ever adds) or kAnnotationRebuilt (as if they had been all zero).  A replay
@@ -346,7 +348,7 @@ int launch_sweeps_blocked(rtdd_ctx *ctx, const Level &L, size_t ip, int rows, in
 // (seq: the solve's sequence number, reported by the kernel either as confirmed or as the first failed one; c.targets: the batch and the u8 targets)
 int launch_finish(rtdd_ctx *ctx, const Level &L, size_t ip, int src_plane, const SolveCall &c, int seq);
 int launch_index_to_weight(rtdd_ctx *ctx, const uint8_t *gray, size_t grayPitch, const float *depth, size_t depthPitch,
-                           int32_t *index2, int level, int rows, int cols);
+                           int32_t *index2, int level, int rows, int cols, int guide = RTDD_GUIDE_GRAY);
 int launch_residual(rtdd_ctx *ctx, const Level &L, size_t ip, int plane, int rows, int cols, float *host_out);
 int launch_rbgs(rtdd_ctx *ctx, const Level &L, size_t ip, int plane, int rows, int cols, int nsweeps, float omega);
 // ---- multigrid.hip ------------------------------------------------------------------------------
@@ -396,6 +398,7 @@ int launch_bokeh(rtdd_ctx *ctx, const Effect &e);
 // ---- cascade.hip -------------------------------------------------------------------------------
 int launch_bgr2gray(rtdd_ctx *ctx, const uint8_t *bgr, size_t bp, uint8_t *gray, size_t gp, int rows, int cols);
 int launch_pyrdown_u8(rtdd_ctx *ctx, const uint8_t *src, size_t sp, int rows, int cols, uint8_t *dst, size_t dp);
+int launch_pyrdown_bgr(rtdd_ctx *ctx, const uint8_t *src, size_t sp, int rows, int cols, uint8_t *dst, size_t dp);     // the same per channel of an interleaved image
 struct PyrupBatch { int n = 1; size_t src = 0, dst = 0, edited = 0, mask = 0, coarse = 0; };      // images and byte strides of a batched pyrUp
 int launch_pyrup_inject(rtdd_ctx *ctx, const float *src, size_t sp, int rows, int cols, float *dst, size_t dp, int drows, int dcols,
                         const uint8_t *edited, size_t ep, const uint8_t *mask, size_t mp, float *coarse_out = nullptr, size_t cp = 0,
@@ -421,7 +424,7 @@ int settle_pending(rtdd_ctx *ctx);      // before a call changes what the logged
 // the one place a call enters the log: kind, opt and the kind's record filled in by the caller, id assigned here; false: not logged
 bool log_call(rtdd_ctx *ctx, PendingOp &op);
 // cascade_api.cpp: levels from_level .. 0 of an estimate (src/main.cpp:261-291); level_seq (optional) receives each level's solve sequence number
-int estimate_levels(rtdd_ctx *ctx, int maxIterations, int from_level, int *level_seq, int first, int n, const LiveTargets &live);
+int estimate_levels(rtdd_ctx *ctx, int maxIterations, int from_level, int *level_seq, int first, int n, const LiveTargets &live, int guide);
 // api.cpp: rtdd_solve_ex with everything the library's own callers add to it (c.targets)
 int solve_with(rtdd_ctx *ctx, const SolveCall &c, rtdd_solve_info *info, SolveOutcome *out);
 // cascade_api.cpp: a live frame's effect (again, on a replay): RTDD_EFFECT_* on the pyramid's level-0 images into live.artistic

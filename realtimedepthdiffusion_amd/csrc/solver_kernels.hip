@@ -168,6 +168,154 @@ __global__ __launch_bounds__(256) void k_index_to_weight(const uint8_t *__restri
 }
 
 // ------------------------------------------------------------------------------------------------
+// The colour guide (extension, include/rtdd.h rtdd_solve_guided): the same passes with the guide read as interleaved BGR, 3 bytes per
+// pixel, and the index of an edge max(|dB|, |dG|, |dR|) -- an integer in [0, 255], a LUT index as it stands.  Gate, thresholds, stores,
+// the "wild depth" flag and the batch strides are k_prepare's.  A pixel travels as b | g << 8 | r << 16.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int bgr_at(const uint8_t *p) { return (int)p[0] | ((int)p[1] << 8) | ((int)p[2] << 16); }
+__device__ __forceinline__ int bgr_index(int p, int q) {
+    const int db = iabs((p & 255) - (q & 255)), dg = iabs(((p >> 8) & 255) - ((q >> 8) & 255)), dr = iabs((p >> 16) - (q >> 16));
+    return max(max(db, dg), dr);
+}
+
+__global__ __launch_bounds__(256) void k_prepare_bgr(const float *__restrict__ depth, size_t depthPitch,
+                                                     const uint8_t *__restrict__ scribble, size_t scribblePitch,
+                                                     const uint8_t *__restrict__ bgr, size_t bgrPitch,
+                                                     float *__restrict__ X0, float *__restrict__ X1,
+                                                     uint32_t *__restrict__ M, int ip, int rows, int cols, int gated, int thr,
+                                                     size_t zDepth, size_t zScribble, size_t zBgr, size_t zPlane, int *sync_words, int wild_seq) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + wave_id();
+    if (x >= cols || y >= rows) return;
+    RTDD_Z(depth, zDepth); RTDD_Z(scribble, zScribble); RTDD_Z(bgr, zBgr); RTDD_Z(X0, zPlane); RTDD_Z(X1, zPlane); RTDD_Z(M, zPlane);
+    const float *drow = (const float *)((const char *)depth + (size_t)y * depthPitch);
+    const uint8_t *crow = bgr + (size_t)y * bgrPitch + 3 * (size_t)x;
+    const float d = drow[x];
+    const int c = bgr_at(crow);
+    const bool dirichlet = scribble[(size_t)y * scribblePitch + x] == 255;
+    int right = 0, down = 0;
+    if (x + 1 < cols) {
+        right = bgr_index(c, bgr_at(crow + 3));
+        if (gated && !(iabs(sat_u8_dev(d) - sat_u8_dev(drow[x + 1])) > thr)) right = 0;
+    }
+    if (y + 1 < rows) {
+        down = bgr_index(c, bgr_at(crow + bgrPitch));
+        if (gated) {
+            const float dd = ((const float *)((const char *)depth + (size_t)(y + 1) * depthPitch))[x];
+            if (!(iabs(sat_u8_dev(d) - sat_u8_dev(dd)) > thr)) down = 0;
+        }
+    }
+    const size_t p = (size_t)y * ip + x;
+    if (depth_is_wild(d)) sync_words[kSyncWild] = wild_seq;
+    X0[p] = d;
+    X1[p] = dirichlet ? d : 0.0f;
+    M[p] = (uint32_t)right | ((uint32_t)down << 8) | (dirichlet ? kMetaDirichlet : 0u);
+}
+
+// Four pixels per thread, for a guide whose pointer, pitch and batch stride are multiples of 4 (depth and scribble as k_prepare4 wants
+// them): a thread's four pixels are the 12 bytes at 3 * x0, a 4-aligned address -- three dwords, no byte of which lies beyond pixel
+// x0 + 3 -- and the right neighbour's 3 bytes are read as a 2-byte and a 1-byte load (a dword there would reach one byte past the row's
+// last pixel).  The row below likewise.  The ragged end of a row: pixel by pixel.
+__device__ __forceinline__ void bgr_unpack4(const uint8_t *q, int (&c)[5]) {
+    const uint32_t *w = (const uint32_t *)q;
+    const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
+    c[0] = (int)(w0 & 0xFFFFFFu); c[1] = (int)((w0 >> 24) | ((w1 & 0xFFFFu) << 8));
+    c[2] = (int)((w1 >> 16) | ((w2 & 0xFFu) << 16)); c[3] = (int)(w2 >> 8);
+}
+
+__global__ __launch_bounds__(256) void k_prepare4_bgr(const float *__restrict__ depth, size_t depthPitch,
+                                                      const uint8_t *__restrict__ scribble, size_t scribblePitch,
+                                                      const uint8_t *__restrict__ bgr, size_t bgrPitch,
+                                                      float *__restrict__ X0, float *__restrict__ X1,
+                                                      uint32_t *__restrict__ M, int ip, int rows, int cols, int gated, int thr,
+                                                      size_t zDepth, size_t zScribble, size_t zBgr, size_t zPlane, int *sync_words, int wild_seq) {
+    const int x0 = 4 * (blockIdx.x * 64 + (threadIdx.x & 63));
+    const int y = blockIdx.y * 4 + wave_id();
+    if (x0 >= cols || y >= rows) return;
+    RTDD_Z(depth, zDepth); RTDD_Z(scribble, zScribble); RTDD_Z(bgr, zBgr); RTDD_Z(X0, zPlane); RTDD_Z(X1, zPlane); RTDD_Z(M, zPlane);
+    const float *drow = (const float *)((const char *)depth + (size_t)y * depthPitch);
+    const uint8_t *crow = bgr + (size_t)y * bgrPitch + 3 * (size_t)x0, *srow = scribble + (size_t)y * scribblePitch;
+    const bool down_ok = y + 1 < rows;
+    float d[5], dd[4];
+    int c[5], cd[5];
+    uint32_t sc;
+    if (x0 + 3 < cols) {
+        const float4 d4 = *(const float4 *)(drow + x0);
+        d[0] = d4.x; d[1] = d4.y; d[2] = d4.z; d[3] = d4.w;
+        bgr_unpack4(crow, c);
+        sc = *(const uint32_t *)(srow + x0);
+        if (down_ok) {
+            bgr_unpack4(crow + bgrPitch, cd);
+            if (gated) { const float4 e4 = *(const float4 *)((const float *)((const char *)depth + (size_t)(y + 1) * depthPitch) + x0); dd[0] = e4.x; dd[1] = e4.y; dd[2] = e4.z; dd[3] = e4.w; }
+        }
+    } else {                                       // ragged end of the row
+        sc = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const bool in = x0 + i < cols;
+            d[i] = in ? drow[x0 + i] : 0.0f; c[i] = in ? bgr_at(crow + 3 * i) : 0;
+            sc |= (uint32_t)(in ? srow[x0 + i] : 0) << (8 * i);
+            cd[i] = in && down_ok ? bgr_at(crow + bgrPitch + 3 * i) : 0;
+            dd[i] = in && down_ok && gated ? ((const float *)((const char *)depth + (size_t)(y + 1) * depthPitch))[x0 + i] : 0.0f;
+        }
+    }
+    const bool right_ok = x0 + 4 < cols;
+    d[4] = right_ok ? drow[x0 + 4] : 0.0f;
+    c[4] = right_ok ? (int)*(const uint16_t *)(crow + 12) | ((int)crow[14] << 16) : 0;
+    float x0v[4], x1v[4];
+    uint32_t mv[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const bool dirichlet = ((sc >> (8 * i)) & 255) == 255;
+        int right = 0, down = 0;
+        if (x0 + i + 1 < cols) {
+            right = bgr_index(c[i], c[i + 1]);
+            if (gated && !(iabs(sat_u8_dev(d[i]) - sat_u8_dev(d[i + 1])) > thr)) right = 0;
+        }
+        if (down_ok) {
+            down = bgr_index(c[i], cd[i]);
+            if (gated && !(iabs(sat_u8_dev(d[i]) - sat_u8_dev(dd[i])) > thr)) down = 0;
+        }
+        x0v[i] = d[i];
+        x1v[i] = dirichlet ? d[i] : 0.0f;
+        mv[i] = (uint32_t)right | ((uint32_t)down << 8) | (dirichlet ? kMetaDirichlet : 0u);
+    }
+    if (depth_is_wild(d[0]) || depth_is_wild(d[1]) || depth_is_wild(d[2]) || depth_is_wild(d[3])) sync_words[kSyncWild] = wild_seq;
+    const size_t p = (size_t)y * ip + x0;
+    *(float4 *)(X0 + p) = make_float4(x0v[0], x0v[1], x0v[2], x0v[3]);
+    *(float4 *)(X1 + p) = make_float4(x1v[0], x1v[1], x1v[2], x1v[3]);
+    *(uint4 *)(M + p) = make_uint4(mv[0], mv[1], mv[2], mv[3]);
+}
+
+// k_index_to_weight for a BGR guide: the reference's int2 format, for parity tests of the colour rule
+__global__ __launch_bounds__(256) void k_index_to_weight_bgr(const uint8_t *__restrict__ bgr, size_t bgrPitch,
+                                                             const float *__restrict__ depth, size_t depthPitch,
+                                                             int32_t *__restrict__ index2, int rows, int cols, int gated, int thr) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + wave_id();
+    if (x >= cols || y >= rows) return;
+    const int c = bgr_at(bgr + (size_t)y * bgrPitch + 3 * (size_t)x);
+    const float *drow = (const float *)((const char *)depth + (size_t)y * depthPitch);
+    const int d = gated ? sat_u8_dev(drow[x]) : 0;
+    int idx[4] = {256, 256, 256, 256};   // left right up down
+    const int dx[4] = {-1, 1, 0, 0}, dy[4] = {0, 0, -1, 1};
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int nx = x + dx[k], ny = y + dy[k];
+        if (nx < 0 || ny < 0 || nx >= cols || ny >= rows) continue;
+        int v = bgr_index(c, bgr_at(bgr + (size_t)ny * bgrPitch + 3 * (size_t)nx));
+        if (gated) {
+            const float nd = ((const float *)((const char *)depth + (size_t)ny * depthPitch))[nx];
+            if (!(iabs(d - sat_u8_dev(nd)) > thr)) v = 0;
+        }
+        idx[k] = v;
+    }
+    const size_t p = (size_t)y * cols + x;
+    index2[2 * p + 0] = idx[0] * 1000 + idx[1];
+    index2[2 * p + 1] = idx[2] * 1000 + idx[3];
+}
+
+// ------------------------------------------------------------------------------------------------
 // One pixel of one sweep: solveDiffusion (src/GPUSolver.cu:73-106) + the Chebyshev update (:257-260)
 // ------------------------------------------------------------------------------------------------
 template <bool CONTRACT>
@@ -408,24 +556,23 @@ int launch_prepare(rtdd_ctx *ctx, const Level &L, size_t ip, const SolveCall &c)
     const int thr = c.level == 0 ? 0 : 4;
     // (B.n = 1: one image, strides unused; L is already image B.first's view)
     const size_t zP = L.elems * sizeof(float);
+    // (c.gray: the guide -- a gray image, or with RTDD_GUIDE_BGR the interleaved colour image; the alignment rule is the same)
     const bool aligned = ((uintptr_t)c.depth % 16 == 0) && c.depthPitch % 16 == 0 && ((uintptr_t)c.gray % 4 == 0) && c.grayPitch % 4 == 0 &&
                          ((uintptr_t)c.scribble % 4 == 0) && c.scribblePitch % 4 == 0 && B.depth % 16 == 0 && B.gray % 4 == 0 && B.scribble % 4 == 0;
-    if (aligned)
-        hipLaunchKernelGGL(k_prepare4, grid64x4(c.rows, (c.cols + 3) / 4, B.n), dim3(256), 0, ctx->stream, c.depth, c.depthPitch, c.scribble, c.scribblePitch,
-                           c.gray, c.grayPitch, L.P(0, ip), L.P(1, ip), L.M(ip), (int)ip, c.rows, c.cols, gated, thr, B.depth, B.scribble, B.gray, zP, ctx->sync_words, ctx->wild_seq);
-    else
-        hipLaunchKernelGGL(k_prepare, grid64x4(c.rows, c.cols, B.n), dim3(256), 0, ctx->stream, c.depth, c.depthPitch, c.scribble, c.scribblePitch,
-                           c.gray, c.grayPitch, L.P(0, ip), L.P(1, ip), L.M(ip), (int)ip, c.rows, c.cols, gated, thr, B.depth, B.scribble, B.gray, zP, ctx->sync_words, ctx->wild_seq);
+    const dim3 grid = aligned ? grid64x4(c.rows, (c.cols + 3) / 4, B.n) : grid64x4(c.rows, c.cols, B.n);
+    auto *kernel = c.guide == RTDD_GUIDE_BGR ? (aligned ? k_prepare4_bgr : k_prepare_bgr) : (aligned ? k_prepare4 : k_prepare);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, ctx->stream, c.depth, c.depthPitch, c.scribble, c.scribblePitch,
+                       c.gray, c.grayPitch, L.P(0, ip), L.P(1, ip), L.M(ip), (int)ip, c.rows, c.cols, gated, thr, B.depth, B.scribble, B.gray, zP, ctx->sync_words, ctx->wild_seq);
     RTDD_LAUNCH_CHECK(ctx, "k_prepare");
     return RTDD_OK;
 }
 
 int launch_index_to_weight(rtdd_ctx *ctx, const uint8_t *gray, size_t grayPitch, const float *depth, size_t depthPitch,
-                           int32_t *index2, int level, int rows, int cols) {
+                           int32_t *index2, int level, int rows, int cols, int guide) {
     const int gated = level != ctx->maxLevel;
     const int thr = level == 0 ? 0 : 4;
-    hipLaunchKernelGGL(k_index_to_weight, grid64x4(rows, cols), dim3(256), 0, ctx->stream, gray, grayPitch, depth, depthPitch,
-                       index2, rows, cols, gated, thr);
+    hipLaunchKernelGGL(guide == RTDD_GUIDE_BGR ? k_index_to_weight_bgr : k_index_to_weight, grid64x4(rows, cols), dim3(256), 0, ctx->stream, gray, grayPitch,
+                       depth, depthPitch, index2, rows, cols, gated, thr);
     RTDD_LAUNCH_CHECK(ctx, "k_index_to_weight");
     return RTDD_OK;
 }
