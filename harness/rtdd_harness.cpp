@@ -185,12 +185,15 @@ static bool write_image(const std::string &path, int w, int h, int ch, const uns
 #define CK(call) do { int rc_ = (call); if (rc_ != RTDD_OK) { std::printf("%s: %s (%s)\n", #call, rtdd_status_string(rc_), rtdd_last_error(ctx)); return rc_; } } while (0)
 
 struct Paint { int x, y, label, radius, frame; };      // frame: --paint-at (live mode: in front of that frame); --paint: before the first estimate
-struct LiveStroke { rtdd_stroke s; int frame; };        // --stroke-at / --erase-at: in front of live frame `frame`
+struct LiveStroke { rtdd_ramp_stroke s; int frame; };   // --stroke-at / --erase-at / --ramp-at: in front of live frame `frame`
 struct Job {
     Pnm bgr, ann;                 // bgr is BGR-interleaved like cv::imread's Mat
     bool has_ann = false;
     std::vector<Paint> paints, live_paints;
-    std::vector<rtdd_stroke> strokes;         // --stroke / --erase, in command-line order: ONE rtdd_paint_strokes call, after the --paint stamps
+    // --stroke / --erase / --ramp, in command-line order, as ramp records (a constant stroke: label0 == label1): ONE call after the --paint
+    // stamps -- rtdd_paint_ramp_strokes when a --ramp is among them, rtdd_paint_strokes otherwise
+    std::vector<rtdd_ramp_stroke> strokes;
+    bool has_ramp = false;
     std::vector<LiveStroke> live_strokes;
     std::string effect;
     int iters = 1000;
@@ -227,25 +230,30 @@ struct Job {
     bool edges_color = false;     // --edges color: the estimates read their edge weights from the BGR image (rtdd_pyramid_set_guide); default gray: the reference's
 };
 
-// --stroke / --erase: the job's strokes on a device image pair, one call
-static int paint_strokes(rtdd_ctx *ctx, const std::vector<rtdd_stroke> &strokes, void *ed, size_t ed_pitch, void *scr, size_t scr_pitch, const void *orig, size_t orig_pitch,
-                         int rows, int cols) {
-    if (strokes.empty()) return RTDD_OK;
-    CK(rtdd_paint_strokes(ctx, strokes.data(), (int)strokes.size(), (uint8_t *)ed, ed_pitch, (uint8_t *)scr, scr_pitch, (const uint8_t *)orig, orig_pitch, rows, cols));
+// --stroke / --erase / --ramp: the job's strokes on a device image pair, one call
+static int paint_strokes(rtdd_ctx *ctx, const Job &job, void *ed, size_t ed_pitch, void *scr, size_t scr_pitch, const void *orig, size_t orig_pitch, int rows, int cols) {
+    if (job.strokes.empty()) return RTDD_OK;
+    if (job.has_ramp) {
+        CK(rtdd_paint_ramp_strokes(ctx, job.strokes.data(), (int)job.strokes.size(), (uint8_t *)ed, ed_pitch, (uint8_t *)scr, scr_pitch, (const uint8_t *)orig, orig_pitch, rows, cols));
+        return RTDD_OK;
+    }
+    std::vector<rtdd_stroke> plain;
+    for (const rtdd_ramp_stroke &q : job.strokes) plain.push_back(rtdd_stroke{q.x0, q.y0, q.x1, q.y1, q.radius, q.brush, q.label0});
+    CK(rtdd_paint_strokes(ctx, plain.data(), (int)plain.size(), (uint8_t *)ed, ed_pitch, (uint8_t *)scr, scr_pitch, (const uint8_t *)orig, orig_pitch, rows, cols));
     return RTDD_OK;
 }
 
-// rtdd_paint_strokes restated for the host's own image pair (--live: the host owns the pair every frame uploads; include/rtdd.h has the
+// rtdd_paint_ramp_strokes (with label0 == label1: rtdd_paint_strokes) restated for the host's own image pair (--live: the host owns the pair every frame uploads; include/rtdd.h has the
 // rules).  Dense images; `orig` is the BGR image.  Returns whether a stroke erased.
-static bool host_strokes(const std::vector<rtdd_stroke> &strokes, unsigned char *scr, unsigned char *ed, const unsigned char *orig, int rows, int cols) {
+static bool host_strokes(const std::vector<rtdd_ramp_stroke> &strokes, unsigned char *scr, unsigned char *ed, const unsigned char *orig, int rows, int cols) {
     typedef long long i64; typedef unsigned long long u64;
     bool erased = false;
-    for (const rtdd_stroke &q : strokes) {
+    for (const rtdd_ramp_stroke &q : strokes) {
         const int h = q.radius / 2;
         const int xa = std::max(std::min(q.x0, q.x1) - h, 0), xb = std::min(std::max(q.x0, q.x1) + h, cols - 1);
         const int ya = std::max(std::min(q.y0, q.y1) - h, 0), yb = std::min(std::max(q.y0, q.y1) + h, rows - 1);
         const i64 dx = q.x1 - q.x0, dy = q.y1 - q.y0, dd = dx * dx + dy * dy, r2 = (i64)q.radius * q.radius;
-        erased = erased || q.label == RTDD_STROKE_ERASE;
+        erased = erased || q.label0 == RTDD_STROKE_ERASE;
         for (int y = ya; y <= yb; y++)
             for (int x = xa; x <= xb; x++) {
                 const i64 vx = x - q.x0, vy = y - q.y0, cross = dx * vy - dy * vx, t = vx * dx + vy * dy;
@@ -257,20 +265,24 @@ static bool host_strokes(const std::vector<rtdd_stroke> &strokes, unsigned char 
                 else in = 2 * ac < (1ull << 32) && (2 * ac) * (2 * ac) <= (u64)r2 * (u64)dd;      // (beyond 2^32 the square exceeds radius^2 |d|^2 <= 2^54)
                 if (!in) continue;
                 const size_t i = (size_t)y * cols + x;
-                if (q.label == RTDD_STROKE_ERASE) { scr[i] = 0; for (int c = 0; c < 3; c++) ed[3 * i + c] = orig[3 * i + c]; }
-                else { scr[i] = 255; for (int c = 0; c < 3; c++) ed[3 * i + c] = (unsigned char)q.label; }
+                if (q.label0 == RTDD_STROKE_ERASE) { scr[i] = 0; for (int c = 0; c < 3; c++) ed[3 * i + c] = orig[3 * i + c]; continue; }
+                i64 label = q.label0;                                   // the ramp: the label at the foot of the perpendicular, rounded half up
+                if (dd != 0) { const i64 tc = std::min(std::max(t, (i64)0), dd); label = (2 * (q.label0 * (dd - tc) + q.label1 * tc) + dd) / (2 * dd); }
+                scr[i] = 255; for (int c = 0; c < 3; c++) ed[3 * i + c] = (unsigned char)label;
             }
     }
     return erased;
 }
 
-// "x0,y0,x1,y1,label,radius[,round]" (erase: no label), with "F:" in front when `frame` is asked for
-static bool parse_stroke(const char *arg, bool erase, rtdd_stroke *q, int *frame) {
+// "x0,y0,x1,y1,label,radius[,round]" (kind 'e', erase: no label; kind 'r', ramp: label0,label1), with "F:" in front when `frame` is asked for
+static bool parse_stroke(const char *arg, char kind, rtdd_ramp_stroke *q, int *frame) {
     int n = 0;
     if (frame) { if (std::sscanf(arg, "%d:%n", frame, &n) != 1 || n == 0) return false; arg += n; n = 0; }
-    q->label = RTDD_STROKE_ERASE; q->brush = RTDD_BRUSH_SQUARE;
-    if (erase ? std::sscanf(arg, "%d,%d,%d,%d,%d%n", &q->x0, &q->y0, &q->x1, &q->y1, &q->radius, &n) != 5
-              : std::sscanf(arg, "%d,%d,%d,%d,%d,%d%n", &q->x0, &q->y0, &q->x1, &q->y1, &q->label, &q->radius, &n) != 6) return false;
+    q->label0 = RTDD_STROKE_ERASE; q->brush = RTDD_BRUSH_SQUARE;
+    if (kind == 'e' ? std::sscanf(arg, "%d,%d,%d,%d,%d%n", &q->x0, &q->y0, &q->x1, &q->y1, &q->radius, &n) != 5
+        : kind == 'r' ? std::sscanf(arg, "%d,%d,%d,%d,%d,%d,%d%n", &q->x0, &q->y0, &q->x1, &q->y1, &q->label0, &q->label1, &q->radius, &n) != 7
+                      : std::sscanf(arg, "%d,%d,%d,%d,%d,%d%n", &q->x0, &q->y0, &q->x1, &q->y1, &q->label0, &q->radius, &n) != 6) return false;
+    if (kind != 'r') q->label1 = q->label0;
     if (!std::strcmp(arg + n, ",round")) q->brush = RTDD_BRUSH_ROUND;
     else if (arg[n] != 0 && std::strcmp(arg + n, ",square")) return false;
     return true;
@@ -350,7 +362,7 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
             for (const Paint &p : job.paints) CK(rtdd_paint_image(ctx, p.x, p.y, p.label, p.radius, (uint8_t *)pe, pie, (uint8_t *)ps, pis, rows, cols));
             void *po; size_t pio;
             CK(rtdd_pyramid_image(ctx, RTDD_IMG_ORIGINAL, 0, &po, &pio, nullptr, nullptr));
-            CK(paint_strokes(ctx, job.strokes, pe, pie, ps, pis, po, pio, rows, cols));
+            CK(paint_strokes(ctx, job, pe, pie, ps, pis, po, pio, rows, cols));
         }
         CK(rtdd_estimate_depth_batch(ctx, job.iters));                  // main.cpp:239-291, for every image
         depth_u8->resize((size_t)rows * cols);
@@ -401,7 +413,7 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
         }
         for (const Paint &p : job.paints)
             CK(rtdd_paint_image(ctx, p.x, p.y, p.label, p.radius, (uint8_t *)p_ed, pi_ed, (uint8_t *)p_scr, pi_scr, rows, cols));
-        CK(paint_strokes(ctx, job.strokes, p_ed, pi_ed, p_scr, pi_scr, p_orig, pi_orig, rows, cols));
+        CK(paint_strokes(ctx, job, p_ed, pi_ed, p_scr, pi_scr, p_orig, pi_orig, rows, cols));
         CK(rtdd_host_alloc(&h_scr.p, (size_t)rows * cols)); CK(rtdd_host_alloc(&h_ed.p, (size_t)rows * cols * 3));
         CK(rtdd_host_alloc(&h_u8[0].p, (size_t)rows * cols)); CK(rtdd_host_alloc(&h_u8[1].p, (size_t)rows * cols));
         CK(rtdd_download(ctx, h_scr.p, cols, p_scr, pi_scr, cols, rows));            // the host's Mats (main.cpp:160-168: decoded on the host there)
@@ -434,7 +446,7 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
             }
             // --stroke-at / --erase-at: the host owns the pair every frame uploads, so the strokes go onto the HOST images (the frames in
             // flight, which are still being uploaded from them, land first); after an erase the coarse levels are built afresh
-            std::vector<rtdd_stroke> now;
+            std::vector<rtdd_ramp_stroke> now;
             for (const LiveStroke &q : job.live_strokes) if (q.frame == n) now.push_back(q.s);
             if (!now.empty()) {
                 while (rtdd_live_pending(ctx) > 0) { const int f = n - rtdd_live_pending(ctx); CK(rtdd_live_wait(ctx)); landed(f); }
@@ -464,7 +476,7 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
             }
             for (const Paint &p : job.paints)                           // main.cpp:55-57
                 CK(rtdd_paint_image(ctx, p.x, p.y, p.label, p.radius, (uint8_t *)p_ed, pi_ed, (uint8_t *)p_scr, pi_scr, rows, cols));
-            CK(paint_strokes(ctx, job.strokes, p_ed, pi_ed, p_scr, pi_scr, p_orig, pi_orig, rows, cols));
+            CK(paint_strokes(ctx, job, p_ed, pi_ed, p_scr, pi_scr, p_orig, pi_orig, rows, cols));
         }
         CK(rtdd_estimate_depth(ctx, job.iters));                        // main.cpp:239-291
         if (!job.refine.empty()) {                                      // extension: converge the finest level
@@ -543,7 +555,8 @@ int main(int argc, const char *argv[]) {
                                  "                    [relight's light flags] [--shadows N (256)] [--shadow-bias B] [--shadow-softness S] [--shadow-strength T] [--ao R (16)] [--ao-directions 4|8] [--ao-bias B] [--ao-strength T] (lighting: shade, cast shadows and occlusion in one call)\n"
                                  "                    [--paint x,y,label,radius]... [--live N [--paint-at frame:x,y,label,radius]...] [--devices D --batch B [--sequential] [--write-all]] [--png] [--cold] [--edges gray|color]\n"
                                  "                    [--stroke x0,y0,x1,y1,label,radius[,round]]... [--erase x0,y0,x1,y1,radius[,round]]...   (segments, in command-line order, one rtdd_paint_strokes call after --paint)\n"
-                                 "                    [--stroke-at frame:x0,y0,x1,y1,label,radius[,round]]... [--erase-at frame:x0,y0,x1,y1,radius[,round]]...   (--live: in front of that frame)\n"
+                                 "                    [--ramp x0,y0,x1,y1,label0,label1,radius[,round]]...   (a depth ramp: label0 at x0,y0 to label1 at x1,y1; in order with --stroke / --erase, all of them one rtdd_paint_ramp_strokes call)\n"
+                                 "                    [--stroke-at frame:x0,y0,x1,y1,label,radius[,round]]... [--erase-at frame:x0,y0,x1,y1,radius[,round]]... [--ramp-at frame:x0,y0,x1,y1,label0,label1,radius[,round]]...   (--live: in front of that frame)\n"
                                  "       rtdd_harness --convert in.(jpg|png|ppm|pgm) out.(png|ppm|pgm)   (JPEG / 8-bit PNG / PNM -> PNG / PNM, no GPU)\n"); return 0; }
     if (argc == 4 && !std::strcmp(argv[1], "--convert")) {               // file format conversion only (no GPU): JPEG / PNG / PNM -> PNG / PNM
         Pnm im;
@@ -577,14 +590,19 @@ int main(int argc, const char *argv[]) {
         else if (!std::strcmp(argv[i], "--png")) png = true;                       // DepthMap.png / ArtisticEffect.png like the reference
         else if (!std::strcmp(argv[i], "--paint")) { Paint p{0, 0, 0, 0, -1}; if (std::sscanf(next(), "%d,%d,%d,%d", &p.x, &p.y, &p.label, &p.radius) == 4) job.paints.push_back(p); }
         else if (!std::strcmp(argv[i], "--paint-at")) { Paint p{0, 0, 0, 0, 0}; if (std::sscanf(next(), "%d:%d,%d,%d,%d", &p.frame, &p.x, &p.y, &p.label, &p.radius) == 5) job.live_paints.push_back(p); }
+        else if (!std::strcmp(argv[i], "--ramp") || !std::strcmp(argv[i], "--ramp-at")) {
+            const bool at = argv[i][6] != 0; LiveStroke q; q.frame = -1;
+            if (!parse_stroke(next(), 'r', &q.s, at ? &q.frame : nullptr)) { std::printf("%s\n", at ? "--ramp-at wants frame:x0,y0,x1,y1,label0,label1,radius[,round]" : "--ramp wants x0,y0,x1,y1,label0,label1,radius[,round]"); return 1; }
+            if (at) job.live_strokes.push_back(q); else { job.strokes.push_back(q.s); job.has_ramp = true; }
+        }
         else if (!std::strcmp(argv[i], "--stroke") || !std::strcmp(argv[i], "--erase")) {
-            const bool erase = argv[i][2] == 'e'; rtdd_stroke q;
-            if (!parse_stroke(next(), erase, &q, nullptr)) { std::printf("%s\n", erase ? "--erase wants x0,y0,x1,y1,radius[,round]" : "--stroke wants x0,y0,x1,y1,label,radius[,round]"); return 1; }
+            const bool erase = argv[i][2] == 'e'; rtdd_ramp_stroke q;
+            if (!parse_stroke(next(), erase ? 'e' : 's', &q, nullptr)) { std::printf("%s\n", erase ? "--erase wants x0,y0,x1,y1,radius[,round]" : "--stroke wants x0,y0,x1,y1,label,radius[,round]"); return 1; }
             job.strokes.push_back(q);
         }
         else if (!std::strcmp(argv[i], "--stroke-at") || !std::strcmp(argv[i], "--erase-at")) {
             const bool erase = argv[i][2] == 'e'; LiveStroke q;
-            if (!parse_stroke(next(), erase, &q.s, &q.frame)) { std::printf("%s\n", erase ? "--erase-at wants frame:x0,y0,x1,y1,radius[,round]" : "--stroke-at wants frame:x0,y0,x1,y1,label,radius[,round]"); return 1; }
+            if (!parse_stroke(next(), erase ? 'e' : 's', &q.s, &q.frame)) { std::printf("%s\n", erase ? "--erase-at wants frame:x0,y0,x1,y1,radius[,round]" : "--stroke-at wants frame:x0,y0,x1,y1,label,radius[,round]"); return 1; }
             job.live_strokes.push_back(q);
         }
         else if (!std::strcmp(argv[i], "--focus")) { job.focus_depth = (float)std::atof(next()); job.focus_x = -1; }

@@ -333,6 +333,48 @@ int rtdd_paint_strokes(rtdd_ctx *ctx, const rtdd_stroke *strokes /* HOST array *
                        const uint8_t *original, size_t originalPitch, /* may be NULL when no stroke erases */
                        int rows, int cols);
 
+/* Depth-ramp strokes (extension; no reference behaviour; found by symbol like rtdd_paint_strokes, no version bump): a stroke whose label
+ * runs linearly from label0 at (x0, y0) to label1 at (x1, y1) -- a floor, a road or a wall seen at an angle in ONE stroke.
+ * Everything but the label is rtdd_paint_strokes: the coverage rule of both brushes, array order (the last stroke covering a pixel decides
+ * it), a painted pixel gets edited = (L, L, L), scribble = 255, an erased one (label0 == label1 == RTDD_STROKE_ERASE) edited = original,
+ * scribble = 0, uncovered pixels are not written; `strokes` is a HOST array read before the call returns; 256 strokes per launch over the
+ * strokes' bounding box; on the pyramid's own level-0 pair the call notes the change itself and asks for rtdd_pyramid_annotation_rebuild
+ * when a stroke erases; a retired level-0 pointer of live mode: RTDD_ERR_STATE.
+ * The label L of a covered pixel p of a painting stroke, with d = p1 - p0, v = p - p0, dd = d.d, in exact integer arithmetic:
+ *   dd == 0 (a stamp):  L = label0
+ *   otherwise:          t = min(max(v.d, 0), dd)
+ *                       N = 2 * (label0 * (dd - t) + label1 * t) + dd          (>= 0)
+ *                       L = N / (2 * dd)                                       (C division: round half up; 0 <= L <= 255)
+ * i.e. the label at the foot of the perpendicular from p, rounded to nearest, ties up.  Beyond either end of the segment (the caps of a
+ * round brush, the corners of a square one) the label is that end's.  The rule is symmetric: (p1, p0, label1, label0) paints the same
+ * bytes.  On the documented domain dd < 2^35 inside a stroke's grown box and N < 2^45.  With label0 == label1 the call is
+ * rtdd_paint_strokes byte for byte.
+ * Refused (RTDD_ERR_INVALID) before any launch, the images untouched: what rtdd_paint_strokes refuses, each of the two labels outside
+ * [-1, 255], and exactly ONE of the two labels being RTDD_STROKE_ERASE (an eraser has no ramp). */
+typedef struct rtdd_ramp_stroke {
+    int x0, y0, x1, y1;             /* as rtdd_stroke */
+    int radius, brush;              /* as rtdd_stroke */
+    int label0, label1;             /* the label at (x0, y0) and at (x1, y1): both in 0..255, or both RTDD_STROKE_ERASE */
+} rtdd_ramp_stroke;
+int rtdd_paint_ramp_strokes(rtdd_ctx *ctx, const rtdd_ramp_stroke *strokes /* HOST array */, int count,
+                            uint8_t *edited, size_t editedPitch, uint8_t *scribble, size_t scribblePitch,
+                            const uint8_t *original, size_t originalPitch, /* may be NULL when no stroke erases */
+                            int rows, int cols);
+
+/* A mouse drag as ONE continuous ramp: the n points xy[0..2n-1] (x, y, x, y ...) become max(n - 1, 1) records whose labels are spread
+ * from label0 at the first point to label1 at the last BY ARC LENGTH.  Host arithmetic only: no context, no launch.
+ *   s_0 = 0, s_i = s_(i-1) + sqrt((double)dd_i) accumulated in index order (dd_i the squared length of segment i - 1 .. i), S = s_(n-1);
+ *   vertex label l_i = S > 0 ? (int)floor(label0 + (label1 - label0) * (s_i / S) + 0.5) : label0  (doubles; the quotient, the product and
+ *   the two sums each rounded on their own, never fused);
+ *   segment i gets (l_i, l_(i+1)): neighbouring segments share their vertex label, l_0 == label0, l_(n-1) == label1 when S > 0.
+ * n == 1 gives one stamp with both labels label0.  At a joint of a ROUND polyline the later segment's cap repaints up to radius / 2 pixels
+ * of the earlier segment's body with the joint's own label (the cap's label is its end's): a deviation of at most the label change over
+ * radius / 2 pixels of the earlier segment, on the inner side of the bend.
+ * RTDD_ERR_INVALID: null xy or out; n < 1 or n > 4097; a coordinate, radius or brush rtdd_paint_ramp_strokes would refuse; a label outside
+ * [0, 255] (RTDD_STROKE_ERASE too: an eraser has no ramp). */
+int rtdd_ramp_polyline(const int *xy /* n points: x, y, x, y ... */, int n, int radius, int brush,
+                       int label0, int label1, rtdd_ramp_stroke *out /* max(n - 1, 1) records */);
+
 /* ---- depth effects (include/GPUDepthEffect.h:4-9) ------------------------------------------ */
 
 /* GPUSimulateDefocus -- src/GPUDepthEffect.cu:29-72,105-113 (exact, via an integer summed-area table). */

@@ -52,7 +52,7 @@ C_ABI_SYMBOLS = [
     "rtdd_live_submit", "rtdd_live_wait", "rtdd_live_pending", "rtdd_host_alloc", "rtdd_host_free",
     "rtdd_pyramid_create_batch", "rtdd_pyramid_select", "rtdd_pyramid_batch", "rtdd_estimate_depth_batch", "rtdd_pyramid_level_info", "rtdd_live_submit_ex",
     "rtdd_simulate_refocus", "rtdd_simulate_haze_ex", "rtdd_simulate_stereo", "rtdd_simulate_lens_blur",
-    "rtdd_paint_strokes", "rtdd_pyramid_annotation_rebuild",
+    "rtdd_paint_strokes", "rtdd_pyramid_annotation_rebuild", "rtdd_paint_ramp_strokes", "rtdd_ramp_polyline",
     "rtdd_simulate_relight", "rtdd_simulate_relight_shadowed", "rtdd_simulate_parallax", "rtdd_simulate_ambient_occlusion",
     "rtdd_simulate_lighting", "rtdd_simulate_bokeh",
     "rtdd_solve_guided", "rtdd_index_to_weight_guided", "rtdd_pyrdown_bgr", "rtdd_pyramid_set_guide", "rtdd_pyramid_guide",
@@ -97,6 +97,24 @@ class SolveInfo(C.Structure):
 class Stroke(C.Structure):
     """rtdd_stroke: the segment (x0, y0)-(x1, y1), `radius` (the reference's scribbleRadius: a diameter), BRUSH_*, label 0..255 or STROKE_ERASE."""
     _fields_ = [("x0", C.c_int), ("y0", C.c_int), ("x1", C.c_int), ("y1", C.c_int), ("radius", C.c_int), ("brush", C.c_int), ("label", C.c_int)]
+
+
+class RampStroke(C.Structure):
+    """rtdd_ramp_stroke: a Stroke whose label runs linearly from label0 at (x0, y0) to label1 at (x1, y1) (both STROKE_ERASE: an eraser)."""
+    _fields_ = [("x0", C.c_int), ("y0", C.c_int), ("x1", C.c_int), ("y1", C.c_int), ("radius", C.c_int), ("brush", C.c_int),
+                ("label0", C.c_int), ("label1", C.c_int)]
+
+
+def ramp_polyline(points, radius, brush, label0, label1):
+    """rtdd_ramp_polyline: the points [(x, y), ...] of a drag as a list of 8-tuples (x0, y0, x1, y1, radius, brush, label0, label1) for
+    Context.paint_ramp_strokes, the labels spread from label0 to label1 by arc length.  Host arithmetic: needs no context and no device."""
+    n = len(points)
+    xy = (C.c_int * max(2 * n, 1))(*[int(v) for p in points for v in p])
+    out = (RampStroke * max(n - 1, 1))()
+    rc = lib().rtdd_ramp_polyline(xy, C.c_int(n), C.c_int(radius), C.c_int(brush), C.c_int(label0), C.c_int(label1), out)
+    if rc != RTDD_OK:
+        raise RtddError(rc, lib().rtdd_status_string(rc).decode() + " -- rtdd_ramp_polyline")
+    return [(q.x0, q.y0, q.x1, q.y1, q.radius, q.brush, q.label0, q.label1) for q in out]
 
 
 class Light(C.Structure):
@@ -374,6 +392,14 @@ class Context:
         e, ep = _img(edited); s, sp = _img(scribble)
         o, op = _img(original) if original is not None else (None, C.c_size_t(0))
         self._check(lib().rtdd_paint_strokes(self._h, arr, C.c_int(len(strokes)), e, ep, s, sp, o, op, C.c_int(rows), C.c_int(cols)))
+
+    def paint_ramp_strokes(self, strokes, edited, scribble, rows, cols, original=None):
+        """rtdd_paint_ramp_strokes: `strokes` (RampStroke objects or 8-tuples x0, y0, x1, y1, radius, brush, label0, label1) in order, one
+        call; `original` is needed when a stroke erases."""
+        arr = (RampStroke * max(len(strokes), 1))(*[q if isinstance(q, RampStroke) else RampStroke(*q) for q in strokes])
+        e, ep = _img(edited); s, sp = _img(scribble)
+        o, op = _img(original) if original is not None else (None, C.c_size_t(0))
+        self._check(lib().rtdd_paint_ramp_strokes(self._h, arr, C.c_int(len(strokes)), e, ep, s, sp, o, op, C.c_int(rows), C.c_int(cols)))
 
     # ---- include/GPUDepthEffect.h
     def GPUSimulateDefocus(self, originalImage, depthImage, artisticImage, rows, cols):

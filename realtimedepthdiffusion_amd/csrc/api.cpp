@@ -689,5 +689,72 @@ int rtdd_paint_strokes(rtdd_ctx *ctx, const rtdd_stroke *strokes, int count, uin
     return launch_paint_strokes(ctx, strokes, count, edited, editedPitch, scribble, scribblePitch, original, originalPitch, rows, cols);
 }
 
+// what rtdd_paint_ramp_strokes and rtdd_ramp_polyline refuse in a record's geometry
+static bool stroke_geometry_ok(int x0, int y0, int x1, int y1, int radius, int brush, const char **why) {
+    for (int v : {x0, y0, x1, y1})
+        if (v < -32768 || v > 32767) { *why = "stroke endpoint outside [-32768, 32767]"; return false; }
+    if (radius < 0 || radius > 1024) { *why = "stroke radius outside [0, 1024]"; return false; }
+    if (brush != RTDD_BRUSH_SQUARE && brush != RTDD_BRUSH_ROUND) { *why = "unknown brush"; return false; }
+    return true;
+}
+
+int rtdd_paint_ramp_strokes(rtdd_ctx *ctx, const rtdd_ramp_stroke *strokes, int count, uint8_t *edited, size_t editedPitch, uint8_t *scribble,
+                            size_t scribblePitch, const uint8_t *original, size_t originalPitch, int rows, int cols) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    REQUIRE(ctx, edited && scribble, "null image pointer");
+    REQUIRE(ctx, rows >= 0 && cols >= 0, "negative size");
+    REQUIRE(ctx, rows <= 32768 && cols <= 32768, "image larger than 32768 pixels in a direction");
+    REQUIRE(ctx, count >= 0 && count <= 4096, "count outside [0, 4096]");
+    REQUIRE(ctx, strokes || count == 0, "null stroke array");
+    bool erases = false;
+    for (int i = 0; i < count; i++) {
+        const rtdd_ramp_stroke &q = strokes[i];
+        const char *why = nullptr;
+        REQUIRE(ctx, stroke_geometry_ok(q.x0, q.y0, q.x1, q.y1, q.radius, q.brush, &why), why);
+        REQUIRE(ctx, q.label0 >= RTDD_STROKE_ERASE && q.label0 <= 255 && q.label1 >= RTDD_STROKE_ERASE && q.label1 <= 255, "stroke label outside [-1, 255]");
+        REQUIRE(ctx, (q.label0 == RTDD_STROKE_ERASE) == (q.label1 == RTDD_STROKE_ERASE), "one label of a ramp erases and the other paints");
+        erases = erases || q.label0 == RTDD_STROKE_ERASE;
+    }
+    REQUIRE(ctx, !erases || original, "an erasing stroke needs the original image");
+    if (rows == 0 || cols == 0 || count == 0) return RTDD_OK;
+    REQUIRE(ctx, editedPitch >= (size_t)cols * 3 && scribblePitch >= (size_t)cols && (!erases || originalPitch >= (size_t)cols * 3),
+        "pitch smaller than a row");
+    DeviceGuard g(ctx->device);
+    // (as rtdd_paint_strokes: the pyramid hears of the write, and of an erasure; nothing goes into the pending-call log -- a paint call
+    // cannot time out, and an estimate that is run again reads the images as the paint calls in front of it left them)
+    RTDD_TRY(pyramid_note_write(ctx, scribble, edited, erases));
+    return launch_paint_ramp_strokes(ctx, strokes, count, edited, editedPitch, scribble, scribblePitch, original, originalPitch, rows, cols);
+}
+
+// host arithmetic only (include/rtdd.h has the rule): doubles, every operation rounded on its own
+int rtdd_ramp_polyline(const int *xy, int n, int radius, int brush, int label0, int label1, rtdd_ramp_stroke *out) {
+#pragma clang fp contract(off)
+    if (!xy || !out || n < 1 || n > 4097) return RTDD_ERR_INVALID;
+    if (label0 < 0 || label0 > 255 || label1 < 0 || label1 > 255) return RTDD_ERR_INVALID;
+    const char *why = nullptr;
+    for (int i = 0; i < n; i++)
+        if (!stroke_geometry_ok(xy[2 * i], xy[2 * i + 1], xy[2 * i], xy[2 * i + 1], radius, brush, &why)) return RTDD_ERR_INVALID;
+    if (n == 1) { out[0] = rtdd_ramp_stroke{xy[0], xy[1], xy[0], xy[1], radius, brush, label0, label0}; return RTDD_OK; }
+    std::vector<double> s((size_t)n);
+    s[0] = 0.0;
+    for (int i = 1; i < n; i++) {
+        const long long dx = (long long)xy[2 * i] - xy[2 * i - 2], dy = (long long)xy[2 * i + 1] - xy[2 * i - 1];
+        s[i] = s[i - 1] + std::sqrt((double)(dx * dx + dy * dy));
+    }
+    const double S = s[n - 1];
+    auto label = [&](int i) {
+        if (!(S > 0.0)) return label0;
+        const double share = s[i] / S, rise = (double)(label1 - label0) * share, at = (double)label0 + rise;
+        return (int)std::floor(at + 0.5);
+    };
+    int prev = label(0);
+    for (int i = 0; i + 1 < n; i++) {
+        const int next = label(i + 1);
+        out[i] = rtdd_ramp_stroke{xy[2 * i], xy[2 * i + 1], xy[2 * i + 2], xy[2 * i + 3], radius, brush, prev, next};
+        prev = next;
+    }
+    return RTDD_OK;
+}
+
 }  // extern "C"
 #pragma GCC visibility pop

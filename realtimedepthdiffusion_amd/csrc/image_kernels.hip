@@ -2,6 +2,7 @@
 // square brush.  All three are tiny, HBM-latency-bound byte kernels; one wave covers 64
 // consecutive pixels of a row so mask/depth accesses coalesce.
 #include <algorithm>
+#include <type_traits>
 
 #include "rtdd_internal.hpp"
 
@@ -311,7 +312,7 @@ __global__ __launch_bounds__(256) void k_paint(int x0, int y0, int x1, int y1, i
 // product below 2^35, and the one square that can pass 2^63 -- (2 cross)^2 -- is compared only after 2 |cross| < 2^32 (at or beyond that
 // it exceeds radius^2 * |d|^2 <= 2^54 anyway).
 constexpr int kStrokeChunk = 256, kStrokeTileW = 64, kStrokeTileH = 16;
-struct PackedStroke { uint32_t p0, p1, meta; };  // x | y << 16 (two's complement halves); radius | brush << 11 | (label + 1) << 12
+struct PackedStroke { uint32_t p0, p1, meta; };  // x | y << 16 (two's complement halves); radius | brush << 11 | (label + 1) << 12 [| label1 << 21: a ramp]
 struct StrokeChunk {
     int count, x0, y0, x1, y1;                    // strokes in this chunk; its bounding box, clipped to the image (inclusive)
     PackedStroke s[kStrokeChunk];
@@ -331,10 +332,35 @@ __device__ __forceinline__ bool stroke_covers(int px, int py, int x0, int y0, in
     return c2 < (1ull << 32) && c2 * c2 <= (unsigned long long)r2 * (unsigned long long)dd;
 }
 
+// rtdd_paint_ramp_strokes' label of a covered pixel (include/rtdd.h), for dd != 0: L = N div (2 dd), N = 2 (l0 (dd - t) + l1 t) + dd,
+// t = v.d clamped to [0, dd].  N is formed as (2 l0 + 1) dd + 2 (l1 - l0) t: the same integer, its first term the same in every lane.
+// Called only behind stroke_covers, i.e. inside the stroke's grown box, where |v|, |d| < 2^17: |v.d| and dd < 2^35, and 0 <= N <=
+// 511 dd < 2^45, D = 2 dd < 2^36 -- every product below fits 64 bits with room.
+// The quotient x = N / D is known to lie in [0, 255.5], so the compiler's general 64-bit division is not needed: an f32 estimate and one
+// correction step.  fn and fd are N and D rounded to f32 (the high word of N is below 2^13 and exact, the low word and the sum round
+// once each: relative error <= 2^-23; D likewise), v_rcp_f32 is good to 1 ulp (2^-23) and the product rounds once more (2^-24):
+// y = fn * rcp(fd) = x (1 + e) with |e| < 2^-21, so |y - x| < 256 * 2^-21 = 2^-13 and q = trunc(y) >= 0 is floor(x) - 1, floor(x) or
+// floor(x) + 1.  The remainder r = N - q D (|r| < 2 D < 2^37, exact in 64 bits) says which: r < 0: one too many; r >= D: one too few;
+// afterwards 0 <= N - q D < D, which is the definition of N div D.
+__device__ __forceinline__ int ramp_label(int px, int py, int x0, int y0, int x1, int y1, int l0, int l1) {
+    const long long dx = x1 - x0, dy = y1 - y0, vx = px - x0, vy = py - y0, dd = dx * dx + dy * dy;
+    const long long t = min(max(vx * dx + vy * dy, 0ll), dd);
+    const long long N = (long long)(2 * l0 + 1) * dd + (long long)(2 * (l1 - l0)) * t, D = 2 * dd;
+    const float fn = __builtin_fmaf((float)(uint32_t)((unsigned long long)N >> 32), 4294967296.0f, (float)(uint32_t)N);
+    int q = (int)(fn * __builtin_amdgcn_rcpf((float)(unsigned long long)D));
+    const long long r = N - (long long)q * D;
+    q += (int)(r >= D) - (int)(r < 0);
+    return q;
+}
+
+// kRamp = false: rtdd_paint_strokes.  kRamp = true: rtdd_paint_ramp_strokes -- the same tiles, cull and walk; the record's fourth word
+// carries label1 above label0 + 1, and a painting stroke whose two labels differ (and which is no stamp: both the same in every lane)
+// evaluates ramp_label for the pixels it covers.  A compile-time variant: the constant-label kernel's code is what it was.
+template <bool kRamp>
 __global__ __launch_bounds__(256) void k_paint_strokes(const StrokeChunk C, uint8_t *__restrict__ edited, size_t editedPitch,
                                                        uint8_t *__restrict__ scribble, size_t scribblePitch,
                                                        const uint8_t *__restrict__ original, size_t originalPitch) {
-    __shared__ int4 live[kStrokeChunk];           // the surviving strokes, unpacked: (x0 | y0 << 16, x1 | y1 << 16, radius, brush | (label + 1) << 1)
+    __shared__ int4 live[kStrokeChunk];           // the surviving strokes, unpacked: (x0 | y0 << 16, x1 | y1 << 16, radius, brush | (label + 1) << 1 [| label1 << 10])
     __shared__ int wave_count[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
     const int tx0 = C.x0 + (int)blockIdx.x * kStrokeTileW, ty0 = C.y0 + (int)blockIdx.y * kStrokeTileH;
@@ -368,7 +394,14 @@ __global__ __launch_bounds__(256) void k_paint_strokes(const StrokeChunk C, uint
             const int4 r = live[i];                                  // (one address for the whole wave: an LDS broadcast)
             if (!stroke_covers(x, y, (int16_t)(r.x & 0xFFFF), (int16_t)((uint32_t)r.x >> 16), (int16_t)(r.y & 0xFFFF), (int16_t)((uint32_t)r.y >> 16),
                                r.z, r.w & 1)) continue;
-            const int label = (r.w >> 1) - 1;                        // RTDD_STROKE_ERASE = -1
+            int label = (r.w >> 1) - 1;                              // RTDD_STROKE_ERASE = -1
+            if constexpr (kRamp) {
+                label = ((r.w >> 1) & 0x1FF) - 1;
+                const int label1 = (r.w >> 10) & 0xFF;
+                if (label >= 0 && label1 != label && r.x != r.y)     // (wave-uniform: the record is)
+                    label = ramp_label(x, y, (int16_t)(r.x & 0xFFFF), (int16_t)((uint32_t)r.x >> 16), (int16_t)(r.y & 0xFFFF), (int16_t)((uint32_t)r.y >> 16),
+                                       label, label1);
+            }
             uint8_t *e = edited + (size_t)y * editedPitch + 3 * x;
             if (label >= 0) {
                 e[0] = (uint8_t)label; e[1] = (uint8_t)label; e[2] = (uint8_t)label;
@@ -476,32 +509,48 @@ int launch_paint(rtdd_ctx *ctx, int x, int y, int color, int radius, uint8_t *ed
     return RTDD_OK;
 }
 
-// strokes: checked by rtdd_paint_strokes (api.cpp) -- coordinates, radius, brush and label inside the packed fields' ranges
-int launch_paint_strokes(rtdd_ctx *ctx, const rtdd_stroke *strokes, int count, uint8_t *edited, size_t editedPitch, uint8_t *scribble,
-                         size_t scribblePitch, const uint8_t *original, size_t originalPitch, int rows, int cols) {
+// strokes: checked by rtdd_paint_strokes / rtdd_paint_ramp_strokes (api.cpp) -- coordinates, radius, brush and labels inside the packed
+// fields' ranges.  One body for both record types: the labels' bits and the kernel's variant are all that differs.
+static uint32_t pack_labels(const rtdd_stroke &q) { return (uint32_t)(q.label + 1) << 12; }
+static uint32_t pack_labels(const rtdd_ramp_stroke &q) { return (uint32_t)(q.label0 + 1) << 12 | (uint32_t)std::max(q.label1, 0) << 21; }
+
+template <class Stroke>
+static int launch_strokes(rtdd_ctx *ctx, const Stroke *strokes, int count, uint8_t *edited, size_t editedPitch, uint8_t *scribble,
+                          size_t scribblePitch, const uint8_t *original, size_t originalPitch, int rows, int cols) {
+    constexpr bool ramp = std::is_same<Stroke, rtdd_ramp_stroke>::value;
     for (int first = 0; first < count; first += kStrokeChunk) {
         StrokeChunk C;
         C.count = count - first < kStrokeChunk ? count - first : kStrokeChunk;
         int bx0 = cols, by0 = rows, bx1 = -1, by1 = -1;              // union of the strokes' boxes, clipped to the image
         for (int i = 0; i < C.count; i++) {
-            const rtdd_stroke &q = strokes[first + i];
+            const Stroke &q = strokes[first + i];
             const int h = q.radius / 2;
             const int x0 = std::max(std::min(q.x0, q.x1) - h, 0), x1 = std::min(std::max(q.x0, q.x1) + h, cols - 1);
             const int y0 = std::max(std::min(q.y0, q.y1) - h, 0), y1 = std::min(std::max(q.y0, q.y1) + h, rows - 1);
             if (x0 <= x1 && y0 <= y1) { bx0 = std::min(bx0, x0); bx1 = std::max(bx1, x1); by0 = std::min(by0, y0); by1 = std::max(by1, y1); }
             C.s[i].p0 = ((uint32_t)q.x0 & 0xFFFFu) | ((uint32_t)q.y0 << 16);
             C.s[i].p1 = ((uint32_t)q.x1 & 0xFFFFu) | ((uint32_t)q.y1 << 16);
-            C.s[i].meta = (uint32_t)q.radius | ((uint32_t)q.brush << 11) | ((uint32_t)(q.label + 1) << 12);
+            C.s[i].meta = (uint32_t)q.radius | ((uint32_t)q.brush << 11) | pack_labels(q);
         }
         for (int i = C.count; i < kStrokeChunk; i++) C.s[i] = PackedStroke{0, 0, 0};
         if (bx1 < bx0 || by1 < by0) continue;                        // every stroke of the chunk lies outside the image
         bx0 &= ~63;                                                  // (a wave's 64 pixels start on a 64-pixel boundary of the row)
         C.x0 = bx0; C.y0 = by0; C.x1 = bx1; C.y1 = by1;
         const dim3 grid((bx1 - bx0) / kStrokeTileW + 1, (by1 - by0) / kStrokeTileH + 1);
-        hipLaunchKernelGGL(k_paint_strokes, grid, dim3(256), 0, ctx->stream, C, edited, editedPitch, scribble, scribblePitch, original, originalPitch);
+        hipLaunchKernelGGL(k_paint_strokes<ramp>, grid, dim3(256), 0, ctx->stream, C, edited, editedPitch, scribble, scribblePitch, original, originalPitch);
         RTDD_LAUNCH_CHECK(ctx, "k_paint_strokes");
     }
     return RTDD_OK;
+}
+
+int launch_paint_strokes(rtdd_ctx *ctx, const rtdd_stroke *strokes, int count, uint8_t *edited, size_t editedPitch, uint8_t *scribble,
+                         size_t scribblePitch, const uint8_t *original, size_t originalPitch, int rows, int cols) {
+    return launch_strokes(ctx, strokes, count, edited, editedPitch, scribble, scribblePitch, original, originalPitch, rows, cols);
+}
+
+int launch_paint_ramp_strokes(rtdd_ctx *ctx, const rtdd_ramp_stroke *strokes, int count, uint8_t *edited, size_t editedPitch, uint8_t *scribble,
+                              size_t scribblePitch, const uint8_t *original, size_t originalPitch, int rows, int cols) {
+    return launch_strokes(ctx, strokes, count, edited, editedPitch, scribble, scribblePitch, original, originalPitch, rows, cols);
 }
 
 }  // namespace rtdd

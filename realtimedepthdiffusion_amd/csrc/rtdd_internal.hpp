@@ -377,6 +377,9 @@ int launch_paint(rtdd_ctx *ctx, int x, int y, int color, int radius, uint8_t *ed
 // rtdd_paint_strokes: `count` checked strokes in array order, kStrokeChunk per launch (the records are kernel arguments)
 int launch_paint_strokes(rtdd_ctx *ctx, const rtdd_stroke *strokes, int count, uint8_t *edited, size_t editedPitch, uint8_t *scribble,
                          size_t scribblePitch, const uint8_t *original, size_t originalPitch, int rows, int cols);
+// rtdd_paint_ramp_strokes: the same launches with the kernel's ramp variant (the second label rides in the 12-byte record's spare bits)
+int launch_paint_ramp_strokes(rtdd_ctx *ctx, const rtdd_ramp_stroke *strokes, int count, uint8_t *edited, size_t editedPitch, uint8_t *scribble,
+                              size_t scribblePitch, const uint8_t *original, size_t originalPitch, int rows, int cols);
 
 // ---- effect_kernels.hip -------------------------------------------------------------------------
 int launch_effect(rtdd_ctx *ctx, const Effect &e);
