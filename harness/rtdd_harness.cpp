@@ -195,6 +195,10 @@ struct Job {
     std::vector<rtdd_ramp_stroke> strokes;
     bool has_ramp = false;
     std::vector<LiveStroke> live_strokes;
+    // --fill / --fill-erase, in command-line order among themselves: one rtdd_fill_polygon call each, after the strokes' call
+    struct Lasso { std::vector<int> xy; rtdd_fill fill; };
+    std::vector<Lasso> fills;
+    int fill_rule = RTDD_FILL_NONZERO;      // --fill-rule nonzero|evenodd: the rule of the --fill / --fill-erase flags behind it
     std::string effect;
     int iters = 1000;
     std::string refine;           // "" | "sor" | "mg": rtdd_refine_depth after every estimate
@@ -231,7 +235,7 @@ struct Job {
 };
 
 // --stroke / --erase / --ramp: the job's strokes on a device image pair, one call
-static int paint_strokes(rtdd_ctx *ctx, const Job &job, void *ed, size_t ed_pitch, void *scr, size_t scr_pitch, const void *orig, size_t orig_pitch, int rows, int cols) {
+static int stroke_calls(rtdd_ctx *ctx, const Job &job, void *ed, size_t ed_pitch, void *scr, size_t scr_pitch, const void *orig, size_t orig_pitch, int rows, int cols) {
     if (job.strokes.empty()) return RTDD_OK;
     if (job.has_ramp) {
         CK(rtdd_paint_ramp_strokes(ctx, job.strokes.data(), (int)job.strokes.size(), (uint8_t *)ed, ed_pitch, (uint8_t *)scr, scr_pitch, (const uint8_t *)orig, orig_pitch, rows, cols));
@@ -241,6 +245,43 @@ static int paint_strokes(rtdd_ctx *ctx, const Job &job, void *ed, size_t ed_pitc
     for (const rtdd_ramp_stroke &q : job.strokes) plain.push_back(rtdd_stroke{q.x0, q.y0, q.x1, q.y1, q.radius, q.brush, q.label0});
     CK(rtdd_paint_strokes(ctx, plain.data(), (int)plain.size(), (uint8_t *)ed, ed_pitch, (uint8_t *)scr, scr_pitch, (const uint8_t *)orig, orig_pitch, rows, cols));
     return RTDD_OK;
+}
+
+// --fill / --fill-erase: the job's polygons on a device image pair, one call each
+static int fill_polygons(rtdd_ctx *ctx, const Job &job, void *ed, size_t ed_pitch, void *scr, size_t scr_pitch, const void *orig, size_t orig_pitch, int rows, int cols) {
+    for (const Job::Lasso &l : job.fills)
+        CK(rtdd_fill_polygon(ctx, l.xy.data(), (int)l.xy.size() / 2, &l.fill, (uint8_t *)ed, ed_pitch, (uint8_t *)scr, scr_pitch, (const uint8_t *)orig, orig_pitch, rows, cols));
+    return RTDD_OK;
+}
+
+// "x,y;x,y;..." and, when the polygon paints, ":label" or ":label0,label1,ax0,ay0,ax1,ay1"
+static bool parse_fill(const char *arg, bool erase, int rule, Job::Lasso *l) {
+    l->xy.clear();
+    l->fill = rtdd_fill{rule, 0, 0, 0, 0, RTDD_STROKE_ERASE, RTDD_STROKE_ERASE};
+    for (;;) {
+        int x, y, n = 0;
+        if (std::sscanf(arg, "%d,%d%n", &x, &y, &n) != 2 || n == 0) return false;
+        l->xy.push_back(x); l->xy.push_back(y);
+        arg += n;
+        if (*arg != ';') break;
+        arg++;
+    }
+    if (erase) return *arg == 0;
+    if (*arg != ':') return false;
+    int n = 0;
+    rtdd_fill &f = l->fill;
+    if (std::sscanf(arg + 1, "%d,%d,%d,%d,%d,%d%n", &f.label0, &f.label1, &f.ax0, &f.ay0, &f.ax1, &f.ay1, &n) == 6 && arg[1 + n] == 0) return true;
+    f = rtdd_fill{rule, 0, 0, 0, 0, 0, 0};
+    n = 0;
+    if (std::sscanf(arg + 1, "%d%n", &f.label0, &n) != 1 || arg[1 + n] != 0) return false;
+    f.label1 = f.label0;
+    return true;
+}
+
+// --stroke / --erase / --ramp: the job's strokes on a device image pair, one call; the --fill / --fill-erase polygons behind them
+static int paint_strokes(rtdd_ctx *ctx, const Job &job, void *ed, size_t ed_pitch, void *scr, size_t scr_pitch, const void *orig, size_t orig_pitch, int rows, int cols) {
+    CK(stroke_calls(ctx, job, ed, ed_pitch, scr, scr_pitch, orig, orig_pitch, rows, cols));
+    return fill_polygons(ctx, job, ed, ed_pitch, scr, scr_pitch, orig, orig_pitch, rows, cols);
 }
 
 // rtdd_paint_ramp_strokes (with label0 == label1: rtdd_paint_strokes) restated for the host's own image pair (--live: the host owns the pair every frame uploads; include/rtdd.h has the
@@ -556,6 +597,7 @@ int main(int argc, const char *argv[]) {
                                  "                    [--paint x,y,label,radius]... [--live N [--paint-at frame:x,y,label,radius]...] [--devices D --batch B [--sequential] [--write-all]] [--png] [--cold] [--edges gray|color]\n"
                                  "                    [--stroke x0,y0,x1,y1,label,radius[,round]]... [--erase x0,y0,x1,y1,radius[,round]]...   (segments, in command-line order, one rtdd_paint_strokes call after --paint)\n"
                                  "                    [--ramp x0,y0,x1,y1,label0,label1,radius[,round]]...   (a depth ramp: label0 at x0,y0 to label1 at x1,y1; in order with --stroke / --erase, all of them one rtdd_paint_ramp_strokes call)\n"
+                                 "                    [--fill \"x,y;x,y;...:label\" | \"x,y;...:label0,label1,ax0,ay0,ax1,ay1\"]... [--fill-erase \"x,y;x,y;...\"]... [--fill-rule nonzero|evenodd]   (a lasso filled with a label, a ramp along the axis, or erased: one rtdd_fill_polygon call each, after the strokes, in command-line order)\n"
                                  "                    [--stroke-at frame:x0,y0,x1,y1,label,radius[,round]]... [--erase-at frame:x0,y0,x1,y1,radius[,round]]... [--ramp-at frame:x0,y0,x1,y1,label0,label1,radius[,round]]...   (--live: in front of that frame)\n"
                                  "       rtdd_harness --convert in.(jpg|png|ppm|pgm) out.(png|ppm|pgm)   (JPEG / 8-bit PNG / PNM -> PNG / PNM, no GPU)\n"); return 0; }
     if (argc == 4 && !std::strcmp(argv[1], "--convert")) {               // file format conversion only (no GPU): JPEG / PNG / PNM -> PNG / PNM
@@ -594,6 +636,17 @@ int main(int argc, const char *argv[]) {
             const bool at = argv[i][6] != 0; LiveStroke q; q.frame = -1;
             if (!parse_stroke(next(), 'r', &q.s, at ? &q.frame : nullptr)) { std::printf("%s\n", at ? "--ramp-at wants frame:x0,y0,x1,y1,label0,label1,radius[,round]" : "--ramp wants x0,y0,x1,y1,label0,label1,radius[,round]"); return 1; }
             if (at) job.live_strokes.push_back(q); else { job.strokes.push_back(q.s); job.has_ramp = true; }
+        }
+        else if (!std::strcmp(argv[i], "--fill-rule")) {
+            const char *r = next();
+            if (!std::strcmp(r, "nonzero")) job.fill_rule = RTDD_FILL_NONZERO;
+            else if (!std::strcmp(r, "evenodd")) job.fill_rule = RTDD_FILL_EVEN_ODD;
+            else { std::printf("--fill-rule wants nonzero or evenodd\n"); return 1; }
+        }
+        else if (!std::strcmp(argv[i], "--fill") || !std::strcmp(argv[i], "--fill-erase")) {
+            const bool erase = argv[i][6] != 0; Job::Lasso l;
+            if (!parse_fill(next(), erase, job.fill_rule, &l)) { std::printf("%s\n", erase ? "--fill-erase wants x,y;x,y;..." : "--fill wants x,y;x,y;...:label or x,y;x,y;...:label0,label1,ax0,ay0,ax1,ay1"); return 1; }
+            job.fills.push_back(l);
         }
         else if (!std::strcmp(argv[i], "--stroke") || !std::strcmp(argv[i], "--erase")) {
             const bool erase = argv[i][2] == 'e'; rtdd_ramp_stroke q;

@@ -375,6 +375,52 @@ int rtdd_paint_ramp_strokes(rtdd_ctx *ctx, const rtdd_ramp_stroke *strokes /* HO
 int rtdd_ramp_polyline(const int *xy /* n points: x, y, x, y ... */, int n, int radius, int brush,
                        int label0, int label1, rtdd_ramp_stroke *out /* max(n - 1, 1) records */);
 
+/* A filled polygon -- the lasso (extension; no reference behaviour; found by symbol like rtdd_paint_ramp_strokes, no version bump; the next
+ * bump of RTDD_VERSION should cover rtdd_paint_strokes, rtdd_pyramid_annotation_rebuild, rtdd_paint_ramp_strokes, rtdd_ramp_polyline and
+ * rtdd_fill_polygon): a region outlined by the user gets one label ("all of this is at that depth"), a ramp ("all of this is that
+ * plane") or is erased ("forget everything I drew in here").  All of it exact integer arithmetic.
+ * Contour: the closed contour v_0 .. v_(n-1), v_0 of the n vertices xy = x, y, x, y ... -- integer pixel coordinates, which may lie
+ *   outside the image; the contour may intersect itself and may repeat a vertex.
+ * Winding of pixel p = (px, py): w = 0; for every edge a -> b of the contour
+ *   cr = (bx - ax) * (py - ay) - (px - ax) * (by - ay)
+ *   w += 1 when ay <= py < by and cr > 0
+ *   w -= 1 when by <= py < ay and cr < 0
+ *   (a horizontal edge never counts).
+ * Boundary: p lies on an edge when cr == 0, min(ax,bx) <= px <= max(ax,bx) and min(ay,by) <= py <= max(ay,by).
+ * Coverage: p is covered when it lies on the boundary, or when w != 0 (RTDD_FILL_NONZERO), or when w is odd (RTDD_FILL_EVEN_ODD).  The
+ *   region is closed: every vertex inside the image is covered; the covered set does not depend on the contour's direction (reversal
+ *   negates w) or on which vertex comes first; a contour with n = 1 or n = 2, or with all vertices collinear, covers exactly the lattice
+ *   points of its segments.
+ * Label: rtdd_paint_ramp_strokes' L with the axis (ax0, ay0) - (ax1, ay1) as the segment: with d = a1 - a0, v = p - a0, dd = d.d,
+ *   dd == 0 or label0 == label1:  L = label0
+ *   otherwise:                    t = min(max(v.d, 0), dd)
+ *                                 N = 2 * (label0 * (dd - t) + label1 * t) + dd
+ *                                 L = N / (2 * dd)                             (C division: round half up; 0 <= L <= 255)
+ *   Beyond either end of the axis the label is that end's.  Any plane over the region can be expressed: lay the axis along its gradient.
+ * Writes: painting (labels 0..255) writes edited = (L, L, L), scribble = 255; erasing (both labels RTDD_STROKE_ERASE) writes edited =
+ *   original at that pixel, scribble = 0; uncovered pixels are not written.
+ * Domain: vertex and axis coordinates in [-32768, 32767]; rows and cols at most 32768; 1 <= n <= 768 (n == 0: RTDD_OK, nothing launched).
+ *   On it |cr| < 2^34, dd < 2^35, N < 2^45 and |w| <= 384.  The vertices travel as kernel arguments (4 bytes each): a host with a longer
+ *   lasso thins it out.
+ * Refused (RTDD_ERR_INVALID) before any launch, the images untouched: a null fill; a null xy with n > 0; n outside [0, 768]; an unknown
+ *   rule; a vertex or axis coordinate outside the domain; a label outside [-1, 255]; exactly ONE label being RTDD_STROKE_ERASE; erasing
+ *   with original == NULL or an original pitch smaller than a row; the null, pitch and size rules of rtdd_paint_strokes.  A retired
+ *   level-0 pointer of live mode: RTDD_ERR_STATE.
+ * On the pyramid's own level-0 RTDD_IMG_SCRIBBLE / RTDD_IMG_EDITED pair the call notes the change itself, and asks for
+ * rtdd_pyramid_annotation_rebuild when it erases, exactly as rtdd_paint_strokes.  xy and fill are HOST memory, read before the call
+ * returns; the call is otherwise stream-ordered and asynchronous: ONE launch over the contour's bounding box clipped to the image (none for
+ * a contour wholly outside).  Calls compose by stream order with each other and with the stroke calls: the later call decides a pixel. */
+enum rtdd_fill_rule { RTDD_FILL_NONZERO = 0, RTDD_FILL_EVEN_ODD = 1 };
+typedef struct rtdd_fill {
+    int rule;                   /* enum rtdd_fill_rule */
+    int ax0, ay0, ax1, ay1;     /* the ramp's axis: label0 at (ax0, ay0), label1 at (ax1, ay1); ignored when label0 == label1 */
+    int label0, label1;         /* both in 0..255, or both RTDD_STROKE_ERASE */
+} rtdd_fill;
+int rtdd_fill_polygon(rtdd_ctx *ctx, const int *xy /* HOST: n vertices x, y, x, y ... */, int n, const rtdd_fill *fill,
+                      uint8_t *edited, size_t editedPitch, uint8_t *scribble, size_t scribblePitch,
+                      const uint8_t *original, size_t originalPitch, /* may be NULL unless erasing */
+                      int rows, int cols);
+
 /* ---- depth effects (include/GPUDepthEffect.h:4-9) ------------------------------------------ */
 
 /* GPUSimulateDefocus -- src/GPUDepthEffect.cu:29-72,105-113 (exact, via an integer summed-area table). */

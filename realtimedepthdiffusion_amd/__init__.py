@@ -52,7 +52,7 @@ C_ABI_SYMBOLS = [
     "rtdd_live_submit", "rtdd_live_wait", "rtdd_live_pending", "rtdd_host_alloc", "rtdd_host_free",
     "rtdd_pyramid_create_batch", "rtdd_pyramid_select", "rtdd_pyramid_batch", "rtdd_estimate_depth_batch", "rtdd_pyramid_level_info", "rtdd_live_submit_ex",
     "rtdd_simulate_refocus", "rtdd_simulate_haze_ex", "rtdd_simulate_stereo", "rtdd_simulate_lens_blur",
-    "rtdd_paint_strokes", "rtdd_pyramid_annotation_rebuild", "rtdd_paint_ramp_strokes", "rtdd_ramp_polyline",
+    "rtdd_paint_strokes", "rtdd_pyramid_annotation_rebuild", "rtdd_paint_ramp_strokes", "rtdd_ramp_polyline", "rtdd_fill_polygon",
     "rtdd_simulate_relight", "rtdd_simulate_relight_shadowed", "rtdd_simulate_parallax", "rtdd_simulate_ambient_occlusion",
     "rtdd_simulate_lighting", "rtdd_simulate_bokeh",
     "rtdd_solve_guided", "rtdd_index_to_weight_guided", "rtdd_pyrdown_bgr", "rtdd_pyramid_set_guide", "rtdd_pyramid_guide",
@@ -66,6 +66,7 @@ LIGHT_DIRECTIONAL, LIGHT_POINT = 0, 1         # rtdd_light.kind
 AO_SHADE, AO_MAP = 0, 1                       # rtdd_ambient_occlusion.mode
 BRUSH_SQUARE, BRUSH_ROUND = 0, 1              # rtdd_stroke.brush
 STROKE_ERASE = -1                             # rtdd_stroke.label: remove the annotation
+FILL_NONZERO, FILL_EVEN_ODD = 0, 1            # rtdd_fill.rule
 # Itanium-mangled names of the reference's ten free functions
 DROPIN_SYMBOLS = [
     "_Z23GPUAllocateDeviceMemoryiii", "_Z19GPUFreeDeviceMemoryi", "_Z14GPULoadWeightsf",
@@ -103,6 +104,12 @@ class RampStroke(C.Structure):
     """rtdd_ramp_stroke: a Stroke whose label runs linearly from label0 at (x0, y0) to label1 at (x1, y1) (both STROKE_ERASE: an eraser)."""
     _fields_ = [("x0", C.c_int), ("y0", C.c_int), ("x1", C.c_int), ("y1", C.c_int), ("radius", C.c_int), ("brush", C.c_int),
                 ("label0", C.c_int), ("label1", C.c_int)]
+
+
+class Fill(C.Structure):
+    """rtdd_fill: FILL_*, the ramp's axis (label0 at (ax0, ay0), label1 at (ax1, ay1); ignored when the labels are equal), the two labels
+    (both STROKE_ERASE: the polygon erases)."""
+    _fields_ = [("rule", C.c_int), ("ax0", C.c_int), ("ay0", C.c_int), ("ax1", C.c_int), ("ay1", C.c_int), ("label0", C.c_int), ("label1", C.c_int)]
 
 
 def ramp_polyline(points, radius, brush, label0, label1):
@@ -400,6 +407,16 @@ class Context:
         e, ep = _img(edited); s, sp = _img(scribble)
         o, op = _img(original) if original is not None else (None, C.c_size_t(0))
         self._check(lib().rtdd_paint_ramp_strokes(self._h, arr, C.c_int(len(strokes)), e, ep, s, sp, o, op, C.c_int(rows), C.c_int(cols)))
+
+    def fill_polygon(self, points, fill, edited, scribble, rows, cols, original=None):
+        """rtdd_fill_polygon: the closed contour through `points` [(x, y), ...] (at most 768) filled by `fill` (a Fill or a 7-tuple rule,
+        ax0, ay0, ax1, ay1, label0, label1); `original` is needed when it erases."""
+        n = len(points)
+        xy = (C.c_int * max(2 * n, 1))(*[int(v) for p in points for v in p])
+        f = fill if isinstance(fill, Fill) else Fill(*fill)
+        e, ep = _img(edited); s, sp = _img(scribble)
+        o, op = _img(original) if original is not None else (None, C.c_size_t(0))
+        self._check(lib().rtdd_fill_polygon(self._h, xy, C.c_int(n), C.byref(f), e, ep, s, sp, o, op, C.c_int(rows), C.c_int(cols)))
 
     # ---- include/GPUDepthEffect.h
     def GPUSimulateDefocus(self, originalImage, depthImage, artisticImage, rows, cols):

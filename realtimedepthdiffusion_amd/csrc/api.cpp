@@ -726,6 +726,32 @@ int rtdd_paint_ramp_strokes(rtdd_ctx *ctx, const rtdd_ramp_stroke *strokes, int 
     return launch_paint_ramp_strokes(ctx, strokes, count, edited, editedPitch, scribble, scribblePitch, original, originalPitch, rows, cols);
 }
 
+int rtdd_fill_polygon(rtdd_ctx *ctx, const int *xy, int n, const rtdd_fill *fill, uint8_t *edited, size_t editedPitch, uint8_t *scribble,
+                      size_t scribblePitch, const uint8_t *original, size_t originalPitch, int rows, int cols) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    REQUIRE(ctx, edited && scribble, "null image pointer");
+    REQUIRE(ctx, rows >= 0 && cols >= 0, "negative size");
+    REQUIRE(ctx, rows <= 32768 && cols <= 32768, "image larger than 32768 pixels in a direction");
+    REQUIRE(ctx, fill, "null fill");
+    REQUIRE(ctx, n >= 0 && n <= 768, "n outside [0, 768]");
+    REQUIRE(ctx, xy || n == 0, "null vertex array");
+    REQUIRE(ctx, fill->rule == RTDD_FILL_NONZERO || fill->rule == RTDD_FILL_EVEN_ODD, "unknown fill rule");
+    for (int i = 0; i < 2 * n; i++) REQUIRE(ctx, xy[i] >= -32768 && xy[i] <= 32767, "vertex coordinate outside [-32768, 32767]");
+    for (int v : {fill->ax0, fill->ay0, fill->ax1, fill->ay1}) REQUIRE(ctx, v >= -32768 && v <= 32767, "axis coordinate outside [-32768, 32767]");
+    REQUIRE(ctx, fill->label0 >= RTDD_STROKE_ERASE && fill->label0 <= 255 && fill->label1 >= RTDD_STROKE_ERASE && fill->label1 <= 255, "fill label outside [-1, 255]");
+    REQUIRE(ctx, (fill->label0 == RTDD_STROKE_ERASE) == (fill->label1 == RTDD_STROKE_ERASE), "one label of a fill erases and the other paints");
+    const bool erases = fill->label0 == RTDD_STROKE_ERASE;
+    REQUIRE(ctx, !erases || original, "an erasing fill needs the original image");
+    if (rows == 0 || cols == 0 || n == 0) return RTDD_OK;
+    REQUIRE(ctx, editedPitch >= (size_t)cols * 3 && scribblePitch >= (size_t)cols && (!erases || originalPitch >= (size_t)cols * 3),
+        "pitch smaller than a row");
+    DeviceGuard g(ctx->device);
+    // (as rtdd_paint_strokes: the pyramid hears of the write, and of an erasure; nothing goes into the pending-call log -- a paint call
+    // cannot time out, and an estimate that is run again reads the images as the paint calls in front of it left them)
+    RTDD_TRY(pyramid_note_write(ctx, scribble, edited, erases));
+    return launch_fill_polygon(ctx, xy, n, *fill, edited, editedPitch, scribble, scribblePitch, original, originalPitch, rows, cols);
+}
+
 // host arithmetic only (include/rtdd.h has the rule): doubles, every operation rounded on its own
 int rtdd_ramp_polyline(const int *xy, int n, int radius, int brush, int label0, int label1, rtdd_ramp_stroke *out) {
 #pragma clang fp contract(off)

@@ -381,6 +381,11 @@ int launch_paint_strokes(rtdd_ctx *ctx, const rtdd_stroke *strokes, int count, u
 int launch_paint_ramp_strokes(rtdd_ctx *ctx, const rtdd_ramp_stroke *strokes, int count, uint8_t *edited, size_t editedPitch, uint8_t *scribble,
                               size_t scribblePitch, const uint8_t *original, size_t originalPitch, int rows, int cols);
 
+// ---- fill_polygon.hip ---------------------------------------------------------------------------
+// rtdd_fill_polygon: the checked contour (1 <= n <= 768 vertices, as kernel arguments) in one launch over its clipped bounding box
+int launch_fill_polygon(rtdd_ctx *ctx, const int *xy, int n, const rtdd_fill &fill, uint8_t *edited, size_t editedPitch, uint8_t *scribble,
+                        size_t scribblePitch, const uint8_t *original, size_t originalPitch, int rows, int cols);
+
 // ---- effect_kernels.hip -------------------------------------------------------------------------
 int launch_effect(rtdd_ctx *ctx, const Effect &e);
 // ---- lens_blur.hip: Effect::kLensBlur (called by launch_effect) ------------------------------------
