@@ -247,6 +247,11 @@ def _img(t):
     return C.c_void_p(t.data_ptr()), C.c_size_t(t.stride(0) * t.element_size())
 
 
+def _paint_images(edited, scribble, original):
+    """The six image arguments of the paint calls: edited, scribble and the optional original, each as (pointer, pitch)."""
+    return (*_img(edited), *_img(scribble), *(_img(original) if original is not None else (None, C.c_size_t(0))))
+
+
 class Context:
     """One solver context per GPU (handle of the C ABI).  Methods carry the reference's names."""
 
@@ -396,17 +401,13 @@ class Context:
         """rtdd_paint_strokes: `strokes` (Stroke objects or 7-tuples x0, y0, x1, y1, radius, brush, label) in order, one call; `original`
         is needed when a stroke erases."""
         arr = (Stroke * max(len(strokes), 1))(*[q if isinstance(q, Stroke) else Stroke(*q) for q in strokes])
-        e, ep = _img(edited); s, sp = _img(scribble)
-        o, op = _img(original) if original is not None else (None, C.c_size_t(0))
-        self._check(lib().rtdd_paint_strokes(self._h, arr, C.c_int(len(strokes)), e, ep, s, sp, o, op, C.c_int(rows), C.c_int(cols)))
+        self._check(lib().rtdd_paint_strokes(self._h, arr, C.c_int(len(strokes)), *_paint_images(edited, scribble, original), C.c_int(rows), C.c_int(cols)))
 
     def paint_ramp_strokes(self, strokes, edited, scribble, rows, cols, original=None):
         """rtdd_paint_ramp_strokes: `strokes` (RampStroke objects or 8-tuples x0, y0, x1, y1, radius, brush, label0, label1) in order, one
         call; `original` is needed when a stroke erases."""
         arr = (RampStroke * max(len(strokes), 1))(*[q if isinstance(q, RampStroke) else RampStroke(*q) for q in strokes])
-        e, ep = _img(edited); s, sp = _img(scribble)
-        o, op = _img(original) if original is not None else (None, C.c_size_t(0))
-        self._check(lib().rtdd_paint_ramp_strokes(self._h, arr, C.c_int(len(strokes)), e, ep, s, sp, o, op, C.c_int(rows), C.c_int(cols)))
+        self._check(lib().rtdd_paint_ramp_strokes(self._h, arr, C.c_int(len(strokes)), *_paint_images(edited, scribble, original), C.c_int(rows), C.c_int(cols)))
 
     def fill_polygon(self, points, fill, edited, scribble, rows, cols, original=None):
         """rtdd_fill_polygon: the closed contour through `points` [(x, y), ...] (at most 768) filled by `fill` (a Fill or a 7-tuple rule,
@@ -414,9 +415,7 @@ class Context:
         n = len(points)
         xy = (C.c_int * max(2 * n, 1))(*[int(v) for p in points for v in p])
         f = fill if isinstance(fill, Fill) else Fill(*fill)
-        e, ep = _img(edited); s, sp = _img(scribble)
-        o, op = _img(original) if original is not None else (None, C.c_size_t(0))
-        self._check(lib().rtdd_fill_polygon(self._h, xy, C.c_int(n), C.byref(f), e, ep, s, sp, o, op, C.c_int(rows), C.c_int(cols)))
+        self._check(lib().rtdd_fill_polygon(self._h, xy, C.c_int(n), C.byref(f), *_paint_images(edited, scribble, original), C.c_int(rows), C.c_int(cols)))
 
     # ---- include/GPUDepthEffect.h
     def GPUSimulateDefocus(self, originalImage, depthImage, artisticImage, rows, cols):

@@ -659,37 +659,30 @@ int rtdd_paint_image(rtdd_ctx *ctx, int x, int y, int scribbleColor, int scribbl
     REQUIRE(ctx, editedPitch >= (size_t)cols * 3 && scribblePitch >= (size_t)cols, "pitch smaller than a row");
     DeviceGuard g(ctx->device);
     RTDD_TRY(pyramid_note_write(ctx, scribble, edited));
-    return launch_paint(ctx, x, y, scribbleColor, scribbleRadius, edited, editedPitch, scribble, scribblePitch, rows, cols);
+    return launch_paint(ctx, x, y, scribbleColor, scribbleRadius, PaintTarget{edited, editedPitch, scribble, scribblePitch, nullptr, 0, rows, cols});
 }
 
-int rtdd_paint_strokes(rtdd_ctx *ctx, const rtdd_stroke *strokes, int count, uint8_t *edited, size_t editedPitch, uint8_t *scribble,
-                       size_t scribblePitch, const uint8_t *original, size_t originalPitch, int rows, int cols) {
-    if (!ctx) return RTDD_ERR_INVALID;
-    REQUIRE(ctx, edited && scribble, "null image pointer");
-    REQUIRE(ctx, rows >= 0 && cols >= 0, "negative size");
-    REQUIRE(ctx, rows <= 32768 && cols <= 32768, "image larger than 32768 pixels in a direction");
-    REQUIRE(ctx, count >= 0 && count <= 4096, "count outside [0, 4096]");
-    REQUIRE(ctx, strokes || count == 0, "null stroke array");
-    bool erases = false;
-    for (int i = 0; i < count; i++) {
-        const rtdd_stroke &q = strokes[i];
-        for (int v : {q.x0, q.y0, q.x1, q.y1}) REQUIRE(ctx, v >= -32768 && v <= 32767, "stroke endpoint outside [-32768, 32767]");
-        REQUIRE(ctx, q.radius >= 0 && q.radius <= 1024, "stroke radius outside [0, 1024]");
-        REQUIRE(ctx, q.brush == RTDD_BRUSH_SQUARE || q.brush == RTDD_BRUSH_ROUND, "unknown brush");
-        REQUIRE(ctx, q.label >= RTDD_STROKE_ERASE && q.label <= 255, "stroke label outside [-1, 255]");
-        erases = erases || q.label == RTDD_STROKE_ERASE;
-    }
-    REQUIRE(ctx, !erases || original, "an erasing stroke needs the original image");
-    if (rows == 0 || cols == 0 || count == 0) return RTDD_OK;
-    REQUIRE(ctx, editedPitch >= (size_t)cols * 3 && scribblePitch >= (size_t)cols && (!erases || originalPitch >= (size_t)cols * 3),
+// ---- rtdd_paint_strokes, rtdd_paint_ramp_strokes, rtdd_fill_polygon: what they share ----
+// A call checks its own records first (they say whether it erases), then its target; an empty image or no record is RTDD_OK before any
+// pitch is looked at; then, with the device set, begin_paint.
+static int check_paint_target(rtdd_ctx *ctx, const PaintTarget &t, bool erases) {
+    REQUIRE(ctx, t.edited && t.scribble, "null image pointer");
+    REQUIRE(ctx, t.rows >= 0 && t.cols >= 0, "negative size");
+    REQUIRE(ctx, t.rows <= 32768 && t.cols <= 32768, "image larger than 32768 pixels in a direction");
+    REQUIRE(ctx, !erases || t.original, "an erasing stroke or fill needs the original image");
+    return RTDD_OK;
+}
+
+// The pitches, and the pyramid hears of the write: an eraser on its own level-0 pair makes the next estimate build the coarse levels,
+// which otherwise only accumulate, afresh.  Nothing goes into the pending-call log -- a paint call cannot time out, and an estimate that
+// is run again reads the images as the paint calls in front of it left them.
+static int begin_paint(rtdd_ctx *ctx, const PaintTarget &t, bool erases) {
+    REQUIRE(ctx, t.editedPitch >= (size_t)t.cols * 3 && t.scribblePitch >= (size_t)t.cols && (!erases || t.originalPitch >= (size_t)t.cols * 3),
         "pitch smaller than a row");
-    DeviceGuard g(ctx->device);
-    // (an eraser on the pyramid's own level-0 pair: the coarse levels, which otherwise only accumulate, are built afresh by the next estimate)
-    RTDD_TRY(pyramid_note_write(ctx, scribble, edited, erases));
-    return launch_paint_strokes(ctx, strokes, count, edited, editedPitch, scribble, scribblePitch, original, originalPitch, rows, cols);
+    return pyramid_note_write(ctx, t.scribble, t.edited, erases);
 }
 
-// what rtdd_paint_ramp_strokes and rtdd_ramp_polyline refuse in a record's geometry
+// what the stroke calls and rtdd_ramp_polyline refuse in a record's geometry
 static bool stroke_geometry_ok(int x0, int y0, int x1, int y1, int radius, int brush, const char **why) {
     for (int v : {x0, y0, x1, y1})
         if (v < -32768 || v > 32767) { *why = "stroke endpoint outside [-32768, 32767]"; return false; }
@@ -698,58 +691,73 @@ static bool stroke_geometry_ok(int x0, int y0, int x1, int y1, int radius, int b
     return true;
 }
 
-int rtdd_paint_ramp_strokes(rtdd_ctx *ctx, const rtdd_ramp_stroke *strokes, int count, uint8_t *edited, size_t editedPitch, uint8_t *scribble,
-                            size_t scribblePitch, const uint8_t *original, size_t originalPitch, int rows, int cols) {
+// ... and in the two labels of a ramp stroke or a fill
+static bool label_pair_ok(int label0, int label1, const char **why) {
+    if (label0 < RTDD_STROKE_ERASE || label0 > 255 || label1 < RTDD_STROKE_ERASE || label1 > 255) { *why = "label outside [-1, 255]"; return false; }
+    if ((label0 == RTDD_STROKE_ERASE) != (label1 == RTDD_STROKE_ERASE)) { *why = "one label of a ramp or a fill erases and the other paints"; return false; }
+    return true;
+}
+
+int rtdd_paint_strokes(rtdd_ctx *ctx, const rtdd_stroke *strokes, int count, uint8_t *edited, size_t editedPitch, uint8_t *scribble,
+                       size_t scribblePitch, const uint8_t *original, size_t originalPitch, int rows, int cols) {
     if (!ctx) return RTDD_ERR_INVALID;
-    REQUIRE(ctx, edited && scribble, "null image pointer");
-    REQUIRE(ctx, rows >= 0 && cols >= 0, "negative size");
-    REQUIRE(ctx, rows <= 32768 && cols <= 32768, "image larger than 32768 pixels in a direction");
+    const PaintTarget t{edited, editedPitch, scribble, scribblePitch, original, originalPitch, rows, cols};
     REQUIRE(ctx, count >= 0 && count <= 4096, "count outside [0, 4096]");
     REQUIRE(ctx, strokes || count == 0, "null stroke array");
     bool erases = false;
+    const char *why = nullptr;
+    for (int i = 0; i < count; i++) {
+        const rtdd_stroke &q = strokes[i];
+        REQUIRE(ctx, stroke_geometry_ok(q.x0, q.y0, q.x1, q.y1, q.radius, q.brush, &why), why);
+        REQUIRE(ctx, q.label >= RTDD_STROKE_ERASE && q.label <= 255, "stroke label outside [-1, 255]");
+        erases = erases || q.label == RTDD_STROKE_ERASE;
+    }
+    RTDD_TRY(check_paint_target(ctx, t, erases));
+    if (rows == 0 || cols == 0 || count == 0) return RTDD_OK;
+    DeviceGuard g(ctx->device);
+    RTDD_TRY(begin_paint(ctx, t, erases));
+    return launch_paint_strokes(ctx, strokes, count, t);
+}
+
+int rtdd_paint_ramp_strokes(rtdd_ctx *ctx, const rtdd_ramp_stroke *strokes, int count, uint8_t *edited, size_t editedPitch, uint8_t *scribble,
+                            size_t scribblePitch, const uint8_t *original, size_t originalPitch, int rows, int cols) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    const PaintTarget t{edited, editedPitch, scribble, scribblePitch, original, originalPitch, rows, cols};
+    REQUIRE(ctx, count >= 0 && count <= 4096, "count outside [0, 4096]");
+    REQUIRE(ctx, strokes || count == 0, "null stroke array");
+    bool erases = false;
+    const char *why = nullptr;
     for (int i = 0; i < count; i++) {
         const rtdd_ramp_stroke &q = strokes[i];
-        const char *why = nullptr;
         REQUIRE(ctx, stroke_geometry_ok(q.x0, q.y0, q.x1, q.y1, q.radius, q.brush, &why), why);
-        REQUIRE(ctx, q.label0 >= RTDD_STROKE_ERASE && q.label0 <= 255 && q.label1 >= RTDD_STROKE_ERASE && q.label1 <= 255, "stroke label outside [-1, 255]");
-        REQUIRE(ctx, (q.label0 == RTDD_STROKE_ERASE) == (q.label1 == RTDD_STROKE_ERASE), "one label of a ramp erases and the other paints");
+        REQUIRE(ctx, label_pair_ok(q.label0, q.label1, &why), why);
         erases = erases || q.label0 == RTDD_STROKE_ERASE;
     }
-    REQUIRE(ctx, !erases || original, "an erasing stroke needs the original image");
+    RTDD_TRY(check_paint_target(ctx, t, erases));
     if (rows == 0 || cols == 0 || count == 0) return RTDD_OK;
-    REQUIRE(ctx, editedPitch >= (size_t)cols * 3 && scribblePitch >= (size_t)cols && (!erases || originalPitch >= (size_t)cols * 3),
-        "pitch smaller than a row");
     DeviceGuard g(ctx->device);
-    // (as rtdd_paint_strokes: the pyramid hears of the write, and of an erasure; nothing goes into the pending-call log -- a paint call
-    // cannot time out, and an estimate that is run again reads the images as the paint calls in front of it left them)
-    RTDD_TRY(pyramid_note_write(ctx, scribble, edited, erases));
-    return launch_paint_ramp_strokes(ctx, strokes, count, edited, editedPitch, scribble, scribblePitch, original, originalPitch, rows, cols);
+    RTDD_TRY(begin_paint(ctx, t, erases));
+    return launch_paint_strokes(ctx, strokes, count, t);
 }
 
 int rtdd_fill_polygon(rtdd_ctx *ctx, const int *xy, int n, const rtdd_fill *fill, uint8_t *edited, size_t editedPitch, uint8_t *scribble,
                       size_t scribblePitch, const uint8_t *original, size_t originalPitch, int rows, int cols) {
     if (!ctx) return RTDD_ERR_INVALID;
-    REQUIRE(ctx, edited && scribble, "null image pointer");
-    REQUIRE(ctx, rows >= 0 && cols >= 0, "negative size");
-    REQUIRE(ctx, rows <= 32768 && cols <= 32768, "image larger than 32768 pixels in a direction");
+    const PaintTarget t{edited, editedPitch, scribble, scribblePitch, original, originalPitch, rows, cols};
     REQUIRE(ctx, fill, "null fill");
     REQUIRE(ctx, n >= 0 && n <= 768, "n outside [0, 768]");
     REQUIRE(ctx, xy || n == 0, "null vertex array");
     REQUIRE(ctx, fill->rule == RTDD_FILL_NONZERO || fill->rule == RTDD_FILL_EVEN_ODD, "unknown fill rule");
     for (int i = 0; i < 2 * n; i++) REQUIRE(ctx, xy[i] >= -32768 && xy[i] <= 32767, "vertex coordinate outside [-32768, 32767]");
     for (int v : {fill->ax0, fill->ay0, fill->ax1, fill->ay1}) REQUIRE(ctx, v >= -32768 && v <= 32767, "axis coordinate outside [-32768, 32767]");
-    REQUIRE(ctx, fill->label0 >= RTDD_STROKE_ERASE && fill->label0 <= 255 && fill->label1 >= RTDD_STROKE_ERASE && fill->label1 <= 255, "fill label outside [-1, 255]");
-    REQUIRE(ctx, (fill->label0 == RTDD_STROKE_ERASE) == (fill->label1 == RTDD_STROKE_ERASE), "one label of a fill erases and the other paints");
+    const char *why = nullptr;
+    REQUIRE(ctx, label_pair_ok(fill->label0, fill->label1, &why), why);
     const bool erases = fill->label0 == RTDD_STROKE_ERASE;
-    REQUIRE(ctx, !erases || original, "an erasing fill needs the original image");
+    RTDD_TRY(check_paint_target(ctx, t, erases));
     if (rows == 0 || cols == 0 || n == 0) return RTDD_OK;
-    REQUIRE(ctx, editedPitch >= (size_t)cols * 3 && scribblePitch >= (size_t)cols && (!erases || originalPitch >= (size_t)cols * 3),
-        "pitch smaller than a row");
     DeviceGuard g(ctx->device);
-    // (as rtdd_paint_strokes: the pyramid hears of the write, and of an erasure; nothing goes into the pending-call log -- a paint call
-    // cannot time out, and an estimate that is run again reads the images as the paint calls in front of it left them)
-    RTDD_TRY(pyramid_note_write(ctx, scribble, edited, erases));
-    return launch_fill_polygon(ctx, xy, n, *fill, edited, editedPitch, scribble, scribblePitch, original, originalPitch, rows, cols);
+    RTDD_TRY(begin_paint(ctx, t, erases));
+    return launch_fill_polygon(ctx, xy, n, *fill, t);
 }
 
 // host arithmetic only (include/rtdd.h has the rule): doubles, every operation rounded on its own

@@ -1,14 +1,14 @@
 // rtdd_fill_polygon (extension, include/rtdd.h): a closed integer contour filled with a label, a ramp or erased -- the lasso beside the
-// brushes of image_kernels.hip.  One launch over the contour's bounding box clipped to the image, 64 x 16 tiles, 256 threads, one wave
-// per row and four rows per wave, as k_paint_strokes.  The vertices travel as kernel arguments (x | y << 16, 4 bytes each, 768 at the
-// most: 3 KB, no device buffer, nothing of the caller's read after the call returns).
+// brushes of image_kernels.hip.  One launch over the contour's bounding box clipped to the image, in k_paint_strokes' tiles
+// (paint_common.hpp).  The vertices travel as kernel arguments (pack_xy: 4 bytes each, 768 at the most: 3 KB, no device buffer, nothing
+// of the caller's read after the call returns).
 #include <algorithm>
 
-#include "rtdd_internal.hpp"
+#include "paint_common.hpp"
 
 namespace rtdd {
 
-constexpr int kFillMaxVertices = 768, kFillTileW = 64, kFillTileH = 16;
+constexpr int kFillMaxVertices = 768;
 struct FillArgs {
     int n;                          // vertices = edges of the closed contour (edge e: v[e] -> v[e + 1 == n ? 0 : e + 1])
     int x0, y0, x1, y1;             // the contour's bounding box clipped to the image (inclusive), x0 rounded down to a multiple of 64
@@ -18,28 +18,22 @@ struct FillArgs {
     int ax0, ay0, adx, ady;         // the axis: its first end and its direction
     long long dd, A;                // adx^2 + ady^2;  (2 label0 + 1) dd
     int B;                          // 2 (label1 - label0)
-    uint32_t v[kFillMaxVertices];   // x | y << 16 (two's complement halves)
+    uint32_t v[kFillMaxVertices];   // pack_xy
 };
 
 // a live edge of a tile: cr at the tile's origin, its direction, and the closed box of the boundary test (whose y-range also says whether
 // the edge goes up, ya < yb, down or neither)
 struct FillEdge { long long cr0; int dxe, dye; int ya_yb, xmin_xmax; };   // the packed pairs: low half | high half << 16, signed halves
 
-// rtdd_paint_ramp_strokes' label rule with the fill's axis as the segment (image_kernels.hip's ramp_label has the derivation and the error
-// bound of the quotient): L = N div D, N = (2 l0 + 1) dd + 2 (l1 - l0) t, t = v.d clamped to [0, dd], D = 2 dd.  The axis is the same for
-// every pixel of a launch, so dd, the first term of N (A), the factor of t (B) and rcp((float)D) come in ready-made.  A pixel may lie
-// anywhere in the image here, not just in a stroke's grown box: |v| < 2^16 + 2^15, |d| < 2^16, so |v.d| < 2^33.2, dd < 2^33, 0 <= N <=
-// 511 dd < 2^42 and D < 2^34 -- inside the bounds ramp_label's estimate was derived for (N < 2^45: its high word below 2^13, exact in
-// f32), so q = trunc(fn * rcp(fd)) is floor(N / D) - 1, floor(N / D) or floor(N / D) + 1 and the exact remainder says which.
+// rtdd_paint_ramp_strokes' label rule with the fill's axis as the segment: L = N div D, N = (2 l0 + 1) dd + 2 (l1 - l0) t, t = v.d clamped
+// to [0, dd], D = 2 dd.  The axis is the same for every pixel of a launch, so dd, the first term of N (A), the factor of t (B) and
+// rcp((float)D) come in ready-made.  A pixel may lie anywhere in the image here, not just in a stroke's grown box: |v| < 2^16 + 2^15,
+// |d| < 2^16, so |v.d| < 2^33.2, dd < 2^33, 0 <= N <= 511 dd < 2^42 and D < 2^34 -- inside the bounds ramp_quotient asks for.
 __device__ __forceinline__ int fill_label(int px, int py, const FillArgs &C, float rcpD) {
     const long long vx = px - C.ax0, vy = py - C.ay0;
     const long long t = min(max(vx * C.adx + vy * C.ady, 0ll), C.dd);
-    const long long N = C.A + (long long)C.B * t, D = 2 * C.dd;
-    const float fn = __builtin_fmaf((float)(uint32_t)((unsigned long long)N >> 32), 4294967296.0f, (float)(uint32_t)N);
-    int q = (int)(fn * rcpD);
-    const long long r = N - (long long)q * D;
-    q += (int)(r >= D) - (int)(r < 0);
-    return q;
+    const long long N = C.A + (long long)C.B * t;
+    return ramp_quotient(N, 2 * C.dd, ramp_f32(N) * rcpD);
 }
 
 // The winding number of include/rtdd.h counts, for pixel p, the edges that cross p's row strictly to the RIGHT of p (cr > 0 on an edge
@@ -59,12 +53,12 @@ __global__ __launch_bounds__(256) void k_fill_polygon(const FillArgs C, uint8_t 
                                                       uint8_t *__restrict__ scribble, size_t scribblePitch,
                                                       const uint8_t *__restrict__ original, size_t originalPitch) {
     __shared__ FillEdge live[kFillMaxVertices];
-    __shared__ int base[kFillTileH];
+    __shared__ int base[kPaintTileH];
     __shared__ int total_s;
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
-    const int tx0 = C.x0 + (int)blockIdx.x * kFillTileW, ty0 = C.y0 + (int)blockIdx.y * kFillTileH;
-    const int tx1 = min(tx0 + kFillTileW - 1, C.x1), ty1 = min(ty0 + kFillTileH - 1, C.y1);
-    if (tid < kFillTileH) base[tid] = 0;
+    const int tx0 = C.x0 + (int)blockIdx.x * kPaintTileW, ty0 = C.y0 + (int)blockIdx.y * kPaintTileH;
+    const int tx1 = min(tx0 + kPaintTileW - 1, C.x1), ty1 = min(ty0 + kPaintTileH - 1, C.y1);
+    if (tid < kPaintTileH) base[tid] = 0;
     if (tid == 0) total_s = 0;
     __syncthreads();
     // cull: edges tid, tid + 256, tid + 512 against this tile (the loop's trip count is the same in every thread: ballots inside)
@@ -74,7 +68,7 @@ __global__ __launch_bounds__(256) void k_fill_polygon(const FillArgs C, uint8_t 
         FillEdge rec{};
         if (e < C.n) {
             const uint32_t pa = C.v[e], pb = C.v[e + 1 == C.n ? 0 : e + 1];
-            const int ax = (int16_t)(pa & 0xFFFF), ay = (int16_t)(pa >> 16), bx = (int16_t)(pb & 0xFFFF), by = (int16_t)(pb >> 16);
+            const int ax = unpack_x(pa), ay = unpack_y(pa), bx = unpack_x(pb), by = unpack_y(pb);
             const int xmin = min(ax, bx), xmax = max(ax, bx), ymin = min(ay, by), ymax = max(ay, by);
             if (ymin <= ty1 && ymax >= ty0 && xmax >= tx0) {
                 if (xmin <= tx1) {
@@ -106,7 +100,7 @@ __global__ __launch_bounds__(256) void k_fill_polygon(const FillArgs C, uint8_t 
     for (int k = 0; k < 4; k++) { w[k] = base[wave + 4 * k]; on[k] = false; }
     for (int i = 0; i < total; i++) {
         const FillEdge r = live[i];                                  // (one address for the whole wave: an LDS broadcast)
-        const int ya = (int16_t)(r.ya_yb & 0xFFFF), yb = r.ya_yb >> 16, xmin = (int16_t)(r.xmin_xmax & 0xFFFF), xmax = r.xmin_xmax >> 16;
+        const int ya = unpack_x(r.ya_yb), yb = r.ya_yb >> 16, xmin = unpack_x(r.xmin_xmax), xmax = r.xmin_xmax >> 16;      // (signed words: the high halves by a shift)
         const bool inx = x >= xmin && x <= xmax;
         long long cr = r.cr0 + (long long)(r.dxe * wave - r.dye * rx);
 #pragma unroll
@@ -137,19 +131,17 @@ __global__ __launch_bounds__(256) void k_fill_polygon(const FillArgs C, uint8_t 
 }
 
 // checked by rtdd_fill_polygon (api.cpp): 1 <= n <= 768, every coordinate in [-32768, 32767], the rule and the labels valid
-int launch_fill_polygon(rtdd_ctx *ctx, const int *xy, int n, const rtdd_fill &fill, uint8_t *edited, size_t editedPitch, uint8_t *scribble,
-                        size_t scribblePitch, const uint8_t *original, size_t originalPitch, int rows, int cols) {
+int launch_fill_polygon(rtdd_ctx *ctx, const int *xy, int n, const rtdd_fill &fill, const PaintTarget &t) {
     FillArgs C{};
-    int bx0 = xy[0], bx1 = xy[0], by0 = xy[1], by1 = xy[1];
+    C.x0 = C.x1 = xy[0]; C.y0 = C.y1 = xy[1];
     for (int i = 0; i < n; i++) {
         const int x = xy[2 * i], y = xy[2 * i + 1];
-        bx0 = std::min(bx0, x); bx1 = std::max(bx1, x); by0 = std::min(by0, y); by1 = std::max(by1, y);
-        C.v[i] = ((uint32_t)x & 0xFFFFu) | ((uint32_t)y << 16);
+        C.x0 = std::min(C.x0, x); C.x1 = std::max(C.x1, x); C.y0 = std::min(C.y0, y); C.y1 = std::max(C.y1, y);
+        C.v[i] = pack_xy(x, y);
     }
-    bx0 = std::max(bx0, 0); by0 = std::max(by0, 0); bx1 = std::min(bx1, cols - 1); by1 = std::min(by1, rows - 1);
-    if (bx1 < bx0 || by1 < by0) return RTDD_OK;                      // the contour lies wholly outside the image
-    bx0 &= ~63;                                                      // (a wave's 64 pixels start on a 64-pixel boundary of the row)
-    C.n = n; C.x0 = bx0; C.y0 = by0; C.x1 = bx1; C.y1 = by1;
+    dim3 grid;
+    if (!paint_grid(C.x0, C.y0, C.x1, C.y1, t.rows, t.cols, grid)) return RTDD_OK;      // the contour lies wholly outside the image
+    C.n = n;
     C.evenodd = fill.rule == RTDD_FILL_EVEN_ODD;
     C.label0 = fill.label0;
     C.ax0 = fill.ax0; C.ay0 = fill.ay0; C.adx = fill.ax1 - fill.ax0; C.ady = fill.ay1 - fill.ay0;
@@ -157,8 +149,7 @@ int launch_fill_polygon(rtdd_ctx *ctx, const int *xy, int n, const rtdd_fill &fi
     C.ramp = fill.label0 >= 0 && fill.label0 != fill.label1 && C.dd != 0;
     C.A = (long long)(2 * fill.label0 + 1) * C.dd;
     C.B = 2 * (fill.label1 - fill.label0);
-    const dim3 grid((bx1 - bx0) / kFillTileW + 1, (by1 - by0) / kFillTileH + 1);
-    hipLaunchKernelGGL(k_fill_polygon, grid, dim3(256), 0, ctx->stream, C, edited, editedPitch, scribble, scribblePitch, original, originalPitch);
+    hipLaunchKernelGGL(k_fill_polygon, grid, dim3(256), 0, ctx->stream, C, t.edited, t.editedPitch, t.scribble, t.scribblePitch, t.original, t.originalPitch);
     RTDD_LAUNCH_CHECK(ctx, "k_fill_polygon");
     return RTDD_OK;
 }

@@ -1,14 +1,16 @@
-// image_kernels.hip -- annotation-side passes: Dirichlet injection, 2x annotation downsample,
-// square brush.  All three are tiny, HBM-latency-bound byte kernels; one wave covers 64
-// consecutive pixels of a row so mask/depth accesses coalesce.
+// image_kernels.hip -- the annotation side: the reference's three byte kernels (Dirichlet injection K5, 2x annotation down-sample K6,
+// square brush K7: one wave covers 64 consecutive pixels of a row so mask/depth accesses coalesce); the annotation pyramid of an estimate
+// in one launch, accumulating or rebuilding, its chain through global memory or in LDS (two kernel templates); brush
+// strokes, constant or ramped (k_paint_strokes<>, which shares paint_common.hpp with fill_polygon.hip's lasso); and the row re-pitch
+// copy.  All tiny and HBM-latency-bound.  Their launchers follow the kernels.
 #include <algorithm>
 #include <type_traits>
 
-#include "rtdd_internal.hpp"
+#include "paint_common.hpp"
 
 namespace rtdd {
 
-// convert (K5) -- /root/reference/src/GPUImageProcessing.cu:8-21
+// convert (K5) -- src/GPUImageProcessing.cu:8-21
 __global__ __launch_bounds__(256) void k_convert(const uint8_t *__restrict__ src, size_t srcPitch, float *__restrict__ dst, size_t dstPitch,
                                                  const uint8_t *__restrict__ mask, size_t maskPitch, int rows, int cols, size_t zSrc, size_t zDst, size_t zMask) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
@@ -48,10 +50,10 @@ __global__ __launch_bounds__(256) void k_pyrdown_annotation(const uint8_t *__res
 // [a 2^l - (2^l - 1), a 2^l] and nothing else feed level-(l + k) pixel a ... : the footprints of the coarsest level's pixels tile
 // EVERY level disjointly.  A workgroup therefore owns kApB x kApB pixels of the coarsest level and, level by level, all the pixels of the
 // finer levels under them: it writes a level, __syncthreads(), and reads it back for the next one -- no other workgroup touches those
-// pixels, nothing is cleared (the coarse images accumulate over the frames exactly as with one launch per level), the scan order and
-// "last hit wins" are pyrDown's above.  Pixels of a fine level beyond the last coarsest pixel's footprint (the level sizes are floors)
-// belong to the workgroups of the next tile row / column: the grid is one tile larger than the coarsest level needs.
-// Five launches of ~7 us each (dependent, tiny) -> one: a live 1080p frame 1.18 -> 1.15 ms of GPU time (profiles/r05_live_timeline_*).
+// pixels, the scan order and "last hit wins" are pyrDown's above.  Pixels of a fine level beyond the last coarsest pixel's footprint (the
+// level sizes are floors) belong to the workgroups of the next tile row / column: the grid is one tile larger than the coarsest level
+// needs.  Five launches of ~7 us each (dependent, tiny) -> one: a live 1080p frame 1.18 -> 1.15 ms of GPU time
+// (profiles/r05_live_timeline_*).
 constexpr int kApMaxLevels = 12, kApB = 2;
 struct AnnotationPyramid {
     int levels;                                   // P
@@ -62,6 +64,16 @@ struct AnnotationPyramid {
     float *depth; size_t dp, zd;                  // the coarsest level's depth image (src/main.cpp:257-259)
 };
 
+// The chain through global memory (any depth).  kRebuild = false accumulates: the coarse images keep what earlier frames left, exactly
+// as with one launch per level.  kRebuild = true (rtdd_pyramid_annotation_rebuild, an erasing paint call) builds the coarse levels as if
+// they had been all zero before the down-sampling: the footprints tile every level completely and disjointly, so each workgroup simply
+// stores EVERY pixel of its footprint and never reads the old coarse contents -- no memsets in front, one launch.  The store is all that
+// differs: accumulating, only on a hit, the flag and channel 0 (K6: nothing is ever cleared); rebuilding, every pixel, hit or not:
+// scribble 255 / 0, edited (winner, 0, 0) / (0, 0, 0) -- channels 1 and 2 of a coarse edited image are never written by
+// GPUPyrDownAnnotation and are zero after creation.
+// (The scan, the footprint origin and the convert tail are written out here and again in the LDS chain: as __forceinline__ functions
+// they moved the kernels' scalar loads and address arithmetic, and scripts/effect_isa_diff.py --multiset is the yardstick of this file.)
+template <bool kRebuild>
 __global__ __launch_bounds__(256) void k_annotation_pyramid(AnnotationPyramid A) {
     const int P = A.levels, top = P - 1;
     const size_t z = blockIdx.z;
@@ -86,7 +98,11 @@ __global__ __launch_bounds__(256) void k_annotation_pyramid(AnnotationPyramid A)
                         if (px >= 0 && py >= 0 && px < pcols && py < prows && ps[(size_t)py * A.sp[l - 1] + px] == 255)
                             hit = pe[(size_t)py * A.ep[l - 1] + 3 * px];
                     }
-                if (hit >= 0) {
+                if constexpr (kRebuild) {
+                    cs[(size_t)y * A.sp[l] + x] = hit >= 0 ? 255 : 0;
+                    uint8_t *e = ce + (size_t)y * A.ep[l] + 3 * x;
+                    e[0] = (uint8_t)(hit >= 0 ? hit : 0); e[1] = 0; e[2] = 0;
+                } else if (hit >= 0) {
                     cs[(size_t)y * A.sp[l] + x] = 255;
                     ce[(size_t)y * A.ep[l] + 3 * x] = (uint8_t)hit;
                 }
@@ -106,20 +122,26 @@ __global__ __launch_bounds__(256) void k_annotation_pyramid(AnnotationPyramid A)
 // The same pyramid with the chain in LDS (pyramids of up to six levels: every size up to 4K).  In footprint-local coordinates (origin =
 // the unclipped first pixel of the workgroup's footprint on that level) level-l pixel (lx, ly) reads level-(l - 1) pixels
 // (2 lx + {0, 1}, 2 ly + {0, 1}), and all a level hands to the next is "the edited value where the scribble flag is 255, else nothing":
-// one short per pixel.  Every global load of the workgroup -- its level-0 footprint and, because the coarse images accumulate over the
-// frames, the OLD state of every coarser level -- is issued before the first is used (ONE memory round trip; a first version that
-// stored each level's map to LDS as it arrived paid one per level and measured no faster than the global chain: EXPERIMENTS.md), then
-// the levels are walked in LDS and the pixels that were hit stored.
-template <int TOP>
+// one short per pixel.  Every global load of the workgroup is issued before the first is used (ONE memory round trip; a first version
+// that stored each level's map to LDS as it arrived paid one per level and measured no faster than the global chain: EXPERIMENTS.md),
+// then the levels are walked in LDS and stored.  Where the two variants differ:
+//   the preload    accumulating: the level-0 footprint and, because the coarse images accumulate over the frames, the OLD state of every
+//                  coarser level.  Rebuilding: level 0 only, a fifth of the loads (the old coarse state is not wanted), its flag masked
+//                  by `in` as it is loaded.
+//   the map write  accumulating: only a pixel inside the level that was hit (its old state is in the map already).  Rebuilding: always,
+//                  in ? hit : -1 -- a pixel outside the level hands nothing on, as in the global chain.
+//   the store      as in the global chain: the pixels that were hit / every pixel of every coarse footprint.
+template <int TOP, bool kRebuild>
 __global__ __launch_bounds__(256) void k_annotation_pyramid_lds(AnnotationPyramid A) {
     constexpr int kN0 = kApB << TOP, kE0 = (kN0 * kN0 + 255) / 256;  // level-0 footprint edge, its entries per thread
     constexpr int kTotal = (4 * kN0 * kN0 - kApB * kApB) / 3;       // sum over the levels of (kApB << (TOP - l))^2
+    constexpr int kLoaded = kRebuild ? 0 : TOP;                      // the last level that is preloaded
     __shared__ short map[kTotal];
     const int tid = threadIdx.x;
     const size_t z = blockIdx.z;
-    int flag[TOP + 1][kE0], val[TOP + 1][kE0];
+    int flag[kLoaded + 1][kE0], val[kLoaded + 1][kE0];
 #pragma unroll
-    for (int l = 0; l <= TOP; l++) {
+    for (int l = 0; l <= kLoaded; l++) {
         const int f = 1 << (TOP - l), n = kApB * f;
         const int x0 = (int)blockIdx.x * kApB * f - (f - 1), y0 = (int)blockIdx.y * kApB * f - (f - 1);
         const uint8_t *ps = A.scribble[l] + z * A.zs[l], *pe = A.edited[l] + z * A.ze[l];
@@ -129,19 +151,21 @@ __global__ __launch_bounds__(256) void k_annotation_pyramid_lds(AnnotationPyrami
             const int i = tid + 256 * k, lx = i & (n - 1), ly = i / n, x = x0 + lx, y = y0 + ly;
             const bool in = i < n * n && x >= 0 && y >= 0 && x < A.cols[l] && y < A.rows[l];
             const int xc = in ? x : 0, yc = in ? y : 0;
-            flag[l][k] = ps[(size_t)yc * A.sp[l] + xc]; val[l][k] = pe[(size_t)yc * A.ep[l] + 3 * xc];
+            if constexpr (kRebuild) flag[l][k] = in ? ps[(size_t)yc * A.sp[l] + xc] : 0;
+            else flag[l][k] = ps[(size_t)yc * A.sp[l] + xc];
+            val[l][k] = pe[(size_t)yc * A.ep[l] + 3 * xc];
         }
     }
     int off = 0;
 #pragma unroll
-    for (int l = 0; l <= TOP; l++) {
+    for (int l = 0; l <= kLoaded; l++) {
         const int f = 1 << (TOP - l), n = kApB * f;
         const int x0 = (int)blockIdx.x * kApB * f - (f - 1), y0 = (int)blockIdx.y * kApB * f - (f - 1);
 #pragma unroll
         for (int k = 0; k < kE0; k++) {
             if (k * 256 >= n * n) continue;
             const int i = tid + 256 * k, lx = i & (n - 1), ly = i / n, x = x0 + lx, y = y0 + ly;
-            const bool in = x >= 0 && y >= 0 && x < A.cols[l] && y < A.rows[l];
+            const bool in = kRebuild || (x >= 0 && y >= 0 && x < A.cols[l] && y < A.rows[l]);
             if (i < n * n) map[off + i] = (short)((in && flag[l][k] == 255) ? val[l][k] : -1);
         }
         off += n * n;
@@ -165,7 +189,15 @@ __global__ __launch_bounds__(256) void k_annotation_pyramid_lds(AnnotationPyrami
                 if (q[1] >= 0) hit = q[1];
                 if (q[pn] >= 0) hit = q[pn];
                 if (q[pn + 1] >= 0) hit = q[pn + 1];
-                if (hit >= 0 && x >= 0 && y >= 0 && x < A.cols[l] && y < A.rows[l]) {
+                if constexpr (kRebuild) {
+                    const bool in = x >= 0 && y >= 0 && x < A.cols[l] && y < A.rows[l];
+                    map[coff + i] = (short)(in ? hit : -1);
+                    if (in) {
+                        cs[(size_t)y * A.sp[l] + x] = hit >= 0 ? 255 : 0;
+                        uint8_t *e = ce + (size_t)y * A.ep[l] + 3 * x;
+                        e[0] = (uint8_t)(hit >= 0 ? hit : 0); e[1] = 0; e[2] = 0;
+                    }
+                } else if (hit >= 0 && x >= 0 && y >= 0 && x < A.cols[l] && y < A.rows[l]) {
                     map[coff + i] = (short)hit;
                     cs[(size_t)y * A.sp[l] + x] = 255;
                     ce[(size_t)y * A.ep[l] + 3 * x] = (uint8_t)hit;
@@ -175,114 +207,7 @@ __global__ __launch_bounds__(256) void k_annotation_pyramid_lds(AnnotationPyrami
         __syncthreads();
         poff = coff;
     }
-    // convert (K5) on the coarsest level: the workgroup's kApB x kApB pixels
-    const int x = (int)blockIdx.x * kApB + (tid % kApB), y = (int)blockIdx.y * kApB + (tid / kApB);
-    if (tid < kApB * kApB && A.depth && x < A.cols[TOP] && y < A.rows[TOP]) {
-        const int v = map[poff + tid];
-        if (v >= 0) ((float *)((char *)A.depth + z * A.zd + (size_t)y * A.dp))[x] = (float)v;
-    }
-}
-
-// The annotation pyramid REBUILT (rtdd_pyramid_annotation_rebuild, an erasing rtdd_paint_strokes): the coarse levels as if they had been
-// all zero before the down-sampling.  Same ownership as k_annotation_pyramid -- a workgroup owns the footprint of its kApB x kApB coarsest
-// pixels on every level, and the footprints tile every level completely and disjointly -- so each workgroup simply stores EVERY pixel of
-// its footprint, hit or not (scribble 255 / 0; edited (winner, 0, 0) / (0, 0, 0): channels 1 and 2 of a coarse edited image are never
-// written by GPUPyrDownAnnotation and are zero after creation), and never reads the old coarse contents: no memsets in front, one launch.
-__global__ __launch_bounds__(256) void k_annotation_rebuild(AnnotationPyramid A) {
-    const int P = A.levels, top = P - 1;
-    const size_t z = blockIdx.z;
-    for (int l = 1; l <= top; l++) {
-        const int f = 1 << (top - l);
-        const int xa = max((int)blockIdx.x * kApB * f - (f - 1), 0), xb = min(((int)blockIdx.x * kApB + kApB - 1) * f, A.cols[l] - 1);
-        const int ya = max((int)blockIdx.y * kApB * f - (f - 1), 0), yb = min(((int)blockIdx.y * kApB + kApB - 1) * f, A.rows[l] - 1);
-        const int w = xb - xa + 1, h = yb - ya + 1;
-        if (w > 0 && h > 0) {
-            const uint8_t *ps = A.scribble[l - 1] + z * A.zs[l - 1], *pe = A.edited[l - 1] + z * A.ze[l - 1];
-            uint8_t *cs = A.scribble[l] + z * A.zs[l], *ce = A.edited[l] + z * A.ze[l];
-            const int prows = A.rows[l - 1], pcols = A.cols[l - 1];
-            for (int i = threadIdx.x; i < w * h; i += 256) {
-                const int x = xa + i % w, y = ya + i / w;
-                int hit = -1;
-#pragma unroll
-                for (int jj = -1; jj <= 0; jj++)
-#pragma unroll
-                    for (int ii = -1; ii <= 0; ii++) {
-                        const int px = 2 * x + ii, py = 2 * y + jj;
-                        if (px >= 0 && py >= 0 && px < pcols && py < prows && ps[(size_t)py * A.sp[l - 1] + px] == 255)
-                            hit = pe[(size_t)py * A.ep[l - 1] + 3 * px];
-                    }
-                cs[(size_t)y * A.sp[l] + x] = hit >= 0 ? 255 : 0;
-                uint8_t *e = ce + (size_t)y * A.ep[l] + 3 * x;
-                e[0] = (uint8_t)(hit >= 0 ? hit : 0); e[1] = 0; e[2] = 0;
-            }
-        }
-        __syncthreads();                                             // the level is read back by this workgroup only
-    }
-    const int x = (int)blockIdx.x * kApB + (int)(threadIdx.x % kApB), y = (int)blockIdx.y * kApB + (int)(threadIdx.x / kApB);
-    if (threadIdx.x < kApB * kApB && A.depth && x < A.cols[top] && y < A.rows[top]) {
-        const uint8_t *m = A.scribble[top] + z * A.zs[top], *e = A.edited[top] + z * A.ze[top];
-        if (m[(size_t)y * A.sp[top] + x] == 255)
-            ((float *)((char *)A.depth + z * A.zd + (size_t)y * A.dp))[x] = (float)e[(size_t)y * A.ep[top] + 3 * x];
-    }
-}
-
-// ... and with the chain in LDS: only the level-0 footprint is loaded (one memory round trip, a fifth of the accumulating kernel's
-// loads: the old coarse state is not wanted), the levels are walked in LDS and every pixel of every coarse footprint is stored.
-template <int TOP>
-__global__ __launch_bounds__(256) void k_annotation_rebuild_lds(AnnotationPyramid A) {
-    constexpr int kN0 = kApB << TOP, kE0 = (kN0 * kN0 + 255) / 256;
-    constexpr int kTotal = (4 * kN0 * kN0 - kApB * kApB) / 3;
-    __shared__ short map[kTotal];
-    const int tid = threadIdx.x;
-    const size_t z = blockIdx.z;
-    {
-        const int x0 = (int)blockIdx.x * kN0 - ((1 << TOP) - 1), y0 = (int)blockIdx.y * kN0 - ((1 << TOP) - 1);
-        const uint8_t *ps = A.scribble[0] + z * A.zs[0], *pe = A.edited[0] + z * A.ze[0];
-        int flag[kE0], val[kE0];
-#pragma unroll
-        for (int k = 0; k < kE0; k++) {
-            const int i = tid + 256 * k, lx = i & (kN0 - 1), ly = i / kN0, x = x0 + lx, y = y0 + ly;
-            const bool in = i < kN0 * kN0 && x >= 0 && y >= 0 && x < A.cols[0] && y < A.rows[0];
-            const int xc = in ? x : 0, yc = in ? y : 0;
-            flag[k] = in ? ps[(size_t)yc * A.sp[0] + xc] : 0; val[k] = pe[(size_t)yc * A.ep[0] + 3 * xc];
-        }
-#pragma unroll
-        for (int k = 0; k < kE0; k++) {
-            const int i = tid + 256 * k;
-            if (i < kN0 * kN0) map[i] = (short)(flag[k] == 255 ? val[k] : -1);
-        }
-    }
-    __syncthreads();
-    int poff = 0;
-#pragma unroll
-    for (int l = 1; l <= TOP; l++) {
-        const int f = 1 << (TOP - l), n = kApB * f, pn = 2 * n, coff = poff + pn * pn;
-        const int x0 = (int)blockIdx.x * kApB * f - (f - 1), y0 = (int)blockIdx.y * kApB * f - (f - 1);
-        uint8_t *cs = A.scribble[l] + z * A.zs[l], *ce = A.edited[l] + z * A.ze[l];
-#pragma unroll
-        for (int k = 0; k < kE0; k++) {
-            if (k * 256 >= n * n) continue;
-            const int i = tid + 256 * k;
-            if (i < n * n) {
-                const int lx = i & (n - 1), ly = i / n, x = x0 + lx, y = y0 + ly;
-                const short *q = map + poff + (2 * ly) * pn + 2 * lx;
-                int hit = -1;                                        // scan order py outer, px inner, the last hit wins (k_pyrdown_annotation)
-                if (q[0] >= 0) hit = q[0];
-                if (q[1] >= 0) hit = q[1];
-                if (q[pn] >= 0) hit = q[pn];
-                if (q[pn + 1] >= 0) hit = q[pn + 1];
-                const bool in = x >= 0 && y >= 0 && x < A.cols[l] && y < A.rows[l];
-                map[coff + i] = (short)(in ? hit : -1);              // (a pixel outside the level hands nothing on, as in the global chain)
-                if (in) {
-                    cs[(size_t)y * A.sp[l] + x] = hit >= 0 ? 255 : 0;
-                    uint8_t *e = ce + (size_t)y * A.ep[l] + 3 * x;
-                    e[0] = (uint8_t)(hit >= 0 ? hit : 0); e[1] = 0; e[2] = 0;
-                }
-            }
-        }
-        __syncthreads();
-        poff = coff;
-    }
+    // convert (K5) on the coarsest level: the workgroup's kApB x kApB pixels, whose labels the map holds
     const int x = (int)blockIdx.x * kApB + (tid % kApB), y = (int)blockIdx.y * kApB + (tid / kApB);
     if (tid < kApB * kApB && A.depth && x < A.cols[TOP] && y < A.rows[TOP]) {
         const int v = map[poff + tid];
@@ -311,15 +236,15 @@ __global__ __launch_bounds__(256) void k_paint(int x0, int y0, int x1, int y1, i
 // endpoints in [-32768, 32767], pixels in [0, 32767], radius <= 1024, so inside a stroke's grown box |v| and |d| stay below 2^17, every
 // product below 2^35, and the one square that can pass 2^63 -- (2 cross)^2 -- is compared only after 2 |cross| < 2^32 (at or beyond that
 // it exceeds radius^2 * |d|^2 <= 2^54 anyway).
-constexpr int kStrokeChunk = 256, kStrokeTileW = 64, kStrokeTileH = 16;
-struct PackedStroke { uint32_t p0, p1, meta; };  // x | y << 16 (two's complement halves); radius | brush << 11 | (label + 1) << 12 [| label1 << 21: a ramp]
+constexpr int kStrokeChunk = 256;
+struct PackedStroke { uint32_t p0, p1, meta; };  // the two ends (pack_xy); radius | brush << 11 | (label + 1) << 12 [| label1 << 21: a ramp]
 struct StrokeChunk {
     int count, x0, y0, x1, y1;                    // strokes in this chunk; its bounding box, clipped to the image (inclusive)
     PackedStroke s[kStrokeChunk];
 };
 
-__device__ __forceinline__ bool stroke_covers(int px, int py, int x0, int y0, int x1, int y1, int radius, int brush) {
-    const int h = radius / 2;
+__device__ __forceinline__ bool stroke_covers(int px, int py, uint32_t p0, uint32_t p1, int radius, int brush) {
+    const int x0 = unpack_x(p0), y0 = unpack_y(p0), x1 = unpack_x(p1), y1 = unpack_y(p1), h = radius / 2;
     if (px < min(x0, x1) - h || px > max(x0, x1) + h || py < min(y0, y1) - h || py > max(y0, y1) + h) return false;
     const long long dx = x1 - x0, dy = y1 - y0, vx = px - x0, vy = py - y0;
     const long long cross = dx * vy - dy * vx;
@@ -336,21 +261,13 @@ __device__ __forceinline__ bool stroke_covers(int px, int py, int x0, int y0, in
 // t = v.d clamped to [0, dd].  N is formed as (2 l0 + 1) dd + 2 (l1 - l0) t: the same integer, its first term the same in every lane.
 // Called only behind stroke_covers, i.e. inside the stroke's grown box, where |v|, |d| < 2^17: |v.d| and dd < 2^35, and 0 <= N <=
 // 511 dd < 2^45, D = 2 dd < 2^36 -- every product below fits 64 bits with room.
-// The quotient x = N / D is known to lie in [0, 255.5], so the compiler's general 64-bit division is not needed: an f32 estimate and one
-// correction step.  fn and fd are N and D rounded to f32 (the high word of N is below 2^13 and exact, the low word and the sum round
-// once each: relative error <= 2^-23; D likewise), v_rcp_f32 is good to 1 ulp (2^-23) and the product rounds once more (2^-24):
-// y = fn * rcp(fd) = x (1 + e) with |e| < 2^-21, so |y - x| < 256 * 2^-21 = 2^-13 and q = trunc(y) >= 0 is floor(x) - 1, floor(x) or
-// floor(x) + 1.  The remainder r = N - q D (|r| < 2 D < 2^37, exact in 64 bits) says which: r < 0: one too many; r >= D: one too few;
-// afterwards 0 <= N - q D < D, which is the definition of N div D.
-__device__ __forceinline__ int ramp_label(int px, int py, int x0, int y0, int x1, int y1, int l0, int l1) {
+// (ramp_quotient, paint_common.hpp, has the division and its error bound.)
+__device__ __forceinline__ int ramp_label(int px, int py, uint32_t p0, uint32_t p1, int l0, int l1) {
+    const int x0 = unpack_x(p0), y0 = unpack_y(p0), x1 = unpack_x(p1), y1 = unpack_y(p1);
     const long long dx = x1 - x0, dy = y1 - y0, vx = px - x0, vy = py - y0, dd = dx * dx + dy * dy;
     const long long t = min(max(vx * dx + vy * dy, 0ll), dd);
     const long long N = (long long)(2 * l0 + 1) * dd + (long long)(2 * (l1 - l0)) * t, D = 2 * dd;
-    const float fn = __builtin_fmaf((float)(uint32_t)((unsigned long long)N >> 32), 4294967296.0f, (float)(uint32_t)N);
-    int q = (int)(fn * __builtin_amdgcn_rcpf((float)(unsigned long long)D));
-    const long long r = N - (long long)q * D;
-    q += (int)(r >= D) - (int)(r < 0);
-    return q;
+    return ramp_quotient(N, D, ramp_f32(N) * __builtin_amdgcn_rcpf((float)(unsigned long long)D));
 }
 
 // kRamp = false: rtdd_paint_strokes.  kRamp = true: rtdd_paint_ramp_strokes -- the same tiles, cull and walk; the record's fourth word
@@ -360,17 +277,17 @@ template <bool kRamp>
 __global__ __launch_bounds__(256) void k_paint_strokes(const StrokeChunk C, uint8_t *__restrict__ edited, size_t editedPitch,
                                                        uint8_t *__restrict__ scribble, size_t scribblePitch,
                                                        const uint8_t *__restrict__ original, size_t originalPitch) {
-    __shared__ int4 live[kStrokeChunk];           // the surviving strokes, unpacked: (x0 | y0 << 16, x1 | y1 << 16, radius, brush | (label + 1) << 1 [| label1 << 10])
+    __shared__ int4 live[kStrokeChunk];           // the surviving strokes, unpacked: (the two ends, radius, brush | (label + 1) << 1 [| label1 << 10])
     __shared__ int wave_count[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
-    const int tx0 = C.x0 + (int)blockIdx.x * kStrokeTileW, ty0 = C.y0 + (int)blockIdx.y * kStrokeTileH;
-    const int tx1 = min(tx0 + kStrokeTileW - 1, C.x1), ty1 = min(ty0 + kStrokeTileH - 1, C.y1);
+    const int tx0 = C.x0 + (int)blockIdx.x * kPaintTileW, ty0 = C.y0 + (int)blockIdx.y * kPaintTileH;
+    const int tx1 = min(tx0 + kPaintTileW - 1, C.x1), ty1 = min(ty0 + kPaintTileH - 1, C.y1);
     // cull: stroke `tid` against this tile
     bool keep = false;
     int4 rec = make_int4(0, 0, 0, 0);
     if (tid < C.count) {
         const PackedStroke q = C.s[tid];
-        const int x0 = (int16_t)(q.p0 & 0xFFFF), y0 = (int16_t)(q.p0 >> 16), x1 = (int16_t)(q.p1 & 0xFFFF), y1 = (int16_t)(q.p1 >> 16);
+        const int x0 = unpack_x(q.p0), y0 = unpack_y(q.p0), x1 = unpack_x(q.p1), y1 = unpack_y(q.p1);
         const int radius = (int)(q.meta & 0x7FF), h = radius / 2;
         keep = min(x0, x1) - h <= tx1 && max(x0, x1) + h >= tx0 && min(y0, y1) - h <= ty1 && max(y0, y1) + h >= ty0;
         rec = make_int4((int)q.p0, (int)q.p1, radius, (int)(q.meta >> 11));
@@ -387,20 +304,18 @@ __global__ __launch_bounds__(256) void k_paint_strokes(const StrokeChunk C, uint
     const int x = tx0 + lane;
     if (x > tx1) return;
 #pragma unroll
-    for (int k = 0; k < kStrokeTileH / 4; k++) {
+    for (int k = 0; k < kPaintTileH / 4; k++) {
         const int y = ty0 + wave + 4 * k;
         if (y > ty1) break;
         for (int i = total - 1; i >= 0; i--) {
             const int4 r = live[i];                                  // (one address for the whole wave: an LDS broadcast)
-            if (!stroke_covers(x, y, (int16_t)(r.x & 0xFFFF), (int16_t)((uint32_t)r.x >> 16), (int16_t)(r.y & 0xFFFF), (int16_t)((uint32_t)r.y >> 16),
-                               r.z, r.w & 1)) continue;
+            if (!stroke_covers(x, y, r.x, r.y, r.z, r.w & 1)) continue;
             int label = (r.w >> 1) - 1;                              // RTDD_STROKE_ERASE = -1
             if constexpr (kRamp) {
                 label = ((r.w >> 1) & 0x1FF) - 1;
                 const int label1 = (r.w >> 10) & 0xFF;
                 if (label >= 0 && label1 != label && r.x != r.y)     // (wave-uniform: the record is)
-                    label = ramp_label(x, y, (int16_t)(r.x & 0xFFFF), (int16_t)((uint32_t)r.x >> 16), (int16_t)(r.y & 0xFFFF), (int16_t)((uint32_t)r.y >> 16),
-                                       label, label1);
+                    label = ramp_label(x, y, r.x, r.y, label, label1);
             }
             uint8_t *e = edited + (size_t)y * editedPitch + 3 * x;
             if (label >= 0) {
@@ -457,6 +372,16 @@ int launch_pyrdown_annotation(rtdd_ctx *ctx, const uint8_t *ps, size_t psp, cons
     return RTDD_OK;
 }
 
+// the kernel for a pyramid of top + 1 levels: the chain in LDS where it is asked for (RTDD_OPT_ANNOTATION_LDS) and compiled (two to six
+// levels), through global memory otherwise
+using AnnotationKernel = void (*)(AnnotationPyramid);
+template <bool kRebuild>
+static AnnotationKernel annotation_kernel(bool lds, int top) {
+    static constexpr AnnotationKernel in_lds[] = {k_annotation_pyramid_lds<1, kRebuild>, k_annotation_pyramid_lds<2, kRebuild>, k_annotation_pyramid_lds<3, kRebuild>,
+                                                  k_annotation_pyramid_lds<4, kRebuild>, k_annotation_pyramid_lds<5, kRebuild>};
+    return lds && top >= 1 && top <= 5 ? in_lds[top - 1] : k_annotation_pyramid<kRebuild>;
+}
+
 int launch_annotation_pyramid(rtdd_ctx *ctx, int levels, uint8_t *const *scribble, const size_t *sp, const size_t *zs, uint8_t *const *edited, const size_t *ep, const size_t *ze,
                               const int *rows, const int *cols, float *depth, size_t dp, size_t zd, int images, bool rebuild) {
     if (levels < 1 || levels > kApMaxLevels) return fail(ctx, RTDD_ERR_INVALID, "annotation pyramid: too many levels");
@@ -477,34 +402,22 @@ int launch_annotation_pyramid(rtdd_ctx *ctx, int levels, uint8_t *const *scribbl
     if (top == 0) { gx = (cols[0] + kApB - 1) / kApB; gy = (rows[0] + kApB - 1) / kApB; }
     if (gx < 1 || gy < 1) return RTDD_OK;
     const dim3 grid(gx, gy, images);
-    const int lds = ctx->opt.annotation_lds;
     if (rebuild) {
-        if (lds && top == 1) hipLaunchKernelGGL(k_annotation_rebuild_lds<1>, grid, dim3(256), 0, ctx->stream, A);
-        else if (lds && top == 2) hipLaunchKernelGGL(k_annotation_rebuild_lds<2>, grid, dim3(256), 0, ctx->stream, A);
-        else if (lds && top == 3) hipLaunchKernelGGL(k_annotation_rebuild_lds<3>, grid, dim3(256), 0, ctx->stream, A);
-        else if (lds && top == 4) hipLaunchKernelGGL(k_annotation_rebuild_lds<4>, grid, dim3(256), 0, ctx->stream, A);
-        else if (lds && top == 5) hipLaunchKernelGGL(k_annotation_rebuild_lds<5>, grid, dim3(256), 0, ctx->stream, A);
-        else hipLaunchKernelGGL(k_annotation_rebuild, grid, dim3(256), 0, ctx->stream, A);
+        hipLaunchKernelGGL(annotation_kernel<true>(ctx->opt.annotation_lds, top), grid, dim3(256), 0, ctx->stream, A);
         RTDD_LAUNCH_CHECK(ctx, "k_annotation_rebuild");
-        return RTDD_OK;
+    } else {
+        hipLaunchKernelGGL(annotation_kernel<false>(ctx->opt.annotation_lds, top), grid, dim3(256), 0, ctx->stream, A);
+        RTDD_LAUNCH_CHECK(ctx, "k_annotation_pyramid");
     }
-    if (lds && top == 1) hipLaunchKernelGGL(k_annotation_pyramid_lds<1>, grid, dim3(256), 0, ctx->stream, A);
-    else if (lds && top == 2) hipLaunchKernelGGL(k_annotation_pyramid_lds<2>, grid, dim3(256), 0, ctx->stream, A);
-    else if (lds && top == 3) hipLaunchKernelGGL(k_annotation_pyramid_lds<3>, grid, dim3(256), 0, ctx->stream, A);
-    else if (lds && top == 4) hipLaunchKernelGGL(k_annotation_pyramid_lds<4>, grid, dim3(256), 0, ctx->stream, A);
-    else if (lds && top == 5) hipLaunchKernelGGL(k_annotation_pyramid_lds<5>, grid, dim3(256), 0, ctx->stream, A);
-    else hipLaunchKernelGGL(k_annotation_pyramid, grid, dim3(256), 0, ctx->stream, A);      // (deeper pyramids: the levels through global memory)
-    RTDD_LAUNCH_CHECK(ctx, "k_annotation_pyramid");
     return RTDD_OK;
 }
 
-int launch_paint(rtdd_ctx *ctx, int x, int y, int color, int radius, uint8_t *edited, size_t editedPitch,
-                 uint8_t *scribble, size_t scribblePitch, int rows, int cols) {
+int launch_paint(rtdd_ctx *ctx, int x, int y, int color, int radius, const PaintTarget &t) {
     const int h = radius / 2;                          // C integer division, as the reference (:58-59)
     const int x0 = x - h < 0 ? 0 : x - h, y0 = y - h < 0 ? 0 : y - h;
-    const int x1 = x + h > cols - 1 ? cols - 1 : x + h, y1 = y + h > rows - 1 ? rows - 1 : y + h;
+    const int x1 = x + h > t.cols - 1 ? t.cols - 1 : x + h, y1 = y + h > t.rows - 1 ? t.rows - 1 : y + h;
     if (x1 < x0 || y1 < y0) return RTDD_OK;            // brush entirely outside the image (or negative radius)
-    hipLaunchKernelGGL(k_paint, grid64x4(y1 - y0 + 1, x1 - x0 + 1), dim3(256), 0, ctx->stream, x0, y0, x1, y1, color, edited, editedPitch, scribble, scribblePitch);
+    hipLaunchKernelGGL(k_paint, grid64x4(y1 - y0 + 1, x1 - x0 + 1), dim3(256), 0, ctx->stream, x0, y0, x1, y1, color, t.edited, t.editedPitch, t.scribble, t.scribblePitch);
     RTDD_LAUNCH_CHECK(ctx, "k_paint");
     return RTDD_OK;
 }
@@ -515,42 +428,29 @@ static uint32_t pack_labels(const rtdd_stroke &q) { return (uint32_t)(q.label + 
 static uint32_t pack_labels(const rtdd_ramp_stroke &q) { return (uint32_t)(q.label0 + 1) << 12 | (uint32_t)std::max(q.label1, 0) << 21; }
 
 template <class Stroke>
-static int launch_strokes(rtdd_ctx *ctx, const Stroke *strokes, int count, uint8_t *edited, size_t editedPitch, uint8_t *scribble,
-                          size_t scribblePitch, const uint8_t *original, size_t originalPitch, int rows, int cols) {
+int launch_paint_strokes(rtdd_ctx *ctx, const Stroke *strokes, int count, const PaintTarget &t) {
     constexpr bool ramp = std::is_same<Stroke, rtdd_ramp_stroke>::value;
     for (int first = 0; first < count; first += kStrokeChunk) {
         StrokeChunk C;
         C.count = count - first < kStrokeChunk ? count - first : kStrokeChunk;
-        int bx0 = cols, by0 = rows, bx1 = -1, by1 = -1;              // union of the strokes' boxes, clipped to the image
+        C.x0 = t.cols; C.y0 = t.rows; C.x1 = -1; C.y1 = -1;          // union of the strokes' boxes, each clipped to the image
         for (int i = 0; i < C.count; i++) {
             const Stroke &q = strokes[first + i];
             const int h = q.radius / 2;
-            const int x0 = std::max(std::min(q.x0, q.x1) - h, 0), x1 = std::min(std::max(q.x0, q.x1) + h, cols - 1);
-            const int y0 = std::max(std::min(q.y0, q.y1) - h, 0), y1 = std::min(std::max(q.y0, q.y1) + h, rows - 1);
-            if (x0 <= x1 && y0 <= y1) { bx0 = std::min(bx0, x0); bx1 = std::max(bx1, x1); by0 = std::min(by0, y0); by1 = std::max(by1, y1); }
-            C.s[i].p0 = ((uint32_t)q.x0 & 0xFFFFu) | ((uint32_t)q.y0 << 16);
-            C.s[i].p1 = ((uint32_t)q.x1 & 0xFFFFu) | ((uint32_t)q.y1 << 16);
-            C.s[i].meta = (uint32_t)q.radius | ((uint32_t)q.brush << 11) | pack_labels(q);
+            const int x0 = std::max(std::min(q.x0, q.x1) - h, 0), x1 = std::min(std::max(q.x0, q.x1) + h, t.cols - 1);
+            const int y0 = std::max(std::min(q.y0, q.y1) - h, 0), y1 = std::min(std::max(q.y0, q.y1) + h, t.rows - 1);
+            if (x0 <= x1 && y0 <= y1) { C.x0 = std::min(C.x0, x0); C.x1 = std::max(C.x1, x1); C.y0 = std::min(C.y0, y0); C.y1 = std::max(C.y1, y1); }
+            C.s[i] = PackedStroke{pack_xy(q.x0, q.y0), pack_xy(q.x1, q.y1), (uint32_t)q.radius | ((uint32_t)q.brush << 11) | pack_labels(q)};
         }
         for (int i = C.count; i < kStrokeChunk; i++) C.s[i] = PackedStroke{0, 0, 0};
-        if (bx1 < bx0 || by1 < by0) continue;                        // every stroke of the chunk lies outside the image
-        bx0 &= ~63;                                                  // (a wave's 64 pixels start on a 64-pixel boundary of the row)
-        C.x0 = bx0; C.y0 = by0; C.x1 = bx1; C.y1 = by1;
-        const dim3 grid((bx1 - bx0) / kStrokeTileW + 1, (by1 - by0) / kStrokeTileH + 1);
-        hipLaunchKernelGGL(k_paint_strokes<ramp>, grid, dim3(256), 0, ctx->stream, C, edited, editedPitch, scribble, scribblePitch, original, originalPitch);
+        dim3 grid;
+        if (!paint_grid(C.x0, C.y0, C.x1, C.y1, t.rows, t.cols, grid)) continue;        // every stroke of the chunk lies outside the image
+        hipLaunchKernelGGL(k_paint_strokes<ramp>, grid, dim3(256), 0, ctx->stream, C, t.edited, t.editedPitch, t.scribble, t.scribblePitch, t.original, t.originalPitch);
         RTDD_LAUNCH_CHECK(ctx, "k_paint_strokes");
     }
     return RTDD_OK;
 }
-
-int launch_paint_strokes(rtdd_ctx *ctx, const rtdd_stroke *strokes, int count, uint8_t *edited, size_t editedPitch, uint8_t *scribble,
-                         size_t scribblePitch, const uint8_t *original, size_t originalPitch, int rows, int cols) {
-    return launch_strokes(ctx, strokes, count, edited, editedPitch, scribble, scribblePitch, original, originalPitch, rows, cols);
-}
-
-int launch_paint_ramp_strokes(rtdd_ctx *ctx, const rtdd_ramp_stroke *strokes, int count, uint8_t *edited, size_t editedPitch, uint8_t *scribble,
-                              size_t scribblePitch, const uint8_t *original, size_t originalPitch, int rows, int cols) {
-    return launch_strokes(ctx, strokes, count, edited, editedPitch, scribble, scribblePitch, original, originalPitch, rows, cols);
-}
+template int launch_paint_strokes(rtdd_ctx *, const rtdd_stroke *, int, const PaintTarget &);
+template int launch_paint_strokes(rtdd_ctx *, const rtdd_ramp_stroke *, int, const PaintTarget &);
 
 }  // namespace rtdd

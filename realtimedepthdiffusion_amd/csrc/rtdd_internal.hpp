@@ -372,19 +372,22 @@ int launch_annotation_pyramid(rtdd_ctx *ctx, int levels, uint8_t *const *scribbl
 int launch_repitch(rtdd_ctx *ctx, hipStream_t stream, const void *src, size_t srcPitch, void *dst, size_t dstPitch, size_t widthBytes, int rows);
 int copy_h2d(rtdd_ctx *ctx, Bounce &b, void *dev, size_t devPitch, const void *host, size_t hostPitch, size_t widthBytes, int rows, hipStream_t stream);
 int copy_d2h(rtdd_ctx *ctx, Bounce &b, void *host, size_t hostPitch, const void *dev, size_t devPitch, size_t widthBytes, int rows, hipStream_t stream);
-int launch_paint(rtdd_ctx *ctx, int x, int y, int color, int radius, uint8_t *edited, size_t editedPitch,
-                 uint8_t *scribble, size_t scribblePitch, int rows, int cols);
-// rtdd_paint_strokes: `count` checked strokes in array order, kStrokeChunk per launch (the records are kernel arguments)
-int launch_paint_strokes(rtdd_ctx *ctx, const rtdd_stroke *strokes, int count, uint8_t *edited, size_t editedPitch, uint8_t *scribble,
-                         size_t scribblePitch, const uint8_t *original, size_t originalPitch, int rows, int cols);
-// rtdd_paint_ramp_strokes: the same launches with the kernel's ramp variant (the second label rides in the 12-byte record's spare bits)
-int launch_paint_ramp_strokes(rtdd_ctx *ctx, const rtdd_ramp_stroke *strokes, int count, uint8_t *edited, size_t editedPitch, uint8_t *scribble,
-                              size_t scribblePitch, const uint8_t *original, size_t originalPitch, int rows, int cols);
+// what the paint calls write: the annotation pair, the original an eraser restores from (null: none given), the size of all three
+struct PaintTarget {
+    uint8_t *edited; size_t editedPitch;
+    uint8_t *scribble; size_t scribblePitch;
+    const uint8_t *original; size_t originalPitch;
+    int rows, cols;
+};
+int launch_paint(rtdd_ctx *ctx, int x, int y, int color, int radius, const PaintTarget &t);
+// rtdd_paint_strokes / rtdd_paint_ramp_strokes (Stroke = rtdd_stroke / rtdd_ramp_stroke: the kernel's constant and ramp variants; a ramp's
+// second label rides in the 12-byte record's spare bits): `count` checked strokes in array order, kStrokeChunk per launch (the records
+// are kernel arguments)
+template <class Stroke> int launch_paint_strokes(rtdd_ctx *ctx, const Stroke *strokes, int count, const PaintTarget &t);
 
 // ---- fill_polygon.hip ---------------------------------------------------------------------------
 // rtdd_fill_polygon: the checked contour (1 <= n <= 768 vertices, as kernel arguments) in one launch over its clipped bounding box
-int launch_fill_polygon(rtdd_ctx *ctx, const int *xy, int n, const rtdd_fill &fill, uint8_t *edited, size_t editedPitch, uint8_t *scribble,
-                        size_t scribblePitch, const uint8_t *original, size_t originalPitch, int rows, int cols);
+int launch_fill_polygon(rtdd_ctx *ctx, const int *xy, int n, const rtdd_fill &fill, const PaintTarget &t);
 
 // ---- effect_kernels.hip -------------------------------------------------------------------------
 int launch_effect(rtdd_ctx *ctx, const Effect &e);

@@ -17,7 +17,14 @@ or exists in one object only a line and the start of its instruction diff; exit 
 is the check for an edit that moves device code into shared helpers: inlining the same statements from another place may rename registers
 and reorder independent instructions, which the exact comparison reports and which costs nothing.  Per kernel it compares the MULTISET of
 mnemonics (operands dropped: how many of each instruction, in any order) and the kernel's resources from the code object's metadata --
-VGPRs, AGPRs, SGPRs, LDS bytes, scratch bytes.  A kernel that differs prints the mnemonics whose counts changed and the resources that did."""
+VGPRs, AGPRs, SGPRs, LDS bytes, scratch bytes.  A kernel that differs prints the mnemonics whose counts changed and the resources that did.
+Instructions behind a kernel's last s_endpgm are not counted: they are padding up to the next function's alignment and never run.
+
+    python scripts/effect_isa_diff.py [--multiset] --rename 'OLD=NEW' [--rename ...] OLD/X.dev.o NEW/X.dev.o
+
+compares the old object's function OLD with the new object's NEW (demangled names, as the tool prints them): for an edit that renames a
+kernel or turns two kernels into instantiations of one template."""
+import argparse
 import collections
 import difflib
 import re
@@ -60,14 +67,24 @@ def resources(path):
     return {demangled[r[".name"]]: tuple(int(r[k]) for k in RESOURCES) for r in recs}
 
 
-def main_multiset(old_path, new_path):
-    old, new, rold, rnew = kernels(old_path), kernels(new_path), resources(old_path), resources(new_path)
+def renamed(d, renames):
+    return {renames.get(k, k): v for k, v in d.items()}
+
+
+def executed(ins):
+    """The instructions up to and including the last s_endpgm (all of them where there is none: a device function)."""
+    ends = [i for i, x in enumerate(ins) if x.split()[0] == "s_endpgm"]
+    return ins[:ends[-1] + 1] if ends else ins
+
+
+def main_multiset(old_path, new_path, renames):
+    old, new, rold, rnew = renamed(kernels(old_path), renames), kernels(new_path), renamed(resources(old_path), renames), resources(new_path)
     names = sorted(n for n in old.keys() | new.keys() if n in rold or n in rnew)       # kernels only: they alone have resources
     bad = 0
     for n in names:
         if n not in new or n not in old:
             print("missing in the", "new" if n not in new else "old", "object:", n); bad += 1; continue
-        a, b = (collections.Counter(i.split()[0] for i in k[n]) for k in (old, new))
+        a, b = (collections.Counter(i.split()[0] for i in executed(k[n])) for k in (old, new))
         if a == b and rold[n] == rnew[n]:
             continue
         print("differs:", n); bad += 1
@@ -81,8 +98,8 @@ def main_multiset(old_path, new_path):
     return 1 if bad else 0
 
 
-def main(old_path, new_path):
-    old, new = kernels(old_path), kernels(new_path)
+def main(old_path, new_path, renames):
+    old, new = renamed(kernels(old_path), renames), kernels(new_path)
     bad = 0
     for n in sorted(old.keys() | new.keys()):
         if n not in new:
@@ -98,4 +115,12 @@ def main(old_path, new_path):
 
 
 if __name__ == "__main__":
-    sys.exit(main_multiset(*sys.argv[2:4]) if sys.argv[1] == "--multiset" else main(sys.argv[1], sys.argv[2]))
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--multiset", action="store_true", help="compare mnemonic multisets and resources instead of the instruction sequences")
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW", help="the old object's function OLD is the new object's NEW (repeatable)")
+    ap.add_argument("old"); ap.add_argument("new")
+    args = ap.parse_args()
+    if any("=" not in r for r in args.rename):
+        ap.error("--rename takes OLD=NEW")
+    names = dict(r.split("=", 1) for r in args.rename)
+    sys.exit((main_multiset if args.multiset else main)(args.old, args.new, names))

@@ -13,18 +13,12 @@ import ramp_ref as rr
 import realtimedepthdiffusion_amd as rt
 import roi_util
 import strokes_ref as sr
-import test_gpu_strokes as tgs
 from cascade_ref import Cascade
 from gpu_util import up
+from paint_gpu import ctx  # noqa: F401
+from paint_gpu import ITERS, _assert_pyramid, _Dev, _images, _pair, raw_target, sub_views
 
 pytestmark = pytest.mark.gpu
-_Dev, _images = tgs._Dev, tgs._images
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    with rt.Context(0) as c:
-        yield c
 
 
 def _start(rows, cols, seed):
@@ -141,9 +135,7 @@ def test_sub_image_views(ctx, layout):
     for k, (V, fill) in enumerate((([(5, 3), (70, 8), (80, 30), (30, 40), (-4, 20)], (pr.FILL_NONZERO, 0, 0, 74, 36, 20, 230)),
                                    (pr.scaled(pr.PENTAGRAM, 2, 1, -6, -5), pr.erase(pr.FILL_EVEN_ODD)))):
         orig, ed, scr = _start(rows, cols, 90 + lead)
-        o = roi_util.Roi(orig, lead, roi_util.pitch_for(cols * 3, lead, residue), roi_util.FILL_INPUT, what="original")
-        e = roi_util.Roi(ed, (lead + 1) % 5, roi_util.pitch_for(cols * 3, (lead + 1) % 5, residue), roi_util.FILL_OUTPUT, seed=1, what="edited")
-        s = roi_util.Roi(scr, lead, roi_util.pitch_for(cols, lead, (residue + 1) % 5), roi_util.FILL_OUTPUT, seed=2, what="scribble")
+        o, e, s = sub_views(orig, ed, scr, layout)
         ctx.fill_polygon(V, fill, e.img, s.img, rows, cols, original=o.img)
         ctx.synchronize()
         covered = pr.fill_polygon(V, fill, ed, scr, orig)
@@ -193,9 +185,8 @@ def test_every_refusal_is_invalid_and_leaves_the_images_alone(ctx):
     def call(pts=tri, n=None, fill=F(), edited=e.img, scribble=s.img, original=o.img, r=rows, c=cols, null_xy=False):
         flat = [v for p in pts for v in p]
         xy = (C.c_int * max(len(flat), 2))(*flat)
-        ed_, sc_, or_ = (edited or (None, 0)), (scribble or (None, 0)), (original or (None, 0))
         return L.rtdd_fill_polygon(ctx._h, None if null_xy else xy, C.c_int(len(pts) if n is None else n), C.byref(fill) if fill is not None else None,
-                                   C.c_void_p(ed_[0]), C.c_size_t(ed_[1]), C.c_void_p(sc_[0]), C.c_size_t(sc_[1]), C.c_void_p(or_[0]), C.c_size_t(or_[1]), C.c_int(r), C.c_int(c))
+                                   *raw_target(edited, scribble, original, r, c))
 
     gone = F(label0=-1, label1=-1)
     refused = {
@@ -246,7 +237,6 @@ def test_every_refusal_is_invalid_and_leaves_the_images_alone(ctx):
 
 
 # ---- on a pyramid --------------------------------------------------------------------------------------------------------------------------
-ITERS = tgs.ITERS
 _refs = {}
 
 
@@ -263,7 +253,7 @@ def _lassos(ann):
 def _reference(oracle, lut, erasing):
     """The reduced pair: estimate, the lassos (the erasing one only when asked for: then the rebuild), estimate."""
     if erasing not in _refs:
-        bgr, ann = tgs._pair()
+        bgr, ann = _pair()
         ref = Cascade(oracle, bgr, ann, lut, 1, threads=oracle.max_threads())
         assert ref.P >= 3
         ref.estimate(ITERS)
@@ -282,7 +272,7 @@ def _reference(oracle, lut, erasing):
 
 @pytest.mark.parametrize("erasing", [False, True], ids=["painting", "erasing"])
 def test_fills_on_the_pyramid_then_an_estimate(oracle, lut, erasing):
-    bgr, ann = tgs._pair()
+    bgr, ann = _pair()
     rows, cols = ann.shape
     ref = _reference(oracle, lut, erasing)
     floor, sky, gone = _lassos(ann)
@@ -295,14 +285,14 @@ def test_fills_on_the_pyramid_then_an_estimate(oracle, lut, erasing):
         for V, fill in (floor, sky) + ((gone,) if erasing else ()):
             c.fill_polygon(V, fill, (ep[0], ep[1]), (sp[0], sp[1]), rows, cols, original=(op[0], op[1]))
         c.estimate_depth(ITERS); c.synchronize()
-        tgs._assert_pyramid(c, ref, "erasing" if erasing else "painting")
+        _assert_pyramid(c, ref, "erasing" if erasing else "painting")
     if erasing:                                                       # not vacuous: without the rebuild the coarse levels keep the erased labels
         kept = _reference(oracle, lut, False)
         assert any((ref.scribble[l] != kept.scribble[l]).any() for l in range(1, ref.P))
 
 
 def test_a_retired_live_pointer_is_refused():
-    bgr, ann = tgs._pair()
+    bgr, ann = _pair()
     rows, cols = ann.shape
     with rt.Context(0) as c:
         c.GPULoadWeights(0.4)

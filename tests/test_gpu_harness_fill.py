@@ -8,8 +8,9 @@ import pytest
 
 import polygon_ref as pr
 import strokes_ref as sr
-import test_gpu_harness_strokes as ths
 from golden_util import NAMES, load
+from paint_gpu import _cascade
+from paint_gpu import _flag as _stroke_flag
 from test_gpu_harness import BIN, ROOT, _read_pnm, _write_pnm
 
 pytestmark = pytest.mark.gpu
@@ -36,9 +37,9 @@ def test_harness_fills_after_the_strokes(tmp_path):
              ([(-5, 170), (128, 190), (260, 170), (260, 215), (128, 200), (-5, 215)], pr.erase()),
              (pr.scaled(pr.PENTAGRAM, 4, 3, 40, -10), pr.constant(17, pr.FILL_EVEN_ODD))]
     args = [BIN, "-i", str(tmp_path / "img.ppm"), "-a", str(tmp_path / "ann.pgm"), "-o", str(tmp_path) + "/", "--iters", "200"]
-    args += _flag(*fills[0]) + ths._flag(stroke) + _flag(*fills[1]) + ["--fill-rule", "evenodd"] + _flag(*fills[2])     # (the stroke goes first wherever it stands)
+    args += _flag(*fills[0]) + _stroke_flag(stroke) + _flag(*fills[1]) + ["--fill-rule", "evenodd"] + _flag(*fills[2])     # (the stroke goes first wherever it stands)
     subprocess.check_output(args, text=True)
-    oracle, c = ths._cascade(g)
+    oracle, c = _cascade(g)
     before = c.scribble[0].copy()
     sr.paint_strokes([stroke], c.edited[0], c.scribble[0], g["bgr"])
     for V, fill in fills:

@@ -8,24 +8,10 @@ import pytest
 
 import strokes_ref as sr
 from golden_util import NAMES, load
+from paint_gpu import _cascade, _flag
 from test_gpu_harness import BIN, ROOT, _read_pnm, _write_pnm
 
 pytestmark = pytest.mark.gpu
-
-
-def _flag(q, frame=None):
-    x0, y0, x1, y1, radius, brush, label = q
-    head = "" if frame is None else f"{frame}:"
-    tail = ",round" if brush == sr.BRUSH_ROUND else ""
-    if label == sr.STROKE_ERASE:
-        return ["--erase" + ("" if frame is None else "-at"), f"{head}{x0},{y0},{x1},{y1},{radius}{tail}"]
-    return ["--stroke" + ("" if frame is None else "-at"), f"{head}{x0},{y0},{x1},{y1},{label},{radius}{tail}"]
-
-
-def _cascade(g):
-    import oracle
-    from cascade_ref import Cascade
-    return oracle, Cascade(oracle, g["bgr"], g["annotation"], oracle.load_weights(0.4), 1, threads=4)
 
 
 @pytest.mark.parametrize("batch", [1, 3])

@@ -1,7 +1,7 @@
 """rtdd_paint_ramp_strokes on the GPU, through the C ABI, the harness' --ramp / --ramp-at included (-m gpu): every comparison is byte
 equality of both images against tests/ramp_ref.py (or, for whole estimates, of every level against the restated cascade fed with the
 restated annotation).  The shapes are small: the label rule has no size-dependent path, and the tiles, the cull and the walk are
-tests/test_gpu_strokes.py's (its helpers are used as they are)."""
+tests/test_gpu_strokes.py's (tests/paint_gpu.py has the helpers of both)."""
 import ctypes as C
 import os
 import subprocess
@@ -13,28 +13,23 @@ import ramp_ref as rr
 import realtimedepthdiffusion_amd as rt
 import roi_util
 import strokes_ref as sr
-import test_gpu_harness_strokes as ths
-import test_gpu_strokes as tgs
 from cascade_ref import Cascade
 from golden_util import NAMES, load
 from gpu_util import up
+from paint_gpu import ctx  # noqa: F401
+from paint_gpu import ITERS, _assert_pyramid, _cascade, _Dev, _images, _pair, _polyline, raw_target, sub_views
+from paint_gpu import _flag as _stroke_flag
+from test_gpu_harness import BIN, ROOT, _read_pnm, _write_pnm
 
 pytestmark = pytest.mark.gpu
 HALF_TIES, extreme_strokes = rr.HALF_TIES, rr.extreme_strokes
-_Dev, _images = tgs._Dev, tgs._images
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    with rt.Context(0) as c:
-        yield c
 
 
 def _ramps(rng, rows, cols, n):
     """test_gpu_strokes' random walk (both brushes, erasers, stamps, strokes partly and wholly outside, a few across the whole domain) with
     a second label: a third of the painting strokes rise, a third fall, a third are constant."""
     out = []
-    for i, q in enumerate(tgs._polyline(rng, rows, cols, n)):
+    for i, q in enumerate(_polyline(rng, rows, cols, n)):
         if q[6] == sr.STROKE_ERASE:
             out.append(q + (sr.STROKE_ERASE,))
         elif i % 3 == 0:
@@ -87,7 +82,7 @@ def test_extreme_geometry_and_half_ties(ctx):
 
 def test_equal_labels_are_the_existing_call_byte_for_byte(ctx):
     for rows, cols, n, seed in ((67, 45, 300, 70), (33, 130, 64, 71), (1, 300, 40, 72)):
-        plain = tgs._polyline(np.random.default_rng(seed), rows, cols, n)
+        plain = _polyline(np.random.default_rng(seed), rows, cols, n)
         assert any(q[6] == sr.STROKE_ERASE for q in plain)
         orig, ed, scr = _images(rows, cols, seed)
         o, e1, s1, e2, s2 = _Dev(orig), _Dev(ed), _Dev(scr), _Dev(ed), _Dev(scr)
@@ -119,9 +114,7 @@ def test_sub_image_views(ctx, layout):
     orig, ed, scr = _images(rows, cols, 90 + lead)
     scr[::3, ::5] = 255
     strokes = _ramps(np.random.default_rng(90 + lead + residue), rows, cols, 24)        # (fewer than 64: none of the walk's image-wide strokes)
-    o = roi_util.Roi(orig, lead, roi_util.pitch_for(cols * 3, lead, residue), roi_util.FILL_INPUT, what="original")
-    e = roi_util.Roi(ed, (lead + 1) % 5, roi_util.pitch_for(cols * 3, (lead + 1) % 5, residue), roi_util.FILL_OUTPUT, seed=1, what="edited")
-    s = roi_util.Roi(scr, lead, roi_util.pitch_for(cols, lead, (residue + 1) % 5), roi_util.FILL_OUTPUT, seed=2, what="scribble")
+    o, e, s = sub_views(orig, ed, scr, layout)
     ctx.paint_ramp_strokes(strokes, e.img, s.img, rows, cols, original=o.img)
     ctx.synchronize()
     rr.paint_ramp_strokes(strokes, ed, scr, orig)
@@ -141,9 +134,7 @@ def test_every_refusal_is_invalid_and_leaves_the_images_alone(ctx):
     def call(strokes=(good,), count=None, edited=e.img, scribble=s.img, original=o.img, r=rows, c=cols, null_strokes=False):
         arr = (rt.RampStroke * max(len(strokes), 1))(*strokes)
         n = len(strokes) if count is None else count
-        ed_, sc_, or_ = (edited or (None, 0)), (scribble or (None, 0)), (original or (None, 0))
-        return L.rtdd_paint_ramp_strokes(ctx._h, None if null_strokes else arr, C.c_int(n), C.c_void_p(ed_[0]), C.c_size_t(ed_[1]), C.c_void_p(sc_[0]),
-                                         C.c_size_t(sc_[1]), C.c_void_p(or_[0]), C.c_size_t(or_[1]), C.c_int(r), C.c_int(c))
+        return L.rtdd_paint_ramp_strokes(ctx._h, None if null_strokes else arr, C.c_int(n), *raw_target(edited, scribble, original, r, c))
 
     def S(**kw):
         f = dict(x0=5, y0=5, x1=9, y1=9, radius=7, brush=1, label0=3, label1=200); f.update(kw)
@@ -191,7 +182,6 @@ def test_every_refusal_is_invalid_and_leaves_the_images_alone(ctx):
 
 
 # ---- the ramp reaches the estimate -----------------------------------------------------------------------------------------------------
-ITERS = tgs.ITERS
 _refs = {}
 
 
@@ -205,7 +195,7 @@ def _annotation(ann):
 
 def _reference(oracle, lut, contract):
     if contract not in _refs:
-        bgr, ann = tgs._pair()
+        bgr, ann = _pair()
         ref = Cascade(oracle, bgr, ann, lut, contract, threads=oracle.max_threads())
         assert ref.P >= 3
         ref.estimate(ITERS)
@@ -221,7 +211,7 @@ def _reference(oracle, lut, contract):
 
 @pytest.mark.parametrize("contract", [1, 0])
 def test_a_ramp_call_then_an_estimate(oracle, lut, contract):
-    bgr, ann = tgs._pair()
+    bgr, ann = _pair()
     rows, cols = ann.shape
     ref = _reference(oracle, lut, contract)
     with rt.Context(0) as c:
@@ -233,13 +223,13 @@ def test_a_ramp_call_then_an_estimate(oracle, lut, contract):
         sp = c.pyramid_image(rt.IMG_SCRIBBLE, 0); ep = c.pyramid_image(rt.IMG_EDITED, 0); op = c.pyramid_image(rt.IMG_ORIGINAL, 0)
         c.paint_ramp_strokes(_annotation(ann), (ep[0], ep[1]), (sp[0], sp[1]), rows, cols, original=(op[0], op[1]))
         c.estimate_depth(ITERS); c.synchronize()
-        tgs._assert_pyramid(c, ref, f"contract {contract}")
+        _assert_pyramid(c, ref, f"contract {contract}")
 
 
 def test_live_frames_with_a_ramp_painted_on_the_host_pair(oracle, lut, ctx):
     """Four live frames, one in flight; in front of frame 2 the host paints a ramp on its own pair (here: with the library, on a device copy
     of it).  Every frame is the restated sequence's."""
-    bgr, ann = tgs._pair()
+    bgr, ann = _pair()
     rows, cols = ann.shape
     ramp = [(20, 20, cols - 30, rows - 25, 13, sr.BRUSH_ROUND, 250, 10), (cols - 10, 5, cols - 60, rows // 2, 8, sr.BRUSH_SQUARE, 0, 90)]
     ref = Cascade(oracle, bgr, ann, lut, 1, threads=oracle.max_threads())
@@ -281,7 +271,7 @@ def test_live_frames_with_a_ramp_painted_on_the_host_pair(oracle, lut, ctx):
 # ---- the harness -------------------------------------------------------------------------------------------------------------------------
 def _flag(q, frame=None):
     if q[6] == q[7]:
-        return ths._flag(q[:7], frame)
+        return _stroke_flag(q[:7], frame)
     x0, y0, x1, y1, radius, brush, l0, l1 = q
     return ["--ramp" + ("" if frame is None else "-at"), ("" if frame is None else f"{frame}:") + f"{x0},{y0},{x1},{y1},{l0},{l1},{radius}" + (",round" if brush == sr.BRUSH_ROUND else "")]
 
@@ -289,14 +279,14 @@ def _flag(q, frame=None):
 def test_harness_ramp_is_the_python_api(tmp_path):
     """--stroke, --ramp, --erase, --ramp in command-line order, one rtdd_paint_ramp_strokes call: the annotated image and the map are what the
     same records through the Python API give (and the annotated image the restatement's)."""
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ths.ROOT, "harness")])
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "harness")])
     g = load(NAMES[0])
-    ths._write_pnm(tmp_path / "img.ppm", g["bgr"][..., ::-1])
-    ths._write_pnm(tmp_path / "ann.pgm", g["annotation"])
+    _write_pnm(tmp_path / "img.ppm", g["bgr"][..., ::-1])
+    _write_pnm(tmp_path / "ann.pgm", g["annotation"])
     rows, cols = g["annotation"].shape
     strokes = [(10, 200, 240, 180, 11, sr.BRUSH_ROUND, 254, 254), (30, 20, 220, 240, 17, sr.BRUSH_ROUND, 10, 250), (-20, 128, 300, 120, 40, sr.BRUSH_SQUARE, -1, -1),
                (250, 100, 5, 140, 9, sr.BRUSH_SQUARE, 255, 0)]
-    args = [ths.BIN, "-i", str(tmp_path / "img.ppm"), "-a", str(tmp_path / "ann.pgm"), "-o", str(tmp_path) + "/", "--iters", "200"]
+    args = [BIN, "-i", str(tmp_path / "img.ppm"), "-a", str(tmp_path / "ann.pgm"), "-o", str(tmp_path) + "/", "--iters", "200"]
     for q in strokes:
         args += _flag(q)
     assert args.count("--ramp") == 2
@@ -312,27 +302,27 @@ def test_harness_ramp_is_the_python_api(tmp_path):
         edited, depth = c.pyramid_download(rt.IMG_EDITED, 0), c.pyramid_download(rt.IMG_DEPTH_U8)
     rr.paint_ramp_strokes(strokes, before_e, before_s, g["bgr"])
     assert np.array_equal(edited, before_e) and len(np.unique(before_e[before_s == 255])) > 100
-    assert np.array_equal(ths._read_pnm(tmp_path / "AnnotatedImage.ppm"), edited[..., ::-1])
-    assert np.array_equal(ths._read_pnm(tmp_path / "DepthMap.pgm"), depth)
+    assert np.array_equal(_read_pnm(tmp_path / "AnnotatedImage.ppm"), edited[..., ::-1])
+    assert np.array_equal(_read_pnm(tmp_path / "DepthMap.pgm"), depth)
 
 
 def test_harness_ramp_in_a_live_view(tmp_path):
     """--live 4 --ramp-at 2:...: the harness paints its own host pair by the restated label rule; it runs, reports frames/s, and every frame
     is the restated cascade's."""
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ths.ROOT, "harness")])
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "harness")])
     g = load(NAMES[1])
-    ths._write_pnm(tmp_path / "img.ppm", g["bgr"][..., ::-1])
-    ths._write_pnm(tmp_path / "ann.pgm", g["annotation"])
+    _write_pnm(tmp_path / "img.ppm", g["bgr"][..., ::-1])
+    _write_pnm(tmp_path / "ann.pgm", g["annotation"])
     at = {2: [(30, 40, 200, 220, 9, sr.BRUSH_ROUND, 240, 15), (250, 10, 180, 100, 6, sr.BRUSH_SQUARE, 3, 180)]}
-    args = [ths.BIN, "-i", str(tmp_path / "img.ppm"), "-a", str(tmp_path / "ann.pgm"), "-o", str(tmp_path) + "/", "--live", "4", "--iters", "200", "--write-all"]
+    args = [BIN, "-i", str(tmp_path / "img.ppm"), "-a", str(tmp_path / "ann.pgm"), "-o", str(tmp_path) + "/", "--live", "4", "--iters", "200", "--write-all"]
     for f, qs in at.items():
         for q in qs:
             args += _flag(q, f)
     out = subprocess.check_output(args, text=True)
     assert "Live:" in out and "frames/s" in out, out
-    _, c = ths._cascade(g)
+    _, c = _cascade(g)
     for n in range(4):
         rr.paint_ramp_strokes(at.get(n, ()), c.edited[0], c.scribble[0], g["bgr"])
         c.estimate(200)
-        assert np.array_equal(ths._read_pnm(tmp_path / f"DepthMap_{n}.pgm"), c.depth_u8), f"frame {n}"
-    assert np.array_equal(ths._read_pnm(tmp_path / "AnnotatedImage.ppm"), c.edited[0][..., ::-1])
+        assert np.array_equal(_read_pnm(tmp_path / f"DepthMap_{n}.pgm"), c.depth_u8), f"frame {n}"
+    assert np.array_equal(_read_pnm(tmp_path / "AnnotatedImage.ppm"), c.edited[0][..., ::-1])

@@ -8,74 +8,16 @@ import pytest
 import realtimedepthdiffusion_amd as rt
 import strokes_ref as sr
 from cascade_ref import Cascade
-from dataset_util import load_pair
 from gpu_util import assert_bit_equal, up
+from paint_gpu import ctx  # noqa: F401
+from paint_gpu import ITERS, _assert_pyramid, _Dev, _images, _pair, _polyline, raw_target
 
 pytestmark = pytest.mark.gpu
-PAD = 0xA5
-
-
-class _Dev:
-    """A pitched device image with padded rows (every padding byte PAD)."""
-
-    def __init__(self, host):
-        import torch
-        host = np.ascontiguousarray(host)
-        self.rows = host.shape[0]
-        self.width = int(np.prod(host.shape[1:]))
-        self.pitch = (self.width + 255) // 256 * 256 + 256
-        self.base = torch.full((self.rows, self.pitch), PAD, dtype=torch.uint8, device="cuda:0")
-        self.base[:, :self.width] = torch.from_numpy(host.reshape(self.rows, self.width)).to("cuda:0")
-        self.shape = host.shape
-
-    @property
-    def img(self):
-        return (self.base.data_ptr(), self.pitch)
-
-    def host(self):
-        a = self.base.cpu().numpy()
-        assert (a[:, self.width:] == PAD).all(), "row padding was written"
-        return np.ascontiguousarray(a[:, :self.width]).reshape(self.shape)
-
-
-def _images(rows, cols, seed):
-    rng = np.random.default_rng(seed)
-    orig = rng.integers(0, 256, (rows, cols, 3), dtype=np.uint8)
-    return orig, orig.copy(), np.zeros((rows, cols), np.uint8)
-
-
-def _polyline(rng, rows, cols, n, long_ones=True):
-    """n segments of a random walk that starts inside and may leave the image: brushes, radii, labels and erasures mixed; it crosses itself,
-    so the order of the strokes matters.  A few strokes reach far outside."""
-    out = []
-    x, y = int(rng.integers(0, cols)), int(rng.integers(0, rows))
-    step = max(4, min(60, max(rows, cols) // 8))
-    for i in range(n):
-        nx = int(np.clip(x + rng.integers(-step, step + 1), -40, cols + 40))
-        ny = int(np.clip(y + rng.integers(-step, step + 1), -40, rows + 40))
-        if i % 7 == 3:
-            nx, ny = x, y                                            # a stamp in the middle of the drag
-        label = sr.STROKE_ERASE if rng.random() < 0.25 else int(rng.integers(0, 256))
-        out.append((x, y, nx, ny, int(rng.integers(0, 32)), int(rng.integers(0, 2)), label))
-        x, y = nx, ny
-    if long_ones and n >= 64:
-        out[n // 3] = (-32768, rows // 3, 32767, rows // 3 + 150, 9, sr.BRUSH_ROUND, 17)        # from far outside to far outside
-        out[n // 2] = (cols // 2, -32768, cols // 2 - 90, 32767, 1024 if rows * cols < 3000000 else 40, sr.BRUSH_SQUARE, sr.STROKE_ERASE)
-        if rows * cols <= 2100000:
-            out[2 * n // 3] = (-32768, -32768, 32767, 32767, 300, sr.BRUSH_ROUND, 201)          # the diagonal of the domain
-        out[n - 5] = (-500, -700, -300, -650, 64, sr.BRUSH_ROUND, 3)                            # wholly outside
-    return out
 
 
 def _run(c, strokes, e, s, o, rows, cols):
     c.paint_strokes(strokes, e.img, s.img, rows, cols, original=o.img if o is not None else None)
     c.synchronize()
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    with rt.Context(0) as c:
-        yield c
 
 
 @pytest.mark.parametrize("rows,cols,n,seed", [(1, 1, 1, 1), (1, 1, 64, 2), (1, 300, 2, 3), (1, 300, 300, 4), (67, 45, 1, 5), (67, 45, 64, 6), (67, 45, 4096, 7),
@@ -138,9 +80,7 @@ def test_every_refusal_is_invalid_and_leaves_the_images_alone(ctx):
     def call(strokes=(good,), count=None, edited=e.img, scribble=s.img, original=o.img, r=rows, c=cols, null_strokes=False):
         arr = (rt.Stroke * max(len(strokes), 1))(*strokes)
         n = len(strokes) if count is None else count
-        ed_, sc_, or_ = (edited or (None, 0)), (scribble or (None, 0)), (original or (None, 0))
-        return L.rtdd_paint_strokes(ctx._h, None if null_strokes else arr, C.c_int(n), C.c_void_p(ed_[0]), C.c_size_t(ed_[1]), C.c_void_p(sc_[0]), C.c_size_t(sc_[1]),
-                                    C.c_void_p(or_[0]), C.c_size_t(or_[1]), C.c_int(r), C.c_int(c))
+        return L.rtdd_paint_strokes(ctx._h, None if null_strokes else arr, C.c_int(n), *raw_target(edited, scribble, original, r, c))
 
     def S(**kw):
         f = dict(x0=5, y0=5, x1=9, y1=9, radius=7, brush=1, label=3); f.update(kw)
@@ -194,13 +134,7 @@ def test_stamps_in_one_call_are_the_calls_of_paint_image(ctx):
 
 
 # ---- the eraser reaches the estimate ---------------------------------------------------------------------------------------------------
-ITERS = 300
 _refs = {}
-
-
-def _pair():
-    bgr, ann, _ = load_pair("Dog")
-    return np.ascontiguousarray(bgr[::2, ::2]), np.ascontiguousarray(ann[::2, ::2])      # 336 x 312: three pyramid levels
 
 
 def _band(ann):
@@ -228,15 +162,6 @@ def _reference(oracle, lut, contract):
         erased.estimate(ITERS); kept.estimate(ITERS)
         _refs[contract] = (erased, kept, first)
     return _refs[contract]
-
-
-def _assert_pyramid(c, ref, what):
-    for l in range(ref.P):
-        assert np.array_equal(c.pyramid_download(rt.IMG_SCRIBBLE, l), ref.scribble[l]), f"{what}: scribble {l}"
-        assert np.array_equal(c.pyramid_download(rt.IMG_EDITED, l), ref.edited[l]), f"{what}: edited {l}"
-    for l in range(ref.P - 1, -1, -1):
-        assert_bit_equal(c.pyramid_download(rt.IMG_DEPTH, l), ref.depth[l], f"{what}: depth {l}")
-    assert np.array_equal(c.pyramid_download(rt.IMG_DEPTH_U8), ref.depth_u8), f"{what}: u8 map"
 
 
 def _erase_on_the_pyramid(c, ann, rows, cols):
