@@ -199,6 +199,11 @@ struct Job {
     struct Lasso { std::vector<int> xy; rtdd_fill fill; };
     std::vector<Lasso> fills;
     int fill_rule = RTDD_FILL_NONZERO;      // --fill-rule nonzero|evenodd: the rule of the --fill / --fill-erase flags behind it
+    // --wand / --wand-erase, in command-line order among themselves: one rtdd_fill_similar call each, after the polygons; --wand-at /
+    // --wand-erase-at (frame >= 0): in front of that live frame
+    struct Wand { rtdd_wand w; int frame; };
+    std::vector<Wand> wands, live_wands;
+    int wand_flags = 0;                     // --wand-connect 4|8: the connectivity of the --wand flags behind it
     std::string effect;
     int iters = 1000;
     std::string refine;           // "" | "sor" | "mg": rtdd_refine_depth after every estimate
@@ -278,10 +283,40 @@ static bool parse_fill(const char *arg, bool erase, int rule, Job::Lasso *l) {
     return true;
 }
 
-// --stroke / --erase / --ramp: the job's strokes on a device image pair, one call; the --fill / --fill-erase polygons behind them
+// --wand / --wand-erase: the job's clicks on a device image pair, one call each (each synchronises); prints what each covered
+static int wand_calls(rtdd_ctx *ctx, const Job &job, void *ed, size_t ed_pitch, void *scr, size_t scr_pitch, const void *orig, size_t orig_pitch, int rows, int cols) {
+    for (const Job::Wand &q : job.wands) {
+        rtdd_wand_info info;
+        CK(rtdd_fill_similar(ctx, &q.w, (uint8_t *)ed, ed_pitch, (uint8_t *)scr, scr_pitch, (const uint8_t *)orig, orig_pitch, rows, cols, &info));
+        std::printf("wand %d,%d tolerance %d: %d pixels, x %d..%d, y %d..%d\n", q.w.x, q.w.y, q.w.tolerance, info.pixels, info.x0, info.x1, info.y0, info.y1);
+    }
+    return RTDD_OK;
+}
+
+// "x,y,tol" and, when the wand paints, ":label" or ":label0,label1,ax0,ay0,ax1,ay1"; with "F:" in front when `frame` is asked for
+static bool parse_wand(const char *arg, bool erase, int flags, rtdd_wand *w, int *frame) {
+    int n = 0;
+    if (frame) { if (std::sscanf(arg, "%d:%n", frame, &n) != 1 || n == 0) return false; arg += n; n = 0; }
+    *w = rtdd_wand{0, 0, 0, flags, 0, 0, 0, 0, RTDD_STROKE_ERASE, RTDD_STROKE_ERASE};
+    if (std::sscanf(arg, "%d,%d,%d%n", &w->x, &w->y, &w->tolerance, &n) != 3 || n == 0) return false;
+    arg += n;
+    if (erase) return *arg == 0;
+    if (*arg != ':') return false;
+    n = 0;
+    if (std::sscanf(arg + 1, "%d,%d,%d,%d,%d,%d%n", &w->label0, &w->label1, &w->ax0, &w->ay0, &w->ax1, &w->ay1, &n) == 6 && arg[1 + n] == 0) return true;
+    w->ax0 = w->ay0 = w->ax1 = w->ay1 = 0;
+    n = 0;
+    if (std::sscanf(arg + 1, "%d%n", &w->label0, &n) != 1 || arg[1 + n] != 0) return false;
+    w->label1 = w->label0;
+    return true;
+}
+
+// --stroke / --erase / --ramp: the job's strokes on a device image pair, one call; the --fill / --fill-erase polygons behind them, the
+// --wand / --wand-erase clicks behind those
 static int paint_strokes(rtdd_ctx *ctx, const Job &job, void *ed, size_t ed_pitch, void *scr, size_t scr_pitch, const void *orig, size_t orig_pitch, int rows, int cols) {
     CK(stroke_calls(ctx, job, ed, ed_pitch, scr, scr_pitch, orig, orig_pitch, rows, cols));
-    return fill_polygons(ctx, job, ed, ed_pitch, scr, scr_pitch, orig, orig_pitch, rows, cols);
+    CK(fill_polygons(ctx, job, ed, ed_pitch, scr, scr_pitch, orig, orig_pitch, rows, cols));
+    return wand_calls(ctx, job, ed, ed_pitch, scr, scr_pitch, orig, orig_pitch, rows, cols);
 }
 
 // rtdd_paint_ramp_strokes (with label0 == label1: rtdd_paint_strokes) restated for the host's own image pair (--live: the host owns the pair every frame uploads; include/rtdd.h has the
@@ -313,6 +348,49 @@ static bool host_strokes(const std::vector<rtdd_ramp_stroke> &strokes, unsigned 
             }
     }
     return erased;
+}
+
+// rtdd_fill_similar restated for the host's own image pair (--live, like host_strokes; include/rtdd.h has the rule): the component by a
+// queue.  Dense images; `orig` is the BGR image; the wand is valid (checked by its caller).  Returns the number of covered pixels.
+static int host_wand(const rtdd_wand &w, unsigned char *scr, unsigned char *ed, const unsigned char *orig, int rows, int cols) {
+    typedef long long i64;
+    const size_t npx = (size_t)rows * cols, seed = (size_t)w.y * cols + w.x;
+    auto similar = [&](size_t i) {
+        for (int c = 0; c < 3; c++) if (std::abs((int)orig[3 * i + c] - (int)orig[3 * seed + c]) > w.tolerance) return false;
+        return true;
+    };
+    std::vector<unsigned char> in(npx, 0);
+    if (w.flags & RTDD_WAND_GLOBAL) { for (size_t i = 0; i < npx; i++) in[i] = similar(i); }
+    else {
+        std::vector<size_t> todo(1, seed);
+        in[seed] = 1;
+        while (!todo.empty()) {
+            const size_t i = todo.back(); todo.pop_back();
+            const int x = (int)(i % cols), y = (int)(i / cols);
+            for (int dy = -1; dy <= 1; dy++)
+                for (int dx = -1; dx <= 1; dx++) {
+                    if ((dx == 0 && dy == 0) || (dx != 0 && dy != 0 && !(w.flags & RTDD_WAND_CONNECT_8))) continue;
+                    const int qx = x + dx, qy = y + dy;
+                    if (qx < 0 || qx >= cols || qy < 0 || qy >= rows) continue;
+                    const size_t j = (size_t)qy * cols + qx;
+                    if (!in[j] && similar(j)) { in[j] = 1; todo.push_back(j); }
+                }
+        }
+    }
+    const i64 dx = w.ax1 - w.ax0, dy = w.ay1 - w.ay0, dd = dx * dx + dy * dy;
+    int covered = 0;
+    for (size_t i = 0; i < npx; i++) {
+        if (!in[i]) continue;
+        covered++;
+        if (w.label0 == RTDD_STROKE_ERASE) { scr[i] = 0; for (int c = 0; c < 3; c++) ed[3 * i + c] = orig[3 * i + c]; continue; }
+        i64 label = w.label0;
+        if (dd != 0 && w.label0 != w.label1) {
+            const i64 t = std::min(std::max(((i64)(i % cols) - w.ax0) * dx + ((i64)(i / cols) - w.ay0) * dy, (i64)0), dd);
+            label = (2 * (w.label0 * (dd - t) + w.label1 * t) + dd) / (2 * dd);
+        }
+        scr[i] = 255; for (int c = 0; c < 3; c++) ed[3 * i + c] = (unsigned char)label;
+    }
+    return covered;
 }
 
 // "x0,y0,x1,y1,label,radius[,round]" (kind 'e', erase: no label; kind 'r', ramp: label0,label1), with "F:" in front when `frame` is asked for
@@ -493,6 +571,14 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
                 while (rtdd_live_pending(ctx) > 0) { const int f = n - rtdd_live_pending(ctx); CK(rtdd_live_wait(ctx)); landed(f); }
                 if (host_strokes(now, (unsigned char *)h_scr.p, (unsigned char *)h_ed.p, job.bgr.px.data(), rows, cols)) CK(rtdd_pyramid_annotation_rebuild(ctx));
             }
+            // --wand-at / --wand-erase-at: likewise on the HOST images, behind the frame's strokes
+            for (const Job::Wand &q : job.live_wands) {
+                if (q.frame != n) continue;
+                if (q.w.x < 0 || q.w.x >= cols || q.w.y < 0 || q.w.y >= rows || q.w.tolerance < 0 || q.w.tolerance > 255) { std::printf("--wand-at %d: the seed lies outside the image or the tolerance outside [0, 255]\n", n); return RTDD_ERR_INVALID; }
+                while (rtdd_live_pending(ctx) > 0) { const int f = n - rtdd_live_pending(ctx); CK(rtdd_live_wait(ctx)); landed(f); }
+                std::printf("frame %d: wand %d,%d tolerance %d: %d pixels\n", n, q.w.x, q.w.y, q.w.tolerance, host_wand(q.w, (unsigned char *)h_scr.p, (unsigned char *)h_ed.p, job.bgr.px.data(), rows, cols));
+                if (q.w.label0 == RTDD_STROKE_ERASE) CK(rtdd_pyramid_annotation_rebuild(ctx));
+            }
             if (rtdd_live_pending(ctx) >= 2) { const int f = n - 2; CK(rtdd_live_wait(ctx)); landed(f); }              // frame n-2's buffer is about to be reused
             CK(rtdd_live_submit_ex(ctx, (const uint8_t *)h_scr.p, cols, (const uint8_t *)h_ed.p, (size_t)cols * 3, job.iters, (uint8_t *)h_u8[n % 2].p, cols,
                                    fx, (uint8_t *)h_art[n % 2].p, (size_t)cols * 3));
@@ -598,6 +684,7 @@ int main(int argc, const char *argv[]) {
                                  "                    [--stroke x0,y0,x1,y1,label,radius[,round]]... [--erase x0,y0,x1,y1,radius[,round]]...   (segments, in command-line order, one rtdd_paint_strokes call after --paint)\n"
                                  "                    [--ramp x0,y0,x1,y1,label0,label1,radius[,round]]...   (a depth ramp: label0 at x0,y0 to label1 at x1,y1; in order with --stroke / --erase, all of them one rtdd_paint_ramp_strokes call)\n"
                                  "                    [--fill \"x,y;x,y;...:label\" | \"x,y;...:label0,label1,ax0,ay0,ax1,ay1\"]... [--fill-erase \"x,y;x,y;...\"]... [--fill-rule nonzero|evenodd]   (a lasso filled with a label, a ramp along the axis, or erased: one rtdd_fill_polygon call each, after the strokes, in command-line order)\n"
+                                 "                    [--wand \"x,y,tol:label\" | \"x,y,tol:label0,label1,ax0,ay0,ax1,ay1\"]... [--wand-erase \"x,y,tol\"]... [--wand-connect 4|8] [--wand-at frame:...]... [--wand-erase-at frame:...]...   (a click: everything joined to x,y within tol of its colour, one rtdd_fill_similar call each, after the polygons; -at: --live, in front of that frame)\n"
                                  "                    [--stroke-at frame:x0,y0,x1,y1,label,radius[,round]]... [--erase-at frame:x0,y0,x1,y1,radius[,round]]... [--ramp-at frame:x0,y0,x1,y1,label0,label1,radius[,round]]...   (--live: in front of that frame)\n"
                                  "       rtdd_harness --convert in.(jpg|png|ppm|pgm) out.(png|ppm|pgm)   (JPEG / 8-bit PNG / PNM -> PNG / PNM, no GPU)\n"); return 0; }
     if (argc == 4 && !std::strcmp(argv[1], "--convert")) {               // file format conversion only (no GPU): JPEG / PNG / PNM -> PNG / PNM
@@ -647,6 +734,19 @@ int main(int argc, const char *argv[]) {
             const bool erase = argv[i][6] != 0; Job::Lasso l;
             if (!parse_fill(next(), erase, job.fill_rule, &l)) { std::printf("%s\n", erase ? "--fill-erase wants x,y;x,y;..." : "--fill wants x,y;x,y;...:label or x,y;x,y;...:label0,label1,ax0,ay0,ax1,ay1"); return 1; }
             job.fills.push_back(l);
+        }
+        else if (!std::strcmp(argv[i], "--wand-connect")) {
+            const char *v = next();
+            if (!std::strcmp(v, "4")) job.wand_flags = 0;
+            else if (!std::strcmp(v, "8")) job.wand_flags = RTDD_WAND_CONNECT_8;
+            else { std::printf("--wand-connect wants 4 or 8\n"); return 1; }
+        }
+        else if (!std::strcmp(argv[i], "--wand") || !std::strcmp(argv[i], "--wand-erase") || !std::strcmp(argv[i], "--wand-at") || !std::strcmp(argv[i], "--wand-erase-at")) {
+            const bool erase = !std::strncmp(argv[i], "--wand-erase", 12), at = ends_with(argv[i], "-at"); Job::Wand q; q.frame = -1;
+            if (!parse_wand(next(), erase, job.wand_flags, &q.w, at ? &q.frame : nullptr)) {
+                std::printf("%s wants %sx,y,tolerance%s\n", argv[i - 1], at ? "frame:" : "", erase ? "" : ":label or ...:label0,label1,ax0,ay0,ax1,ay1"); return 1;
+            }
+            (at ? job.live_wands : job.wands).push_back(q);
         }
         else if (!std::strcmp(argv[i], "--stroke") || !std::strcmp(argv[i], "--erase")) {
             const bool erase = argv[i][2] == 'e'; rtdd_ramp_stroke q;

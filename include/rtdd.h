@@ -421,6 +421,59 @@ int rtdd_fill_polygon(rtdd_ctx *ctx, const int *xy /* HOST: n vertices x, y, x, 
                       const uint8_t *original, size_t originalPitch, /* may be NULL unless erasing */
                       int rows, int cols);
 
+/* Fill what looks like the clicked pixel -- the magic wand (extension; no reference behaviour; found by symbol like rtdd_fill_polygon, no
+ * version bump; the next bump of RTDD_VERSION should cover rtdd_fill_similar too): one click inside a surface selects everything joined to
+ * the click whose colour is close to the clicked colour, and the selection gets rtdd_fill_polygon's label, ramp or erasure.  All of it
+ * exact integer arithmetic; the covered set is a connected component, so the bytes do not depend on how the device schedules the search.
+ * Seed colour: (sB, sG, sR) = original at (x, y), READ ON THE DEVICE when the call runs.
+ * Eligible: pixel p with colour (B, G, R) in `original` is eligible when max(|B - sB|, |G - sG|, |R - sR|) <= tolerance -- the Chebyshev
+ *   distance RTDD_GUIDE_BGR takes its index from; a gray image passed as B = G = R behaves as gray.  The seed is always eligible;
+ *   tolerance 255 makes every pixel eligible.
+ * Covered: with RTDD_WAND_GLOBAL every eligible pixel.  Otherwise the eligible pixels joined to the seed by a path of eligible pixels
+ *   whose steps go to one of the 4 neighbours (left, right, up, down) or, with RTDD_WAND_CONNECT_8, to one of the 8 neighbours.  The image
+ *   border ends a path: nothing wraps.  At least the seed is covered.
+ * What "similar" reads: `original` only.  The scribbles and labels already in the pair play no part in it.
+ * Label and writes: rtdd_fill_polygon's.  With d = a1 - a0, v = p - a0, dd = d.d along the axis (ax0, ay0) - (ax1, ay1),
+ *   dd == 0 or label0 == label1:  L = label0
+ *   otherwise:                    t = min(max(v.d, 0), dd);  N = 2 * (label0 * (dd - t) + label1 * t) + dd;  L = N / (2 * dd)
+ *   painting (labels 0..255) writes edited = (L, L, L), scribble = 255; erasing (both labels RTDD_STROKE_ERASE) writes edited = original
+ *   at that pixel, scribble = 0; uncovered pixels are not written.
+ * The limit of the tool: a boundary whose step in colour is within the tolerance is no boundary.  An object of gray 100 on gray 108, both
+ *   with noise of +-2, selected with tolerance 5 leaks into the background (102 against 106); with a step of 12 the selection is exactly
+ *   the object.  Choose the tolerance below the weakest edge of the region.
+ * Refused (RTDD_ERR_INVALID) before any launch, the images untouched: a null wand; a seed outside the image; a tolerance outside [0, 255];
+ *   flag bits other than the two below; an axis coordinate outside [-32768, 32767]; a label outside [-1, 255]; exactly ONE label being
+ *   RTDD_STROKE_ERASE; the null, pitch and size rules of rtdd_fill_polygon (rows or cols above 32768 among them); a null original or an
+ *   original pitch smaller than a row -- ALWAYS here, not only when erasing: it is what "similar" reads.  rows == 0 or cols == 0 is
+ *   RTDD_ERR_INVALID too, unlike the other paint calls: no seed lies inside an empty image.  A retired level-0 pointer of live mode:
+ *   RTDD_ERR_STATE.
+ * On the pyramid's own level-0 RTDD_IMG_SCRIBBLE / RTDD_IMG_EDITED pair the call notes the change itself, and asks for
+ * rtdd_pyramid_annotation_rebuild when it erases, exactly as rtdd_fill_polygon.
+ * THE CALL SYNCHRONISES, unlike the other paint calls: the search grows the selection in passes over the image, and how many it needs
+ * depends on the data, so the host reads a counter back between rounds of passes.  It returns with both images written and `info` filled.
+ * Work queued on the context's stream in front of it is waited for; logged solves and estimates are confirmed (or healed) first, as by
+ * rtdd_index_to_weight_guided.  The cost is a handful of nearly empty launches per 64 pixels of distance the selection travels, plus one
+ * synchronisation per round of 8 passes.  info->passes counts the passes up to the first that changed nothing: a diagnostic, NOT
+ * deterministic (a pass may or may not see what a neighbouring wave wrote in the same pass); everything else is. */
+enum rtdd_wand_flags { RTDD_WAND_CONNECT_8 = 1,   /* default: 4-connected */
+                       RTDD_WAND_GLOBAL    = 2 }; /* every similar pixel of the image, connected or not */
+typedef struct rtdd_wand {
+    int x, y;                   /* the clicked pixel; must lie inside the image */
+    int tolerance;              /* 0..255 */
+    int flags;                  /* enum rtdd_wand_flags, or-ed */
+    int ax0, ay0, ax1, ay1;     /* the ramp's axis, as rtdd_fill */
+    int label0, label1;         /* both 0..255, or both RTDD_STROKE_ERASE */
+} rtdd_wand;
+typedef struct rtdd_wand_info {
+    int pixels;                 /* covered pixels (>= 1) */
+    int x0, y0, x1, y1;         /* their inclusive bounding box */
+    int passes;                 /* grow passes that ran: a diagnostic, NOT deterministic (0 with RTDD_WAND_GLOBAL) */
+} rtdd_wand_info;
+int rtdd_fill_similar(rtdd_ctx *ctx, const rtdd_wand *wand,
+                      uint8_t *edited, size_t editedPitch, uint8_t *scribble, size_t scribblePitch,
+                      const uint8_t *original, size_t originalPitch,   /* always needed: it is what "similar" reads */
+                      int rows, int cols, rtdd_wand_info *info /* may be NULL */);
+
 /* ---- depth effects (include/GPUDepthEffect.h:4-9) ------------------------------------------ */
 
 /* GPUSimulateDefocus -- src/GPUDepthEffect.cu:29-72,105-113 (exact, via an integer summed-area table). */

@@ -52,7 +52,7 @@ C_ABI_SYMBOLS = [
     "rtdd_live_submit", "rtdd_live_wait", "rtdd_live_pending", "rtdd_host_alloc", "rtdd_host_free",
     "rtdd_pyramid_create_batch", "rtdd_pyramid_select", "rtdd_pyramid_batch", "rtdd_estimate_depth_batch", "rtdd_pyramid_level_info", "rtdd_live_submit_ex",
     "rtdd_simulate_refocus", "rtdd_simulate_haze_ex", "rtdd_simulate_stereo", "rtdd_simulate_lens_blur",
-    "rtdd_paint_strokes", "rtdd_pyramid_annotation_rebuild", "rtdd_paint_ramp_strokes", "rtdd_ramp_polyline", "rtdd_fill_polygon",
+    "rtdd_paint_strokes", "rtdd_pyramid_annotation_rebuild", "rtdd_paint_ramp_strokes", "rtdd_ramp_polyline", "rtdd_fill_polygon", "rtdd_fill_similar",
     "rtdd_simulate_relight", "rtdd_simulate_relight_shadowed", "rtdd_simulate_parallax", "rtdd_simulate_ambient_occlusion",
     "rtdd_simulate_lighting", "rtdd_simulate_bokeh",
     "rtdd_solve_guided", "rtdd_index_to_weight_guided", "rtdd_pyrdown_bgr", "rtdd_pyramid_set_guide", "rtdd_pyramid_guide",
@@ -67,6 +67,8 @@ AO_SHADE, AO_MAP = 0, 1                       # rtdd_ambient_occlusion.mode
 BRUSH_SQUARE, BRUSH_ROUND = 0, 1              # rtdd_stroke.brush
 STROKE_ERASE = -1                             # rtdd_stroke.label: remove the annotation
 FILL_NONZERO, FILL_EVEN_ODD = 0, 1            # rtdd_fill.rule
+WAND_CONNECT_8, WAND_GLOBAL = 1, 2            # rtdd_wand.flags
+WAND_ROUND = 8                                # grow passes rtdd_fill_similar queues between two synchronisations (csrc/fill_similar.hip: kWandRound)
 # Itanium-mangled names of the reference's ten free functions
 DROPIN_SYMBOLS = [
     "_Z23GPUAllocateDeviceMemoryiii", "_Z19GPUFreeDeviceMemoryi", "_Z14GPULoadWeightsf",
@@ -110,6 +112,18 @@ class Fill(C.Structure):
     """rtdd_fill: FILL_*, the ramp's axis (label0 at (ax0, ay0), label1 at (ax1, ay1); ignored when the labels are equal), the two labels
     (both STROKE_ERASE: the polygon erases)."""
     _fields_ = [("rule", C.c_int), ("ax0", C.c_int), ("ay0", C.c_int), ("ax1", C.c_int), ("ay1", C.c_int), ("label0", C.c_int), ("label1", C.c_int)]
+
+
+class Wand(C.Structure):
+    """rtdd_wand: the clicked pixel (x, y), the tolerance 0..255, WAND_* flags, and rtdd_fill's axis and two labels (both STROKE_ERASE: the
+    selection is erased)."""
+    _fields_ = [("x", C.c_int), ("y", C.c_int), ("tolerance", C.c_int), ("flags", C.c_int), ("ax0", C.c_int), ("ay0", C.c_int), ("ax1", C.c_int),
+                ("ay1", C.c_int), ("label0", C.c_int), ("label1", C.c_int)]
+
+
+class WandInfo(C.Structure):
+    """rtdd_wand_info: the covered pixels, their inclusive bounding box, and the grow passes that ran (a diagnostic: not deterministic)."""
+    _fields_ = [("pixels", C.c_int), ("x0", C.c_int), ("y0", C.c_int), ("x1", C.c_int), ("y1", C.c_int), ("passes", C.c_int)]
 
 
 def ramp_polyline(points, radius, brush, label0, label1):
@@ -416,6 +430,15 @@ class Context:
         xy = (C.c_int * max(2 * n, 1))(*[int(v) for p in points for v in p])
         f = fill if isinstance(fill, Fill) else Fill(*fill)
         self._check(lib().rtdd_fill_polygon(self._h, xy, C.c_int(n), C.byref(f), *_paint_images(edited, scribble, original), C.c_int(rows), C.c_int(cols)))
+
+    def fill_similar(self, wand, edited, scribble, rows, cols, original):
+        """rtdd_fill_similar: everything joined to the clicked pixel whose colour in `original` is within the tolerance of the clicked colour
+        is filled by `wand` (a Wand or a 10-tuple x, y, tolerance, flags, ax0, ay0, ax1, ay1, label0, label1).  SYNCHRONISES; returns the
+        WandInfo."""
+        w = wand if isinstance(wand, Wand) else Wand(*wand)
+        info = WandInfo()
+        self._check(lib().rtdd_fill_similar(self._h, C.byref(w), *_paint_images(edited, scribble, original), C.c_int(rows), C.c_int(cols), C.byref(info)))
+        return info
 
     # ---- include/GPUDepthEffect.h
     def GPUSimulateDefocus(self, originalImage, depthImage, artisticImage, rows, cols):

@@ -662,7 +662,7 @@ int rtdd_paint_image(rtdd_ctx *ctx, int x, int y, int scribbleColor, int scribbl
     return launch_paint(ctx, x, y, scribbleColor, scribbleRadius, PaintTarget{edited, editedPitch, scribble, scribblePitch, nullptr, 0, rows, cols});
 }
 
-// ---- rtdd_paint_strokes, rtdd_paint_ramp_strokes, rtdd_fill_polygon: what they share ----
+// ---- rtdd_paint_strokes, rtdd_paint_ramp_strokes, rtdd_fill_polygon, rtdd_fill_similar: what they share ----
 // A call checks its own records first (they say whether it erases), then its target; an empty image or no record is RTDD_OK before any
 // pitch is looked at; then, with the device set, begin_paint.
 static int check_paint_target(rtdd_ctx *ctx, const PaintTarget &t, bool erases) {
@@ -758,6 +758,31 @@ int rtdd_fill_polygon(rtdd_ctx *ctx, const int *xy, int n, const rtdd_fill *fill
     DeviceGuard g(ctx->device);
     RTDD_TRY(begin_paint(ctx, t, erases));
     return launch_fill_polygon(ctx, xy, n, *fill, t);
+}
+
+// The one paint call that synchronises (the number of grow passes depends on the data) and the one that always reads the original.
+int rtdd_fill_similar(rtdd_ctx *ctx, const rtdd_wand *wand, uint8_t *edited, size_t editedPitch, uint8_t *scribble, size_t scribblePitch,
+                      const uint8_t *original, size_t originalPitch, int rows, int cols, rtdd_wand_info *info) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    const PaintTarget t{edited, editedPitch, scribble, scribblePitch, original, originalPitch, rows, cols};
+    REQUIRE(ctx, wand, "null wand");
+    REQUIRE(ctx, wand->tolerance >= 0 && wand->tolerance <= 255, "tolerance outside [0, 255]");
+    REQUIRE(ctx, (wand->flags & ~(RTDD_WAND_CONNECT_8 | RTDD_WAND_GLOBAL)) == 0, "unknown wand flag");
+    for (int v : {wand->ax0, wand->ay0, wand->ax1, wand->ay1}) REQUIRE(ctx, v >= -32768 && v <= 32767, "axis coordinate outside [-32768, 32767]");
+    const char *why = nullptr;
+    REQUIRE(ctx, label_pair_ok(wand->label0, wand->label1, &why), why);
+    REQUIRE(ctx, original, "null original image: it is what \"similar\" reads");
+    RTDD_TRY(check_paint_target(ctx, t, false));
+    REQUIRE(ctx, wand->x >= 0 && wand->x < cols && wand->y >= 0 && wand->y < rows, "the seed lies outside the image (an empty image has no seed)");
+    REQUIRE(ctx, editedPitch >= (size_t)cols * 3 && scribblePitch >= (size_t)cols && originalPitch >= (size_t)cols * 3, "pitch smaller than a row");
+    const bool erases = wand->label0 == RTDD_STROKE_ERASE;
+    DeviceGuard g(ctx->device);
+    // the call synchronises the stream: confirm (or heal) the logged solves and estimates through their own path first, while the state
+    // they ran on still exists -- and before the pyramid hears of this write, which a replayed estimate would otherwise take for its own;
+    // the synchronisations behind that are plain.  Not logged itself, like every paint call.
+    RTDD_TRY(settle_pending(ctx));
+    RTDD_TRY(begin_paint(ctx, t, erases));
+    return launch_fill_similar(ctx, *wand, t, info);
 }
 
 // host arithmetic only (include/rtdd.h has the rule): doubles, every operation rounded on its own

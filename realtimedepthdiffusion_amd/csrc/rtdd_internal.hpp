@@ -389,6 +389,11 @@ template <class Stroke> int launch_paint_strokes(rtdd_ctx *ctx, const Stroke *st
 // rtdd_fill_polygon: the checked contour (1 <= n <= 768 vertices, as kernel arguments) in one launch over its clipped bounding box
 int launch_fill_polygon(rtdd_ctx *ctx, const int *xy, int n, const rtdd_fill &fill, const PaintTarget &t);
 
+// ---- fill_similar.hip ---------------------------------------------------------------------------
+// rtdd_fill_similar: the checked wand on three given images; grows the selection in rounds of passes and SYNCHRONISES the stream
+// (the table buffer ctx->sat holds its two bit planes); info may be null
+int launch_fill_similar(rtdd_ctx *ctx, const rtdd_wand &wand, const PaintTarget &t, rtdd_wand_info *info);
+
 // ---- effect_kernels.hip -------------------------------------------------------------------------
 int launch_effect(rtdd_ctx *ctx, const Effect &e);
 // ---- lens_blur.hip: Effect::kLensBlur (called by launch_effect) ------------------------------------
