@@ -73,6 +73,25 @@ __device__ __forceinline__ bool solve_is_dead(int *sync_words, int seq, bool fir
     return true;
 }
 
+// The flag a thread polls, as a byte offset from sync_words: lane i (of 9, i != 4) of wave 0 polls neighbour (i%3-1, i/3-1); -1 = this
+// thread polls nothing.  It depends on the thread and the tile only, so a kernel that exchanges many times works it out once
+// (sweep_blocked.hip keeps it in its exchange record) and hands it to exchange_wait_at().
+__device__ __forceinline__ int exchange_poll_offset(int tid, int bx, int by, int gx, int gy, int tile_base) {
+    const int pw = tid >> 6, pl = tid & 63;
+    if (pw != 0 || pl >= 9 || pl == 4) return -1;
+    const int nx = bx + pl % 3 - 1, ny = by + pl / 3 - 1;
+    if (nx < 0 || ny < 0 || nx >= gx || ny >= gy) return -1;
+    return (kSyncFlags + (tile_base + ny * gx + nx) * kSyncFlagStride) * (int)sizeof(int);      // (< 2^31: kSyncWords ints)
+}
+
+// A flag read as the relaxed agent-scope atomic load it is (global_load_dword sc1 and its wait), written out so that the address stays
+// scalar base + 32-bit lane offset inside the polling loop (left to the compiler the loop keeps a 64-bit sum per lane).
+__device__ __forceinline__ int load_flag_at(const int *base, unsigned off) {
+    int v;
+    asm volatile("global_load_dword %0, %1, %2 sc1\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(off), "s"(base) : "memory");
+    return v;
+}
+
 // Called by EVERY thread of the workgroup after its payload stores are drained (s_waitcnt vmcnt(0)) and a __syncthreads().
 // Publishes this tile's counter, waits for the up-to-8 neighbouring tiles' counters, makes their payload visible (one agent
 // acquire by wave 0) and ends with a __syncthreads().  Returns true when the launch is dead (see kSyncStatus): the caller
@@ -80,37 +99,33 @@ __device__ __forceinline__ bool solve_is_dead(int *sync_words, int seq, bool fir
 // Protocol (cdna_hip_programming.md Guideline 16, R1): write-through (sc1) payload stores; EVERY storing wave drains vmcnt;
 // workgroup barrier; ONE lane stores the flag (agent-scope atomic); 8 lanes poll the neighbours' flags relaxed with s_sleep;
 // ONE agent acquire; barrier; plain vector loads.
+// exchange_wait_at() is exchange_wait() with the polled flag's place worked out by the caller (exchange_poll_offset): the flag is addressed as the
+// scalar base sync_words plus that 32-bit offset, so an exchange forms no 64-bit address per lane.
 template <bool ACQUIRE = true, bool ARRIVAL = false>
-__device__ __forceinline__ bool exchange_wait(int *sync_words, int *dead_lds, int tid, int tile_id, int bx, int by, int gx, int gy, int value, int tile_base = 0) {
+__device__ __forceinline__ bool exchange_wait_at(int *sync_words, int *dead_lds, int tid, int tile_id, int poll_off, int value, int tile_base = 0) {
     int *flags = sync_words + kSyncFlags + tile_base * kSyncFlagStride;      // (tile_base: a batched launch gives every image's tiles flags of their own)
     if (tid == 0 && __hip_atomic_load(&sync_words[kSyncWithhold], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != tile_id + 1)
         __hip_atomic_store(&flags[tile_id * kSyncFlagStride], value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // Lane i (of 9, i != 4) of wave 0 polls neighbour (i%3-1, i/3-1).  A poll is a round trip to memory (the flag was stored sc1: it is in
-    // no L2).  (Several polling waves, each started a fraction of a trip after the one before and the first to see all its neighbours
-    // telling the others through LDS, measured no faster: EXPERIMENTS.md.)
-    const int pw = tid >> 6, pl = tid & 63;
-    if (pw == 0 && pl < 9 && pl != 4) {
-        const int nx = bx + pl % 3 - 1, ny = by + pl / 3 - 1;
-        if (nx >= 0 && ny >= 0 && nx < gx && ny < gy) {
-            const int nb = ny * gx + nx;
-            unsigned long long t0 = 0, limit = 0;
-            unsigned spins = 0;
-            while (__hip_atomic_load(&flags[nb * kSyncFlagStride], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - value < 0) {
-                __builtin_amdgcn_s_sleep(4);
-                if ((++spins & 63u) == 0) {                              // every 64 polls (tens of microseconds): clock and status word
-                    const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-                    if (t0 == 0) {
-                        t0 = now;
-                        const int l = __hip_atomic_load(&sync_words[kSyncLimit], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        limit = l > 0 ? (unsigned long long)l : kDefaultPollLimit;
-                        if (ARRIVAL && limit > kArrivalPollLimit) limit = kArrivalPollLimit;
-                    }
-                    const bool failed = __hip_atomic_load(&sync_words[kSyncStatus], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-                    if (failed || now - t0 > limit) {
-                        if (!failed) __hip_atomic_store(&sync_words[kSyncStatus], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        __hip_atomic_store(dead_lds, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        break;
-                    }
+    // A poll is a round trip to memory (the flag was stored sc1: it is in no L2).  (Several polling waves, each started a fraction of a
+    // trip after the one before and the first to see all its neighbours telling the others through LDS, measured no faster: EXPERIMENTS.md.)
+    if (poll_off >= 0) {
+        unsigned long long t0 = 0, limit = 0;
+        unsigned spins = 0;
+        while (load_flag_at(sync_words, (unsigned)poll_off) - value < 0) {
+            __builtin_amdgcn_s_sleep(4);
+            if ((++spins & 63u) == 0) {                              // every 64 polls (tens of microseconds): clock and status word
+                const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+                if (t0 == 0) {
+                    t0 = now;
+                    const int l = __hip_atomic_load(&sync_words[kSyncLimit], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    limit = l > 0 ? (unsigned long long)l : kDefaultPollLimit;
+                    if (ARRIVAL && limit > kArrivalPollLimit) limit = kArrivalPollLimit;
+                }
+                const bool failed = __hip_atomic_load(&sync_words[kSyncStatus], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+                if (failed || now - t0 > limit) {
+                    if (!failed) __hip_atomic_store(&sync_words[kSyncStatus], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(dead_lds, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    break;
                 }
             }
         }
@@ -121,6 +136,11 @@ __device__ __forceinline__ bool exchange_wait(int *sync_words, int *dead_lds, in
     if (!ACQUIRE && tid < 64) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the polls themselves have returned
     __syncthreads();
     return __hip_atomic_load(dead_lds, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0;
+}
+
+template <bool ACQUIRE = true, bool ARRIVAL = false>
+__device__ __forceinline__ bool exchange_wait(int *sync_words, int *dead_lds, int tid, int tile_id, int bx, int by, int gx, int gy, int value, int tile_base = 0) {
+    return exchange_wait_at<ACQUIRE, ARRIVAL>(sync_words, dead_lds, tid, tile_id, exchange_poll_offset(tid, bx, by, gx, gy, tile_base), value, tile_base);
 }
 
 #endif

@@ -74,6 +74,13 @@ __global__ __launch_bounds__(NT, (NT >= 1024 || G <= 3 ? 4 : G <= 4 ? 3 : 2)) vo
     __shared__ float4 edge[2][NTR][2][LX];     // [buffer][thread row][0 = its top row, 1 = its bottom row][lane]
     __shared__ int published[NT / 64 + 1];     // per wave: number of sweeps whose edge rows it has published; [NT/64]: the maximum over the waves
     __shared__ int dead_s;                     // the launch has failed (persist_sync.hpp): leave
+    // PERSIST: a thread's EXCHANGE RECORD, built once per launch behind the tile setup and read back at every halo exchange:
+    //   .x  byte offset of its 4-pixel group in row y0 of a plane (mod 2^32: y0 or x0 may be negative; row g adds g * pitch, and every
+    //       row that is stored or loaded lies inside the plane, whose size the host keeps below 4 GiB for a persistent launch)
+    //   .y  bit g: store row g (its centre's band), bit 8+g: load row g (halo inside the image), bits 16-18: how many of the group's
+    //       4 pixels lie left of `cols`, bit 19: fewer than 4 do (the group straddles the image's right edge)
+    //   .z  byte offset from sync_words of the neighbour flag this thread polls, -1 = none (persist_sync.hpp exchange_poll_offset)
+    __shared__ int4 xrec[PERSIST ? NT : 1];
 
     // (gx, gy) = the grid of tiles.  xcd_tiles > 0 (every multi-tile launch): a 1-D launch of 8 * xcd_tiles workgroups in which
     // workgroup p -- dispatched to XCD p % 8 -- takes tile number (p % 8) * xcd_tiles + p / 8, so that each XCD owns a run
@@ -135,7 +142,7 @@ __global__ __launch_bounds__(NT, (NT >= 1024 || G <= 3 ? 4 : G <= 4 ? 3 : 2)) vo
         // tile's loads are in flight.  A workgroup that is not resident never announces itself, its neighbours give up within a
         // millisecond, the status word is set and every workgroup leaves here, before any sweep (also at once when an earlier
         // persistent launch of this context has timed out).  Its barrier is also the one the table's staging needs.
-        if (exchange_wait<false, true>(sync_words, &dead_s, tid, tile_id, bx, by, gx, gy, flag_base, tile_base)) return;
+        if (exchange_wait_at<false, true>(sync_words, &dead_s, tid, tile_id, exchange_poll_offset(tid, bx, by, gx, gy, tile_base), flag_base, tile_base)) return;
     } else {
         __syncthreads();
     }
@@ -146,6 +153,28 @@ __global__ __launch_bounds__(NT, (NT >= 1024 || G <= 3 ? 4 : G <= 4 ? 3 : 2)) vo
     const int tx0 = bx * TW - hx, ty0 = by * TH - hy;
     const bool tile_inside = tx0 >= 0 && tx0 + EW < cols && ty0 >= 1 && ty0 + eh < rows;
 #include "sweep_tile_setup.inc"       // vxr / vpr / mr / mup -> a, b, weights, divisors, reciprocals
+    if constexpr (PERSIST) {
+        // The exchange record (xrec above).  Which rows a thread stores and loads, where they lie and which flag it polls are the same at
+        // every one of a solve's exchanges (124 at 1080p), and the coordinates they follow from are live here anyway; worked out at the
+        // exchange they were ~100 instructions per wave of 64-bit address arithmetic and coordinate compares, and held in registers
+        // across the sweeps they push the sweep loop's operands into scratch.  So: once, here, and parked in LDS.
+        const bool xin = colok && 4 * lx >= hx && 4 * lx < EW - hx;
+        uint32_t bits = 0;
+#pragma unroll
+        for (int g = 0; g < G; g++) {
+            const int y = y0 + g, ty = tr * G + g;
+            const bool central = xin && ty >= hy && ty < eh - hy;
+            const bool band = ty < 2 * hy || ty >= eh - 2 * hy || 4 * lx < 2 * hx || 4 * lx >= EW - 2 * hx;
+            const bool ok = colok && y >= 0 && y < rows;
+            if (central && y < rows && band) bits |= 1u << g;            // my centre, within two halo widths of its edge: some neighbour's halo
+            if (ok && !central) bits |= 0x100u << g;                    // a halo pixel inside the image: some neighbour's centre
+        }
+        const int nv = min(max(cols - x0, 0), 4);
+        bits |= (uint32_t)nv << 16;
+        if (colok && nv < 4) bits |= 1u << 19;
+        const uint32_t off0 = ((uint32_t)y0 * (uint32_t)ip + (uint32_t)x0) * 4u;
+        xrec[tid] = make_int4((int)off0, (int)bits, exchange_poll_offset(tid, bx, by, gx, gy, tile_base), 0);
+    }
 
     RTDD_STAMP(1);
     __builtin_amdgcn_s_setprio(0);
@@ -171,24 +200,46 @@ __global__ __launch_bounds__(NT, (NT >= 1024 || G <= 3 ? 4 : G <= 4 ? 3 : 2)) vo
 #include "sweep_tile_sweeps.inc"      // publish / await / sweep lambdas
     // (the divide variant is chosen per wave; the neighbour handshake above does not care which one a wave runs)
     int s = 0, blk = 0;
-    bool odd = false;
+    bool odd = false, dead = false;          // dead: the launch has failed (exchange_wait_at returned true): leave, behind the loop
     RTDD_XT_BEGIN;
     for (;; blk++) {
         const int s_end = min(s + block_sweeps, nsweeps);
         publish(a[0], a[G - 1], s, 0);               // block prologue: the rows the first sweep of this block reads (a = newest here; s is even)
         using P0 = std::integral_constant<int, 0>; using P1 = std::integral_constant<int, 1>;
-        if (!wave_unsafe) {
-            for (; s + 1 < s_end; s += 2) {
+        if constexpr (!PERSIST) {
+            if (!wave_unsafe) {
+                for (; s + 1 < s_end; s += 2) {
+                    sweep(a, b, s, std::true_type{}, false, P0{});
+                    sweep(b, a, s + 1, std::true_type{}, s + 2 >= s_end, P1{});
+                }
+                if (s < s_end) { sweep(a, b, s, std::true_type{}, true, P0{}); s++; odd = true; }
+            } else {
+                for (; s + 1 < s_end; s += 2) {
+                    sweep(a, b, s, std::false_type{}, false, P0{});
+                    sweep(b, a, s + 1, std::false_type{}, s + 2 >= s_end, P1{});
+                }
+                if (s < s_end) { sweep(a, b, s, std::false_type{}, true, P0{}); s++; odd = true; }
+            }
+        } else {
+            // The same choice written as two loops ONE AFTER THE OTHER, the first of them empty for a wave of the full-divide variant and the
+            // second for every other wave.  As an if / else inside the block loop the compiler kept the tile as it was at the top of the
+            // block alive through the first variant's sweeps (the second's input, as far as it could tell), ran those on a copy, and
+            // every block paid 24 v_mov_b64 of the whole tile, 12 in front of the sweeps and 12 behind the exchange.
+            const int s_fast = wave_unsafe ? s : s_end;
+            for (; s + 1 < s_fast; s += 2) {
                 sweep(a, b, s, std::true_type{}, false, P0{});
                 sweep(b, a, s + 1, std::true_type{}, s + 2 >= s_end, P1{});
             }
-            if (s < s_end) { sweep(a, b, s, std::true_type{}, true, P0{}); s++; odd = true; }
-        } else {
-            for (; s + 1 < s_end; s += 2) {
-                sweep(a, b, s, std::false_type{}, false, P0{});
+            if (s < s_fast) { sweep(a, b, s, std::true_type{}, true, P0{}); s++; odd = true; }
+            // (the odd sweep that ends a tail block is the first half of a pair here, not a sweep of its own behind the loop: with one the
+            // tiles of two rows per thread kept x_{k-1} in different registers in the sweeps and at the exchange, and moved it at every block)
+            while (s < s_end) {
+                const bool single = s + 1 >= s_end;
+                sweep(a, b, s, std::false_type{}, single, P0{});
+                if (single) { s++; odd = true; break; }
                 sweep(b, a, s + 1, std::false_type{}, s + 2 >= s_end, P1{});
+                s += 2;
             }
-            if (s < s_end) { sweep(a, b, s, std::false_type{}, true, P0{}); s++; odd = true; }
         }
         if (!PERSIST || s >= nsweeps) break;
         RTDD_XT(0);
@@ -198,25 +249,20 @@ __global__ __launch_bounds__(NT, (NT >= 1024 || G <= 3 ? 4 : G <= 4 ? 3 : 2)) vo
         // Exchange buffers alternate between (Yk,Ym) and (Xk,Xm) by block parity: a neighbour publishes block b+1 only
         // after consuming my block-b strips, and I overwrite that buffer (block b+2) only after waiting for its b+1.
         {
-            float *Ek = (blk & 1) ? Xk : Yk, *Em = (blk & 1) ? Xm : Ym;
-            // The exchange's addresses and predicates are recomputed here from "laundered" copies of the thread coordinates: left
-            // to itself the compiler hoists them (six 64-bit offsets, a dozen lane masks) out of the block loop, where they stay
-            // live across the sweeps and push the sweep loop's operands into scratch.
+            const float *Ek = (blk & 1) ? Xk : Yk, *Em = (blk & 1) ? Xm : Ym;
+            // Everything that depends on the thread's place comes out of its exchange record (xrec, built behind the setup) with one LDS
+            // read; the planes are addressed as scalar base + 32-bit offset.  The index is a "laundered" copy of tid, so that the compiler
+            // cannot form the record's address outside the block loop and keep it live across the sweeps.
             int tid_x = tid;
             asm volatile("" : "+v"(tid_x));
-            const int lx = tid_x % LX, tr = tid_x / LX;
-            const int x0 = bx * TW - hx + 4 * lx, y0 = by * TH - hy + tr * G;
-            const bool colok = x0 >= 0 && x0 < cols;
-            const bool xin = colok && 4 * lx >= hx && 4 * lx < EW - hx;
+            const int4 rec = xrec[tid_x];
+            const uint32_t off0 = (uint32_t)rec.x, bits = (uint32_t)rec.y, pitch = (uint32_t)ip * 4u;
+            RTDD_XT(5);
 #pragma unroll
             for (int g = 0; g < G; g++) {
-                const int y = y0 + g, ty = tr * G + g;
-                const bool central = xin && ty >= hy && ty < eh - hy && y < rows;
-                const bool band = ty < 2 * hy || ty >= eh - 2 * hy || 4 * lx < 2 * hx || 4 * lx >= EW - 2 * hx;
-                if (central && band) {
-                    const size_t off = (size_t)y * ip + x0;
-                    store_sc1((float4 *)(Ek + off), make_float4(a[g][0], a[g][1], a[g][2], a[g][3]));
-                    store_sc1((float4 *)(Em + off), make_float4(b[g][0], b[g][1], b[g][2], b[g][3]));
+                if (bits & (1u << g)) {
+                    store_sc1_at(Ek, off0 + g * pitch, a[g]);
+                    store_sc1_at(Em, off0 + g * pitch, b[g]);
                 }
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // every storing wave drains its write-through stores
@@ -225,64 +271,52 @@ __global__ __launch_bounds__(NT, (NT >= 1024 || G <= 3 ? 4 : G <= 4 ? 3 : 2)) vo
 #ifndef RTDD_EXCHANGE_ACQUIRE
 #define RTDD_EXCHANGE_ACQUIRE 0
 #endif
-            if (exchange_wait<RTDD_EXCHANGE_ACQUIRE != 0>(sync_words, &dead_s, tid, tile_id, bx, by, gx, gy, flag_base + blk + 1, tile_base)) return;      // flag, bounded poll, (acquire,) barrier
+            if (exchange_wait_at<RTDD_EXCHANGE_ACQUIRE != 0>(sync_words, &dead_s, tid, tile_id, rec.z, flag_base + blk + 1, tile_base)) { dead = true; break; }      // flag, bounded poll, (acquire,) barrier
             RTDD_XT(2);
             RTDD_XT(3);
 #if RTDD_EXCHANGE_ACQUIRE
 #pragma unroll
             for (int g = 0; g < G; g++) {
-                const int y = y0 + g, ty = tr * G + g;
-                const bool central = xin && ty >= hy && ty < eh - hy;
-                const bool ok = colok && y >= 0 && y < rows;
-                if (ok && !central) {                                    // a halo pixel inside the image: some neighbour's centre
-                    const size_t off = (size_t)y * ip + x0;
-                    const float4 vx = *(const float4 *)(Ek + off), vp = *(const float4 *)(Em + off);      // plain vector loads behind the agent acquire
-                    const float xv[4] = {vx.x, vx.y, vx.z, vx.w}, pv[4] = {vp.x, vp.y, vp.z, vp.w};
-#pragma unroll
-                    for (int i = 0; i < 4; i++) { const bool in = x0 + i < cols; a[g][i] = in ? xv[i] : 0.0f; b[g][i] = in ? pv[i] : 0.0f; }
+                if (bits & (0x100u << g)) {                              // plain vector loads behind the agent acquire
+                    a[g] = *(const f4r *)((const char *)Ek + (off0 + g * pitch));
+                    b[g] = *(const f4r *)((const char *)Em + (off0 + g * pitch));
                 }
             }
 #else
             // No acquire: every halo load is a 16-byte sc1 load straight into the tile's registers (the strips were stored sc1 and drained
-            // before their owner's flag; the polling wave loads after its poll, the others after the barrier exchange_wait ends with).
-            // Round 2 measured the acquire at 0.8-0.9 us of a 15.7 us block.  All loads are issued, then ONE wait that the loaded
-            // registers pass through (so that no use can be scheduled in front of it).
-            f4v_t hk[G], hm[G];
+            // before their owner's flag; the polling wave loads after its poll, the others after the barrier exchange_wait_at ends with).
+            // Round 2 measured the acquire at 0.8-0.9 us of a 15.7 us block.  All loads are issued, then ONE wait, in one statement
+            // (sweep_common.hpp load_halo_rows_sc1): a[g] / b[g] are the loads' own destinations, a row or lane that is not loaded keeps its
+            // value, and nothing is copied in or out.
+            {
+                uint32_t off[G];
+                unsigned long long lanes[G];
 #pragma unroll
-            for (int g = 0; g < G; g++) {
-                const int y = y0 + g, ty = tr * G + g;
-                const bool central = xin && ty >= hy && ty < eh - hy;
-                const bool ok = colok && y >= 0 && y < rows;
-                hk[g] = a[g]; hm[g] = b[g];
-                if (ok && !central) {                                    // a halo pixel inside the image: some neighbour's centre
-                    const size_t off = (size_t)y * ip + x0;
-                    load_sc1(hk[g], Ek + off); load_sc1(hm[g], Em + off);
-                }
-            }
-            if constexpr (G == 1) asm volatile("s_waitcnt vmcnt(0)" : "+v"(hk[0]), "+v"(hm[0]) :: "memory");
-            else if constexpr (G == 2) asm volatile("s_waitcnt vmcnt(0)" : "+v"(hk[0]), "+v"(hm[0]), "+v"(hk[1]), "+v"(hm[1]) :: "memory");
-            else if constexpr (G == 3) asm volatile("s_waitcnt vmcnt(0)" : "+v"(hk[0]), "+v"(hm[0]), "+v"(hk[1]), "+v"(hm[1]), "+v"(hk[2]), "+v"(hm[2]) :: "memory");
-            else if constexpr (G == 4) asm volatile("s_waitcnt vmcnt(0)" : "+v"(hk[0]), "+v"(hm[0]), "+v"(hk[1]), "+v"(hm[1]), "+v"(hk[2]), "+v"(hm[2]), "+v"(hk[3]), "+v"(hm[3]) :: "memory");
-            else {
-                static_assert(G == 6, "add a wait for this G");
-                asm volatile("s_waitcnt vmcnt(0)" : "+v"(hk[0]), "+v"(hm[0]), "+v"(hk[1]), "+v"(hm[1]), "+v"(hk[2]), "+v"(hm[2]) :: "memory");
-                asm volatile("s_waitcnt vmcnt(0)" : "+v"(hk[3]), "+v"(hm[3]), "+v"(hk[4]), "+v"(hm[4]), "+v"(hk[5]), "+v"(hm[5]) :: "memory");
-            }
-#pragma unroll
-            for (int g = 0; g < G; g++) {
-                const int y = y0 + g, ty = tr * G + g;
-                const bool central = xin && ty >= hy && ty < eh - hy;
-                const bool ok = colok && y >= 0 && y < rows;
-                if (ok && !central) {
-#pragma unroll
-                    for (int i = 0; i < 4; i++) { const bool in = x0 + i < cols; a[g][i] = in ? hk[g][i] : 0.0f; b[g][i] = in ? hm[g][i] : 0.0f; }
-                }
+                for (int g = 0; g < G; g++) { off[g] = off0 + g * pitch; lanes[g] = __builtin_amdgcn_ballot_w64((bits & (0x100u << g)) != 0); }
+                RTDD_XT(6);
+                load_halo_rows_sc1<G>(a, b, Ek, Em, off, lanes);
+                RTDD_XT(7);
             }
 #endif
+            // A group that straddles the image's right edge (cols % 4 != 0, the tile column that holds `cols`) was loaded whole: its
+            // pixels beyond the edge go back to 0.  Wave-uniform: no wave of any other tile column, and no wave at all when cols is a
+            // multiple of 4 (1920), has anything behind the wait.
+            if (__builtin_amdgcn_ballot_w64((bits & (1u << 19)) != 0) != 0) {
+                asm volatile("");                                        // (keeps this a branch: the one-row tiles' eight selects were otherwise run by every wave)
+                const int nv = (int)((bits >> 16) & 7u);
+#pragma unroll
+                for (int g = 0; g < G; g++) {
+                    if (bits & (0x100u << g)) {
+#pragma unroll
+                        for (int i = 0; i < 4; i++) { const bool in = i < nv; a[g][i] = in ? a[g][i] : 0.0f; b[g][i] = in ? b[g][i] : 0.0f; }
+                    }
+                }
+            }
         }
         (void)ntiles;
         RTDD_XT(4);
     }
+    if (PERSIST && dead) return;
     // results of the last block go to the exchange buffer of ITS parity (free by the argument above; blk = 0 -> Yk/Ym)
     if (PERSIST && (blk & 1)) { Yk = Xk; Ym = Xm; }
     RTDD_STAMP(2);
@@ -732,7 +766,8 @@ static int launch_sweeps_blocked_impl(rtdd_ctx *ctx, const Level &L, size_t ip, 
         int block_sweeps = m;
         bool persistent = !single && want_persistent && (int)(grid.x * grid.y) * images <= ctx->num_cus && grid.x * grid.y * images <= (unsigned)kSyncMaxTiles &&
                                 (T % 2 == 0) && n - done > T && hy == T &&
-                                hx <= TW && hy <= TH;      // the halo must lie inside the 8 immediate neighbours' centres
+                                hx <= TW && hy <= TH &&    // the halo must lie inside the 8 immediate neighbours' centres
+                                (size_t)rows * ip * sizeof(float) < ((size_t)1 << 32);      // (the exchange addresses a plane by 32-bit byte offsets)
         if (is_col_tile(tile)) persistent = false;          // (the column-layout kernel has no persistent mode)
         if (persistent) {
 #define RTDD_TILE_CASE(id, LX_, NT_, G_) case id: persistent = persistent_possible<LX_, NT_, G_>(ctx, tile, kTiles[tile].nt); break;

@@ -1,5 +1,5 @@
 // sweep_common.hpp -- device helpers of the register-resident sweep kernels (sweep_blocked.hip): DPP lane
-// shifts, the write-through store / sc1 load of the inter-workgroup hand-off, the 3-operation divide and the rounded reciprocal.
+// shifts, the write-through stores / sc1 loads of the inter-workgroup hand-off, the 3-operation divide and the rounded reciprocal.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -27,23 +27,49 @@ __device__ __forceinline__ float lane_from_next(float v) {   // lane l <- lane l
 __device__ __forceinline__ float lds_from_prev(int prev4, float v) { return __int_as_float(__builtin_amdgcn_ds_bpermute(prev4, __float_as_int(v))); }
 __device__ __forceinline__ float lds_from_next(int prev4, float v) { return __int_as_float(__builtin_amdgcn_ds_bpermute(prev4 + 8, __float_as_int(v))); }
 
-// write-through (sc1) 16-byte store for inter-workgroup hand-offs (no release fence needed; the storing wave drains vmcnt itself)
-__device__ __forceinline__ void store_sc1(float4 *p, float4 v) {
-    typedef float f4v __attribute__((ext_vector_type(4)));
-    const f4v t = {v.x, v.y, v.z, v.w};
-    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(t) : "memory");
-}
-
-// 16-byte sc1 load to registers (bypasses this CU's L1, served by L2 / memory): with EVERY load of handed-off bytes of this form, every
-// store of them sc1 and drained, and the flag protocol of persist_sync.hpp, the consumer needs no agent-scope acquire
-// (MI355X_MICROARCH.md, "Valid forms", table row 1).  The value is NOT there when the statement returns: wait_loads() below.
+// The inter-workgroup hand-off's accesses (persist_sync.hpp).  Stores: write-through (sc1) 16-byte stores, no release fence needed -- the
+// storing wave drains vmcnt itself.  Loads: 16-byte sc1 loads to registers (they bypass this CU's L1 and are served by L2 / memory): with
+// EVERY load of handed-off bytes of this form, every store of them sc1 and drained, and the flag protocol of persist_sync.hpp, the consumer
+// needs no agent-scope acquire (MI355X_MICROARCH.md, "Valid forms", table row 1).  Both take the address as a scalar base plus a 32-bit
+// unsigned byte offset per lane (the instructions' `saddr` form): a kernel that exchanges the same rows many times keeps one offset per
+// thread and forms no 64-bit address (sweep_blocked.hip).
 typedef float f4v_t __attribute__((ext_vector_type(4)));
-// `dst` is a read-write operand: on the path AROUND a conditional load the register keeps its old value, so the register allocator has no
-// reason to give the load a register of its own and copy it at the join -- in front of the wait, where the copy would read stale bits.
-// tests/test_isa_hazards.py checks in the disassembly that nothing reads or writes a load's registers before the next s_waitcnt vmcnt(0).
-__device__ __forceinline__ void load_sc1(f4v_t &dst, const float *p) {
-    asm volatile("global_load_dwordx4 %0, %1, off sc1" : "+v"(dst) : "v"(p) : "memory");
+__device__ __forceinline__ void store_sc1_at(const float *base, uint32_t off, f4v_t v) {
+    asm volatile("global_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1" ::"v"(off), "v"(v), "s"(base) : "memory");
 }
+// The halo loads of a thread's G rows from two planes, and the wait behind them, as ONE statement: row g is loaded (16 bytes from `bk`
+// into a[g], 16 from `bm` into b[g], both at byte offset off[g]) in the lanes of mask[g]; the other lanes' registers, and rows whose
+// mask is empty, keep their values.  a[] / b[] are read-write operands of the statement that also holds the s_waitcnt: whatever
+// registers the compiler hands in are the ones that are loaded AND waited for, so no copy of a loaded register can come to lie between
+// a load and the wait (two statements, loads and wait, leave the register allocator free to move a value in between -- it did, in the
+// 168-register instantiations -- and such a copy reads stale bits).  tests/test_isa_hazards.py checks it on the disassembly all the same.
+// EXEC is saved in front and put back behind, as in masked_fmac4 below; an SALU write of EXEC needs no wait state before a VMEM instruction.
+#define RTDD_HALO_ROW(n) "s_and_b64 exec, %[sv], %[m" #n "]\n\tglobal_load_dwordx4 %[a" #n "], %[o" #n "], %[bk] sc1\n\tglobal_load_dwordx4 %[b" #n "], %[o" #n "], %[bm] sc1\n\t"
+#define RTDD_HALO_OUT(n) [a##n] "+v"(a[n]), [b##n] "+v"(b[n])
+#define RTDD_HALO_IN(n) [o##n] "v"(off[n]), [m##n] "s"(mask[n])
+#define RTDD_HALO_ASM(rows, outs, ins) asm volatile("s_mov_b64 %[sv], exec\n\t" rows "s_mov_b64 exec, %[sv]\n\ts_waitcnt vmcnt(0)" : outs, [sv] "=&s"(sv) : ins, [bk] "s"(bk), [bm] "s"(bm) : "memory", "scc")
+#define RTDD_C ,
+template <int G>
+__device__ __forceinline__ void load_halo_rows_sc1(f4v_t (&a)[G], f4v_t (&b)[G], const float *bk, const float *bm, const uint32_t (&off)[G], const unsigned long long (&mask)[G]) {
+    unsigned long long sv;
+    if constexpr (G == 1) RTDD_HALO_ASM(RTDD_HALO_ROW(0), RTDD_HALO_OUT(0), RTDD_HALO_IN(0));
+    else if constexpr (G == 2) RTDD_HALO_ASM(RTDD_HALO_ROW(0) RTDD_HALO_ROW(1), RTDD_HALO_OUT(0) RTDD_C RTDD_HALO_OUT(1), RTDD_HALO_IN(0) RTDD_C RTDD_HALO_IN(1));
+    else if constexpr (G == 3) RTDD_HALO_ASM(RTDD_HALO_ROW(0) RTDD_HALO_ROW(1) RTDD_HALO_ROW(2), RTDD_HALO_OUT(0) RTDD_C RTDD_HALO_OUT(1) RTDD_C RTDD_HALO_OUT(2),
+                                             RTDD_HALO_IN(0) RTDD_C RTDD_HALO_IN(1) RTDD_C RTDD_HALO_IN(2));
+    else if constexpr (G == 4) RTDD_HALO_ASM(RTDD_HALO_ROW(0) RTDD_HALO_ROW(1) RTDD_HALO_ROW(2) RTDD_HALO_ROW(3), RTDD_HALO_OUT(0) RTDD_C RTDD_HALO_OUT(1) RTDD_C RTDD_HALO_OUT(2) RTDD_C RTDD_HALO_OUT(3),
+                                             RTDD_HALO_IN(0) RTDD_C RTDD_HALO_IN(1) RTDD_C RTDD_HALO_IN(2) RTDD_C RTDD_HALO_IN(3));
+    else {
+        static_assert(G == 6, "add a statement for this G");
+        RTDD_HALO_ASM(RTDD_HALO_ROW(0) RTDD_HALO_ROW(1) RTDD_HALO_ROW(2) RTDD_HALO_ROW(3) RTDD_HALO_ROW(4) RTDD_HALO_ROW(5),
+                      RTDD_HALO_OUT(0) RTDD_C RTDD_HALO_OUT(1) RTDD_C RTDD_HALO_OUT(2) RTDD_C RTDD_HALO_OUT(3) RTDD_C RTDD_HALO_OUT(4) RTDD_C RTDD_HALO_OUT(5),
+                      RTDD_HALO_IN(0) RTDD_C RTDD_HALO_IN(1) RTDD_C RTDD_HALO_IN(2) RTDD_C RTDD_HALO_IN(3) RTDD_C RTDD_HALO_IN(4) RTDD_C RTDD_HALO_IN(5));
+    }
+}
+#undef RTDD_C
+#undef RTDD_HALO_ASM
+#undef RTDD_HALO_IN
+#undef RTDD_HALO_OUT
+#undef RTDD_HALO_ROW
 
 // Result stores: plain (non-temporal and write-through stores measured no faster: EXPERIMENTS.md).
 __device__ __forceinline__ void store_result(float4 *p, float4 v) { *p = v; }

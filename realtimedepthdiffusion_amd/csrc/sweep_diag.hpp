@@ -14,7 +14,9 @@ __device__ unsigned long long g_stamps[4096][5];
 #define RTDD_STAMP_LAST(k) do { __builtin_amdgcn_s_waitcnt(0); RTDD_STAMP(k); } while (0)
 // (round 6) the tile's loads have LANDED: a wait the product build does not have at this point, so that the stamp splits `load + setup`
 #define RTDD_STAMP_LOADED(k) do { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); RTDD_STAMP(k); } while (0)
-__device__ unsigned long long g_xphase[4096][6];
+// [0] sweeps, [1] strip stores + drain + barrier, [2] flag + poll, [3] (acquire +) barrier, [4] behind the halo loads' wait, [5] from the end of the sweeps to
+// the first strip store, [6] from the poll's barrier to the last halo load issued, [7] the halo loads' wait
+__device__ unsigned long long g_xphase[4096][8];
 #define RTDD_XT(k) do { if (threadIdx.x == 0) { const unsigned long long t_ = __builtin_amdgcn_s_memrealtime(); g_xphase[blockIdx.y * gridDim.x + blockIdx.x][k] += t_ - xt_; xt_ = t_; } } while (0)
 #define RTDD_XT_BEGIN unsigned long long xt_ = __builtin_amdgcn_s_memrealtime()
 #else

@@ -150,6 +150,10 @@
         RTDD_TL(2, s);
 #pragma unroll
         for (int gi = 1; gi < G - 1; gi++) group([gi](int g) { return g == gi; });
+        // (no instruction: the row just written passes through one statement as FOUR CONSECUTIVE registers.  The one-row persistent tiles
+        // otherwise keep x_{k-1} in one place during the sweeps and in another at the halo exchange, whose 16-byte loads need the row
+        // consecutive, and move it there and back at every exchange -- tests/test_isa_exchange.py)
+        if constexpr (PERSIST && G == 1) asm volatile("" : "+v"(oth[0]));
         RTDD_TL(3, s);
     };
 

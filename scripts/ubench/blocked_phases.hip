@@ -51,7 +51,7 @@ int main(int argc, char **argv) {
     double a = 0, b = 0, c = 0, start = 0, ld = 0;
     for (int i = 0; i < 4096; i++) if (st[i][3] > st[i][0] && st[i][0] != 0) { ld += st[i][4] - st[i][0]; a += st[i][1] - st[i][0]; b += st[i][2] - st[i][1]; c += st[i][3] - st[i][2]; start += st[i][0] - t0; }
     if (getenv("RTDD_PERSIST")) {
-        static unsigned long long z6[4096][6]; hipMemcpyToSymbol(HIP_SYMBOL(g_xphase), z6, sizeof(z6));
+        static unsigned long long z6[4096][8]; hipMemcpyToSymbol(HIP_SYMBOL(g_xphase), z6, sizeof(z6));
         ctx.opt.persistent = 1; ctx.num_cus = 256;
         hipEvent_t p0, p1; hipEventCreate(&p0); hipEventCreate(&p1);
         const int nb = 25;
@@ -59,11 +59,15 @@ int main(int argc, char **argv) {
         launch_sweeps_blocked(&ctx, L, ip, rows, cols, om_d, T * nb, &pk, &pm, &ln);
         hipEventRecord(p1, ctx.stream); hipDeviceSynchronize();
         float pms; hipEventElapsedTime(&pms, p0, p1);
-        static unsigned long long xp[4096][6]; hipMemcpyFromSymbol(xp, HIP_SYMBOL(g_xphase), sizeof(xp));
-        double ph[5] = {0, 0, 0, 0, 0}; int nw = 0;
-        for (int i = 0; i < 4096; i++) if (xp[i][0]) { nw++; for (int k = 0; k < 5; k++) ph[k] += xp[i][k]; }
+        static unsigned long long xp[4096][8]; hipMemcpyFromSymbol(xp, HIP_SYMBOL(g_xphase), sizeof(xp));
+        double ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}; int nw = 0;
+        for (int i = 0; i < 4096; i++) if (xp[i][0]) { nw++; for (int k = 0; k < 8; k++) ph[k] += xp[i][k]; }
+        const double per = 1.0 / nw / 100 / (nb - 1);
+        // (publish = until the first strip store + stores, drain, barrier; halo load = until the last load is issued + the wait + behind the wait)
         printf("PERSISTENT %d launches, %d blocks of %d sweeps: %.2f us per block; wave-0 means per block: sweeps %.2f, publish+drain+barrier %.2f, flag+poll %.2f, acquire+barrier %.2f, halo load %.2f us\n",
-               ln, nb, T, pms * 1e3 / nb, ph[0] / nw / 100 / (nb - 1), ph[1] / nw / 100 / (nb - 1), ph[2] / nw / 100 / (nb - 1), ph[3] / nw / 100 / (nb - 1), ph[4] / nw / 100 / (nb - 1));
+               ln, nb, T, pms * 1e3 / nb, ph[0] * per, (ph[5] + ph[1]) * per, ph[2] * per, ph[3] * per, (ph[6] + ph[7] + ph[4]) * per);
+        printf("  publish: %.2f us before the first strip store, %.2f stores + drain + barrier; halo load: %.2f us until the last load is issued, %.2f waiting, %.2f behind the wait\n",
+               ph[5] * per, ph[1] * per, ph[6] * per, ph[7] * per, ph[4] * per);
     }
     printf("%dx%d tile %d T %d: %d workgroups; mean per WG: start skew %.2f us, load+setup %.2f us (of it: until the slowest wave's loads have landed %.2f, setup behind them %.2f), %d sweeps %.2f us (%.3f us/sweep), store %.2f us; first start -> last end %.2f us\n",
            cols, rows, tile, T, n, start / n / 100, a / n / 100, ld / n / 100, (a - ld) / n / 100, T, b / n / 100, b / n / 100 / T, c / n / 100, (tend - t0) / 100.0);
