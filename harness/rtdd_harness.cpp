@@ -31,6 +31,11 @@
 //                                 runs, in front of frame F (the user painting into a live view)
 //     --refine sor|mg|auto [--tolerance T] = extension: converge the finest level after the estimate (rtdd_refine_depth)
 //     --edges gray|color = extension: the estimates' edge weights from the gray image (default, the reference's) or from the BGR image (rtdd_pyramid_set_guide)
+//     --regions cut|smooth|both = extension: depth regions (rtdd_pyramid_set_regions) -- the estimates cut the edges between different region
+//                                 ids, smooth the edges inside one region, or both; the regions are painted into the pyramid's region pair
+//                                 before the estimate by --region-fill "x,y;x,y;...:id" (a lasso, rtdd_fill_polygon under the --fill-rule in
+//                                 force) and --region-wand "x,y,tol:id" (a click, rtdd_fill_similar on the photograph under the
+//                                 --wand-connect in force), the fills first, each kind in command-line order
 // and adds what the reference cannot do: --devices N --batch B runs B independent estimates
 // round-robin over N GPUs, one host thread + one HIP stream + one rtdd_ctx per GPU, no collective.
 #include <hip/hip_runtime.h>
@@ -236,6 +241,10 @@ struct Job {
     rtdd_ambient_occlusion ao = {RTDD_AO_SHADE, 8, 16, 2.0f, 0.0f, 1.0f};
     bool sequential = false;      // --sequential: a --batch as one estimate after the other (default: rtdd_estimate_depth_batch, all images in the same launches)
     bool cold = false;            // --cold: no warm-up: the first (and, without --live, only) estimate pays the one-time costs
+    // --regions cut|smooth|both, --region-fill, --region-wand: rtdd_region_flags and what is painted into the pyramid's region pair
+    int region_flags = 0;
+    std::vector<Lasso> region_fills;
+    std::vector<Wand> region_wands;
     bool edges_color = false;     // --edges color: the estimates read their edge weights from the BGR image (rtdd_pyramid_set_guide); default gray: the reference's
 };
 
@@ -317,6 +326,24 @@ static int paint_strokes(rtdd_ctx *ctx, const Job &job, void *ed, size_t ed_pitc
     CK(stroke_calls(ctx, job, ed, ed_pitch, scr, scr_pitch, orig, orig_pitch, rows, cols));
     CK(fill_polygons(ctx, job, ed, ed_pitch, scr, scr_pitch, orig, orig_pitch, rows, cols));
     return wand_calls(ctx, job, ed, ed_pitch, scr, scr_pitch, orig, orig_pitch, rows, cols);
+}
+
+// --regions: the flags, then the --region-fill polygons and the --region-wand clicks on the selected image's region pair (the label is the
+// region id; "similar" reads the photograph).  Behind rtdd_pyramid_set_image, which makes the image's regions unassigned again
+static int region_calls(rtdd_ctx *ctx, const Job &job, const void *orig, size_t orig_pitch, int rows, int cols) {
+    if (job.region_flags == 0) return RTDD_OK;
+    CK(rtdd_pyramid_set_regions(ctx, job.region_flags));
+    void *pe, *pm; size_t pie, pim;
+    CK(rtdd_pyramid_image(ctx, RTDD_IMG_REGION_EDITED, 0, &pe, &pie, nullptr, nullptr));
+    CK(rtdd_pyramid_image(ctx, RTDD_IMG_REGION_MASK, 0, &pm, &pim, nullptr, nullptr));
+    for (const Job::Lasso &l : job.region_fills)
+        CK(rtdd_fill_polygon(ctx, l.xy.data(), (int)l.xy.size() / 2, &l.fill, (uint8_t *)pe, pie, (uint8_t *)pm, pim, (const uint8_t *)orig, orig_pitch, rows, cols));
+    for (const Job::Wand &q : job.region_wands) {
+        rtdd_wand_info info;
+        CK(rtdd_fill_similar(ctx, &q.w, (uint8_t *)pe, pie, (uint8_t *)pm, pim, (const uint8_t *)orig, orig_pitch, rows, cols, &info));
+        std::printf("region wand %d,%d tolerance %d: region %d, %d pixels\n", q.w.x, q.w.y, q.w.tolerance, q.w.label0, info.pixels);
+    }
+    return RTDD_OK;
 }
 
 // rtdd_paint_ramp_strokes (with label0 == label1: rtdd_paint_strokes) restated for the host's own image pair (--live: the host owns the pair every frame uploads; include/rtdd.h has the
@@ -482,6 +509,7 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
             void *po; size_t pio;
             CK(rtdd_pyramid_image(ctx, RTDD_IMG_ORIGINAL, 0, &po, &pio, nullptr, nullptr));
             CK(paint_strokes(ctx, job, pe, pie, ps, pis, po, pio, rows, cols));
+            CK(region_calls(ctx, job, po, pio, rows, cols));
         }
         CK(rtdd_estimate_depth_batch(ctx, job.iters));                  // main.cpp:239-291, for every image
         depth_u8->resize((size_t)rows * cols);
@@ -533,6 +561,7 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
         for (const Paint &p : job.paints)
             CK(rtdd_paint_image(ctx, p.x, p.y, p.label, p.radius, (uint8_t *)p_ed, pi_ed, (uint8_t *)p_scr, pi_scr, rows, cols));
         CK(paint_strokes(ctx, job, p_ed, pi_ed, p_scr, pi_scr, p_orig, pi_orig, rows, cols));
+        CK(region_calls(ctx, job, p_orig, pi_orig, rows, cols));
         CK(rtdd_host_alloc(&h_scr.p, (size_t)rows * cols)); CK(rtdd_host_alloc(&h_ed.p, (size_t)rows * cols * 3));
         CK(rtdd_host_alloc(&h_u8[0].p, (size_t)rows * cols)); CK(rtdd_host_alloc(&h_u8[1].p, (size_t)rows * cols));
         CK(rtdd_download(ctx, h_scr.p, cols, p_scr, pi_scr, cols, rows));            // the host's Mats (main.cpp:160-168: decoded on the host there)
@@ -604,6 +633,7 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
             for (const Paint &p : job.paints)                           // main.cpp:55-57
                 CK(rtdd_paint_image(ctx, p.x, p.y, p.label, p.radius, (uint8_t *)p_ed, pi_ed, (uint8_t *)p_scr, pi_scr, rows, cols));
             CK(paint_strokes(ctx, job, p_ed, pi_ed, p_scr, pi_scr, p_orig, pi_orig, rows, cols));
+            CK(region_calls(ctx, job, p_orig, pi_orig, rows, cols));
         }
         CK(rtdd_estimate_depth(ctx, job.iters));                        // main.cpp:239-291
         if (!job.refine.empty()) {                                      // extension: converge the finest level
@@ -680,7 +710,7 @@ int main(int argc, const char *argv[]) {
                                  "                    [--shadows N [--shadow-bias B] [--shadow-softness S] [--shadow-strength T]] (relight with cast shadows)\n"
                                  "                    [--ao-radius R] [--ao-directions 4|8] [--ao-bias B] [--ao-strength T] [--relief S] [--ao-map] (ao)  [--ao R [--ao-directions ..] [--ao-bias ..] [--ao-strength ..]] (relight with its ambient term occluded)\n"
                                  "                    [relight's light flags] [--shadows N (256)] [--shadow-bias B] [--shadow-softness S] [--shadow-strength T] [--ao R (16)] [--ao-directions 4|8] [--ao-bias B] [--ao-strength T] (lighting: shade, cast shadows and occlusion in one call)\n"
-                                 "                    [--paint x,y,label,radius]... [--live N [--paint-at frame:x,y,label,radius]...] [--devices D --batch B [--sequential] [--write-all]] [--png] [--cold] [--edges gray|color]\n"
+                                 "                    [--paint x,y,label,radius]... [--live N [--paint-at frame:x,y,label,radius]...] [--devices D --batch B [--sequential] [--write-all]] [--png] [--cold] [--edges gray|color] [--regions cut|smooth|both [--region-fill x,y;...:id]... [--region-wand x,y,tol:id]...]\n"
                                  "                    [--stroke x0,y0,x1,y1,label,radius[,round]]... [--erase x0,y0,x1,y1,radius[,round]]...   (segments, in command-line order, one rtdd_paint_strokes call after --paint)\n"
                                  "                    [--ramp x0,y0,x1,y1,label0,label1,radius[,round]]...   (a depth ramp: label0 at x0,y0 to label1 at x1,y1; in order with --stroke / --erase, all of them one rtdd_paint_ramp_strokes call)\n"
                                  "                    [--fill \"x,y;x,y;...:label\" | \"x,y;...:label0,label1,ax0,ay0,ax1,ay1\"]... [--fill-erase \"x,y;x,y;...\"]... [--fill-rule nonzero|evenodd]   (a lasso filled with a label, a ramp along the axis, or erased: one rtdd_fill_polygon call each, after the strokes, in command-line order)\n"
@@ -707,6 +737,21 @@ int main(int argc, const char *argv[]) {
             const char *v = next();
             if (!std::strcmp(v, "color")) job.edges_color = true;
             else if (std::strcmp(v, "gray")) { std::printf("--edges wants gray or color\n"); return 1; }
+        }
+        else if (!std::strcmp(argv[i], "--regions")) {
+            const char *v = next();
+            job.region_flags = !std::strcmp(v, "cut") ? RTDD_REGION_CUT : !std::strcmp(v, "smooth") ? RTDD_REGION_SMOOTH : !std::strcmp(v, "both") ? RTDD_REGION_CUT | RTDD_REGION_SMOOTH : 0;
+            if (!job.region_flags) { std::printf("--regions wants cut, smooth or both\n"); return 1; }
+        }
+        else if (!std::strcmp(argv[i], "--region-fill")) {
+            Job::Lasso l;
+            if (!parse_fill(next(), false, job.fill_rule, &l) || l.fill.label0 != l.fill.label1) { std::printf("--region-fill wants x,y;x,y;...:id\n"); return 1; }
+            job.region_fills.push_back(l);
+        }
+        else if (!std::strcmp(argv[i], "--region-wand")) {
+            Job::Wand q; q.frame = -1;
+            if (!parse_wand(next(), false, job.wand_flags, &q.w, nullptr) || q.w.label0 != q.w.label1) { std::printf("--region-wand wants x,y,tol:id\n"); return 1; }
+            job.region_wands.push_back(q);
         }
         else if (!std::strcmp(argv[i], "--iters")) job.iters = std::atoi(next());
         else if (!std::strcmp(argv[i], "--refine")) job.refine = next();          // sor | mg | auto
@@ -812,6 +857,7 @@ int main(int argc, const char *argv[]) {
     // cast shadows belong to relight, and their parameters to --shadows: a stray one is refused, not dropped
     const bool lighting = job.effect == "lighting";                           // takes --shadows and --ao together, each with its parameters
     if (job.shadows && job.effect != "relight" && !lighting) { std::printf("--shadows needs --effect relight\n"); return 1; }
+    if (job.region_flags == 0 && (!job.region_fills.empty() || !job.region_wands.empty())) { std::printf("--region-fill and --region-wand need --regions cut|smooth|both\n"); return 1; }
     if (shadow_opt && !job.shadows && !lighting) { std::printf("--shadow-bias, --shadow-softness and --shadow-strength need --shadows N\n"); return 1; }
     // ambient occlusion is --effect ao, or --ao R under --effect relight (without cast shadows: one call renders one or the other); its
     // parameters belong to one of the two: a stray one is refused, not dropped

@@ -281,6 +281,56 @@ int rtdd_index_to_weight_guided(rtdd_ctx *ctx, const uint8_t *guide, size_t guid
                                 const float *depth, size_t depthPitch,
                                 int32_t *index2, int level, int rows, int cols);
 
+/* Depth regions (extension; no reference behaviour): painted object masks the diffusion cannot cross.  Added after ABI version 230
+ * without a version bump: a host finds rtdd_solve_regions, rtdd_index_to_weight_regions, rtdd_region_codes, rtdd_pyramid_set_regions,
+ * rtdd_pyramid_regions and rtdd_pyramid_regions_changed by symbol, and the next bump of RTDD_VERSION should cover them together with
+ * the colour guide's calls above (and RTDD_IMG_REGION_EDITED / _MASK / _CODE).
+ * Where the diffusion may flow is otherwise decided by the photograph alone, and the photograph can be wrong both ways: a weak edge
+ * leaks (a step in colour too small to cut is no boundary for the solver, whatever labels are painted), and a texture blocks (a floor
+ * of random tiles stops diffusion inside one surface).  A REGION CODE says "this is one object", separately from "this pixel has that
+ * depth": one u8 per pixel, 0 = unassigned.
+ * THE RULE, for two 4-neighbours p, q inside the image with codes rp, rq.  Let i be the index the existing rule gives -- the gray or
+ * BGR guide (above), then the depth gate of level != maxLevel with its threshold.  Nothing about i changes.  Then, in this order:
+ *     1. RTDD_REGION_CUT is set and rp != rq               -> the index is 255
+ *     2. else RTDD_REGION_SMOOTH is set and rp == rq != 0  -> the index is 0
+ *     3. else                                              -> the index is i
+ * Outside the image the index stays 256.  THE OVERRIDE COMES AFTER THE GATE: at gated levels the reference zeroes every edge whose two
+ * pixels start at the same u8 depth, and a cut holds there too (level 0 of an estimate would otherwise forget it).  An edge between
+ * a region and unassigned pixels is cut; an edge between two unassigned pixels is the reference's edge, untouched.
+ *   - A cut edge's weight is LUT[255], not 0: 5.6e-45 at the reference's beta 0.4, a denormal.  The per-pixel meta word of the sweeps
+ *     has 8 bits per index, so 256 ("no neighbour") cannot be stored there, and the sweep kernels are not touched for it: they read
+ *     only those indices, so every method, sweep kernel, tile, launch mode, batch and live path is covered by the prepare pass alone.
+ *   - A caller who loads a small beta (rtdd_load_weights) gets a cut as weak as its LUT[255].
+ *   - A region with no scribble inside keeps diffusing only within itself, from whatever depth it started with: a region needs a
+ *     label of its own.
+ *   - A pixel ALL of whose edges are cut has a denormal divisor: the sweep's full-divide path on those pixels (the case
+ *     tests/test_gpu_parity.py::test_denormal_divisor_takes_the_full_divide pins).
+ * An all-zero code image, or regionFlags 0, or regions == NULL with regionFlags 0, gives the existing indices byte for byte, and the
+ * call then IS rtdd_solve_guided: the same record, the same launches, the same bits.  `regions`: u8, pitch >= cols, any address and any
+ * pitch (a 4-byte aligned pointer and pitch, next to aligned depth, scribble and guide, take the four-pixel prepare kernel).
+ * Refused: what rtdd_solve_guided refuses, unknown flag bits, regions == NULL with regionFlags != 0, a region pitch smaller than a row.
+ * A healed time-out (RTDD_ERR_TIMEOUT) runs a region solve again with its regions. */
+enum rtdd_region_flags { RTDD_REGION_CUT = 1, RTDD_REGION_SMOOTH = 2 };
+int rtdd_solve_regions(rtdd_ctx *ctx, float *depth, size_t depthPitch,
+                       const uint8_t *scribble, size_t scribblePitch,
+                       const uint8_t *guide, size_t guidePitch, int guideKind,
+                       const uint8_t *regions, size_t regionsPitch, int regionFlags,
+                       int rows, int cols, int level,
+                       const rtdd_solve_params *params, rtdd_solve_info *info);
+/* rtdd_index_to_weight_guided with the rule above on top: the index pass alone, in the reference's int2 format, for parity tests. */
+int rtdd_index_to_weight_regions(rtdd_ctx *ctx, const uint8_t *guide, size_t guidePitch, int guideKind,
+                                 const uint8_t *regions, size_t regionsPitch, int regionFlags,
+                                 const float *depth, size_t depthPitch,
+                                 int32_t *index2, int level, int rows, int cols);
+/* The packing rule of the pyramid's code planes (rtdd_pyramid_set_regions below) on caller images: from a rows x cols level-0 region
+ * pair -- `edited` u8x3 and `mask` u8, what the paint calls write -- the codes of pyramid level `level` (0..15), floor(rows / 2^level)
+ * x floor(cols / 2^level) of them:
+ *     code_level(y, x) = code_0(y << level, x << level),   code_0(y, x) = mask(y, x) == 255 ? edited(y, 3 x) : 0
+ * A pixel painted with label 0, or erased, is unassigned.  Top-left sampling composes across levels, so no level depends on another.
+ * Stream-ordered; an empty level writes nothing. */
+int rtdd_region_codes(rtdd_ctx *ctx, const uint8_t *edited, size_t editedPitch, const uint8_t *mask, size_t maskPitch,
+                      int rows, int cols, int level, uint8_t *codes, size_t codesPitch);
+
 /* ---- image processing (include/GPUImageProcessing.h:4-10) ---------------------------------- */
 
 /* GPUConvertToFloat -- src/GPUImageProcessing.cu:8-21,72-79: dst[y][x] = src[y][3x] where mask==255. */
@@ -819,8 +869,12 @@ enum rtdd_pyramid_image_kind {
     RTDD_IMG_DEPTH = 4,             /* f32 */
     RTDD_IMG_DEPTH_U8 = 5,          /* u8, level 0 only */
     RTDD_IMG_ARTISTIC = 6,          /* u8x3, level 0 only: output of the effect calls */
-    RTDD_IMG_GUIDE_BGR = 7          /* u8x3 on every level, ceil-sized chain like RTDD_IMG_GRAY; level 0 IS RTDD_IMG_ORIGINAL.  The levels above 0:
+    RTDD_IMG_GUIDE_BGR = 7,         /* u8x3 on every level, ceil-sized chain like RTDD_IMG_GRAY; level 0 IS RTDD_IMG_ORIGINAL.  The levels above 0:
                                        RTDD_ERR_STATE until a call of rtdd_pyramid_set_guide with RTDD_GUIDE_BGR has made them */
+    /* the depth regions (rtdd_pyramid_set_regions): RTDD_ERR_STATE until its first call with non-zero flags has made them */
+    RTDD_IMG_REGION_EDITED = 8,     /* u8x3, level 0 only: what a paint call is given as `edited` to paint a region (the label is the region id) */
+    RTDD_IMG_REGION_MASK = 9,       /* u8, level 0 only: ... and as `scribble` */
+    RTDD_IMG_REGION_CODE = 10       /* u8 on every level, sized like RTDD_IMG_SCRIBBLE: the codes the level's solve reads */
 };
 int rtdd_pyramid_levels(int rows, int cols);             /* src/main.cpp:95 */
 int rtdd_pyramid_create(rtdd_ctx *ctx, int rows, int cols);   /* main.cpp:92-155 minus I/O: images, depth := 255, rtdd_allocate */
@@ -856,6 +910,24 @@ int rtdd_pyramid_set_image(rtdd_ctx *ctx, const uint8_t *bgr, size_t pitch);
  * Refused: no pyramid (RTDD_ERR_STATE), an unknown kind.  rtdd_pyramid_guide: the guide in force (RTDD_GUIDE_GRAY without a pyramid). */
 int rtdd_pyramid_set_guide(rtdd_ctx *ctx, int guideKind);
 int rtdd_pyramid_guide(rtdd_ctx *ctx);
+/* The depth regions of the pyramid's estimates (enum rtdd_region_flags and the rule: rtdd_solve_regions above).  The first call with
+ * non-zero flags allocates, zeroed and per image of a batch, a second level-0 pair -- RTDD_IMG_REGION_EDITED, RTDD_IMG_REGION_MASK --
+ * and one code plane per level, RTDD_IMG_REGION_CODE (RTDD_ERR_NOMEM: nothing is kept).  The pair is painted with the paint calls as they
+ * are: rtdd_paint_image, rtdd_paint_strokes, rtdd_paint_ramp_strokes, rtdd_fill_polygon and rtdd_fill_similar given the pyramid's own
+ * REGION pair as `edited` / `scribble` note a region change (where, given the annotation pair, they note an annotation change): the
+ * label is the region id, an erased pixel or one painted with label 0 is unassigned, and the annotation is neither marked as changed
+ * nor asked to be rebuilt.  rtdd_fill_similar's "similar" still reads the photograph passed as `original`.  rtdd_upload into the pair
+ * notes the change too; a host that writes it by other means says so with rtdd_pyramid_regions_changed (RTDD_ERR_STATE without regions).
+ * While the flags are non-zero, rtdd_estimate_depth, rtdd_estimate_depth_batch, rtdd_live_submit / _ex and rtdd_refine_depth first fill
+ * every level's code plane from the pair when it changed (one launch: rtdd_region_codes' rule for every level and every image of a
+ * batch), then solve every level with that level's codes and the flags.  Independent of rtdd_pyramid_set_guide: all four combinations
+ * work.  Flags 0 switches the effect off and keeps the images, so a host can toggle before and after; a pyramid that never asks
+ * allocates nothing and launches nothing it did not launch before.  rtdd_pyramid_set_image makes the selected image's regions
+ * unassigned again, like its annotation.  A logged estimate remembers the flags it ran with: a healed time-out runs it again with them.
+ * Refused: no pyramid (RTDD_ERR_STATE), unknown flag bits.  rtdd_pyramid_regions: the flags in force (0 without a pyramid). */
+int rtdd_pyramid_set_regions(rtdd_ctx *ctx, int flags);
+int rtdd_pyramid_regions(rtdd_ctx *ctx);
+int rtdd_pyramid_regions_changed(rtdd_ctx *ctx);
 /* annotation: DEVICE pointer to a 1-channel u8 map; decode rule of src/main.cpp:160-168 (value != 32 -> label, mask 255) */
 int rtdd_pyramid_set_annotation(rtdd_ctx *ctx, const uint8_t *annotation, size_t pitch);
 int rtdd_pyramid_image(rtdd_ctx *ctx, int kind, int level, void **ptr, size_t *pitch, int *rows, int *cols);

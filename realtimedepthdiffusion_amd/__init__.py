@@ -56,8 +56,12 @@ C_ABI_SYMBOLS = [
     "rtdd_simulate_relight", "rtdd_simulate_relight_shadowed", "rtdd_simulate_parallax", "rtdd_simulate_ambient_occlusion",
     "rtdd_simulate_lighting", "rtdd_simulate_bokeh",
     "rtdd_solve_guided", "rtdd_index_to_weight_guided", "rtdd_pyrdown_bgr", "rtdd_pyramid_set_guide", "rtdd_pyramid_guide",
+    "rtdd_solve_regions", "rtdd_index_to_weight_regions", "rtdd_region_codes", "rtdd_pyramid_set_regions", "rtdd_pyramid_regions",
+    "rtdd_pyramid_regions_changed",
 ]
 IMG_ORIGINAL, IMG_GRAY, IMG_SCRIBBLE, IMG_EDITED, IMG_DEPTH, IMG_DEPTH_U8, IMG_ARTISTIC, IMG_GUIDE_BGR = range(8)
+IMG_REGION_EDITED, IMG_REGION_MASK, IMG_REGION_CODE = 8, 9, 10    # the depth regions' level-0 pair and per-level codes (rtdd_pyramid_set_regions)
+REGION_CUT, REGION_SMOOTH = 1, 2              # rtdd_region_flags: edges between different codes are cut, edges inside one region are smoothed
 GUIDE_GRAY, GUIDE_BGR = 0, 1                  # rtdd_guide: what the edge weights are read from (rtdd_solve_guided, rtdd_pyramid_set_guide)
 EFFECT_NONE, EFFECT_DEFOCUS, EFFECT_DESATURATION, EFFECT_HAZE = range(4)
 STEREO_VIEW, STEREO_ANAGLYPH = 0, 1           # rtdd_simulate_stereo's modes
@@ -370,6 +374,19 @@ class Context:
         self.last_cycles = info.cycles
         return info.iterations, info.residual
 
+    def solve_regions(self, depthImage, scribbleImage, guideImage, guideKind, regionImage, regionFlags, rows, cols, level,
+                      method=METHOD_CHEBYSHEV_JACOBI, maxIterations=1000, tolerance=0.0, checkEvery=0, relaxation=0.0):
+        """rtdd_solve_regions: solve_guided with the region rule on top -- `regionImage` holds one u8 code per pixel (0: unassigned; None
+        with regionFlags 0: solve_guided itself), `regionFlags` REGION_CUT | REGION_SMOOTH."""
+        dp, dpitch = _img(depthImage); sp, spitch = _img(scribbleImage); gp, gpitch = _img(guideImage)
+        rp, rpitch = _img(regionImage) if regionImage is not None else (None, C.c_size_t(0))
+        params = SolveParams(method, maxIterations, tolerance, checkEvery, relaxation)
+        info = SolveInfo()
+        self._check(lib().rtdd_solve_regions(self._h, dp, dpitch, sp, spitch, gp, gpitch, C.c_int(guideKind), rp, rpitch, C.c_int(regionFlags),
+                                             C.c_int(rows), C.c_int(cols), C.c_int(level), C.byref(params), C.byref(info)))
+        self.last_cycles = info.cycles
+        return info.iterations, info.residual
+
     def last_solve_info(self):
         """What the most recent solve on this context actually ran (kernel, tile, depth, persistence, contraction, counts)."""
         info = SolveInfo()
@@ -394,6 +411,17 @@ class Context:
         gp, gpitch = _img(guideImage); dp, dpitch = _img(depthImage)
         self._check(lib().rtdd_index_to_weight_guided(self._h, gp, gpitch, C.c_int(guideKind), dp, dpitch, C.c_void_p(index2.data_ptr()),
                                                       C.c_int(level), C.c_int(rows), C.c_int(cols)))
+
+    def index_to_weight_regions(self, guideImage, guideKind, regionImage, regionFlags, depthImage, index2, level, rows, cols):
+        gp, gpitch = _img(guideImage); dp, dpitch = _img(depthImage)
+        rp, rpitch = _img(regionImage) if regionImage is not None else (None, C.c_size_t(0))
+        self._check(lib().rtdd_index_to_weight_regions(self._h, gp, gpitch, C.c_int(guideKind), rp, rpitch, C.c_int(regionFlags), dp, dpitch,
+                                                       C.c_void_p(index2.data_ptr()), C.c_int(level), C.c_int(rows), C.c_int(cols)))
+
+    def region_codes(self, edited, mask, rows, cols, level, codes):
+        """rtdd_region_codes: the codes of pyramid level `level` from a rows x cols level-0 region pair, into `codes`."""
+        e, ep = _img(edited); m, mp = _img(mask); c, cp = _img(codes)
+        self._check(lib().rtdd_region_codes(self._h, e, ep, m, mp, C.c_int(rows), C.c_int(cols), C.c_int(level), c, cp))
 
     # ---- include/GPUImageProcessing.h
     def GPUConvertToFloat(self, src, dst, mask, rows, cols):
@@ -566,6 +594,18 @@ class Context:
     def pyramid_guide(self):
         return int(lib().rtdd_pyramid_guide(self._h))
 
+    def pyramid_set_regions(self, flags):
+        """REGION_CUT | REGION_SMOOTH: the estimates apply the region rule with the codes painted into IMG_REGION_EDITED / IMG_REGION_MASK
+        (the first non-zero call allocates them); 0 switches the effect off and keeps the images."""
+        self._check(lib().rtdd_pyramid_set_regions(self._h, C.c_int(flags)))
+
+    def pyramid_regions(self):
+        return int(lib().rtdd_pyramid_regions(self._h))
+
+    def pyramid_regions_changed(self):
+        """The host wrote the region pair through the raw pointers: the code planes are filled again before the next estimate."""
+        self._check(lib().rtdd_pyramid_regions_changed(self._h))
+
     def pyramid_set_annotation(self, annotation):
         p, pitch = _img(annotation)
         self._check(lib().rtdd_pyramid_set_annotation(self._h, p, pitch))
@@ -586,7 +626,7 @@ class Context:
     def pyramid_download(self, kind, level=0):
         import numpy as np
         ptr, pitch, rows, cols = self.pyramid_image(kind, level)
-        dtype, ch = (np.float32, 1) if kind == IMG_DEPTH else (np.uint8, 3 if kind in (IMG_ORIGINAL, IMG_EDITED, IMG_ARTISTIC, IMG_GUIDE_BGR) else 1)
+        dtype, ch = (np.float32, 1) if kind == IMG_DEPTH else (np.uint8, 3 if kind in (IMG_ORIGINAL, IMG_EDITED, IMG_ARTISTIC, IMG_GUIDE_BGR, IMG_REGION_EDITED) else 1)
         out = np.empty((rows, cols, ch) if ch == 3 else (rows, cols), dtype)
         if rows and cols:
             w = cols * ch * out.itemsize

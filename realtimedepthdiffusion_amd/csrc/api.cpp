@@ -316,6 +316,8 @@ static int check_solve_args(rtdd_ctx *ctx, const SolveCall &c) {
     REQUIRE(ctx, c.depthPitch >= (size_t)c.cols * sizeof(float), "depth pitch smaller than a row");
     REQUIRE(ctx, c.guide == RTDD_GUIDE_GRAY || c.guide == RTDD_GUIDE_BGR, "unknown guide kind");
     REQUIRE(ctx, c.scribblePitch >= (size_t)c.cols && c.grayPitch >= (size_t)c.cols * (c.guide == RTDD_GUIDE_BGR ? 3 : 1), "u8 pitch smaller than a row");
+    REQUIRE(ctx, (c.regionFlags & ~(RTDD_REGION_CUT | RTDD_REGION_SMOOTH)) == 0, "unknown region flag");
+    REQUIRE(ctx, c.regionFlags == 0 || (c.regions && c.regionsPitch >= (size_t)c.cols), "region flags without a region image, or its pitch smaller than a row");
     if (ctx->levels.empty()) return fail(ctx, RTDD_ERR_STATE, "rtdd_allocate has not been called");
     if (!ctx->weights_loaded) return fail(ctx, RTDD_ERR_STATE, "rtdd_load_weights has not been called");
     REQUIRE(ctx, c.level >= 0 && c.level < (int)ctx->levels.size(), "level out of range");
@@ -518,6 +520,20 @@ int rtdd_solve_guided(rtdd_ctx *ctx, float *depth, size_t depthPitch, const uint
     return solve_with(ctx, {depth, depthPitch, scribble, scribblePitch, guide, guidePitch, guideKind, rows, cols, level, *params, {}}, info, nullptr);
 }
 
+// rtdd_solve_guided with depth regions.  No regions, or flags 0, is rtdd_solve_guided: the record then holds neither
+int rtdd_solve_regions(rtdd_ctx *ctx, float *depth, size_t depthPitch, const uint8_t *scribble, size_t scribblePitch,
+                       const uint8_t *guide, size_t guidePitch, int guideKind, const uint8_t *regions, size_t regionsPitch, int regionFlags,
+                       int rows, int cols, int level, const rtdd_solve_params *params, rtdd_solve_info *info) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    REQUIRE(ctx, params != nullptr, "null params");
+    REQUIRE(ctx, (regionFlags & ~(RTDD_REGION_CUT | RTDD_REGION_SMOOTH)) == 0, "unknown region flag");
+    REQUIRE(ctx, regions || regionFlags == 0, "region flags without a region image");
+    REQUIRE(ctx, !regions || cols <= 0 || regionsPitch >= (size_t)cols, "region pitch smaller than a row");
+    SolveCall c{depth, depthPitch, scribble, scribblePitch, guide, guidePitch, guideKind, rows, cols, level, *params, {}};
+    if (regions && regionFlags != 0) { c.regions = regions; c.regionsPitch = regionsPitch; c.regionFlags = regionFlags; }
+    return solve_with(ctx, c, info, nullptr);
+}
+
 }  // extern "C"
 #pragma GCC visibility pop
 
@@ -602,7 +618,16 @@ int rtdd_index_to_weight(rtdd_ctx *ctx, const uint8_t *gray, size_t grayPitch, c
 
 int rtdd_index_to_weight_guided(rtdd_ctx *ctx, const uint8_t *guide, size_t guidePitch, int guideKind, const float *depth, size_t depthPitch,
                                 int32_t *index2, int level, int rows, int cols) {
+    return rtdd_index_to_weight_regions(ctx, guide, guidePitch, guideKind, nullptr, 0, 0, depth, depthPitch, index2, level, rows, cols);
+}
+
+int rtdd_index_to_weight_regions(rtdd_ctx *ctx, const uint8_t *guide, size_t guidePitch, int guideKind, const uint8_t *regions, size_t regionsPitch,
+                                 int regionFlags, const float *depth, size_t depthPitch, int32_t *index2, int level, int rows, int cols) {
     if (!ctx) return RTDD_ERR_INVALID;
+    REQUIRE(ctx, (regionFlags & ~(RTDD_REGION_CUT | RTDD_REGION_SMOOTH)) == 0, "unknown region flag");
+    REQUIRE(ctx, regions || regionFlags == 0, "region flags without a region image");
+    REQUIRE(ctx, !regions || cols <= 0 || regionsPitch >= (size_t)cols, "region pitch smaller than a row");
+    if (!regions) regionFlags = 0;
     const uint8_t *gray = guide;
     REQUIRE(ctx, guideKind == RTDD_GUIDE_GRAY || guideKind == RTDD_GUIDE_BGR, "unknown guide kind");
     const size_t grayPitch = guideKind == RTDD_GUIDE_BGR ? guidePitch / 3 : guidePitch;       // (compared with cols below: pitch >= 3 * cols)
@@ -614,7 +639,24 @@ int rtdd_index_to_weight_guided(rtdd_ctx *ctx, const uint8_t *guide, size_t guid
     // reads a depth image a logged, unconfirmed solve may not have written (its copy-back stores nothing after a time-out) and is not
     // logged itself: confirm or heal first.  Nothing logged: nothing to wait for.
     RTDD_TRY(settle_pending(ctx));
-    return launch_index_to_weight(ctx, guide, guidePitch, depth, depthPitch, index2, level, rows, cols, guideKind);
+    return launch_index_to_weight(ctx, guide, guidePitch, depth, depthPitch, index2, level, rows, cols, guideKind, regions, regionsPitch, regionFlags);
+}
+
+// the packing rule of the pyramid's code planes (cascade.hip k_region_codes) on caller images: level `level` of a rows x cols pair
+int rtdd_region_codes(rtdd_ctx *ctx, const uint8_t *edited, size_t editedPitch, const uint8_t *mask, size_t maskPitch, int rows, int cols,
+                      int level, uint8_t *codes, size_t codesPitch) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    REQUIRE(ctx, edited && mask && codes, "null image pointer");
+    REQUIRE(ctx, rows >= 0 && cols >= 0 && rows <= 32768 && cols <= 32768, "size outside [0, 32768]");
+    REQUIRE(ctx, level >= 0 && level < 16, "level outside [0, 15]");
+    RegionLevels lv{};
+    lv.n = 1; lv.shift[0] = level; lv.rows[0] = rows >> level; lv.cols[0] = cols >> level;       // the floor chain (rtdd_allocate's level sizes)
+    if (lv.rows[0] == 0 || lv.cols[0] == 0) return RTDD_OK;
+    REQUIRE(ctx, editedPitch >= (size_t)cols * 3 && maskPitch >= (size_t)cols && codesPitch >= (size_t)lv.cols[0], "pitch smaller than a row");
+    lv.codes[0] = codes; lv.pitch[0] = codesPitch; lv.stride[0] = 0;
+    DeviceGuard g(ctx->device);
+    RTDD_TRY(pyramid_check_read(ctx, mask, edited));
+    return launch_region_codes(ctx, edited, editedPitch, 0, mask, maskPitch, 0, lv, 1);
 }
 
 // ---- image processing ---------------------------------------------------------------------------

@@ -73,6 +73,37 @@ __global__ __launch_bounds__(256) void k_pyrdown_bgr(const uint8_t *__restrict__
     o[0] = (uint8_t)((s[0] + 128) >> 8); o[1] = (uint8_t)((s[1] + 128) >> 8); o[2] = (uint8_t)((s[2] + 128) >> 8);
 }
 
+// Depth regions (include/rtdd.h rtdd_pyramid_set_regions): every level's code plane from the level-0 region pair, one launch.  The code
+// of level l at (y, x) is the level-0 code at (y << l, x << l), and the level-0 code is the label where the mask says painted, else 0
+// (unassigned) -- top-left sampling composes across levels, so no level waits for another.  The levels are the floor chain's
+// (rows_l = floor(rows / 2^l)): y <= rows_l - 1 gives (y << l) <= rows_l * 2^l - 2^l <= rows - 2^l, inside level 0.  A workgroup is one
+// 64 x 4 tile of one level: lv.first_block[i] .. lv.first_block[i + 1] - 1 are entry i's tiles, row-major; blockIdx.z = image.
+__global__ __launch_bounds__(256) void k_region_codes(const uint8_t *__restrict__ edited, size_t ep, size_t ze, const uint8_t *__restrict__ mask, size_t mp,
+                                                      size_t zm, const RegionLevels lv) {
+    int i = 0;
+    while (i + 1 < lv.n && (int)blockIdx.x >= lv.first_block[i + 1]) i++;
+    const int t = blockIdx.x - lv.first_block[i], tiles_x = (lv.cols[i] + 63) / 64;
+    const int x = (t % tiles_x) * 64 + (threadIdx.x & 63), y = (t / tiles_x) * 4 + wave_id();
+    if (x >= lv.cols[i] || y >= lv.rows[i]) return;
+    RTDD_Z(edited, ze); RTDD_Z(mask, zm);
+    const size_t sy = (size_t)y << lv.shift[i], sx = (size_t)x << lv.shift[i];
+    const uint8_t code = mask[sy * mp + sx] == 255 ? edited[sy * ep + 3 * sx] : (uint8_t)0;
+    (lv.codes[i] + (size_t)blockIdx.z * lv.stride[i])[(size_t)y * lv.pitch[i] + x] = code;
+}
+
+int launch_region_codes(rtdd_ctx *ctx, const uint8_t *edited, size_t ep, size_t ze, const uint8_t *mask, size_t mp, size_t zm, RegionLevels &lv, int images) {
+    int blocks = 0;
+    for (int i = 0; i < lv.n; i++) {
+        lv.first_block[i] = blocks;
+        blocks += ((lv.cols[i] + 63) / 64) * ((lv.rows[i] + 3) / 4);       // (an empty level: no tile)
+    }
+    lv.first_block[lv.n] = blocks;
+    if (blocks == 0) return RTDD_OK;
+    hipLaunchKernelGGL(k_region_codes, dim3(blocks, 1, images), dim3(256), 0, ctx->stream, edited, ep, ze, mask, mp, zm, lv);
+    RTDD_LAUNCH_CHECK(ctx, "k_region_codes");
+    return RTDD_OK;
+}
+
 // f32 pyrUp as src/main.cpp:272-279 calls it, with the Dirichlet re-injection of GPUConvertToFloat (src/main.cpp:281-283,
 // src/GPUImageProcessing.cu:19) fused in.  The reference uses TWO OpenCV routines: cv::cuda::pyrUp when the destination is exactly
 // twice the source (main.cpp:273), the host's cv::pyrUp with the explicit size otherwise (main.cpp:277).  Both mirror at the

@@ -29,6 +29,15 @@ struct Pyramid {
     int guide = RTDD_GUIDE_GRAY;
     std::vector<Image> color;
     bool image_set = false;               // rtdd_pyramid_set_image has been called: there is something to build the chain from
+    // Depth regions (rtdd_pyramid_set_regions): a second level-0 pair the paint calls write like the annotation's -- the label is the
+    // region id -- and one u8 code plane per level (the floor chain, like scribble[]) which k_region_codes fills from it, all levels in
+    // one launch, before the first estimate after the pair changed.  While region_flags != 0 the per-level solves apply the flags with
+    // level l's codes.  Allocated zeroed by the first non-zero request, kept from then on; a pyramid that never asks has none.
+    int region_flags = 0;
+    Image region_edited, region_mask;
+    std::vector<Image> region_code;
+    bool regions_dirty = false;           // (of ANY image of a batch: the launch covers them all)
+    bool has_regions() const { return region_mask.ptr != nullptr; }
     const Image &guide_image(int kind, int l) const { return kind != RTDD_GUIDE_BGR ? gray[l] : l == 0 ? original : color[l]; }
     // The coarse annotation levels and the coarsest level's injection depend on the annotation only (src/main.cpp:249-259;
     // GPUPyrDownAnnotation only ever adds, SURVEY A.8, and the solver never moves a Dirichlet pixel): they are brought up to date
@@ -159,6 +168,13 @@ int pyramid_note_write(rtdd_ctx *ctx, const void *scribble, const void *edited, 
     Pyramid *p = ctx->pyr;
     if (!p) return RTDD_OK;
     if (stale_live_pointer(p, scribble) || stale_live_pointer(p, edited)) return fail(ctx, RTDD_ERR_STATE, kStaleText);
+    // the pyramid's own region pair: a region change -- the code planes are filled again before the next estimate that uses them; the
+    // annotation is neither marked as changed nor asked to be rebuilt (an erased region pixel is simply unassigned)
+    if (p->has_regions() && (inside(p->region_mask, scribble) || inside(p->region_edited, edited) || inside(p->region_mask, edited)
+                             || inside(p->region_edited, scribble))) {
+        p->regions_dirty = true;
+        return RTDD_OK;
+    }
     if (erases && p->levels > 0 && (inside(p->scribble[0], scribble) || inside(p->edited[0], edited))) p->annotation_rebuild = true;
     for (int l = 0; l < p->levels; l++)
         if (inside(p->scribble[l], scribble) || inside(p->edited[l], edited) || inside(p->scribble[l], edited)
@@ -186,6 +202,32 @@ static int annotation_pyramid(rtdd_ctx *ctx, Pyramid *p, bool rebuild) {
     }
     return launch_annotation_pyramid(ctx, P, sc, sp, zs, ed, ep, ze, lr, lc, (float *)p->depth[P - 1].ptr, p->depth[P - 1].pitch,
                                      p->depth[P - 1].stride, p->images, rebuild);
+}
+
+// the code planes of every level and every image of the batch from the level-0 region pair, one launch (cascade.hip)
+static int region_codes(rtdd_ctx *ctx, Pyramid *p) {
+    if (p->levels > RegionLevels::kMax) return fail(ctx, RTDD_ERR_INVALID, "more than 12 pyramid levels");
+    DeviceGuard g(ctx->device);
+    RegionLevels lv{};
+    lv.n = p->levels;
+    for (int l = 0; l < p->levels; l++) {
+        const Image &im = p->region_code[l];
+        lv.codes[l] = (uint8_t *)im.ptr; lv.pitch[l] = im.pitch; lv.stride[l] = im.stride; lv.rows[l] = im.rows; lv.cols[l] = im.cols; lv.shift[l] = l;
+    }
+    return launch_region_codes(ctx, (const uint8_t *)p->region_edited.ptr, p->region_edited.pitch, p->region_edited.stride,
+                               (const uint8_t *)p->region_mask.ptr, p->region_mask.pitch, p->region_mask.stride, lv, p->images);
+}
+// in front of an estimate or a refinement: what the solves are to apply (0: nothing), the code planes brought up to date for it
+static int regions_for_solve(rtdd_ctx *ctx, Pyramid *p, int *flags) {
+    *flags = p->region_flags;
+    if (p->region_flags == 0 || !p->regions_dirty) return RTDD_OK;
+    // the planes are about to be rewritten, and a logged estimate that has to be run again reads them as they are: confirm (or heal)
+    // what is logged first, while the codes it ran on still exist
+    DeviceGuard g(ctx->device);
+    RTDD_TRY(settle_pending(ctx));
+    RTDD_TRY(region_codes(ctx, p));
+    p->regions_dirty = false;
+    return RTDD_OK;
 }
 
 static int alloc_image(rtdd_ctx *ctx, Image &im, int rows, int cols, int elem, int fill, int images = 1) {
@@ -236,8 +278,8 @@ void pyramid_free(rtdd_ctx *ctx) {
     if (!ctx->pyr) return;
     Pyramid *p = ctx->pyr;
     live_free(p);
-    free_image(p->original); free_image(p->depth_u8); free_image(p->artistic);
-    for (auto *v : {&p->gray, &p->scribble, &p->edited, &p->depth, &p->color})
+    free_image(p->original); free_image(p->depth_u8); free_image(p->artistic); free_image(p->region_edited); free_image(p->region_mask);
+    for (auto *v : {&p->gray, &p->scribble, &p->edited, &p->depth, &p->color, &p->region_code})
         for (auto &im : *v) free_image(im);
     delete p;
     ctx->pyr = nullptr;
@@ -332,6 +374,11 @@ int rtdd_pyramid_set_image(rtdd_ctx *ctx, const uint8_t *bgr, size_t pitch) {
     // over to the next one -- the depth pyramid it warm-starts from (:136) and the coarse annotation levels, which
     // GPUPyrDownAnnotation only ever adds to -- goes back to its initial state.
     p->annotation_dirty = true;
+    if (p->has_regions()) {                        // ... and the image's regions: every pixel unassigned again
+        RTDD_HIP(ctx, hipMemsetAsync(p->region_mask.at(b), 0, p->region_mask.stride, ctx->stream));
+        RTDD_HIP(ctx, hipMemsetAsync(p->region_edited.at(b), 0, p->region_edited.stride, ctx->stream));
+        p->regions_dirty = true;
+    }
     for (int l = 0; l < p->levels; l++) {
         if (p->scribble[l].ptr) RTDD_HIP(ctx,
             hipMemsetAsync(p->scribble[l].at(b), 0, p->scribble[l].pitch * p->scribble[l].rows, ctx->stream));
@@ -383,6 +430,42 @@ int rtdd_pyramid_set_guide(rtdd_ctx *ctx, int guideKind) {
     return RTDD_OK;
 }
 
+int rtdd_pyramid_regions(rtdd_ctx *ctx) { return ctx && ctx->pyr ? ctx->pyr->region_flags : 0; }
+
+int rtdd_pyramid_set_regions(rtdd_ctx *ctx, int flags) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    if (!ctx->pyr) return fail(ctx, RTDD_ERR_STATE, "rtdd_pyramid_create has not been called");
+    Pyramid *p = ctx->pyr;
+    REQUIRE(ctx, (flags & ~(RTDD_REGION_CUT | RTDD_REGION_SMOOTH)) == 0, "unknown region flag");
+    if (flags == 0 || p->has_regions()) { p->region_flags = flags; return RTDD_OK; }       // (0 keeps the images: a host toggles)
+    DeviceGuard g(ctx->device);
+    // the first request: the level-0 pair and every level's codes, zeroed, per image of a batch -- or none of them
+    Image ed, mk;
+    std::vector<Image> code(p->levels);
+    int rc = alloc_image(ctx, ed, p->rows, p->cols, 3, 0, p->images);
+    if (rc == RTDD_OK) rc = alloc_image(ctx, mk, p->rows, p->cols, 1, 0, p->images);
+    for (int l = 0; l < p->levels && rc == RTDD_OK; l++) rc = alloc_image(ctx, code[l], p->scribble[l].rows, p->scribble[l].cols, 1, 0, p->images);
+    if (rc != RTDD_OK) {
+        // (alloc_image reports every HIP error alike; the last one says whether the device ran out of memory)
+        const bool nomem = hipGetLastError() == hipErrorOutOfMemory;
+        free_image(ed); free_image(mk);
+        for (auto &im : code) free_image(im);
+        return nomem ? fail(ctx, RTDD_ERR_NOMEM, "hipMalloc(region images)", hipErrorOutOfMemory) : rc;
+    }
+    p->region_edited = ed; p->region_mask = mk; p->region_code.swap(code);
+    p->regions_dirty = false;                       // (all zero: the codes of an all-unassigned pair)
+    p->region_flags = flags;
+    return RTDD_OK;
+}
+
+int rtdd_pyramid_regions_changed(rtdd_ctx *ctx) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    if (!ctx->pyr) return fail(ctx, RTDD_ERR_STATE, "rtdd_pyramid_create has not been called");
+    if (!ctx->pyr->has_regions()) return fail(ctx, RTDD_ERR_STATE, "the pyramid has no regions: rtdd_pyramid_set_regions first");
+    ctx->pyr->regions_dirty = true;
+    return RTDD_OK;
+}
+
 int rtdd_pyramid_set_annotation(rtdd_ctx *ctx, const uint8_t *annotation, size_t pitch) {
     if (!ctx) return RTDD_ERR_INVALID;
     if (!ctx->pyr) return fail(ctx, RTDD_ERR_STATE, "rtdd_pyramid_create has not been called");
@@ -412,6 +495,10 @@ int rtdd_pyramid_image(rtdd_ctx *ctx, int kind, int level, void **ptr, size_t *p
         case RTDD_IMG_GUIDE_BGR:
             if (level > 0 && p->color.empty()) return fail(ctx, RTDD_ERR_STATE, "the colour guide's coarse levels do not exist: rtdd_pyramid_set_guide(RTDD_GUIDE_BGR) first");
             im = level == 0 ? &p->original : &p->color[level];
+            break;
+        case RTDD_IMG_REGION_EDITED: case RTDD_IMG_REGION_MASK: case RTDD_IMG_REGION_CODE:
+            if (!p->has_regions()) return fail(ctx, RTDD_ERR_STATE, "the pyramid has no regions: rtdd_pyramid_set_regions first");
+            im = kind == RTDD_IMG_REGION_CODE ? &p->region_code[level] : level != 0 ? nullptr : kind == RTDD_IMG_REGION_EDITED ? &p->region_edited : &p->region_mask;
             break;
         default: break;
     }
@@ -467,7 +554,8 @@ static int estimate_submit(rtdd_ctx *ctx, int maxIterations, unsigned long long 
     PendingOp::Estimate &e = op.estimate;
     e.annotation = annotation; e.maxIterations = maxIterations;
     e.batch_first = first; e.batch_n = n; e.live = live; e.guide = p->guide;
-    rc = estimate_levels(ctx, maxIterations, P - 1, e.level_seq, first, n, live, e.guide);
+    if ((rc = regions_for_solve(ctx, p, &e.regionFlags)) != RTDD_OK) return rc;
+    rc = estimate_levels(ctx, maxIterations, P - 1, e.level_seq, first, n, live, e.guide, e.regionFlags);
     if (rc == RTDD_OK && live.effect) rc = live_effect(ctx, live);      // src/main.cpp:190-230: the sticky effect, on this frame's map
     if (rc == RTDD_OK && log_call(ctx, op) && op_id) *op_id = op.id;
     return rc;
@@ -726,12 +814,13 @@ int rtdd_live_submit_ex(rtdd_ctx *ctx, const uint8_t *hostScribble, size_t scrib
 
 namespace rtdd {
 
-int estimate_levels(rtdd_ctx *ctx, int maxIterations, int from_level, int *level_seq, int first, int n, const LiveTargets &live, int guide) {
+int estimate_levels(rtdd_ctx *ctx, int maxIterations, int from_level, int *level_seq, int first, int n, const LiveTargets &live, int guide, int regionFlags) {
     Pyramid *p = ctx->pyr;
     if (!p) return fail(ctx, RTDD_ERR_STATE, "the pyramid is gone");
     if (first < 0 || n < 1 || first + n > p->images) return fail(ctx, RTDD_ERR_INVALID, "images outside the pyramid's batch");
     const int P = p->levels;
     if (guide == RTDD_GUIDE_BGR && P > 1 && p->color.empty()) return fail(ctx, RTDD_ERR_STATE, "the colour guide's levels are gone");
+    if (regionFlags != 0 && !p->has_regions()) return fail(ctx, RTDD_ERR_STATE, "the region codes are gone");
     if (from_level > P - 1) from_level = P - 1;
     int rc = RTDD_OK;
     for (int l = from_level; l >= 0 && rc == RTDD_OK; l--) {                   // src/main.cpp:261-288
@@ -759,9 +848,15 @@ int estimate_levels(rtdd_ctx *ctx, int maxIterations, int from_level, int *level
             rtdd_solve_params sp;
             sp.method = RTDD_METHOD_CHEBYSHEV_JACOBI; sp.maxIterations = iters; sp.tolerance = 0.0f; sp.checkEvery = 0;
             sp.relaxation = 0.0f;
-            rc = solve_with(ctx, {(float *)p->depth[l].at(first), p->depth[l].pitch, (const uint8_t *)p->scribble[l].at(first),
-                                  p->scribble[l].pitch, (const uint8_t *)gd.at(first), gd.pitch, guide, p->depth[l].rows,
-                                  p->depth[l].cols, l, sp, t}, nullptr, &done);
+            SolveCall c{(float *)p->depth[l].at(first), p->depth[l].pitch, (const uint8_t *)p->scribble[l].at(first),
+                        p->scribble[l].pitch, (const uint8_t *)gd.at(first), gd.pitch, guide, p->depth[l].rows,
+                        p->depth[l].cols, l, sp, t};
+            if (regionFlags != 0) {                                              // level l's codes, a batch's `stride` apart
+                const Image &rg = p->region_code[l];
+                c.regions = (const uint8_t *)rg.at(first); c.regionsPitch = rg.pitch; c.regionFlags = regionFlags;
+                c.targets.batch.regions = rg.stride;
+            }
+            rc = solve_with(ctx, c, nullptr, &done);
             if (level_seq && l < 32) level_seq[l] = done.seq;
             if (rc == RTDD_OK) {
                 p->level_info[l] = ctx->last_info; p->level_launch_images[l] = ctx->last_launch_images;
@@ -829,7 +924,7 @@ int estimate_replay(rtdd_ctx *ctx, const PendingOp::Estimate &e, int failed_seq)
         RTDD_TRY(annotation_pyramid(ctx, p, e.annotation == PendingOp::kAnnotationRebuilt));
         ctx->heal_rebuilt = true;
     }
-    int rc = from >= 0 ? estimate_levels(ctx, e.maxIterations, from, nullptr, e.batch_first, e.batch_n, e.live, e.guide) : RTDD_OK;
+    int rc = from >= 0 ? estimate_levels(ctx, e.maxIterations, from, nullptr, e.batch_first, e.batch_n, e.live, e.guide, e.regionFlags) : RTDD_OK;
     if (rc == RTDD_OK && e.live.effect) rc = live_effect(ctx, e.live);
     return rc;
 }
@@ -851,8 +946,12 @@ int rtdd_refine_depth(rtdd_ctx *ctx, const rtdd_solve_params *params, rtdd_solve
     t.u8 = (uint8_t *)p->depth_u8.at(b); t.u8_pitch = p->depth_u8.pitch;
     t.batch.first = b;
     const Image &gd = p->guide_image(p->guide, 0);
-    return solve_with(ctx, {(float *)p->depth[0].at(b), p->depth[0].pitch, (const uint8_t *)p->scribble[0].at(b), p->scribble[0].pitch,
-                            (const uint8_t *)gd.at(b), gd.pitch, p->guide, p->rows, p->cols, 0, *params, t}, info, nullptr);
+    SolveCall c{(float *)p->depth[0].at(b), p->depth[0].pitch, (const uint8_t *)p->scribble[0].at(b), p->scribble[0].pitch,
+                (const uint8_t *)gd.at(b), gd.pitch, p->guide, p->rows, p->cols, 0, *params, t};
+    int flags = 0;
+    RTDD_TRY(regions_for_solve(ctx, p, &flags));
+    if (flags != 0) { c.regions = (const uint8_t *)p->region_code[0].at(b); c.regionsPitch = p->region_code[0].pitch; c.regionFlags = flags; }
+    return solve_with(ctx, c, info, nullptr);
 }
 
 int rtdd_bgr2gray(rtdd_ctx *ctx, const uint8_t *bgr, size_t bgrPitch, uint8_t *gray, size_t grayPitch, int rows, int cols) {

@@ -57,6 +57,7 @@ struct Batch {
     int n = 1;                            // images per launch
     int first = 0;                        // the first one's index in the context's batched allocations
     size_t depth = 0, scribble = 0, gray = 0, u8 = 0;     // byte strides of the caller-side arguments of the solve in progress (gray: the guide's, gray or colour)
+    size_t regions = 0;                   // ... and of its region codes (SolveCall::regions)
 };
 #define RTDD_Z(ptr, stride) ptr = (decltype(ptr))((const char *)(ptr) + (size_t)blockIdx.z * (size_t)(stride))
 
@@ -83,6 +84,10 @@ struct SolveCall {
     int rows = 0, cols = 0, level = 0;
     rtdd_solve_params params{};
     SolveTargets targets;                           // (rtdd_refine_depth: the selected image of a batch, the u8 copy of the result)
+    // depth regions (rtdd_solve_regions): one u8 code per pixel and rtdd_region_flags.  regionFlags == 0: no regions -- `regions` is
+    // null, nothing of them is launched, the call is rtdd_solve_guided.  Part of the record, so a replay runs a region solve with regions
+    const uint8_t *regions = nullptr; size_t regionsPitch = 0;
+    int regionFlags = 0;
 };
 // A live frame's own images (cascade_api.cpp): the level-0 annotation pair its estimate ran on, the second target of its u8 map
 // (u8_pitch 0: a staging slot with the pyramid's pitch), and the sticky depth effect behind it (src/main.cpp:190-230) with its target.
@@ -193,6 +198,7 @@ struct PendingOp {
         int level_seq[32] = {};           // sequence number of level l's solve (0: the level is empty)
         int batch_first = 0, batch_n = 1; // the images of the context's batched pyramid the estimate covers
         int guide = RTDD_GUIDE_GRAY;      // the guide the estimate ran with (rtdd_pyramid_set_guide): a replay uses it, not the pyramid's current one
+        int regionFlags = 0;              // ... and the rtdd_region_flags (rtdd_pyramid_set_regions): likewise; the code planes are read as they are
         LiveTargets live;                 // a live frame: its annotation pair, its map's second target, its effect (scribble == nullptr: not one)
         // what the estimate did to the coarse annotation levels in front of its solves: kAnnotationNone (they were up to date),
         // kAnnotationAccumulated (GPUPyrDownAnnotation: only ever adds) or kAnnotationRebuilt (as if they had been all zero).  A replay
@@ -347,8 +353,10 @@ int launch_sweeps_blocked(rtdd_ctx *ctx, const Level &L, size_t ip, int rows, in
 // the first of them to find it set records ctx->guard_seq in sync_words[kSyncFailedSeq])
 // (seq: the solve's sequence number, reported by the kernel either as confirmed or as the first failed one; c.targets: the batch and the u8 targets)
 int launch_finish(rtdd_ctx *ctx, const Level &L, size_t ip, int src_plane, const SolveCall &c, int seq);
+// (regionFlags != 0: the rule of rtdd_solve_regions on top, from the code image `regions`)
 int launch_index_to_weight(rtdd_ctx *ctx, const uint8_t *gray, size_t grayPitch, const float *depth, size_t depthPitch,
-                           int32_t *index2, int level, int rows, int cols, int guide = RTDD_GUIDE_GRAY);
+                           int32_t *index2, int level, int rows, int cols, int guide = RTDD_GUIDE_GRAY,
+                           const uint8_t *regions = nullptr, size_t regionsPitch = 0, int regionFlags = 0);
 int launch_residual(rtdd_ctx *ctx, const Level &L, size_t ip, int plane, int rows, int cols, float *host_out);
 int launch_rbgs(rtdd_ctx *ctx, const Level &L, size_t ip, int plane, int rows, int cols, int nsweeps, float omega);
 // ---- multigrid.hip ------------------------------------------------------------------------------
@@ -423,9 +431,19 @@ int launch_depth_to_u8(rtdd_ctx *ctx, const float *src, size_t sp, uint8_t *dst,
 int launch_decode_annotation(rtdd_ctx *ctx, const uint8_t *bgr, size_t bp, const uint8_t *ann, size_t ap, uint8_t *edited, size_t ep,
                              uint8_t *scribble, size_t sp, int rows, int cols);
 int launch_fill_f32(rtdd_ctx *ctx, float *dst, size_t dp, int rows, int cols, float v);
+// k_region_codes: the code planes of `n` pyramid levels from one level-0 region pair (edited u8x3, mask u8), one launch over `images`
+// images.  Entry i is level shift[i] of the floor chain: rows[i] x cols[i] codes, code (y, x) read at (y << shift, x << shift)
+struct RegionLevels {
+    static constexpr int kMax = 12;
+    int n = 0;
+    uint8_t *codes[kMax]; size_t pitch[kMax], stride[kMax];
+    int rows[kMax], cols[kMax], shift[kMax], first_block[kMax + 1];
+};
+int launch_region_codes(rtdd_ctx *ctx, const uint8_t *edited, size_t ep, size_t ze, const uint8_t *mask, size_t mp, size_t zm, RegionLevels &lv, int images);
 void pyramid_free(rtdd_ctx *ctx);
 // an annotation image is about to be written: one of the pyramid's?  RTDD_ERR_STATE for a level-0 pointer a live frame has retired
 // (erases: labels were REMOVED -- when the images are the pyramid's level-0 pair the next estimate rebuilds the coarse levels)
+// (the pyramid's own REGION pair, rtdd_pyramid_set_regions: a region change is noted instead, the annotation's state is left alone)
 int pyramid_note_write(rtdd_ctx *ctx, const void *scribble, const void *edited, bool erases = false);
 int pyramid_check_read(rtdd_ctx *ctx, const void *a, const void *b);     // ... about to be read
 
@@ -440,7 +458,7 @@ int settle_pending(rtdd_ctx *ctx);      // before a call changes what the logged
 // the one place a call enters the log: kind, opt and the kind's record filled in by the caller, id assigned here; false: not logged
 bool log_call(rtdd_ctx *ctx, PendingOp &op);
 // cascade_api.cpp: levels from_level .. 0 of an estimate (src/main.cpp:261-291); level_seq (optional) receives each level's solve sequence number
-int estimate_levels(rtdd_ctx *ctx, int maxIterations, int from_level, int *level_seq, int first, int n, const LiveTargets &live, int guide);
+int estimate_levels(rtdd_ctx *ctx, int maxIterations, int from_level, int *level_seq, int first, int n, const LiveTargets &live, int guide, int regionFlags);
 // api.cpp: rtdd_solve_ex with everything the library's own callers add to it (c.targets)
 int solve_with(rtdd_ctx *ctx, const SolveCall &c, rtdd_solve_info *info, SolveOutcome *out);
 // cascade_api.cpp: a live frame's effect (again, on a replay): RTDD_EFFECT_* on the pyramid's level-0 images into live.artistic

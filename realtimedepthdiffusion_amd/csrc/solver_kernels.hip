@@ -33,15 +33,36 @@ __device__ __forceinline__ int sat_u8_dev(float v) {
 __device__ __forceinline__ int iabs(int a) { return a < 0 ? -a : a; }
 
 // ------------------------------------------------------------------------------------------------
+// Depth regions (extension, include/rtdd.h rtdd_solve_regions): one u8 code per pixel, 0 = unassigned.  The rule works on the index `i`
+// an edge has AFTER the guide and the depth gate have made it: a cut edge gets index 255, an edge inside one assigned region index 0.
+// The sweeps read only the 8-bit indices of the meta word, so the prepare pass (and the index pass of the parity tests) is all there is
+// to it: each body below carries the rule behind a compile-time switch, REGIONS, and is instantiated twice -- as the kernel it has
+// always been (the code image is never looked at; the device code is what it was) and as its _regions variant, which reads one byte
+// more per pixel: the pixel's code, from which the right neighbour's and the one's below come with the rows the body reads anyway.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int region_index(int i, int rp, int rq, int flags) {
+    if ((flags & RTDD_REGION_CUT) && rp != rq) return 255;
+    if ((flags & RTDD_REGION_SMOOTH) && rp == rq && rp != 0) return 0;
+    return i;
+}
+// the prepare kernels' parameters (g, gp, zg: the guide, its pitch and its batch stride under the body's own names) ...
+#define RTDD_PREPARE_PARAMS(g, gp, zg)                                                                                                      \
+    const float *__restrict__ depth, size_t depthPitch, const uint8_t *__restrict__ scribble, size_t scribblePitch,                         \
+    const uint8_t *__restrict__ g, size_t gp, float *__restrict__ X0, float *__restrict__ X1, uint32_t *__restrict__ M, int ip, int rows,    \
+    int cols, int gated, int thr, size_t zDepth, size_t zScribble, size_t zg, size_t zPlane, int *sync_words, int wild_seq
+#define RTDD_PREPARE_ARGS(g, gp, zg) \
+    depth, depthPitch, scribble, scribblePitch, g, gp, X0, X1, M, ip, rows, cols, gated, thr, zDepth, zScribble, zg, zPlane, sync_words, wild_seq
+// ... and what a _regions variant takes behind them: the code image, the byte stride between a batch's code images, rtdd_region_flags
+#define RTDD_REGION_PARAMS const uint8_t *__restrict__ codes, size_t codesPitch, size_t zCodes, int regionFlags
+#define RTDD_REGION_ARGS codes, codesPitch, zCodes, regionFlags
+#define RTDD_NO_REGIONS nullptr, 0, 0, 0
+
+// ------------------------------------------------------------------------------------------------
 // k_prepare: edge-weight indices (src/GPUSolver.cu:183-222) + staging (:290-292), fused.
 // gated = (level != maxLevel); thr = (level == 0) ? 0 : 4   (:201-202)
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_prepare(const float *__restrict__ depth, size_t depthPitch,
-                                                 const uint8_t *__restrict__ scribble, size_t scribblePitch,
-                                                 const uint8_t *__restrict__ gray, size_t grayPitch,
-                                                 float *__restrict__ X0, float *__restrict__ X1,
-                                                 uint32_t *__restrict__ M, int ip, int rows, int cols, int gated, int thr,
-                                                 size_t zDepth, size_t zScribble, size_t zGray, size_t zPlane, int *sync_words, int wild_seq) {
+template <bool REGIONS>
+__device__ __forceinline__ void prepare_px(RTDD_PREPARE_PARAMS(gray, grayPitch, zGray), RTDD_REGION_PARAMS) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     const int y = blockIdx.y * 4 + wave_id();
     if (x >= cols || y >= rows) return;
@@ -51,10 +72,13 @@ __global__ __launch_bounds__(256) void k_prepare(const float *__restrict__ depth
     const float d = drow[x];
     const int g = grow[x];
     const bool dirichlet = scribble[(size_t)y * scribblePitch + x] == 255;
+    const uint8_t *rrow = nullptr;                 // REGIONS: the row of codes
+    if (REGIONS) { RTDD_Z(codes, zCodes); rrow = codes + (size_t)y * codesPitch; }
     int right = 0, down = 0;
     if (x + 1 < cols) {
         right = iabs(g - (int)grow[x + 1]);
         if (gated && !(iabs(sat_u8_dev(d) - sat_u8_dev(drow[x + 1])) > thr)) right = 0;
+        if (REGIONS) right = region_index(right, rrow[x], rrow[x + 1], regionFlags);
     }
     if (y + 1 < rows) {
         down = iabs(g - (int)grow[x + grayPitch]);
@@ -62,6 +86,7 @@ __global__ __launch_bounds__(256) void k_prepare(const float *__restrict__ depth
             const float dd = ((const float *)((const char *)depth + (size_t)(y + 1) * depthPitch))[x];
             if (!(iabs(sat_u8_dev(d) - sat_u8_dev(dd)) > thr)) down = 0;
         }
+        if (REGIONS) down = region_index(down, rrow[x], rrow[x + codesPitch], regionFlags);
     }
     const size_t p = (size_t)y * ip + x;
     if (depth_is_wild(d)) sync_words[kSyncWild] = wild_seq;      // (persist_sync.hpp: the blocked sweeps then take their full-divide variant)
@@ -69,16 +94,43 @@ __global__ __launch_bounds__(256) void k_prepare(const float *__restrict__ depth
     X1[p] = dirichlet ? d : 0.0f;     // x_{-1} = 0 on free pixels (cudaMemset, :290); Dirichlet value in both planes (:291-292)
     M[p] = (uint32_t)right | ((uint32_t)down << 8) | (dirichlet ? kMetaDirichlet : 0u);
 }
+__global__ __launch_bounds__(256) void k_prepare(RTDD_PREPARE_PARAMS(gray, grayPitch, zGray)) {
+    prepare_px<false>(RTDD_PREPARE_ARGS(gray, grayPitch, zGray), RTDD_NO_REGIONS);
+}
+__global__ __launch_bounds__(256) void k_prepare_regions(RTDD_PREPARE_PARAMS(gray, grayPitch, zGray), RTDD_REGION_PARAMS) {
+    prepare_px<true>(RTDD_PREPARE_ARGS(gray, grayPitch, zGray), RTDD_REGION_ARGS);
+}
 
 // The same pass, four pixels per thread, for callers whose rows are 16-byte (depth) / 4-byte (gray, scribble) aligned -- what
 // cudaMallocPitch-style allocations give: one 16-byte load per depth row, one 4-byte load per u8 row, 16-byte stores of the three
 // planes.  A group that would run past the end of a row falls back to the scalar form above, pixel by pixel.
-__global__ __launch_bounds__(256) void k_prepare4(const float *__restrict__ depth, size_t depthPitch,
-                                                  const uint8_t *__restrict__ scribble, size_t scribblePitch,
-                                                  const uint8_t *__restrict__ gray, size_t grayPitch,
-                                                  float *__restrict__ X0, float *__restrict__ X1,
-                                                  uint32_t *__restrict__ M, int ip, int rows, int cols, int gated, int thr,
-                                                  size_t zDepth, size_t zScribble, size_t zGray, size_t zPlane, int *sync_words, int wild_seq) {
+// REGIONS: the four codes are one dword more of each of the two rows (the code image under the gray guide's alignment rule), the ragged
+// end and the right neighbour byte by byte like the guide's.
+// rc[i], rd[i]: the codes of pixel x0 + i (i = 4: the right neighbour of the group) and of the pixel below it, 0 outside the image
+struct RegionCodes4 { int rc[5], rd[4]; };
+template <bool REGIONS>
+__device__ __forceinline__ void load_codes4(RegionCodes4 &r, const uint8_t *rrow, size_t codesPitch, int x0, int cols, bool down_ok) {
+    if (!REGIONS) return;
+    if (x0 + 3 < cols) {
+        const uint32_t c4 = *(const uint32_t *)(rrow + x0);
+        r.rc[0] = c4 & 255; r.rc[1] = (c4 >> 8) & 255; r.rc[2] = (c4 >> 16) & 255; r.rc[3] = c4 >> 24;
+        if (down_ok) {
+            const uint32_t e4 = *(const uint32_t *)(rrow + codesPitch + x0);
+            r.rd[0] = e4 & 255; r.rd[1] = (e4 >> 8) & 255; r.rd[2] = (e4 >> 16) & 255; r.rd[3] = e4 >> 24;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const bool in = x0 + i < cols;
+            r.rc[i] = in ? rrow[x0 + i] : 0;
+            r.rd[i] = in && down_ok ? rrow[x0 + i + codesPitch] : 0;
+        }
+    }
+    r.rc[4] = x0 + 4 < cols ? rrow[x0 + 4] : 0;
+}
+
+template <bool REGIONS>
+__device__ __forceinline__ void prepare4_px(RTDD_PREPARE_PARAMS(gray, grayPitch, zGray), RTDD_REGION_PARAMS) {
     const int x0 = 4 * (blockIdx.x * 64 + (threadIdx.x & 63));
     const int y = blockIdx.y * 4 + wave_id();
     if (x0 >= cols || y >= rows) return;
@@ -89,6 +141,8 @@ __global__ __launch_bounds__(256) void k_prepare4(const float *__restrict__ dept
     float d[5], dd[4];
     int g[5], gd[4];
     uint32_t sc;
+    RegionCodes4 rg;
+    if (REGIONS) { RTDD_Z(codes, zCodes); load_codes4<REGIONS>(rg, codes + (size_t)y * codesPitch, codesPitch, x0, cols, down_ok); }
     if (x0 + 3 < cols) {
         const float4 d4 = *(const float4 *)(drow + x0);
         d[0] = d4.x; d[1] = d4.y; d[2] = d4.z; d[3] = d4.w;
@@ -122,10 +176,12 @@ __global__ __launch_bounds__(256) void k_prepare4(const float *__restrict__ dept
         if (x0 + i + 1 < cols) {
             right = iabs(g[i] - g[i + 1]);
             if (gated && !(iabs(sat_u8_dev(d[i]) - sat_u8_dev(d[i + 1])) > thr)) right = 0;
+            if (REGIONS) right = region_index(right, rg.rc[i], rg.rc[i + 1], regionFlags);
         }
         if (down_ok) {
             down = iabs(g[i] - gd[i]);
             if (gated && !(iabs(sat_u8_dev(d[i]) - sat_u8_dev(dd[i])) > thr)) down = 0;
+            if (REGIONS) down = region_index(down, rg.rc[i], rg.rd[i], regionFlags);
         }
         x0v[i] = d[i];
         x1v[i] = dirichlet ? d[i] : 0.0f;
@@ -138,11 +194,28 @@ __global__ __launch_bounds__(256) void k_prepare4(const float *__restrict__ dept
     *(float4 *)(X1 + p) = make_float4(x1v[0], x1v[1], x1v[2], x1v[3]);
     *(uint4 *)(M + p) = make_uint4(mv[0], mv[1], mv[2], mv[3]);
 }
+__global__ __launch_bounds__(256) void k_prepare4(RTDD_PREPARE_PARAMS(gray, grayPitch, zGray)) {
+    prepare4_px<false>(RTDD_PREPARE_ARGS(gray, grayPitch, zGray), RTDD_NO_REGIONS);
+}
+__global__ __launch_bounds__(256) void k_prepare4_regions(RTDD_PREPARE_PARAMS(gray, grayPitch, zGray), RTDD_REGION_PARAMS) {
+    prepare4_px<true>(RTDD_PREPARE_ARGS(gray, grayPitch, zGray), RTDD_REGION_ARGS);
+}
 
 // The reference's own index format, for parity tests of the weight pass (src/GPUSolver.cu:136-224).
+// REGIONS: the rule of region_index on every edge inside the image, behind the gate; outside the image the index stays 256.  The two
+// index-pass kernels are templates themselves, k_index_to_weight<false> being the kernel that was (its last argument is then empty):
+// as a body inlined into two thin kernels, like the prepare passes above, the compiler ordered a few scalar compares differently.
+template <bool REGIONS> struct RegionImage {};
+template <> struct RegionImage<true> { const uint8_t *codes; size_t pitch; int flags; };
+__device__ __forceinline__ int region_index(int i, int x, int y, int nx, int ny, const RegionImage<true> &rg) {
+    return region_index(i, rg.codes[(size_t)y * rg.pitch + x], rg.codes[(size_t)ny * rg.pitch + nx], rg.flags);
+}
+__device__ __forceinline__ int region_index(int i, int, int, int, int, const RegionImage<false> &) { return i; }
+
+template <bool REGIONS>
 __global__ __launch_bounds__(256) void k_index_to_weight(const uint8_t *__restrict__ gray, size_t grayPitch,
                                                          const float *__restrict__ depth, size_t depthPitch,
-                                                         int32_t *__restrict__ index2, int rows, int cols, int gated, int thr) {
+                                                         int32_t *__restrict__ index2, int rows, int cols, int gated, int thr, const RegionImage<REGIONS> rg) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     const int y = blockIdx.y * 4 + wave_id();
     if (x >= cols || y >= rows) return;
@@ -160,6 +233,7 @@ __global__ __launch_bounds__(256) void k_index_to_weight(const uint8_t *__restri
             const float nd = ((const float *)((const char *)depth + (size_t)ny * depthPitch))[nx];
             if (!(iabs(d - sat_u8_dev(nd)) > thr)) v = 0;
         }
+        if (REGIONS) v = region_index(v, x, y, nx, ny, rg);
         idx[k] = v;
     }
     const size_t p = (size_t)y * cols + x;
@@ -178,12 +252,8 @@ __device__ __forceinline__ int bgr_index(int p, int q) {
     return max(max(db, dg), dr);
 }
 
-__global__ __launch_bounds__(256) void k_prepare_bgr(const float *__restrict__ depth, size_t depthPitch,
-                                                     const uint8_t *__restrict__ scribble, size_t scribblePitch,
-                                                     const uint8_t *__restrict__ bgr, size_t bgrPitch,
-                                                     float *__restrict__ X0, float *__restrict__ X1,
-                                                     uint32_t *__restrict__ M, int ip, int rows, int cols, int gated, int thr,
-                                                     size_t zDepth, size_t zScribble, size_t zBgr, size_t zPlane, int *sync_words, int wild_seq) {
+template <bool REGIONS>
+__device__ __forceinline__ void prepare_bgr_px(RTDD_PREPARE_PARAMS(bgr, bgrPitch, zBgr), RTDD_REGION_PARAMS) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     const int y = blockIdx.y * 4 + wave_id();
     if (x >= cols || y >= rows) return;
@@ -193,10 +263,13 @@ __global__ __launch_bounds__(256) void k_prepare_bgr(const float *__restrict__ d
     const float d = drow[x];
     const int c = bgr_at(crow);
     const bool dirichlet = scribble[(size_t)y * scribblePitch + x] == 255;
+    const uint8_t *rrow = nullptr;
+    if (REGIONS) { RTDD_Z(codes, zCodes); rrow = codes + (size_t)y * codesPitch; }
     int right = 0, down = 0;
     if (x + 1 < cols) {
         right = bgr_index(c, bgr_at(crow + 3));
         if (gated && !(iabs(sat_u8_dev(d) - sat_u8_dev(drow[x + 1])) > thr)) right = 0;
+        if (REGIONS) right = region_index(right, rrow[x], rrow[x + 1], regionFlags);
     }
     if (y + 1 < rows) {
         down = bgr_index(c, bgr_at(crow + bgrPitch));
@@ -204,12 +277,19 @@ __global__ __launch_bounds__(256) void k_prepare_bgr(const float *__restrict__ d
             const float dd = ((const float *)((const char *)depth + (size_t)(y + 1) * depthPitch))[x];
             if (!(iabs(sat_u8_dev(d) - sat_u8_dev(dd)) > thr)) down = 0;
         }
+        if (REGIONS) down = region_index(down, rrow[x], rrow[x + codesPitch], regionFlags);
     }
     const size_t p = (size_t)y * ip + x;
     if (depth_is_wild(d)) sync_words[kSyncWild] = wild_seq;
     X0[p] = d;
     X1[p] = dirichlet ? d : 0.0f;
     M[p] = (uint32_t)right | ((uint32_t)down << 8) | (dirichlet ? kMetaDirichlet : 0u);
+}
+__global__ __launch_bounds__(256) void k_prepare_bgr(RTDD_PREPARE_PARAMS(bgr, bgrPitch, zBgr)) {
+    prepare_bgr_px<false>(RTDD_PREPARE_ARGS(bgr, bgrPitch, zBgr), RTDD_NO_REGIONS);
+}
+__global__ __launch_bounds__(256) void k_prepare_bgr_regions(RTDD_PREPARE_PARAMS(bgr, bgrPitch, zBgr), RTDD_REGION_PARAMS) {
+    prepare_bgr_px<true>(RTDD_PREPARE_ARGS(bgr, bgrPitch, zBgr), RTDD_REGION_ARGS);
 }
 
 // Four pixels per thread, for a guide whose pointer, pitch and batch stride are multiples of 4 (depth and scribble as k_prepare4 wants
@@ -223,12 +303,8 @@ __device__ __forceinline__ void bgr_unpack4(const uint8_t *q, int (&c)[5]) {
     c[2] = (int)((w1 >> 16) | ((w2 & 0xFFu) << 16)); c[3] = (int)(w2 >> 8);
 }
 
-__global__ __launch_bounds__(256) void k_prepare4_bgr(const float *__restrict__ depth, size_t depthPitch,
-                                                      const uint8_t *__restrict__ scribble, size_t scribblePitch,
-                                                      const uint8_t *__restrict__ bgr, size_t bgrPitch,
-                                                      float *__restrict__ X0, float *__restrict__ X1,
-                                                      uint32_t *__restrict__ M, int ip, int rows, int cols, int gated, int thr,
-                                                      size_t zDepth, size_t zScribble, size_t zBgr, size_t zPlane, int *sync_words, int wild_seq) {
+template <bool REGIONS>
+__device__ __forceinline__ void prepare4_bgr_px(RTDD_PREPARE_PARAMS(bgr, bgrPitch, zBgr), RTDD_REGION_PARAMS) {
     const int x0 = 4 * (blockIdx.x * 64 + (threadIdx.x & 63));
     const int y = blockIdx.y * 4 + wave_id();
     if (x0 >= cols || y >= rows) return;
@@ -239,6 +315,8 @@ __global__ __launch_bounds__(256) void k_prepare4_bgr(const float *__restrict__ 
     float d[5], dd[4];
     int c[5], cd[5];
     uint32_t sc;
+    RegionCodes4 rg;
+    if (REGIONS) { RTDD_Z(codes, zCodes); load_codes4<REGIONS>(rg, codes + (size_t)y * codesPitch, codesPitch, x0, cols, down_ok); }
     if (x0 + 3 < cols) {
         const float4 d4 = *(const float4 *)(drow + x0);
         d[0] = d4.x; d[1] = d4.y; d[2] = d4.z; d[3] = d4.w;
@@ -271,10 +349,12 @@ __global__ __launch_bounds__(256) void k_prepare4_bgr(const float *__restrict__ 
         if (x0 + i + 1 < cols) {
             right = bgr_index(c[i], c[i + 1]);
             if (gated && !(iabs(sat_u8_dev(d[i]) - sat_u8_dev(d[i + 1])) > thr)) right = 0;
+            if (REGIONS) right = region_index(right, rg.rc[i], rg.rc[i + 1], regionFlags);
         }
         if (down_ok) {
             down = bgr_index(c[i], cd[i]);
             if (gated && !(iabs(sat_u8_dev(d[i]) - sat_u8_dev(dd[i])) > thr)) down = 0;
+            if (REGIONS) down = region_index(down, rg.rc[i], rg.rd[i], regionFlags);
         }
         x0v[i] = d[i];
         x1v[i] = dirichlet ? d[i] : 0.0f;
@@ -286,11 +366,18 @@ __global__ __launch_bounds__(256) void k_prepare4_bgr(const float *__restrict__ 
     *(float4 *)(X1 + p) = make_float4(x1v[0], x1v[1], x1v[2], x1v[3]);
     *(uint4 *)(M + p) = make_uint4(mv[0], mv[1], mv[2], mv[3]);
 }
+__global__ __launch_bounds__(256) void k_prepare4_bgr(RTDD_PREPARE_PARAMS(bgr, bgrPitch, zBgr)) {
+    prepare4_bgr_px<false>(RTDD_PREPARE_ARGS(bgr, bgrPitch, zBgr), RTDD_NO_REGIONS);
+}
+__global__ __launch_bounds__(256) void k_prepare4_bgr_regions(RTDD_PREPARE_PARAMS(bgr, bgrPitch, zBgr), RTDD_REGION_PARAMS) {
+    prepare4_bgr_px<true>(RTDD_PREPARE_ARGS(bgr, bgrPitch, zBgr), RTDD_REGION_ARGS);
+}
 
 // k_index_to_weight for a BGR guide: the reference's int2 format, for parity tests of the colour rule
+template <bool REGIONS>
 __global__ __launch_bounds__(256) void k_index_to_weight_bgr(const uint8_t *__restrict__ bgr, size_t bgrPitch,
                                                              const float *__restrict__ depth, size_t depthPitch,
-                                                             int32_t *__restrict__ index2, int rows, int cols, int gated, int thr) {
+                                                             int32_t *__restrict__ index2, int rows, int cols, int gated, int thr, const RegionImage<REGIONS> rg) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     const int y = blockIdx.y * 4 + wave_id();
     if (x >= cols || y >= rows) return;
@@ -308,6 +395,7 @@ __global__ __launch_bounds__(256) void k_index_to_weight_bgr(const uint8_t *__re
             const float nd = ((const float *)((const char *)depth + (size_t)ny * depthPitch))[nx];
             if (!(iabs(d - sat_u8_dev(nd)) > thr)) v = 0;
         }
+        if (REGIONS) v = region_index(v, x, y, nx, ny, rg);
         idx[k] = v;
     }
     const size_t p = (size_t)y * cols + x;
@@ -557,9 +645,20 @@ int launch_prepare(rtdd_ctx *ctx, const Level &L, size_t ip, const SolveCall &c)
     // (B.n = 1: one image, strides unused; L is already image B.first's view)
     const size_t zP = L.elems * sizeof(float);
     // (c.gray: the guide -- a gray image, or with RTDD_GUIDE_BGR the interleaved colour image; the alignment rule is the same)
-    const bool aligned = ((uintptr_t)c.depth % 16 == 0) && c.depthPitch % 16 == 0 && ((uintptr_t)c.gray % 4 == 0) && c.grayPitch % 4 == 0 &&
+    bool aligned = ((uintptr_t)c.depth % 16 == 0) && c.depthPitch % 16 == 0 && ((uintptr_t)c.gray % 4 == 0) && c.grayPitch % 4 == 0 &&
                          ((uintptr_t)c.scribble % 4 == 0) && c.scribblePitch % 4 == 0 && B.depth % 16 == 0 && B.gray % 4 == 0 && B.scribble % 4 == 0;
+    // (depth regions, c.regionFlags != 0: the _regions variants; the code image under the u8 guide's alignment rule)
+    const bool regions = c.regionFlags != 0;
+    if (regions) aligned = aligned && ((uintptr_t)c.regions % 4 == 0) && c.regionsPitch % 4 == 0 && B.regions % 4 == 0;
     const dim3 grid = aligned ? grid64x4(c.rows, (c.cols + 3) / 4, B.n) : grid64x4(c.rows, c.cols, B.n);
+    if (regions) {
+        auto *kernel = c.guide == RTDD_GUIDE_BGR ? (aligned ? k_prepare4_bgr_regions : k_prepare_bgr_regions) : (aligned ? k_prepare4_regions : k_prepare_regions);
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, ctx->stream, c.depth, c.depthPitch, c.scribble, c.scribblePitch,
+                           c.gray, c.grayPitch, L.P(0, ip), L.P(1, ip), L.M(ip), (int)ip, c.rows, c.cols, gated, thr, B.depth, B.scribble, B.gray, zP, ctx->sync_words, ctx->wild_seq,
+                           c.regions, c.regionsPitch, B.regions, c.regionFlags);
+        RTDD_LAUNCH_CHECK(ctx, "k_prepare_regions");
+        return RTDD_OK;
+    }
     auto *kernel = c.guide == RTDD_GUIDE_BGR ? (aligned ? k_prepare4_bgr : k_prepare_bgr) : (aligned ? k_prepare4 : k_prepare);
     hipLaunchKernelGGL(kernel, grid, dim3(256), 0, ctx->stream, c.depth, c.depthPitch, c.scribble, c.scribblePitch,
                        c.gray, c.grayPitch, L.P(0, ip), L.P(1, ip), L.M(ip), (int)ip, c.rows, c.cols, gated, thr, B.depth, B.scribble, B.gray, zP, ctx->sync_words, ctx->wild_seq);
@@ -568,11 +667,17 @@ int launch_prepare(rtdd_ctx *ctx, const Level &L, size_t ip, const SolveCall &c)
 }
 
 int launch_index_to_weight(rtdd_ctx *ctx, const uint8_t *gray, size_t grayPitch, const float *depth, size_t depthPitch,
-                           int32_t *index2, int level, int rows, int cols, int guide) {
+                           int32_t *index2, int level, int rows, int cols, int guide, const uint8_t *regions, size_t regionsPitch, int regionFlags) {
     const int gated = level != ctx->maxLevel;
     const int thr = level == 0 ? 0 : 4;
-    hipLaunchKernelGGL(guide == RTDD_GUIDE_BGR ? k_index_to_weight_bgr : k_index_to_weight, grid64x4(rows, cols), dim3(256), 0, ctx->stream, gray, grayPitch,
-                       depth, depthPitch, index2, rows, cols, gated, thr);
+    if (regionFlags != 0) {
+        hipLaunchKernelGGL(guide == RTDD_GUIDE_BGR ? k_index_to_weight_bgr<true> : k_index_to_weight<true>, grid64x4(rows, cols), dim3(256), 0, ctx->stream,
+                           gray, grayPitch, depth, depthPitch, index2, rows, cols, gated, thr, RegionImage<true>{regions, regionsPitch, regionFlags});
+        RTDD_LAUNCH_CHECK(ctx, "k_index_to_weight<regions>");
+        return RTDD_OK;
+    }
+    hipLaunchKernelGGL(guide == RTDD_GUIDE_BGR ? k_index_to_weight_bgr<false> : k_index_to_weight<false>, grid64x4(rows, cols), dim3(256), 0, ctx->stream, gray, grayPitch,
+                       depth, depthPitch, index2, rows, cols, gated, thr, RegionImage<false>{});
     RTDD_LAUNCH_CHECK(ctx, "k_index_to_weight");
     return RTDD_OK;
 }
