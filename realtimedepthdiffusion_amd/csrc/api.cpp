@@ -1,7 +1,7 @@
 // api.cpp -- the core of the extern "C" surface of librtdd.so (include/rtdd.h): context, option table, profile, rtdd_allocate /
 // rtdd_load_weights, the per-level solve driver (GPUMatrixFreeSolver, /root/reference/src/GPUSolver.cu:274-316) with the solve entry
-// points, and the image entry points' thin forwards.  The pending-call log and its replay: heal.cpp; the depth effects:
-// effects_api.cpp; the pyramid and the whole estimate: cascade_api.cpp.  Host code only; kernels live in the *.hip files.
+// points.  The pending-call log and its replay: heal.cpp; the depth effects: effects_api.cpp; the calls on images they are handed:
+// image_api.cpp; the pyramid, the whole estimate, live mode: pyramid.cpp, estimate.cpp, live.cpp.  Host code only; kernels: *.hip.
 #include <climits>
 #include <cmath>
 #include <cstring>
@@ -657,204 +657,6 @@ int rtdd_region_codes(rtdd_ctx *ctx, const uint8_t *edited, size_t editedPitch, 
     DeviceGuard g(ctx->device);
     RTDD_TRY(pyramid_check_read(ctx, mask, edited));
     return launch_region_codes(ctx, edited, editedPitch, 0, mask, maskPitch, 0, lv, 1);
-}
-
-// ---- image processing ---------------------------------------------------------------------------
-
-int rtdd_convert_to_float(rtdd_ctx *ctx, const uint8_t *src, size_t srcPitch, float *dst, size_t dstPitch,
-                          const uint8_t *mask, size_t maskPitch, int rows, int cols) {
-    if (!ctx) return RTDD_ERR_INVALID;
-    REQUIRE(ctx, src && dst && mask, "null image pointer");
-    REQUIRE(ctx, rows >= 0 && cols >= 0, "negative size");
-    REQUIRE(ctx, f32_image_aligned(dst, dstPitch), kF32AlignText);
-    if (rows == 0 || cols == 0) return RTDD_OK;
-    REQUIRE(ctx, srcPitch >= (size_t)cols * 3 && dstPitch >= (size_t)cols * 4 && maskPitch >= (size_t)cols, "pitch smaller than a row");
-    DeviceGuard g(ctx->device);
-    // (the coarsest depth image of the context's pyramid? then the next estimate injects again; stale annotation pointers: RTDD_ERR_STATE)
-    RTDD_TRY(pyramid_check_read(ctx, src, mask));
-    RTDD_TRY(pyramid_note_write(ctx, dst, dst));
-    return launch_convert(ctx, src, srcPitch, dst, dstPitch, mask, maskPitch, rows, cols);
-}
-
-int rtdd_pyrdown_annotation(rtdd_ctx *ctx, const uint8_t *prevScribble, size_t prevScribblePitch, const uint8_t *prevEdited,
-                            size_t prevEditedPitch, int previousRows, int previousCols, uint8_t *currScribble,
-                            size_t currScribblePitch, uint8_t *currEdited, size_t currEditedPitch, int currentRows, int currentCols) {
-    if (!ctx) return RTDD_ERR_INVALID;
-    REQUIRE(ctx, prevScribble && prevEdited && currScribble && currEdited, "null image pointer");
-    REQUIRE(ctx, previousRows >= 0 && previousCols >= 0 && currentRows >= 0 && currentCols >= 0, "negative size");
-    if (currentRows == 0 || currentCols == 0) return RTDD_OK;
-    REQUIRE(ctx, prevScribblePitch >= (size_t)previousCols && prevEditedPitch >= (size_t)previousCols * 3 &&
-                 currScribblePitch >= (size_t)currentCols && currEditedPitch >= (size_t)currentCols * 3, "pitch smaller than a row");
-    DeviceGuard g(ctx->device);
-    RTDD_TRY(pyramid_check_read(ctx, prevScribble, prevEdited));
-    RTDD_TRY(pyramid_note_write(ctx, currScribble, currEdited));
-    return launch_pyrdown_annotation(ctx, prevScribble, prevScribblePitch, prevEdited, prevEditedPitch, previousRows, previousCols,
-                                     currScribble, currScribblePitch, currEdited, currEditedPitch, currentRows, currentCols);
-}
-
-int rtdd_paint_image(rtdd_ctx *ctx, int x, int y, int scribbleColor, int scribbleRadius, uint8_t *edited, size_t editedPitch,
-                     uint8_t *scribble, size_t scribblePitch, int rows, int cols) {
-    if (!ctx) return RTDD_ERR_INVALID;
-    REQUIRE(ctx, edited && scribble, "null image pointer");
-    REQUIRE(ctx, rows >= 0 && cols >= 0, "negative size");
-    if (rows == 0 || cols == 0) return RTDD_OK;
-    REQUIRE(ctx, editedPitch >= (size_t)cols * 3 && scribblePitch >= (size_t)cols, "pitch smaller than a row");
-    DeviceGuard g(ctx->device);
-    RTDD_TRY(pyramid_note_write(ctx, scribble, edited));
-    return launch_paint(ctx, x, y, scribbleColor, scribbleRadius, PaintTarget{edited, editedPitch, scribble, scribblePitch, nullptr, 0, rows, cols});
-}
-
-// ---- rtdd_paint_strokes, rtdd_paint_ramp_strokes, rtdd_fill_polygon, rtdd_fill_similar: what they share ----
-// A call checks its own records first (they say whether it erases), then its target; an empty image or no record is RTDD_OK before any
-// pitch is looked at; then, with the device set, begin_paint.
-static int check_paint_target(rtdd_ctx *ctx, const PaintTarget &t, bool erases) {
-    REQUIRE(ctx, t.edited && t.scribble, "null image pointer");
-    REQUIRE(ctx, t.rows >= 0 && t.cols >= 0, "negative size");
-    REQUIRE(ctx, t.rows <= 32768 && t.cols <= 32768, "image larger than 32768 pixels in a direction");
-    REQUIRE(ctx, !erases || t.original, "an erasing stroke or fill needs the original image");
-    return RTDD_OK;
-}
-
-// The pitches, and the pyramid hears of the write: an eraser on its own level-0 pair makes the next estimate build the coarse levels,
-// which otherwise only accumulate, afresh.  Nothing goes into the pending-call log -- a paint call cannot time out, and an estimate that
-// is run again reads the images as the paint calls in front of it left them.
-static int begin_paint(rtdd_ctx *ctx, const PaintTarget &t, bool erases) {
-    REQUIRE(ctx, t.editedPitch >= (size_t)t.cols * 3 && t.scribblePitch >= (size_t)t.cols && (!erases || t.originalPitch >= (size_t)t.cols * 3),
-        "pitch smaller than a row");
-    return pyramid_note_write(ctx, t.scribble, t.edited, erases);
-}
-
-// what the stroke calls and rtdd_ramp_polyline refuse in a record's geometry
-static bool stroke_geometry_ok(int x0, int y0, int x1, int y1, int radius, int brush, const char **why) {
-    for (int v : {x0, y0, x1, y1})
-        if (v < -32768 || v > 32767) { *why = "stroke endpoint outside [-32768, 32767]"; return false; }
-    if (radius < 0 || radius > 1024) { *why = "stroke radius outside [0, 1024]"; return false; }
-    if (brush != RTDD_BRUSH_SQUARE && brush != RTDD_BRUSH_ROUND) { *why = "unknown brush"; return false; }
-    return true;
-}
-
-// ... and in the two labels of a ramp stroke or a fill
-static bool label_pair_ok(int label0, int label1, const char **why) {
-    if (label0 < RTDD_STROKE_ERASE || label0 > 255 || label1 < RTDD_STROKE_ERASE || label1 > 255) { *why = "label outside [-1, 255]"; return false; }
-    if ((label0 == RTDD_STROKE_ERASE) != (label1 == RTDD_STROKE_ERASE)) { *why = "one label of a ramp or a fill erases and the other paints"; return false; }
-    return true;
-}
-
-int rtdd_paint_strokes(rtdd_ctx *ctx, const rtdd_stroke *strokes, int count, uint8_t *edited, size_t editedPitch, uint8_t *scribble,
-                       size_t scribblePitch, const uint8_t *original, size_t originalPitch, int rows, int cols) {
-    if (!ctx) return RTDD_ERR_INVALID;
-    const PaintTarget t{edited, editedPitch, scribble, scribblePitch, original, originalPitch, rows, cols};
-    REQUIRE(ctx, count >= 0 && count <= 4096, "count outside [0, 4096]");
-    REQUIRE(ctx, strokes || count == 0, "null stroke array");
-    bool erases = false;
-    const char *why = nullptr;
-    for (int i = 0; i < count; i++) {
-        const rtdd_stroke &q = strokes[i];
-        REQUIRE(ctx, stroke_geometry_ok(q.x0, q.y0, q.x1, q.y1, q.radius, q.brush, &why), why);
-        REQUIRE(ctx, q.label >= RTDD_STROKE_ERASE && q.label <= 255, "stroke label outside [-1, 255]");
-        erases = erases || q.label == RTDD_STROKE_ERASE;
-    }
-    RTDD_TRY(check_paint_target(ctx, t, erases));
-    if (rows == 0 || cols == 0 || count == 0) return RTDD_OK;
-    DeviceGuard g(ctx->device);
-    RTDD_TRY(begin_paint(ctx, t, erases));
-    return launch_paint_strokes(ctx, strokes, count, t);
-}
-
-int rtdd_paint_ramp_strokes(rtdd_ctx *ctx, const rtdd_ramp_stroke *strokes, int count, uint8_t *edited, size_t editedPitch, uint8_t *scribble,
-                            size_t scribblePitch, const uint8_t *original, size_t originalPitch, int rows, int cols) {
-    if (!ctx) return RTDD_ERR_INVALID;
-    const PaintTarget t{edited, editedPitch, scribble, scribblePitch, original, originalPitch, rows, cols};
-    REQUIRE(ctx, count >= 0 && count <= 4096, "count outside [0, 4096]");
-    REQUIRE(ctx, strokes || count == 0, "null stroke array");
-    bool erases = false;
-    const char *why = nullptr;
-    for (int i = 0; i < count; i++) {
-        const rtdd_ramp_stroke &q = strokes[i];
-        REQUIRE(ctx, stroke_geometry_ok(q.x0, q.y0, q.x1, q.y1, q.radius, q.brush, &why), why);
-        REQUIRE(ctx, label_pair_ok(q.label0, q.label1, &why), why);
-        erases = erases || q.label0 == RTDD_STROKE_ERASE;
-    }
-    RTDD_TRY(check_paint_target(ctx, t, erases));
-    if (rows == 0 || cols == 0 || count == 0) return RTDD_OK;
-    DeviceGuard g(ctx->device);
-    RTDD_TRY(begin_paint(ctx, t, erases));
-    return launch_paint_strokes(ctx, strokes, count, t);
-}
-
-int rtdd_fill_polygon(rtdd_ctx *ctx, const int *xy, int n, const rtdd_fill *fill, uint8_t *edited, size_t editedPitch, uint8_t *scribble,
-                      size_t scribblePitch, const uint8_t *original, size_t originalPitch, int rows, int cols) {
-    if (!ctx) return RTDD_ERR_INVALID;
-    const PaintTarget t{edited, editedPitch, scribble, scribblePitch, original, originalPitch, rows, cols};
-    REQUIRE(ctx, fill, "null fill");
-    REQUIRE(ctx, n >= 0 && n <= 768, "n outside [0, 768]");
-    REQUIRE(ctx, xy || n == 0, "null vertex array");
-    REQUIRE(ctx, fill->rule == RTDD_FILL_NONZERO || fill->rule == RTDD_FILL_EVEN_ODD, "unknown fill rule");
-    for (int i = 0; i < 2 * n; i++) REQUIRE(ctx, xy[i] >= -32768 && xy[i] <= 32767, "vertex coordinate outside [-32768, 32767]");
-    for (int v : {fill->ax0, fill->ay0, fill->ax1, fill->ay1}) REQUIRE(ctx, v >= -32768 && v <= 32767, "axis coordinate outside [-32768, 32767]");
-    const char *why = nullptr;
-    REQUIRE(ctx, label_pair_ok(fill->label0, fill->label1, &why), why);
-    const bool erases = fill->label0 == RTDD_STROKE_ERASE;
-    RTDD_TRY(check_paint_target(ctx, t, erases));
-    if (rows == 0 || cols == 0 || n == 0) return RTDD_OK;
-    DeviceGuard g(ctx->device);
-    RTDD_TRY(begin_paint(ctx, t, erases));
-    return launch_fill_polygon(ctx, xy, n, *fill, t);
-}
-
-// The one paint call that synchronises (the number of grow passes depends on the data) and the one that always reads the original.
-int rtdd_fill_similar(rtdd_ctx *ctx, const rtdd_wand *wand, uint8_t *edited, size_t editedPitch, uint8_t *scribble, size_t scribblePitch,
-                      const uint8_t *original, size_t originalPitch, int rows, int cols, rtdd_wand_info *info) {
-    if (!ctx) return RTDD_ERR_INVALID;
-    const PaintTarget t{edited, editedPitch, scribble, scribblePitch, original, originalPitch, rows, cols};
-    REQUIRE(ctx, wand, "null wand");
-    REQUIRE(ctx, wand->tolerance >= 0 && wand->tolerance <= 255, "tolerance outside [0, 255]");
-    REQUIRE(ctx, (wand->flags & ~(RTDD_WAND_CONNECT_8 | RTDD_WAND_GLOBAL)) == 0, "unknown wand flag");
-    for (int v : {wand->ax0, wand->ay0, wand->ax1, wand->ay1}) REQUIRE(ctx, v >= -32768 && v <= 32767, "axis coordinate outside [-32768, 32767]");
-    const char *why = nullptr;
-    REQUIRE(ctx, label_pair_ok(wand->label0, wand->label1, &why), why);
-    REQUIRE(ctx, original, "null original image: it is what \"similar\" reads");
-    RTDD_TRY(check_paint_target(ctx, t, false));
-    REQUIRE(ctx, wand->x >= 0 && wand->x < cols && wand->y >= 0 && wand->y < rows, "the seed lies outside the image (an empty image has no seed)");
-    REQUIRE(ctx, editedPitch >= (size_t)cols * 3 && scribblePitch >= (size_t)cols && originalPitch >= (size_t)cols * 3, "pitch smaller than a row");
-    const bool erases = wand->label0 == RTDD_STROKE_ERASE;
-    DeviceGuard g(ctx->device);
-    // the call synchronises the stream: confirm (or heal) the logged solves and estimates through their own path first, while the state
-    // they ran on still exists -- and before the pyramid hears of this write, which a replayed estimate would otherwise take for its own;
-    // the synchronisations behind that are plain.  Not logged itself, like every paint call.
-    RTDD_TRY(settle_pending(ctx));
-    RTDD_TRY(begin_paint(ctx, t, erases));
-    return launch_fill_similar(ctx, *wand, t, info);
-}
-
-// host arithmetic only (include/rtdd.h has the rule): doubles, every operation rounded on its own
-int rtdd_ramp_polyline(const int *xy, int n, int radius, int brush, int label0, int label1, rtdd_ramp_stroke *out) {
-#pragma clang fp contract(off)
-    if (!xy || !out || n < 1 || n > 4097) return RTDD_ERR_INVALID;
-    if (label0 < 0 || label0 > 255 || label1 < 0 || label1 > 255) return RTDD_ERR_INVALID;
-    const char *why = nullptr;
-    for (int i = 0; i < n; i++)
-        if (!stroke_geometry_ok(xy[2 * i], xy[2 * i + 1], xy[2 * i], xy[2 * i + 1], radius, brush, &why)) return RTDD_ERR_INVALID;
-    if (n == 1) { out[0] = rtdd_ramp_stroke{xy[0], xy[1], xy[0], xy[1], radius, brush, label0, label0}; return RTDD_OK; }
-    std::vector<double> s((size_t)n);
-    s[0] = 0.0;
-    for (int i = 1; i < n; i++) {
-        const long long dx = (long long)xy[2 * i] - xy[2 * i - 2], dy = (long long)xy[2 * i + 1] - xy[2 * i - 1];
-        s[i] = s[i - 1] + std::sqrt((double)(dx * dx + dy * dy));
-    }
-    const double S = s[n - 1];
-    auto label = [&](int i) {
-        if (!(S > 0.0)) return label0;
-        const double share = s[i] / S, rise = (double)(label1 - label0) * share, at = (double)label0 + rise;
-        return (int)std::floor(at + 0.5);
-    };
-    int prev = label(0);
-    for (int i = 0; i + 1 < n; i++) {
-        const int next = label(i + 1);
-        out[i] = rtdd_ramp_stroke{xy[2 * i], xy[2 * i + 1], xy[2 * i + 2], xy[2 * i + 3], radius, brush, prev, next};
-        prev = next;
-    }
-    return RTDD_OK;
 }
 
 }  // extern "C"

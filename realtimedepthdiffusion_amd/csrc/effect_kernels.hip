@@ -867,7 +867,7 @@ static int defocus_body(rtdd_ctx *ctx, const uint8_t *orig, size_t op, const flo
     return RTDD_OK;
 }
 
-// Every depth effect (arguments checked by effects_api.cpp or cascade_api.cpp): k_blend's three modes and the two defocus bodies.
+// Every depth effect (arguments checked by effects_api.cpp or live.cpp): k_blend's three modes and the two defocus bodies.
 int launch_effect(rtdd_ctx *ctx, const Effect &e) {
     switch (e.kind) {
         case RTDD_EFFECT_DEFOCUS:

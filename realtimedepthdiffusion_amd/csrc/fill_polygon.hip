@@ -130,7 +130,7 @@ __global__ __launch_bounds__(256) void k_fill_polygon(const FillArgs C, uint8_t 
     }
 }
 
-// checked by rtdd_fill_polygon (api.cpp): 1 <= n <= 768, every coordinate in [-32768, 32767], the rule and the labels valid
+// checked by rtdd_fill_polygon (image_api.cpp): 1 <= n <= 768, every coordinate in [-32768, 32767], the rule and the labels valid
 int launch_fill_polygon(rtdd_ctx *ctx, const int *xy, int n, const rtdd_fill &fill, const PaintTarget &t) {
     FillArgs C{};
     C.x0 = C.x1 = xy[0]; C.y0 = C.y1 = xy[1];

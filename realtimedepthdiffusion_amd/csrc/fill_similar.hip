@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256) void k_wand_paint(const WandArgs C, const u64 
     }
 }
 
-// checked by rtdd_fill_similar (api.cpp): the seed inside the image, tolerance, flags, labels and axis valid, all three images given.
+// checked by rtdd_fill_similar (image_api.cpp): the seed inside the image, tolerance, flags, labels and axis valid, all three images given.
 // Synchronises: the number of grow passes depends on the data.
 int launch_fill_similar(rtdd_ctx *ctx, const rtdd_wand &wand, const PaintTarget &t, rtdd_wand_info *out) {
     const int W = (t.cols + 63) / 64;

@@ -422,7 +422,7 @@ int launch_paint(rtdd_ctx *ctx, int x, int y, int color, int radius, const Paint
     return RTDD_OK;
 }
 
-// strokes: checked by rtdd_paint_strokes / rtdd_paint_ramp_strokes (api.cpp) -- coordinates, radius, brush and labels inside the packed
+// strokes: checked by rtdd_paint_strokes / rtdd_paint_ramp_strokes (image_api.cpp) -- coordinates, radius, brush and labels inside the packed
 // fields' ranges.  One body for both record types: the labels' bits and the kernel's variant are all that differs.
 static uint32_t pack_labels(const rtdd_stroke &q) { return (uint32_t)(q.label + 1) << 12; }
 static uint32_t pack_labels(const rtdd_ramp_stroke &q) { return (uint32_t)(q.label0 + 1) << 12 | (uint32_t)std::max(q.label1, 0) << 21; }

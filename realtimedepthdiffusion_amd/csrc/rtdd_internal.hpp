@@ -89,7 +89,7 @@ struct SolveCall {
     const uint8_t *regions = nullptr; size_t regionsPitch = 0;
     int regionFlags = 0;
 };
-// A live frame's own images (cascade_api.cpp): the level-0 annotation pair its estimate ran on, the second target of its u8 map
+// A live frame's own images (live.cpp): the level-0 annotation pair its estimate ran on, the second target of its u8 map
 // (u8_pitch 0: a staging slot with the pyramid's pitch), and the sticky depth effect behind it (src/main.cpp:190-230) with its target.
 struct LiveTargets {
     void *scribble = nullptr, *edited = nullptr;
@@ -225,7 +225,7 @@ struct Bounce { void *ptr = nullptr; size_t bytes = 0; };
 
 struct rtdd_ctx {
     int device = 0;
-    rtdd::Pyramid *pyr = nullptr;       // whole-estimate driver state (cascade_api.cpp)
+    rtdd::Pyramid *pyr = nullptr;       // whole-estimate driver state (pyramid.hpp)
     rtdd::MgState *mg = nullptr;        // multigrid hierarchy buffers (multigrid.hip), kept between solves of one size
     hipStream_t stream = nullptr;
     std::vector<rtdd::Level> levels;
@@ -272,7 +272,7 @@ struct rtdd_ctx {
     int publish_seq = 0;
     bool status_writer_behind = false;
     signed char persist_fit[17][2];  // per (tile id, contraction): does one workgroup of the persistent kernel fit a CU of THIS device (-1 = not asked yet)
-    rtdd::Bounce bounce;            // host <-> device 2-D copies with an unaligned host pitch, on ctx->stream (copy_h2d / copy_d2h, cascade_api.cpp)
+    rtdd::Bounce bounce;            // host <-> device 2-D copies with an unaligned host pitch, on ctx->stream (copy_h2d / copy_d2h, image_api.cpp)
     uint32_t *sat = nullptr;        // defocus summed-area table scratch; the parallax view's keys
     size_t sat_elems = 0;
     int sat_rows = 0, sat_cols = 0;     // the geometry the table's zero padding was laid out for (effect_kernels.hip)
@@ -317,6 +317,12 @@ inline void note_publisher(rtdd_ctx *ctx, int seq) { ctx->persistent_used = true
 
 #define REQUIRE(ctx, cond, msg) \
     do { if (!(cond)) return ::rtdd::fail((ctx), RTDD_ERR_INVALID, msg); } while (0)
+// the first line of every entry point that works on the context's pyramid
+#define REQUIRE_PYRAMID(ctx)                                                                                             \
+    do {                                                                                                                 \
+        if (!(ctx)) return RTDD_ERR_INVALID;                                                                             \
+        if (!(ctx)->pyr) return ::rtdd::fail((ctx), RTDD_ERR_STATE, "rtdd_pyramid_create has not been called");          \
+    } while (0)
 // evaluate a call that returns an rtdd status; leave the function with it unless it is RTDD_OK
 #define RTDD_TRY(call) \
     do { const int rc_ = (call); if (rc_ != RTDD_OK) return rc_; } while (0)
@@ -378,6 +384,19 @@ int launch_pyrdown_annotation(rtdd_ctx *ctx, const uint8_t *ps, size_t psp, cons
 int launch_annotation_pyramid(rtdd_ctx *ctx, int levels, uint8_t *const *scribble, const size_t *sp, const size_t *zs, uint8_t *const *edited, const size_t *ep, const size_t *ze,
                               const int *rows, const int *cols, float *depth, size_t dp, size_t zd, int images, bool rebuild = false);
 int launch_repitch(rtdd_ctx *ctx, hipStream_t stream, const void *src, size_t srcPitch, void *dst, size_t dstPitch, size_t widthBytes, int rows);
+// ---- image_api.cpp: copies between host and device images ---------------------------------------
+// hipMemcpy2DAsync between host and device takes ~9 us PER ROW when the host pitch is no multiple of four -- 8 ms for one plane of a
+// 910-pixel-wide image (the dataset's Arara) where an aligned pitch takes 25 us (profiles/r05_copy2d_pitch.txt): slow_pitch.  A host
+// image with such a pitch whose rows are contiguous (what a continuous cv::Mat or a numpy array is) moves as ONE linear copy through a
+// contiguous device buffer and a re-pitching kernel (wants_bounce); any other layout takes the runtime's copy as it is.
+inline bool slow_pitch(size_t hostPitch, int rows) { return hostPitch % 4 != 0 && rows > 1; }
+inline bool wants_bounce(size_t hostPitch, size_t widthBytes, int rows) { return slow_pitch(hostPitch, rows) && hostPitch == widthBytes; }
+// copy_h2d is its two halves on one stream.  The first leaves the host on copyStream: straight into the device image, or (wants_bounce)
+// linearly into `b`, whose uses kernelStream orders; the second re-pitches `b` into the device image on kernelStream (nothing to do
+// for a copy that went straight).  A live frame puts an event between them (live.cpp).
+int copy_h2d_linear(rtdd_ctx *ctx, Bounce &b, void *dev, size_t devPitch, const void *host, size_t hostPitch, size_t widthBytes, int rows,
+                    hipStream_t copyStream, hipStream_t kernelStream);
+int copy_h2d_repitch(rtdd_ctx *ctx, const Bounce &b, void *dev, size_t devPitch, size_t hostPitch, size_t widthBytes, int rows, hipStream_t kernelStream);
 int copy_h2d(rtdd_ctx *ctx, Bounce &b, void *dev, size_t devPitch, const void *host, size_t hostPitch, size_t widthBytes, int rows, hipStream_t stream);
 int copy_d2h(rtdd_ctx *ctx, Bounce &b, void *host, size_t hostPitch, const void *dev, size_t devPitch, size_t widthBytes, int rows, hipStream_t stream);
 // what the paint calls write: the annotation pair, the original an eraser restores from (null: none given), the size of all three
@@ -440,6 +459,7 @@ struct RegionLevels {
     int rows[kMax], cols[kMax], shift[kMax], first_block[kMax + 1];
 };
 int launch_region_codes(rtdd_ctx *ctx, const uint8_t *edited, size_t ep, size_t ze, const uint8_t *mask, size_t mp, size_t zm, RegionLevels &lv, int images);
+// ---- pyramid.cpp -------------------------------------------------------------------------------
 void pyramid_free(rtdd_ctx *ctx);
 // an annotation image is about to be written: one of the pyramid's?  RTDD_ERR_STATE for a level-0 pointer a live frame has retired
 // (erases: labels were REMOVED -- when the images are the pyramid's level-0 pair the next estimate rebuilds the coarse levels)
@@ -457,13 +477,9 @@ void prune_confirmed(rtdd_ctx *ctx);    // drop the logged calls a copy-back ker
 int settle_pending(rtdd_ctx *ctx);      // before a call changes what the logged calls ran on: synchronise + check (+ heal) while that state still exists
 // the one place a call enters the log: kind, opt and the kind's record filled in by the caller, id assigned here; false: not logged
 bool log_call(rtdd_ctx *ctx, PendingOp &op);
-// cascade_api.cpp: levels from_level .. 0 of an estimate (src/main.cpp:261-291); level_seq (optional) receives each level's solve sequence number
-int estimate_levels(rtdd_ctx *ctx, int maxIterations, int from_level, int *level_seq, int first, int n, const LiveTargets &live, int guide, int regionFlags);
 // api.cpp: rtdd_solve_ex with everything the library's own callers add to it (c.targets)
 int solve_with(rtdd_ctx *ctx, const SolveCall &c, rtdd_solve_info *info, SolveOutcome *out);
-// cascade_api.cpp: a live frame's effect (again, on a replay): RTDD_EFFECT_* on the pyramid's level-0 images into live.artistic
-int live_effect(rtdd_ctx *ctx, const LiveTargets &live);
-// an estimate of the pending log again, from the level whose solve has sequence number failed_seq (0: every level)
+// estimate.cpp: an estimate of the pending log again, from the level whose solve has sequence number failed_seq (0: every level)
 int estimate_replay(rtdd_ctx *ctx, const PendingOp::Estimate &e, int failed_seq);
 
 // the reference's host-side omega recurrence (src/GPUSolver.cu:282-299)

@@ -580,6 +580,45 @@ def test_live_frames_with_a_sticky_effect_match_the_oracle(oracle, lut, effect, 
             c.live_submit_ex(scr.a, ed.a, out[0].a, 4, art[0].a, 1000)       # unknown effect
 
 
+@pytest.mark.parametrize("pageable", [False, True])
+@pytest.mark.parametrize("in_flight", [2, 1])
+def test_live_frames_of_an_odd_width_with_a_sticky_effect(oracle, lut, in_flight, pageable):
+    """Live frames WITH a sticky effect (haze) of an image whose width is no multiple of four (contiguous host images: pitches 241 and
+    723).  One frame at a time: the artistic image's download is queued on the compute stream through the contiguous device buffer, the
+    map stored straight into a page-locked image or staged for a pageable one.  Two in flight: map and artistic image are both staged
+    and share rtdd_live_wait's page-locked buffer, one behind the other.  Every map is the oracle's n-th warm-started estimate, every
+    artistic image the oracle's haze on that estimate's depth map; the third frame has no effect."""
+    rows, cols = 135, 241
+    bgr, ann = _bgr(rows, cols, 12)
+    ref = Cascade(oracle, bgr, ann, lut, 1, threads=4)
+    mk = _Pageable if pageable else rt.host_image
+    with rt.Context(0) as c:
+        c.GPULoadWeights(0.4)
+        c.pyramid_create(rows, cols)
+        c.pyramid_set_image(up(bgr)); c.pyramid_set_annotation(up(ann)); c.synchronize()
+        scr = mk((rows, cols)); ed = mk((rows, cols, 3))
+        out = [mk((rows, cols)) for _ in range(2)]; art = [mk((rows, cols, 3)) for _ in range(2)]
+        scr.a[...] = ref.scribble[0]; ed.a[...] = ref.edited[0]
+        frames = 4
+        got = []
+        for n in range(frames):
+            if n >= in_flight:
+                k = len(got); c.live_wait(); got.append((out[k % 2].a.copy(), art[k % 2].a.copy()))
+            # (a slot's previous artistic image must not leak into the frame without an effect)
+            c.live_submit_ex(scr.a, ed.a, out[n % 2].a, rt.EFFECT_HAZE if n != 2 else rt.EFFECT_NONE, art[n % 2].a if n != 2 else None, 1000)
+            assert c.live_pending() == min(n + 1, in_flight)
+        while c.live_pending():
+            k = len(got); c.live_wait(); got.append((out[k % 2].a.copy(), art[k % 2].a.copy()))
+        c.synchronize()
+        assert c.get_option(rt.OPT_TIMEOUT_HEALS) == 0
+        for n in range(frames):
+            ref.estimate(1000)
+            assert np.array_equal(got[n][0], ref.depth_u8), f"frame {n}: u8 map"
+            if n != 2:
+                assert np.array_equal(got[n][1], oracle.haze(bgr, ref.depth[0], 1)), f"frame {n}: artistic image"
+        assert np.array_equal(c.pyramid_download(rt.IMG_ARTISTIC), oracle.haze(bgr, ref.depth[0], 1))
+
+
 def test_a_retired_live_annotation_pointer_is_refused(oracle, lut):
     """After an uploading live frame the pyramid's level-0 scribble / edited images ARE the uploaded pair: a pointer rtdd_pyramid_image
     handed out before names a buffer no estimate reads.  Painting / uploading / converting through it would lose the strokes silently:
