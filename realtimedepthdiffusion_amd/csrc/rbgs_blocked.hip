@@ -15,6 +15,7 @@
 
 #include "rtdd_internal.hpp"
 #include "persist_sync.hpp"
+#include "sweep_common.hpp"    // div_tiny
 
 namespace rtdd {
 namespace {
@@ -32,10 +33,7 @@ __device__ __forceinline__ float div3(float n, float d, float y) {     // see sw
 }
 
 // SOR: successive over-relaxation, x <- clamp(x + omega (clamp(gs) - x)); omega = 1 is plain Gauss-Seidel and takes the !SOR path.
-__device__ __forceinline__ float rcp_rn(float d) {       // == 1.0f/d for every normal d with a normal reciprocal (sweep_blocked.hip)
-    const float y0 = __builtin_amdgcn_rcpf(d);
-    return __builtin_fmaf(__builtin_fmaf(-d, y0, 1.0f), y0, y0);
-}
+// (rcp_rn: sweep_common.hpp)
 
 // write-through (sc1) 16-byte store for the inter-workgroup hand-off of the persistent mode (see sweep_blocked.hip)
 __device__ __forceinline__ void store_sc1(float4 *p, float4 v) {
@@ -200,12 +198,27 @@ __global__ __launch_bounds__(NT, 4) void k_rbgs_blocked(float *X, float *Y, cons
                     else q[g][i] = sum / cnt[g][i];
                 }
             }
-            if (FAST && __builtin_expect(__builtin_amdgcn_ballot_w64(tmin < kTinyT) != 0, 0)) {      // wave-uniform, rare: full IEEE divide
+            if (FAST && __builtin_expect(__builtin_amdgcn_ballot_w64(tmin < kTinyT) != 0, 0)) {      // wave-uniform, rare
+                // tiny lanes: the scaled quotient; the full IEEE divide only where one of them is suspect (sweep_common.hpp div_tiny)
+                bool suspect = false;
 #pragma unroll
                 for (int g = 0; g < G; g++) {
                     if (!pick(g)) continue;
 #pragma unroll
-                    for (int i = 0; i < 4; i++) if (((g + i) & 1) == C) q[g][i] = wsum(g, i) / cnt[g][i];
+                    for (int i = 0; i < 4; i++) {
+                        if (((g + i) & 1) != C) continue;
+                        bool s;
+                        q[g][i] = div_tiny(wsum(g, i), cnt[g][i], rcp[g][i], s);
+                        suspect |= s;
+                    }
+                }
+                if (__builtin_expect(__builtin_amdgcn_ballot_w64(suspect) != 0, 0)) {
+#pragma unroll
+                    for (int g = 0; g < G; g++) {
+                        if (!pick(g)) continue;
+#pragma unroll
+                        for (int i = 0; i < 4; i++) if (((g + i) & 1) == C) q[g][i] = wsum(g, i) / cnt[g][i];
+                    }
                 }
             }
 #pragma unroll

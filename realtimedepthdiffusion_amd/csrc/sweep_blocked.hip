@@ -493,7 +493,12 @@ __global__ __launch_bounds__(1024) void k_sweep_col(const float *__restrict__ Xk
             if (FAST) {
                 q0 = div_tail(s0, cnt[g0], rcp[g0]); q1 = div_tail(s1, cnt[g1], rcp[g1]);
                 const uint32_t t0 = (__float_as_uint(s0) << 1) + 0xFFFFFFFFu, t1 = (__float_as_uint(s1) << 1) + 0xFFFFFFFFu;
-                if (__builtin_expect(__builtin_amdgcn_ballot_w64((t0 < t1 ? t0 : t1) < kTinyT) != 0, 0)) { q0 = s0 / cnt[g0]; q1 = s1 / cnt[g1]; }
+                if (__builtin_expect(__builtin_amdgcn_ballot_w64((t0 < t1 ? t0 : t1) < kTinyT) != 0, 0)) {
+                    // tiny lanes: the scaled quotient; the IEEE divide only where one of them is suspect (sweep_common.hpp div_tiny)
+                    bool u0, u1;
+                    q0 = div_tiny(s0, cnt[g0], rcp[g0], u0); q1 = div_tiny(s1, cnt[g1], rcp[g1], u1);
+                    if (__builtin_expect(__builtin_amdgcn_ballot_w64(u0 || u1) != 0, 0)) { q0 = s0 / cnt[g0]; q1 = s1 / cnt[g1]; }
+                }
             } else { q0 = s0 / cnt[g0]; q1 = s1 / cnt[g1]; }
             const int gs[2] = {g0, g1}; const float qs[2] = {q0, q1};
 #pragma unroll

@@ -88,8 +88,9 @@ __device__ __forceinline__ void store_result(float4 *p, float4 v) { *p = v; }
 // remainder, a multiple of 2^(e_n - 47), is exactly representable), n/d bounded (a weighted mean) and n finite: with n = +-inf, or a
 // sum or n*y that overflows, fma(-d, inf, inf) is NaN where the IEEE quotient is +-inf, and the clamp behind it turns that NaN into 0
 // and +inf into 255.
-// Anything else takes the full divide under a wave-uniform branch.  Three guards send a wave there: a divisor below 2^-126 (tested per
-// launch), a numerator below 2^-100 (tested per group of rows, sweep_tile_sweeps.inc), and -- the upper end of the domain -- a solve
+// Anything else leaves the 3-operation step under a wave-uniform branch.  Three guards send a wave there: a divisor below 2^-126 (tested
+// per launch: the full divide), a numerator below 2^-100 (tested per group of rows, sweep_tile_sweeps.inc: div_tiny below, and the full
+// divide only for a group with a suspect lane), and -- the upper end of the domain, the full divide again -- a solve
 // whose INPUT holds a depth that is not finite or is 2^100 or more in magnitude: k_prepare reads every depth anyway and raises a
 // launch-wide flag that every wave of the sweep kernels ORs into its choice (persist_sync.hpp kSyncWild, where it is also shown that
 // an iterate that starts below that threshold never reaches an overflowing numerator).  Nothing per sweep.
@@ -97,6 +98,31 @@ __device__ __forceinline__ float div_tail(float n, float d, float y) {
     const float q0 = n * y;
     const float r = __builtin_fmaf(-d, q0, n);
     return __builtin_fmaf(r, y, q0);
+}
+
+// The quotient of a TINY numerator (|n| < 2^-100, denormals included; d normal and <= 4, y = RN(1/d)) without the 11-operation divide:
+//      N = n * 2^64            exact, and inside div_tail's domain (2^-85 <= |N| < 2^-36, or 0)
+//      Q = div_tail(N, d, y)   = RN24(N / d)
+//      q = Q * 2^-64           exact while the quotient is normal; ONE more rounding, to the 2^-149 grid, when it is denormal
+// Rounding is monotone and the midpoints of the 2^-149 grid are themselves 24-bit numbers at that scale, so Q lies on the same side of
+// every midpoint as N / d does -- unless Q IS a midpoint.  Only then can the second rounding differ from RN(n / d) (ties-to-even on Q
+// against the side N / d really lies on), and Q is a midpoint exactly when |Q - q * 2^64| == 2^-86 (q * 2^64 and the difference are
+// exact).  Such a lane is `suspect`: a fifth of the denormal quotients are, and half of those are in fact wrong, so the caller sends the
+// row group to the IEEE divide under a second wave-uniform branch when any of its lanes is.
+// The scale is per lane: 2^64 where the numerator is tiny and 1 elsewhere (n * 2^64 could overflow there), so that a lane that is not
+// tiny gets div_tail(n, d, y) again -- the valid quotient it already had -- and is never suspect (Q - q == 0).  The caller needs no
+// select and keeps no earlier quotient alive across the branch.  Ten VALU operations, none of them quarter rate.
+// The multiplications by 2^+-64 need f32 denormals honoured, as the whole solve does.  Checked against hipcc's divide on gfx950 for all
+// 2^23 divisor significands and every underflow depth of the quotient: scripts/ubench/div_tiny_exhaustive.hip, log in profiles/;
+// restated in C in tests/test_div_tiny_cpu.py.
+__device__ __forceinline__ float div_tiny(float n, float d, float y, bool &suspect) {
+    const bool tiny = __builtin_fabsf(n) < 0x1p-100f;            // (a zero numerator: +0 either way)
+    const float up = tiny ? 0x1p64f : 1.0f, down = tiny ? 0x1p-64f : 1.0f;
+    const float N = n * up;
+    const float Q = div_tail(N, d, y);
+    const float q = Q * down;
+    suspect = __builtin_fabsf(__builtin_fmaf(q, -up, Q)) == 0x1p-86f;
+    return q;
 }
 
 // RN(1/d) for a normal d with a normal reciprocal: v_rcp_f32 (1 ulp) + one Newton step.  Equal to the IEEE quotient 1.0f/d for
