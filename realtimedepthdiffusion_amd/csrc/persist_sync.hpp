@@ -86,9 +86,14 @@ __device__ __forceinline__ int exchange_poll_offset(int tid, int bx, int by, int
 
 // A flag read as the relaxed agent-scope atomic load it is (global_load_dword sc1 and its wait), written out so that the address stays
 // scalar base + 32-bit lane offset inside the polling loop (left to the compiler the loop keeps a 64-bit sum per lane).
+// The s_nop 4 in front: the compiler pads no hazard whose consumer is inside an asm string, and where it has spilled `base` to a VGPR lane
+// it restores it with v_readlane_b32 directly in front of the statement -- a VALU write of an SGPR that a VMEM instruction reads needs 5
+// wait states, or the load goes to whatever the pair held before (k_sweep_blocked<32, 512, 6, true, true> faulted that way; EXPERIMENTS.md
+// "Tile 3").  The same opening is in every statement of sweep_common.hpp that addresses through a scalar base; tests/test_isa_narrowed_exec.py
+// checks the wait states on the built objects.  Five cycles per poll, next to an s_sleep.
 __device__ __forceinline__ int load_flag_at(const int *base, unsigned off) {
     int v;
-    asm volatile("global_load_dword %0, %1, %2 sc1\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(off), "s"(base) : "memory");
+    asm volatile("s_nop 4\n\tglobal_load_dword %0, %1, %2 sc1\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(off), "s"(base) : "memory");
     return v;
 }
 

@@ -199,26 +199,12 @@ __global__ __launch_bounds__(NT, 4) void k_rbgs_blocked(float *X, float *Y, cons
                 }
             }
             if (FAST && __builtin_expect(__builtin_amdgcn_ballot_w64(tmin < kTinyT) != 0, 0)) {      // wave-uniform, rare
-                // tiny lanes: the scaled quotient; the full IEEE divide only where one of them is suspect (sweep_common.hpp div_tiny)
-                bool suspect = false;
+                // tiny lanes: the scaled quotient, rounded once (sweep_common.hpp div_tiny)
 #pragma unroll
                 for (int g = 0; g < G; g++) {
                     if (!pick(g)) continue;
 #pragma unroll
-                    for (int i = 0; i < 4; i++) {
-                        if (((g + i) & 1) != C) continue;
-                        bool s;
-                        q[g][i] = div_tiny(wsum(g, i), cnt[g][i], rcp[g][i], s);
-                        suspect |= s;
-                    }
-                }
-                if (__builtin_expect(__builtin_amdgcn_ballot_w64(suspect) != 0, 0)) {
-#pragma unroll
-                    for (int g = 0; g < G; g++) {
-                        if (!pick(g)) continue;
-#pragma unroll
-                        for (int i = 0; i < 4; i++) if (((g + i) & 1) == C) q[g][i] = wsum(g, i) / cnt[g][i];
-                    }
+                    for (int i = 0; i < 4; i++) if (((g + i) & 1) == C) q[g][i] = div_tiny(wsum(g, i), cnt[g][i], rcp[g][i]);
                 }
             }
 #pragma unroll

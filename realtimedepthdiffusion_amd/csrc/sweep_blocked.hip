@@ -158,20 +158,26 @@ __global__ __launch_bounds__(NT, (NT >= 1024 || G <= 3 ? 4 : G <= 4 ? 3 : 2)) vo
         // every one of a solve's exchanges (124 at 1080p), and the coordinates they follow from are live here anyway; worked out at the
         // exchange they were ~100 instructions per wave of 64-bit address arithmetic and coordinate compares, and held in registers
         // across the sweeps they push the sweep loop's operands into scratch.  So: once, here, and parked in LDS.
-        const bool xin = colok && 4 * lx >= hx && 4 * lx < EW - hx;
+        // Every predicate below is combined with `&` / `|` on purpose, never `&&` / `||`: a short-circuit on a per-lane condition is a
+        // region that runs under a NARROWED EXEC, and in k_sweep_blocked<32, 1024, 4, true, true> the register allocator split the live
+        // range of `lx` there -- `v_mov_b32 v36, v118` under EXEC = colok -- after which every lane took lx from v36.  The lanes right of
+        // the image (x0 >= cols, the last tile column) kept what v36 held before, 0, published their edge rows into lane 0's LDS slots
+        // and wiped the halo lane's rows at every sweep (EXPERIMENTS.md "Tile 3"; tests/test_isa_narrowed_exec.py checks every
+        // instantiation for such a copy).  Nothing here is worth a branch anyway: the operands are all in registers.
+        const bool xin = colok & (4 * lx >= hx) & (4 * lx < EW - hx);
         uint32_t bits = 0;
 #pragma unroll
         for (int g = 0; g < G; g++) {
             const int y = y0 + g, ty = tr * G + g;
-            const bool central = xin && ty >= hy && ty < eh - hy;
-            const bool band = ty < 2 * hy || ty >= eh - 2 * hy || 4 * lx < 2 * hx || 4 * lx >= EW - 2 * hx;
-            const bool ok = colok && y >= 0 && y < rows;
-            if (central && y < rows && band) bits |= 1u << g;            // my centre, within two halo widths of its edge: some neighbour's halo
-            if (ok && !central) bits |= 0x100u << g;                    // a halo pixel inside the image: some neighbour's centre
+            const bool central = xin & (ty >= hy) & (ty < eh - hy);
+            const bool band = (ty < 2 * hy) | (ty >= eh - 2 * hy) | (4 * lx < 2 * hx) | (4 * lx >= EW - 2 * hx);
+            const bool ok = colok & (y >= 0) & (y < rows);
+            bits |= (uint32_t)(central & (y < rows) & band) << g;       // my centre, within two halo widths of its edge: some neighbour's halo
+            bits |= (uint32_t)(ok & !central) << (8 + g);               // a halo pixel inside the image: some neighbour's centre
         }
         const int nv = min(max(cols - x0, 0), 4);
         bits |= (uint32_t)nv << 16;
-        if (colok && nv < 4) bits |= 1u << 19;
+        bits |= (uint32_t)(colok & (nv < 4)) << 19;
         const uint32_t off0 = ((uint32_t)y0 * (uint32_t)ip + (uint32_t)x0) * 4u;
         xrec[tid] = make_int4((int)off0, (int)bits, exchange_poll_offset(tid, bx, by, gx, gy, tile_base), 0);
     }
@@ -494,10 +500,8 @@ __global__ __launch_bounds__(1024) void k_sweep_col(const float *__restrict__ Xk
                 q0 = div_tail(s0, cnt[g0], rcp[g0]); q1 = div_tail(s1, cnt[g1], rcp[g1]);
                 const uint32_t t0 = (__float_as_uint(s0) << 1) + 0xFFFFFFFFu, t1 = (__float_as_uint(s1) << 1) + 0xFFFFFFFFu;
                 if (__builtin_expect(__builtin_amdgcn_ballot_w64((t0 < t1 ? t0 : t1) < kTinyT) != 0, 0)) {
-                    // tiny lanes: the scaled quotient; the IEEE divide only where one of them is suspect (sweep_common.hpp div_tiny)
-                    bool u0, u1;
-                    q0 = div_tiny(s0, cnt[g0], rcp[g0], u0); q1 = div_tiny(s1, cnt[g1], rcp[g1], u1);
-                    if (__builtin_expect(__builtin_amdgcn_ballot_w64(u0 || u1) != 0, 0)) { q0 = s0 / cnt[g0]; q1 = s1 / cnt[g1]; }
+                    // tiny lanes: the scaled quotient, rounded once (sweep_common.hpp div_tiny)
+                    q0 = div_tiny(s0, cnt[g0], rcp[g0]); q1 = div_tiny(s1, cnt[g1], rcp[g1]);
                 }
             } else { q0 = s0 / cnt[g0]; q1 = s1 / cnt[g1]; }
             const int gs[2] = {g0, g1}; const float qs[2] = {q0, q1};

@@ -32,10 +32,13 @@ __device__ __forceinline__ float lds_from_next(int prev4, float v) { return __in
 // EVERY load of handed-off bytes of this form, every store of them sc1 and drained, and the flag protocol of persist_sync.hpp, the consumer
 // needs no agent-scope acquire (MI355X_MICROARCH.md, "Valid forms", table row 1).  Both take the address as a scalar base plus a 32-bit
 // unsigned byte offset per lane (the instructions' `saddr` form): a kernel that exchanges the same rows many times keeps one offset per
-// thread and forms no 64-bit address (sweep_blocked.hip).
+// thread and forms no 64-bit address (sweep_blocked.hip).  Each statement opens with the wait states that a scalar base fresh from a
+// v_readlane_b32 (an SGPR the compiler had spilled to a VGPR lane) needs before a VMEM instruction may read it -- 5; the compiler pads
+// nothing inside a statement (persist_sync.hpp load_flag_at: the fault this comes from).  The halo statement's two scalar instructions
+// in front of its first load count for two of them.
 typedef float f4v_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void store_sc1_at(const float *base, uint32_t off, f4v_t v) {
-    asm volatile("global_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1" ::"v"(off), "v"(v), "s"(base) : "memory");
+    asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1" ::"v"(off), "v"(v), "s"(base) : "memory");
 }
 // The halo loads of a thread's G rows from two planes, and the wait behind them, as ONE statement: row g is loaded (16 bytes from `bk`
 // into a[g], 16 from `bm` into b[g], both at byte offset off[g]) in the lanes of mask[g]; the other lanes' registers, and rows whose
@@ -47,7 +50,7 @@ __device__ __forceinline__ void store_sc1_at(const float *base, uint32_t off, f4
 #define RTDD_HALO_ROW(n) "s_and_b64 exec, %[sv], %[m" #n "]\n\tglobal_load_dwordx4 %[a" #n "], %[o" #n "], %[bk] sc1\n\tglobal_load_dwordx4 %[b" #n "], %[o" #n "], %[bm] sc1\n\t"
 #define RTDD_HALO_OUT(n) [a##n] "+v"(a[n]), [b##n] "+v"(b[n])
 #define RTDD_HALO_IN(n) [o##n] "v"(off[n]), [m##n] "s"(mask[n])
-#define RTDD_HALO_ASM(rows, outs, ins) asm volatile("s_mov_b64 %[sv], exec\n\t" rows "s_mov_b64 exec, %[sv]\n\ts_waitcnt vmcnt(0)" : outs, [sv] "=&s"(sv) : ins, [bk] "s"(bk), [bm] "s"(bm) : "memory", "scc")
+#define RTDD_HALO_ASM(rows, outs, ins) asm volatile("s_nop 2\n\ts_mov_b64 %[sv], exec\n\t" rows "s_mov_b64 exec, %[sv]\n\ts_waitcnt vmcnt(0)" : outs, [sv] "=&s"(sv) : ins, [bk] "s"(bk), [bm] "s"(bm) : "memory", "scc")
 #define RTDD_C ,
 template <int G>
 __device__ __forceinline__ void load_halo_rows_sc1(f4v_t (&a)[G], f4v_t (&b)[G], const float *bk, const float *bm, const uint32_t (&off)[G], const unsigned long long (&mask)[G]) {
@@ -89,8 +92,8 @@ __device__ __forceinline__ void store_result(float4 *p, float4 v) { *p = v; }
 // sum or n*y that overflows, fma(-d, inf, inf) is NaN where the IEEE quotient is +-inf, and the clamp behind it turns that NaN into 0
 // and +inf into 255.
 // Anything else leaves the 3-operation step under a wave-uniform branch.  Three guards send a wave there: a divisor below 2^-126 (tested
-// per launch: the full divide), a numerator below 2^-100 (tested per group of rows, sweep_tile_sweeps.inc: div_tiny below, and the full
-// divide only for a group with a suspect lane), and -- the upper end of the domain, the full divide again -- a solve
+// per launch: the full divide), a numerator below 2^-100 (tested per group of rows, sweep_tile_sweeps.inc: div_tiny below, ten plain
+// operations and no divide), and -- the upper end of the domain, the full divide again -- a solve
 // whose INPUT holds a depth that is not finite or is 2^100 or more in magnitude: k_prepare reads every depth anyway and raises a
 // launch-wide flag that every wave of the sweep kernels ORs into its choice (persist_sync.hpp kSyncWild, where it is also shown that
 // an iterate that starts below that threshold never reaches an overflowing numerator).  Nothing per sweep.
@@ -101,28 +104,37 @@ __device__ __forceinline__ float div_tail(float n, float d, float y) {
 }
 
 // The quotient of a TINY numerator (|n| < 2^-100, denormals included; d normal and <= 4, y = RN(1/d)) without the 11-operation divide:
-//      N = n * 2^64            exact, and inside div_tail's domain (2^-85 <= |N| < 2^-36, or 0)
-//      Q = div_tail(N, d, y)   = RN24(N / d)
-//      q = Q * 2^-64           exact while the quotient is normal; ONE more rounding, to the 2^-149 grid, when it is denormal
-// Rounding is monotone and the midpoints of the 2^-149 grid are themselves 24-bit numbers at that scale, so Q lies on the same side of
-// every midpoint as N / d does -- unless Q IS a midpoint.  Only then can the second rounding differ from RN(n / d) (ties-to-even on Q
-// against the side N / d really lies on), and Q is a midpoint exactly when |Q - q * 2^64| == 2^-86 (q * 2^64 and the difference are
-// exact).  Such a lane is `suspect`: a fifth of the denormal quotients are, and half of those are in fact wrong, so the caller sends the
-// row group to the IEEE divide under a second wave-uniform branch when any of its lanes is.
+//      N  = n * 2^64                   exact, and inside div_tail's domain (2^-85 <= |N| < 2^-36, or 0)
+//      qd = (N * y) * 2^-64            a first quotient ON THE QUOTIENT'S OWN GRID: the multiplication by 2^-64 rounds N * y to a
+//                                      multiple of 2^-149 where the quotient is denormal and is exact where it is normal
+//      R  = fma(-d, qd * 2^64, N)      the remainder of N against that grid point (qd * 2^64 is exact)
+//      q  = fma(R, y * 2^-64, qd)      qd + R / d, rounded ONCE (y * 2^-64 is exact: y >= 1/4)
+// This is div_tail's correction step carried out at the quotient's scale.  The form it replaces scaled back AFTER the correction and so
+// rounded twice, to 24 bits and then to the 2^-149 grid: wrong wherever the 24-bit quotient sat on a midpoint of that grid, which it had
+// to detect (a fifth of the denormal quotients) and hand to the IEEE divide.  Here the only rounding that sees the grid is the last one.
+// Why R is exact: write g for the spacing of the quotient's grid at the scale of N (2^-85 where the quotient is denormal, its ulp
+// otherwise) and Qd = qd * 2^64.  Qd is a multiple of g with at most 24 significant bits, d a multiple of ulp(d), N a multiple of
+// 2^-85 and of its own ulp: so R = N - d * Qd is a multiple of ulp(d) * g, and as long as Qd is one of the two grid points next to N / d,
+// |R| < |d| * g < 2^24 * ulp(d) * g -- it fits 24 bits and the fma returns it exactly (the usual exact-remainder argument, with g in the
+// place of the quotient's ulp).  N * y is within 2^-23 of N / d relatively and the rounding to the grid adds half a step, so Qd IS such
+// a neighbour except possibly in the top binade of the denormal range with a divisor significand close to 2, where the bound on
+// |Qd - N / d| is 1.25 g rather than g; R may then need a 25th bit and is rounded by 2^-25 of itself, far below what moves the result
+// across a midpoint -- that corner is covered by the exhaustive run, not by this argument.  Why the last fma rounds once, to the right
+// grid: qd is on the grid, |R * y * 2^-64| is about a step or less, the exact sum qd + R / d is n / d up to y's relative error 2^-24 applied
+// to the CORRECTION only (2^-24 of a step), and the fma rounds that sum directly to f32 -- which, for a denormal result, IS the 2^-149 grid.
 // The scale is per lane: 2^64 where the numerator is tiny and 1 elsewhere (n * 2^64 could overflow there), so that a lane that is not
-// tiny gets div_tail(n, d, y) again -- the valid quotient it already had -- and is never suspect (Q - q == 0).  The caller needs no
-// select and keeps no earlier quotient alive across the branch.  Ten VALU operations, none of them quarter rate.
+// tiny gets div_tail(n, d, y) again, operation for operation -- the valid quotient it already had.  The caller needs no select, keeps no
+// earlier quotient alive across the branch and has no second branch behind it.  Ten VALU operations, none of them quarter rate.
 // The multiplications by 2^+-64 need f32 denormals honoured, as the whole solve does.  Checked against hipcc's divide on gfx950 for all
 // 2^23 divisor significands and every underflow depth of the quotient: scripts/ubench/div_tiny_exhaustive.hip, log in profiles/;
-// restated in C in tests/test_div_tiny_cpu.py.
-__device__ __forceinline__ float div_tiny(float n, float d, float y, bool &suspect) {
+// restated in C in tests/test_div_tiny_once_cpu.py (tests/test_div_tiny_cpu.py keeps the two-rounding form and its suspects on record).
+__device__ __forceinline__ float div_tiny(float n, float d, float y) {
     const bool tiny = __builtin_fabsf(n) < 0x1p-100f;            // (a zero numerator: +0 either way)
     const float up = tiny ? 0x1p64f : 1.0f, down = tiny ? 0x1p-64f : 1.0f;
     const float N = n * up;
-    const float Q = div_tail(N, d, y);
-    const float q = Q * down;
-    suspect = __builtin_fabsf(__builtin_fmaf(q, -up, Q)) == 0x1p-86f;
-    return q;
+    const float qd = (N * y) * down;
+    const float R = __builtin_fmaf(-d, qd * up, N);
+    return __builtin_fmaf(R, y * down, qd);
 }
 
 // RN(1/d) for a normal d with a normal reciprocal: v_rcp_f32 (1 ulp) + one Newton step.  Equal to the IEEE quotient 1.0f/d for

@@ -110,30 +110,16 @@
                 if (FAST) { tmin = min(min(tmin, t[0]), t[1]); tmin = min(min(tmin, t[2]), t[3]); }
             }
             if (FAST && __builtin_expect(__builtin_amdgcn_ballot_w64(tmin < kTinyT) != 0, 0)) {      // wave-uniform; rare on synthetic images, not on photographs
-                // The tiny lanes take the scaled quotient (sweep_common.hpp div_tiny: ten plain operations, against the divide's 11 with its
-                // v_rcp_f32 and v_div_*); every other lane gets the quotient it had again (its scale is 1).  Only a lane whose scaled quotient
-                // sits exactly on a midpoint of the denormal grid sends the group to the IEEE divide.
+                // The tiny lanes take the scaled quotient (sweep_common.hpp div_tiny: ten plain operations, rounded once, against the divide's
+                // 11 with its v_rcp_f32 and v_div_*); every other lane gets the quotient it had again (its scale is 1).
                 // The persistent tiles have the registers to keep a row's four sums up to here; the launch-per-block tiles sit at their cap
                 // of 128 and form each sum again where it is used, as the redo always did.
                 auto sum_of = [&](int g, int i) { return PERSIST ? sums[g][i] : wsum(g, i); };
-                bool suspect = false;
 #pragma unroll
                 for (int g = 0; g < G; g++) {
                     if (!pick(g)) continue;
 #pragma unroll
-                    for (int i = 0; i < 4; i++) {
-                        bool s;
-                        q[g][i] = div_tiny(sum_of(g, i), cnt[g][i], rcp[g][i], s);
-                        suspect |= s;
-                    }
-                }
-                if (__builtin_expect(__builtin_amdgcn_ballot_w64(suspect) != 0, 0)) {
-#pragma unroll
-                    for (int g = 0; g < G; g++) {
-                        if (!pick(g)) continue;
-#pragma unroll
-                        for (int i = 0; i < 4; i++) q[g][i] = sum_of(g, i) / cnt[g][i];
-                    }
+                    for (int i = 0; i < 4; i++) q[g][i] = div_tiny(sum_of(g, i), cnt[g][i], rcp[g][i]);
                 }
             }
 #pragma unroll

@@ -1,7 +1,8 @@
-// Exhaustive check (gfx950) of div_tiny (csrc/sweep_common.hpp): for a numerator 0 < |n| < 2^-100,
-//     N = n * 2^64;  Q = div_tail(N, d, y);  q = Q * 2^-64        with  y = RN(1/d)  (IEEE 1.0f/d)
-// is bit-identical to the IEEE-754 correctly rounded n/d (hipcc's `/` with -fhip-fp32-correctly-rounded-divide-sqrt) in every lane that
-// is not SUSPECT (|Q - q * 2^64| == 2^-86: Q on a midpoint of the 2^-149 grid), and in the suspect lanes whose remainder N - d Q is zero.
+// Exhaustive check (gfx950) of div_tiny (csrc/sweep_common.hpp), the one-rounding form: for a numerator 0 < |n| < 2^-100,
+//     N = n * 2^64;  qd = (N * y) * 2^-64;  R = fma(-d, qd * 2^64, N);  q = fma(R, y * 2^-64, qd)        with  y = RN(1/d)  (IEEE 1.0f/d)
+// is bit-identical to the IEEE-754 correctly rounded n/d (hipcc's `/` with -fhip-fp32-correctly-rounded-divide-sqrt) in EVERY lane: 0
+// mismatches is the requirement, full stop.  For the record it also counts the pairs that the two-rounding form before it
+// (Q = div_tail(N, d, y); q = Q * 2^-64) called suspect (Q on a midpoint of the 2^-149 grid) and those of them that form got wrong.
 // It also shows that the multiplications by 2^+-64 honour f32 denormals in the mode the kernels are compiled for.
 // Divisors: all 2^23 significands, in both binades [1,2) and [2,4) (a denormal quotient does not scale with the divisor's binade: the
 // numerator cannot follow below 2^-149), plus 4.0 itself with the first significand.  Numerators, per divisor, in EVERY binade below
@@ -18,14 +19,20 @@ __device__ __forceinline__ float div_tail(float n, float d, float y) {
     const float r = __builtin_fmaf(-d, q0, n);
     return __builtin_fmaf(r, y, q0);
 }
-__device__ __forceinline__ float div_tiny(float n, float d, float y, bool &suspect, bool &rem) {
+__device__ __forceinline__ float div_tiny(float n, float d, float y) {
     const bool tiny = __builtin_fabsf(n) < 0x1p-100f;
     const float up = tiny ? 0x1p64f : 1.0f, down = tiny ? 0x1p-64f : 1.0f;
     const float N = n * up;
+    const float qd = (N * y) * down;
+    const float R = __builtin_fmaf(-d, qd * up, N);
+    return __builtin_fmaf(R, y * down, qd);
+}
+// the two-rounding form, for the census of what it could not do
+__device__ __forceinline__ float div_tiny_twice(float n, float d, float y, bool &suspect) {
+    const float N = n * 0x1p64f;
     const float Q = div_tail(N, d, y);
-    const float q = Q * down;
-    suspect = __builtin_fabsf(__builtin_fmaf(q, -up, Q)) == 0x1p-86f;
-    rem = __builtin_fmaf(-d, Q, N) != 0.0f;
+    const float q = Q * 0x1p-64f;
+    suspect = __builtin_fabsf(__builtin_fmaf(q, -0x1p64f, Q)) == 0x1p-86f;
     return q;
 }
 struct Counts { unsigned long long pairs, bad, suspects, suspects_differ, denormal_q, tie_bad, deepest; };
@@ -33,14 +40,15 @@ __device__ void one(uint32_t nbits, float d, float y, Counts &c, unsigned *examp
     const float n = __uint_as_float(nbits);
     if ((nbits << 1) == 0 || (nbits << 1) >= (27u << 24)) return;         // 0 < |n| < 2^-100
     const float want = n / d;
-    bool s, rem;
-    const float got = div_tiny(n, d, y, s, rem);
+    bool s;
+    const float got = div_tiny(n, d, y);
+    const float old = div_tiny_twice(n, d, y, s);
     c.pairs++;
     if (__builtin_fabsf(want) < 0x1p-126f) c.denormal_q++;
     if (want == 0.0f) c.deepest++;
     const bool differ = __float_as_uint(got) != __float_as_uint(want);
-    if (s) { c.suspects++; c.suspects_differ += differ; c.tie_bad += differ && !rem; }
-    else if (differ) {
+    if (s) { c.suspects++; c.suspects_differ += __float_as_uint(old) != __float_as_uint(want); c.tie_bad += differ; }
+    if (differ) {
         c.bad++;
         if (atomicAdd(&example[0], 1u) == 0) { example[1] = nbits; example[2] = __float_as_uint(d); example[3] = __float_as_uint(got); }
     }
@@ -88,8 +96,8 @@ int main(int argc, char **argv) {
     }
     unsigned long long h[8]; unsigned hex[4];
     CK(hipMemcpy(h, counters, 64, hipMemcpyDeviceToHost)); CK(hipMemcpy(hex, ex, 16, hipMemcpyDeviceToHost));
-    printf("divisor significands %u x 2 binades, pairs %llu (denormal quotients %llu, quotients that round to zero %llu): mismatches outside the suspects = %llu, "
-           "suspects = %llu (%.3f %% of the pairs, %.1f %% of the denormal quotients), suspects that differ from the IEEE quotient = %llu, of them with a zero remainder = %llu\n",
+    printf("divisor significands %u x 2 binades, pairs %llu (denormal quotients %llu, quotients that round to zero %llu): mismatches = %llu; "
+           "for the record, the two-rounding form's suspects = %llu (%.3f %% of the pairs, %.1f %% of the denormal quotients), of them wrong in that form = %llu, wrong in this one = %llu\n",
            total, h[0], h[4], h[6], h[1], h[2], 100.0 * h[2] / (h[0] ? h[0] : 1), 100.0 * h[2] / (h[4] ? h[4] : 1), h[3], h[5]);
     if (h[1]) printf("first mismatch: n = 0x%08x d = 0x%08x got 0x%08x\n", hex[1], hex[2], hex[3]);
     return h[1] || h[5] ? 1 : 0;
