@@ -36,6 +36,10 @@
 //                                 before the estimate by --region-fill "x,y;x,y;...:id" (a lasso, rtdd_fill_polygon under the --fill-rule in
 //                                 force) and --region-wand "x,y,tol:id" (a click, rtdd_fill_similar on the photograph under the
 //                                 --wand-connect in force), the fills first, each kind in command-line order
+//     --layer sprite --layer-alpha alpha --layer-at x,y [--layer-scale S] [--layer-filter nearest|bilinear] [--layer-depth z | --layer-plane
+//                                 x0,y0,z0,x1,y1,z1] [--layer-feather f] [--layer-opacity o] = extension: a sprite inserted into the scene at
+//                                 a depth (rtdd_composite_layer), after the estimate and before --effect, which then runs on the composite and
+//                                 ITS depth map; without --effect <out>ArtisticEffect is the composite; not with --live
 // and adds what the reference cannot do: --devices N --batch B runs B independent estimates
 // round-robin over N GPUs, one host thread + one HIP stream + one rtdd_ctx per GPU, no collective.
 #include <hip/hip_runtime.h>
@@ -246,6 +250,12 @@ struct Job {
     std::vector<Lasso> region_fills;
     std::vector<Wand> region_wands;
     bool edges_color = false;     // --edges color: the estimates read their edge weights from the BGR image (rtdd_pyramid_set_guide); default gray: the reference's
+    // --layer sprite --layer-alpha alpha --layer-at x,y [--layer-scale S] [--layer-filter nearest|bilinear] [--layer-depth z | --layer-plane
+    // x0,y0,z0,x1,y1,z1] [--layer-feather f] [--layer-opacity o]: rtdd_composite_layer after the estimate; --effect then runs on the composite
+    // and ITS depth map.  sprite: B, G, R, A interleaved, rows and cols in `layer`
+    bool has_layer = false;
+    std::vector<unsigned char> sprite;
+    rtdd_layer layer = {0, 0, 0, 0, 256, RTDD_LAYER_NEAREST, 255, 0, 0, 0, 0, 128.0f, 128.0f, 0.0f};
 };
 
 // --stroke / --erase / --ramp: the job's strokes on a device image pair, one call
@@ -471,9 +481,13 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
     // everything this function owns, released on EVERY return path (the CK() early returns included)
     struct Owned {
         rtdd_ctx *ctx = nullptr; hipStream_t stream = nullptr; unsigned char *d_bgr = nullptr, *d_ann = nullptr;
+        unsigned char *d_sprite = nullptr, *d_lart = nullptr; float *d_lz = nullptr;      // --layer: the sprite, the composite and its depth map
         ~Owned() {
             if (d_bgr) (void)hipFree(d_bgr);
             if (d_ann) (void)hipFree(d_ann);
+            if (d_sprite) (void)hipFree(d_sprite);
+            if (d_lart) (void)hipFree(d_lart);
+            if (d_lz) (void)hipFree(d_lz);
             if (ctx) rtdd_ctx_destroy(ctx);           // synchronises the stream first
             if (stream) (void)hipStreamDestroy(stream);
         }
@@ -488,7 +502,7 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
     CK(rtdd_load_weights(ctx, 0.4f));                                   // main.cpp:152-155
     // --batch B without an effect or a refinement: this device's images as ONE batched pyramid -- every level of all of them in the same
     // launches (rtdd_estimate_depth_batch: the coarse levels of one 1080p image use a quarter of the chip)
-    const bool batched = !live && count > 1 && !job.sequential && job.effect.empty() && job.refine.empty();
+    const bool batched = !live && count > 1 && !job.sequential && job.effect.empty() && job.refine.empty() && !job.has_layer;
     if (batched) {
         CK(rtdd_pyramid_create_batch(ctx, rows, cols, count));
         if (job.edges_color) CK(rtdd_pyramid_set_guide(ctx, RTDD_GUIDE_BGR));
@@ -543,6 +557,12 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
     CK(rtdd_pyramid_image(ctx, RTDD_IMG_DEPTH, 0, &p_depth, &pi_depth, nullptr, nullptr));
     CK(rtdd_pyramid_image(ctx, RTDD_IMG_ARTISTIC, 0, &p_art, &pi_art, nullptr, nullptr));
     CK(rtdd_pyramid_image(ctx, RTDD_IMG_DEPTH_U8, 0, &p_u8, &pi_u8, nullptr, nullptr));
+    if (job.has_layer) {                                                // --layer: the sprite goes up once; the composite and its depth map get images of their own
+        const size_t sw = (size_t)job.layer.cols * 4;
+        if (hipMalloc((void **)&own.d_sprite, sw * job.layer.rows) != hipSuccess || hipMalloc((void **)&own.d_lart, (size_t)rows * cols * 3) != hipSuccess ||
+            hipMalloc((void **)&own.d_lz, (size_t)rows * cols * 4) != hipSuccess) { std::printf("device %d: out of memory\n", device); return RTDD_ERR_NOMEM; }
+        CK(rtdd_upload(ctx, own.d_sprite, sw, job.sprite.data(), sw, sw, job.layer.rows));
+    }
 
     // --live N: the reference's frame loop as it clocks it (main.cpp:232-295) -- every frame uploads the host's scribble and edited
     // images (:236-237), estimates, downloads the u8 map (:290-291) -- two frames in flight (rtdd_live_submit_ex): the copies of one frame
@@ -645,6 +665,16 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
             if (n == 0 && job.refine == "auto") std::printf("refine auto: %d cycles + %d sweeps, residual %g\n", si.cycles, si.iterations, si.residual);
             else if (n == 0) std::printf("refine %s: %d %s, residual %g\n", job.refine.c_str(), si.iterations, job.refine == "mg" ? "cycles" : "sweeps", si.residual);
         }
+        // --layer: the sprite is inserted after the estimate; the effect below then reads the composite and the composite's depth map
+        // (desaturation's gray image stays the photograph's)
+        void *const l_orig = job.has_layer ? (void *)own.d_lart : p_orig, *const l_depth = job.has_layer ? (void *)own.d_lz : p_depth;
+        const size_t li_orig = job.has_layer ? (size_t)cols * 3 : pi_orig, li_depth = job.has_layer ? (size_t)cols * 4 : pi_depth;
+        if (job.has_layer)
+            CK(rtdd_composite_layer(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, own.d_sprite, (size_t)job.layer.cols * 4, own.d_lart, li_orig,
+                                    own.d_lz, li_depth, rows, cols, &job.layer));
+        {
+        void *const p_orig = l_orig, *const p_depth = l_depth;          // (the names the effect calls below use)
+        const size_t pi_orig = li_orig, pi_depth = li_depth;
         if (job.effect == "defocus") CK(rtdd_simulate_defocus(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols));
         else if (job.effect == "desaturation") CK(rtdd_simulate_desaturation(ctx, (uint8_t *)p_orig, pi_orig, (uint8_t *)p_gray, pi_gray, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols));
         else if (job.effect == "haze" && job.haze_ex)
@@ -690,9 +720,11 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
             ao.relief = job.light.relief;
             CK(rtdd_simulate_ambient_occlusion(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols, &ao, nullptr));
         }
+        }
         depth_u8->resize((size_t)rows * cols);
         CK(rtdd_download(ctx, depth_u8->data(), cols, p_u8, pi_u8, cols, rows));   // main.cpp:291 (synchronises)
         if (!job.effect.empty()) { art->resize((size_t)rows * cols * 3); CK(rtdd_download(ctx, art->data(), (size_t)cols * 3, p_art, pi_art, (size_t)cols * 3, rows)); }
+        else if (job.has_layer) { art->resize((size_t)rows * cols * 3); CK(rtdd_download(ctx, art->data(), (size_t)cols * 3, l_orig, li_orig, (size_t)cols * 3, rows)); }     // no effect: the composite itself
         if (every_map) every_map->push_back(*depth_u8);                 // --write-all: the n-th estimate of this device
     }
     *ms_per_estimate = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / (count > 0 ? count : 1);
@@ -710,6 +742,7 @@ int main(int argc, const char *argv[]) {
                                  "                    [--shadows N [--shadow-bias B] [--shadow-softness S] [--shadow-strength T]] (relight with cast shadows)\n"
                                  "                    [--ao-radius R] [--ao-directions 4|8] [--ao-bias B] [--ao-strength T] [--relief S] [--ao-map] (ao)  [--ao R [--ao-directions ..] [--ao-bias ..] [--ao-strength ..]] (relight with its ambient term occluded)\n"
                                  "                    [relight's light flags] [--shadows N (256)] [--shadow-bias B] [--shadow-softness S] [--shadow-strength T] [--ao R (16)] [--ao-directions 4|8] [--ao-bias B] [--ao-strength T] (lighting: shade, cast shadows and occlusion in one call)\n"
+                                 "                    [--layer sprite.(ppm|png|jpg) [--layer-alpha alpha.(pgm|png)] --layer-at x,y [--layer-scale S (256)] [--layer-filter nearest|bilinear] [--layer-depth z (128) | --layer-plane x0,y0,z0,x1,y1,z1] [--layer-feather f] [--layer-opacity o (255)]]   (a sprite inserted at a depth after the estimate, rtdd_composite_layer: --effect then runs on the composite and its depth map; without --effect ArtisticEffect is the composite)\n"
                                  "                    [--paint x,y,label,radius]... [--live N [--paint-at frame:x,y,label,radius]...] [--devices D --batch B [--sequential] [--write-all]] [--png] [--cold] [--edges gray|color] [--regions cut|smooth|both [--region-fill x,y;...:id]... [--region-wand x,y,tol:id]...]\n"
                                  "                    [--stroke x0,y0,x1,y1,label,radius[,round]]... [--erase x0,y0,x1,y1,radius[,round]]...   (segments, in command-line order, one rtdd_paint_strokes call after --paint)\n"
                                  "                    [--ramp x0,y0,x1,y1,label0,label1,radius[,round]]...   (a depth ramp: label0 at x0,y0 to label1 at x1,y1; in order with --stroke / --erase, all of them one rtdd_paint_ramp_strokes call)\n"
@@ -724,7 +757,8 @@ int main(int argc, const char *argv[]) {
     }
     Job job;
     std::string in, an, out = "";
-    bool png = false, write_all = false, shadow_opt = false, ao_opt = false, ao_radius_opt = false;
+    bool png = false, write_all = false, shadow_opt = false, ao_opt = false, ao_radius_opt = false, layer_at = false, layer_opt = false;
+    std::string layer_path, layer_alpha_path;
     int devices = 1, batch = 1, live = 0;
     for (int i = 1; i < argc; i++) {
         auto next = [&]() -> const char * { return i + 1 < argc ? argv[++i] : ""; };
@@ -846,6 +880,24 @@ int main(int argc, const char *argv[]) {
             for (int k = 0; k < 3; k++) if (c[k] < 0 || c[k] > 255) { std::printf("--light-color: each of b,g,r must be 0..255\n"); return 1; }
             job.light.colorB = (uint8_t)c[0]; job.light.colorG = (uint8_t)c[1]; job.light.colorR = (uint8_t)c[2];
         }
+        else if (!std::strcmp(argv[i], "--layer")) layer_path = next();
+        else if (!std::strcmp(argv[i], "--layer-alpha")) { layer_alpha_path = next(); layer_opt = true; }
+        else if (!std::strcmp(argv[i], "--layer-at")) { if (std::sscanf(next(), "%d,%d", &job.layer.x, &job.layer.y) != 2) { std::printf("--layer-at wants x,y\n"); return 1; } layer_at = layer_opt = true; }
+        else if (!std::strcmp(argv[i], "--layer-scale")) { job.layer.scale = std::atoi(next()); layer_opt = true; }
+        else if (!std::strcmp(argv[i], "--layer-filter")) {
+            const char *v = next();
+            if (!std::strcmp(v, "bilinear")) job.layer.filter = RTDD_LAYER_BILINEAR;
+            else if (std::strcmp(v, "nearest")) { std::printf("--layer-filter wants nearest or bilinear\n"); return 1; }
+            layer_opt = true;
+        }
+        else if (!std::strcmp(argv[i], "--layer-depth")) { job.layer.depth0 = job.layer.depth1 = (float)std::atof(next()); job.layer.x0 = job.layer.y0 = job.layer.x1 = job.layer.y1 = 0; layer_opt = true; }
+        else if (!std::strcmp(argv[i], "--layer-plane")) {
+            rtdd_layer &q = job.layer;
+            if (std::sscanf(next(), "%d,%d,%f,%d,%d,%f", &q.x0, &q.y0, &q.depth0, &q.x1, &q.y1, &q.depth1) != 6) { std::printf("--layer-plane wants x0,y0,z0,x1,y1,z1\n"); return 1; }
+            layer_opt = true;
+        }
+        else if (!std::strcmp(argv[i], "--layer-feather")) { job.layer.feather = (float)std::atof(next()); layer_opt = true; }
+        else if (!std::strcmp(argv[i], "--layer-opacity")) { job.layer.opacity = std::atoi(next()); layer_opt = true; }
         else if (!std::strcmp(argv[i], "--haze-beta")) { job.haze_beta = (float)std::atof(next()); job.haze_ex = true; }
         else if (!std::strcmp(argv[i], "--airlight")) {
             if (std::sscanf(next(), "%d,%d,%d", &job.air[0], &job.air[1], &job.air[2]) != 3) { std::printf("--airlight wants b,g,r\n"); return 1; }
@@ -869,6 +921,22 @@ int main(int argc, const char *argv[]) {
     if (live > 0 && (job.effect == "refocus" || job.effect == "stereo" || job.effect == "parallax" || job.effect == "relight" || job.effect == "ao" || lighting || (job.effect == "haze" && job.haze_ex))) {
         std::printf("--live renders the reference's three effects only: --effect refocus, --effect stereo, --effect parallax, --effect relight, --effect ao, --effect lighting and --haze-beta / --airlight are not supported with --live\n");
         return 1;
+    }
+    // a layer is a sprite and where it lands; its parameters belong to it: a stray one is refused, not dropped.  A live frame renders no layer
+    if (layer_opt && layer_path.empty()) { std::printf("--layer-alpha, --layer-at, --layer-scale, --layer-filter, --layer-depth, --layer-plane, --layer-feather and --layer-opacity need --layer sprite\n"); return 1; }
+    if (!layer_path.empty() && !layer_at) { std::printf("--layer needs --layer-at x,y\n"); return 1; }
+    if (live > 0 && !layer_path.empty()) { std::printf("--layer is not supported with --live\n"); return 1; }
+    if (!layer_path.empty()) {
+        Pnm s, a;
+        if (!read_image(layer_path, s) || s.ch != 3) { std::printf("cannot read %s as a colour image (binary PPM, 8-bit PNG or JPEG)\n", layer_path.c_str()); return 2; }
+        if (!layer_alpha_path.empty() && (!read_image(layer_alpha_path, a) || a.ch != 1 || a.w != s.w || a.h != s.h)) { std::printf("cannot read %s as a gray image of the sprite's size\n", layer_alpha_path.c_str()); return 2; }
+        job.layer.rows = s.h; job.layer.cols = s.w;
+        job.sprite.resize((size_t)s.w * s.h * 4);
+        for (size_t i = 0; i < (size_t)s.w * s.h; i++) {                     // the file is RGB; no --layer-alpha: opaque
+            job.sprite[4 * i] = s.px[3 * i + 2]; job.sprite[4 * i + 1] = s.px[3 * i + 1]; job.sprite[4 * i + 2] = s.px[3 * i];
+            job.sprite[4 * i + 3] = layer_alpha_path.empty() ? 255 : a.px[i];
+        }
+        job.has_layer = true;
     }
     Pnm rgb;
     if (!read_image(in, rgb)) { std::printf("cannot read %s as a binary PPM / PGM, an 8-bit PNG or a JPEG\n", in.c_str()); return 2; }
@@ -922,7 +990,7 @@ int main(int argc, const char *argv[]) {
         for (size_t i = 0; i + 2 < o.size(); i += 3) { o[i] = annotated[0][i + 2]; o[i + 2] = annotated[0][i]; }     // BGR -> RGB for the file
         if (!o.empty() && !write_image(out + (png ? "AnnotatedImage.png" : "AnnotatedImage.ppm"), rgb.w, rgb.h, 3, o.data())) return 5;
     }
-    if (!job.effect.empty()) {
+    if (!job.effect.empty() || job.has_layer) {                          // (--layer without --effect: the composite)
         std::vector<unsigned char> o(art[0]);
         for (size_t i = 0; i < o.size(); i += 3) { o[i] = art[0][i + 2]; o[i + 2] = art[0][i]; }     // BGR -> RGB for the file
         if (!write_image(out + (png ? "ArtisticEffect.png" : "ArtisticEffect.ppm"), rgb.w, rgb.h, 3, o.data())) return 5;

@@ -544,7 +544,8 @@ int rtdd_simulate_haze(rtdd_ctx *ctx, const uint8_t *original, size_t originalPi
 /* ---- aimed depth effects (extensions; no reference behaviour) --------------------------------
  * Added after ABI version 230 without a version bump: a host finds them by symbol (dlsym).  The next bump of RTDD_VERSION
  * should cover them (rtdd_simulate_refocus, rtdd_simulate_lens_blur, rtdd_simulate_haze_ex, rtdd_simulate_stereo, rtdd_simulate_relight,
- * rtdd_simulate_relight_shadowed, rtdd_simulate_parallax, rtdd_simulate_ambient_occlusion, rtdd_simulate_lighting, rtdd_simulate_bokeh),
+ * rtdd_simulate_relight_shadowed, rtdd_simulate_parallax, rtdd_simulate_ambient_occlusion, rtdd_simulate_lighting, rtdd_simulate_bokeh,
+ * rtdd_composite_layer),
  * together with a
  * parameterised live effect
  * (rtdd_live_submit_ex takes an effect code only and knows none of them). */
@@ -854,6 +855,60 @@ int rtdd_simulate_lighting(rtdd_ctx *ctx, const uint8_t *original, size_t origin
                            const float *depth, size_t depthPitch, uint8_t *artistic, size_t artisticPitch,
                            int rows, int cols, const rtdd_light *light, const rtdd_shadow *shadow,
                            const rtdd_ambient_occlusion *ao /* all three HOST, read before the call returns */);
+
+/* Composite a layer: a SPRITE (u8 x 4: B, G, R, A; straight alpha) is inserted into the photograph at a depth, and the scene's own depth
+ * map hides the parts of it that lie behind nearer things -- a title behind the subject, an object on the floor, a logo on the far wall.
+ * The call also writes the composite's depth map (the layer's depth where the layer won, the scene's elsewhere), so that every effect
+ * above treats the inserted object as part of the scene: artistic and depthOut of this call are original and depth of the next one,
+ * another layer included (one layer per call).  Depth 0 is near, 255 far, as every effect reads it.  Integers are exact; every f32
+ * operation below is one operation, rounded once, NONE fused; / on floats is IEEE correctly rounded.  Per image pixel (px, py):
+ *   1. SPRITE COORDINATE in 1/256 texel, floor division in 64 bits:
+ *        U = floor(((2 (px - x) + 1) * 32768) / scale) - 128          V likewise from py, y
+ *      (the pixel's centre, in texels the texel centres at the integers).  The pixel is COVERED iff 0 <= U + 128 < 256 * layer.cols and
+ *      0 <= V + 128 < 256 * layer.rows.  An uncovered pixel gets artistic = original and depthOut = depth: the depth's bits are copied,
+ *      a NaN included.
+ *   2. SAMPLE (c_B, c_G, c_R, a):
+ *      RTDD_LAYER_NEAREST:  the texel (floor((U + 128) / 256), floor((V + 128) / 256)) as it is.
+ *      RTDD_LAYER_BILINEAR: iu = floor(U / 256), fu = U - 256 iu, likewise iv, fv; the four taps (iu | iu + 1, iv | iv + 1), each index
+ *        clamped into the sprite; tap weights w = (256 - fu | fu) * (256 - fv | fv), which sum to 65536.  The interpolation is
+ *        ALPHA-WEIGHTED, so a transparent texel's colour never bleeds:  A = sum of w a,  C_c = sum of w a c  (A < 2^24, C_c < 2^32);
+ *        a = (A + 32768) >> 16;  c = A ? (C_c + (A >> 1)) div A : 0.
+ *   3. LAYER DEPTH, a plane: dd = (x1-x0)^2 + (y1-y0)^2;  n = (px-x0)(x1-x0) + (py-y0)(y1-y0) clamped to [0, dd] (then n < 2^31);
+ *        z = dd ? depth0 + ((depth1 - depth0) * ((float)n / (float)dd)) : depth0
+ *   4. VISIBILITY v in 0 .. 256:  d' = fminf(fmaxf(d, 0), 255), a NaN depth is 0 (stereo's clamp);  diff = d' - z
+ *        feather == 0:  v = diff >= 0 ? 256 : 0                       (at equal depth the layer is in front)
+ *        otherwise:     t = (diff / feather) + 0.5f;  v = (int)(fminf(fmaxf(t, 0), 1) * 256.0f)
+ *   5. BLEND, exact in 32 bits unsigned:  e = a * opacity * v  (<= E = 255 * 255 * 256 = 16646400);
+ *        per channel c of B, G, R:  out_c = (c_c * e + o_c * (E - e) + E / 2) div E
+ *   6. DEPTH OUT:  depthOut = (2 e >= E) ? z : d                       (d itself, not d': bits copied)
+ * Identities: opacity 0, a sprite of alpha 0, or a layer behind everything (depth 255, feather 0, every d < 255) give the original and
+ * a bit copy of the depth; RTDD_LAYER_BILINEAR at scale 256 is RTDD_LAYER_NEAREST (fu = fv = 0); an opaque sprite at depth 0 with
+ * feather 0 and opacity 255 is a paste.  No mip-mapping: a sprite minified below roughly 1/2 (scale < 128) aliases.  A sprite that lands
+ * wholly outside the image is not an error: the call then copies.
+ * One kernel launch that stores every pixel of artistic, and of depthOut when given, exactly once; asynchronous, stream-ordered,
+ * deterministic; the output does not depend on RTDD_OPT_FP_CONTRACT.  Not in place: a healed time-out runs the call again, and the second
+ * run must read what the first one read.  RTDD_VERSION is unchanged: a host finds the symbol by name.
+ * Refused on the host (RTDD_ERR_INVALID), before any launch: the rules of the three effects (null pointers, pitches, image size; the
+ * f32 alignment rule for depthOut too, and depthOutPitch >= 4 * cols); original == artistic; depth == depthOut; a null layer; a null
+ * sprite, or spritePitch < 4 * layer.cols; any field outside the ranges below; an unknown filter; a non-finite float. */
+enum rtdd_layer_filter { RTDD_LAYER_NEAREST = 0, RTDD_LAYER_BILINEAR = 1 };
+typedef struct rtdd_layer {
+    int   rows, cols;           /* the sprite's size in texels, 1 .. 16384 each */
+    int   x, y;                 /* where the sprite's top-left corner lands in the image, each in [-16384, 16383]; may lie outside */
+    int   scale;                /* size on screen in 1/256: 256 = texel for pixel; 16 .. 4096 */
+    int   filter;               /* enum rtdd_layer_filter */
+    int   opacity;              /* 0 .. 255 */
+    int   x0, y0, x1, y1;       /* the layer's depth is a plane: depth0 at (x0, y0), depth1 at (x1, y1); image coordinates, each in
+                                   [-16384, 16383]; (x0, y0) == (x1, y1): the constant depth0 */
+    float depth0, depth1;       /* finite, in [0, 255] */
+    float feather;              /* finite, >= 0: the depth interval over which the scene takes over from the layer; 0: a hard edge */
+} rtdd_layer;                   /* 56 bytes, ints and floats only */
+int rtdd_composite_layer(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch,
+                         const float *depth, size_t depthPitch,
+                         const uint8_t *sprite, size_t spritePitch,     /* DEVICE, u8 x 4 */
+                         uint8_t *artistic, size_t artisticPitch,
+                         float *depthOut, size_t depthOutPitch,         /* may be NULL: no depth is written */
+                         int rows, int cols, const rtdd_layer *layer /* HOST, read before the call returns */);
 
 /* ---- whole-estimate driver ------------------------------------------------
  * One depth estimate = the loop body of src/main.cpp:232-295, run as a single stream-ordered launch

@@ -54,7 +54,7 @@ C_ABI_SYMBOLS = [
     "rtdd_simulate_refocus", "rtdd_simulate_haze_ex", "rtdd_simulate_stereo", "rtdd_simulate_lens_blur",
     "rtdd_paint_strokes", "rtdd_pyramid_annotation_rebuild", "rtdd_paint_ramp_strokes", "rtdd_ramp_polyline", "rtdd_fill_polygon", "rtdd_fill_similar",
     "rtdd_simulate_relight", "rtdd_simulate_relight_shadowed", "rtdd_simulate_parallax", "rtdd_simulate_ambient_occlusion",
-    "rtdd_simulate_lighting", "rtdd_simulate_bokeh",
+    "rtdd_simulate_lighting", "rtdd_simulate_bokeh", "rtdd_composite_layer",
     "rtdd_solve_guided", "rtdd_index_to_weight_guided", "rtdd_pyrdown_bgr", "rtdd_pyramid_set_guide", "rtdd_pyramid_guide",
     "rtdd_solve_regions", "rtdd_index_to_weight_regions", "rtdd_region_codes", "rtdd_pyramid_set_regions", "rtdd_pyramid_regions",
     "rtdd_pyramid_regions_changed",
@@ -68,6 +68,7 @@ STEREO_VIEW, STEREO_ANAGLYPH = 0, 1           # rtdd_simulate_stereo's modes
 APERTURE_BOX, APERTURE_DISC = 0, 1            # rtdd_simulate_lens_blur's shapes
 LIGHT_DIRECTIONAL, LIGHT_POINT = 0, 1         # rtdd_light.kind
 AO_SHADE, AO_MAP = 0, 1                       # rtdd_ambient_occlusion.mode
+LAYER_NEAREST, LAYER_BILINEAR = 0, 1          # rtdd_layer.filter
 BRUSH_SQUARE, BRUSH_ROUND = 0, 1              # rtdd_stroke.brush
 STROKE_ERASE = -1                             # rtdd_stroke.label: remove the annotation
 FILL_NONZERO, FILL_EVEN_ODD = 0, 1            # rtdd_fill.rule
@@ -187,6 +188,19 @@ class AmbientOcclusion(C.Structure):
 
     def __init__(self, mode=AO_SHADE, directions=8, radius=16, relief=1.0, bias=0.0, strength=1.0):
         super().__init__(mode, directions, radius, relief, bias, strength)
+
+
+class Layer(C.Structure):
+    """rtdd_layer: a sprite of rows x cols texels whose top-left corner lands at image pixel (x, y), `scale` / 256 pixels per texel,
+    LAYER_NEAREST or LAYER_BILINEAR, `opacity` 0..255; its depth is a plane, depth0 at (x0, y0) and depth1 at (x1, y1) (the same point:
+    the constant depth0); `feather` is the depth interval over which the scene takes over from the layer (0: a hard edge)."""
+    _fields_ = [("rows", C.c_int), ("cols", C.c_int), ("x", C.c_int), ("y", C.c_int), ("scale", C.c_int), ("filter", C.c_int),
+                ("opacity", C.c_int), ("x0", C.c_int), ("y0", C.c_int), ("x1", C.c_int), ("y1", C.c_int), ("depth0", C.c_float),
+                ("depth1", C.c_float), ("feather", C.c_float)]
+
+    def __init__(self, rows=1, cols=1, x=0, y=0, scale=256, filter=LAYER_NEAREST, opacity=255, x0=0, y0=0, x1=0, y1=0, depth0=0.0,
+                 depth1=0.0, feather=0.0):
+        super().__init__(rows, cols, x, y, scale, filter, opacity, x0, y0, x1, y1, depth0, depth1, feather)
 
 
 class Profile(C.Structure):
@@ -557,6 +571,16 @@ class Context:
                                                  C.byref(light) if light is not None else None,
                                                  C.byref(shadow) if shadow is not None else None,
                                                  C.byref(ao) if ao is not None else None))
+
+    def composite_layer(self, originalImage, depthImage, spriteImage, artisticImage, depthOutImage, rows, cols, layer):
+        """A sprite (u8 x 4: B, G, R, A; straight alpha) inserted into the scene as `layer` (a Layer, or None for the C call's null
+        pointer) says: the depth map hides what lies behind nearer things.  depthOutImage (None: not written) receives the composite's
+        depth map -- the layer's depth where the layer won, the scene's elsewhere -- for the effects that follow."""
+        o, op = _img(originalImage); d, dp = _img(depthImage); a, ap = _img(artisticImage)
+        s, sp = _img(spriteImage) if spriteImage is not None else (None, C.c_size_t(0))
+        z, zp = _img(depthOutImage) if depthOutImage is not None else (None, C.c_size_t(0))
+        self._check(lib().rtdd_composite_layer(self._h, o, op, d, dp, s, sp, a, ap, z, zp, C.c_int(rows), C.c_int(cols),
+                                               C.byref(layer) if layer is not None else None))
 
     # ---- whole-estimate driver (src/main.cpp:92-155, 232-295)
     def pyramid_create(self, rows, cols):

@@ -305,5 +305,43 @@ int rtdd_simulate_lighting(rtdd_ctx *ctx, const uint8_t *original, size_t origin
     return simulate(ctx, e);
 }
 
+// How many pixels p = origin, origin + 1, ... a sprite axis of `texels` texels covers (include/rtdd.h rtdd_composite_layer, step 1):
+// those with (2 (p - origin) + 1) * 32768 < 256 * texels * scale, i.e. 2 (p - origin) + 1 < texels * scale / 128.
+static int layer_extent(int texels, int scale) { return (texels * scale + 127) / 256; }        // (texels * scale <= 2^26)
+
+int rtdd_composite_layer(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
+                         const uint8_t *sprite, size_t spritePitch, uint8_t *artistic, size_t artisticPitch, float *depthOut,
+                         size_t depthOutPitch, int rows, int cols, const rtdd_layer *layer) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    int rc = check_effect(ctx, original, depth, artistic, originalPitch, depthPitch, artisticPitch, rows, cols);
+    if (rc != RTDD_OK) return rc;
+    if (depthOut) {
+        REQUIRE(ctx, depthOutPitch >= (size_t)cols * 4, "pitch smaller than a row");
+        REQUIRE(ctx, f32_image_aligned(depthOut, depthOutPitch), kF32AlignText);
+    }
+    REQUIRE(ctx, original != artistic && (const float *)depthOut != depth, "a layer cannot be composited in place");
+    REQUIRE(ctx, layer, "null layer");
+    const rtdd_layer &q = *layer;
+    REQUIRE(ctx, q.rows >= 1 && q.rows <= 16384 && q.cols >= 1 && q.cols <= 16384, "the sprite's rows or cols outside [1, 16384]");
+    REQUIRE(ctx, sprite && spritePitch >= (size_t)q.cols * 4, "bad sprite image");
+    for (int v : {q.x, q.y, q.x0, q.y0, q.x1, q.y1}) REQUIRE(ctx, v >= -16384 && v <= 16383, "a layer coordinate outside [-16384, 16383]");
+    REQUIRE(ctx, q.scale >= 16 && q.scale <= 4096, "scale outside [16, 4096]");
+    REQUIRE(ctx, q.filter == RTDD_LAYER_NEAREST || q.filter == RTDD_LAYER_BILINEAR, "filter must be RTDD_LAYER_NEAREST or RTDD_LAYER_BILINEAR");
+    REQUIRE(ctx, q.opacity >= 0 && q.opacity <= 255, "opacity outside [0, 255]");
+    for (float v : {q.depth0, q.depth1, q.feather}) REQUIRE(ctx, std::isfinite(v), "a non-finite value in the layer");
+    REQUIRE(ctx, q.depth0 >= 0.0f && q.depth0 <= 255.0f && q.depth1 >= 0.0f && q.depth1 <= 255.0f, "depth0 or depth1 outside [0, 255]");
+    REQUIRE(ctx, q.feather >= 0.0f, "feather must be >= 0");
+    if (rows == 0 || cols == 0) return RTDD_OK;
+    Effect e{Effect::kComposite, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols};
+    Effect::Composite &k = e.composite;
+    k.layer = q; k.sprite = sprite; k.spritePitch = spritePitch;
+    k.depthOut = depthOut; k.depthOutPitch = depthOut ? depthOutPitch : 0;
+    // the footprint, clipped to the image; a sprite wholly outside leaves it empty (all 0) and the launch copies
+    const int fx0 = std::max(q.x, 0), fx1 = std::min(q.x + layer_extent(q.cols, q.scale), cols);
+    const int fy0 = std::max(q.y, 0), fy1 = std::min(q.y + layer_extent(q.rows, q.scale), rows);
+    if (fx0 < fx1 && fy0 < fy1) { k.fx0 = fx0; k.fy0 = fy0; k.fx1 = fx1; k.fy1 = fy1; }
+    return simulate(ctx, e);
+}
+
 }  // extern "C"
 #pragma GCC visibility pop

@@ -101,8 +101,8 @@ struct LiveTargets {
 // One depth effect, arguments checked: what to render, on which images, with which parameters.  Built by the rtdd_simulate_* entry
 // points (effects_api.cpp) and by a live frame (live_effect), launched by launch_effect, and logged by value (PendingOp) to be launched again.
 struct Effect {
-    enum : int { kRefocus = RTDD_EFFECT_HAZE + 1, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow, kParallax, kAmbientOcclusion, kLighting, kBokeh };   // the extensions, after the public kinds
-    int kind = RTDD_EFFECT_NONE;                    // RTDD_EFFECT_DEFOCUS / _DESATURATION / _HAZE, kRefocus, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow, kParallax, kAmbientOcclusion, kLighting, kBokeh
+    enum : int { kRefocus = RTDD_EFFECT_HAZE + 1, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow, kParallax, kAmbientOcclusion, kLighting, kBokeh, kComposite };   // the extensions, after the public kinds
+    int kind = RTDD_EFFECT_NONE;                    // RTDD_EFFECT_DEFOCUS / _DESATURATION / _HAZE, kRefocus, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow, kParallax, kAmbientOcclusion, kLighting, kBokeh, kComposite
     const uint8_t *original = nullptr; size_t originalPitch = 0;
     const float *depth = nullptr; size_t depthPitch = 0;
     uint8_t *artistic = nullptr; size_t artisticPitch = 0;
@@ -147,6 +147,15 @@ struct Effect {
         float relief = 0.0f, bias = 0.0f, strength = 0.0f;
         bool lit = false;
     } occlusion = {};
+    // a composited layer (kComposite): rtdd_layer as the entry point checked it (include/rtdd.h rtdd_composite_layer), the sprite and the
+    // second output, by value -- a replay needs no rtdd_layer.  The footprint: the image pixels [fx0, fx1) x [fy0, fy1) the sprite covers,
+    // clipped to the image (all 0: none, the launch copies); a pixel outside it is uncovered, one inside it is tested by the kernel
+    struct Composite {
+        rtdd_layer layer = {};
+        const uint8_t *sprite = nullptr; size_t spritePitch = 0;
+        float *depthOut = nullptr; size_t depthOutPitch = 0;       // null: no depth is written
+        int fx0 = 0, fy0 = 0, fx1 = 0, fy1 = 0;
+    } composite = {};
 };
 
 // The defocus window scale K of src/GPUDepthEffect.cu:42, (int)(aperture * diagonal) -- double * float and the int products as there,
@@ -437,6 +446,8 @@ int launch_ambient_occlusion(rtdd_ctx *ctx, const Effect &e);
 int launch_lighting(rtdd_ctx *ctx, const Effect &e);
 // ---- bokeh.hip: Effect::kBokeh (called by launch_effect) -------------------------------------------
 int launch_bokeh(rtdd_ctx *ctx, const Effect &e);
+// ---- composite.hip: Effect::kComposite (called by launch_effect) -----------------------------------
+int launch_composite(rtdd_ctx *ctx, const Effect &e);
 
 // ---- cascade.hip -------------------------------------------------------------------------------
 int launch_bgr2gray(rtdd_ctx *ctx, const uint8_t *bgr, size_t bp, uint8_t *gray, size_t gp, int rows, int cols);
