@@ -40,6 +40,12 @@
 //                                 x0,y0,z0,x1,y1,z1] [--layer-feather f] [--layer-opacity o] = extension: a sprite inserted into the scene at
 //                                 a depth (rtdd_composite_layer), after the estimate and before --effect, which then runs on the composite and
 //                                 ITS depth map; without --effect <out>ArtisticEffect is the composite; not with --live
+//     --remove-region id [--remove-grow N] [--remove-behind D] = extension: the painted region `id` (--regions, --region-fill / --region-wand)
+//                                 taken out of the scene after the estimate (rtdd_remove_object; the mask is the region's code plane): the
+//                                 hole, grown by N, is filled from the pixels at least D far.  --move-region id:dx,dy[:depth] lifts the
+//                                 region (rtdd_lift_layer), removes it and composites it (dx, dy) away at `depth` (default: its own nearest
+//                                 depth, one constant).  Before --layer and --effect, which run on the result and ITS depth map; without
+//                                 them <out>ArtisticEffect is the result; not with --live
 // and adds what the reference cannot do: --devices N --batch B runs B independent estimates
 // round-robin over N GPUs, one host thread + one HIP stream + one rtdd_ctx per GPU, no collective.
 #include <hip/hip_runtime.h>
@@ -256,6 +262,13 @@ struct Job {
     bool has_layer = false;
     std::vector<unsigned char> sprite;
     rtdd_layer layer = {0, 0, 0, 0, 256, RTDD_LAYER_NEAREST, 255, 0, 0, 0, 0, 128.0f, 128.0f, 0.0f};
+    // --remove-region ID [--remove-grow N] [--remove-behind D]: rtdd_remove_object after the estimate, the region's code plane the mask;
+    // --move-region ID:dx,dy[:depth]: rtdd_lift_layer, rtdd_remove_object and rtdd_composite_layer of the sprite (dx, dy) away, at `depth`
+    // or at the region's own nearest depth.  Before --layer and --effect, which run on the result and ITS depth map
+    bool has_remove = false, has_move = false, move_has_depth = false;
+    rtdd_removal removal = {0, 0, 0.0f};                            // select: the region id
+    int move_dx = 0, move_dy = 0;
+    float move_depth = 0.0f;
 };
 
 // --stroke / --erase / --ramp: the job's strokes on a device image pair, one call
@@ -482,12 +495,18 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
     struct Owned {
         rtdd_ctx *ctx = nullptr; hipStream_t stream = nullptr; unsigned char *d_bgr = nullptr, *d_ann = nullptr;
         unsigned char *d_sprite = nullptr, *d_lart = nullptr; float *d_lz = nullptr;      // --layer: the sprite, the composite and its depth map
+        unsigned char *d_rart = nullptr, *d_msprite = nullptr, *d_mart = nullptr; float *d_rz = nullptr, *d_mz = nullptr;     // --remove-region / --move-region
         ~Owned() {
             if (d_bgr) (void)hipFree(d_bgr);
             if (d_ann) (void)hipFree(d_ann);
             if (d_sprite) (void)hipFree(d_sprite);
             if (d_lart) (void)hipFree(d_lart);
             if (d_lz) (void)hipFree(d_lz);
+            if (d_rart) (void)hipFree(d_rart);
+            if (d_rz) (void)hipFree(d_rz);
+            if (d_msprite) (void)hipFree(d_msprite);
+            if (d_mart) (void)hipFree(d_mart);
+            if (d_mz) (void)hipFree(d_mz);
             if (ctx) rtdd_ctx_destroy(ctx);           // synchronises the stream first
             if (stream) (void)hipStreamDestroy(stream);
         }
@@ -502,7 +521,7 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
     CK(rtdd_load_weights(ctx, 0.4f));                                   // main.cpp:152-155
     // --batch B without an effect or a refinement: this device's images as ONE batched pyramid -- every level of all of them in the same
     // launches (rtdd_estimate_depth_batch: the coarse levels of one 1080p image use a quarter of the chip)
-    const bool batched = !live && count > 1 && !job.sequential && job.effect.empty() && job.refine.empty() && !job.has_layer;
+    const bool batched = !live && count > 1 && !job.sequential && job.effect.empty() && job.refine.empty() && !job.has_layer && !job.has_remove && !job.has_move;
     if (batched) {
         CK(rtdd_pyramid_create_batch(ctx, rows, cols, count));
         if (job.edges_color) CK(rtdd_pyramid_set_guide(ctx, RTDD_GUIDE_BGR));
@@ -562,6 +581,12 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
         if (hipMalloc((void **)&own.d_sprite, sw * job.layer.rows) != hipSuccess || hipMalloc((void **)&own.d_lart, (size_t)rows * cols * 3) != hipSuccess ||
             hipMalloc((void **)&own.d_lz, (size_t)rows * cols * 4) != hipSuccess) { std::printf("device %d: out of memory\n", device); return RTDD_ERR_NOMEM; }
         CK(rtdd_upload(ctx, own.d_sprite, sw, job.sprite.data(), sw, sw, job.layer.rows));
+    }
+    if (job.has_remove || job.has_move) {                               // --remove-region / --move-region: the scene without the object, and where it is moved its sprite and the scene with it again
+        const size_t px = (size_t)rows * cols;
+        bool ok = hipMalloc((void **)&own.d_rart, px * 3) == hipSuccess && hipMalloc((void **)&own.d_rz, px * 4) == hipSuccess;
+        if (ok && job.has_move) ok = hipMalloc((void **)&own.d_msprite, px * 4) == hipSuccess && hipMalloc((void **)&own.d_mart, px * 3) == hipSuccess && hipMalloc((void **)&own.d_mz, px * 4) == hipSuccess;
+        if (!ok) { std::printf("device %d: out of memory\n", device); return RTDD_ERR_NOMEM; }
     }
 
     // --live N: the reference's frame loop as it clocks it (main.cpp:232-295) -- every frame uploads the host's scribble and edited
@@ -667,10 +692,40 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
         }
         // --layer: the sprite is inserted after the estimate; the effect below then reads the composite and the composite's depth map
         // (desaturation's gray image stays the photograph's)
-        void *const l_orig = job.has_layer ? (void *)own.d_lart : p_orig, *const l_depth = job.has_layer ? (void *)own.d_lz : p_depth;
-        const size_t li_orig = job.has_layer ? (size_t)cols * 3 : pi_orig, li_depth = job.has_layer ? (size_t)cols * 4 : pi_depth;
+        // --remove-region / --move-region come first: the region's code plane (level 0, written by the estimate) is the mask, the id selects.
+        // r_orig / r_depth: the scene without the object (--move-region: with it composited again where it went)
+        void *r_orig = p_orig, *r_depth = p_depth;
+        size_t ri_orig = pi_orig, ri_depth = pi_depth;
+        if (job.has_remove || job.has_move) {
+            void *p_code; size_t pi_code;
+            CK(rtdd_pyramid_image(ctx, RTDD_IMG_REGION_CODE, 0, &p_code, &pi_code, nullptr, nullptr));
+            const size_t w3 = (size_t)cols * 3, w4 = (size_t)cols * 4;
+            CK(rtdd_remove_object(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_code, pi_code, own.d_rart, w3, own.d_rz, w4, rows, cols, &job.removal));
+            r_orig = own.d_rart; r_depth = own.d_rz; ri_orig = w3; ri_depth = w4;
+            if (job.has_move) {
+                // the sprite is the whole image's box, so it covers the region wherever that lies; it lands (dx, dy) away
+                CK(rtdd_lift_layer(ctx, (uint8_t *)p_orig, pi_orig, (uint8_t *)p_code, pi_code, rows, cols, job.removal.select, 0, 0, own.d_msprite, w4, rows, cols));
+                rtdd_layer L = {rows, cols, job.move_dx, job.move_dy, 256, RTDD_LAYER_NEAREST, 255, 0, 0, 0, 0, job.move_depth, job.move_depth, 0.0f};
+                if (!job.move_has_depth) {
+                    // keep the region's own depth, as one constant: the nearest d' of its pixels, read from a download of the map and the codes
+                    std::vector<float> z((size_t)rows * cols); std::vector<unsigned char> code((size_t)rows * cols);
+                    CK(rtdd_download(ctx, z.data(), w4, p_depth, pi_depth, w4, rows));
+                    CK(rtdd_download(ctx, code.data(), cols, p_code, pi_code, cols, rows));
+                    float nearest = 255.0f;
+                    for (size_t i = 0; i < z.size(); i++)
+                        if (code[i] == job.removal.select) nearest = std::min(nearest, z[i] > 0.0f ? std::min(z[i], 255.0f) : 0.0f);
+                    L.depth0 = L.depth1 = nearest;
+                    if (n == 0) std::printf("move region %d by %d,%d at its own depth %g\n", job.removal.select, job.move_dx, job.move_dy, nearest);
+                }
+                CK(rtdd_composite_layer(ctx, own.d_rart, w3, own.d_rz, w4, own.d_msprite, w4, own.d_mart, w3, own.d_mz, w4, rows, cols, &L));
+                r_orig = own.d_mart; r_depth = own.d_mz;
+            }
+        }
+        const bool edited = job.has_layer || job.has_remove || job.has_move;
+        void *const l_orig = job.has_layer ? (void *)own.d_lart : r_orig, *const l_depth = job.has_layer ? (void *)own.d_lz : r_depth;
+        const size_t li_orig = job.has_layer ? (size_t)cols * 3 : ri_orig, li_depth = job.has_layer ? (size_t)cols * 4 : ri_depth;
         if (job.has_layer)
-            CK(rtdd_composite_layer(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, own.d_sprite, (size_t)job.layer.cols * 4, own.d_lart, li_orig,
+            CK(rtdd_composite_layer(ctx, (uint8_t *)r_orig, ri_orig, (float *)r_depth, ri_depth, own.d_sprite, (size_t)job.layer.cols * 4, own.d_lart, li_orig,
                                     own.d_lz, li_depth, rows, cols, &job.layer));
         {
         void *const p_orig = l_orig, *const p_depth = l_depth;          // (the names the effect calls below use)
@@ -724,7 +779,7 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
         depth_u8->resize((size_t)rows * cols);
         CK(rtdd_download(ctx, depth_u8->data(), cols, p_u8, pi_u8, cols, rows));   // main.cpp:291 (synchronises)
         if (!job.effect.empty()) { art->resize((size_t)rows * cols * 3); CK(rtdd_download(ctx, art->data(), (size_t)cols * 3, p_art, pi_art, (size_t)cols * 3, rows)); }
-        else if (job.has_layer) { art->resize((size_t)rows * cols * 3); CK(rtdd_download(ctx, art->data(), (size_t)cols * 3, l_orig, li_orig, (size_t)cols * 3, rows)); }     // no effect: the composite itself
+        else if (edited) { art->resize((size_t)rows * cols * 3); CK(rtdd_download(ctx, art->data(), (size_t)cols * 3, l_orig, li_orig, (size_t)cols * 3, rows)); }     // no effect: the composite itself
         if (every_map) every_map->push_back(*depth_u8);                 // --write-all: the n-th estimate of this device
     }
     *ms_per_estimate = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / (count > 0 ? count : 1);
@@ -743,6 +798,7 @@ int main(int argc, const char *argv[]) {
                                  "                    [--ao-radius R] [--ao-directions 4|8] [--ao-bias B] [--ao-strength T] [--relief S] [--ao-map] (ao)  [--ao R [--ao-directions ..] [--ao-bias ..] [--ao-strength ..]] (relight with its ambient term occluded)\n"
                                  "                    [relight's light flags] [--shadows N (256)] [--shadow-bias B] [--shadow-softness S] [--shadow-strength T] [--ao R (16)] [--ao-directions 4|8] [--ao-bias B] [--ao-strength T] (lighting: shade, cast shadows and occlusion in one call)\n"
                                  "                    [--layer sprite.(ppm|png|jpg) [--layer-alpha alpha.(pgm|png)] --layer-at x,y [--layer-scale S (256)] [--layer-filter nearest|bilinear] [--layer-depth z (128) | --layer-plane x0,y0,z0,x1,y1,z1] [--layer-feather f] [--layer-opacity o (255)]]   (a sprite inserted at a depth after the estimate, rtdd_composite_layer: --effect then runs on the composite and its depth map; without --effect ArtisticEffect is the composite)\n"
+                                 "                    [--remove-region id [--remove-grow N (0..8)] [--remove-behind D] | --move-region id:dx,dy[:depth] [--remove-grow N] [--remove-behind D]]   (with --regions: the painted region taken out of the scene, rtdd_remove_object, or moved, rtdd_lift_layer + rtdd_remove_object + rtdd_composite_layer; before --layer and --effect, which run on the result and its depth map)\n"
                                  "                    [--paint x,y,label,radius]... [--live N [--paint-at frame:x,y,label,radius]...] [--devices D --batch B [--sequential] [--write-all]] [--png] [--cold] [--edges gray|color] [--regions cut|smooth|both [--region-fill x,y;...:id]... [--region-wand x,y,tol:id]...]\n"
                                  "                    [--stroke x0,y0,x1,y1,label,radius[,round]]... [--erase x0,y0,x1,y1,radius[,round]]...   (segments, in command-line order, one rtdd_paint_strokes call after --paint)\n"
                                  "                    [--ramp x0,y0,x1,y1,label0,label1,radius[,round]]...   (a depth ramp: label0 at x0,y0 to label1 at x1,y1; in order with --stroke / --erase, all of them one rtdd_paint_ramp_strokes call)\n"
@@ -757,7 +813,7 @@ int main(int argc, const char *argv[]) {
     }
     Job job;
     std::string in, an, out = "";
-    bool png = false, write_all = false, shadow_opt = false, ao_opt = false, ao_radius_opt = false, layer_at = false, layer_opt = false;
+    bool png = false, write_all = false, shadow_opt = false, ao_opt = false, ao_radius_opt = false, layer_at = false, layer_opt = false, remove_opt = false;
     std::string layer_path, layer_alpha_path;
     int devices = 1, batch = 1, live = 0;
     for (int i = 1; i < argc; i++) {
@@ -880,6 +936,14 @@ int main(int argc, const char *argv[]) {
             for (int k = 0; k < 3; k++) if (c[k] < 0 || c[k] > 255) { std::printf("--light-color: each of b,g,r must be 0..255\n"); return 1; }
             job.light.colorB = (uint8_t)c[0]; job.light.colorG = (uint8_t)c[1]; job.light.colorR = (uint8_t)c[2];
         }
+        else if (!std::strcmp(argv[i], "--remove-region")) { job.removal.select = std::atoi(next()); job.has_remove = true; }
+        else if (!std::strcmp(argv[i], "--remove-grow")) { job.removal.grow = std::atoi(next()); remove_opt = true; }
+        else if (!std::strcmp(argv[i], "--remove-behind")) { job.removal.sourceMinDepth = (float)std::atof(next()); remove_opt = true; }
+        else if (!std::strcmp(argv[i], "--move-region")) {
+            const int got = std::sscanf(next(), "%d:%d,%d:%f", &job.removal.select, &job.move_dx, &job.move_dy, &job.move_depth);
+            if (got < 3) { std::printf("--move-region wants id:dx,dy or id:dx,dy:depth\n"); return 1; }
+            job.move_has_depth = got == 4; job.has_move = true;
+        }
         else if (!std::strcmp(argv[i], "--layer")) layer_path = next();
         else if (!std::strcmp(argv[i], "--layer-alpha")) { layer_alpha_path = next(); layer_opt = true; }
         else if (!std::strcmp(argv[i], "--layer-at")) { if (std::sscanf(next(), "%d,%d", &job.layer.x, &job.layer.y) != 2) { std::printf("--layer-at wants x,y\n"); return 1; } layer_at = layer_opt = true; }
@@ -926,6 +990,12 @@ int main(int argc, const char *argv[]) {
     if (layer_opt && layer_path.empty()) { std::printf("--layer-alpha, --layer-at, --layer-scale, --layer-filter, --layer-depth, --layer-plane, --layer-feather and --layer-opacity need --layer sprite\n"); return 1; }
     if (!layer_path.empty() && !layer_at) { std::printf("--layer needs --layer-at x,y\n"); return 1; }
     if (live > 0 && !layer_path.empty()) { std::printf("--layer is not supported with --live\n"); return 1; }
+    // a removal works on a painted region: its flags belong to it, it needs the regions, and one of the two forms at a time
+    if (remove_opt && !job.has_remove && !job.has_move) { std::printf("--remove-grow and --remove-behind need --remove-region id or --move-region id:dx,dy\n"); return 1; }
+    if (job.has_remove && job.has_move) { std::printf("--remove-region and --move-region: one at a time\n"); return 1; }
+    if (live > 0 && (job.has_remove || job.has_move)) { std::printf("--remove-region and --move-region are not supported with --live\n"); return 1; }
+    if ((job.has_remove || job.has_move) && job.region_flags == 0) { std::printf("--remove-region and --move-region need --regions cut|smooth|both and a painted region\n"); return 1; }
+    if ((job.has_remove || job.has_move) && (job.removal.select < 1 || job.removal.select > 255)) { std::printf("a region id is 1..255\n"); return 1; }
     if (!layer_path.empty()) {
         Pnm s, a;
         if (!read_image(layer_path, s) || s.ch != 3) { std::printf("cannot read %s as a colour image (binary PPM, 8-bit PNG or JPEG)\n", layer_path.c_str()); return 2; }
@@ -990,7 +1060,7 @@ int main(int argc, const char *argv[]) {
         for (size_t i = 0; i + 2 < o.size(); i += 3) { o[i] = annotated[0][i + 2]; o[i + 2] = annotated[0][i]; }     // BGR -> RGB for the file
         if (!o.empty() && !write_image(out + (png ? "AnnotatedImage.png" : "AnnotatedImage.ppm"), rgb.w, rgb.h, 3, o.data())) return 5;
     }
-    if (!job.effect.empty() || job.has_layer) {                          // (--layer without --effect: the composite)
+    if (!job.effect.empty() || job.has_layer || job.has_remove || job.has_move) {     // (--layer, --remove-region or --move-region without --effect: their result)
         std::vector<unsigned char> o(art[0]);
         for (size_t i = 0; i < o.size(); i += 3) { o[i] = art[0][i + 2]; o[i + 2] = art[0][i]; }     // BGR -> RGB for the file
         if (!write_image(out + (png ? "ArtisticEffect.png" : "ArtisticEffect.ppm"), rgb.w, rgb.h, 3, o.data())) return 5;

@@ -545,7 +545,7 @@ int rtdd_simulate_haze(rtdd_ctx *ctx, const uint8_t *original, size_t originalPi
  * Added after ABI version 230 without a version bump: a host finds them by symbol (dlsym).  The next bump of RTDD_VERSION
  * should cover them (rtdd_simulate_refocus, rtdd_simulate_lens_blur, rtdd_simulate_haze_ex, rtdd_simulate_stereo, rtdd_simulate_relight,
  * rtdd_simulate_relight_shadowed, rtdd_simulate_parallax, rtdd_simulate_ambient_occlusion, rtdd_simulate_lighting, rtdd_simulate_bokeh,
- * rtdd_composite_layer),
+ * rtdd_composite_layer, rtdd_remove_object, rtdd_lift_layer),
  * together with a
  * parameterised live effect
  * (rtdd_live_submit_ex takes an effect code only and knows none of them). */
@@ -909,6 +909,62 @@ int rtdd_composite_layer(rtdd_ctx *ctx, const uint8_t *original, size_t original
                          uint8_t *artistic, size_t artisticPitch,
                          float *depthOut, size_t depthOutPitch,         /* may be NULL: no depth is written */
                          int rows, int cols, const rtdd_layer *layer /* HOST, read before the call returns */);
+
+/* Remove an object, and lift it out as a sprite: the opposite of rtdd_composite_layer.  A MASK (u8, rows x cols, DEVICE) says which
+ * pixels are the object -- what the wand, the lasso or a region code (RTDD_IMG_REGION_CODE) selected.  rtdd_lift_layer cuts the selection
+ * out as a sprite for rtdd_composite_layer; rtdd_remove_object fills what it leaves behind, colour AND depth, by a push-pull over a
+ * pyramid, and hands on the depth map like rtdd_composite_layer: insert, delete, move.  Depth 0 is near, 255 far.
+ *   d' = d > 0 ? fminf(d, 255) : +0        (= fminf(fmaxf(d, 0), 255) with the zero's sign settled: a NaN, -0 and every negative depth are +0)
+ * Integers are exact; every f32 operation below is one operation, rounded once, NONE fused; / is IEEE correctly rounded.
+ *   CLASSES at level 0.  A pixel is SELECTED iff its mask byte != 0 (select == 0) or == select (select 1..255: a region code), and
+ *     ELIGIBLE iff d' >= sourceMinDepth.
+ *       HOLE:      selected, or eligible and within Chebyshev distance `grow` of a selected pixel of the image (the ring never eats into a
+ *                  nearer neighbour)
+ *       SOURCE:    not a hole, and eligible
+ *       BYSTANDER: everything else: kept, and never read as a source
+ *   LEVELS.  Level 0 is rows x cols, level k+1 is ceil(r / 2) x ceil(c / 2); the chain ends at the first level that is 1 x 1.  A sample is
+ *     (B, G, R) in 0..255, a depth in f32 and a valid bit.  At level 0 the valid samples are the sources, with depth d'.
+ *   PULL.  Sample (i, j) of level k+1 from its children (2i+a, 2j+b) that exist and are valid, in the order (0,0), (0,1), (1,0), (1,1);
+ *     n their count.  n == 0: not valid.  Otherwise per channel  c = (2 * sum c + n) div (2 n),  and the depth
+ *     (((d1 + d2) + d3) + d4) / (float)n  over the valid children in that order.
+ *   PUSH, from the level below the top down to level 0.  A sample (y, x) of level k that is not valid (at level 0: a hole; bystanders
+ *     are left alone) is filled from level k+1:  yn = y >> 1;  yf = (y & 1) ? yn + 1 : yn - 1, clamped into the coarse level; x likewise.
+ *       per channel  c = (9 c[yn,xn] + 3 c[yn,xf] + 3 c[yf,xn] + c[yf,xf] + 8) >> 4
+ *       depth        t = 9 * d[yn,xn];  t = t + 3 * d[yn,xf];  t = t + 3 * d[yf,xn];  t = t + d[yf,xf];  depth = t * 0.0625f
+ *     (each product and each sum rounded on its own).  The filled sample is valid iff [yn,xn] is: with the chain run to 1 x 1 a coarse
+ *     level is wholly valid or, if the image has no source at all, wholly invalid.
+ *   OUTPUT.  A filled hole pixel gets the colour and the depth it was filled with.  Every other pixel gets original's bytes and depth's
+ *     bits, a NaN included -- the hole pixels of an image without a single source too.
+ * Identities: no selected pixel, and no source anywhere, each give a bit copy of both inputs; a hole whose sources all have one colour
+ * is filled with exactly that colour ((16 c + 8) >> 4 = c; the depth may differ by a rounding).
+ *   LIFT.  Texel (u, v) of the sprite is image pixel (x + u, y + v): inside the image and selected (by mask and select alone: no grow,
+ *     no depth) it is (B, G, R, 255) from original, otherwise (0, 0, 0, 0).  Every texel of the sprite is stored exactly once.
+ * The three calls together: with a sprite box that covers the selection, grow = 0 and any sourceMinDepth, rtdd_composite_layer of the
+ * lifted sprite onto rtdd_remove_object's two outputs (layer.rows / cols the sprite's, x, y the lift's, scale 256, RTDD_LAYER_NEAREST,
+ * opacity 255, depth0 = 0 with (x0, y0) == (x1, y1), feather 0) gives `original` back byte for byte.
+ * Both calls: asynchronous, stream-ordered, deterministic, independent of RTDD_OPT_FP_CONTRACT; not in place (a healed time-out runs
+ * the call again, and the second run must read what the first one read).  rtdd_remove_object stores every pixel of artistic, and of
+ * depthOut when given, exactly once; it keeps its coarse levels in the context's table buffer.  RTDD_VERSION is unchanged.
+ * Refused on the host (RTDD_ERR_INVALID), before any launch: rtdd_composite_layer's image rules for every pointer, with maskPitch >=
+ * cols and spritePitch >= 4 * spriteCols; original == artistic; depth == depthOut; a null mask; a null removal; any field outside its
+ * range; a non-finite float. */
+typedef struct rtdd_removal {
+    int   select;               /* 0: a pixel is selected iff its mask byte != 0;  1 .. 255: iff its mask byte == select (a region code) */
+    int   grow;                 /* 0 .. 8: the hole also takes the eligible pixels within this Chebyshev distance of a selected pixel */
+    float sourceMinDepth;       /* finite, in [0, 255]: only pixels at least this far are sources of the fill; 0: every pixel */
+} rtdd_removal;                 /* 12 bytes */
+int rtdd_remove_object(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch,
+                       const float *depth, size_t depthPitch,
+                       const uint8_t *mask, size_t maskPitch,           /* DEVICE, u8, rows x cols */
+                       uint8_t *artistic, size_t artisticPitch,
+                       float *depthOut, size_t depthOutPitch,           /* may be NULL: no depth is written */
+                       int rows, int cols, const rtdd_removal *removal /* HOST, read before the call returns */);
+int rtdd_lift_layer(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch,
+                    const uint8_t *mask, size_t maskPitch,              /* DEVICE, u8, rows x cols */
+                    int rows, int cols, int select /* 0 .. 255, as rtdd_removal.select */,
+                    int x, int y,                                       /* the sprite's corner in the image, each in [-16384, 16383] */
+                    uint8_t *sprite, size_t spritePitch,                /* DEVICE, u8 x 4, written */
+                    int spriteRows, int spriteCols                      /* 1 .. 16384 each */);
 
 /* ---- whole-estimate driver ------------------------------------------------
  * One depth estimate = the loop body of src/main.cpp:232-295, run as a single stream-ordered launch

@@ -54,7 +54,7 @@ C_ABI_SYMBOLS = [
     "rtdd_simulate_refocus", "rtdd_simulate_haze_ex", "rtdd_simulate_stereo", "rtdd_simulate_lens_blur",
     "rtdd_paint_strokes", "rtdd_pyramid_annotation_rebuild", "rtdd_paint_ramp_strokes", "rtdd_ramp_polyline", "rtdd_fill_polygon", "rtdd_fill_similar",
     "rtdd_simulate_relight", "rtdd_simulate_relight_shadowed", "rtdd_simulate_parallax", "rtdd_simulate_ambient_occlusion",
-    "rtdd_simulate_lighting", "rtdd_simulate_bokeh", "rtdd_composite_layer",
+    "rtdd_simulate_lighting", "rtdd_simulate_bokeh", "rtdd_composite_layer", "rtdd_remove_object", "rtdd_lift_layer",
     "rtdd_solve_guided", "rtdd_index_to_weight_guided", "rtdd_pyrdown_bgr", "rtdd_pyramid_set_guide", "rtdd_pyramid_guide",
     "rtdd_solve_regions", "rtdd_index_to_weight_regions", "rtdd_region_codes", "rtdd_pyramid_set_regions", "rtdd_pyramid_regions",
     "rtdd_pyramid_regions_changed",
@@ -74,6 +74,32 @@ STROKE_ERASE = -1                             # rtdd_stroke.label: remove the an
 FILL_NONZERO, FILL_EVEN_ODD = 0, 1            # rtdd_fill.rule
 WAND_CONNECT_8, WAND_GLOBAL = 1, 2            # rtdd_wand.flags
 WAND_ROUND = 8                                # grow passes rtdd_fill_similar queues between two synchronisations (csrc/fill_similar.hip: kWandRound)
+# rtdd_remove_object's grouping (csrc/rtdd_internal.hpp: kRemoveTile, kRemoveGroup, kRemoveApex, kRemoveApexChain): a workgroup owns a
+# REMOVE_TILE-square tile of a level and takes REMOVE_GROUP levels in LDS; one workgroup takes a level of at most REMOVE_APEX samples
+# (its chain up to 1 x 1 at most REMOVE_APEX_CHAIN) to the top and back
+REMOVE_TILE, REMOVE_GROUP, REMOVE_APEX = 64, 3, 8192
+REMOVE_APEX_CHAIN = REMOVE_APEX + REMOVE_APEX // 2 + 64
+
+
+def remove_plan(rows, cols):
+    """The levels rtdd_remove_object stores for a rows x cols image (csrc/remove.hip remove_plan): [(levels taken, rows, cols of the level
+    stored), ...], one entry per pull group; the apex takes the last.  2 * len + 1 launches."""
+    def chain(r, c):
+        n = r * c
+        while r > 1 or c > 1:
+            r, c = (r + 1) // 2, (c + 1) // 2
+            n += r * c
+        return n
+    plan, r, c = [], rows, cols
+    while True:
+        g = 0
+        while g < REMOVE_GROUP and (r > 1 or c > 1):
+            r, c, g = (r + 1) // 2, (c + 1) // 2, g + 1
+        plan.append((g, r, c))
+        if r * c <= REMOVE_APEX and chain(r, c) <= REMOVE_APEX_CHAIN:
+            return plan
+
+
 # Itanium-mangled names of the reference's ten free functions (SURVEY.md 8b)
 DROPIN_SYMBOLS = [
     "_Z23GPUAllocateDeviceMemoryiii", "_Z19GPUFreeDeviceMemoryi", "_Z14GPULoadWeightsf",
@@ -201,6 +227,16 @@ class Layer(C.Structure):
     def __init__(self, rows=1, cols=1, x=0, y=0, scale=256, filter=LAYER_NEAREST, opacity=255, x0=0, y0=0, x1=0, y1=0, depth0=0.0,
                  depth1=0.0, feather=0.0):
         super().__init__(rows, cols, x, y, scale, filter, opacity, x0, y0, x1, y1, depth0, depth1, feather)
+
+
+class Removal(C.Structure):
+    """rtdd_removal: a pixel is selected iff its mask byte != 0 (`select` 0) or == select (1..255, a region code); the hole also takes
+    the eligible pixels within Chebyshev distance `grow` (0..8) of a selected one; only pixels at least `sourceMinDepth` far are sources
+    of the fill (0: every pixel)."""
+    _fields_ = [("select", C.c_int), ("grow", C.c_int), ("sourceMinDepth", C.c_float)]
+
+    def __init__(self, select=0, grow=0, sourceMinDepth=0.0):
+        super().__init__(select, grow, sourceMinDepth)
 
 
 class Profile(C.Structure):
@@ -581,6 +617,23 @@ class Context:
         z, zp = _img(depthOutImage) if depthOutImage is not None else (None, C.c_size_t(0))
         self._check(lib().rtdd_composite_layer(self._h, o, op, d, dp, s, sp, a, ap, z, zp, C.c_int(rows), C.c_int(cols),
                                                C.byref(layer) if layer is not None else None))
+
+    def remove_object(self, originalImage, depthImage, maskImage, artisticImage, depthOutImage, rows, cols, removal):
+        """The pixels `maskImage` (u8, rows x cols) selects as `removal` (a Removal, or None for the C call's null pointer) says are filled,
+        colour and depth, from what lies around them (a push-pull over a pyramid).  depthOutImage (None: not written) receives the depth
+        map without the object, for the effects that follow."""
+        o, op = _img(originalImage); d, dp = _img(depthImage); a, ap = _img(artisticImage)
+        m, mp = _img(maskImage) if maskImage is not None else (None, C.c_size_t(0))
+        z, zp = _img(depthOutImage) if depthOutImage is not None else (None, C.c_size_t(0))
+        self._check(lib().rtdd_remove_object(self._h, o, op, d, dp, m, mp, a, ap, z, zp, C.c_int(rows), C.c_int(cols),
+                                             C.byref(removal) if removal is not None else None))
+
+    def lift_layer(self, originalImage, maskImage, rows, cols, select, x, y, spriteImage, spriteRows, spriteCols):
+        """The selected pixels (mask byte != 0, or == select) of the box whose corner is image pixel (x, y) cut out as a u8 x 4 sprite
+        (B, G, R, 255; everything else 0, 0, 0, 0) for composite_layer."""
+        o, op = _img(originalImage); m, mp = _img(maskImage); s, sp = _img(spriteImage)
+        self._check(lib().rtdd_lift_layer(self._h, o, op, m, mp, C.c_int(rows), C.c_int(cols), C.c_int(select), C.c_int(x), C.c_int(y),
+                                          s, sp, C.c_int(spriteRows), C.c_int(spriteCols)))
 
     # ---- whole-estimate driver (src/main.cpp:92-155, 232-295)
     def pyramid_create(self, rows, cols):

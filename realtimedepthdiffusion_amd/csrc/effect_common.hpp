@@ -1,4 +1,4 @@
-// effect_common.hpp -- what the depth-effect translation units (effect_kernels.hip, lens_blur.hip, relight.hip, relight_shadow.hip, parallax.hip, ambient_occlusion.hip, lighting.hip, bokeh.hip, composite.hip) share.  Device: the
+// effect_common.hpp -- what the depth-effect translation units (effect_kernels.hip, lens_blur.hip, relight.hip, relight_shadow.hip, parallax.hip, ambient_occlusion.hip, lighting.hip, bokeh.hip, composite.hip, remove.hip) share.  Device: the
 // packed 3 x 21-bit pixel sums of the defocus tables, the 64-bit DPP scans, the quotients, the focus read, the workgroup -> tile decode,
 // the tile geometry.  Host: the pixel form, row alignment, the launch grids of the two tile kernels and the two table lookups, the
 // table buffer.

@@ -884,6 +884,8 @@ int launch_effect(rtdd_ctx *ctx, const Effect &e) {
         case Effect::kLighting: return launch_lighting(ctx, e);        // lighting.hip
         case Effect::kBokeh: return launch_bokeh(ctx, e);              // bokeh.hip
         case Effect::kComposite: return launch_composite(ctx, e);      // composite.hip
+        case Effect::kRemove: return launch_remove(ctx, e);            // remove.hip
+        case Effect::kLift: return launch_lift(ctx, e);                // remove.hip
         case RTDD_EFFECT_DESATURATION:
             return launch_blend<0>(ctx, e.original, e.originalPitch, e.gray, e.grayPitch, e.depth, e.depthPitch, e.artistic, e.artisticPitch,
                                    e.rows, e.cols);

@@ -343,5 +343,50 @@ int rtdd_composite_layer(rtdd_ctx *ctx, const uint8_t *original, size_t original
     return simulate(ctx, e);
 }
 
+int rtdd_remove_object(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
+                       const uint8_t *mask, size_t maskPitch, uint8_t *artistic, size_t artisticPitch, float *depthOut,
+                       size_t depthOutPitch, int rows, int cols, const rtdd_removal *removal) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    int rc = check_effect(ctx, original, depth, artistic, originalPitch, depthPitch, artisticPitch, rows, cols);
+    if (rc != RTDD_OK) return rc;
+    if (depthOut) {
+        REQUIRE(ctx, depthOutPitch >= (size_t)cols * 4, "pitch smaller than a row");
+        REQUIRE(ctx, f32_image_aligned(depthOut, depthOutPitch), kF32AlignText);
+    }
+    REQUIRE(ctx, original != artistic && (const float *)depthOut != depth, "an object cannot be removed in place");
+    REQUIRE(ctx, mask && maskPitch >= (size_t)cols, "bad mask image");
+    REQUIRE(ctx, removal, "null removal");
+    const rtdd_removal &q = *removal;
+    REQUIRE(ctx, q.select >= 0 && q.select <= 255, "select outside [0, 255]");
+    REQUIRE(ctx, q.grow >= 0 && q.grow <= 8, "grow outside [0, 8]");
+    REQUIRE(ctx, std::isfinite(q.sourceMinDepth), "a non-finite value in the removal");
+    REQUIRE(ctx, q.sourceMinDepth >= 0.0f && q.sourceMinDepth <= 255.0f, "sourceMinDepth outside [0, 255]");
+    if (rows == 0 || cols == 0) return RTDD_OK;
+    Effect e{Effect::kRemove, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols};
+    Effect::Remove &k = e.remove;
+    k.removal = q; k.mask = mask; k.maskPitch = maskPitch;
+    k.depthOut = depthOut; k.depthOutPitch = depthOut ? depthOutPitch : 0;
+    return simulate(ctx, e);
+}
+
+int rtdd_lift_layer(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const uint8_t *mask, size_t maskPitch, int rows, int cols,
+                    int select, int x, int y, uint8_t *sprite, size_t spritePitch, int spriteRows, int spriteCols) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    REQUIRE(ctx, original && mask && sprite, "null image pointer");
+    REQUIRE(ctx, rows >= 0 && cols >= 0, "negative size");
+    REQUIRE(ctx, (long long)rows * rows + (long long)cols * cols < 2147483647LL, "image too large");
+    REQUIRE(ctx, originalPitch >= (size_t)cols * 3 && maskPitch >= (size_t)cols, "pitch smaller than a row");
+    REQUIRE(ctx, original != sprite, "a sprite cannot be lifted in place");
+    REQUIRE(ctx, spriteRows >= 1 && spriteRows <= 16384 && spriteCols >= 1 && spriteCols <= 16384, "the sprite's rows or cols outside [1, 16384]");
+    REQUIRE(ctx, spritePitch >= (size_t)spriteCols * 4, "pitch smaller than a row");
+    REQUIRE(ctx, select >= 0 && select <= 255, "select outside [0, 255]");
+    REQUIRE(ctx, x >= -16384 && x <= 16383 && y >= -16384 && y <= 16383, "a sprite coordinate outside [-16384, 16383]");
+    Effect e{Effect::kLift, original, originalPitch, nullptr, 0, nullptr, 0, rows, cols};      // (an empty image: a transparent sprite)
+    Effect::Lift &k = e.lift;
+    k.mask = mask; k.maskPitch = maskPitch; k.select = select; k.x = x; k.y = y;
+    k.sprite = sprite; k.spritePitch = spritePitch; k.spriteRows = spriteRows; k.spriteCols = spriteCols;
+    return simulate(ctx, e);
+}
+
 }  // extern "C"
 #pragma GCC visibility pop

@@ -101,8 +101,8 @@ struct LiveTargets {
 // One depth effect, arguments checked: what to render, on which images, with which parameters.  Built by the rtdd_simulate_* entry
 // points (effects_api.cpp) and by a live frame (live_effect), launched by launch_effect, and logged by value (PendingOp) to be launched again.
 struct Effect {
-    enum : int { kRefocus = RTDD_EFFECT_HAZE + 1, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow, kParallax, kAmbientOcclusion, kLighting, kBokeh, kComposite };   // the extensions, after the public kinds
-    int kind = RTDD_EFFECT_NONE;                    // RTDD_EFFECT_DEFOCUS / _DESATURATION / _HAZE, kRefocus, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow, kParallax, kAmbientOcclusion, kLighting, kBokeh, kComposite
+    enum : int { kRefocus = RTDD_EFFECT_HAZE + 1, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow, kParallax, kAmbientOcclusion, kLighting, kBokeh, kComposite, kRemove, kLift };   // the extensions, after the public kinds
+    int kind = RTDD_EFFECT_NONE;                    // RTDD_EFFECT_DEFOCUS / _DESATURATION / _HAZE, kRefocus, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow, kParallax, kAmbientOcclusion, kLighting, kBokeh, kComposite, kRemove, kLift
     const uint8_t *original = nullptr; size_t originalPitch = 0;
     const float *depth = nullptr; size_t depthPitch = 0;
     uint8_t *artistic = nullptr; size_t artisticPitch = 0;
@@ -156,6 +156,20 @@ struct Effect {
         float *depthOut = nullptr; size_t depthOutPitch = 0;       // null: no depth is written
         int fx0 = 0, fy0 = 0, fx1 = 0, fy1 = 0;
     } composite = {};
+    // a removed object (kRemove): rtdd_removal as the entry point checked it (include/rtdd.h rtdd_remove_object), the mask and the second
+    // output, by value
+    struct Remove {
+        rtdd_removal removal = {};
+        const uint8_t *mask = nullptr; size_t maskPitch = 0;
+        float *depthOut = nullptr; size_t depthOutPitch = 0;       // null: no depth is written
+    } remove = {};
+    // a lifted sprite (kLift, rtdd_lift_layer): reads original (rows x cols) and the mask, writes the sprite; depth and artistic are null
+    struct Lift {
+        const uint8_t *mask = nullptr; size_t maskPitch = 0;
+        int select = 0, x = 0, y = 0;
+        uint8_t *sprite = nullptr; size_t spritePitch = 0;
+        int spriteRows = 0, spriteCols = 0;
+    } lift = {};
 };
 
 // The defocus window scale K of src/GPUDepthEffect.cu:42, (int)(aperture * diagonal) -- double * float and the int products as there,
@@ -448,6 +462,13 @@ int launch_lighting(rtdd_ctx *ctx, const Effect &e);
 int launch_bokeh(rtdd_ctx *ctx, const Effect &e);
 // ---- composite.hip: Effect::kComposite (called by launch_effect) -----------------------------------
 int launch_composite(rtdd_ctx *ctx, const Effect &e);
+// ---- remove.hip: Effect::kRemove and Effect::kLift (called by launch_effect) -----------------------
+// The push-pull's grouping (DESIGN.md section 4 "Remove"), mirrored by REMOVE_TILE, REMOVE_GROUP, REMOVE_APEX and remove_plan() of
+// realtimedepthdiffusion_amd/__init__.py: a workgroup owns a kRemoveTile-square tile of a level and takes kRemoveGroup levels in LDS;
+// one workgroup takes a level of at most kRemoveApex samples to 1 x 1 and back, its whole chain (at most kRemoveApexChain samples) in LDS.
+constexpr int kRemoveTile = 64, kRemoveGroup = 3, kRemoveApex = 8192, kRemoveApexChain = kRemoveApex + kRemoveApex / 2 + 64;
+int launch_remove(rtdd_ctx *ctx, const Effect &e);
+int launch_lift(rtdd_ctx *ctx, const Effect &e);
 
 // ---- cascade.hip -------------------------------------------------------------------------------
 int launch_bgr2gray(rtdd_ctx *ctx, const uint8_t *bgr, size_t bp, uint8_t *gray, size_t gp, int rows, int cols);
