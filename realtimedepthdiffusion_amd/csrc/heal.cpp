@@ -19,10 +19,11 @@ int prepare_persistent_launch(rtdd_ctx *ctx, int nblocks, int *flag_base) {
     *flag_base = ctx->flag_epoch;
     ctx->flag_epoch += nblocks + 1;
     const int limit = ctx->opt.debug_poll_limit_us > 0 ? ctx->opt.debug_poll_limit_us * 100 : 0;        // 10 ns ticks
-    if (ctx->sync_header[0] != ctx->opt.debug_withhold_tile || ctx->sync_header[1] != limit) {
-        RTDD_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)(ctx->sync_words + kSyncWithhold), ctx->opt.debug_withhold_tile, 1, ctx->stream));
+    // (RTDD_OPT_DEBUG_WITHHOLD_TILE is no control word: every persistent launch is handed ctx->opt.debug_withhold_tile as an argument,
+    // the value at the time it is enqueued -- the order a stream-ordered write of the word gave; persist_sync.hpp exchange_wait_at)
+    if (ctx->sync_limit != limit) {
         RTDD_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)(ctx->sync_words + kSyncLimit), limit, 1, ctx->stream));
-        ctx->sync_header[0] = ctx->opt.debug_withhold_tile; ctx->sync_header[1] = limit;
+        ctx->sync_limit = limit;
     }
     note_status_writer(ctx);
     return RTDD_OK;

@@ -9,8 +9,8 @@
 //                    RTDD_ERR_TIMEOUT.  Once it is set every workgroup that sees it stops exchanging and returns, and every
 //                    later persistent launch returns at once, so a failed estimate drains in microseconds instead of spinning
 //                    through its remaining exchanges.
-//   [kSyncWithhold]  debug (RTDD_OPT_DEBUG_WITHHOLD_TILE): tile number + 1 whose flag is never published (0 = off), to make the
-//                    timeout path testable.
+//   [kSyncWithhold]  reserved, never written or read (it held RTDD_OPT_DEBUG_WITHHOLD_TILE until the persistent kernels were handed that
+//                    value as an argument -- exchange_wait_at's `withhold`; the index stays so that the layout does not move).
 //   [kSyncLimit]     poll limit in 10 ns ticks of s_memrealtime (0 = kDefaultPollLimit).
 //   [kSyncFailedSeq] sequence number of the first solve whose copy-back kernel (k_finish / k_pyrup_inject) found the status word set and
 //                    therefore stored nothing: the host re-runs the pending calls from that one on (heal.cpp check_persistent_status).  0 = none.
@@ -106,11 +106,21 @@ __device__ __forceinline__ int load_flag_at(const int *base, unsigned off) {
 // ONE agent acquire; barrier; plain vector loads.
 // exchange_wait_at() is exchange_wait() with the polled flag's place worked out by the caller (exchange_poll_offset): the flag is addressed as the
 // scalar base sync_words plus that 32-bit offset, so an exchange forms no 64-bit address per lane.
+// `withhold`: the testing aid RTDD_OPT_DEBUG_WITHHOLD_TILE -- tile number + 1 whose flag is never published (in a batch: every image's
+// tile of that number), 0 = off -- to make the time-out path testable.  A KERNEL ARGUMENT, the option's value when the launch was
+// enqueued: as a control word read here it was a trip to L2 and a vmcnt wait between the barrier and the flag store of every exchange,
+// exactly where every tile of the grid is waiting for its neighbours' flags (tests/test_isa_exchange_chain.py).
 template <bool ACQUIRE = true, bool ARRIVAL = false>
-__device__ __forceinline__ bool exchange_wait_at(int *sync_words, int *dead_lds, int tid, int tile_id, int poll_off, int value, int tile_base = 0) {
+__device__ __forceinline__ bool exchange_wait_at(int *sync_words, int *dead_lds, int tid, int tile_id, int poll_off, int value, int withhold, int tile_base = 0) {
     int *flags = sync_words + kSyncFlags + tile_base * kSyncFlagStride;      // (tile_base: a batched launch gives every image's tiles flags of their own)
-    if (tid == 0 && __hip_atomic_load(&sync_words[kSyncWithhold], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != tile_id + 1)
-        __hip_atomic_store(&flags[tile_id * kSyncFlagStride], value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid == 0 && withhold != tile_id + 1) {
+        // The flag's address is scalar; the store still wants a vector offset, 0.  It is made HERE (no instruction but the v_mov_b32 of
+        // the constant): left to the register allocator the 1024-thread tile of four rows per thread, which sits at its cap of 128
+        // registers, reloaded a spilled tuple of zeros from scratch for it and waited for that load in front of the flag store.
+        unsigned zero = 0;
+        asm volatile("" : "+v"(zero));
+        __hip_atomic_store((int *)((char *)&flags[tile_id * kSyncFlagStride] + zero), value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     // A poll is a round trip to memory (the flag was stored sc1: it is in no L2).  (Several polling waves, each started a fraction of a
     // trip after the one before and the first to see all its neighbours telling the others through LDS, measured no faster: EXPERIMENTS.md.)
     if (poll_off >= 0) {
@@ -144,8 +154,8 @@ __device__ __forceinline__ bool exchange_wait_at(int *sync_words, int *dead_lds,
 }
 
 template <bool ACQUIRE = true, bool ARRIVAL = false>
-__device__ __forceinline__ bool exchange_wait(int *sync_words, int *dead_lds, int tid, int tile_id, int bx, int by, int gx, int gy, int value, int tile_base = 0) {
-    return exchange_wait_at<ACQUIRE, ARRIVAL>(sync_words, dead_lds, tid, tile_id, exchange_poll_offset(tid, bx, by, gx, gy, tile_base), value, tile_base);
+__device__ __forceinline__ bool exchange_wait(int *sync_words, int *dead_lds, int tid, int tile_id, int bx, int by, int gx, int gy, int value, int withhold, int tile_base = 0) {
+    return exchange_wait_at<ACQUIRE, ARRIVAL>(sync_words, dead_lds, tid, tile_id, exchange_poll_offset(tid, bx, by, gx, gy, tile_base), value, withhold, tile_base);
 }
 
 #endif

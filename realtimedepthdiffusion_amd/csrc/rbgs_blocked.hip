@@ -52,7 +52,7 @@ __device__ __forceinline__ void store_sc1(float4 *p, float4 v) {
 template <int LX, int NT, int G, bool CONTRACT, bool SOR, bool PERSIST>
 __global__ __launch_bounds__(NT, 4) void k_rbgs_blocked(float *X, float *Y, const uint32_t *__restrict__ M,
                                                         const float *__restrict__ lut_g, int ip, int rows, int cols, int hx, int hy, int nsweeps, float omega, int gx, int gy, int xcd_tiles,
-                                                        int block_sweeps, int *sync_words, int flag_base, int wild_seq) {
+                                                        int block_sweeps, int *sync_words, int flag_base, int wild_seq, int withhold) {
     static_assert(G % 2 == 0, "the compile-time colour pattern needs an even number of rows per thread");
     constexpr int EW = 4 * LX, NTR = NT / LX;
     typedef float f4r __attribute__((ext_vector_type(4)));
@@ -74,7 +74,7 @@ __global__ __launch_bounds__(NT, 4) void k_rbgs_blocked(float *X, float *Y, cons
     if (tid == 0) { dead_s = PERSIST && __hip_atomic_load(&sync_words[kSyncStatus], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0; }
     if (PERSIST) {
         // arrival, as in k_sweep_blocked: announce, see the 8 neighbours announce within a millisecond, or leave before any sweep
-        if (exchange_wait<false, true>(sync_words, &dead_s, tid, by * gx + bx, bx, by, gx, gy, flag_base)) return;
+        if (exchange_wait<false, true>(sync_words, &dead_s, tid, by * gx + bx, bx, by, gx, gy, flag_base, withhold)) return;
     } else {
         __syncthreads();
     }
@@ -263,7 +263,7 @@ __global__ __launch_bounds__(NT, 4) void k_rbgs_blocked(float *X, float *Y, cons
 #ifndef RTDD_EXCHANGE_ACQUIRE
 #define RTDD_EXCHANGE_ACQUIRE 0      // 1: one agent-scope acquire by wave 0 and plain vector loads (the fallback form; built and tested once per round: tests/test_isa_hazards.py, scripts/build_variant.sh)
 #endif
-        if (exchange_wait<RTDD_EXCHANGE_ACQUIRE != 0>(sync_words, &dead_s, tid, tile_id, bx, by, gx, gy, flag_base + blk + 1)) return;      // flag, bounded poll, (acquire,) barrier (persist_sync.hpp)
+        if (exchange_wait<RTDD_EXCHANGE_ACQUIRE != 0>(sync_words, &dead_s, tid, tile_id, bx, by, gx, gy, flag_base + blk + 1, withhold)) return;      // flag, bounded poll, (acquire,) barrier (persist_sync.hpp)
 #if RTDD_EXCHANGE_ACQUIRE
 #pragma unroll
         for (int g = 0; g < G; g++) {
@@ -358,7 +358,7 @@ int launch_rbgs_blocked(rtdd_ctx *ctx, const Level &L, size_t ip, int rows, int 
         int block_sweeps = m, flag_base = 0;
         if (persistent) {
             m = n - done;
-            RTDD_TRY(prepare_persistent_launch(ctx, (m + block_sweeps - 1) / block_sweeps, &flag_base));   // this launch's flag values, debug words
+            RTDD_TRY(prepare_persistent_launch(ctx, (m + block_sweeps - 1) / block_sweeps, &flag_base));   // this launch's flag values, the poll limit
             note_status_writer(ctx);
         }
         int out = -1;
@@ -368,8 +368,8 @@ int launch_rbgs_blocked(rtdd_ctx *ctx, const Level &L, size_t ip, int rows, int 
         const bool sor = omega != 1.0f;
         const int xcd_tiles = single ? 0 : ((int)(grid.x * grid.y) + 7) / 8;
         const dim3 launch_grid = xcd_tiles > 0 ? dim3(8 * xcd_tiles) : grid;
-#define RTDD_RBGS_GO(NT_, C_, S_) do { if (persistent) hipLaunchKernelGGL((k_rbgs_blocked<32, NT_, 4, C_, S_, true>), launch_grid, dim3(nthreads), 0, ctx->stream, X, Y, L.M(ip), ctx->lut_dev, (int)ip, rows, cols, hx, hy, m, omega, (int)grid.x, (int)grid.y, xcd_tiles, block_sweeps, ctx->sync_words, flag_base, ctx->wild_seq); \
-        else hipLaunchKernelGGL((k_rbgs_blocked<32, NT_, 4, C_, S_, false>), launch_grid, dim3(nthreads), 0, ctx->stream, X, Y, L.M(ip), ctx->lut_dev, (int)ip, rows, cols, hx, hy, m, omega, (int)grid.x, (int)grid.y, xcd_tiles, block_sweeps, ctx->sync_words, flag_base, ctx->wild_seq); } while (0)
+#define RTDD_RBGS_GO(NT_, C_, S_) do { if (persistent) hipLaunchKernelGGL((k_rbgs_blocked<32, NT_, 4, C_, S_, true>), launch_grid, dim3(nthreads), 0, ctx->stream, X, Y, L.M(ip), ctx->lut_dev, (int)ip, rows, cols, hx, hy, m, omega, (int)grid.x, (int)grid.y, xcd_tiles, block_sweeps, ctx->sync_words, flag_base, ctx->wild_seq, ctx->opt.debug_withhold_tile); \
+        else hipLaunchKernelGGL((k_rbgs_blocked<32, NT_, 4, C_, S_, false>), launch_grid, dim3(nthreads), 0, ctx->stream, X, Y, L.M(ip), ctx->lut_dev, (int)ip, rows, cols, hx, hy, m, omega, (int)grid.x, (int)grid.y, xcd_tiles, block_sweeps, ctx->sync_words, flag_base, ctx->wild_seq, ctx->opt.debug_withhold_tile); } while (0)
         const int variant = (big ? 4 : 0) | (ctx->opt.fp_contract ? 2 : 0) | (sor ? 1 : 0);
         switch (variant) {
             case 0: RTDD_RBGS_GO(512, false, false); break;

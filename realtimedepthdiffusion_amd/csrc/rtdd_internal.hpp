@@ -267,7 +267,7 @@ struct rtdd_ctx {
     bool defocus_band_sticky = false;    // a banded-table defocus met windows beyond a slice (depths above 255): one whole-image table from then on
     bool defocus_table_sticky = false;   // a tile-kernel defocus met out-of-range depths (seen at a synchronisation): automatic choice = the table from then on
     int flag_epoch = 0;             // the per-tile flags of the persistent kernels only ever grow: base value of the next persistent launch (heal.cpp)
-    int sync_header[2] = {0, 0};    // what sync_words[kSyncWithhold], [kSyncLimit] currently hold on the device
+    int sync_limit = 0;             // what sync_words[kSyncLimit] currently holds on the device
     int last_nominal_depth = 0;     // sweeps per launch / exchange the most recent blocked solve was configured with (its last launch may be shorter)
     int last_launch_images = 1;     // images each sweep launch of the most recent solve covered (sweep_blocked.hip: a batch in the same launches, or image after image)
     rtdd_solve_info last_info{};    // of the most recent solve; kernel/tile/temporal_depth/persistent are filled in by the sweep launchers
@@ -500,7 +500,7 @@ int pyramid_note_write(rtdd_ctx *ctx, const void *scribble, const void *edited, 
 int pyramid_check_read(rtdd_ctx *ctx, const void *a, const void *b);     // ... about to be read
 
 // ---- heal.cpp ----------------------------------------------------------------------------------
-// persistent kernels (persist_sync.hpp): reserve the launch's flag values and refresh the debug words before a persistent launch;
+// persistent kernels (persist_sync.hpp): reserve the launch's flag values and refresh the poll-limit word before a persistent launch;
 // read the status word where the stream has just been synchronised (-> RTDD_ERR_TIMEOUT, status cleared)
 int prepare_persistent_launch(rtdd_ctx *ctx, int nblocks, int *flag_base);
 // in_solve: called from a residual check inside rtdd_solve_ex -- after a successful heal of the calls before it that solve starts over (kRestartSolve)

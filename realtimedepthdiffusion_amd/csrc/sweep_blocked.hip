@@ -64,7 +64,7 @@ __global__ __launch_bounds__(NT, (NT >= 1024 || G <= 3 ? 4 : G <= 4 ? 3 : 2)) vo
                                                       const uint32_t *__restrict__ M, const float *__restrict__ lut_g,
                                                       const float *__restrict__ omegas, int ip, int rows, int cols,
                                                       int hx, int hy, int nsweeps, float gamma,
-                                                      int block_sweeps, int *sync_words, int gx, int gy, int xcd_tiles, int flag_base, size_t zPlane, int wild_seq) {
+                                                      int block_sweeps, int *sync_words, int gx, int gy, int xcd_tiles, int flag_base, size_t zPlane, int wild_seq, int withhold) {
     // block_sweeps == nsweeps: the plain time-blocked launch (results -> Yk/Ym).
     // block_sweeps <  nsweeps: PERSISTENT mode -- the workgroup keeps its tile in registers for the whole solve and,
     // every block_sweeps (= halo width, even) sweeps, trades halo strips with its 8 neighbours through memory instead
@@ -142,7 +142,7 @@ __global__ __launch_bounds__(NT, (NT >= 1024 || G <= 3 ? 4 : G <= 4 ? 3 : 2)) vo
         // tile's loads are in flight.  A workgroup that is not resident never announces itself, its neighbours give up within a
         // millisecond, the status word is set and every workgroup leaves here, before any sweep (also at once when an earlier
         // persistent launch of this context has timed out).  Its barrier is also the one the table's staging needs.
-        if (exchange_wait_at<false, true>(sync_words, &dead_s, tid, tile_id, exchange_poll_offset(tid, bx, by, gx, gy, tile_base), flag_base, tile_base)) return;
+        if (exchange_wait_at<false, true>(sync_words, &dead_s, tid, tile_id, exchange_poll_offset(tid, bx, by, gx, gy, tile_base), flag_base, withhold, tile_base)) return;
     } else {
         __syncthreads();
     }
@@ -277,7 +277,7 @@ __global__ __launch_bounds__(NT, (NT >= 1024 || G <= 3 ? 4 : G <= 4 ? 3 : 2)) vo
 #ifndef RTDD_EXCHANGE_ACQUIRE
 #define RTDD_EXCHANGE_ACQUIRE 0
 #endif
-            if (exchange_wait_at<RTDD_EXCHANGE_ACQUIRE != 0>(sync_words, &dead_s, tid, tile_id, rec.z, flag_base + blk + 1, tile_base)) { dead = true; break; }      // flag, bounded poll, (acquire,) barrier
+            if (exchange_wait_at<RTDD_EXCHANGE_ACQUIRE != 0>(sync_words, &dead_s, tid, tile_id, rec.z, flag_base + blk + 1, withhold, tile_base)) { dead = true; break; }      // flag, bounded poll, (acquire,) barrier
             RTDD_XT(2);
             RTDD_XT(3);
 #if RTDD_EXCHANGE_ACQUIRE
@@ -605,7 +605,7 @@ static void launch_cfg(rtdd_ctx *ctx, dim3 grid, int xcd_tiles, int nthreads, fl
                        const float *omegas, int ip, int rows, int cols, int hx, int hy, int n, float gamma, int block_sweeps, int flag_base, size_t zPlane, int images) {
     const bool persist = block_sweeps < n;
     const dim3 launch_grid = xcd_tiles > 0 ? dim3(8 * xcd_tiles, 1, images) : dim3(grid.x, grid.y, images);
-#define RTDD_LAUNCH(C, P) hipLaunchKernelGGL((k_sweep_blocked<LX, NT, G, C, P>), launch_grid, dim3(nthreads), 0, ctx->stream, Xk, Xm, Yk, Ym, M, ctx->lut_dev, omegas, ip, rows, cols, hx, hy, n, gamma, block_sweeps, ctx->sync_words, (int)grid.x, (int)grid.y, xcd_tiles, flag_base, zPlane, ctx->wild_seq)
+#define RTDD_LAUNCH(C, P) hipLaunchKernelGGL((k_sweep_blocked<LX, NT, G, C, P>), launch_grid, dim3(nthreads), 0, ctx->stream, Xk, Xm, Yk, Ym, M, ctx->lut_dev, omegas, ip, rows, cols, hx, hy, n, gamma, block_sweeps, ctx->sync_words, (int)grid.x, (int)grid.y, xcd_tiles, flag_base, zPlane, ctx->wild_seq, ctx->opt.debug_withhold_tile)
     if (ctx->opt.fp_contract) { if (persist) RTDD_LAUNCH(true, true); else RTDD_LAUNCH(true, false); }
     else { if (persist) RTDD_LAUNCH(false, true); else RTDD_LAUNCH(false, false); }
 #undef RTDD_LAUNCH
@@ -787,7 +787,7 @@ static int launch_sweeps_blocked_impl(rtdd_ctx *ctx, const Level &L, size_t ip, 
         if (persistent) {
             block_sweeps = T;
             m = n - done;
-            RTDD_TRY(prepare_persistent_launch(ctx, (m + T - 1) / T, &flag_base));   // this launch's flag values, debug words
+            RTDD_TRY(prepare_persistent_launch(ctx, (m + T - 1) / T, &flag_base));   // this launch's flag values, the poll limit
             note_status_writer(ctx);
         }
         // XCD-aware tile placement: +1.5-4 % persistent (strips traded inside one L2), +8 % at 4K launch-per-block (a tile's halo is its
