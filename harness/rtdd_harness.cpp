@@ -12,7 +12,10 @@
 //                 --effect stereo --disparity D [--zero-parallax Z | --zero-parallax-at X,Y] [--anaglyph]   (rtdd_simulate_stereo; default:
 //                 zero parallax at depth 0, the view),
 //                 --effect parallax --shift dx,dy [--dolly z] [--zero-parallax Z | --zero-parallax-at X,Y]   (rtdd_simulate_parallax: the camera moved
-//                 sideways, up or forward; default: no dolly, zero parallax at depth 0),
+//                 sideways, up or forward; default: no dolly, zero parallax at depth 0; with --plate-region id [--remove-grow N] [--remove-behind D]
+//                 the painted region `id` is removed into a background plate held aside (rtdd_remove_object; the scene stays) and the view
+//                 rendered over both layers (rtdd_simulate_parallax_layered); --parallax-depth-out FILE and --parallax-coverage FILE write
+//                 the view's depth map (u8, as DepthMap) and its coverage codes as PGM or PNG),
 //                 --effect relight [--light-dir x,y,z | --light-at X,Y [--light-height H] [--light-radius R]] [--relief S] [--ambient A] [--diffuse D]
 //                 [--light-color b,g,r]   (rtdd_simulate_relight; default: a white directional light from the upper left, (-1, -1, 1), relief 2,
 //                 ambient 0.25, diffuse 1; --light-at: a point light over that pixel, anchored at its depth, height 100, radius 200)
@@ -269,7 +272,14 @@ struct Job {
     rtdd_removal removal = {0, 0, 0.0f};                            // select: the region id
     int move_dx = 0, move_dy = 0;
     float move_depth = 0.0f;
+    // --effect parallax --plate-region ID [--remove-grow N] [--remove-behind D]: the painted region removed (rtdd_remove_object, `removal`)
+    // into a background plate held aside -- the scene itself stays -- and the view rendered over both layers
+    // (rtdd_simulate_parallax_layered); --parallax-depth-out FILE / --parallax-coverage FILE: its depth map (u8, as DepthMap) and coverage
+    bool has_plate = false;
+    std::string parallax_depth_out, parallax_coverage;
 };
+// what --parallax-depth-out and --parallax-coverage write: device 0's last view
+struct ParallaxFiles { std::vector<unsigned char> depth_u8, coverage; };
 
 // --stroke / --erase / --ramp: the job's strokes on a device image pair, one call
 static int stroke_calls(rtdd_ctx *ctx, const Job &job, void *ed, size_t ed_pitch, void *scr, size_t scr_pitch, const void *orig, size_t orig_pitch, int rows, int cols) {
@@ -490,12 +500,14 @@ static void warm_up(int device) {
 
 // One GPU: context + stream + device staging, runs `count` estimates; keeps the last result on the host.
 static int run_device(int device, const Job &job, int count, bool live, std::vector<unsigned char> *depth_u8, std::vector<unsigned char> *art, double *ms_per_estimate,
-                      std::vector<std::vector<unsigned char>> *every_map = nullptr, std::vector<unsigned char> *annotated = nullptr) {
+                      std::vector<std::vector<unsigned char>> *every_map = nullptr, std::vector<unsigned char> *annotated = nullptr,
+                      ParallaxFiles *parallax_files = nullptr) {
     // everything this function owns, released on EVERY return path (the CK() early returns included)
     struct Owned {
         rtdd_ctx *ctx = nullptr; hipStream_t stream = nullptr; unsigned char *d_bgr = nullptr, *d_ann = nullptr;
         unsigned char *d_sprite = nullptr, *d_lart = nullptr; float *d_lz = nullptr;      // --layer: the sprite, the composite and its depth map
         unsigned char *d_rart = nullptr, *d_msprite = nullptr, *d_mart = nullptr; float *d_rz = nullptr, *d_mz = nullptr;     // --remove-region / --move-region
+        unsigned char *d_part = nullptr, *d_pz8 = nullptr, *d_pcov = nullptr; float *d_pplz = nullptr, *d_pz = nullptr;          // --plate-region: the plate; the view's depth map (f32, u8) and coverage
         ~Owned() {
             if (d_bgr) (void)hipFree(d_bgr);
             if (d_ann) (void)hipFree(d_ann);
@@ -507,6 +519,11 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
             if (d_msprite) (void)hipFree(d_msprite);
             if (d_mart) (void)hipFree(d_mart);
             if (d_mz) (void)hipFree(d_mz);
+            if (d_part) (void)hipFree(d_part);
+            if (d_pplz) (void)hipFree(d_pplz);
+            if (d_pz) (void)hipFree(d_pz);
+            if (d_pz8) (void)hipFree(d_pz8);
+            if (d_pcov) (void)hipFree(d_pcov);
             if (ctx) rtdd_ctx_destroy(ctx);           // synchronises the stream first
             if (stream) (void)hipStreamDestroy(stream);
         }
@@ -586,6 +603,15 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
         const size_t px = (size_t)rows * cols;
         bool ok = hipMalloc((void **)&own.d_rart, px * 3) == hipSuccess && hipMalloc((void **)&own.d_rz, px * 4) == hipSuccess;
         if (ok && job.has_move) ok = hipMalloc((void **)&own.d_msprite, px * 4) == hipSuccess && hipMalloc((void **)&own.d_mart, px * 3) == hipSuccess && hipMalloc((void **)&own.d_mz, px * 4) == hipSuccess;
+        if (!ok) { std::printf("device %d: out of memory\n", device); return RTDD_ERR_NOMEM; }
+    }
+    const bool want_pz = !job.parallax_depth_out.empty(), want_pcov = !job.parallax_coverage.empty();
+    if (job.has_plate || want_pz || want_pcov) {                       // --plate-region, --parallax-depth-out, --parallax-coverage
+        const size_t px = (size_t)rows * cols;
+        bool ok = true;
+        if (job.has_plate) ok = hipMalloc((void **)&own.d_part, px * 3) == hipSuccess && hipMalloc((void **)&own.d_pplz, px * 4) == hipSuccess;
+        if (ok && want_pz) ok = hipMalloc((void **)&own.d_pz, px * 4) == hipSuccess && hipMalloc((void **)&own.d_pz8, px) == hipSuccess;
+        if (ok && want_pcov) ok = hipMalloc((void **)&own.d_pcov, px) == hipSuccess;
         if (!ok) { std::printf("device %d: out of memory\n", device); return RTDD_ERR_NOMEM; }
     }
 
@@ -750,7 +776,25 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
                                     job.zero_depth, job.zero_x, job.zero_y, job.anaglyph ? RTDD_STEREO_ANAGLYPH : RTDD_STEREO_VIEW));
         else if (job.effect == "parallax") {
             const rtdd_parallax view = {job.shift_x, job.shift_y, job.dolly, job.zero_depth, job.zero_x, job.zero_y};
-            CK(rtdd_simulate_parallax(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols, &view));
+            const size_t w1 = (size_t)cols, w3 = w1 * 3, w4 = w1 * 4;
+            if (job.has_plate) {                                        // the region taken out of the scene into the plate; the scene itself stays
+                void *p_code; size_t pi_code;
+                CK(rtdd_pyramid_image(ctx, RTDD_IMG_REGION_CODE, 0, &p_code, &pi_code, nullptr, nullptr));
+                CK(rtdd_remove_object(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_code, pi_code, own.d_part, w3, own.d_pplz, w4, rows, cols, &job.removal));
+            }
+            if (job.has_plate || own.d_pz || own.d_pcov)
+                CK(rtdd_simulate_parallax_layered(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, own.d_part, w3, own.d_pplz, w4, (uint8_t *)p_art, pi_art,
+                                                  own.d_pz, w4, own.d_pcov, w1, rows, cols, &view));
+            else CK(rtdd_simulate_parallax(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_art, pi_art, rows, cols, &view));
+            if (own.d_pz && parallax_files) {                           // the view's depth map as the harness writes every depth map: u8
+                CK(rtdd_depth_to_u8(ctx, own.d_pz, w4, own.d_pz8, w1, rows, cols));
+                parallax_files->depth_u8.resize((size_t)rows * cols);
+                CK(rtdd_download(ctx, parallax_files->depth_u8.data(), w1, own.d_pz8, w1, w1, rows));
+            }
+            if (own.d_pcov && parallax_files) {
+                parallax_files->coverage.resize((size_t)rows * cols);
+                CK(rtdd_download(ctx, parallax_files->coverage.data(), w1, own.d_pcov, w1, w1, rows));
+            }
         }
         else if (job.effect == "relight") {
             rtdd_light light = job.light;
@@ -792,7 +836,7 @@ int main(int argc, const char *argv[]) {
     if (argc == 1) { std::printf("Usage: rtdd_harness -i image.(jpg|png|ppm) [-a annotation.(png|pgm)] [-o prefix] [--effect defocus|desaturation|haze|refocus|stereo|parallax|relight|ao|lighting] [--iters N] [--refine sor|mg|auto [--tolerance T]]\n"
                                  "                    [--focus D | --focus-at X,Y] [--aperture A] [--bokeh box|disc|spread] (refocus)  [--haze-beta B] [--airlight b,g,r] (haze)\n"
                                  "                    [--disparity D] [--zero-parallax Z | --zero-parallax-at X,Y] [--anaglyph] (stereo)\n"
-                                 "                    --shift dx,dy [--dolly z] [--zero-parallax Z | --zero-parallax-at X,Y] (parallax)\n"
+                                 "                    --shift dx,dy [--dolly z] [--zero-parallax Z | --zero-parallax-at X,Y] [--plate-region id [--remove-grow N] [--remove-behind D]] [--parallax-depth-out FILE] [--parallax-coverage FILE] (parallax; --plate-region with --regions: the painted region removed into a background plate, rtdd_simulate_parallax_layered)\n"
                                  "                    [--light-dir x,y,z | --light-at X,Y [--light-height H] [--light-radius R]] [--relief S] [--ambient A] [--diffuse D] [--light-color b,g,r] (relight)\n"
                                  "                    [--shadows N [--shadow-bias B] [--shadow-softness S] [--shadow-strength T]] (relight with cast shadows)\n"
                                  "                    [--ao-radius R] [--ao-directions 4|8] [--ao-bias B] [--ao-strength T] [--relief S] [--ao-map] (ao)  [--ao R [--ao-directions ..] [--ao-bias ..] [--ao-strength ..]] (relight with its ambient term occluded)\n"
@@ -937,6 +981,9 @@ int main(int argc, const char *argv[]) {
             job.light.colorB = (uint8_t)c[0]; job.light.colorG = (uint8_t)c[1]; job.light.colorR = (uint8_t)c[2];
         }
         else if (!std::strcmp(argv[i], "--remove-region")) { job.removal.select = std::atoi(next()); job.has_remove = true; }
+        else if (!std::strcmp(argv[i], "--plate-region")) { job.removal.select = std::atoi(next()); job.has_plate = true; }
+        else if (!std::strcmp(argv[i], "--parallax-depth-out")) job.parallax_depth_out = next();
+        else if (!std::strcmp(argv[i], "--parallax-coverage")) job.parallax_coverage = next();
         else if (!std::strcmp(argv[i], "--remove-grow")) { job.removal.grow = std::atoi(next()); remove_opt = true; }
         else if (!std::strcmp(argv[i], "--remove-behind")) { job.removal.sourceMinDepth = (float)std::atof(next()); remove_opt = true; }
         else if (!std::strcmp(argv[i], "--move-region")) {
@@ -991,7 +1038,14 @@ int main(int argc, const char *argv[]) {
     if (!layer_path.empty() && !layer_at) { std::printf("--layer needs --layer-at x,y\n"); return 1; }
     if (live > 0 && !layer_path.empty()) { std::printf("--layer is not supported with --live\n"); return 1; }
     // a removal works on a painted region: its flags belong to it, it needs the regions, and one of the two forms at a time
-    if (remove_opt && !job.has_remove && !job.has_move) { std::printf("--remove-grow and --remove-behind need --remove-region id or --move-region id:dx,dy\n"); return 1; }
+    if (remove_opt && !job.has_remove && !job.has_move && !job.has_plate) { std::printf("--remove-grow and --remove-behind need --remove-region id, --move-region id:dx,dy or --plate-region id\n"); return 1; }
+    // the two-layer parallax view: a plate is a painted region removed for --effect parallax alone; one removal per run
+    const bool parallax_out = !job.parallax_depth_out.empty() || !job.parallax_coverage.empty();
+    if (live > 0 && (job.has_plate || parallax_out)) { std::printf("--plate-region, --parallax-depth-out and --parallax-coverage are not supported with --live\n"); return 1; }
+    if ((job.has_plate || parallax_out) && job.effect != "parallax") { std::printf("--plate-region, --parallax-depth-out and --parallax-coverage need --effect parallax\n"); return 1; }
+    if (job.has_plate && (job.has_remove || job.has_move)) { std::printf("--plate-region cannot be combined with --remove-region or --move-region\n"); return 1; }
+    if (job.has_plate && job.region_flags == 0) { std::printf("--plate-region needs --regions cut|smooth|both and a painted region\n"); return 1; }
+    if (job.has_plate && (job.removal.select < 1 || job.removal.select > 255)) { std::printf("a region id is 1..255\n"); return 1; }
     if (job.has_remove && job.has_move) { std::printf("--remove-region and --move-region: one at a time\n"); return 1; }
     if (live > 0 && (job.has_remove || job.has_move)) { std::printf("--remove-region and --move-region are not supported with --live\n"); return 1; }
     if ((job.has_remove || job.has_move) && job.region_flags == 0) { std::printf("--remove-region and --move-region need --regions cut|smooth|both and a painted region\n"); return 1; }
@@ -1037,9 +1091,10 @@ int main(int argc, const char *argv[]) {
     for (int b = 0; b < batch; b++) counts[b % devices]++;               // image b -> device b % D
     if (live > 0) { counts.assign(devices, 0); counts[0] = live; }
     auto t0 = std::chrono::steady_clock::now();
+    ParallaxFiles parallax_files;
     std::vector<std::thread> th;
     for (int d = 0; d < devices; d++)
-        th.emplace_back([&, d]() { rcs[d] = counts[d] ? run_device(d, job, counts[d], live > 0, &depth[d], &art[d], &ms[d], write_all ? &every[d] : nullptr, d == 0 ? &annotated[0] : nullptr) : 0; });
+        th.emplace_back([&, d]() { rcs[d] = counts[d] ? run_device(d, job, counts[d], live > 0, &depth[d], &art[d], &ms[d], write_all ? &every[d] : nullptr, d == 0 ? &annotated[0] : nullptr, d == 0 ? &parallax_files : nullptr) : 0; });
     for (auto &t : th) t.join();
     const double wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     for (int d = 0; d < devices; d++) if (rcs[d]) return 4;
@@ -1065,6 +1120,8 @@ int main(int argc, const char *argv[]) {
         for (size_t i = 0; i < o.size(); i += 3) { o[i] = art[0][i + 2]; o[i + 2] = art[0][i]; }     // BGR -> RGB for the file
         if (!write_image(out + (png ? "ArtisticEffect.png" : "ArtisticEffect.ppm"), rgb.w, rgb.h, 3, o.data())) return 5;
     }
+    if (!job.parallax_depth_out.empty() && !write_image(job.parallax_depth_out, rgb.w, rgb.h, 1, parallax_files.depth_u8.data())) { std::printf("cannot write %s\n", job.parallax_depth_out.c_str()); return 5; }
+    if (!job.parallax_coverage.empty() && !write_image(job.parallax_coverage, rgb.w, rgb.h, 1, parallax_files.coverage.data())) { std::printf("cannot write %s\n", job.parallax_coverage.c_str()); return 5; }
     if (write_all)
         for (int d = 0; d < devices; d++)
             for (size_t n = 0; n < every[d].size(); n++) {

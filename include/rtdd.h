@@ -545,7 +545,7 @@ int rtdd_simulate_haze(rtdd_ctx *ctx, const uint8_t *original, size_t originalPi
  * Added after ABI version 230 without a version bump: a host finds them by symbol (dlsym).  The next bump of RTDD_VERSION
  * should cover them (rtdd_simulate_refocus, rtdd_simulate_lens_blur, rtdd_simulate_haze_ex, rtdd_simulate_stereo, rtdd_simulate_relight,
  * rtdd_simulate_relight_shadowed, rtdd_simulate_parallax, rtdd_simulate_ambient_occlusion, rtdd_simulate_lighting, rtdd_simulate_bokeh,
- * rtdd_composite_layer, rtdd_remove_object, rtdd_lift_layer),
+ * rtdd_composite_layer, rtdd_remove_object, rtdd_lift_layer, rtdd_simulate_parallax_layered),
  * together with a
  * parameterised live effect
  * (rtdd_live_submit_ex takes an effect code only and knows none of them). */
@@ -775,6 +775,51 @@ typedef struct rtdd_parallax {
 int rtdd_simulate_parallax(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch,
                            const float *depth, size_t depthPitch, uint8_t *artistic, size_t artisticPitch,
                            int rows, int cols, const rtdd_parallax *view /* HOST, read before the call returns */);
+
+/* Parallax over TWO LAYERS: rtdd_simulate_parallax with a BACKGROUND PLATE -- the scene without the object, colour and depth, as
+ * rtdd_remove_object writes it -- that fills what the camera's move uncovers, instead of a smear of the background's edge pixel; and
+ * with the view's own depth map and a coverage map as outputs, so that artistic / depthOut are original / depth of every other call.
+ * Everything not named here is rtdd_simulate_parallax's, bit for bit: d', z0, (ax, ay), the source shift, the march, every f32
+ * operation rounded once with nothing fused.
+ *   SOURCES:  every pixel of the front layer (original, depth), as there.  With a plate, every pixel of the plate too: d' of plateDepth,
+ *       the colour of plate, the same (ax, ay) at its own position.  z0 is the same for both layers; in the pixel form it is read from
+ *       the FRONT map at (zeroX, zeroY), on the device, when the kernel runs.
+ *   WINNER:  the smallest d'; among equal d' the FRONT layer; among equal d' and layer the smallest y * cols + x.
+ *       A plate pixel whose d' equals the front's d' at the SAME pixel lands on the same target with the same depth: it always loses, and
+ *       an implementation may skip it without reading its colour (a plate from rtdd_remove_object then costs work on its hole alone).
+ *   CRACK:  a slanted surface is stretched by the warp and one-pixel gaps open between its own sources, where the plate would shine
+ *       through.  Take a BACK-won target t, with (ax, ay), m, stx, sty at t as the hole rule forms them, and m != 0:
+ *           p+ = t + ((int)rintf(stx), (int)rintf(sty)),  p- = t - ((int)rintf(stx), (int)rintf(sty))        (the march's step k = 1)
+ *       t is a crack iff p+ and p- are both inside the image, both FRONT-won, and both winners' d' are STRICTLY smaller than the d' of
+ *       t's winner.  A crack takes the source of p+.  A crack's neighbours are front-won, so they are never cracks: no recursion.  A
+ *       one-pixel gap between an object and front-layer background at the plate's own depth is a true disocclusion (equal d'): it keeps
+ *       the plate's pixel.  A surface stretched by more than 2 x opens gaps two pixels wide, which this rule does not close.
+ *   HOLE (a target neither layer lands on):  the march as there, over "filled" = a source of either layer landed.  The hole takes the
+ *       SOURCE of the first filled p: p's winner, or, where p is a crack, the crack's source.
+ *   OUTPUTS:  artistic[t] = the colour of t's source, from original or plate by its layer.  depthOut[t] = that source's d' (the clamped
+ *       value with -0 folded into +0, never the map's raw bits).  A hole that both marches leave, or one with m == 0, gets original[t]
+ *       and the front d'(t).  coverage[t] = 0 front-won, 1 back-won, 2 a crack, 3 a hole filled by a march, 4 a hole left as the original.
+ *       The codes are chosen so that rtdd_remove_object(artistic, depthOut, coverage, ..., select = 3) fills the remaining smears by
+ *       push-pull.
+ * Identities: with plate == NULL artistic is rtdd_simulate_parallax's byte for byte; so it is with a plate equal to the front layer (the
+ * same arrays, or copies), and with a plate whose DEPTH has the front's d' everywhere, whatever its colours; shiftX == shiftY == 0 with
+ * dolly == 0 gives original, the front d' and coverage 0 everywhere, with no plate or a plate that is nowhere NEARER than the front
+ * layer at the same pixel (every background plate; a plate pixel that is nearer wins its own target by the WINNER rule, motion or
+ * none).  The outcome never depends on the order in which sources reach a
+ * target, nor on RTDD_OPT_FP_CONTRACT.  Stream-ordered, the same scratch and passes as rtdd_simulate_parallax; with plate, depthOut and
+ * coverage all NULL the launches are that call's.  Not in place: a healed time-out runs the call again, and the second run must read
+ * what the first one read.  RTDD_VERSION is unchanged: a host finds the symbol by name.
+ * Refused on the host (RTDD_ERR_INVALID), before any launch: everything rtdd_simulate_parallax refuses of the images and the view;
+ * exactly one of plate / plateDepth null; platePitch < 3 * cols; plateDepthPitch or depthOutPitch below 4 * cols, or either image
+ * misaligned as depth's rule says; coveragePitch < cols; artistic equal to original or plate; depthOut equal to depth or plateDepth. */
+int rtdd_simulate_parallax_layered(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch,
+                                   const float *depth, size_t depthPitch,                 /* the FRONT layer */
+                                   const uint8_t *plate, size_t platePitch,
+                                   const float *plateDepth, size_t plateDepthPitch,       /* the BACK layer: both or neither NULL */
+                                   uint8_t *artistic, size_t artisticPitch,
+                                   float *depthOut, size_t depthOutPitch,                 /* may be NULL: no depth is written */
+                                   uint8_t *coverage, size_t coveragePitch,               /* may be NULL: u8, rows x cols */
+                                   int rows, int cols, const rtdd_parallax *view /* HOST, read before the call returns */);
 
 /* Ambient occlusion: the third term of relight's lighting model.  The height field H(x, y) = relief * (255 - d'(x, y)) of
  * rtdd_simulate_relight_shadowed is searched, from every pixel, along 4 or 8 fixed compass directions over `radius` pixels for its

@@ -55,6 +55,7 @@ C_ABI_SYMBOLS = [
     "rtdd_paint_strokes", "rtdd_pyramid_annotation_rebuild", "rtdd_paint_ramp_strokes", "rtdd_ramp_polyline", "rtdd_fill_polygon", "rtdd_fill_similar",
     "rtdd_simulate_relight", "rtdd_simulate_relight_shadowed", "rtdd_simulate_parallax", "rtdd_simulate_ambient_occlusion",
     "rtdd_simulate_lighting", "rtdd_simulate_bokeh", "rtdd_composite_layer", "rtdd_remove_object", "rtdd_lift_layer",
+    "rtdd_simulate_parallax_layered",
     "rtdd_solve_guided", "rtdd_index_to_weight_guided", "rtdd_pyrdown_bgr", "rtdd_pyramid_set_guide", "rtdd_pyramid_guide",
     "rtdd_solve_regions", "rtdd_index_to_weight_regions", "rtdd_region_codes", "rtdd_pyramid_set_regions", "rtdd_pyramid_regions",
     "rtdd_pyramid_regions_changed",
@@ -589,6 +590,21 @@ class Context:
         o, op = _img(originalImage); d, dp = _img(depthImage); a, ap = _img(artisticImage)
         self._check(lib().rtdd_simulate_parallax(self._h, o, op, d, dp, a, ap, C.c_int(rows), C.c_int(cols),
                                                  C.byref(view) if view is not None else None))
+
+    def simulate_parallax_layered(self, originalImage, depthImage, plateImage, plateDepthImage, artisticImage, depthOutImage, coverageImage,
+                                  rows, cols, view):
+        """simulate_parallax over two layers: the plate (plateImage u8 x 3 and plateDepthImage f32, both or neither None: the scene without
+        the object, as remove_object writes it) fills what the camera's move uncovers.  depthOutImage (f32) and coverageImage (u8: 0
+        front-won, 1 back-won, 2 a crack, 3 a hole filled by a march, 4 a hole left as the original) receive the view's depth map and its
+        coverage; each may be None for the C call's null pointer."""
+        null = (None, C.c_size_t(0))
+        o, op = _img(originalImage); d, dp = _img(depthImage); a, ap = _img(artisticImage)
+        p, pp = _img(plateImage) if plateImage is not None else null
+        q, qp = _img(plateDepthImage) if plateDepthImage is not None else null
+        z, zp = _img(depthOutImage) if depthOutImage is not None else null
+        c, cp = _img(coverageImage) if coverageImage is not None else null
+        self._check(lib().rtdd_simulate_parallax_layered(self._h, o, op, d, dp, p, pp, q, qp, a, ap, z, zp, c, cp, C.c_int(rows), C.c_int(cols),
+                                                         C.byref(view) if view is not None else None))
 
     def simulate_ambient_occlusion(self, originalImage, depthImage, artisticImage, rows, cols, ao, light=None):
         """Ambient occlusion from the depth map as `ao` (an AmbientOcclusion, or None for the C call's null pointer) says: alone

@@ -879,7 +879,8 @@ int launch_effect(rtdd_ctx *ctx, const Effect &e) {
         case Effect::kLensBlur: return launch_lens_blur(ctx, e);       // lens_blur.hip
         case Effect::kRelight: return launch_relight(ctx, e);          // relight.hip
         case Effect::kRelightShadow: return launch_relight_shadow(ctx, e);     // relight_shadow.hip
-        case Effect::kParallax: return launch_parallax(ctx, e);        // parallax.hip
+        case Effect::kParallax:
+        case Effect::kParallaxLayered: return launch_parallax(ctx, e); // parallax.hip
         case Effect::kAmbientOcclusion: return launch_ambient_occlusion(ctx, e);   // ambient_occlusion.hip
         case Effect::kLighting: return launch_lighting(ctx, e);        // lighting.hip
         case Effect::kBokeh: return launch_bokeh(ctx, e);              // bokeh.hip

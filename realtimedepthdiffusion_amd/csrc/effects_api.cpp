@@ -224,11 +224,9 @@ int rtdd_simulate_relight_shadowed(rtdd_ctx *ctx, const uint8_t *original, size_
     return simulate(ctx, e);
 }
 
-int rtdd_simulate_parallax(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
-                           uint8_t *artistic, size_t artisticPitch, int rows, int cols, const rtdd_parallax *view) {
-    if (!ctx) return RTDD_ERR_INVALID;
-    int rc = check_effect(ctx, original, depth, artistic, originalPitch, depthPitch, artisticPitch, rows, cols);
-    if (rc != RTDD_OK) return rc;
+// The checks of rtdd_simulate_parallax's view behind the images', and the view as the kernels take it (e.parallax), for the two parallax calls.
+static int prepare_parallax(rtdd_ctx *ctx, Effect &e, const rtdd_parallax *view) {
+    const int rows = e.rows, cols = e.cols;
     REQUIRE(ctx, view, "null view");
     const rtdd_parallax &q = *view;
     REQUIRE(ctx, q.shiftX >= -256 && q.shiftX <= 256 && q.shiftY >= -256 && q.shiftY <= 256, "|shiftX| and |shiftY| must be <= 256");
@@ -238,13 +236,53 @@ int rtdd_simulate_parallax(rtdd_ctx *ctx, const uint8_t *original, size_t origin
     if (q.zeroX < 0) REQUIRE(ctx, std::isfinite(q.zeroParallaxDepth) && q.zeroParallaxDepth >= 0.0f && q.zeroParallaxDepth <= 255.0f,
                              "zeroParallaxDepth must be finite and in [0, 255]");
     else REQUIRE(ctx, q.zeroX < cols && q.zeroY >= 0 && q.zeroY < rows, "zero-parallax pixel outside the image");
-    if (rows == 0 || cols == 0) return RTDD_OK;
-    REQUIRE(ctx, original != artistic, "parallax cannot run in place");
-    Effect e{Effect::kParallax, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols};
     Effect::Parallax &P = e.parallax;
     P.shiftX = q.shiftX; P.shiftY = q.shiftY; P.dolly = q.dolly; P.zeroX = q.zeroX; P.zeroY = q.zeroY;
     P.zeroDepth = q.zeroParallaxDepth;
     P.cx = (float)(cols - 1) * 0.5f; P.cy = (float)(rows - 1) * 0.5f;
+    return RTDD_OK;
+}
+
+int rtdd_simulate_parallax(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
+                           uint8_t *artistic, size_t artisticPitch, int rows, int cols, const rtdd_parallax *view) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    int rc = check_effect(ctx, original, depth, artistic, originalPitch, depthPitch, artisticPitch, rows, cols);
+    if (rc != RTDD_OK) return rc;
+    Effect e{Effect::kParallax, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols};
+    rc = prepare_parallax(ctx, e, view);
+    if (rc != RTDD_OK) return rc;
+    if (rows == 0 || cols == 0) return RTDD_OK;
+    REQUIRE(ctx, original != artistic, "parallax cannot run in place");
+    return simulate(ctx, e);
+}
+
+int rtdd_simulate_parallax_layered(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch,
+                                   const uint8_t *plate, size_t platePitch, const float *plateDepth, size_t plateDepthPitch,
+                                   uint8_t *artistic, size_t artisticPitch, float *depthOut, size_t depthOutPitch, uint8_t *coverage,
+                                   size_t coveragePitch, int rows, int cols, const rtdd_parallax *view) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    int rc = check_effect(ctx, original, depth, artistic, originalPitch, depthPitch, artisticPitch, rows, cols);
+    if (rc != RTDD_OK) return rc;
+    REQUIRE(ctx, (plate == nullptr) == (plateDepth == nullptr), "plate and plateDepth must both be given or both be null");
+    if (plate) {
+        REQUIRE(ctx, platePitch >= (size_t)cols * 3 && plateDepthPitch >= (size_t)cols * 4, "pitch smaller than a row");
+        REQUIRE(ctx, f32_image_aligned(plateDepth, plateDepthPitch), kF32AlignText);
+    }
+    if (depthOut) {
+        REQUIRE(ctx, depthOutPitch >= (size_t)cols * 4, "pitch smaller than a row");
+        REQUIRE(ctx, f32_image_aligned(depthOut, depthOutPitch), kF32AlignText);
+    }
+    if (coverage) REQUIRE(ctx, coveragePitch >= (size_t)cols, "pitch smaller than a row");
+    Effect e{Effect::kParallaxLayered, original, originalPitch, depth, depthPitch, artistic, artisticPitch, rows, cols};
+    rc = prepare_parallax(ctx, e, view);
+    if (rc != RTDD_OK) return rc;
+    if (rows == 0 || cols == 0) return RTDD_OK;
+    REQUIRE(ctx, original != artistic && plate != artistic, "parallax cannot run in place");
+    REQUIRE(ctx, !depthOut || ((const float *)depthOut != depth && (const float *)depthOut != plateDepth), "parallax cannot run in place");
+    Effect::ParallaxLayers &l = e.layers;
+    if (plate) { l.plate = plate; l.platePitch = platePitch; l.plateDepth = plateDepth; l.plateDepthPitch = plateDepthPitch; }
+    if (depthOut) { l.depthOut = depthOut; l.depthOutPitch = depthOutPitch; }
+    if (coverage) { l.coverage = coverage; l.coveragePitch = coveragePitch; }
     return simulate(ctx, e);
 }
 

@@ -1,4 +1,4 @@
-// parallax.hip -- the 2-D parallax view (rtdd_simulate_parallax, include/rtdd.h): the camera moved sideways, up or forward.  Stereo's
+// parallax.hip -- the 2-D parallax view (rtdd_simulate_parallax and rtdd_simulate_parallax_layered, include/rtdd.h): the camera moved sideways, up or forward.  Stereo's
 // forward warp with a shift in x AND y that may vary over the image (the dolly): sources cross rows, so the occlusion is resolved over
 // the whole image, in a z-buffer in global memory, and holes open -- and are filled -- in every direction.
 //
@@ -120,9 +120,155 @@ __global__ __launch_bounds__(256) void k_parallax_resolve(const uint8_t *__restr
     }
 }
 
-// rtdd_simulate_parallax (arguments checked by effects_api.cpp): the keys emptied, scattered, resolved.
+// ---- the two-layer view (rtdd_simulate_parallax_layered) ------------------------------------------------------------------------------
+// The same three passes over the same keys; bit 31 of a key's low word says that the source is a plate pixel, so that at equal d' the
+// front layer wins and the source index (< 2^30) still breaks the ties within a layer.  The two kernels above are rtdd_simulate_parallax's
+// and stay as they are; these are launched when the call has a plate, a depthOut or a coverage.
+typedef Effect::ParallaxLayers Layers;
+constexpr uint32_t kPxBack = 0x80000000u;
+
+// one source: depth d' = dc, shift field (ax, ay), low word `low`
+__device__ __forceinline__ void parallax_put(u64 *__restrict__ keys, int rows, int cols, int x, int y, float ax, float ay, float dc, float z0,
+                                             uint32_t low) {
+    const float dz = dc - z0;
+    const int tx = x + (int)rintf((ax * dz) / 255.0f), ty = y + (int)rintf((ay * dz) / 255.0f);
+    if (tx < 0 || tx >= cols || ty < 0 || ty >= rows) return;       // the only stores of the kernel: inside the rows * cols keys
+    const u64 key = ((u64)__float_as_uint(dc) << 32) | low;
+    (void)__hip_atomic_fetch_min(&keys[(size_t)ty * cols + tx], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// One lane per pixel, both layers: a wave reads 256 contiguous bytes of each depth row.  A plate source whose d' equals the front's at the
+// same pixel lands on the same target with the same high word and the larger low word: it never wins, and no atomic is issued for it
+// (d' is never -0 or NaN: equal bits are equal depths).  A plate made by rtdd_remove_object costs atomics on its hole alone.
+__global__ __launch_bounds__(256) void k_parallax_scatter_layered(const float *__restrict__ depth, size_t dp, const float *__restrict__ pdepth,
+                                                                  size_t pdp, u64 *__restrict__ keys, int rows, int cols, Parallax v,
+                                                                  const float *__restrict__ zp) {
+    const int y = blockIdx.y * 4 + wave_id();
+    if (y >= rows) return;                                           // wave-uniform
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    if (x >= cols) return;
+    const float z0 = zp ? parallax_depth(*zp) : v.zeroDepth;        // the FRONT map's pixel, for both layers
+    const float dc = parallax_depth(((const float *)((const char *)depth + (size_t)y * dp))[x]);
+    const float pc = parallax_depth(((const float *)((const char *)pdepth + (size_t)y * pdp))[x]);
+    float ax, ay;
+    parallax_a(v, x, y, ax, ay);
+    const uint32_t self = (uint32_t)(y * cols + x);
+    parallax_put(keys, rows, cols, x, y, ax, ay, dc, z0, self);
+    if (__float_as_uint(pc) != __float_as_uint(dc)) parallax_put(keys, rows, cols, x, y, ax, ay, pc, z0, self | kPxBack);
+}
+
+// parallax_march that also says where it stopped: (px, py) of the filled target whose key it returns
+__device__ __forceinline__ u64 parallax_march_to(const u64 *__restrict__ keys, int rows, int cols, int x, int y, float stx, float sty, int sign,
+                                                 int &px, int &py) {
+    for (int k = 1;; k++) {
+        const float kf = (float)k;
+        px = x + sign * (int)rintf(kf * stx); py = y + sign * (int)rintf(kf * sty);
+        if (px < 0 || px >= cols || py < 0 || py >= rows) return kPxEmpty;
+        const u64 key = keys[(size_t)py * cols + px];
+        if (key != kPxEmpty) return key;
+    }
+}
+
+// The key of the SOURCE of a filled target (x, y) whose own key is `key`: the key itself, unless the target is a crack -- back-won, m != 0,
+// and both neighbours p+ and p- of the march's step k = 1 inside the image, front-won and strictly nearer -- which takes p+'s key.  An
+// empty key has bit 31 of its low word set: it counts as not front-won.  The high words are non-negative floats: integer order.
+__device__ __forceinline__ u64 parallax_source(const u64 *__restrict__ keys, int rows, int cols, const Parallax &v, int x, int y, u64 key) {
+    if (!((uint32_t)key & kPxBack)) return key;
+    float ax, ay;
+    parallax_a(v, x, y, ax, ay);
+    const float m = fmaxf(fabsf(ax), fabsf(ay));
+    if (m == 0.0f) return key;
+    const int dx = (int)rintf(ax / m), dy = (int)rintf(ay / m);      // (rintf(1.0f * st) of the march: the product is exact)
+    const int px = x + dx, py = y + dy, qx = x - dx, qy = y - dy;
+    if (px < 0 || px >= cols || py < 0 || py >= rows || qx < 0 || qx >= cols || qy < 0 || qy >= rows) return key;
+    const u64 kp = keys[(size_t)py * cols + px], kq = keys[(size_t)qy * cols + qx];
+    const uint32_t ht = (uint32_t)(key >> 32);
+    if ((((uint32_t)kp | (uint32_t)kq) & kPxBack) || (uint32_t)(kp >> 32) >= ht || (uint32_t)(kq >> 32) >= ht) return key;
+    return kp;
+}
+
+struct PxOut { uint32_t bgr; float d; uint32_t code; };
+
+// VEC: four targets per lane; the rows of artistic and coverage take dword stores, those of depthOut a float4 (every GIVEN output is
+// aligned for it); else one target per lane, bytes and single floats.  depthOut and coverage may be null, the plate too (wave-uniform).
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_parallax_resolve_layered(const uint8_t *__restrict__ orig, size_t op, const float *__restrict__ depth,
+                                                                  size_t dp, const uint8_t *__restrict__ plate, size_t pp,
+                                                                  const u64 *__restrict__ keys, uint8_t *__restrict__ art, size_t ap,
+                                                                  float *__restrict__ dout, size_t zp, uint8_t *__restrict__ cov, size_t cp,
+                                                                  int rows, int cols, Parallax v) {
+    const int y = blockIdx.y * 4 + wave_id();
+    if (y >= rows) return;                                           // wave-uniform
+    const int lane = threadIdx.x & 63;
+    uint8_t *arow = art + (size_t)y * ap;
+    float *zrow = dout ? (float *)((char *)dout + (size_t)y * zp) : nullptr;
+    uint8_t *crow = cov ? cov + (size_t)y * cp : nullptr;
+    auto pixel = [&](int x) -> PxOut {                               // colour, d' and coverage code of view[(x, y)]
+        const uint32_t self = (uint32_t)(y * cols + x);
+        u64 key = keys[self];
+        uint32_t code;
+        if (key == kPxEmpty) {                                       // a hole: towards the background side (+a), then the other one
+            code = 4;
+            float ax, ay;
+            parallax_a(v, x, y, ax, ay);
+            const float m = fmaxf(fabsf(ax), fabsf(ay));
+            if (m != 0.0f) {
+                const float stx = ax / m, sty = ay / m;
+                int px, py;
+                key = parallax_march_to(keys, rows, cols, x, y, stx, sty, 1, px, py);
+                if (key == kPxEmpty) key = parallax_march_to(keys, rows, cols, x, y, stx, sty, -1, px, py);
+                if (key != kPxEmpty) { code = 3; key = parallax_source(keys, rows, cols, v, px, py, key); }     // the hit may be a crack
+            }
+        } else {
+            const u64 s = parallax_source(keys, rows, cols, v, x, y, key);
+            code = !((uint32_t)key & kPxBack) ? 0 : (s != key ? 2 : 1);     // (a crack's source is front-won: never the key itself)
+            key = s;
+        }
+        PxOut o;
+        o.code = code;
+        if (key == kPxEmpty) {                                       // a hole that stays: original[t] and the front d'(t)
+            o.bgr = bgr_of_index(orig, op, self, cols);
+            o.d = parallax_depth(((const float *)((const char *)depth + (size_t)y * dp))[x]);
+        } else {
+            const uint32_t low = (uint32_t)key;
+            o.bgr = (low & kPxBack) ? bgr_of_index(plate, pp, low & ~kPxBack, cols) : bgr_of_index(orig, op, low, cols);
+            o.d = __uint_as_float((uint32_t)(key >> 32));            // the clamped d' with +0, as the scatter packed it
+        }
+        return o;
+    };
+    auto store1 = [&](int x, const PxOut &o) {
+        uint8_t *p = arow + 3 * (size_t)x;
+        p[0] = (uint8_t)o.bgr; p[1] = (uint8_t)(o.bgr >> 8); p[2] = (uint8_t)(o.bgr >> 16);
+        if (zrow) zrow[x] = o.d;
+        if (crow) crow[x] = (uint8_t)o.code;
+    };
+    if (!VEC) {
+        const int x = blockIdx.x * 64 + lane;
+        if (x >= cols) return;
+        store1(x, pixel(x));
+        return;
+    }
+    const int x = (blockIdx.x * 64 + lane) * 4;
+    if (x >= cols) return;
+    if (x + 3 < cols) {
+        const PxOut o0 = pixel(x), o1 = pixel(x + 1), o2 = pixel(x + 2), o3 = pixel(x + 3);
+        uint32_t *a3 = (uint32_t *)(arow + 3 * (size_t)x);
+        a3[0] = o0.bgr | (o1.bgr << 24);
+        a3[1] = (o1.bgr >> 8) | (o2.bgr << 16);
+        a3[2] = (o2.bgr >> 16) | (o3.bgr << 8);
+        if (zrow) *(float4 *)(zrow + x) = make_float4(o0.d, o1.d, o2.d, o3.d);
+        if (crow) *(uint32_t *)(crow + x) = o0.code | (o1.code << 8) | (o2.code << 16) | (o3.code << 24);
+    } else {
+        for (int xx = x; xx < cols; xx++) store1(xx, pixel(xx));     // the ragged end of a row
+    }
+}
+
+// rtdd_simulate_parallax and rtdd_simulate_parallax_layered (arguments checked by effects_api.cpp): the keys emptied, scattered,
+// resolved.  A layered call without a plate, a depthOut and a coverage IS rtdd_simulate_parallax: the same launches.
 int launch_parallax(rtdd_ctx *ctx, const Effect &e) {
     const Parallax &v = e.parallax;
+    const Layers &l = e.layers;
+    const bool layered = e.kind == Effect::kParallaxLayered && (l.plate || l.depthOut || l.coverage);
     // The keys live in the context's table buffer.  rows * cols < 2^30 (check_effect), so the buffer stays below 8 GiB and every key
     // index fits the kernels' size_t arithmetic: what can fail is the allocation.
     const size_t npx = (size_t)e.rows * e.cols;
@@ -133,13 +279,32 @@ int launch_parallax(rtdd_ctx *ctx, const Effect &e) {
     ctx->sat_rows = ctx->sat_cols = 0;                               // whatever table lay here is gone: the next table-path defocus zeroes its padding again
     u64 *keys = (u64 *)ctx->sat;
     RTDD_HIP(ctx, hipMemsetAsync(keys, 0xFF, npx * sizeof(u64), ctx->stream));
-    const float *zp = pixel_ptr(e.depth, e.depthPitch, v.zeroX, v.zeroY);     // the pixel form of z0
-    const dim3 g((e.cols + 63) / 64, (e.rows + 3) / 4);
-    hipLaunchKernelGGL(k_parallax_scatter, g, dim3(256), 0, ctx->stream, e.depth, e.depthPitch, keys, e.rows, e.cols, v, zp);
-    RTDD_LAUNCH_CHECK(ctx, "k_parallax_scatter");
+    const float *zp = pixel_ptr(e.depth, e.depthPitch, v.zeroX, v.zeroY);     // the pixel form of z0: the FRONT map's
+    const dim3 g((e.cols + 63) / 64, (e.rows + 3) / 4), g4((e.cols + 255) / 256, g.y);
+    if (layered && l.plate) {
+        hipLaunchKernelGGL(k_parallax_scatter_layered, g, dim3(256), 0, ctx->stream, e.depth, e.depthPitch, l.plateDepth, l.plateDepthPitch, keys,
+                           e.rows, e.cols, v, zp);
+        RTDD_LAUNCH_CHECK(ctx, "k_parallax_scatter_layered");
+    } else {
+        hipLaunchKernelGGL(k_parallax_scatter, g, dim3(256), 0, ctx->stream, e.depth, e.depthPitch, keys, e.rows, e.cols, v, zp);
+        RTDD_LAUNCH_CHECK(ctx, "k_parallax_scatter");
+    }
+    if (layered) {
+        const bool vec = rows_aligned(e.artistic, e.artisticPitch) && (!l.depthOut || rows_aligned(l.depthOut, l.depthOutPitch, 16)) &&
+                         (!l.coverage || rows_aligned(l.coverage, l.coveragePitch));
+        if (vec)
+            hipLaunchKernelGGL(k_parallax_resolve_layered<true>, g4, dim3(256), 0, ctx->stream, e.original, e.originalPitch, e.depth, e.depthPitch,
+                               l.plate, l.platePitch, keys, e.artistic, e.artisticPitch, l.depthOut, l.depthOutPitch, l.coverage, l.coveragePitch,
+                               e.rows, e.cols, v);
+        else hipLaunchKernelGGL(k_parallax_resolve_layered<false>, g, dim3(256), 0, ctx->stream, e.original, e.originalPitch, e.depth, e.depthPitch,
+                                l.plate, l.platePitch, keys, e.artistic, e.artisticPitch, l.depthOut, l.depthOutPitch, l.coverage, l.coveragePitch,
+                                e.rows, e.cols, v);
+        RTDD_LAUNCH_CHECK(ctx, "k_parallax_resolve_layered");
+        return RTDD_OK;
+    }
     if (rows_aligned(e.artistic, e.artisticPitch))
-        hipLaunchKernelGGL(k_parallax_resolve<true>, dim3((e.cols + 255) / 256, g.y), dim3(256), 0, ctx->stream, e.original, e.originalPitch, keys,
-                           e.artistic, e.artisticPitch, e.rows, e.cols, v);
+        hipLaunchKernelGGL(k_parallax_resolve<true>, g4, dim3(256), 0, ctx->stream, e.original, e.originalPitch, keys, e.artistic, e.artisticPitch,
+                           e.rows, e.cols, v);
     else hipLaunchKernelGGL(k_parallax_resolve<false>, g, dim3(256), 0, ctx->stream, e.original, e.originalPitch, keys, e.artistic, e.artisticPitch,
                             e.rows, e.cols, v);
     RTDD_LAUNCH_CHECK(ctx, "k_parallax_resolve");

@@ -101,8 +101,8 @@ struct LiveTargets {
 // One depth effect, arguments checked: what to render, on which images, with which parameters.  Built by the rtdd_simulate_* entry
 // points (effects_api.cpp) and by a live frame (live_effect), launched by launch_effect, and logged by value (PendingOp) to be launched again.
 struct Effect {
-    enum : int { kRefocus = RTDD_EFFECT_HAZE + 1, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow, kParallax, kAmbientOcclusion, kLighting, kBokeh, kComposite, kRemove, kLift };   // the extensions, after the public kinds
-    int kind = RTDD_EFFECT_NONE;                    // RTDD_EFFECT_DEFOCUS / _DESATURATION / _HAZE, kRefocus, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow, kParallax, kAmbientOcclusion, kLighting, kBokeh, kComposite, kRemove, kLift
+    enum : int { kRefocus = RTDD_EFFECT_HAZE + 1, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow, kParallax, kAmbientOcclusion, kLighting, kBokeh, kComposite, kRemove, kLift, kParallaxLayered };   // the extensions, after the public kinds
+    int kind = RTDD_EFFECT_NONE;                    // RTDD_EFFECT_DEFOCUS / _DESATURATION / _HAZE, kRefocus, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow, kParallax, kAmbientOcclusion, kLighting, kBokeh, kComposite, kRemove, kLift, kParallaxLayered
     const uint8_t *original = nullptr; size_t originalPitch = 0;
     const float *depth = nullptr; size_t depthPitch = 0;
     uint8_t *artistic = nullptr; size_t artisticPitch = 0;
@@ -137,6 +137,14 @@ struct Effect {
         float dolly = 0.0f, zeroDepth = 0.0f;
         float cx = 0.0f, cy = 0.0f;                 // (float)(cols - 1) * 0.5f, (float)(rows - 1) * 0.5f
     } parallax = {};
+    // the two-layer parallax view (kParallaxLayered, include/rtdd.h rtdd_simulate_parallax_layered): `parallax` as above, and the back
+    // layer and the two extra outputs, by value; each null when the call had none.  All of them null: rtdd_simulate_parallax's launches
+    struct ParallaxLayers {
+        const uint8_t *plate = nullptr; size_t platePitch = 0;
+        const float *plateDepth = nullptr; size_t plateDepthPitch = 0;
+        float *depthOut = nullptr; size_t depthOutPitch = 0;
+        uint8_t *coverage = nullptr; size_t coveragePitch = 0;
+    } layers = {};
     // ambient occlusion (kAmbientOcclusion): rtdd_ambient_occlusion as the entry point checked it (include/rtdd.h
     // rtdd_simulate_ambient_occlusion), by value -- a replay needs no rtdd_ambient_occlusion.  lit: the call had a light, prepared in
     // `light` as relight's (light.relief == relief bit for bit); the tables inv_j[k] depend on k alone and are the launcher's.
@@ -452,7 +460,7 @@ int launch_lens_blur(rtdd_ctx *ctx, const Effect &e);
 int launch_relight(rtdd_ctx *ctx, const Effect &e);
 // ---- relight_shadow.hip: Effect::kRelightShadow (called by launch_effect) --------------------------
 int launch_relight_shadow(rtdd_ctx *ctx, const Effect &e);
-// ---- parallax.hip: Effect::kParallax (called by launch_effect) -------------------------------------
+// ---- parallax.hip: Effect::kParallax and Effect::kParallaxLayered (called by launch_effect) ---------
 int launch_parallax(rtdd_ctx *ctx, const Effect &e);
 // ---- ambient_occlusion.hip: Effect::kAmbientOcclusion (called by launch_effect) --------------------
 int launch_ambient_occlusion(rtdd_ctx *ctx, const Effect &e);
