@@ -24,8 +24,6 @@
 
 namespace rtdd {
 
-typedef Effect::Occlusion Occlusion;
-
 enum : int { kAoOutShade = 0, kAoOutMap = 1, kAoOutDirectional = 2, kAoOutPoint = 3 };     // the first two are rtdd_ao_mode's
 
 // RMAX: the largest radius the LDS array has a halo for; NW: waves per workgroup; DIRS: 4 or 8; OUT: what is written.
@@ -39,51 +37,14 @@ __global__ __launch_bounds__(64 * NW) void k_ambient_occlusion(const uint8_t *__
     const int r = A.radius;                                          // <= RMAX (launch_ambient_occlusion)
     const int wave = wave_id(), lane = threadIdx.x & 63;
     const int x0 = blockIdx.x * kAoW, y0 = blockIdx.y * kAoH;
-
-    // staging: rows y0 - r .. y0 + 15 + r, columns x0 - r .. x0 + 63 + r; a wave a row at a time, its lanes consecutive words
-    const int rw = kAoW + 2 * r, rh = kAoH + 2 * r;
-    for (int ry = wave; ry < rh; ry += NW) {
-        const int gy = y0 - r + ry;
-        const bool row_inside = (unsigned)gy < (unsigned)rows;       // (wave-uniform)
-        const float *drow = (const float *)((const char *)depth + (size_t)(row_inside ? gy : 0) * dp);
-        float *hrow = Hs + (RMAX - r + ry) * P + (RMAX - r);
-        for (int rx = lane; rx < rw; rx += 64) {
-            const int gx = x0 - r + rx;
-            float h = -INFINITY;
-            if (row_inside && (unsigned)gx < (unsigned)cols) h = A.relief * (255.0f - clamp_depth(drow[gx]));
-            hrow[rx] = h;
-        }
-    }
+    ao_stage<RMAX, NW>(Hs, depth, dp, rows, cols, x0, y0, r, A.relief, wave, lane);
     __syncthreads();                                                 // the one barrier: every wave reaches it
 
-    constexpr int ux[8] = {1, 1, 0, -1, -1, -1, 0, 1}, uy[8] = {0, 1, 1, 1, 0, -1, -1, -1};
-    float Lz = 0.0f;
-    if (OUT == kAoOutPoint) {
-        const float dA = anchor_px ? clamp_depth(*anchor_px) : L.anchorDepth;
-        Lz = (L.relief * (255.0f - dA)) + L.z;
-    }
+    const float Lz = OUT == kAoOutPoint ? point_light_height(L, anchor_px) : 0.0f;
     for (int ty = wave; ty < kAoH; ty += NW) {
         const int x = x0 + lane, y = y0 + ty;
         const float *own = Hs + (RMAX + ty) * P + RMAX + lane;
-        const float h = *own;                                        // H(x, y); minus infinity beyond the image (such a lane stores nothing)
-        float tmax[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll 4
-        for (int k = 1; k <= r; k++) {
-            const float ia = T.axis[k - 1], id = T.diag[k - 1];      // (wave-uniform)
-#pragma unroll
-            for (int j = 0; j < 8; j += 8 / DIRS) {
-                const float rise = (own[k * (uy[j] * P + ux[j])] - h) - A.bias;
-                tmax[j] = fmaxf(tmax[j], rise * ((j & 1) ? id : ia));
-            }
-        }
-        float s = 0.0f;
-#pragma unroll
-        for (int j = 0; j < 8; j += 8 / DIRS) {
-            const float occ = tmax[j] / sqrtf(1.0f + (tmax[j] * tmax[j]));
-            s = j == 0 ? occ : s + occ;
-        }
-        const float mean = s * (1.0f / (float)DIRS);
-        const float ao = 1.0f - (A.strength * mean);
+        const float ao = ao_factor<RMAX, DIRS>(own, *own, A, T, r);  // H(x, y) is minus infinity beyond the image (such a lane stores nothing)
         if (x >= cols || y >= rows) continue;                        // (behind the barrier; no cross-lane operation below)
         uint8_t *a = art + (size_t)y * ap + 3 * (size_t)x;
         if (OUT == kAoOutMap) {
@@ -96,15 +57,12 @@ __global__ __launch_bounds__(64 * NW) void k_ambient_occlusion(const uint8_t *__
             for (int c = 0; c < 3; c++) a[c] = (uint8_t)(int)((float)o[c] * ao);
             continue;
         }
-        // under a light: k_relight's shade from the map itself (replicated border), the ambient term occluded
-        const float *drow = (const float *)((const char *)depth + (size_t)y * dp);
-        const float *urow = (const float *)((const char *)depth + (size_t)max(y - 1, 0) * dp);
-        const float *lrow = (const float *)((const char *)depth + (size_t)min(y + 1, rows - 1) * dp);
-        const float shade = relight_shade<OUT == kAoOutPoint>(L, Lz, clamp_depth(drow[x]), clamp_depth(drow[max(x - 1, 0)]),
-                                                              clamp_depth(drow[min(x + 1, cols - 1)]), clamp_depth(urow[x]), clamp_depth(lrow[x]), x, y);
+        // under a light: k_relight's shade from the map itself, the ambient term occluded
+        float dc;
+        const float shade = shade_at<OUT == kAoOutPoint>(L, Lz, depth, dp, rows, cols, x, y, dc);
         const float amb = L.ambient * ao;
 #pragma unroll
-        for (int c = 0; c < 3; c++) a[c] = (uint8_t)relight_u8_ambient(L, c, amb, shade, o[c]);
+        for (int c = 0; c < 3; c++) a[c] = (uint8_t)relight_u8(L, c, amb, shade, o[c]);
     }
 }
 
@@ -128,15 +86,12 @@ static void launch_class(rtdd_ctx *ctx, const Effect &e, const Occlusion &A, con
 int launch_ambient_occlusion(rtdd_ctx *ctx, const Effect &e) {
     static const AoTables T = ao_tables();
     Occlusion A = e.occlusion;
-    if (A.strength == 0.0f || A.relief == 0.0f) A.radius = 0;
+    if (occlusion_cannot_show(A)) A.radius = 0;
     if (A.radius < 0 || A.radius > kAoMaxRadius) return fail(ctx, RTDD_ERR_INVALID, "ambient occlusion: radius outside [0, 64]");
     const bool point = A.lit && e.light.kind == RTDD_LIGHT_POINT;
     const int out = A.lit ? (point ? kAoOutPoint : kAoOutDirectional) : (A.mode == RTDD_AO_MAP ? kAoOutMap : kAoOutShade);
     const float *anchor_px = point ? pixel_ptr(e.depth, e.depthPitch, e.light.anchorX, e.light.anchorY) : nullptr;
-    if (A.radius <= 8) launch_class<8, 4>(ctx, e, A, T, out, anchor_px);
-    else if (A.radius <= 16) launch_class<16, 4>(ctx, e, A, T, out, anchor_px);
-    else if (A.radius <= 32) launch_class<32, 8>(ctx, e, A, T, out, anchor_px);
-    else launch_class<64, 16>(ctx, e, A, T, out, anchor_px);
+    ao_radius_class(A.radius, [&](auto c) { launch_class<decltype(c)::RMAX, decltype(c)::NW>(ctx, e, A, T, out, anchor_px); });
     RTDD_LAUNCH_CHECK(ctx, "k_ambient_occlusion");
     return RTDD_OK;
 }

@@ -30,7 +30,6 @@
 // Measured (profiles/r16_bokeh.txt): 1.2 - 1.8 T samples/s, 0.37 ms at 1080p with the default aperture.
 #include "rtdd_internal.hpp"
 #include "effect_common.hpp"
-#include "relight_common.hpp"
 
 namespace rtdd {
 
@@ -96,8 +95,7 @@ __global__ __launch_bounds__(64 * NW) void k_bokeh(const uint8_t *__restrict__ o
                 const int k = (int)((double)(Kf * fabsf(t)) / 255.0);             // 0 .. K: |t| <= 255
                 const int s = t < 0.0f ? -k : k;
                 kmax = max(kmax, k);
-                const uint8_t *o = orow + 3 * (size_t)gx;
-                word = (uint32_t)o[0] | ((uint32_t)o[1] << 8) | ((uint32_t)o[2] << 16) | ((uint32_t)(s & 255) << 24);
+                word = load_bgr(orow + 3 * (size_t)gx) | ((uint32_t)(s & 255) << 24);
             }
             wrow[rx] = word;
         }
@@ -142,10 +140,7 @@ __global__ __launch_bounds__(64 * NW) void k_bokeh(const uint8_t *__restrict__ o
             }
             if (x < cols) res = (uint32_t)(Sb / W) | ((uint32_t)(Sg / W) << 8) | ((uint32_t)(Sr / W) << 16);      // W >= wt[kp] > 0: p reaches itself
         }
-        if (x < cols) {
-            uint8_t *a = art + (size_t)y * ap + 3 * (size_t)x;
-            a[0] = (uint8_t)res; a[1] = (uint8_t)(res >> 8); a[2] = (uint8_t)(res >> 16);
-        }
+        if (x < cols) store_bgr(art + (size_t)y * ap + 3 * (size_t)x, res);
     }
 }
 

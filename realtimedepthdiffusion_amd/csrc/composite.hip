@@ -106,7 +106,7 @@ __device__ __forceinline__ uint32_t layer_pixel(const Composite &k, const LayerR
         z = L.depth0 + ((L.depth1 - L.depth0) * ((float)(int)n / (float)(int)dd));
     }
     // 4. the visibility
-    const float diff = fminf(fmaxf(d, 0.0f), 255.0f) - z;           // (a NaN depth is 0)
+    const float diff = clamp_depth(d) - z;
     uint32_t v;
     if (L.feather == 0.0f) v = diff >= 0.0f ? 256u : 0u;
     else v = (uint32_t)(int)(fminf(fmaxf((diff / L.feather) + 0.5f, 0.0f), 1.0f) * 256.0f);
@@ -141,12 +141,10 @@ __global__ __launch_bounds__(256) void k_composite_layer(const uint8_t *__restri
     if (strip_hits) r = layer_row<FILTER>(k, y);
     // one pixel from and to memory: the one-pixel-per-lane path and the ragged end of a vectorised row
     auto pixel = [&](int x) {
-        const uint8_t *q = orow + 3 * (size_t)x;
-        uint32_t o = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16);
+        uint32_t o = load_bgr(orow + 3 * (size_t)x);
         float z = drow[x];
         if (r.covered) o = layer_pixel<FILTER>(k, r, aligned, x, o, z, z);
-        uint8_t *t = arow + 3 * (size_t)x;
-        t[0] = (uint8_t)o; t[1] = (uint8_t)(o >> 8); t[2] = (uint8_t)(o >> 16);
+        store_bgr(arow + 3 * (size_t)x, o);
         if (DOUT) zrow[x] = z;
     };
     if (!VEC) {

@@ -1,13 +1,35 @@
-// effect_common.hpp -- what the depth-effect translation units (effect_kernels.hip, lens_blur.hip, relight.hip, relight_shadow.hip, parallax.hip, ambient_occlusion.hip, lighting.hip, bokeh.hip, composite.hip, remove.hip) share.  Device: the
-// packed 3 x 21-bit pixel sums of the defocus tables, the 64-bit DPP scans, the quotients, the focus read, the workgroup -> tile decode,
-// the tile geometry.  Host: the pixel form, row alignment, the launch grids of the two tile kernels and the two table lookups, the
-// table buffer.
+// effect_common.hpp -- what the depth-effect translation units (effect_kernels.hip, lens_blur.hip, relight.hip, relight_shadow.hip,
+// parallax.hip, ambient_occlusion.hip, lighting.hip, bokeh.hip, composite.hip, remove.hip) and relight_common.hpp share.
+// Device: the clamped depth, the loads and stores of a BGR pixel packed b | g << 8 | r << 16, the packed 3 x 21-bit pixel sums of the
+// defocus tables, the 64-bit DPP scans, the quotients, the focus read, the workgroup -> tile decode, the tile geometry.  Host: the pixel
+// form, row alignment, the launch grids of the two tile kernels and the two table lookups, the table buffer.
 // Included inside no namespace; everything here is in namespace rtdd.
 #pragma once
 
 #include "rtdd_internal.hpp"
 
 namespace rtdd {
+
+// ---- the clamped depth, and a BGR pixel as b | g << 8 | r << 16 ----
+__device__ __forceinline__ float clamp_depth(float d) { return fminf(fmaxf(d, 0.0f), 255.0f); }     // a NaN depth is 0 (stereo's clamp)
+
+__device__ __forceinline__ uint32_t load_bgr(const uint8_t *px) { return (uint32_t)px[0] | ((uint32_t)px[1] << 8) | ((uint32_t)px[2] << 16); }
+__device__ __forceinline__ void store_bgr(uint8_t *px, uint32_t v) { px[0] = (uint8_t)v; px[1] = (uint8_t)(v >> 8); px[2] = (uint8_t)(v >> 16); }
+// four pixels (each < 2^24) as the three dwords at px, the first of the four (4-byte aligned)
+__device__ __forceinline__ void store_bgr4(uint8_t *px, uint32_t o0, uint32_t o1, uint32_t o2, uint32_t o3) {
+    uint32_t *a3 = (uint32_t *)px;
+    a3[0] = o0 | (o1 << 24);
+    a3[1] = (o1 >> 8) | (o2 << 16);
+    a3[2] = (o2 >> 16) | (o3 << 8);
+}
+// a wave's 64 pixels `res` of columns x0 .. x0 + 63 of the row `arow` (4-byte aligned, all 64 inside the image) as dwords: the three
+// dwords of a quad of pixels stored by its first three lanes after one quad permute
+__device__ __forceinline__ void store_bgr_quads(uint8_t *arow, int x0, int lane, uint32_t res) {
+    const int j = lane & 3;
+    const uint32_t nxt = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)res, 0xF9, 0xF, 0xF, true);   // quad_perm:[1,2,3,3]
+    const uint32_t out = (res >> (8 * j)) | (nxt << ((24 - 8 * j) & 31));
+    if (j < 3) ((uint32_t *)(arow + 3 * (size_t)x0))[3 * (lane >> 2) + j] = out;
+}
 
 // ---- packed sums and scans (the summed-area table of effect_kernels.hip explains the packing) ----
 typedef unsigned long long u64;

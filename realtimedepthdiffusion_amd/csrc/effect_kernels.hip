@@ -134,14 +134,10 @@ constexpr int kStMaxD = 256, kStW = 1024, kStMaxE = kStW + 2 * (kStMaxD + 1), kS
 constexpr uint32_t kStEmpty = 0xFFFFFFFFu;
 
 __device__ __forceinline__ int stereo_shift(float d, float z0, float D) {
-    const float dc = fminf(fmaxf(d, 0.0f), 255.0f);                 // a NaN depth is 0
-    return (int)rintf((D * (dc - z0)) / 255.0f);                    // (-ffp-contract=off, IEEE divide: three roundings)
+    return (int)rintf((D * (clamp_depth(d) - z0)) / 255.0f);                    // (-ffp-contract=off, IEEE divide: three roundings)
 }
 // pixel x of an interleaved BGR row as b | g << 8 | r << 16
-__device__ __forceinline__ uint32_t bgr_at(const uint8_t *row, int x) {
-    const uint8_t *p = row + 3 * (size_t)x;
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
-}
+__device__ __forceinline__ uint32_t bgr_at(const uint8_t *row, int x) { return load_bgr(row + 3 * (size_t)x); }
 
 // VEC: 4 targets per thread with dword accesses (needs 4-byte aligned rows of the original and the artistic image).  zp: the depth
 // map's zero-parallax pixel (the pixel form, read here when the kernel runs), else z0 is the value `zval`.
@@ -156,7 +152,7 @@ __global__ __launch_bounds__(256) void k_stereo(const uint8_t *__restrict__ orig
     const int y = blockIdx.y, t0 = blockIdx.x * kStW, t1 = min(cols, t0 + kStW);
     const int aD = D < 0 ? -D : D, sg = D < 0 ? -1 : 1, H = aD + 1;
     const int e0 = max(0, t0 - H), e1 = min(cols, t1 + H), nE = e1 - e0;
-    const float z0 = zp ? fminf(fmaxf(*zp, 0.0f), 255.0f) : zval;
+    const float z0 = zp ? clamp_depth(*zp) : zval;
     const float Df = (float)D;
     const float *drow = (const float *)((const char *)depth + (size_t)y * dp);
     const uint8_t *orow = orig + (size_t)y * op;
@@ -239,15 +235,9 @@ __global__ __launch_bounds__(256) void k_stereo(const uint8_t *__restrict__ orig
         out[i] = v;
     }
     if (whole) {
-        uint32_t *a3 = (uint32_t *)(arow + 3 * (size_t)tb);
-        a3[0] = out[0] | (out[1] << 24);
-        a3[1] = (out[1] >> 8) | (out[2] << 16);
-        a3[2] = (out[2] >> 16) | (out[3] << 8);
+        store_bgr4(arow + 3 * (size_t)tb, out[0], out[1], out[2], out[3]);
     } else {
-        for (int i = 0; i < 4 && tb + i < t1; i++) {
-            uint8_t *p = arow + 3 * (size_t)(tb + i);
-            p[0] = (uint8_t)out[i]; p[1] = (uint8_t)(out[i] >> 8); p[2] = (uint8_t)(out[i] >> 16);
-        }
+        for (int i = 0; i < 4 && tb + i < t1; i++) store_bgr(arow + 3 * (size_t)(tb + i), out[i]);
     }
 }
 
@@ -445,7 +435,7 @@ __global__ __launch_bounds__(256) void k_defocus(const uint8_t *__restrict__ ori
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)Tpad, 0, (int)((uint32_t)(trows + 1) * (uint32_t)tpitch * 8u), 0x00020000);
     const uint32_t pitch8 = (uint32_t)tpitch * 8u;
     const bool whole = VEC && x0 + 64 <= cols;                      // wave-uniform: the output as dwords
-    const int x = x0 + lane, xc = min(x, cols - 1), j = lane & 3;
+    const int x = x0 + lane, xc = min(x, cols - 1);
     float d[kLk2Rows];
 #pragma unroll
     for (int i = 0; i < kLk2Rows; i++) d[i] = ((const float *)((const char *)depth + (size_t)min(yw + i, rows - 1) * dp))[xc];
@@ -549,21 +539,12 @@ __global__ __launch_bounds__(256) void k_defocus(const uint8_t *__restrict__ ori
             }
         }
         if (__builtin_expect(__builtin_amdgcn_ballot_w64(cnt[i] == 0u) != 0, 0)) {   // count == 0 (src/GPUDepthEffect.cu:62-66): the pixel itself
-            if (cnt[i] == 0u) {
-                const uint8_t *o = orig + (size_t)yc * op + 3 * (size_t)xc;
-                res = o[0] | (o[1] << 8) | (o[2] << 16);
-            }
+            if (cnt[i] == 0u) res = load_bgr(orig + (size_t)yc * op + 3 * (size_t)xc);
         }
         if (y < row1) {                                             // wave-uniform (row1 <= rows: this launch's last output row + 1)
             uint8_t *arow = art + (size_t)y * ap;
-            if (whole) {
-                const uint32_t nxt = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)res, 0xF9, 0xF, 0xF, true);   // quad_perm:[1,2,3,3]
-                const uint32_t out = (res >> (8 * j)) | (nxt << ((24 - 8 * j) & 31));
-                if (j < 3) ((uint32_t *)(arow + 3 * (size_t)x0))[3 * (lane >> 2) + j] = out;
-            } else if (x < cols) {
-                uint8_t *a = arow + 3 * (size_t)x;
-                a[0] = (uint8_t)res; a[1] = (uint8_t)(res >> 8); a[2] = (uint8_t)(res >> 16);
-            }
+            if (whole) store_bgr_quads(arow, x0, lane, res);
+            else if (x < cols) store_bgr(arow + 3 * (size_t)x, res);
         }     // wave-uniform (row1 <= rows: this launch's last output row + 1)
     }
 }
@@ -643,8 +624,7 @@ __global__ __launch_bounds__(256, 2) void k_defocus_tile(const uint8_t *__restri
             const uint32_t prv = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)L, 0x90, 0xF, 0xF, true);   // quad_perm:[0,0,1,2]
             opx[i] = __builtin_amdgcn_alignbit(L, prv, (32 - 8 * j) & 31) & 0xFFFFFFu;
         } else {
-            const uint8_t *o = orow + 3 * (size_t)xc;
-            opx[i] = o[0] | (o[1] << 8) | (o[2] << 16);
+            opx[i] = load_bgr(orow + 3 * (size_t)xc);
         }
     }
 
@@ -743,14 +723,8 @@ __global__ __launch_bounds__(256, 2) void k_defocus_tile(const uint8_t *__restri
         }
         if (y < rows) {                                             // wave-uniform
             uint8_t *arow = art + (size_t)y * ap;
-            if (whole) {
-                const uint32_t nxt = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)res, 0xF9, 0xF, 0xF, true);   // quad_perm:[1,2,3,3]
-                const uint32_t out = (res >> (8 * j)) | (nxt << ((24 - 8 * j) & 31));
-                if (j < 3) ((uint32_t *)(arow + 3 * (size_t)tx0))[3 * (lane >> 2) + j] = out;
-            } else if (x < cols) {
-                uint8_t *a = arow + 3 * (size_t)x;
-                a[0] = (uint8_t)res; a[1] = (uint8_t)(res >> 8); a[2] = (uint8_t)(res >> 16);
-            }
+            if (whole) store_bgr_quads(arow, tx0, lane, res);
+            else if (x < cols) store_bgr(arow + 3 * (size_t)x, res);
         }    // wave-uniform
     }
 }

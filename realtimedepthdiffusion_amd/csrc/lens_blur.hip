@@ -49,19 +49,12 @@ __device__ __forceinline__ uint32_t disc_quot(u64 X, uint32_t sb, uint32_t sg, u
 }
 
 // a wave's 64 results b | g << 8 | r << 16 of row y, columns x0 .. x0 + 63, to the image.  whole (wave-uniform: 4-byte aligned rows and
-// all 64 columns inside the image): `art` moves as dwords, the three dwords of a quad of pixels stored by its first three lanes after
-// one quad permute; else bytes, column by column
+// all 64 columns inside the image): `art` moves as dwords (store_bgr_quads); else bytes, column by column
 __device__ __forceinline__ void store_row(uint8_t *__restrict__ art, size_t ap, int y, int x0, int lane, int cols, bool whole, uint32_t res) {
     uint8_t *arow = art + (size_t)y * ap;
-    const int j = lane & 3, x = x0 + lane;
-    if (whole) {
-        const uint32_t nxt = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)res, 0xF9, 0xF, 0xF, true);   // quad_perm:[1,2,3,3]
-        const uint32_t out = (res >> (8 * j)) | (nxt << ((24 - 8 * j) & 31));
-        if (j < 3) ((uint32_t *)(arow + 3 * (size_t)x0))[3 * (lane >> 2) + j] = out;
-    } else if (x < cols) {
-        uint8_t *a = arow + 3 * (size_t)x;
-        a[0] = (uint8_t)res; a[1] = (uint8_t)(res >> 8); a[2] = (uint8_t)(res >> 16);
-    }
+    const int x = x0 + lane;
+    if (whole) store_bgr_quads(arow, x0, lane, res);
+    else if (x < cols) store_bgr(arow + 3 * (size_t)x, res);
 }
 
 // ---- the row-prefix table in global memory ---------------------------------------------------------------------------------------

@@ -23,11 +23,6 @@
 
 namespace rtdd {
 
-typedef Effect::Shadow Shadow;
-typedef Effect::Occlusion Occlusion;
-
-constexpr int kLtGroup = 4;          // steps of the march per group of loads (k_relight_shadow's)
-
 template <int RMAX, int NW, int DIRS, bool POINT>
 __global__ __launch_bounds__(64 * NW) void k_lighting(const uint8_t *__restrict__ orig, size_t op, const float *__restrict__ depth, size_t dp,
                                                       uint8_t *__restrict__ art, size_t ap, int rows, int cols, Light L, Shadow S, Occlusion A,
@@ -38,116 +33,29 @@ __global__ __launch_bounds__(64 * NW) void k_lighting(const uint8_t *__restrict_
     const int r = A.radius;                                          // 1 .. RMAX (launch_lighting)
     const int wave = wave_id(), lane = threadIdx.x & 63;
     const int x0 = blockIdx.x * kAoW, y0 = blockIdx.y * kAoH;
-
-    // staging: rows y0 - r .. y0 + 15 + r, columns x0 - r .. x0 + 63 + r; a wave a row at a time, its lanes consecutive words
-    const int rw = kAoW + 2 * r, rh = kAoH + 2 * r;
-    for (int ry = wave; ry < rh; ry += NW) {
-        const int gy = y0 - r + ry;
-        const bool row_inside = (unsigned)gy < (unsigned)rows;       // (wave-uniform)
-        const float *srow = (const float *)((const char *)depth + (size_t)(row_inside ? gy : 0) * dp);
-        float *hrow = Hs + (RMAX - r + ry) * P + (RMAX - r);
-        for (int rx = lane; rx < rw; rx += 64) {
-            const int gx = x0 - r + rx;
-            float h = -INFINITY;
-            if (row_inside && (unsigned)gx < (unsigned)cols) h = A.relief * (255.0f - clamp_depth(srow[gx]));
-            hrow[rx] = h;
-        }
-    }
+    ao_stage<RMAX, NW>(Hs, depth, dp, rows, cols, x0, y0, r, A.relief, wave, lane);
     __syncthreads();                                                 // the one barrier: every wave reaches it
 
-    constexpr int ux[8] = {1, 1, 0, -1, -1, -1, 0, 1}, uy[8] = {0, 1, 1, 1, 0, -1, -1, -1};
-    float Lz = 0.0f;
-    if (POINT) {
-        const float dA = anchor_px ? clamp_depth(*anchor_px) : L.anchorDepth;
-        Lz = (L.relief * (255.0f - dA)) + L.z;
-    }
-    const bool soft = S.softness > 0.0f;                             // (wave-uniform)
-    const float hmax = L.relief * 255.0f;
+    const float Lz = POINT ? point_light_height(L, anchor_px) : 0.0f;
     for (int ty = wave; ty < kAoH; ty += NW) {
         const int x = x0 + lane, y = y0 + ty;
         const float *own = Hs + (RMAX + ty) * P + RMAX + lane;
         const float h = *own;                                        // H(x, y); minus infinity beyond the image (such a lane stores nothing)
 
-        // the horizons: k_ambient_occlusion's march over the staged heights
-        float tmax[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll 4
-        for (int k = 1; k <= r; k++) {
-            const float ia = T.axis[k - 1], id = T.diag[k - 1];      // (wave-uniform)
-#pragma unroll
-            for (int j = 0; j < 8; j += 8 / DIRS) {
-                const float rise = (own[k * (uy[j] * P + ux[j])] - h) - A.bias;
-                tmax[j] = fmaxf(tmax[j], rise * ((j & 1) ? id : ia));
-            }
-        }
-        float s = 0.0f;
-#pragma unroll
-        for (int j = 0; j < 8; j += 8 / DIRS) {
-            const float occ = tmax[j] / sqrtf(1.0f + (tmax[j] * tmax[j]));
-            s = j == 0 ? occ : s + occ;
-        }
-        const float mean = s * (1.0f / (float)DIRS);
-        const float ao = 1.0f - (A.strength * mean);
+        const float ao = ao_factor<RMAX, DIRS>(own, h, A, T, r);     // the horizons over the staged heights
         if (x >= cols || y >= rows) continue;                        // (behind the barrier; no cross-lane operation below)
-
-        // k_relight's shade from the map itself (replicated border)
+        // The shade from the map itself, and the march towards the light: its steps bounded to those inside the IMAGE (not the staged
+        // region), its samples from global memory
+        float dc;
+        const float shade = shade_at<POINT>(L, Lz, depth, dp, rows, cols, x, y, dc);
         const float *drow = (const float *)((const char *)depth + (size_t)y * dp);
-        const float *urow = (const float *)((const char *)depth + (size_t)max(y - 1, 0) * dp);
-        const float *lrow = (const float *)((const char *)depth + (size_t)min(y + 1, rows - 1) * dp);
-        const float shade = relight_shade<POINT>(L, Lz, clamp_depth(drow[x]), clamp_depth(drow[max(x - 1, 0)]), clamp_depth(drow[min(x + 1, cols - 1)]),
-                                                 clamp_depth(urow[x]), clamp_depth(lrow[x]), x, y);
-
-        // k_relight_shadow's march.  Its direction: the record's (a directional light), or this pixel's own towards the point light
-        float sx = S.sx, sy = S.sy, rise = S.rise;
-        int n = S.maxSteps;
-        if (POINT) {
-            const float vx = L.x - (float)x, vy = L.y - (float)y, vz = Lz - h;
-            const float m = fmaxf(fabsf(vx), fabsf(vy));
-            if (m < 1.0f) { n = 0; sx = sy = rise = 0.0f; }             // the light stands over this pixel: lit
-            else { sx = vx / m; sy = vy / m; rise = vz / m; n = min(n, (int)m); }
-        }
-        // the steps that stay inside the IMAGE (not the staged region): the largest k <= n whose (px, py) is inside; monotonic in k,
-        // so the bound is exact and the march below tests none
-        const auto inside = [&](int k) {
-            const float kf = (float)k;
-            return (unsigned)(x + (int)rintf(kf * sx)) < (unsigned)cols && (unsigned)(y + (int)rintf(kf * sy)) < (unsigned)rows;
-        };
-        if (n > 0 && !inside(n)) {
-            int lo = 0;                                                  // inside(lo), !inside(n)
-            while (n - lo > 1) {
-                const int mid = (lo + n) >> 1;
-                if (inside(mid)) lo = mid; else n = mid;
-            }
-            n = lo;
-        }
-        // a group that reaches past n repeats step n, which a maximum does not see
-        const float h0 = h + S.bias;
-        const char *ownd = (const char *)(drow + x);
-        float q = 0.0f;
-        for (int k0 = 1; k0 <= n; k0 += kLtGroup) {
-            float dv[kLtGroup];
-#pragma unroll
-            for (int j = 0; j < kLtGroup; j++) {
-                const float kf = (float)min(k0 + j, n);
-                const int dx = (int)rintf(kf * sx), dy = (int)rintf(kf * sy);
-                dv[j] = *(const float *)(ownd + ((ptrdiff_t)dy * (ptrdiff_t)dp + (ptrdiff_t)dx * 4));
-            }
-            float ray = 0.0f;
-#pragma unroll
-            for (int j = 0; j < kLtGroup; j++) {
-                const float kf = (float)min(k0 + j, n);
-                ray = h0 + (kf * rise);
-                const float occ = (L.relief * (255.0f - clamp_depth(dv[j]))) - ray;
-                if (occ > 0.0f) q = soft ? fmaxf(q, fminf(occ / (kf * S.softness), 1.0f)) : 1.0f;
-            }
-            // over: a full shadow, or the ray has risen above every height (rise >= 0: it stays there)
-            if (q == 1.0f || (rise >= 0.0f && ray > hmax)) break;
-        }
+        const float q = shadow_march<POINT, kSoftByRecord>(L, S, Lz, h, drow, dp, x, y, rows, cols);
         const float lit = shade * (1.0f - (S.strength * q));
         const float amb = L.ambient * ao;
         const uint8_t *o = orig + (size_t)y * op + 3 * (size_t)x;
         uint8_t *a = art + (size_t)y * ap + 3 * (size_t)x;
 #pragma unroll
-        for (int c = 0; c < 3; c++) a[c] = (uint8_t)relight_u8_ambient(L, c, amb, lit, o[c]);
+        for (int c = 0; c < 3; c++) a[c] = (uint8_t)relight_u8(L, c, amb, lit, o[c]);
     }
 }
 
@@ -170,14 +78,11 @@ int launch_lighting(rtdd_ctx *ctx, const Effect &e) {
     const Shadow &S = e.shadow;
     const Occlusion &A = e.occlusion;
     const bool point = L.kind == RTDD_LIGHT_POINT;
-    if (A.radius == 0 || A.strength == 0.0f || A.relief == 0.0f) return launch_relight_shadow(ctx, e);
-    if (S.maxSteps == 0 || S.strength == 0.0f || (!point && S.sx == 0.0f && S.sy == 0.0f)) return launch_ambient_occlusion(ctx, e);
+    if (occlusion_cannot_show(A)) return launch_relight_shadow(ctx, e);
+    if (shadow_cannot_show(L, S)) return launch_ambient_occlusion(ctx, e);
     if (A.radius < 0 || A.radius > kAoMaxRadius) return fail(ctx, RTDD_ERR_INVALID, "lighting: radius outside [0, 64]");
     const float *anchor_px = point ? pixel_ptr(e.depth, e.depthPitch, L.anchorX, L.anchorY) : nullptr;
-    if (A.radius <= 8) launch_class<8, 4>(ctx, e, T, anchor_px);
-    else if (A.radius <= 16) launch_class<16, 4>(ctx, e, T, anchor_px);
-    else if (A.radius <= 32) launch_class<32, 8>(ctx, e, T, anchor_px);
-    else launch_class<64, 16>(ctx, e, T, anchor_px);
+    ao_radius_class(A.radius, [&](auto c) { launch_class<decltype(c)::RMAX, decltype(c)::NW>(ctx, e, T, anchor_px); });
     RTDD_LAUNCH_CHECK(ctx, "k_lighting");
     return RTDD_OK;
 }

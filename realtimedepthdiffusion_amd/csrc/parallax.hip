@@ -33,7 +33,17 @@ __device__ __forceinline__ void parallax_a(const Parallax &v, int x, int y, floa
     ay = (float)v.shiftY - (v.dolly * ((float)y - v.cy));
 }
 // d' with -0 folded into +0 (fmaxf may return either zero): the key's high word is then a non-negative integer
-__device__ __forceinline__ float parallax_depth(float d) { return fminf(fmaxf(d, 0.0f), 255.0f) + 0.0f; }
+__device__ __forceinline__ float parallax_depth(float d) { return clamp_depth(d) + 0.0f; }
+
+// one source: depth d' = dc, shift field (ax, ay), low word `low`
+__device__ __forceinline__ void parallax_put(u64 *__restrict__ keys, int rows, int cols, int x, int y, float ax, float ay, float dc, float z0,
+                                             uint32_t low) {
+    const float dz = dc - z0;
+    const int tx = x + (int)rintf((ax * dz) / 255.0f), ty = y + (int)rintf((ay * dz) / 255.0f);
+    if (tx < 0 || tx >= cols || ty < 0 || ty >= rows) return;       // the only stores of the kernel: inside the rows * cols keys
+    const u64 key = ((u64)__float_as_uint(dc) << 32) | low;
+    (void)__hip_atomic_fetch_min(&keys[(size_t)ty * cols + tx], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 
 __global__ __launch_bounds__(256) void k_parallax_scatter(const float *__restrict__ depth, size_t dp, u64 *__restrict__ keys, int rows, int cols,
                                                           Parallax v, const float *__restrict__ zp) {
@@ -43,32 +53,41 @@ __global__ __launch_bounds__(256) void k_parallax_scatter(const float *__restric
     if (x >= cols) return;
     const float z0 = zp ? parallax_depth(*zp) : v.zeroDepth;        // the pixel form: one uniform load per wave, when the kernel runs
     const float dc = parallax_depth(((const float *)((const char *)depth + (size_t)y * dp))[x]);
-    const float dz = dc - z0;
     float ax, ay;
     parallax_a(v, x, y, ax, ay);
-    const int tx = x + (int)rintf((ax * dz) / 255.0f), ty = y + (int)rintf((ay * dz) / 255.0f);
-    if (tx < 0 || tx >= cols || ty < 0 || ty >= rows) return;       // the only store of this kernel: inside the rows * cols keys
-    const u64 key = ((u64)__float_as_uint(dc) << 32) | (uint32_t)(y * cols + x);
-    (void)__hip_atomic_fetch_min(&keys[(size_t)ty * cols + tx], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    parallax_put(keys, rows, cols, x, y, ax, ay, dc, z0, (uint32_t)(y * cols + x));
 }
 
 // pixel `i` (= y * cols + x) of an interleaved BGR image as b | g << 8 | r << 16
 __device__ __forceinline__ uint32_t bgr_of_index(const uint8_t *__restrict__ orig, size_t op, uint32_t i, int cols) {
     const uint32_t sy = i / (uint32_t)cols, sx = i - sy * (uint32_t)cols;
-    const uint8_t *p = orig + (size_t)sy * op + 3 * (size_t)sx;
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+    return load_bgr(orig + (size_t)sy * op + 3 * (size_t)sx);
 }
 
-// The march of a hole at (x, y) with the step (stx, sty): the key of the first filled target on it, kPxEmpty when it leaves the image first.
-// One of |stx|, |sty| is 1: step k is k pixels along the major axis, so at most max(rows, cols) - 1 steps stay inside the image.
-__device__ __forceinline__ u64 parallax_march(const u64 *__restrict__ keys, int rows, int cols, int x, int y, float stx, float sty, int sign) {
+// The march of a hole at (x, y) with the step (stx, sty): the key of the first filled target on it and where it stopped, (px, py);
+// kPxEmpty when it leaves the image first.  One of |stx|, |sty| is 1: step k is k pixels along the major axis, so at most
+// max(rows, cols) - 1 steps stay inside the image.
+__device__ __forceinline__ u64 parallax_march(const u64 *__restrict__ keys, int rows, int cols, int x, int y, float stx, float sty, int sign,
+                                              int &px, int &py) {
     for (int k = 1;; k++) {
         const float kf = (float)k;
-        const int px = x + sign * (int)rintf(kf * stx), py = y + sign * (int)rintf(kf * sty);
+        px = x + sign * (int)rintf(kf * stx); py = y + sign * (int)rintf(kf * sty);
         if (px < 0 || px >= cols || py < 0 || py >= rows) return kPxEmpty;
         const u64 key = keys[(size_t)py * cols + px];
         if (key != kPxEmpty) return key;
     }
+}
+
+// A hole at (x, y): the key of the first filled target towards the background side (+a), then towards the other one, and its position
+// (px, py); kPxEmpty where neither march meets one (or a == 0: no direction).
+__device__ __forceinline__ u64 parallax_hole(const u64 *__restrict__ keys, int rows, int cols, const Parallax &v, int x, int y, int &px, int &py) {
+    float ax, ay;
+    parallax_a(v, x, y, ax, ay);
+    const float m = fmaxf(fabsf(ax), fabsf(ay));
+    if (m == 0.0f) return kPxEmpty;
+    const float stx = ax / m, sty = ay / m;
+    const u64 key = parallax_march(keys, rows, cols, x, y, stx, sty, 1, px, py);
+    return key != kPxEmpty ? key : parallax_march(keys, rows, cols, x, y, stx, sty, -1, px, py);
 }
 
 // VEC: four targets per lane, the artistic row written as dwords (its rows 4-byte aligned); else one target per lane, written as bytes.
@@ -83,59 +102,32 @@ __global__ __launch_bounds__(256) void k_parallax_resolve(const uint8_t *__restr
     auto pixel = [&](int x) -> uint32_t {                            // view[(x, y)]
         const uint32_t self = (uint32_t)(y * cols + x);
         u64 key = keys[self];
-        if (key == kPxEmpty) {                                       // a hole: towards the background side (+a), then the other one
-            float ax, ay;
-            parallax_a(v, x, y, ax, ay);
-            const float m = fmaxf(fabsf(ax), fabsf(ay));
-            if (m != 0.0f) {
-                const float stx = ax / m, sty = ay / m;
-                key = parallax_march(keys, rows, cols, x, y, stx, sty, 1);
-                if (key == kPxEmpty) key = parallax_march(keys, rows, cols, x, y, stx, sty, -1);
-            }
-        }
+        int px, py;                                                  // (where a hole's march stopped: not needed here)
+        if (key == kPxEmpty) key = parallax_hole(keys, rows, cols, v, x, y, px, py);
         return bgr_of_index(orig, op, key == kPxEmpty ? self : (uint32_t)key, cols);
     };
     if (!VEC) {
         const int x = blockIdx.x * 64 + lane;
         if (x >= cols) return;
-        const uint32_t o = pixel(x);
-        uint8_t *p = arow + 3 * (size_t)x;
-        p[0] = (uint8_t)o; p[1] = (uint8_t)(o >> 8); p[2] = (uint8_t)(o >> 16);
+        store_bgr(arow + 3 * (size_t)x, pixel(x));
         return;
     }
     const int x = (blockIdx.x * 64 + lane) * 4;
     if (x >= cols) return;
     if (x + 3 < cols) {
         const uint32_t o0 = pixel(x), o1 = pixel(x + 1), o2 = pixel(x + 2), o3 = pixel(x + 3);
-        uint32_t *a3 = (uint32_t *)(arow + 3 * (size_t)x);
-        a3[0] = o0 | (o1 << 24);
-        a3[1] = (o1 >> 8) | (o2 << 16);
-        a3[2] = (o2 >> 16) | (o3 << 8);
+        store_bgr4(arow + 3 * (size_t)x, o0, o1, o2, o3);
     } else {
-        for (int xx = x; xx < cols; xx++) {                          // the ragged end of a row
-            const uint32_t o = pixel(xx);
-            uint8_t *p = arow + 3 * (size_t)xx;
-            p[0] = (uint8_t)o; p[1] = (uint8_t)(o >> 8); p[2] = (uint8_t)(o >> 16);
-        }
+        for (int xx = x; xx < cols; xx++) store_bgr(arow + 3 * (size_t)xx, pixel(xx));     // the ragged end of a row
     }
 }
 
 // ---- the two-layer view (rtdd_simulate_parallax_layered) ------------------------------------------------------------------------------
 // The same three passes over the same keys; bit 31 of a key's low word says that the source is a plate pixel, so that at equal d' the
-// front layer wins and the source index (< 2^30) still breaks the ties within a layer.  The two kernels above are rtdd_simulate_parallax's
-// and stay as they are; these are launched when the call has a plate, a depthOut or a coverage.
+// front layer wins and the source index (< 2^30) still breaks the ties within a layer.  The two kernels above are rtdd_simulate_parallax's;
+// these are launched when the call has a plate, a depthOut or a coverage.
 typedef Effect::ParallaxLayers Layers;
 constexpr uint32_t kPxBack = 0x80000000u;
-
-// one source: depth d' = dc, shift field (ax, ay), low word `low`
-__device__ __forceinline__ void parallax_put(u64 *__restrict__ keys, int rows, int cols, int x, int y, float ax, float ay, float dc, float z0,
-                                             uint32_t low) {
-    const float dz = dc - z0;
-    const int tx = x + (int)rintf((ax * dz) / 255.0f), ty = y + (int)rintf((ay * dz) / 255.0f);
-    if (tx < 0 || tx >= cols || ty < 0 || ty >= rows) return;       // the only stores of the kernel: inside the rows * cols keys
-    const u64 key = ((u64)__float_as_uint(dc) << 32) | low;
-    (void)__hip_atomic_fetch_min(&keys[(size_t)ty * cols + tx], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // One lane per pixel, both layers: a wave reads 256 contiguous bytes of each depth row.  A plate source whose d' equals the front's at the
 // same pixel lands on the same target with the same high word and the larger low word: it never wins, and no atomic is issued for it
@@ -155,18 +147,6 @@ __global__ __launch_bounds__(256) void k_parallax_scatter_layered(const float *_
     const uint32_t self = (uint32_t)(y * cols + x);
     parallax_put(keys, rows, cols, x, y, ax, ay, dc, z0, self);
     if (__float_as_uint(pc) != __float_as_uint(dc)) parallax_put(keys, rows, cols, x, y, ax, ay, pc, z0, self | kPxBack);
-}
-
-// parallax_march that also says where it stopped: (px, py) of the filled target whose key it returns
-__device__ __forceinline__ u64 parallax_march_to(const u64 *__restrict__ keys, int rows, int cols, int x, int y, float stx, float sty, int sign,
-                                                 int &px, int &py) {
-    for (int k = 1;; k++) {
-        const float kf = (float)k;
-        px = x + sign * (int)rintf(kf * stx); py = y + sign * (int)rintf(kf * sty);
-        if (px < 0 || px >= cols || py < 0 || py >= rows) return kPxEmpty;
-        const u64 key = keys[(size_t)py * cols + px];
-        if (key != kPxEmpty) return key;
-    }
 }
 
 // The key of the SOURCE of a filled target (x, y) whose own key is `key`: the key itself, unless the target is a crack -- back-won, m != 0,
@@ -209,16 +189,9 @@ __global__ __launch_bounds__(256) void k_parallax_resolve_layered(const uint8_t 
         uint32_t code;
         if (key == kPxEmpty) {                                       // a hole: towards the background side (+a), then the other one
             code = 4;
-            float ax, ay;
-            parallax_a(v, x, y, ax, ay);
-            const float m = fmaxf(fabsf(ax), fabsf(ay));
-            if (m != 0.0f) {
-                const float stx = ax / m, sty = ay / m;
-                int px, py;
-                key = parallax_march_to(keys, rows, cols, x, y, stx, sty, 1, px, py);
-                if (key == kPxEmpty) key = parallax_march_to(keys, rows, cols, x, y, stx, sty, -1, px, py);
-                if (key != kPxEmpty) { code = 3; key = parallax_source(keys, rows, cols, v, px, py, key); }     // the hit may be a crack
-            }
+            int px, py;
+            key = parallax_hole(keys, rows, cols, v, x, y, px, py);
+            if (key != kPxEmpty) { code = 3; key = parallax_source(keys, rows, cols, v, px, py, key); }     // the hit may be a crack
         } else {
             const u64 s = parallax_source(keys, rows, cols, v, x, y, key);
             code = !((uint32_t)key & kPxBack) ? 0 : (s != key ? 2 : 1);     // (a crack's source is front-won: never the key itself)
@@ -237,8 +210,7 @@ __global__ __launch_bounds__(256) void k_parallax_resolve_layered(const uint8_t 
         return o;
     };
     auto store1 = [&](int x, const PxOut &o) {
-        uint8_t *p = arow + 3 * (size_t)x;
-        p[0] = (uint8_t)o.bgr; p[1] = (uint8_t)(o.bgr >> 8); p[2] = (uint8_t)(o.bgr >> 16);
+        store_bgr(arow + 3 * (size_t)x, o.bgr);
         if (zrow) zrow[x] = o.d;
         if (crow) crow[x] = (uint8_t)o.code;
     };
@@ -252,10 +224,7 @@ __global__ __launch_bounds__(256) void k_parallax_resolve_layered(const uint8_t 
     if (x >= cols) return;
     if (x + 3 < cols) {
         const PxOut o0 = pixel(x), o1 = pixel(x + 1), o2 = pixel(x + 2), o3 = pixel(x + 3);
-        uint32_t *a3 = (uint32_t *)(arow + 3 * (size_t)x);
-        a3[0] = o0.bgr | (o1.bgr << 24);
-        a3[1] = (o1.bgr >> 8) | (o2.bgr << 16);
-        a3[2] = (o2.bgr >> 16) | (o3.bgr << 8);
+        store_bgr4(arow + 3 * (size_t)x, o0.bgr, o1.bgr, o2.bgr, o3.bgr);
         if (zrow) *(float4 *)(zrow + x) = make_float4(o0.d, o1.d, o2.d, o3.d);
         if (crow) *(uint32_t *)(crow + x) = o0.code | (o1.code << 8) | (o2.code << 16) | (o3.code << 24);
     } else {

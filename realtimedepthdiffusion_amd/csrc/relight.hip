@@ -12,7 +12,7 @@
 // tests/relight_ref.py and do not depend on RTDD_OPT_FP_CONTRACT.
 #include "rtdd_internal.hpp"
 #include "effect_common.hpp"
-#include "relight_common.hpp"       // clamp_depth, relight_shade, relight_u8: shared with relight_shadow.hip
+#include "relight_common.hpp"
 
 namespace rtdd {
 
@@ -29,19 +29,13 @@ __global__ __launch_bounds__(256) void k_relight(const uint8_t *__restrict__ ori
     const float *lrow = (const float *)((const char *)depth + (size_t)min(y + 1, rows - 1) * dp);
     const uint8_t *orow = orig + (size_t)y * op;
     uint8_t *arow = art + (size_t)y * ap;
-    float Lz = 0.0f;
-    if (POINT) {
-        // the anchor: one uniform load per wave (the pixel form reads the map when the kernel runs, as refocus's focus)
-        const float dA = anchor_px ? clamp_depth(*anchor_px) : L.anchorDepth;
-        Lz = (L.relief * (255.0f - dA)) + L.z;
-    }
+    const float Lz = POINT ? point_light_height(L, anchor_px) : 0.0f;
     // one pixel, every neighbour from memory: the one-pixel-per-lane path and the ragged end of a vectorised row
     auto pixel = [&](int x) {
-        const float dc = clamp_depth(drow[x]);
-        const float dl = clamp_depth(drow[max(x - 1, 0)]), dr = clamp_depth(drow[min(x + 1, cols - 1)]);
-        const float s = relight_shade<POINT>(L, Lz, dc, dl, dr, clamp_depth(urow[x]), clamp_depth(lrow[x]), x, y);
+        float dc;
+        const float s = shade_in_rows<POINT>(L, Lz, drow, urow, lrow, cols, x, y, dc);     // (the wave's rows: the vectorised path reads them too)
 #pragma unroll
-        for (int c = 0; c < 3; c++) arow[3 * (size_t)x + c] = (uint8_t)relight_u8(L, c, s, orow[3 * (size_t)x + c]);
+        for (int c = 0; c < 3; c++) arow[3 * (size_t)x + c] = (uint8_t)relight_u8(L, c, L.ambient, s, orow[3 * (size_t)x + c]);
     };
     if (!VEC) {
         const int x = blockIdx.x * 64 + lane;
@@ -75,7 +69,7 @@ __global__ __launch_bounds__(256) void k_relight(const uint8_t *__restrict__ ori
     for (int i = 0; i < 4; i++) {
         const float s = relight_shade<POINT>(L, Lz, dv[i + 1], dv[i], dv[i + 2], clamp_depth(uv[i]), clamp_depth(lv[i]), x + i, y);
 #pragma unroll
-        for (int c = 0; c < 3; c++) rb[3 * i + c] = relight_u8(L, c, s, ob[3 * i + c]);
+        for (int c = 0; c < 3; c++) rb[3 * i + c] = relight_u8(L, c, L.ambient, s, ob[3 * i + c]);
     }
     store_bytes12(arow + 3 * (size_t)x, rb);
 }

@@ -48,7 +48,7 @@ struct Div {
     __device__ __forceinline__ int quot(int idx) const { return (int)__umulhi((uint32_t)idx, inv); }
 };
 
-__device__ __forceinline__ float clamp_depth(float d) { return d > 0.0f ? fminf(d, 255.0f) : 0.0f; }       // NaN, -0, negatives: +0
+__device__ __forceinline__ float remove_depth(float d) { return d > 0.0f ? fminf(d, 255.0f) : 0.0f; }       // NaN, -0, negatives: +0
 __device__ __forceinline__ bool is_selected(uint32_t m, int select) { return select == 0 ? m != 0u : m == (uint32_t)select; }
 
 // ---- classes of level 0 over an S x S window at (oy, ox), which may reach outside the image: 0 bystander or outside, 1 source, 2 hole.
@@ -63,7 +63,7 @@ __device__ void classify(const Images &im, int rows, int cols, int oy, int ox, u
             uint8_t f = 0;
             if (y >= 0 && y < rows && x >= 0 && x < cols) {
                 const bool sel = is_selected(im.mask[(size_t)y * im.mp + x], im.select);
-                const float d = clamp_depth(*(const float *)((const char *)im.depth + (size_t)y * im.dp + 4 * (size_t)x));
+                const float d = remove_depth(*(const float *)((const char *)im.depth + (size_t)y * im.dp + 4 * (size_t)x));
                 f = sel ? 2 : (d >= im.minDepth ? 1 : 0);
             }
             flags[idx] = f;
@@ -95,7 +95,7 @@ __device__ void classify(const Images &im, int rows, int cols, int oy, int ox, u
         if (y >= 0 && y < rows && x >= 0 && x < cols) {
             uint8_t near = 0;
             for (int s = 0; s <= 2 * g; s++) near |= rowd[(i + s) * S + j];
-            const float d = clamp_depth(*(const float *)((const char *)im.depth + (size_t)y * im.dp + 4 * (size_t)x));
+            const float d = remove_depth(*(const float *)((const char *)im.depth + (size_t)y * im.dp + 4 * (size_t)x));
             const bool eligible = d >= im.minDepth;
             f = (selb[(i + g) * W + j + g] || (eligible && near)) ? 2 : (eligible ? 1 : 0);
         }
@@ -110,9 +110,8 @@ struct FromImages {
     __device__ __forceinline__ bool operator()(int y, int x, uint32_t &c, float &d) const {
         const int i = y - r.oy, j = x - r.ox;
         if (y >= rows || x >= cols || (unsigned)i >= (unsigned)r.n || (unsigned)j >= (unsigned)r.n || flags[i * r.n + j] != 1) return false;
-        const uint8_t *q = im.orig + (size_t)y * im.op + 3 * (size_t)x;
-        c = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16);
-        d = clamp_depth(*(const float *)((const char *)im.depth + (size_t)y * im.dp + 4 * (size_t)x));
+        c = load_bgr(im.orig + (size_t)y * im.op + 3 * (size_t)x);
+        d = remove_depth(*(const float *)((const char *)im.depth + (size_t)y * im.dp + 4 * (size_t)x));
         return true;
     }
 };
@@ -407,12 +406,10 @@ __global__ __launch_bounds__(kThreads) void k_remove_push(Images im, Stored src,
         if (c) { px = c & 0xffffffu; z = d; }
     };
     auto pixel = [&](int y, int x) {
-        const uint8_t *q = im.orig + (size_t)y * im.op + 3 * (size_t)x;
-        uint32_t px = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16);
+        uint32_t px = load_bgr(im.orig + (size_t)y * im.op + 3 * (size_t)x);
         float z = *(const float *)((const char *)im.depth + (size_t)y * im.dp + 4 * (size_t)x);
         fill(y, x, px, z);
-        uint8_t *t = o.art + (size_t)y * o.ap + 3 * (size_t)x;
-        t[0] = (uint8_t)px; t[1] = (uint8_t)(px >> 8); t[2] = (uint8_t)(px >> 16);
+        store_bgr(o.art + (size_t)y * o.ap + 3 * (size_t)x, px);
         if (o.z) *(float *)((char *)o.z + (size_t)y * o.zp + 4 * (size_t)x) = z;
     };
     if (!VEC) {
@@ -542,8 +539,7 @@ __global__ __launch_bounds__(256) void k_lift_layer(const uint8_t *__restrict__ 
         const int x = k.x + u0 + i;
         t[i] = 0u;
         if (row_in && u0 + i < k.spriteCols && x >= 0 && x < cols && is_selected(mask[(size_t)y * mp + x], k.select)) {
-            const uint8_t *q = orig + (size_t)y * op + 3 * (size_t)x;
-            t[i] = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | 0xff000000u;
+            t[i] = load_bgr(orig + (size_t)y * op + 3 * (size_t)x) | 0xff000000u;
         }
     }
     uint8_t *srow = k.sprite + (size_t)v * k.spritePitch + 4 * (size_t)u0;

@@ -157,7 +157,8 @@ def test_identities_on_the_device(ctx):
         ctx.synchronize()
         return down(art)
 
-    for L in _lights(rows, cols, 1.5):
+    lights = _lights(rows, cols, 1.5)
+    for L in lights:
         Lc = rt.Light(**L)
         plain = other(ctx.simulate_relight, Lc)
         shadowed = other(ctx.simulate_relight_shadowed, Lc, rt.Shadow(**S))
@@ -168,6 +169,10 @@ def test_identities_on_the_device(ctx):
             assert_same_image(_run(ctx, o, d, rows, cols, L, S, A0), shadowed, ("relight_shadowed", L, A0))
             for S0 in (dict(S, maxSteps=0), dict(S, strength=0.0)):
                 assert_same_image(_run(ctx, o, d, rows, cols, L, S0, A0), plain, ("relight", L, S0, A0))
+        if L is lights[0] or L is lights[2]:                             # the kernel itself, not the launcher's shortcuts: k_lighting runs ...
+            # ... with a bias no horizon can clear (ao == 1 exactly), and with one no step can occlude under (q == 0)
+            assert_same_image(_run(ctx, o, d, rows, cols, L, S, dict(A, bias=65536.0)), shadowed, ("k_lighting, ao == 1", L))
+            assert_same_image(_run(ctx, o, d, rows, cols, L, dict(S, bias=65536.0), A), under, ("k_lighting, q == 0", L))
         full = _run(ctx, o, d, rows, cols, L, S, A)                      # ... and with both terms it is none of the three
         assert not np.array_equal(full, under) and not np.array_equal(full, shadowed) and not np.array_equal(full, plain)
     up_ = light(DIRECTIONAL, 0, 0, 3, relief=1.5, ambient=0.75, diffuse=1.5)    # the light straight above (m == 0) casts no shadow
