@@ -38,7 +38,10 @@
 //                                 ids, smooth the edges inside one region, or both; the regions are painted into the pyramid's region pair
 //                                 before the estimate by --region-fill "x,y;x,y;...:id" (a lasso, rtdd_fill_polygon under the --fill-rule in
 //                                 force) and --region-wand "x,y,tol:id" (a click, rtdd_fill_similar on the photograph under the
-//                                 --wand-connect in force), the fills first, each kind in command-line order
+//                                 --wand-connect in force), the fills first, each kind in command-line order; AFTER the estimate by
+//                                 --region-surface "x,y,step[,below,above]:id" (a click on the estimated depth map, rtdd_fill_surface;
+//                                 behind --surface-global every pixel in the band), which also fills the level-0 code plane again, so
+//                                 that --remove-region / --move-region / --plate-region take the region; not with --live or --batch
 //     --layer sprite --layer-alpha alpha --layer-at x,y [--layer-scale S] [--layer-filter nearest|bilinear] [--layer-depth z | --layer-plane
 //                                 x0,y0,z0,x1,y1,z1] [--layer-feather f] [--layer-opacity o] = extension: a sprite inserted into the scene at
 //                                 a depth (rtdd_composite_layer), after the estimate and before --effect, which then runs on the composite and
@@ -258,6 +261,8 @@ struct Job {
     int region_flags = 0;
     std::vector<Lasso> region_fills;
     std::vector<Wand> region_wands;
+    // --region-surface "x,y,step[,below,above]:id" (after --surface-global: every pixel in the band): rtdd_fill_surface after the estimate
+    std::vector<rtdd_surface_wand> region_surfaces;
     bool edges_color = false;     // --edges color: the estimates read their edge weights from the BGR image (rtdd_pyramid_set_guide); default gray: the reference's
     // --layer sprite --layer-alpha alpha --layer-at x,y [--layer-scale S] [--layer-filter nearest|bilinear] [--layer-depth z | --layer-plane
     // x0,y0,z0,x1,y1,z1] [--layer-feather f] [--layer-opacity o]: rtdd_composite_layer after the estimate; --effect then runs on the composite
@@ -377,6 +382,33 @@ static int region_calls(rtdd_ctx *ctx, const Job &job, const void *orig, size_t 
         std::printf("region wand %d,%d tolerance %d: region %d, %d pixels\n", q.w.x, q.w.y, q.w.tolerance, q.w.label0, info.pixels);
     }
     return RTDD_OK;
+}
+
+// --region-surface: the clicks on the estimate's own depth map (level 0) into the region pair, one rtdd_fill_surface call each (each
+// synchronises); then the level-0 code plane, which --remove-region / --move-region / --plate-region read, is filled again from the pair
+static int region_surface_calls(rtdd_ctx *ctx, const Job &job, const void *depth, size_t depth_pitch, int rows, int cols) {
+    if (job.region_surfaces.empty()) return RTDD_OK;
+    void *pe, *pm, *pc; size_t pie, pim, pic;
+    CK(rtdd_pyramid_image(ctx, RTDD_IMG_REGION_EDITED, 0, &pe, &pie, nullptr, nullptr));
+    CK(rtdd_pyramid_image(ctx, RTDD_IMG_REGION_MASK, 0, &pm, &pim, nullptr, nullptr));
+    CK(rtdd_pyramid_image(ctx, RTDD_IMG_REGION_CODE, 0, &pc, &pic, nullptr, nullptr));
+    for (const rtdd_surface_wand &w : job.region_surfaces) {
+        rtdd_wand_info info;
+        CK(rtdd_fill_surface(ctx, &w, (uint8_t *)pe, pie, (uint8_t *)pm, pim, nullptr, 0, (const float *)depth, depth_pitch, rows, cols, &info));
+        std::printf("region surface %d,%d step %g band %g,%g%s: region %d, %d pixels, x %d..%d, y %d..%d\n", w.x, w.y, w.step, w.below, w.above,
+                    (w.flags & RTDD_SURFACE_GLOBAL) ? " global" : "", w.label0, info.pixels, info.x0, info.x1, info.y0, info.y1);
+    }
+    return rtdd_region_codes(ctx, (const uint8_t *)pe, pie, (const uint8_t *)pm, pim, rows, cols, 0, (uint8_t *)pc, pic);
+}
+
+// "x,y,step:id" or "x,y,step,below,above:id"
+static bool parse_surface(const char *arg, int flags, rtdd_surface_wand *w) {
+    *w = rtdd_surface_wand{0, 0, 0.0f, 255.0f, 255.0f, flags, 0, 0, 0, 0, 0, 0};
+    int n = 0;
+    if (std::sscanf(arg, "%d,%d,%f,%f,%f:%d%n", &w->x, &w->y, &w->step, &w->below, &w->above, &w->label0, &n) == 6 && n > 0 && arg[n] == 0) { w->label1 = w->label0; return true; }
+    w->below = w->above = 255.0f; n = 0;
+    if (std::sscanf(arg, "%d,%d,%f:%d%n", &w->x, &w->y, &w->step, &w->label0, &n) == 4 && n > 0 && arg[n] == 0) { w->label1 = w->label0; return true; }
+    return false;
 }
 
 // rtdd_paint_ramp_strokes (with label0 == label1: rtdd_paint_strokes) restated for the host's own image pair (--live: the host owns the pair every frame uploads; include/rtdd.h has the
@@ -716,6 +748,8 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
             if (n == 0 && job.refine == "auto") std::printf("refine auto: %d cycles + %d sweeps, residual %g\n", si.cycles, si.iterations, si.residual);
             else if (n == 0) std::printf("refine %s: %d %s, residual %g\n", job.refine.c_str(), si.iterations, job.refine == "mg" ? "cycles" : "sweeps", si.residual);
         }
+        // --region-surface: the regions clicked on the estimate's depth map, before anything below reads the level-0 code plane
+        CK(region_surface_calls(ctx, job, p_depth, pi_depth, rows, cols));
         // --layer: the sprite is inserted after the estimate; the effect below then reads the composite and the composite's depth map
         // (desaturation's gray image stays the photograph's)
         // --remove-region / --move-region come first: the region's code plane (level 0, written by the estimate) is the mask, the id selects.
@@ -843,7 +877,7 @@ int main(int argc, const char *argv[]) {
                                  "                    [relight's light flags] [--shadows N (256)] [--shadow-bias B] [--shadow-softness S] [--shadow-strength T] [--ao R (16)] [--ao-directions 4|8] [--ao-bias B] [--ao-strength T] (lighting: shade, cast shadows and occlusion in one call)\n"
                                  "                    [--layer sprite.(ppm|png|jpg) [--layer-alpha alpha.(pgm|png)] --layer-at x,y [--layer-scale S (256)] [--layer-filter nearest|bilinear] [--layer-depth z (128) | --layer-plane x0,y0,z0,x1,y1,z1] [--layer-feather f] [--layer-opacity o (255)]]   (a sprite inserted at a depth after the estimate, rtdd_composite_layer: --effect then runs on the composite and its depth map; without --effect ArtisticEffect is the composite)\n"
                                  "                    [--remove-region id [--remove-grow N (0..8)] [--remove-behind D] | --move-region id:dx,dy[:depth] [--remove-grow N] [--remove-behind D]]   (with --regions: the painted region taken out of the scene, rtdd_remove_object, or moved, rtdd_lift_layer + rtdd_remove_object + rtdd_composite_layer; before --layer and --effect, which run on the result and its depth map)\n"
-                                 "                    [--paint x,y,label,radius]... [--live N [--paint-at frame:x,y,label,radius]...] [--devices D --batch B [--sequential] [--write-all]] [--png] [--cold] [--edges gray|color] [--regions cut|smooth|both [--region-fill x,y;...:id]... [--region-wand x,y,tol:id]...]\n"
+                                 "                    [--paint x,y,label,radius]... [--live N [--paint-at frame:x,y,label,radius]...] [--devices D --batch B [--sequential] [--write-all]] [--png] [--cold] [--edges gray|color] [--regions cut|smooth|both [--region-fill x,y;...:id]... [--region-wand x,y,tol:id]... [--surface-global] [--region-surface x,y,step[,below,above]:id]...]   (--region-surface: a click on the ESTIMATED depth map, rtdd_fill_surface into the region pair after the estimate and before --remove-region / --move-region / --plate-region; --surface-global: the clicks behind it take every pixel in their band; not with --live or --batch)\n"
                                  "                    [--stroke x0,y0,x1,y1,label,radius[,round]]... [--erase x0,y0,x1,y1,radius[,round]]...   (segments, in command-line order, one rtdd_paint_strokes call after --paint)\n"
                                  "                    [--ramp x0,y0,x1,y1,label0,label1,radius[,round]]...   (a depth ramp: label0 at x0,y0 to label1 at x1,y1; in order with --stroke / --erase, all of them one rtdd_paint_ramp_strokes call)\n"
                                  "                    [--fill \"x,y;x,y;...:label\" | \"x,y;...:label0,label1,ax0,ay0,ax1,ay1\"]... [--fill-erase \"x,y;x,y;...\"]... [--fill-rule nonzero|evenodd]   (a lasso filled with a label, a ramp along the axis, or erased: one rtdd_fill_polygon call each, after the strokes, in command-line order)\n"
@@ -860,6 +894,7 @@ int main(int argc, const char *argv[]) {
     bool png = false, write_all = false, shadow_opt = false, ao_opt = false, ao_radius_opt = false, layer_at = false, layer_opt = false, remove_opt = false;
     std::string layer_path, layer_alpha_path;
     int devices = 1, batch = 1, live = 0;
+    int surface_flags = 0;                  // --surface-global: the --region-surface clicks behind it take every pixel in their band
     for (int i = 1; i < argc; i++) {
         auto next = [&]() -> const char * { return i + 1 < argc ? argv[++i] : ""; };
         if (!std::strcmp(argv[i], "-i")) in = next();
@@ -881,6 +916,12 @@ int main(int argc, const char *argv[]) {
             Job::Lasso l;
             if (!parse_fill(next(), false, job.fill_rule, &l) || l.fill.label0 != l.fill.label1) { std::printf("--region-fill wants x,y;x,y;...:id\n"); return 1; }
             job.region_fills.push_back(l);
+        }
+        else if (!std::strcmp(argv[i], "--surface-global")) surface_flags = RTDD_SURFACE_GLOBAL;
+        else if (!std::strcmp(argv[i], "--region-surface")) {
+            rtdd_surface_wand w;
+            if (!parse_surface(next(), surface_flags, &w) || w.label0 < 1 || w.label0 > 255) { std::printf("--region-surface wants x,y,step:id or x,y,step,below,above:id, the id 1..255\n"); return 1; }
+            job.region_surfaces.push_back(w);
         }
         else if (!std::strcmp(argv[i], "--region-wand")) {
             Job::Wand q; q.frame = -1;
@@ -1021,6 +1062,8 @@ int main(int argc, const char *argv[]) {
     const bool lighting = job.effect == "lighting";                           // takes --shadows and --ao together, each with its parameters
     if (job.shadows && job.effect != "relight" && !lighting) { std::printf("--shadows needs --effect relight\n"); return 1; }
     if (job.region_flags == 0 && (!job.region_fills.empty() || !job.region_wands.empty())) { std::printf("--region-fill and --region-wand need --regions cut|smooth|both\n"); return 1; }
+    if (!job.region_surfaces.empty() && job.region_flags == 0) { std::printf("--region-surface needs --regions cut|smooth|both\n"); return 1; }
+    if (!job.region_surfaces.empty() && (live > 0 || batch > 1)) { std::printf("--region-surface is not supported with --live or --batch\n"); return 1; }
     if (shadow_opt && !job.shadows && !lighting) { std::printf("--shadow-bias, --shadow-softness and --shadow-strength need --shadows N\n"); return 1; }
     // ambient occlusion is --effect ao, or --ao R under --effect relight (without cast shadows: one call renders one or the other); its
     // parameters belong to one of the two: a stray one is refused, not dropped

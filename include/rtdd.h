@@ -524,6 +524,61 @@ int rtdd_fill_similar(rtdd_ctx *ctx, const rtdd_wand *wand,
                       const uint8_t *original, size_t originalPitch,   /* always needed: it is what "similar" reads */
                       int rows, int cols, rtdd_wand_info *info /* may be NULL */);
 
+/* Fill the surface under the clicked pixel -- the wand that follows the depth map, not colour (extension; no reference behaviour; found by
+ * symbol like rtdd_fill_similar, no version bump; the next bump of RTDD_VERSION should cover rtdd_fill_surface too): one click on an object
+ * selects "the thing at this distance, bounded by depth discontinuities", or, globally, "everything in this band of depths", and the
+ * selection gets rtdd_fill_polygon's label, ramp or erasure.  Every comparison below is on f32 values, each operation rounded once.
+ * Clamped depth: d'(p) = d > 0 ? fminf(d, 255) : +0 for the depth d at p -- rtdd_remove_object's rule: a NaN, -0 and every negative depth
+ *   are +0, +inf is 255, a denormal stays what it is.
+ * Seed depth: ds = d'(x, y), READ ON THE DEVICE when the call runs.
+ * Band: lo = ds - below, hi = ds + above (one f32 operation each).
+ * Admissible: p is admissible iff lo <= d'(p) && d'(p) <= hi.  The seed always is; 255 on a side is no limit on that side.
+ * Link: two 4-neighbours p, q inside the image are linked iff both are admissible and fabsf(d'(p) - d'(q)) <= step (one f32 subtraction;
+ *   symmetric, since a - b == -(b - a) exactly).
+ * Covered: the pixels joined to the seed by a path of links; at least the seed.  The image border ends a path: nothing wraps.  With
+ *   RTDD_SURFACE_GLOBAL every admissible pixel is covered, linked or not; `step` is validated and otherwise ignored.
+ * Connectivity: 4-neighbours only.  A link is a property of a pair of pixels, kept as one bit plane per direction; diagonal links would
+ *   take two more link planes and are not built.
+ * The covered set is a connected component of an undirected graph: the bytes do not depend on how the device schedules the search.
+ * Label and writes: exactly rtdd_fill_polygon's -- the constant label, the ramp along the axis (ax0, ay0) - (ax1, ay1), or the erasure;
+ *   uncovered pixels are not written.  `depth` is never written.
+ * What the tool reads: `depth` only -- neither the colours nor the labels already in the pair.  Where it fails:
+ *   - a surface that touches another at the same depth, such as an object's foot on a floor, is joined to it; the band (below, above) is
+ *     what stops the floor from running away;
+ *   - a selection is only as good as the depth map.  A 48 x 40 ellipse of 513 pixels in three parts of gray 30 / 120 / 230 on gray 170
+ *     (noise +-2), one stroke of label 60 across the parts, one stamp of 200 on the background, solved for 300 or 1000 sweeps: the depth
+ *     is 60.0 on every object pixel and at least 132.4 outside, and step 1, 2, 4 or 8 (or the band 30 with step 255, or the global band)
+ *     selects exactly the 513 pixels -- no tolerance of rtdd_fill_similar does (it misses 301 or takes 1407 of the background).  The same
+ *     ellipse filled with 2 x 2 tiles of random grays 60..140 blocks the single-level solve inside the object: the depth there ranges
+ *     from 60 to 128 and the rule covers 84 to 150 of the 513 pixels (steps 2..8, 300 to 3000 sweeps), none of the background.
+ *     RTDD_REGION_SMOOTH exists for that case.
+ * Not built: 8-connectivity; a rule that reads colour AND depth; re-estimating after the click (the caller's to queue).
+ * Refused (RTDD_ERR_INVALID) before any launch, the images untouched: a null wand; a null depth; a depth pitch smaller than 4 * cols or
+ *   not a multiple of 4; a depth pointer not 4-byte aligned; a seed outside the image (rows == 0 or cols == 0 included: no seed lies inside
+ *   an empty image); step, below or above non-finite or outside [0, 255]; flag bits other than RTDD_SURFACE_GLOBAL; an axis coordinate
+ *   outside [-32768, 32767]; a label outside [-1, 255]; exactly ONE label being RTDD_STROKE_ERASE; the null, pitch and size rules of
+ *   rtdd_fill_polygon -- `original` may be NULL unless erasing.  A retired level-0 pointer of live mode: RTDD_ERR_STATE.
+ * On the pyramid's own level-0 RTDD_IMG_SCRIBBLE / RTDD_IMG_EDITED pair the call notes the change itself, and asks for
+ * rtdd_pyramid_annotation_rebuild when it erases, exactly as rtdd_fill_similar.  The region pair (RTDD_IMG_REGION_EDITED / _MASK) is a
+ * legal target, and the intended one for rtdd_remove_object, rtdd_lift_layer and a background plate.
+ * THE CALL SYNCHRONISES, like rtdd_fill_similar and for the same reason.  Logged solves and estimates are confirmed (or healed) first:
+ * `depth` is usually the output of an estimate that is still in the log, and it is final before it is read.  info->passes is a
+ * diagnostic, NOT deterministic, and 0 with RTDD_SURFACE_GLOBAL; everything else is deterministic. */
+enum rtdd_surface_flags { RTDD_SURFACE_GLOBAL = 1 };   /* every admissible pixel, connected or not */
+typedef struct rtdd_surface_wand {
+    int   x, y;                 /* the clicked pixel; inside the image */
+    float step;                 /* finite, [0, 255]: two neighbours are joined when their depths differ by at most this */
+    float below, above;         /* finite, [0, 255]: only depths in [ds - below, ds + above] take part; 255 = no limit on that side */
+    int   flags;                /* enum rtdd_surface_flags */
+    int   ax0, ay0, ax1, ay1;   /* the ramp's axis, as rtdd_fill */
+    int   label0, label1;       /* both 0..255, or both RTDD_STROKE_ERASE */
+} rtdd_surface_wand;
+int rtdd_fill_surface(rtdd_ctx *ctx, const rtdd_surface_wand *wand,
+                      uint8_t *edited, size_t editedPitch, uint8_t *scribble, size_t scribblePitch,
+                      const uint8_t *original, size_t originalPitch,   /* may be NULL unless erasing */
+                      const float *depth, size_t depthPitch,           /* DEVICE f32, read only */
+                      int rows, int cols, rtdd_wand_info *info /* may be NULL */);
+
 /* ---- depth effects (include/GPUDepthEffect.h:4-9) ------------------------------------------ */
 
 /* GPUSimulateDefocus -- src/GPUDepthEffect.cu:29-72,105-113 (exact, via an integer summed-area table). */

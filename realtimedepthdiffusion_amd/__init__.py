@@ -52,7 +52,7 @@ C_ABI_SYMBOLS = [
     "rtdd_live_submit", "rtdd_live_wait", "rtdd_live_pending", "rtdd_host_alloc", "rtdd_host_free",
     "rtdd_pyramid_create_batch", "rtdd_pyramid_select", "rtdd_pyramid_batch", "rtdd_estimate_depth_batch", "rtdd_pyramid_level_info", "rtdd_live_submit_ex",
     "rtdd_simulate_refocus", "rtdd_simulate_haze_ex", "rtdd_simulate_stereo", "rtdd_simulate_lens_blur",
-    "rtdd_paint_strokes", "rtdd_pyramid_annotation_rebuild", "rtdd_paint_ramp_strokes", "rtdd_ramp_polyline", "rtdd_fill_polygon", "rtdd_fill_similar",
+    "rtdd_paint_strokes", "rtdd_pyramid_annotation_rebuild", "rtdd_paint_ramp_strokes", "rtdd_ramp_polyline", "rtdd_fill_polygon", "rtdd_fill_similar", "rtdd_fill_surface",
     "rtdd_simulate_relight", "rtdd_simulate_relight_shadowed", "rtdd_simulate_parallax", "rtdd_simulate_ambient_occlusion",
     "rtdd_simulate_lighting", "rtdd_simulate_bokeh", "rtdd_composite_layer", "rtdd_remove_object", "rtdd_lift_layer",
     "rtdd_simulate_parallax_layered",
@@ -74,6 +74,7 @@ BRUSH_SQUARE, BRUSH_ROUND = 0, 1              # rtdd_stroke.brush
 STROKE_ERASE = -1                             # rtdd_stroke.label: remove the annotation
 FILL_NONZERO, FILL_EVEN_ODD = 0, 1            # rtdd_fill.rule
 WAND_CONNECT_8, WAND_GLOBAL = 1, 2            # rtdd_wand.flags
+SURFACE_GLOBAL = 1                            # rtdd_surface_wand.flags
 WAND_ROUND = 8                                # grow passes rtdd_fill_similar queues between two synchronisations (csrc/fill_similar.hip: kWandRound)
 # rtdd_remove_object's grouping (csrc/rtdd_internal.hpp: kRemoveTile, kRemoveGroup, kRemoveApex, kRemoveApexChain): a workgroup owns a
 # REMOVE_TILE-square tile of a level and takes REMOVE_GROUP levels in LDS; one workgroup takes a level of at most REMOVE_APEX samples
@@ -151,6 +152,13 @@ class Wand(C.Structure):
     selection is erased)."""
     _fields_ = [("x", C.c_int), ("y", C.c_int), ("tolerance", C.c_int), ("flags", C.c_int), ("ax0", C.c_int), ("ay0", C.c_int), ("ax1", C.c_int),
                 ("ay1", C.c_int), ("label0", C.c_int), ("label1", C.c_int)]
+
+
+class SurfaceWand(C.Structure):
+    """rtdd_surface_wand: the clicked pixel (x, y), the largest depth step between two joined neighbours, the band [ds - below, ds + above]
+    around the clicked depth ds (255: no limit on that side), SURFACE_* flags, and rtdd_fill's axis and two labels."""
+    _fields_ = [("x", C.c_int), ("y", C.c_int), ("step", C.c_float), ("below", C.c_float), ("above", C.c_float), ("flags", C.c_int),
+                ("ax0", C.c_int), ("ay0", C.c_int), ("ax1", C.c_int), ("ay1", C.c_int), ("label0", C.c_int), ("label1", C.c_int)]
 
 
 class WandInfo(C.Structure):
@@ -517,6 +525,16 @@ class Context:
         w = wand if isinstance(wand, Wand) else Wand(*wand)
         info = WandInfo()
         self._check(lib().rtdd_fill_similar(self._h, C.byref(w), *_paint_images(edited, scribble, original), C.c_int(rows), C.c_int(cols), C.byref(info)))
+        return info
+
+    def fill_surface(self, wand, edited, scribble, rows, cols, depth, original=None):
+        """rtdd_fill_surface: everything joined to the clicked pixel through neighbours whose depths in `depth` (f32) differ by at most the
+        step, inside the band around the clicked depth, is filled by `wand` (a SurfaceWand or a 12-tuple x, y, step, below, above, flags,
+        ax0, ay0, ax1, ay1, label0, label1); `original` is needed when it erases.  SYNCHRONISES; returns the WandInfo."""
+        w = wand if isinstance(wand, SurfaceWand) else SurfaceWand(*wand)
+        info = WandInfo()
+        d, dp = _img(depth)
+        self._check(lib().rtdd_fill_surface(self._h, C.byref(w), *_paint_images(edited, scribble, original), d, dp, C.c_int(rows), C.c_int(cols), C.byref(info)))
         return info
 
     # ---- include/GPUDepthEffect.h

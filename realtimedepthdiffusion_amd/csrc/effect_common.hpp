@@ -12,6 +12,8 @@ namespace rtdd {
 
 // ---- the clamped depth, and a BGR pixel as b | g << 8 | r << 16 ----
 __device__ __forceinline__ float clamp_depth(float d) { return fminf(fmaxf(d, 0.0f), 255.0f); }     // a NaN depth is 0 (stereo's clamp)
+// rtdd_remove_object's and rtdd_fill_surface's d': NaN, -0 and every negative are +0, so equal bits are equal depths
+__device__ __forceinline__ float remove_depth(float d) { return d > 0.0f ? fminf(d, 255.0f) : 0.0f; }
 
 __device__ __forceinline__ uint32_t load_bgr(const uint8_t *px) { return (uint32_t)px[0] | ((uint32_t)px[1] << 8) | ((uint32_t)px[2] << 16); }
 __device__ __forceinline__ void store_bgr(uint8_t *px, uint32_t v) { px[0] = (uint8_t)v; px[1] = (uint8_t)(v >> 8); px[2] = (uint8_t)(v >> 16); }

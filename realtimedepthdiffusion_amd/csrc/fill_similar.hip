@@ -16,7 +16,22 @@
 // ordering.  Reach only ever grows and every bit set is a true member of the component, so whatever mixture of old and new the read
 // returns is a SUBSET of the truth: it can delay a bit by a pass, never set a wrong one.  A pass in which no wave changed a word proves
 // the fixpoint: nobody wrote, so every halo read in it was of the final state, and every block was at its own fixpoint against it.
+//
+// rtdd_fill_surface (extension, include/rtdd.h): the same wand on the depth map -- two neighbours are joined when their clamped depths
+// differ by at most `step` and both lie in the band around the clicked depth.  A link is a property of a PAIR of pixels, so no
+// eligibility plane can state it: three planes, laid out as above,
+//   H          bit x: the link (x, y) - (x + 1, y); 0 for the last column and at or beyond `cols`
+//   V          bit x: the link (x, y) - (x, y + 1); 0 for the last row and at or beyond `cols`
+//   reach      the seed's bit, grown to the fixpoint (RTDD_SURFACE_GLOBAL: the admissible plane itself; H and V are not built)
+//   k_surface_links   the planes: a wave owns one word's columns over kSurfaceStrip rows and keeps the row below in registers for the
+//                     next round, so a row is loaded once (and once more per strip); the right neighbour comes by a lane shift
+//   k_surface_grow    k_wand_grow's pass with the link fill in place of the eligibility fill: the same block, halo, loop and counter,
+//                     and the same argument for the racing reads (reach only grows, every bit set is true; H and V are constant)
+//   k_wand_paint      itself, with the same result words and host fold; the host's loop over rounds of passes is the wand's
+//                     (wand_grow_rounds)
+// 4-connectivity only: a diagonal link would be two more planes (one per diagonal) and two more loads per row of the grow pass.
 #include <climits>
+#include <cmath>
 
 #include "effect_common.hpp"
 #include "paint_common.hpp"
@@ -123,6 +138,91 @@ __global__ __launch_bounds__(256) void k_wand_grow(const u64 *__restrict__ elig,
     if (__ballot(changed) != 0 && lane == 0) atomicAdd(mine, 1);
 }
 
+// ---- rtdd_fill_surface ----
+constexpr int kSurfaceStrip = 8;          // consecutive rows of one word's columns that a wave of k_surface_links walks
+
+// One wave per word and strip: rows (4 blockIdx.y + wave) kSurfaceStrip ..., columns 64 blockIdx.x + lane.  The seed lies inside the image
+// and depthPitch is a multiple of 4 (checked by the caller).  `cur` is d' of the lane's pixel; the row below, loaded for the V links,
+// is the next round's `cur`.  Nothing is read outside the image: the right neighbour only where x + 1 < cols, the row below only where
+// y + 1 < rows.
+__global__ __launch_bounds__(256) void k_surface_links(const float *__restrict__ depth, size_t depthPitch, int rows, int cols, int W, int sx, int sy,
+                                                       float step, float below, float above, int global, u64 *__restrict__ H, u64 *__restrict__ V,
+                                                       u64 *__restrict__ reach, int *__restrict__ info) {
+    if (blockIdx.x == 0 && blockIdx.y == 0)
+        for (int i = threadIdx.x; i < kWandInfoWords; i += 256) info[i] = wand_info_init(i % kWandSlotStride);
+    const int y0 = ((int)blockIdx.y * 4 + wave_id()) * kSurfaceStrip;
+    if (y0 >= rows) return;                                          // wave-uniform: the ballots below have their whole wave
+    const int lane = threadIdx.x & 63, x = (int)blockIdx.x * 64 + lane;
+    auto at = [&](int yy, int xx) { return remove_depth(((const float *)((const char *)depth + (size_t)yy * depthPitch))[xx]); };
+    const float ds = at(sy, sx);                                     // (the same address in every lane)
+    const float lo = ds - below, hi = ds + above;
+    const bool inx = x < cols, right_in = x + 1 < cols;
+    float cur = inx ? at(y0, x) : 0.0f;
+    for (int k = 0; k < kSurfaceStrip; k++) {
+        const int y = y0 + k;
+        if (y >= rows) break;                                        // wave-uniform
+        const bool down_in = y + 1 < rows;
+        float right = __shfl_down(cur, 1);
+        if (lane == 63) right = right_in ? at(y, x + 1) : 0.0f;
+        const float down = inx && down_in ? at(y + 1, x) : 0.0f;
+        const bool a = inx && lo <= cur && cur <= hi;
+        const size_t i = (size_t)y * W + blockIdx.x;
+        if (global) {
+            const u64 aw = __ballot(a);
+            if (lane == 0) reach[i] = aw;
+        } else {
+            const u64 hw = __ballot(a && right_in && lo <= right && right <= hi && fabsf(cur - right) <= step);
+            const u64 vw = __ballot(a && down_in && lo <= down && down <= hi && fabsf(cur - down) <= step);
+            if (lane == 0) {
+                H[i] = hw; V[i] = vw;
+                reach[i] = y == sy && (int)blockIdx.x == (sx >> 6) ? 1ull << (sx & 63) : 0ull;
+            }
+        }
+        cur = down;
+    }
+}
+
+// every bit joined to a bit of r through link bits, towards higher bits: bit x of h links x to x + 1, so adding the reached link bits to
+// h carries through each run of links from its lowest reached one and lands on the pixel above the run -- which is reached; the carry
+// out of bit 63 (the link into the next word) is dropped: that word's wave picks it up through its side bit.  Towards lower bits the
+// same on the reversed words, the link x - (x + 1) then lying at the reversed index of x + 1: one further down.
+__device__ __forceinline__ u64 surface_fill_up(u64 h, u64 r) { return r | ((h + (r & h)) ^ h); }
+__device__ __forceinline__ u64 surface_fill_row(u64 h, u64 r) {
+    r = surface_fill_up(h, r);
+    return __brevll(surface_fill_up(__brevll(h) >> 1, __brevll(r)));
+}
+
+// One pass: k_wand_grow's, under 4-connectivity, with links.  A reached neighbour counts where the link to it is set: the word to the
+// left under bit 63 of ITS H word, the word to the right under bit 63 of the own one, the row above under its V word, the row below
+// under the own one.
+__global__ __launch_bounds__(256) void k_surface_grow(const u64 *__restrict__ H, const u64 *__restrict__ V, u64 *reach, int rows, int W, const int *prev, int *mine) {
+    if (prev && *prev == 0) return;
+    const int bx = (int)blockIdx.x * 4 + wave_id();
+    if (bx >= W) return;                                             // wave-uniform
+    const int lane = threadIdx.x & 63, y0 = (int)blockIdx.y * kWandBlock, y = y0 + lane;
+    const bool in = y < rows;
+    auto word = [&](const u64 *plane, int yy, int xx) -> u64 { return yy >= 0 && yy < rows && xx >= 0 && xx < W ? plane[(size_t)yy * W + xx] : 0ull; };
+    const u64 h = word(H, y, bx), v = word(V, y, bx);
+    const u64 r0 = word(reach, y, bx);
+    // the halo, read once, each bit under its link: the two side bits of this row (as bits 0 and 63: where they touch), and the row
+    // above the block (in lane 0) and below it (in lane 63)
+    const u64 side = ((word(reach, y, bx - 1) & word(H, y, bx - 1)) >> 63) | ((word(reach, y, bx + 1) << 63) & h);
+    const u64 habove = lane == 0 ? word(reach, y0 - 1, bx) & word(V, y0 - 1, bx) : 0ull;
+    const u64 hbelow = lane == 63 ? word(reach, y0 + kWandBlock, bx) & v : 0ull;
+    if (__ballot((r0 | side | habove | hbelow) != 0) == 0) return;   // nothing reached in the block or around it
+    u64 r = r0;
+    for (;;) {
+        const u64 up = __shfl_up(r & v, 1), dn = __shfl_down(r, 1) & v;
+        const u64 next = surface_fill_row(h, r | side | (lane == 0 ? habove : up) | (lane == 63 ? hbelow : dn));
+        const bool grew = next != r;
+        r = next;
+        if (__ballot(grew) == 0) break;
+    }
+    const bool changed = r != r0;
+    if (changed && in) reach[(size_t)y * W + bx] = r;                // (r != 0 only where a link ends: inside the image)
+    if (__ballot(changed) != 0 && lane == 0) atomicAdd(mine, 1);
+}
+
 // k_fill_polygon's tile and write (fill_polygon.hip) under the reach bit; x0 = y0 = 0: the launch covers the image
 __global__ __launch_bounds__(256) void k_wand_paint(const WandArgs C, const u64 *__restrict__ reach, uint8_t *__restrict__ edited, size_t editedPitch,
                                                     uint8_t *__restrict__ scribble, size_t scribblePitch,
@@ -169,47 +269,40 @@ __global__ __launch_bounds__(256) void k_wand_paint(const WandArgs C, const u64 
     }
 }
 
-// checked by rtdd_fill_similar (image_api.cpp): the seed inside the image, tolerance, flags, labels and axis valid, all three images given.
-// Synchronises: the number of grow passes depends on the data.
-int launch_fill_similar(rtdd_ctx *ctx, const rtdd_wand &wand, const PaintTarget &t, rtdd_wand_info *out) {
-    const int W = (t.cols + 63) / 64;
-    const size_t plane = (size_t)t.rows * W;                         // (at most 2^15 * 2^9 words)
-    if (ensure_sat(ctx, 4 * plane + kWandInfoWords + kWandRound) != RTDD_OK) {
-        (void)hipGetLastError();
-        return fail(ctx, RTDD_ERR_NOMEM, "fill_similar: the two bit planes could not be allocated");
-    }
-    ctx->sat_rows = ctx->sat_cols = 0;                               // whatever table lay here is gone: the next table-path defocus zeroes its padding again
-    u64 *elig = (u64 *)ctx->sat, *reach = elig + plane;
-    int *info = (int *)(reach + plane), *counters = info + kWandInfoWords;
-    const int global = (wand.flags & RTDD_WAND_GLOBAL) != 0, connect8 = (wand.flags & RTDD_WAND_CONNECT_8) != 0;
-    hipLaunchKernelGGL(k_wand_mask, dim3(W, (t.rows + 3) / 4), dim3(256), 0, ctx->stream, t.original, t.originalPitch, t.rows, t.cols, W, wand.x, wand.y,
-                       wand.tolerance, global, elig, reach, info);
-    RTDD_LAUNCH_CHECK(ctx, "k_wand_mask");
-    long long passes = 0;
-    if (!global) {
-        const long long limit = (long long)t.rows * t.cols + 1;      // every pass short of the fixpoint adds a pixel
-        const dim3 grid((W + 3) / 4, (t.rows + kWandBlock - 1) / kWandBlock);
-        for (bool done = false; !done;) {
-            if (passes >= limit) return fail(ctx, RTDD_ERR_STATE, "fill_similar: no fixpoint within rows * cols + 1 passes (cannot happen: every pass short of it adds a pixel)");
-            RTDD_HIP(ctx, hipMemsetAsync(counters, 0, kWandRound * sizeof(int), ctx->stream));
-            for (int p = 0; p < kWandRound; p++) {
-                hipLaunchKernelGGL(k_wand_grow, grid, dim3(256), 0, ctx->stream, elig, reach, t.rows, W, connect8, p > 0 ? counters + p - 1 : nullptr, counters + p);
-                RTDD_LAUNCH_CHECK(ctx, "k_wand_grow");
-            }
-            int host[kWandRound];
-            RTDD_HIP(ctx, hipMemcpyAsync(host, counters, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
-            RTDD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            for (int p = 0; p < kWandRound && !done; p++) { passes++; done = host[p] == 0; }
+// ---- host: what the two wands share ----
+// the u32 words of the table buffer behind `planes` bit planes: the result records and a round's counters
+static size_t wand_words(size_t plane, int planes) { return 2 * planes * plane + kWandInfoWords + kWandRound; }
+
+// Rounds of kWandRound passes, each pass launched (and its launch checked) by launch(prev, mine) with the counter of the pass before (null for the first of the
+// call) and its own, until a pass changed nothing; the counters are read back once per round.  SYNCHRONISES.
+template <class Launch>
+static int wand_grow_rounds(rtdd_ctx *ctx, const PaintTarget &t, int *counters, long long &passes, Launch launch) {
+    const long long limit = (long long)t.rows * t.cols + 1;          // every pass short of the fixpoint adds a pixel
+    for (bool done = false; !done;) {
+        if (passes >= limit) return fail(ctx, RTDD_ERR_STATE, "wand: no fixpoint within rows * cols + 1 passes (cannot happen: every pass short of it adds a pixel)");
+        RTDD_HIP(ctx, hipMemsetAsync(counters, 0, kWandRound * sizeof(int), ctx->stream));
+        for (int p = 0; p < kWandRound; p++) {
+            RTDD_TRY(launch(p > 0 ? counters + p - 1 : nullptr, counters + p));
         }
+        int host[kWandRound];
+        RTDD_HIP(ctx, hipMemcpyAsync(host, counters, sizeof(host), hipMemcpyDeviceToHost, ctx->stream));
+        RTDD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (int p = 0; p < kWandRound && !done; p++) { passes++; done = host[p] == 0; }
     }
+    return RTDD_OK;
+}
+
+// k_wand_paint under the grown plane, the result records folded on the host.  SYNCHRONISES.
+static int wand_paint(rtdd_ctx *ctx, const PaintTarget &t, int W, int ax0, int ay0, int ax1, int ay1, int label0, int label1, const u64 *reach,
+                      int *info, long long passes, rtdd_wand_info *out) {
     WandArgs C{};
     C.rows = t.rows; C.cols = t.cols; C.W = W;
-    C.label0 = wand.label0;
-    C.ax0 = wand.ax0; C.ay0 = wand.ay0; C.adx = wand.ax1 - wand.ax0; C.ady = wand.ay1 - wand.ay0;
+    C.label0 = label0;
+    C.ax0 = ax0; C.ay0 = ay0; C.adx = ax1 - ax0; C.ady = ay1 - ay0;
     C.dd = (long long)C.adx * C.adx + (long long)C.ady * C.ady;
-    C.ramp = wand.label0 >= 0 && wand.label0 != wand.label1 && C.dd != 0;
-    C.A = (long long)(2 * wand.label0 + 1) * C.dd;
-    C.B = 2 * (wand.label1 - wand.label0);
+    C.ramp = label0 >= 0 && label0 != label1 && C.dd != 0;
+    C.A = (long long)(2 * label0 + 1) * C.dd;
+    C.B = 2 * (label1 - label0);
     hipLaunchKernelGGL(k_wand_paint, dim3(W, (t.rows + kPaintTileH - 1) / kPaintTileH), dim3(256), 0, ctx->stream, C, reach, t.edited, t.editedPitch,
                        t.scribble, t.scribblePitch, t.original, t.originalPitch, info);
     RTDD_LAUNCH_CHECK(ctx, "k_wand_paint");
@@ -226,6 +319,62 @@ int launch_fill_similar(rtdd_ctx *ctx, const rtdd_wand &wand, const PaintTarget 
     }
     if (out) *out = rtdd_wand_info{r[kWandPixels], r[kWandX0], r[kWandY0], r[kWandX1], r[kWandY1], (int)std::min<long long>(passes, INT_MAX)};
     return RTDD_OK;
+}
+
+// checked by rtdd_fill_similar (image_api.cpp): the seed inside the image, tolerance, flags, labels and axis valid, all three images given.
+// Synchronises: the number of grow passes depends on the data.
+int launch_fill_similar(rtdd_ctx *ctx, const rtdd_wand &wand, const PaintTarget &t, rtdd_wand_info *out) {
+    const int W = (t.cols + 63) / 64;
+    const size_t plane = (size_t)t.rows * W;                         // (at most 2^15 * 2^9 words)
+    if (ensure_sat(ctx, wand_words(plane, 2)) != RTDD_OK) {
+        (void)hipGetLastError();
+        return fail(ctx, RTDD_ERR_NOMEM, "fill_similar: the two bit planes could not be allocated");
+    }
+    ctx->sat_rows = ctx->sat_cols = 0;                               // whatever table lay here is gone: the next table-path defocus zeroes its padding again
+    u64 *elig = (u64 *)ctx->sat, *reach = elig + plane;
+    int *info = (int *)(reach + plane), *counters = info + kWandInfoWords;
+    const int global = (wand.flags & RTDD_WAND_GLOBAL) != 0, connect8 = (wand.flags & RTDD_WAND_CONNECT_8) != 0;
+    hipLaunchKernelGGL(k_wand_mask, dim3(W, (t.rows + 3) / 4), dim3(256), 0, ctx->stream, t.original, t.originalPitch, t.rows, t.cols, W, wand.x, wand.y,
+                       wand.tolerance, global, elig, reach, info);
+    RTDD_LAUNCH_CHECK(ctx, "k_wand_mask");
+    long long passes = 0;
+    if (!global) {
+        const dim3 grid((W + 3) / 4, (t.rows + kWandBlock - 1) / kWandBlock);
+        RTDD_TRY(wand_grow_rounds(ctx, t, counters, passes, [&](const int *prev, int *mine) {
+            hipLaunchKernelGGL(k_wand_grow, grid, dim3(256), 0, ctx->stream, elig, reach, t.rows, W, connect8, prev, mine);
+            RTDD_LAUNCH_CHECK(ctx, "k_wand_grow");
+            return (int)RTDD_OK;
+        }));
+    }
+    return wand_paint(ctx, t, W, wand.ax0, wand.ay0, wand.ax1, wand.ay1, wand.label0, wand.label1, reach, info, passes, out);
+}
+
+// checked by rtdd_fill_surface (image_api.cpp): the seed inside the image; step, band, flags, labels and axis valid; the depth map given
+// and aligned.  Synchronises, as launch_fill_similar.
+int launch_fill_surface(rtdd_ctx *ctx, const rtdd_surface_wand &wand, const PaintTarget &t, const float *depth, size_t depthPitch, rtdd_wand_info *out) {
+    const int W = (t.cols + 63) / 64;
+    const size_t plane = (size_t)t.rows * W;
+    if (ensure_sat(ctx, wand_words(plane, 3)) != RTDD_OK) {
+        (void)hipGetLastError();
+        return fail(ctx, RTDD_ERR_NOMEM, "fill_surface: the three bit planes could not be allocated");
+    }
+    ctx->sat_rows = ctx->sat_cols = 0;                               // (as launch_fill_similar)
+    u64 *H = (u64 *)ctx->sat, *V = H + plane, *reach = V + plane;
+    int *info = (int *)(reach + plane), *counters = info + kWandInfoWords;
+    const int global = (wand.flags & RTDD_SURFACE_GLOBAL) != 0;
+    hipLaunchKernelGGL(k_surface_links, dim3(W, (t.rows + 4 * kSurfaceStrip - 1) / (4 * kSurfaceStrip)), dim3(256), 0, ctx->stream, depth, depthPitch,
+                       t.rows, t.cols, W, wand.x, wand.y, wand.step, wand.below, wand.above, global, H, V, reach, info);
+    RTDD_LAUNCH_CHECK(ctx, "k_surface_links");
+    long long passes = 0;
+    if (!global) {
+        const dim3 grid((W + 3) / 4, (t.rows + kWandBlock - 1) / kWandBlock);
+        RTDD_TRY(wand_grow_rounds(ctx, t, counters, passes, [&](const int *prev, int *mine) {
+            hipLaunchKernelGGL(k_surface_grow, grid, dim3(256), 0, ctx->stream, H, V, reach, t.rows, W, prev, mine);
+            RTDD_LAUNCH_CHECK(ctx, "k_surface_grow");
+            return (int)RTDD_OK;
+        }));
+    }
+    return wand_paint(ctx, t, W, wand.ax0, wand.ay0, wand.ax1, wand.ay1, wand.label0, wand.label1, reach, info, passes, out);
 }
 
 }  // namespace rtdd

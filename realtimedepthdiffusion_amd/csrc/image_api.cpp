@@ -211,6 +211,33 @@ int rtdd_fill_similar(rtdd_ctx *ctx, const rtdd_wand *wand, uint8_t *edited, siz
     return launch_fill_similar(ctx, *wand, t, info);
 }
 
+// rtdd_fill_similar's sibling on the depth map: synchronises for the same reason, and reads `original` only when it erases.
+int rtdd_fill_surface(rtdd_ctx *ctx, const rtdd_surface_wand *wand, uint8_t *edited, size_t editedPitch, uint8_t *scribble, size_t scribblePitch,
+                      const uint8_t *original, size_t originalPitch, const float *depth, size_t depthPitch, int rows, int cols,
+                      rtdd_wand_info *info) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    const PaintTarget t{edited, editedPitch, scribble, scribblePitch, original, originalPitch, rows, cols};
+    REQUIRE(ctx, wand, "null wand");
+    for (float v : {wand->step, wand->below, wand->above})
+        REQUIRE(ctx, std::isfinite(v) && v >= 0.0f && v <= 255.0f, "step, below or above not a finite value in [0, 255]");
+    REQUIRE(ctx, (wand->flags & ~RTDD_SURFACE_GLOBAL) == 0, "unknown surface wand flag");
+    for (int v : {wand->ax0, wand->ay0, wand->ax1, wand->ay1}) REQUIRE(ctx, v >= -32768 && v <= 32767, "axis coordinate outside [-32768, 32767]");
+    const char *why = nullptr;
+    REQUIRE(ctx, label_pair_ok(wand->label0, wand->label1, &why), why);
+    const bool erases = wand->label0 == RTDD_STROKE_ERASE;
+    REQUIRE(ctx, depth, "null depth map: it is what the surface wand reads");
+    RTDD_TRY(check_paint_target(ctx, t, erases));
+    REQUIRE(ctx, wand->x >= 0 && wand->x < cols && wand->y >= 0 && wand->y < rows, "the seed lies outside the image (an empty image has no seed)");
+    REQUIRE(ctx, depthPitch >= (size_t)cols * 4, "pitch smaller than a row");
+    REQUIRE(ctx, f32_image_aligned(depth, depthPitch), kF32AlignText);
+    REQUIRE(ctx, editedPitch >= (size_t)cols * 3 && scribblePitch >= (size_t)cols && (!erases || originalPitch >= (size_t)cols * 3), "pitch smaller than a row");
+    DeviceGuard g(ctx->device);
+    // (as rtdd_fill_similar; here it is also what makes the depth map final: it is usually the output of an estimate still in the log)
+    RTDD_TRY(settle_pending(ctx));
+    RTDD_TRY(begin_paint(ctx, t, erases));
+    return launch_fill_surface(ctx, *wand, t, depth, depthPitch, info);
+}
+
 // host arithmetic only (include/rtdd.h has the rule): doubles, every operation rounded on its own
 int rtdd_ramp_polyline(const int *xy, int n, int radius, int brush, int label0, int label1, rtdd_ramp_stroke *out) {
 #pragma clang fp contract(off)

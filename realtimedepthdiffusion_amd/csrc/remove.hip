@@ -48,7 +48,6 @@ struct Div {
     __device__ __forceinline__ int quot(int idx) const { return (int)__umulhi((uint32_t)idx, inv); }
 };
 
-__device__ __forceinline__ float remove_depth(float d) { return d > 0.0f ? fminf(d, 255.0f) : 0.0f; }       // NaN, -0, negatives: +0
 __device__ __forceinline__ bool is_selected(uint32_t m, int select) { return select == 0 ? m != 0u : m == (uint32_t)select; }
 
 // ---- classes of level 0 over an S x S window at (oy, ox), which may reach outside the image: 0 bystander or outside, 1 source, 2 hole.

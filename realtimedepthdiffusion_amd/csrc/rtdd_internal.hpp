@@ -451,6 +451,8 @@ int launch_fill_polygon(rtdd_ctx *ctx, const int *xy, int n, const rtdd_fill &fi
 // rtdd_fill_similar: the checked wand on three given images; grows the selection in rounds of passes and SYNCHRONISES the stream
 // (the table buffer ctx->sat holds its two bit planes); info may be null
 int launch_fill_similar(rtdd_ctx *ctx, const rtdd_wand &wand, const PaintTarget &t, rtdd_wand_info *info);
+// rtdd_fill_surface: the checked surface wand and the depth map it reads (f32, aligned); three bit planes, otherwise as launch_fill_similar
+int launch_fill_surface(rtdd_ctx *ctx, const rtdd_surface_wand &wand, const PaintTarget &t, const float *depth, size_t depthPitch, rtdd_wand_info *info);
 
 // ---- effect_kernels.hip -------------------------------------------------------------------------
 int launch_effect(rtdd_ctx *ctx, const Effect &e);
