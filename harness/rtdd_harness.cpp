@@ -42,6 +42,10 @@
 //                                 --region-surface "x,y,step[,below,above]:id" (a click on the estimated depth map, rtdd_fill_surface;
 //                                 behind --surface-global every pixel in the band), which also fills the level-0 code plane again, so
 //                                 that --remove-region / --move-region / --plate-region take the region; not with --live or --batch
+//     --segment "step[,lo,hi[,minPixels[,maxRegions[,firstCode]]]]" = extension, with --regions: every surface of the estimated depth map at
+//                                 once (rtdd_segment_surfaces; defaults 0,255, 64, 8, 1) -- the largest become the regions firstCode,
+//                                 firstCode + 1, ... of the region pair, one line printed per region; behind the --region-surface clicks,
+//                                 and like them it fills the level-0 code plane again; not with --live or --batch
 //     --layer sprite --layer-alpha alpha --layer-at x,y [--layer-scale S] [--layer-filter nearest|bilinear] [--layer-depth z | --layer-plane
 //                                 x0,y0,z0,x1,y1,z1] [--layer-feather f] [--layer-opacity o] = extension: a sprite inserted into the scene at
 //                                 a depth (rtdd_composite_layer), after the estimate and before --effect, which then runs on the composite and
@@ -263,6 +267,9 @@ struct Job {
     std::vector<Wand> region_wands;
     // --region-surface "x,y,step[,below,above]:id" (after --surface-global: every pixel in the band): rtdd_fill_surface after the estimate
     std::vector<rtdd_surface_wand> region_surfaces;
+    // --segment "step[,lo,hi[,minPixels[,maxRegions[,firstCode]]]]": rtdd_segment_surfaces after the estimate, behind the clicks above
+    bool segment = false;
+    rtdd_segmentation segmentation{};
     bool edges_color = false;     // --edges color: the estimates read their edge weights from the BGR image (rtdd_pyramid_set_guide); default gray: the reference's
     // --layer sprite --layer-alpha alpha --layer-at x,y [--layer-scale S] [--layer-filter nearest|bilinear] [--layer-depth z | --layer-plane
     // x0,y0,z0,x1,y1,z1] [--layer-feather f] [--layer-opacity o]: rtdd_composite_layer after the estimate; --effect then runs on the composite
@@ -387,7 +394,7 @@ static int region_calls(rtdd_ctx *ctx, const Job &job, const void *orig, size_t 
 // --region-surface: the clicks on the estimate's own depth map (level 0) into the region pair, one rtdd_fill_surface call each (each
 // synchronises); then the level-0 code plane, which --remove-region / --move-region / --plate-region read, is filled again from the pair
 static int region_surface_calls(rtdd_ctx *ctx, const Job &job, const void *depth, size_t depth_pitch, int rows, int cols) {
-    if (job.region_surfaces.empty()) return RTDD_OK;
+    if (job.region_surfaces.empty() && !job.segment) return RTDD_OK;
     void *pe, *pm, *pc; size_t pie, pim, pic;
     CK(rtdd_pyramid_image(ctx, RTDD_IMG_REGION_EDITED, 0, &pe, &pie, nullptr, nullptr));
     CK(rtdd_pyramid_image(ctx, RTDD_IMG_REGION_MASK, 0, &pm, &pim, nullptr, nullptr));
@@ -398,7 +405,26 @@ static int region_surface_calls(rtdd_ctx *ctx, const Job &job, const void *depth
         std::printf("region surface %d,%d step %g band %g,%g%s: region %d, %d pixels, x %d..%d, y %d..%d\n", w.x, w.y, w.step, w.below, w.above,
                     (w.flags & RTDD_SURFACE_GLOBAL) ? " global" : "", w.label0, info.pixels, info.x0, info.x1, info.y0, info.y1);
     }
+    if (job.segment) {                                                // --segment: every surface at once, one line per region
+        std::vector<rtdd_segment> seg((size_t)job.segmentation.maxRegions);
+        rtdd_segment_info info;
+        CK(rtdd_segment_surfaces(ctx, &job.segmentation, (uint8_t *)pe, pie, (uint8_t *)pm, pim, (const float *)depth, depth_pitch, nullptr, 0, rows, cols,
+                                 seg.data(), &info));
+        std::printf("segment step %g band %g,%g minPixels %d: %d components, %d candidates, %d regions, %d pixels\n", job.segmentation.step, job.segmentation.lo,
+                    job.segmentation.hi, job.segmentation.minPixels, info.components, info.candidates, info.regions, info.pixels);
+        for (int k = 0; k < info.regions; k++)
+            std::printf("segment region %d: %d pixels, root %d,%d, x %d..%d, y %d..%d, depth %.9g..%.9g\n", seg[k].code, seg[k].pixels, seg[k].rootX, seg[k].rootY,
+                        seg[k].x0, seg[k].x1, seg[k].y0, seg[k].y1, seg[k].dmin, seg[k].dmax);
+    }
     return rtdd_region_codes(ctx, (const uint8_t *)pe, pie, (const uint8_t *)pm, pim, rows, cols, 0, (uint8_t *)pc, pic);
+}
+
+// "step", "step,lo,hi", "step,lo,hi,minPixels", "...,maxRegions", "...,firstCode" (the library checks the values)
+static bool parse_segment(const char *arg, rtdd_segmentation *g) {
+    *g = rtdd_segmentation{0.0f, 0.0f, 255.0f, 64, 8, 1, 0};
+    int n = 0;
+    const int got = std::sscanf(arg, "%f%n,%f,%f%n,%d%n,%d%n,%d%n", &g->step, &n, &g->lo, &g->hi, &n, &g->minPixels, &n, &g->maxRegions, &n, &g->firstCode, &n);
+    return got >= 1 && got != 2 && n > 0 && arg[n] == 0;
 }
 
 // "x,y,step:id" or "x,y,step,below,above:id"
@@ -748,7 +774,7 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
             if (n == 0 && job.refine == "auto") std::printf("refine auto: %d cycles + %d sweeps, residual %g\n", si.cycles, si.iterations, si.residual);
             else if (n == 0) std::printf("refine %s: %d %s, residual %g\n", job.refine.c_str(), si.iterations, job.refine == "mg" ? "cycles" : "sweeps", si.residual);
         }
-        // --region-surface: the regions clicked on the estimate's depth map, before anything below reads the level-0 code plane
+        // --region-surface, --segment: the regions clicked or found on the estimate's depth map, before anything below reads the level-0 code plane
         CK(region_surface_calls(ctx, job, p_depth, pi_depth, rows, cols));
         // --layer: the sprite is inserted after the estimate; the effect below then reads the composite and the composite's depth map
         // (desaturation's gray image stays the photograph's)
@@ -877,7 +903,7 @@ int main(int argc, const char *argv[]) {
                                  "                    [relight's light flags] [--shadows N (256)] [--shadow-bias B] [--shadow-softness S] [--shadow-strength T] [--ao R (16)] [--ao-directions 4|8] [--ao-bias B] [--ao-strength T] (lighting: shade, cast shadows and occlusion in one call)\n"
                                  "                    [--layer sprite.(ppm|png|jpg) [--layer-alpha alpha.(pgm|png)] --layer-at x,y [--layer-scale S (256)] [--layer-filter nearest|bilinear] [--layer-depth z (128) | --layer-plane x0,y0,z0,x1,y1,z1] [--layer-feather f] [--layer-opacity o (255)]]   (a sprite inserted at a depth after the estimate, rtdd_composite_layer: --effect then runs on the composite and its depth map; without --effect ArtisticEffect is the composite)\n"
                                  "                    [--remove-region id [--remove-grow N (0..8)] [--remove-behind D] | --move-region id:dx,dy[:depth] [--remove-grow N] [--remove-behind D]]   (with --regions: the painted region taken out of the scene, rtdd_remove_object, or moved, rtdd_lift_layer + rtdd_remove_object + rtdd_composite_layer; before --layer and --effect, which run on the result and its depth map)\n"
-                                 "                    [--paint x,y,label,radius]... [--live N [--paint-at frame:x,y,label,radius]...] [--devices D --batch B [--sequential] [--write-all]] [--png] [--cold] [--edges gray|color] [--regions cut|smooth|both [--region-fill x,y;...:id]... [--region-wand x,y,tol:id]... [--surface-global] [--region-surface x,y,step[,below,above]:id]...]   (--region-surface: a click on the ESTIMATED depth map, rtdd_fill_surface into the region pair after the estimate and before --remove-region / --move-region / --plate-region; --surface-global: the clicks behind it take every pixel in their band; not with --live or --batch)\n"
+                                 "                    [--paint x,y,label,radius]... [--live N [--paint-at frame:x,y,label,radius]...] [--devices D --batch B [--sequential] [--write-all]] [--png] [--cold] [--edges gray|color] [--regions cut|smooth|both [--region-fill x,y;...:id]... [--region-wand x,y,tol:id]... [--surface-global] [--region-surface x,y,step[,below,above]:id]... [--segment step[,lo,hi[,minPixels[,maxRegions[,firstCode]]]]]]   (--segment: every surface of the ESTIMATED depth map at once, rtdd_segment_surfaces into the region pair behind the clicks, the largest as regions firstCode, firstCode + 1, ...; --region-surface: a click on the ESTIMATED depth map, rtdd_fill_surface into the region pair after the estimate and before --remove-region / --move-region / --plate-region; --surface-global: the clicks behind it take every pixel in their band; not with --live or --batch)\n"
                                  "                    [--stroke x0,y0,x1,y1,label,radius[,round]]... [--erase x0,y0,x1,y1,radius[,round]]...   (segments, in command-line order, one rtdd_paint_strokes call after --paint)\n"
                                  "                    [--ramp x0,y0,x1,y1,label0,label1,radius[,round]]...   (a depth ramp: label0 at x0,y0 to label1 at x1,y1; in order with --stroke / --erase, all of them one rtdd_paint_ramp_strokes call)\n"
                                  "                    [--fill \"x,y;x,y;...:label\" | \"x,y;...:label0,label1,ax0,ay0,ax1,ay1\"]... [--fill-erase \"x,y;x,y;...\"]... [--fill-rule nonzero|evenodd]   (a lasso filled with a label, a ramp along the axis, or erased: one rtdd_fill_polygon call each, after the strokes, in command-line order)\n"
@@ -918,6 +944,10 @@ int main(int argc, const char *argv[]) {
             job.region_fills.push_back(l);
         }
         else if (!std::strcmp(argv[i], "--surface-global")) surface_flags = RTDD_SURFACE_GLOBAL;
+        else if (!std::strcmp(argv[i], "--segment")) {
+            if (!parse_segment(next(), &job.segmentation)) { std::printf("--segment wants step[,lo,hi[,minPixels[,maxRegions[,firstCode]]]]\n"); return 1; }
+            job.segment = true;
+        }
         else if (!std::strcmp(argv[i], "--region-surface")) {
             rtdd_surface_wand w;
             if (!parse_surface(next(), surface_flags, &w) || w.label0 < 1 || w.label0 > 255) { std::printf("--region-surface wants x,y,step:id or x,y,step,below,above:id, the id 1..255\n"); return 1; }
@@ -1064,6 +1094,8 @@ int main(int argc, const char *argv[]) {
     if (job.region_flags == 0 && (!job.region_fills.empty() || !job.region_wands.empty())) { std::printf("--region-fill and --region-wand need --regions cut|smooth|both\n"); return 1; }
     if (!job.region_surfaces.empty() && job.region_flags == 0) { std::printf("--region-surface needs --regions cut|smooth|both\n"); return 1; }
     if (!job.region_surfaces.empty() && (live > 0 || batch > 1)) { std::printf("--region-surface is not supported with --live or --batch\n"); return 1; }
+    if (job.segment && job.region_flags == 0) { std::printf("--segment needs --regions cut|smooth|both\n"); return 1; }
+    if (job.segment && (live > 0 || batch > 1)) { std::printf("--segment is not supported with --live or --batch\n"); return 1; }
     if (shadow_opt && !job.shadows && !lighting) { std::printf("--shadow-bias, --shadow-softness and --shadow-strength need --shadows N\n"); return 1; }
     // ambient occlusion is --effect ao, or --ao R under --effect relight (without cast shadows: one call renders one or the other); its
     // parameters belong to one of the two: a stray one is refused, not dropped

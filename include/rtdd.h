@@ -579,6 +579,66 @@ int rtdd_fill_surface(rtdd_ctx *ctx, const rtdd_surface_wand *wand,
                       const float *depth, size_t depthPitch,           /* DEVICE f32, read only */
                       int rows, int cols, rtdd_wand_info *info /* may be NULL */);
 
+/* Every surface of the depth map in one call -- connected-component labelling of rtdd_fill_surface's link graph (extension; no reference
+ * behaviour; found by symbol like rtdd_fill_surface, no version bump; the next bump of RTDD_VERSION should cover it too).  Where the wand
+ * answers "what is under this click", this answers "what are the surfaces": the largest components are numbered and painted as region
+ * codes, and a label map turns every later click into a lookup.  Every comparison is on f32 values, each operation rounded once.
+ * Clamped depth: d'(p) = d > 0 ? fminf(d, 255) : +0 -- rtdd_fill_surface's: a NaN, -0 and every negative depth are +0, +inf is 255.
+ * Admissible: lo <= d'(p) && d'(p) <= hi, with lo and hi given as absolute values: there is no seed, nothing is read to form the band.
+ * Link: two 4-neighbours p, q inside the image are linked iff both are admissible and fabsf(d'(p) - d'(q)) <= step (one f32
+ *   subtraction): exactly rtdd_fill_surface's link.
+ * Component: the pixels joined by a path of links.  An admissible pixel with no link is a component of one pixel; an inadmissible pixel
+ *   belongs to no component.  The image border ends a path.
+ * Root: the smallest linear index y * cols + x of a component's pixels.  Size: the number of its pixels.
+ * Candidates: the components of at least minPixels pixels.
+ * Ranking: candidates by size descending, then by root ascending.  The first K = min(candidates, maxRegions) are the regions; region k
+ *   (0-based) has the code firstCode + k.
+ * Writes, on the paint calls' pair (edited u8 x 3, scribble u8): a pixel of region k gets edited = (code, code, code), scribble = 255;
+ *   every other pixel is not written.  `depth` is never written.  The region pair (RTDD_IMG_REGION_EDITED / _MASK) is the intended target
+ *   and the annotation pair is legal; on the pyramid's own pairs the call notes the change exactly as rtdd_fill_surface.  edited and
+ *   scribble may BOTH be NULL when only the label map or the records are wanted.
+ * Label map (optional): device int32, pitch a multiple of 4 and at least 4 * cols, pointer 4-byte aligned.  Every pixel is written exactly
+ *   once: the root of its component, or -1 where it is inadmissible.  The padding keeps its bytes.
+ * Records (optional): a HOST array of maxRegions entries; the first K are filled, in rank order: the code, the size, the root as
+ *   (rootX, rootY), the inclusive bounding box, and dmin / dmax, the smallest and largest d' of the region (d' >= +0, so the order of the
+ *   bit patterns is the order of the values: integer minima and maxima of the bits, exact; nothing is summed).
+ * Info: components (all of them), candidates, regions (K) and pixels (the sum over the regions).  Everything returned is deterministic: the
+ *   result is a property of an undirected graph.  There is no `passes`: nothing iterates to a fixpoint.
+ * Refused (RTDD_ERR_INVALID) before any launch, nothing written: a null parameter struct; a null depth; a depth pitch smaller than
+ *   4 * cols or not a multiple of 4, a depth pointer not 4-byte aligned; step, lo or hi non-finite or outside [0, 255]; lo > hi;
+ *   minPixels < 1; maxRegions outside 1..255; firstCode outside 1..255 or firstCode + maxRegions - 1 > 255; any flag bit (none is defined);
+ *   rows or cols of 0, negative or above 32768; exactly ONE of edited and scribble being NULL; a pitch of the pair smaller than a row; a
+ *   label map whose pitch or pointer breaks the rule above.  A retired level-0 pointer of live mode: RTDD_ERR_STATE.  Scratch that cannot
+ *   be allocated: RTDD_ERR_NOMEM, nothing written.
+ * THE CALL SYNCHRONISES, because it returns counts and records: once, or twice when more than 1024 components have minPixels pixels (the
+ * candidates beyond the first 1024 take a second copy).  Logged solves and estimates are confirmed (or healed) first, as by
+ * rtdd_fill_surface.  The label map is complete when the call returns; the writes to the pair are queued on the context's stream behind
+ * it, like every other paint call's.  Not logged by the heal log.  Six launches (five without a pair), whatever the data and the size:
+ * links, tile labels, border merge, flatten and reduce, collect, paint.  The scratch is the context's table buffer: about 17 bytes per
+ * pixel for the planes and the parents, 28 per pixel for the records and 32 * rows * cols / minPixels for the candidate list.
+ * Not built: 8-connectivity; a rule over colour and depth; merging small components into neighbours; clearing the rest of the pair;
+ * numbering by nearness (the records carry dmin: renumber on the host). */
+typedef struct rtdd_segmentation {
+    float step;                 /* finite, [0, 255]: rtdd_surface_wand's */
+    float lo, hi;               /* finite, [0, 255], lo <= hi: only depths in [lo, hi] take part */
+    int   minPixels;            /* >= 1: smaller components are no candidates */
+    int   maxRegions;           /* 1..255 */
+    int   firstCode;            /* 1..255, firstCode + maxRegions - 1 <= 255 */
+    int   flags;                /* 0 */
+} rtdd_segmentation;
+typedef struct rtdd_segment {
+    int   code, pixels, rootX, rootY;
+    int   x0, y0, x1, y1;       /* inclusive bounding box */
+    float dmin, dmax;           /* smallest and largest clamped depth */
+} rtdd_segment;                 /* 40 bytes */
+typedef struct rtdd_segment_info { int components, candidates, regions, pixels; } rtdd_segment_info;
+int rtdd_segment_surfaces(rtdd_ctx *ctx, const rtdd_segmentation *seg,
+                          uint8_t *edited, size_t editedPitch, uint8_t *scribble, size_t scribblePitch,   /* both NULL: nothing painted */
+                          const float *depth, size_t depthPitch,           /* DEVICE f32, read only */
+                          int32_t *labels, size_t labelsPitch,             /* DEVICE int32, may be NULL */
+                          int rows, int cols, rtdd_segment *segments /* HOST, maxRegions entries, may be NULL */,
+                          rtdd_segment_info *info /* may be NULL */);
+
 /* ---- depth effects (include/GPUDepthEffect.h:4-9) ------------------------------------------ */
 
 /* GPUSimulateDefocus -- src/GPUDepthEffect.cu:29-72,105-113 (exact, via an integer summed-area table). */

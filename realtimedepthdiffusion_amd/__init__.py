@@ -52,7 +52,7 @@ C_ABI_SYMBOLS = [
     "rtdd_live_submit", "rtdd_live_wait", "rtdd_live_pending", "rtdd_host_alloc", "rtdd_host_free",
     "rtdd_pyramid_create_batch", "rtdd_pyramid_select", "rtdd_pyramid_batch", "rtdd_estimate_depth_batch", "rtdd_pyramid_level_info", "rtdd_live_submit_ex",
     "rtdd_simulate_refocus", "rtdd_simulate_haze_ex", "rtdd_simulate_stereo", "rtdd_simulate_lens_blur",
-    "rtdd_paint_strokes", "rtdd_pyramid_annotation_rebuild", "rtdd_paint_ramp_strokes", "rtdd_ramp_polyline", "rtdd_fill_polygon", "rtdd_fill_similar", "rtdd_fill_surface",
+    "rtdd_paint_strokes", "rtdd_pyramid_annotation_rebuild", "rtdd_paint_ramp_strokes", "rtdd_ramp_polyline", "rtdd_fill_polygon", "rtdd_fill_similar", "rtdd_fill_surface", "rtdd_segment_surfaces",
     "rtdd_simulate_relight", "rtdd_simulate_relight_shadowed", "rtdd_simulate_parallax", "rtdd_simulate_ambient_occlusion",
     "rtdd_simulate_lighting", "rtdd_simulate_bokeh", "rtdd_composite_layer", "rtdd_remove_object", "rtdd_lift_layer",
     "rtdd_simulate_parallax_layered",
@@ -75,6 +75,8 @@ STROKE_ERASE = -1                             # rtdd_stroke.label: remove the an
 FILL_NONZERO, FILL_EVEN_ODD = 0, 1            # rtdd_fill.rule
 WAND_CONNECT_8, WAND_GLOBAL = 1, 2            # rtdd_wand.flags
 SURFACE_GLOBAL = 1                            # rtdd_surface_wand.flags
+SEGMENT_TILE_W, SEGMENT_TILE_H = 64, 16       # the tile rtdd_segment_surfaces labels in LDS before it merges across borders (csrc/segment.hip: kPaintTileW, kPaintTileH)
+SEGMENT_HEAD = 1024                           # candidates it reads back with the counters; more take a second copy (csrc/segment.hip: kSegHead)
 WAND_ROUND = 8                                # grow passes rtdd_fill_similar queues between two synchronisations (csrc/fill_similar.hip: kWandRound)
 # rtdd_remove_object's grouping (csrc/rtdd_internal.hpp: kRemoveTile, kRemoveGroup, kRemoveApex, kRemoveApexChain): a workgroup owns a
 # REMOVE_TILE-square tile of a level and takes REMOVE_GROUP levels in LDS; one workgroup takes a level of at most REMOVE_APEX samples
@@ -164,6 +166,24 @@ class SurfaceWand(C.Structure):
 class WandInfo(C.Structure):
     """rtdd_wand_info: the covered pixels, their inclusive bounding box, and the grow passes that ran (a diagnostic: not deterministic)."""
     _fields_ = [("pixels", C.c_int), ("x0", C.c_int), ("y0", C.c_int), ("x1", C.c_int), ("y1", C.c_int), ("passes", C.c_int)]
+
+
+class Segmentation(C.Structure):
+    """rtdd_segmentation: the largest depth step between two joined neighbours, the absolute band [lo, hi] of depths that take part, the
+    smallest component that is a candidate, the number of regions wanted (1..255), the first region's code, flags (0)."""
+    _fields_ = [("step", C.c_float), ("lo", C.c_float), ("hi", C.c_float), ("minPixels", C.c_int), ("maxRegions", C.c_int), ("firstCode", C.c_int),
+                ("flags", C.c_int)]
+
+
+class Segment(C.Structure):
+    """rtdd_segment: a region's code, size, root, inclusive bounding box and the smallest and largest clamped depth in it."""
+    _fields_ = [("code", C.c_int), ("pixels", C.c_int), ("rootX", C.c_int), ("rootY", C.c_int), ("x0", C.c_int), ("y0", C.c_int), ("x1", C.c_int),
+                ("y1", C.c_int), ("dmin", C.c_float), ("dmax", C.c_float)]
+
+
+class SegmentInfo(C.Structure):
+    """rtdd_segment_info: all components, those of at least minPixels pixels, the regions numbered, and the pixels in them."""
+    _fields_ = [("components", C.c_int), ("candidates", C.c_int), ("regions", C.c_int), ("pixels", C.c_int)]
 
 
 def ramp_polyline(points, radius, brush, label0, label1):
@@ -536,6 +556,20 @@ class Context:
         d, dp = _img(depth)
         self._check(lib().rtdd_fill_surface(self._h, C.byref(w), *_paint_images(edited, scribble, original), d, dp, C.c_int(rows), C.c_int(cols), C.byref(info)))
         return info
+
+    def segment_surfaces(self, seg, edited, scribble, rows, cols, depth, labels=None):
+        """rtdd_segment_surfaces: every component of rtdd_fill_surface's link graph over `depth` (f32) under `seg` (a Segmentation or a
+        7-tuple step, lo, hi, minPixels, maxRegions, firstCode, flags); the largest are painted into the pair as codes firstCode, ...
+        (edited and scribble both None: nothing is painted) and `labels` (int32, optional) gets every pixel's root or -1.  SYNCHRONISES;
+        returns (SegmentInfo, [Segment, ...] in rank order)."""
+        g = seg if isinstance(seg, Segmentation) else Segmentation(*seg)
+        info = SegmentInfo()
+        records = (Segment * max(g.maxRegions, 1))()
+        none = (None, C.c_size_t(0))
+        self._check(lib().rtdd_segment_surfaces(self._h, C.byref(g), *(_img(edited) if edited is not None else none),
+                                                *(_img(scribble) if scribble is not None else none), *_img(depth),
+                                                *(_img(labels) if labels is not None else none), C.c_int(rows), C.c_int(cols), records, C.byref(info)))
+        return info, [records[k] for k in range(info.regions)]
 
     # ---- include/GPUDepthEffect.h
     def GPUSimulateDefocus(self, originalImage, depthImage, artisticImage, rows, cols):

@@ -238,6 +238,35 @@ int rtdd_fill_surface(rtdd_ctx *ctx, const rtdd_surface_wand *wand, uint8_t *edi
     return launch_fill_surface(ctx, *wand, t, depth, depthPitch, info);
 }
 
+// Every component of rtdd_fill_surface's link graph in one call: synchronises for the counts and records, settles first for
+// rtdd_fill_surface's reason.  Everything is checked before the device is touched.
+int rtdd_segment_surfaces(rtdd_ctx *ctx, const rtdd_segmentation *seg, uint8_t *edited, size_t editedPitch, uint8_t *scribble, size_t scribblePitch,
+                          const float *depth, size_t depthPitch, int32_t *labels, size_t labelsPitch, int rows, int cols, rtdd_segment *segments,
+                          rtdd_segment_info *info) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    const PaintTarget t{edited, editedPitch, scribble, scribblePitch, nullptr, 0, rows, cols};
+    REQUIRE(ctx, seg, "null segmentation");
+    for (float v : {seg->step, seg->lo, seg->hi}) REQUIRE(ctx, std::isfinite(v) && v >= 0.0f && v <= 255.0f, "step, lo or hi not a finite value in [0, 255]");
+    REQUIRE(ctx, seg->lo <= seg->hi, "lo above hi");
+    REQUIRE(ctx, seg->minPixels >= 1, "minPixels below 1");
+    REQUIRE(ctx, seg->maxRegions >= 1 && seg->maxRegions <= 255, "maxRegions outside [1, 255]");
+    REQUIRE(ctx, seg->firstCode >= 1 && seg->firstCode <= 255 && seg->firstCode + seg->maxRegions - 1 <= 255, "the codes firstCode .. firstCode + maxRegions - 1 leave [1, 255]");
+    REQUIRE(ctx, seg->flags == 0, "unknown segmentation flag");
+    REQUIRE(ctx, depth, "null depth map: it is what the segmentation reads");
+    REQUIRE(ctx, (edited != nullptr) == (scribble != nullptr), "one image of the pair given without the other");
+    REQUIRE(ctx, rows >= 1 && cols >= 1, "an empty image, or a negative size");
+    REQUIRE(ctx, rows <= 32768 && cols <= 32768, "image larger than 32768 pixels in a direction");
+    REQUIRE(ctx, depthPitch >= (size_t)cols * 4, "pitch smaller than a row");
+    REQUIRE(ctx, f32_image_aligned(depth, depthPitch), kF32AlignText);
+    REQUIRE(ctx, !edited || (editedPitch >= (size_t)cols * 3 && scribblePitch >= (size_t)cols), "pitch smaller than a row");
+    REQUIRE(ctx, !labels || (labelsPitch >= (size_t)cols * 4 && (uintptr_t)labels % 4 == 0 && labelsPitch % 4 == 0),
+            "the label map needs a pitch of at least 4 * cols and a pointer and a pitch that are multiples of 4");
+    DeviceGuard g(ctx->device);
+    RTDD_TRY(settle_pending(ctx));                                   // (as rtdd_fill_surface)
+    if (edited) RTDD_TRY(begin_paint(ctx, t, false));
+    return launch_segment_surfaces(ctx, *seg, t, depth, depthPitch, labels, labelsPitch, segments, info);
+}
+
 // host arithmetic only (include/rtdd.h has the rule): doubles, every operation rounded on its own
 int rtdd_ramp_polyline(const int *xy, int n, int radius, int brush, int label0, int label1, rtdd_ramp_stroke *out) {
 #pragma clang fp contract(off)

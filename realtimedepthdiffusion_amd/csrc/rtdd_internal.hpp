@@ -454,6 +454,12 @@ int launch_fill_similar(rtdd_ctx *ctx, const rtdd_wand &wand, const PaintTarget 
 // rtdd_fill_surface: the checked surface wand and the depth map it reads (f32, aligned); three bit planes, otherwise as launch_fill_similar
 int launch_fill_surface(rtdd_ctx *ctx, const rtdd_surface_wand &wand, const PaintTarget &t, const float *depth, size_t depthPitch, rtdd_wand_info *info);
 
+// ---- segment.hip --------------------------------------------------------------------------------
+// rtdd_segment_surfaces: the checked parameters; t.edited and t.scribble both null or both given, labels and segments may be null;
+// SYNCHRONISES (once, or twice), the paint pass is queued behind that
+int launch_segment_surfaces(rtdd_ctx *ctx, const rtdd_segmentation &sg, const PaintTarget &t, const float *depth, size_t depthPitch, int32_t *labels,
+                            size_t labelsPitch, rtdd_segment *segments, rtdd_segment_info *info);
+
 // ---- effect_kernels.hip -------------------------------------------------------------------------
 int launch_effect(rtdd_ctx *ctx, const Effect &e);
 // ---- lens_blur.hip: Effect::kLensBlur (called by launch_effect) ------------------------------------
