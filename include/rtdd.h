@@ -240,6 +240,14 @@ int rtdd_solve_ex(rtdd_ctx *ctx, float *depth, size_t depthPitch,
  * solves inside rtdd_estimate_depth: the finest level's). */
 int rtdd_last_solve_info(rtdd_ctx *ctx, rtdd_solve_info *info);
 
+/* Read only, for tests and diagnosis: how many waves of this context's persistent Jacobi launches have entered SCALED MODE since the
+ * context was created.  A wave of a persistent launch (RTDD_OPT_PERSISTENT) whose sweeps keep meeting numerators below 2^-100 -- free
+ * pixels enclosed by label-0 strokes decay that far -- divides every pixel by a uniformly scaled form of the same correctly rounded
+ * divide from the next halo exchange on; results are the same bits, and nothing switches the mode off.  It is not entered in a solve whose
+ * input holds a depth of 2^32 or more in magnitude, and never by a launch per block of sweeps.  Synchronises (rtdd_ctx_synchronize).
+ * (A function and not a read-only rtdd_option: found by symbol, no version bump; the next bump of RTDD_VERSION should cover it.) */
+int rtdd_scaled_mode_waves(rtdd_ctx *ctx, int *waves);
+
 /* Diagnostic for the parity tests: after a RTDD_METHOD_MULTIGRID solve, copy plane `which` (0-4: couplings E,S,SE,SW and
  * diagonal D; 5-8: interpolation weights; 9-11: e, b, r) of hierarchy level `level` to host memory, dense rows x cols
  * floats.  host == NULL only reports the size.  Synchronises. */

@@ -43,7 +43,7 @@ RTDD_ERR_TIMEOUT = 6
 C_ABI_SYMBOLS = [
     "rtdd_ctx_create", "rtdd_ctx_destroy", "rtdd_ctx_set_stream", "rtdd_ctx_synchronize", "rtdd_set_option",
     "rtdd_get_option", "rtdd_last_error", "rtdd_status_string", "rtdd_version", "rtdd_allocate", "rtdd_free",
-    "rtdd_load_weights", "rtdd_matrix_free_solver", "rtdd_solve_ex", "rtdd_last_solve_info", "rtdd_multigrid_level", "rtdd_index_to_weight", "rtdd_convert_to_float",
+    "rtdd_load_weights", "rtdd_matrix_free_solver", "rtdd_solve_ex", "rtdd_last_solve_info", "rtdd_scaled_mode_waves", "rtdd_multigrid_level", "rtdd_index_to_weight", "rtdd_convert_to_float",
     "rtdd_pyrdown_annotation", "rtdd_paint_image", "rtdd_simulate_defocus", "rtdd_simulate_desaturation",
     "rtdd_simulate_haze", "rtdd_profile_enable", "rtdd_profile_get",
     "rtdd_pyramid_levels", "rtdd_pyramid_create", "rtdd_pyramid_destroy", "rtdd_pyramid_set_image",
@@ -471,6 +471,12 @@ class Context:
         info = SolveInfo()
         self._check(lib().rtdd_last_solve_info(self._h, C.byref(info)))
         return info
+
+    def scaled_mode_waves(self):
+        """How many waves of this context's persistent Jacobi launches have entered scaled mode so far (rtdd_scaled_mode_waves; synchronises)."""
+        n = C.c_int(0)
+        self._check(lib().rtdd_scaled_mode_waves(self._h, C.byref(n)))
+        return n.value
 
     def multigrid_level(self, level, which):
         """Diagnostic: plane `which` of hierarchy level `level` after a METHOD_MULTIGRID solve, as a numpy array."""

@@ -559,7 +559,7 @@ int rtdd::solve_with(rtdd_ctx *ctx, const SolveCall &c, rtdd_solve_info *info, S
         if (!ctx->healing) RTDD_TRY(settle_pending(ctx));
         RTDD_HIP(ctx, hipStreamSynchronize(ctx->stream));
         *(volatile int *)ctx->confirm_host = 0;
-        RTDD_HIP(ctx, hipMemset(ctx->sync_words + kSyncWild, 0, sizeof(int)));
+        RTDD_HIP(ctx, hipMemset(ctx->sync_words + kSyncWild, 0, 2 * sizeof(int)));      // (kSyncWild and kSyncLarge)
         ctx->solve_seq = 0; ctx->publish_seq = 0;
     }
     const int seq = ++ctx->solve_seq;
@@ -589,6 +589,14 @@ extern "C" {
 int rtdd_last_solve_info(rtdd_ctx *ctx, rtdd_solve_info *info) {
     if (!ctx || !info) return RTDD_ERR_INVALID;
     *info = ctx->last_info;
+    return RTDD_OK;
+}
+
+int rtdd_scaled_mode_waves(rtdd_ctx *ctx, int *waves) {
+    if (!ctx || !waves) return RTDD_ERR_INVALID;
+    RTDD_TRY(rtdd_ctx_synchronize(ctx));
+    DeviceGuard g(ctx->device);
+    RTDD_HIP(ctx, hipMemcpy(waves, ctx->sync_words + kSyncScaled, sizeof(int), hipMemcpyDeviceToHost));      // (persist_sync.hpp: the waves count themselves)
     return RTDD_OK;
 }
 

@@ -21,6 +21,13 @@
 //                    magnitude (solver_kernels.hip; a plain vector store, made only when such a value is found).  The register-blocked
 //                    sweep kernels compare it with their own solve's number and, when equal, run the variant with the full IEEE divide
 //                    and explicit absent neighbours (sweep_common.hpp div_tail).  Never cleared: sequence numbers do not repeat.
+//   [kSyncLarge]     sequence number of the most recent solve whose k_prepare met a depth of 2^32 or more in magnitude (or not finite: every
+//                    wild depth is large too).  Raised where kSyncWild is raised and in the same way.  The persistent sweep compares it with
+//                    its solve's number: when equal, no wave of the launch enters SCALED MODE (sweep_common.hpp div_scaled, whose numerator
+//                    times 2^64 must not overflow).  The word behind kSyncWild, so that the kernel reads both with one 8-byte load.
+//   [kSyncScaled]    how many waves have entered scaled mode over the life of the context: one lane of a wave adds 1 when the wave
+//                    enters it (once per wave and launch, on the cold path).  Read back by rtdd_scaled_mode_waves, for the tests: nothing
+//                    in the product depends on it.
 //   [kSyncFlags ..]  one block counter per tile.  Monotonic over the life of the context: launch L's workgroups publish base_L + block
 //                    number, base_L handed in by the host (heal.cpp prepare_persistent_launch), so nothing is zeroed between launches.
 #pragma once
@@ -31,7 +38,7 @@ namespace rtdd {
 // kSyncFlagStride: ints between the flags of consecutive tiles.  64 = one flag per 256 bytes (its own line, and neighbouring tiles on different memory channels): a tile's flag is stored once and polled
 // by up to 8 neighbours, all through memory (sc1); packed 32 to a line (round 2) every store and poll of 32 tiles met on one line: 1080p 1.17 -> 1.24 Tpx-it/s with one line each, +1.5 % more at 256 bytes.
 constexpr int kSyncStatus = 0, kSyncWithhold = 1, kSyncLimit = 2, kSyncNonLocal = 3 /* k_defocus_tile met windows beyond its region (effect_kernels.hip) */, kSyncFailedSeq = 4,
-              kSyncConfirmPtr = 6 /* two ints: the device address of the context's page-locked `confirmed sequence number` word */, kSyncWild = 8, kSyncFlags = 32, kSyncMaxTiles = 1024, kSyncFlagStride = 64;
+              kSyncConfirmPtr = 6 /* two ints: the device address of the context's page-locked `confirmed sequence number` word */, kSyncWild = 8, kSyncLarge = 9 /* = kSyncWild + 1: one 8-byte load */, kSyncScaled = 10, kSyncFlags = 32, kSyncMaxTiles = 1024, kSyncFlagStride = 64;
 constexpr int kSyncWords = kSyncFlags + kSyncMaxTiles * kSyncFlagStride;              // size of sync_words in ints
 constexpr unsigned long long kDefaultPollLimit = 20000000ull;      // 200 ms: legitimate waits are microseconds
 // Round 6: the FIRST thing a persistent workgroup does is announce itself (its flag := the launch's base value) and wait for its
@@ -48,6 +55,10 @@ constexpr unsigned long long kArrivalPollLimit = 150000ull;        // 1.5 ms
 // and the 3-operation divide's q0 = n * y is within an ulp of a weighted mean, no larger than the largest of them.  Red-black: the
 // update is clamped to [0, 255] outright.  (tests/wild_depth.py: `magnitudes` runs just below the threshold, `huge` above it.)
 constexpr float kWildDepth = 0x1p100f;
+// A depth of this magnitude or more (or a NaN) makes k_prepare raise kSyncLarge as well.  By the same argument an iterate that starts below
+// it stays within a small multiple of 2^32, and a sum of four of them (weights <= 1) below 2^64 with about 2^30 to spare: the numerator
+// div_scaled multiplies by 2^64 stays finite.  Depth maps in [0, 255] never raise the word.
+constexpr float kLargeDepth = 0x1p32f;
 
 #ifdef __HIPCC__
 // true when depth value d must send its solve to the sweep kernels' full-divide variant (NaN compares false)
@@ -56,6 +67,15 @@ __device__ __forceinline__ bool depth_is_wild(float d) { return !(__builtin_fabs
 // of the kernel, next to the tile loads: read where it is used, behind the setup, the load sits alone on every launch's critical
 // path while the chip's tile loads are in flight (4K, 125 launches per solve: 5 % slower; EXPERIMENTS.md).
 __device__ __forceinline__ int load_wild_word(const int *sync_words) { return sync_words[kSyncWild]; }
+__device__ __forceinline__ bool depth_is_large(float d) { return !(__builtin_fabsf(d) < kLargeDepth); }
+// What every prepare body does with a depth it has read (plain vector stores, made only when such a value is found).
+__device__ __forceinline__ void raise_depth_words(int *sync_words, bool wild, bool large, int seq) {
+    if (wild) sync_words[kSyncWild] = seq;
+    if (large) sync_words[kSyncLarge] = seq;
+}
+// kSyncWild and kSyncLarge in one load (.x, .y): the persistent sweep's, at the same place as load_wild_word and for the same reason.
+static_assert(kSyncLarge == kSyncWild + 1 && kSyncWild % 2 == 0, "the two words are read as one aligned pair");
+__device__ __forceinline__ int2 load_wild_and_large_words(const int *sync_words) { return *(const int2 *)(sync_words + kSyncWild); }
 // The kernels that publish a solve's result into the caller's buffers call this first (every thread; `first` = one thread of the
 // grid): true = a sweep launch in front of them gave up, store nothing.  The reference's solver always leaves a valid depth map
 // (src/GPUSolver.cu:311-314); here a failed solve leaves its INPUT in place so that the host can run it again.

@@ -89,7 +89,7 @@ __device__ __forceinline__ void prepare_px(RTDD_PREPARE_PARAMS(gray, grayPitch, 
         if (REGIONS) down = region_index(down, rrow[x], rrow[x + codesPitch], regionFlags);
     }
     const size_t p = (size_t)y * ip + x;
-    if (depth_is_wild(d)) sync_words[kSyncWild] = wild_seq;      // (persist_sync.hpp: the blocked sweeps then take their full-divide variant)
+    raise_depth_words(sync_words, depth_is_wild(d), depth_is_large(d), wild_seq);      // (persist_sync.hpp: the blocked sweeps then take their full-divide variant / stay out of scaled mode)
     X0[p] = d;
     X1[p] = dirichlet ? d : 0.0f;     // x_{-1} = 0 on free pixels (cudaMemset, :290); Dirichlet value in both planes (:291-292)
     M[p] = (uint32_t)right | ((uint32_t)down << 8) | (dirichlet ? kMetaDirichlet : 0u);
@@ -188,7 +188,8 @@ __device__ __forceinline__ void prepare4_px(RTDD_PREPARE_PARAMS(gray, grayPitch,
         mv[i] = (uint32_t)right | ((uint32_t)down << 8) | (dirichlet ? kMetaDirichlet : 0u);
     }
     // (pixels past the end of a ragged row were loaded as 0)
-    if (depth_is_wild(d[0]) || depth_is_wild(d[1]) || depth_is_wild(d[2]) || depth_is_wild(d[3])) sync_words[kSyncWild] = wild_seq;
+    raise_depth_words(sync_words, depth_is_wild(d[0]) || depth_is_wild(d[1]) || depth_is_wild(d[2]) || depth_is_wild(d[3]),
+                      depth_is_large(d[0]) || depth_is_large(d[1]) || depth_is_large(d[2]) || depth_is_large(d[3]), wild_seq);
     const size_t p = (size_t)y * ip + x0;          // the planes' rows are 256-byte aligned and padded: whole 16-byte stores always fit; columns >= cols are never read as pixels
     *(float4 *)(X0 + p) = make_float4(x0v[0], x0v[1], x0v[2], x0v[3]);
     *(float4 *)(X1 + p) = make_float4(x1v[0], x1v[1], x1v[2], x1v[3]);
@@ -280,7 +281,7 @@ __device__ __forceinline__ void prepare_bgr_px(RTDD_PREPARE_PARAMS(bgr, bgrPitch
         if (REGIONS) down = region_index(down, rrow[x], rrow[x + codesPitch], regionFlags);
     }
     const size_t p = (size_t)y * ip + x;
-    if (depth_is_wild(d)) sync_words[kSyncWild] = wild_seq;
+    raise_depth_words(sync_words, depth_is_wild(d), depth_is_large(d), wild_seq);
     X0[p] = d;
     X1[p] = dirichlet ? d : 0.0f;
     M[p] = (uint32_t)right | ((uint32_t)down << 8) | (dirichlet ? kMetaDirichlet : 0u);
@@ -360,7 +361,8 @@ __device__ __forceinline__ void prepare4_bgr_px(RTDD_PREPARE_PARAMS(bgr, bgrPitc
         x1v[i] = dirichlet ? d[i] : 0.0f;
         mv[i] = (uint32_t)right | ((uint32_t)down << 8) | (dirichlet ? kMetaDirichlet : 0u);
     }
-    if (depth_is_wild(d[0]) || depth_is_wild(d[1]) || depth_is_wild(d[2]) || depth_is_wild(d[3])) sync_words[kSyncWild] = wild_seq;
+    raise_depth_words(sync_words, depth_is_wild(d[0]) || depth_is_wild(d[1]) || depth_is_wild(d[2]) || depth_is_wild(d[3]),
+                      depth_is_large(d[0]) || depth_is_large(d[1]) || depth_is_large(d[2]) || depth_is_large(d[3]), wild_seq);
     const size_t p = (size_t)y * ip + x0;
     *(float4 *)(X0 + p) = make_float4(x0v[0], x0v[1], x0v[2], x0v[3]);
     *(float4 *)(X1 + p) = make_float4(x1v[0], x1v[1], x1v[2], x1v[3]);

@@ -118,7 +118,10 @@ __global__ __launch_bounds__(NT, (NT >= 1024 || G <= 3 ? 4 : G <= 4 ? 3 : 2)) vo
 
     // ---- load the extended tile once: every load is issued BEFORE the weight table is staged in LDS and the barrier behind it, so
     // that a launch pays one memory round trip, not two in a row (launch-per-block: 125 launches per 1000 sweeps at 4K) ------------
-    const int wild_word = load_wild_word(sync_words);     // (persist_sync.hpp kSyncWild: in flight with the tile)
+    // (persist_sync.hpp kSyncWild: in flight with the tile.  The persistent launch reads kSyncLarge, the word behind it, in the same load)
+    int wild_word, large_word = 0;
+    if constexpr (PERSIST) { const int2 w = load_wild_and_large_words(sync_words); wild_word = w.x; large_word = w.y; }
+    else wild_word = load_wild_word(sync_words);
     float4 vxr[G], vpr[G];
     uint4 mr[G], mup = make_uint4(0, 0, 0, 0);
 #pragma unroll
@@ -203,6 +206,18 @@ __global__ __launch_bounds__(NT, (NT >= 1024 || G <= 3 ? 4 : G <= 4 ? 3 : 2)) vo
     // before their counter is known, fetching counter and rows in one go, s_setprio feedback for lagging waves, a half-sweep
     // stagger between groups of four waves, a wave-level (barrier-free) hand-off between workgroups, and a "zebra" row order (even
     // waves top-down, odd waves bottom-up, every edge row published as soon as it is computed and fetched a step ahead).
+    // SCALED MODE (persistent launches).  A wave whose sweeps keep meeting tiny numerators -- free pixels enclosed by label-0 strokes, which
+    // decay into the denormals and stay there -- pays the 3-operation divide, the test and div_tiny in every such row group of every sweep,
+    // and every tile of the grid waits for the slowest wave at the next exchange.  Such a wave switches, at a block boundary, to sweeps
+    // that divide EVERY pixel by div_scaled (sweep_common.hpp): seven operations where the fast path has 4.75, no test, no branch, the
+    // same bits.  It stays there to the end of the launch: the form is valid for every numerator the solve can hold, and the pockets that
+    // cause it persist.  Not in a solve whose input holds a depth of 2^32 or more (kSyncLarge), and never for a wave of the IEEE variant.
+    // ONE wave-uniform scalar holds it all: bit 0 the wave is in scaled mode, bit 1 it may never enter it (kSyncLarge), bit 2 a fast sweep
+    // of the wave took its tiny branch (set inside that branch: sweep_tile_sweeps.inc).  The wave enters the mode at a block boundary where
+    // the word is exactly kMetTiny; in the mode no fast sweep runs, so the word stays kScaled.
+    constexpr int kScaled = 1, kNeverScaled = 2, kMetTiny = 4;
+    int tiny_state = PERSIST && large_word == wild_seq ? kNeverScaled : 0;
+    using DivScaled = std::integral_constant<int, 2>;
 #include "sweep_tile_sweeps.inc"      // publish / await / sweep lambdas
     // (the divide variant is chosen per wave; the neighbour handshake above does not care which one a wave runs)
     int s = 0, blk = 0;
@@ -231,7 +246,9 @@ __global__ __launch_bounds__(NT, (NT >= 1024 || G <= 3 ? 4 : G <= 4 ? 3 : 2)) vo
             // second for every other wave.  As an if / else inside the block loop the compiler kept the tile as it was at the top of the
             // block alive through the first variant's sweeps (the second's input, as far as it could tell), ran those on a copy, and
             // every block paid 24 v_mov_b64 of the whole tile, 12 in front of the sweeps and 12 behind the exchange.
-            const int s_fast = wave_unsafe ? s : s_end;
+            // ... and a third between them, which takes every sweep of a wave in scaled mode; the other two are then empty for it.
+            const bool scaled = (tiny_state & kScaled) != 0;
+            const int s_fast = (wave_unsafe | scaled) ? s : s_end;
             for (; s + 1 < s_fast; s += 2) {
                 sweep(a, b, s, std::true_type{}, false, P0{});
                 sweep(b, a, s + 1, std::true_type{}, s + 2 >= s_end, P1{});
@@ -239,6 +256,19 @@ __global__ __launch_bounds__(NT, (NT >= 1024 || G <= 3 ? 4 : G <= 4 ? 3 : 2)) vo
             if (s < s_fast) { sweep(a, b, s, std::true_type{}, true, P0{}); s++; odd = true; }
             // (the odd sweep that ends a tail block is the first half of a pair here, not a sweep of its own behind the loop: with one the
             // tiles of two rows per thread kept x_{k-1} in different registers in the sweeps and at the exchange, and moved it at every block)
+            // (no instruction: between the loops the two-row tiles' rows pass through one statement as four consecutive registers each, where
+            // the halo loads want them.  With three loops their allocation otherwise kept the tile in other registers during the sweeps
+            // and moved all of it around every exchange -- tests/test_isa_exchange.py.  The scaled sweep ends with the same statement for its two rows)
+            if constexpr (G == 2) asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(b[0]), "+v"(b[1]));
+            const int s_scaled = scaled ? s_end : s;
+            while (s < s_scaled) {                   // (its odd tail inside the pair, like the loop below and for the same reason)
+                const bool single = s + 1 >= s_end;
+                sweep(a, b, s, DivScaled{}, single, P0{});
+                if (single) { s++; odd = true; break; }
+                sweep(b, a, s + 1, DivScaled{}, s + 2 >= s_end, P1{});
+                s += 2;
+            }
+            if constexpr (G == 2) asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(b[0]), "+v"(b[1]));
             while (s < s_end) {
                 const bool single = s + 1 >= s_end;
                 sweep(a, b, s, std::false_type{}, single, P0{});
@@ -249,6 +279,14 @@ __global__ __launch_bounds__(NT, (NT >= 1024 || G <= 3 ? 4 : G <= 4 ? 3 : 2)) vo
         }
         if (!PERSIST || s >= nsweeps) break;
         RTDD_XT(0);
+        if constexpr (PERSIST) {
+            // The block just done met tiny numerators: scaled mode from the next block on.  Once per wave and launch; one lane counts it
+            // (persist_sync.hpp kSyncScaled: how a test knows that the mode was entered -- nothing else reads the word).
+            if (__builtin_expect(tiny_state == kMetTiny, 0)) {
+                tiny_state = kScaled;
+                if ((tid & 63) == 0) __hip_atomic_fetch_add(&sync_words[kSyncScaled], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
 
         // ---- persistent mode: refresh the halo from the neighbours (block_sweeps is even here, so a = newest) ----
         // Protocol: persist_sync.hpp (write-through payload stores, every storing wave drains, barrier, then exchange_wait()).

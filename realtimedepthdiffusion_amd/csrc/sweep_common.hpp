@@ -137,6 +137,25 @@ __device__ __forceinline__ float div_tiny(float n, float d, float y) {
     return __builtin_fmaf(R, y * down, qd);
 }
 
+// div_tiny with the scale a CONSTANT, 2^64 in every lane: the quotient of ANY numerator with |n| < 2^64 (zero and the denormals included;
+// d normal, y = RN(1/d), the quotient a bounded mean as above), rounded once.  No test in front of it, no fast attempt, no select:
+//   * |n| < 2^-100: operation for operation what div_tiny does in a tiny lane, proven there;
+//   * an ordinary numerator: n * 2^64 is exact (this is where |n| < 2^64 is needed: it must not overflow), N * y rounds to 24 bits and its
+//     multiplication by 2^-64 is exact wherever the quotient is normal, so qd IS div_tail's q0, R is 2^64 times div_tail's remainder --
+//     exact, the same argument -- and the last fma rounds qd + R * y / 2^64 = q0 + r * y once: Markstein's step itself;
+//   * in between (a quotient in or next to the denormals from a numerator of 2^-100 or more) it is div_tiny's argument again: the first
+//     quotient lies on the quotient's own grid, the remainder against it is exact, the last fma is the only rounding that sees the grid.
+// Seven full-rate operations, the constants literals of the multiplications.  Who may use it: the persistent sweep's waves in scaled mode
+// (sweep_blocked.hip), in a solve whose input holds no depth of 2^32 or more (persist_sync.hpp kSyncLarge, where the bound on the numerator
+// is derived).  Restated in C and checked against the IEEE divide in tests/test_div_scaled_cpu.py, on gfx950 by
+// scripts/ubench/div_scaled_exhaustive.hip.
+__device__ __forceinline__ float div_scaled(float n, float d, float y) {
+    const float N = n * 0x1p64f;
+    const float qd = (N * y) * 0x1p-64f;
+    const float R = __builtin_fmaf(-d, qd * 0x1p64f, N);
+    return __builtin_fmaf(R, y * 0x1p-64f, qd);
+}
+
 // RN(1/d) for a normal d with a normal reciprocal: v_rcp_f32 (1 ulp) + one Newton step.  Equal to the IEEE quotient 1.0f/d for
 // EVERY such f32 (all 4 227 858 434 of them checked on the GPU, scripts/ubench/rcp_exhaustive.hip, profiles/r01_rcp_exhaustive.log):
 // 3 VALU ops instead of the 11 of the full divide, in the per-launch setup of every pixel.

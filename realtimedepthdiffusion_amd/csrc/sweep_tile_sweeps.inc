@@ -1,6 +1,6 @@
 // sweep_tile_sweeps.inc -- included INSIDE the body of k_sweep_blocked (sweep_blocked.hip): the per-wave publish / await of edge rows
 // through LDS and ONE sweep of the register-resident tile, as lambdas over the tile's registers.
-// Expects in scope: PERSIST (constexpr bool), CONTRACT, G, LX, edge[], published[], dead_s, sync_words, omegas, gamma, tid, lx, tr, ntr,
+// Expects in scope: PERSIST (constexpr bool), tiny_state and kMetTiny (int: the bit a fast sweep of a persistent wave sets when it takes its tiny branch), CONTRACT, G, LX, edge[], published[], dead_s, sync_words, omegas, gamma, tid, lx, tr, ntr,
 // bx, by, gx and the tile registers of sweep_tile_setup.inc.
     constexpr uint32_t kTinyT = 2u * 0x0D800000u - 1u;          // bits(2^-100) = 27 << 23
     const int prev4 = (((int)threadIdx.x + 63) & 63) * 4;       // horizontal neighbours across lanes by ds_bpermute_b32, issued a group ahead (sweep_common.hpp: why not DPP)
@@ -51,7 +51,10 @@
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     };
     auto sweep = [&](f4r (&cur)[G], f4r (&oth)[G], int s, auto fast, bool last_of_block, auto parity) {
-        constexpr bool FAST = decltype(fast)::value;
+        // `fast`: std::false_type = the IEEE divide and explicit absent neighbours, std::true_type = the 3-operation divide with the tiny test
+        // behind it, DivScaled = every quotient by div_scaled (a persistent wave in scaled mode, sweep_blocked.hip): no test, no branch
+        constexpr int MODE = (int)decltype(fast)::value;
+        constexpr bool FAST = MODE == 1, SCALED = MODE == 2, IEEE = MODE == 0;
         constexpr int buf = decltype(parity)::value;         // = s & 1
         RTDD_TL(0, s);
         // The first / last thread row of the tile has no row above / below in LDS: it reads its OWN published row instead (any
@@ -66,13 +69,13 @@
         // border, which the reference skips, or discarded halo.
         auto shifts = [&](int g) {
             xl0[g] = lds_from_prev(prev4, wr[g][3] * cur[g][3]); xr3[g] = lds_from_next(prev4, cur[g][0]);
-            if (!FAST) { xl0[g] = lx == 0 ? 0.0f : xl0[g]; xr3[g] = lx == LX - 1 ? 0.0f : xr3[g]; }
+            if (IEEE) { xl0[g] = lx == 0 ? 0.0f : xl0[g]; xr3[g] = lx == LX - 1 ? 0.0f : xr3[g]; }
         };
         shifts(0); if (G > 1) shifts(G - 1);                 // in flight during the wait for the neighbouring waves' rows
         await(s);
         float4 up4 = edge[buf][tr > 0 ? tr - 1 : 0][G > 1 && tr > 0 ? 1 : 0][lx];
         float4 dn4 = edge[buf][tr < ntr - 1 ? tr + 1 : tr][G == 1 || tr < ntr - 1 ? 0 : 1][lx];
-        if (!FAST) { if (tr == 0) up4 = make_float4(0, 0, 0, 0); if (tr == ntr - 1) dn4 = make_float4(0, 0, 0, 0); }
+        if (IEEE) { if (tr == 0) up4 = make_float4(0, 0, 0, 0); if (tr == ntr - 1) dn4 = make_float4(0, 0, 0, 0); }
         const float up[4] = {up4.x, up4.y, up4.z, up4.w}, dn[4] = {dn4.x, dn4.y, dn4.z, dn4.w};
         RTDD_TL_ROWS_IN_HAND(s);
         // omega and gamma in VGPRs: an fma with an SGPR operand issues at 4.3 cycles per wave-instruction, with three VGPRs at 3.1
@@ -103,6 +106,7 @@
                 uint32_t t[4];
 #pragma unroll
                 for (int i = 0; i < 4; i++) {
+                    if (SCALED) { q[g][i] = div_scaled(wsum(g, i), cnt[g][i], rcp[g][i]); continue; }
                     const float sum = sums[g][i] = wsum(g, i);
                     if (FAST) { q[g][i] = div_tail(sum, cnt[g][i], rcp[g][i]); t[i] = (__float_as_uint(sum) << 1) + 0xFFFFFFFFu; }
                     else q[g][i] = sum / cnt[g][i];
@@ -115,6 +119,7 @@
                 // The persistent tiles have the registers to keep a row's four sums up to here; the launch-per-block tiles sit at their cap
                 // of 128 and form each sum again where it is used, as the redo always did.
                 auto sum_of = [&](int g, int i) { return PERSIST ? sums[g][i] : wsum(g, i); };
+                if constexpr (PERSIST) tiny_state |= kMetTiny;      // (wave-uniform, a scalar: the wave may enter scaled mode at the next block boundary)
 #pragma unroll
                 for (int g = 0; g < G; g++) {
                     if (!pick(g)) continue;
@@ -159,6 +164,7 @@
         // otherwise keep x_{k-1} in one place during the sweeps and in another at the halo exchange, whose 16-byte loads need the row
         // consecutive, and move it there and back at every exchange -- tests/test_isa_exchange.py)
         if constexpr (PERSIST && G == 1) asm volatile("" : "+v"(oth[0]));
+        if constexpr (PERSIST && G == 2 && SCALED) asm volatile("" : "+v"(oth[0]), "+v"(oth[1]));      // (the two-row tiles in scaled mode: sweep_blocked.hip, between the loops)
         RTDD_TL(3, s);
     };
 

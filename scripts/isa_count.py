@@ -10,6 +10,9 @@ How the loop is found: every backward branch of the function closes a loop; from
 FALL-THROUGH path (conditional branches not taken -- the waiting loops, the full-divide path and the time-out reports all hang off
 taken branches, by construction: __builtin_expect -- unconditional branches followed) until the walk reaches a branch back to the loop's
 head.  The sweep pair is the loop whose fall-through path holds exactly 24 v_med3_f32 (12 pixels x 2 sweeps) and no v_div_scale_f32.
+A persistent instantiation has a second such loop, the sweep pair of a wave in scaled mode (csrc/sweep_common.hpp div_scaled): it is told
+apart by its multiplications by the literal 2^64 and is not the loop that is counted -- it belongs to the exchange's `region`, like the
+full-divide variant's loops.
 """
 import glob
 import os
@@ -49,6 +52,14 @@ def disassemble(obj):
     return funcs
 
 
+SCALE_LITERAL = "0x5f800000"                  # bits(2^64): only div_scaled / div_tiny multiply by it
+
+
+def is_fast_pair(path, pixels):
+    """The fall-through path of the FAST sweep pair of a thread of `pixels` pixels: one clamp per pixel and sweep, no full divide, no scaled divide."""
+    return sum(t.startswith("v_med3_f32") for t in path) == 2 * pixels and not any(t.startswith("v_div_scale") or SCALE_LITERAL in t for t in path)
+
+
 def fallthrough_loops(instrs):
     """For every backward branch: the instructions on the fall-through path from its target back to a branch to that target."""
     index = {a: i for i, (a, _, _) in enumerate(instrs)}
@@ -86,8 +97,7 @@ def sweep_pair(obj=None, kernel=HOT_KERNEL):
         raise RuntimeError(f"{kernel}: {len(names)} functions match in {obj}")
     found = []
     for head, path in fallthrough_loops(funcs[names[0]]):
-        med3 = sum(t.startswith("v_med3_f32") for t in path)
-        if med3 == 2 * PIXELS_PER_THREAD and not any(t.startswith("v_div_scale") for t in path):
+        if is_fast_pair(path, PIXELS_PER_THREAD):
             found.append(path)
     if len(found) != 1:
         raise RuntimeError(f"{kernel}: expected ONE loop with 24 v_med3_f32 and no full divide on its fall-through path, found {len(found)}")
@@ -157,7 +167,7 @@ def exchange_region(instrs, G):
     index = {a: i for i, (a, _, _) in enumerate(instrs)}
     head = None
     for h, path in fallthrough_loops(instrs):
-        if sum(t.startswith("v_med3_f32") for t in path) == 8 * G and not any(t.startswith("v_div_scale") for t in path):
+        if is_fast_pair(path, 4 * G):
             if head is not None:
                 raise RuntimeError("two sweep-pair loops without a full divide")
             head = index[h]
