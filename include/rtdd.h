@@ -241,10 +241,14 @@ int rtdd_solve_ex(rtdd_ctx *ctx, float *depth, size_t depthPitch,
 int rtdd_last_solve_info(rtdd_ctx *ctx, rtdd_solve_info *info);
 
 /* Read only, for tests and diagnosis: how many waves of this context's persistent Jacobi launches have entered SCALED MODE since the
- * context was created.  A wave of a persistent launch (RTDD_OPT_PERSISTENT) whose sweeps keep meeting numerators below 2^-100 -- free
- * pixels enclosed by label-0 strokes decay that far -- divides every pixel by a uniformly scaled form of the same correctly rounded
- * divide from the next halo exchange on; results are the same bits, and nothing switches the mode off.  It is not entered in a solve whose
- * input holds a depth of 2^32 or more in magnitude, and never by a launch per block of sweeps.  Synchronises (rtdd_ctx_synchronize).
+ * context was created.  A wave in the mode divides every pixel by a uniformly scaled form of the same correctly rounded divide; results
+ * are the same bits, and nothing switches the mode off before the launch ends.  In a persistent launch (RTDD_OPT_PERSISTENT) of the tile
+ * a 1080p solve runs (tile 4: 128 x 96 pixels, 1024 threads) every wave that may enter the mode enters it before its first sweep, and the count
+ * grows by that number of waves with every such launch (each workgroup adds its waves in one step).  In the other persistent tiles a
+ * wave enters at the halo exchange behind a block of sweeps that met numerators below 2^-100 -- free pixels enclosed by label-0 strokes
+ * decay that far -- and adds 1 there.  The mode is not entered by a wave that holds a pixel with a denormal divisor, nor in a solve whose
+ * input holds a depth of 2^32 or more in magnitude, and never by a launch per block of sweeps or a single-tile launch.  Synchronises
+ * (rtdd_ctx_synchronize).
  * (A function and not a read-only rtdd_option: found by symbol, no version bump; the next bump of RTDD_VERSION should cover it.) */
 int rtdd_scaled_mode_waves(rtdd_ctx *ctx, int *waves);
 

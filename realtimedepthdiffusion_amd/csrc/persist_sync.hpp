@@ -23,11 +23,13 @@
 //                    and explicit absent neighbours (sweep_common.hpp div_tail).  Never cleared: sequence numbers do not repeat.
 //   [kSyncLarge]     sequence number of the most recent solve whose k_prepare met a depth of 2^32 or more in magnitude (or not finite: every
 //                    wild depth is large too).  Raised where kSyncWild is raised and in the same way.  The persistent sweep compares it with
-//                    its solve's number: when equal, no wave of the launch enters SCALED MODE (sweep_common.hpp div_scaled, whose numerator
+//                    its solve's number: when equal, no wave of the launch enters SCALED MODE (sweep_common.hpp div_scaled4 / div_scaled, whose numerator
 //                    times 2^64 must not overflow).  The word behind kSyncWild, so that the kernel reads both with one 8-byte load.
-//   [kSyncScaled]    how many waves have entered scaled mode over the life of the context: one lane of a wave adds 1 when the wave
-//                    enters it (once per wave and launch, on the cold path).  Read back by rtdd_scaled_mode_waves, for the tests: nothing
-//                    in the product depends on it.
+//   [kSyncScaled]    how many waves have entered scaled mode over the life of the context.  Waves that enter at the start of a launch
+//                    (sweep_blocked.hip kFromStart: every eligible wave of a 1080p launch, 4032 of them) count themselves in LDS, and one
+//                    lane per WORKGROUP adds their number; a wave that enters on demand, at a block boundary, adds 1 from one lane (once
+//                    per wave and launch, on the cold path).  Read back by rtdd_scaled_mode_waves, for the tests: nothing in the product
+//                    depends on it.
 //   [kSyncFlags ..]  one block counter per tile.  Monotonic over the life of the context: launch L's workgroups publish base_L + block
 //                    number, base_L handed in by the host (heal.cpp prepare_persistent_launch), so nothing is zeroed between launches.
 #pragma once
@@ -57,7 +59,7 @@ constexpr unsigned long long kArrivalPollLimit = 150000ull;        // 1.5 ms
 constexpr float kWildDepth = 0x1p100f;
 // A depth of this magnitude or more (or a NaN) makes k_prepare raise kSyncLarge as well.  By the same argument an iterate that starts below
 // it stays within a small multiple of 2^32, and a sum of four of them (weights <= 1) below 2^64 with about 2^30 to spare: the numerator
-// div_scaled multiplies by 2^64 stays finite.  Depth maps in [0, 255] never raise the word.
+// div_scaled4 and div_scaled multiply by 2^64 stays finite.  Depth maps in [0, 255] never raise the word.
 constexpr float kLargeDepth = 0x1p32f;
 
 #ifdef __HIPCC__

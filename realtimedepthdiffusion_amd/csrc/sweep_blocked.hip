@@ -81,6 +81,12 @@ __global__ __launch_bounds__(NT, (NT >= 1024 || G <= 3 ? 4 : G <= 4 ? 3 : 2)) vo
     //       4 pixels lie left of `cols`, bit 19: fewer than 4 do (the group straddles the image's right edge)
     //   .z  byte offset from sync_words of the neighbour flag this thread polls, -1 = none (persist_sync.hpp exchange_poll_offset)
     __shared__ int4 xrec[PERSIST ? NT : 1];
+    // The persistent tile whose waves enter scaled mode at the start (SCALED MODE, below), and their count of themselves:
+    // (waves that have reported << 16) | waves that entered.  No other instantiation touches the word, so none of them holds it.
+    // (static: the generic lambdas of sweep_tile_sweeps.inc name it in a dependent condition, and an automatic constexpr there becomes one
+    // more capture of every closure -- which alone changed the code of the one- and two-row tiles, setup included)
+    static constexpr bool kFromStart = PERSIST && LX == 32 && NT == 1024 && G == 3;
+    __shared__ int entered_s;
 
     // (gx, gy) = the grid of tiles.  xcd_tiles > 0 (every multi-tile launch): a 1-D launch of 8 * xcd_tiles workgroups in which
     // workgroup p -- dispatched to XCD p % 8 -- takes tile number (p % 8) * xcd_tiles + p / 8, so that each XCD owns a run
@@ -138,7 +144,7 @@ __global__ __launch_bounds__(NT, (NT >= 1024 || G <= 3 ? 4 : G <= 4 ? 3 : 2)) vo
     if (colok && y0 - 1 >= 0 && y0 < rows) mup = *(const uint4 *)(M + (size_t)(y0 - 1) * ip + x0);     // the row above the block: its down-weights
     for (int i = tid; i < 257; i += (int)blockDim.x) lut[i] = lut_g[i];
     if (tid <= NT / 64) published[tid] = 0;
-    if (tid == 0) { dead_s = PERSIST && __hip_atomic_load(&sync_words[kSyncStatus], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0; }
+    if (tid == 0) { dead_s = PERSIST && __hip_atomic_load(&sync_words[kSyncStatus], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0; if constexpr (kFromStart) entered_s = 0; }
     const int ntiles = gx * gy, tile_base = (int)blockIdx.z * ntiles, tile_id = by * gx + bx;
     if (PERSIST) {
         // Arrival (persist_sync.hpp kArrivalPollLimit): the tile's flag := the launch's base value, then the 8 neighbours' -- while the
@@ -206,17 +212,52 @@ __global__ __launch_bounds__(NT, (NT >= 1024 || G <= 3 ? 4 : G <= 4 ? 3 : 2)) vo
     // before their counter is known, fetching counter and rows in one go, s_setprio feedback for lagging waves, a half-sweep
     // stagger between groups of four waves, a wave-level (barrier-free) hand-off between workgroups, and a "zebra" row order (even
     // waves top-down, odd waves bottom-up, every edge row published as soon as it is computed and fetched a step ahead).
-    // SCALED MODE (persistent launches).  A wave whose sweeps keep meeting tiny numerators -- free pixels enclosed by label-0 strokes, which
-    // decay into the denormals and stay there -- pays the 3-operation divide, the test and div_tiny in every such row group of every sweep,
-    // and every tile of the grid waits for the slowest wave at the next exchange.  Such a wave switches, at a block boundary, to sweeps
-    // that divide EVERY pixel by div_scaled (sweep_common.hpp): seven operations where the fast path has 4.75, no test, no branch, the
-    // same bits.  It stays there to the end of the launch: the form is valid for every numerator the solve can hold, and the pockets that
-    // cause it persist.  Not in a solve whose input holds a depth of 2^32 or more (kSyncLarge), and never for a wave of the IEEE variant.
+    // SCALED MODE (persistent launches).  The fast sweep pays for its 3-operation divide with the tiny test behind it -- a v_lshl_add_u32 per
+    // pixel and a v_min3_u32 per two, all half rate, a ballot and a branch per row group -- and, where the test fires (free pixels enclosed
+    // by label-0 strokes decay into the denormals and stay there), with div_tiny on top; every tile of the grid waits for the slowest
+    // wave at the next exchange.  A wave in scaled mode divides EVERY pixel by one uniformly scaled form, valid for every numerator the
+    // solve can hold: no test, no branch, no sums kept alive, the same bits.  It stays in the mode to the end of the launch.
+    // Who enters, and when:
+    //   * never: a wave of the IEEE variant (wave_unsafe: a denormal divisor has no scaled reciprocal), and any wave of a solve whose
+    //     input holds a depth of 2^32 or more (kSyncLarge: n * 2^64 must stay finite) -- these run the fast pair, as every wave of a
+    //     launch-per-block instantiation does;
+    //   * AT THE START, here behind the tile setup: every other wave of the from-start tile (kFromStart).  It never runs a fast sweep.  Its
+    //     divide is div_scaled4 (sweep_common.hpp), four full-rate operations where the fast path has 4.75: the registers cnt[] / rcp[]
+    //     hold D = d * 2^64 and ys = y * 2^-64, two exact multiplications per pixel made once, in the loop right below;
+    //   * on demand: in the other tiles, a wave whose block of fast sweeps took the tiny branch, at that block's boundary.  Its divide is
+    //     the seven-operation div_scaled on the unconverted constants: those instantiations are instruction for instruction what they were.
+    // kFromStart is a property of the tile: <32, 1024, 3>, the 1080p tile, the ONE tile that was measured from the start (-3.9 % per step,
+    // EXPERIMENTS.md "Scaled mode from sweep 0").  Every other tile stays on demand because nothing was measured for it, not because it is
+    // known to lose: the other three-row tiles share this tile's loop and may well gain the same, the one- and two-row tiles are
+    // suspected of being bound by the latency of a sweep's dependent chain (k_sweep_col lost with a longer chain).  With the four-operation
+    // divide and the conversion at the block boundary built into the on-demand tiles as well, the two benchmark lines that run tile 9 --
+    // in which no wave enters the mode -- read 1 % slower than the parent, so those tiles keep the parent's code.
     // ONE wave-uniform scalar holds it all: bit 0 the wave is in scaled mode, bit 1 it may never enter it (kSyncLarge), bit 2 a fast sweep
-    // of the wave took its tiny branch (set inside that branch: sweep_tile_sweeps.inc).  The wave enters the mode at a block boundary where
+    // of the wave took its tiny branch (set inside that branch: sweep_tile_sweeps.inc).  On demand the wave enters at a block boundary where
     // the word is exactly kMetTiny; in the mode no fast sweep runs, so the word stays kScaled.
     constexpr int kScaled = 1, kNeverScaled = 2, kMetTiny = 4;
     int tiny_state = PERSIST && large_word == wild_seq ? kNeverScaled : 0;
+    if constexpr (kFromStart) {
+        const bool enters = (tiny_state == 0) & !wave_unsafe;        // (wave-uniform)
+        if (enters) {
+            tiny_state = kScaled;
+#pragma unroll
+            for (int g = 0; g < G; g++)
+#pragma unroll
+                for (int i = 0; i < 4; i++) { cnt[g][i] *= 0x1p64f; rcp[g][i] *= 0x1p-64f; }      // D and ys, both exact
+        }
+        // The count behind rtdd_scaled_mode_waves (persist_sync.hpp kSyncScaled) stays "waves that entered", but 4032 waves adding 1 to one
+        // word at the top of every 1080p launch would be a hot spot of their own: the waves of a workgroup count themselves in LDS, and the
+        // one that reports last adds the workgroup's number -- one add per workgroup, no barrier.
+        // (blockDim.x is a multiple of 64 in every launch of this kernel -- whole waves, as `nwv` in sweep_tile_sweeps.inc assumes too)
+        if ((tid & 63) == 0) {
+            const int before = __hip_atomic_fetch_add(&entered_s, 0x10000 + (enters ? 1 : 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if ((before >> 16) == ((int)blockDim.x >> 6) - 1) {
+                const int n_entered = (before & 0xFFFF) + (enters ? 1 : 0);
+                if (n_entered) __hip_atomic_fetch_add(&sync_words[kSyncScaled], n_entered, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
     using DivScaled = std::integral_constant<int, 2>;
 #include "sweep_tile_sweeps.inc"      // publish / await / sweep lambdas
     // (the divide variant is chosen per wave; the neighbour handshake above does not care which one a wave runs)
@@ -261,12 +302,22 @@ __global__ __launch_bounds__(NT, (NT >= 1024 || G <= 3 ? 4 : G <= 4 ? 3 : 2)) vo
             // and moved all of it around every exchange -- tests/test_isa_exchange.py.  The scaled sweep ends with the same statement for its two rows)
             if constexpr (G == 2) asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(b[0]), "+v"(b[1]));
             const int s_scaled = scaled ? s_end : s;
-            while (s < s_scaled) {                   // (its odd tail inside the pair, like the loop below and for the same reason)
-                const bool single = s + 1 >= s_end;
-                sweep(a, b, s, DivScaled{}, single, P0{});
-                if (single) { s++; odd = true; break; }
-                sweep(b, a, s + 1, DivScaled{}, s + 2 >= s_end, P1{});
-                s += 2;
+            if constexpr (kFromStart) {
+                // (where this is the loop that nearly every wave runs it has the fast loop's shape, pairs and then the odd sweep of a tail
+                // block: with the tail inside the pair this tile ran each pair on a copy of the tile and moved it back, 50 v_mov a pair)
+                for (; s + 1 < s_scaled; s += 2) {
+                    sweep(a, b, s, DivScaled{}, false, P0{});
+                    sweep(b, a, s + 1, DivScaled{}, s + 2 >= s_end, P1{});
+                }
+                if (s < s_scaled) { sweep(a, b, s, DivScaled{}, true, P0{}); s++; odd = true; }
+            } else {
+                while (s < s_scaled) {               // (its odd tail inside the pair, like the loop below and for the same reason)
+                    const bool single = s + 1 >= s_end;
+                    sweep(a, b, s, DivScaled{}, single, P0{});
+                    if (single) { s++; odd = true; break; }
+                    sweep(b, a, s + 1, DivScaled{}, s + 2 >= s_end, P1{});
+                    s += 2;
+                }
             }
             if constexpr (G == 2) asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(b[0]), "+v"(b[1]));
             while (s < s_end) {
@@ -279,8 +330,9 @@ __global__ __launch_bounds__(NT, (NT >= 1024 || G <= 3 ? 4 : G <= 4 ? 3 : 2)) vo
         }
         if (!PERSIST || s >= nsweeps) break;
         RTDD_XT(0);
-        if constexpr (PERSIST) {
-            // The block just done met tiny numerators: scaled mode from the next block on.  Once per wave and launch; one lane counts it
+        if constexpr (PERSIST && !kFromStart) {
+            // The block just done met tiny numerators: scaled mode from the next block on.  Once per wave and launch (never in the
+            // from-start tile, whose eligible waves are in the mode already); one lane counts it
             // (persist_sync.hpp kSyncScaled: how a test knows that the mode was entered -- nothing else reads the word).
             if (__builtin_expect(tiny_state == kMetTiny, 0)) {
                 tiny_state = kScaled;

@@ -156,6 +156,40 @@ __device__ __forceinline__ float div_scaled(float n, float d, float y) {
     return __builtin_fmaf(R, y * 0x1p-64f, qd);
 }
 
+// div_scaled in FOUR operations, with the two per-pixel constants stored in scaled form: D = d * 2^64 in place of the divisor and
+// ys = y * 2^-64 in place of its reciprocal.  It replaces div_scaled in the tile that enters scaled mode at the start (sweep_blocked.hip
+// kFromStart, sweep_tile_sweeps.inc MODE == 2); the tiles that enter on demand keep div_scaled, above, which is also the form this one is
+// derived from and checked against (tests/test_div_scaled_cpu.py).
+//      N  = n * 2^64               exact for |n| < 2^64
+//      qd = N * ys                 = RN(n * y): ONE rounding, to 24 bits where the quotient is normal and to the 2^-149 grid where it is not
+//      R  = fma(-D, qd, N)         = 2^64 * (n - d * qd)
+//      q  = fma(R, ys, qd)         = RN(qd + (n - d * qd) * y): the only rounding that sees the result's grid
+// Domain: |n| < 2^64 (persist_sync.hpp kSyncLarge), d normal and <= 4, y = RN(1/d), the quotient a bounded mean.  Then both conversions
+// are exact and stay normal: D <= 2^66, and 2^-66 <= ys <= 2^62 because 1/4 <= y <= 2^126.  They are made once, behind the tile setup, where the
+// wave enters scaled mode (sweep_blocked.hip); a wave of the IEEE variant (a denormal divisor) never converts.
+// Against div_scaled, operation by operation: N is the same number.  -D * qd is, exactly, -d * (qd * 2^64) -- div_scaled's product, whose
+// factor qd * 2^64 is exact -- so R is the same fma of the same three real numbers GIVEN THE SAME qd; likewise the last fma (ys is
+// div_scaled's y * 2^-64, exact).  The one difference is qd: div_scaled rounds N * y to 24 bits and then, multiplying by 2^-64, to the
+// quotient's grid (twice where the quotient is denormal); here N * ys is the real number n * y rounded to that grid once.
+//   * the quotient normal (every ordinary numerator, |n| >= 2^-100 included): the grid IS 24 bits, both forms give qd = RN(n * y) = div_tail's
+//     q0, R = 2^64 * div_tail's r, exact by the usual argument, and the last fma is Markstein's: the same bits as div_tail and div_scaled;
+//   * the quotient denormal or next to it: div_tiny's argument needs of qd only that it lies ON the quotient's grid and is one of the two
+//     grid points next to N / d, so that R = N - d * Qd (Qd = qd * 2^64, a multiple of the step g with at most 24 bits) is a multiple of
+//     ulp(d) * g below 2^24 * ulp(d) * g and the fma returns it exactly.  Here n * y is off n / d by y's rounding alone, 2^-24 of a
+//     quotient of fewer than 2^23 steps: under half a step; the single rounding to the grid adds at most half a step.  So |Qd - N / d| < g
+//     for EVERY denormal quotient -- the double rounding's extra half ulp, which left div_tiny's argument the top denormal binade as a
+//     corner for the exhaustive run, is gone.  The two forms can differ only in WHICH neighbour they start from; the last fma adds the
+//     exact remainder over d to either and rounds the same real number, n / d up to 2^-24 of a step, once.
+// A zero numerator of either sign gives +0, as div_tail does.  Four full-rate operations, the 2^64 a literal of the first multiplication
+// (scripts/isa_count.py finds the scaled sweep pair by it); no register more than div_tail's three operands.  Restated in C and checked
+// against the IEEE divide, div_scaled and div_tail in tests/test_div_scaled4_cpu.py; on gfx950 by scripts/ubench/div_scaled4_exhaustive.hip.
+__device__ __forceinline__ float div_scaled4(float n, float D, float ys) {
+    const float N = n * 0x1p64f;
+    const float qd = N * ys;
+    const float R = __builtin_fmaf(-D, qd, N);
+    return __builtin_fmaf(R, ys, qd);
+}
+
 // RN(1/d) for a normal d with a normal reciprocal: v_rcp_f32 (1 ulp) + one Newton step.  Equal to the IEEE quotient 1.0f/d for
 // EVERY such f32 (all 4 227 858 434 of them checked on the GPU, scripts/ubench/rcp_exhaustive.hip, profiles/r01_rcp_exhaustive.log):
 // 3 VALU ops instead of the 11 of the full divide, in the per-launch setup of every pixel.

@@ -1,6 +1,6 @@
 // sweep_tile_sweeps.inc -- included INSIDE the body of k_sweep_blocked (sweep_blocked.hip): the per-wave publish / await of edge rows
 // through LDS and ONE sweep of the register-resident tile, as lambdas over the tile's registers.
-// Expects in scope: PERSIST (constexpr bool), tiny_state and kMetTiny (int: the bit a fast sweep of a persistent wave sets when it takes its tiny branch), CONTRACT, G, LX, edge[], published[], dead_s, sync_words, omegas, gamma, tid, lx, tr, ntr,
+// Expects in scope: PERSIST (constexpr bool), tiny_state and kMetTiny (int: the bit a fast sweep of a persistent wave sets when it takes its tiny branch; kFromStart (constexpr bool): a wave in scaled mode holds d * 2^64 / y * 2^-64 in cnt[] / rcp[] and divides by div_scaled4), CONTRACT, G, LX, edge[], published[], dead_s, sync_words, omegas, gamma, tid, lx, tr, ntr,
 // bx, by, gx and the tile registers of sweep_tile_setup.inc.
     constexpr uint32_t kTinyT = 2u * 0x0D800000u - 1u;          // bits(2^-100) = 27 << 23
     const int prev4 = (((int)threadIdx.x + 63) & 63) * 4;       // horizontal neighbours across lanes by ds_bpermute_b32, issued a group ahead (sweep_common.hpp: why not DPP)
@@ -52,7 +52,7 @@
     };
     auto sweep = [&](f4r (&cur)[G], f4r (&oth)[G], int s, auto fast, bool last_of_block, auto parity) {
         // `fast`: std::false_type = the IEEE divide and explicit absent neighbours, std::true_type = the 3-operation divide with the tiny test
-        // behind it, DivScaled = every quotient by div_scaled (a persistent wave in scaled mode, sweep_blocked.hip): no test, no branch
+        // behind it, DivScaled = every quotient by div_scaled4 (the from-start tile, whose cnt[] / rcp[] hold d * 2^64 / y * 2^-64) or div_scaled (the on-demand tiles) -- a persistent wave in scaled mode, sweep_blocked.hip: no test, no branch
         constexpr int MODE = (int)decltype(fast)::value;
         constexpr bool FAST = MODE == 1, SCALED = MODE == 2, IEEE = MODE == 0;
         constexpr int buf = decltype(parity)::value;         // = s & 1
@@ -106,7 +106,8 @@
                 uint32_t t[4];
 #pragma unroll
                 for (int i = 0; i < 4; i++) {
-                    if (SCALED) { q[g][i] = div_scaled(wsum(g, i), cnt[g][i], rcp[g][i]); continue; }
+                    if constexpr (SCALED && kFromStart) { q[g][i] = div_scaled4(wsum(g, i), cnt[g][i], rcp[g][i]); continue; }      // (cnt / rcp hold D / ys)
+                    else if constexpr (SCALED) { q[g][i] = div_scaled(wsum(g, i), cnt[g][i], rcp[g][i]); continue; }
                     const float sum = sums[g][i] = wsum(g, i);
                     if (FAST) { q[g][i] = div_tail(sum, cnt[g][i], rcp[g][i]); t[i] = (__float_as_uint(sum) << 1) + 0xFFFFFFFFu; }
                     else q[g][i] = sum / cnt[g][i];

@@ -10,9 +10,10 @@ How the loop is found: every backward branch of the function closes a loop; from
 FALL-THROUGH path (conditional branches not taken -- the waiting loops, the full-divide path and the time-out reports all hang off
 taken branches, by construction: __builtin_expect -- unconditional branches followed) until the walk reaches a branch back to the loop's
 head.  The sweep pair is the loop whose fall-through path holds exactly 24 v_med3_f32 (12 pixels x 2 sweeps) and no v_div_scale_f32.
-A persistent instantiation has a second such loop, the sweep pair of a wave in scaled mode (csrc/sweep_common.hpp div_scaled): it is told
-apart by its multiplications by the literal 2^64 and is not the loop that is counted -- it belongs to the exchange's `region`, like the
-full-divide variant's loops.
+A persistent instantiation has a second such loop, the sweep pair of a wave in scaled mode (csrc/sweep_common.hpp: div_scaled4 in the from-start tile, the 1080p one, div_scaled in the others): it is told
+apart by its multiplications by the literal 2^64 and is not the loop sweep_pair() counts -- it belongs to the exchange's `region`, like the
+full-divide variant's loops.  scaled_pair() is its census: in the tile that enters the mode at sweep 0 (the 1080p tile) it is the loop the
+waves actually run; in every other persistent tile it finds the seven-operation loop of the on-demand mode.  kernel_resources() reads VGPRs and private segment sizes of the persistent instantiations from the code object's notes.
 """
 import glob
 import os
@@ -52,7 +53,7 @@ def disassemble(obj):
     return funcs
 
 
-SCALE_LITERAL = "0x5f800000"                  # bits(2^64): only div_scaled / div_tiny multiply by it
+SCALE_LITERAL = "0x5f800000"                  # bits(2^64): only the scaled divides multiply by it (div_scaled4 in the from-start tile, div_scaled in the on-demand tiles, div_tiny)
 
 
 def is_fast_pair(path, pixels):
@@ -108,6 +109,62 @@ def sweep_pair(obj=None, kernel=HOT_KERNEL):
     valu = sum(n for k, n in by.items() if k.startswith("v_"))
     return {"valu": valu, "salu": sum(n for k, n in by.items() if k.startswith("s_")), "lds": sum(n for k, n in by.items() if k.startswith("ds_")),
             "instructions": len(path), "per_pixel_sweep": valu / (2.0 * PIXELS_PER_THREAD), "by_mnemonic": dict(sorted(by.items(), key=lambda kv: -kv[1]))}
+
+
+def is_scaled_pair(path, pixels):
+    """The fall-through path of the SCALED sweep pair (a wave in scaled mode, csrc/sweep_common.hpp div_scaled4 / div_scaled): one clamp per pixel and sweep,
+    no full divide, and multiplications by the literal 2^64."""
+    return sum(t.startswith("v_med3_f32") for t in path) == 2 * pixels and not any(t.startswith("v_div_scale") for t in path) and any(SCALE_LITERAL in t for t in path)
+
+
+def scaled_pair(obj=None, kernel=HOT_KERNEL, pixels=PIXELS_PER_THREAD):
+    """Instruction census of the scaled sweep pair of one persistent instantiation, as sweep_pair() gives it for the fast pair, plus
+    'scale_literals' (multiplications by 2^64), 'scratch' (scratch accesses) and 'text' (the instructions themselves)."""
+    if obj is None:
+        obj = os.path.join(ROOT, "realtimedepthdiffusion_amd", "csrc", "sweep_blocked.o")
+        if not os.path.exists(obj):
+            obj = os.path.join(ROOT, "realtimedepthdiffusion_amd", "librtdd.so")
+    funcs = disassemble(obj)
+    names = [n for n in funcs if kernel in n]
+    if len(names) != 1:
+        raise RuntimeError(f"{kernel}: {len(names)} functions match in {obj}")
+    found = [path for head, path in fallthrough_loops(funcs[names[0]]) if is_scaled_pair(path, pixels)]
+    if len(found) != 1:
+        raise RuntimeError(f"{kernel}: expected ONE loop with {2 * pixels} v_med3_f32, no full divide and multiplications by 2^64 on its fall-through path, found {len(found)}")
+    path = found[0]
+    by = {}
+    for t in path:
+        by[t.split()[0]] = by.get(t.split()[0], 0) + 1
+    valu = sum(n for k, n in by.items() if k.startswith("v_"))
+    return {"valu": valu, "salu": sum(n for k, n in by.items() if k.startswith("s_")), "lds": sum(n for k, n in by.items() if k.startswith("ds_")),
+            "instructions": len(path), "per_pixel_sweep": valu / (2.0 * pixels), "scale_literals": sum(SCALE_LITERAL in t for t in path),
+            "scratch": sum(t.startswith(("scratch_", "buffer_load", "buffer_store")) for t in path),
+            "by_mnemonic": dict(sorted(by.items(), key=lambda kv: -kv[1])), "text": path}
+
+
+def kernel_resources(obj=None):
+    """{mangled name: {'vgprs', 'private_segment'}} of the persistent instantiations, from the code object's notes.  (`vgprs` is the
+    kernel's whole register count, AGPRs included: 128 or fewer admit the four waves per SIMD that a 1024-thread workgroup needs; LDS is not looked at.)"""
+    if obj is None:
+        obj = os.path.join(ROOT, "realtimedepthdiffusion_amd", "csrc", "sweep_blocked.o")
+        if not os.path.exists(obj):
+            obj = os.path.join(ROOT, "realtimedepthdiffusion_amd", "librtdd.so")
+    tmp = tempfile.mkdtemp(prefix="isa_count_")
+    try:
+        local = os.path.join(tmp, "x.o")
+        shutil.copy(obj, local)
+        subprocess.check_call([OBJDUMP, "--offloading", local], stdout=subprocess.DEVNULL, cwd=tmp)
+        notes = "\n".join(subprocess.check_output([os.path.join(os.path.dirname(OBJDUMP), "llvm-readelf"), "--notes", d], text=True) for d in sorted(glob.glob(local + ".*gfx950*")))
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    out = {}
+    for block in notes.split("- .agpr_count:")[1:]:
+        name = re.search(r"\.name:\s+(\S+)", block)
+        if not name or not re.search(r"k_sweep_blockedILi\d+ELi\d+ELi\d+ELb[01]ELb1EEE", name.group(1)):
+            continue
+        vgprs = int(re.search(r"\.vgpr_count:\s+(\d+)", block).group(1))
+        out[name.group(1)] = {"vgprs": vgprs, "private_segment": int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", block).group(1))}
+    return out
 
 
 # ---- the halo exchange of the persistent instantiations -------------------------------------------------------------------------
@@ -264,3 +321,6 @@ if __name__ == "__main__":
     c = sweep_pair(*sys.argv[1:2])
     print(json.dumps(c, indent=1))
     print(json.dumps(exchange_census(*sys.argv[1:2]), indent=1))
+    c = scaled_pair(*sys.argv[1:2])
+    del c["text"]
+    print(json.dumps(c, indent=1))
