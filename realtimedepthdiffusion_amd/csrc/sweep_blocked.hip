@@ -30,6 +30,11 @@
 
 namespace rtdd {
 
+// The divide tag of the from-start tile's scaled sweeps (k_sweep_blocked, SCALED MODE): MODE 2 like every scaled sweep's, and with it
+// gamma in the vector register the wave keeps for the launch.
+struct DivScaledFromStart : std::integral_constant<int, 2> {
+    float gamma;
+};
 
 template <bool CONTRACT, bool FAST>
 __device__ __forceinline__ float relax(float xl, float xr, float xu, float xd, float wl, float wr, float wu, float wd,
@@ -261,6 +266,12 @@ __global__ __launch_bounds__(NT, (NT >= 1024 || G <= 3 ? 4 : G <= 4 ? 3 : 2)) vo
     using DivScaled = std::integral_constant<int, 2>;
 #include "sweep_tile_sweeps.inc"      // publish / await / sweep lambdas
     // (the divide variant is chosen per wave; the neighbour handshake above does not care which one a wave runs)
+    // gamma as a vector operand (sweep_tile_sweeps.inc: why not the SGPR): the from-start tile's scaled sweeps take it from ONE register, made
+    // here and live across the launch -- a launch constant needs no v_mov per sweep, and the tile has the register.  It reaches the sweep
+    // inside the tag that selects the divide, a by-value argument: one more capture of the closures would shift the code of the other
+    // tiles (kFromStart, above).  Every other sweep makes its own copy per sweep, as before.
+    DivScaledFromStart div_from_start{{}, gamma};
+    if constexpr (kFromStart) asm volatile("" : "+v"(div_from_start.gamma));
     int s = 0, blk = 0;
     bool odd = false, dead = false;          // dead: the launch has failed (exchange_wait_at returned true): leave, behind the loop
     RTDD_XT_BEGIN;
@@ -306,10 +317,10 @@ __global__ __launch_bounds__(NT, (NT >= 1024 || G <= 3 ? 4 : G <= 4 ? 3 : 2)) vo
                 // (where this is the loop that nearly every wave runs it has the fast loop's shape, pairs and then the odd sweep of a tail
                 // block: with the tail inside the pair this tile ran each pair on a copy of the tile and moved it back, 50 v_mov a pair)
                 for (; s + 1 < s_scaled; s += 2) {
-                    sweep(a, b, s, DivScaled{}, false, P0{});
-                    sweep(b, a, s + 1, DivScaled{}, s + 2 >= s_end, P1{});
+                    sweep(a, b, s, div_from_start, false, P0{});
+                    sweep(b, a, s + 1, div_from_start, s + 2 >= s_end, P1{});
                 }
-                if (s < s_scaled) { sweep(a, b, s, DivScaled{}, true, P0{}); s++; odd = true; }
+                if (s < s_scaled) { sweep(a, b, s, div_from_start, true, P0{}); s++; odd = true; }
             } else {
                 while (s < s_scaled) {               // (its odd tail inside the pair, like the loop below and for the same reason)
                     const bool single = s + 1 >= s_end;

@@ -183,11 +183,32 @@ __device__ __forceinline__ float div_scaled(float n, float d, float y) {
 // A zero numerator of either sign gives +0, as div_tail does.  Four full-rate operations, the 2^64 a literal of the first multiplication
 // (scripts/isa_count.py finds the scaled sweep pair by it); no register more than div_tail's three operands.  Restated in C and checked
 // against the IEEE divide, div_scaled and div_tail in tests/test_div_scaled4_cpu.py; on gfx950 by scripts/ubench/div_scaled4_exhaustive.hip.
+// The numerator's chain WITHOUT its leading `0 +` (sweep_tile_sweeps.inc wsum, this tile's scaled pair only).  Every other sweep starts a
+// pixel's sum as 0 + p, p the left term (weight times value, a rounded product or the first fma's), and adds the other three terms; here
+// the chain starts at p itself -- an addition less per row with contraction, per pixel without.  Why no quotient changes:
+//   * 0 + p differs from p only for p = -0, where it is +0;
+//   * a -0 in the place of a +0 addend changes a later partial sum only while every product added so far is an exact zero (a nonzero
+//     product, however it rounds, gives the same sum with either zero), and then only that sum's sign: (-0) + (-0) = -0 where
+//     (+0) + (-0) = +0, as an addition or inside an fma;
+//   * so the chain's result differs at most by being -0 in place of +0;
+//   * and div_scaled4 gives +0 for both: N = -+0, qd = -+0 (ys > 0), R = fma(-D, qd, N) = (+-0) + (-+0) = +0 in round-to-nearest,
+//     q = fma(+0, ys, -+0) = +0 + -+0 = +0.
+// The IEEE variant (-0 / d = -0 there) and the fast variant keep the addition.  Restated from the sources and compared bit for bit, both contraction forms, in tests/test_div_scaled4_signed_zero_cpu.py.
 __device__ __forceinline__ float div_scaled4(float n, float D, float ys) {
     const float N = n * 0x1p64f;
     const float qd = N * ys;
     const float R = __builtin_fmaf(-D, qd, N);
     return __builtin_fmaf(R, ys, qd);
+}
+
+// fma(a, b, c) as ONE three-address v_fma_f32, all operands in VGPRs.  For an fma whose addend stays live behind it (the update's
+// fma(gamma, r - x, x): x is read again by the next sweep) the compiler picks between that and a copy of the addend plus the two-address
+// v_fmac_f32; in one of the six rows of the from-start tile's scaled pair -- the row whose sweep straddles the loop's back edge -- it took the
+// copy, one v_mov_b32 per pixel.  The same operation on the same operands, rounded once.
+__device__ __forceinline__ float fma_vvv(float a, float b, float c) {
+    float r;
+    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
 }
 
 // RN(1/d) for a normal d with a normal reciprocal: v_rcp_f32 (1 ulp) + one Newton step.  Equal to the IEEE quotient 1.0f/d for

@@ -79,9 +79,11 @@
         const float up[4] = {up4.x, up4.y, up4.z, up4.w}, dn[4] = {dn4.x, dn4.y, dn4.z, dn4.w};
         RTDD_TL_ROWS_IN_HAND(s);
         // omega and gamma in VGPRs: an fma with an SGPR operand issues at 4.3 cycles per wave-instruction, with three VGPRs at 3.1
-        // (profiles/r05_excp_probe.txt); one v_mov per wave and sweep
+        // (profiles/r05_excp_probe.txt); one v_mov per wave and sweep -- of omega only in the from-start tile's scaled sweeps, which take gamma
+        // from the register the wave made in front of the block loop (sweep_blocked.hip DivScaledFromStart)
         float omega_v = omegas[s], gamma_v = gamma;
-        asm volatile("" : "+v"(omega_v), "+v"(gamma_v));
+        if constexpr (SCALED && kFromStart) { gamma_v = fast.gamma; asm volatile("" : "+v"(omega_v)); }
+        else asm volatile("" : "+v"(omega_v), "+v"(gamma_v));
         // weighted sum of pixel (g, i): solveDiffusion, src/GPUSolver.cu:73-106, absent neighbours carried as (w = 0, x = 0)
         auto wsum = [&](int g, int i) {
             const float xl = i == 0 ? xl0[g] : cur[g][i - 1];
@@ -90,7 +92,11 @@
             const float xd = g == G - 1 ? dn[i] : cur[g + 1][i];
             const float wu = g == 0 ? wu0[i] : wd[g - 1][i];
             // xl0[g] holds the previous lane's wr[g][3] * cur[g][3]; RN(wl * xl) + 0 is what fma(wl, xl, 0) and 0 + wl * xl both give
-            float sum = i == 0 ? 0.0f + xl0[g] : (CONTRACT ? __builtin_fmaf(wr[g][i - 1], xl, 0.0f) : 0.0f + wr[g][i - 1] * xl);
+            // (the scaled pair of the from-start tile starts the chain AT the left term, without the `0 +`: a sum that is -0 in place of +0 is
+            // all that can come of it, and div_scaled4 answers +0 to both -- sweep_common.hpp)
+            float sum;
+            if constexpr (SCALED && kFromStart) sum = i == 0 ? xl0[g] : (CONTRACT ? __builtin_fmaf(wr[g][i - 1], xl, 0.0f) : wr[g][i - 1] * xl);
+            else sum = i == 0 ? 0.0f + xl0[g] : (CONTRACT ? __builtin_fmaf(wr[g][i - 1], xl, 0.0f) : 0.0f + wr[g][i - 1] * xl);
             sum = CONTRACT ? __builtin_fmaf(wr[g][i], xr, sum) : sum + wr[g][i] * xr;
             sum = CONTRACT ? __builtin_fmaf(wu, xu, sum) : sum + wu * xu;
             sum = CONTRACT ? __builtin_fmaf(wd[g][i], xd, sum) : sum + wd[g][i] * xd;
@@ -137,7 +143,10 @@
                     const float r = __builtin_amdgcn_fmed3f(q[g][i], 0.0f, 255.0f);        // :104; cnt == 0 was replaced by 1 (sum is 0 there): r = 0 (:103)
                     const float x = cur[g][i];
                     o[i] = oth[g][i];
-                    t[i] = (CONTRACT ? __builtin_fmaf(gamma_v, r - x, x) : gamma_v * (r - x) + x) - o[i];       // src/GPUSolver.cu:259, all but its last operation
+                    // src/GPUSolver.cu:259, all but its last operation (the from-start tile's scaled pair: the same fma as ONE three-address
+                    // instruction in every row -- sweep_common.hpp fma_vvv)
+                    if constexpr (SCALED && kFromStart && CONTRACT) t[i] = fma_vvv(gamma_v, r - x, x) - o[i];
+                    else t[i] = (CONTRACT ? __builtin_fmaf(gamma_v, r - x, x) : gamma_v * (r - x) + x) - o[i];
                     if (!CONTRACT) t[i] = omega_v * t[i];
                 }
                 // x_{k+1} = fma(omega, t, x_{k-1}) replaces x_{k-1} on the free pixels; a Dirichlet pixel's register already holds its value
