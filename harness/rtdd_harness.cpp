@@ -56,6 +56,11 @@
 //                                 region (rtdd_lift_layer), removes it and composites it (dx, dy) away at `depth` (default: its own nearest
 //                                 depth, one constant).  Before --layer and --effect, which run on the result and ITS depth map; without
 //                                 them <out>ArtisticEffect is the result; not with --live
+//     --select-grow R2 | --select-shrink R2 = extension, with --remove-region, --move-region or --plate-region: the region's code plane is
+//                                 first refined into a 0 / 255 mask (rtdd_refine_mask: grown out to, or shrunk in by, the squared Euclidean
+//                                 distance R2, 1 .. 1048576), and that mask is what the removal, the lift and the plate read; one of the two
+//     --move-feather W          = extension, with --move-region: the sprite gets a soft edge, W pixels wide (0 < W <= 64), inside the selection
+//                                 (rtdd_refine_mask's feather lo = -W, hi = 0, then rtdd_lift_layer_matte); the removal stays on the hard mask
 // and adds what the reference cannot do: --devices N --batch B runs B independent estimates
 // round-robin over N GPUs, one host thread + one HIP stream + one rtdd_ctx per GPU, no collective.
 #include <hip/hip_runtime.h>
@@ -289,7 +294,24 @@ struct Job {
     // (rtdd_simulate_parallax_layered); --parallax-depth-out FILE / --parallax-coverage FILE: its depth map (u8, as DepthMap) and coverage
     bool has_plate = false;
     std::string parallax_depth_out, parallax_coverage;
+    // --select-grow R2 / --select-shrink R2: the region's code plane refined (rtdd_refine_mask) into the 0 / 255 mask the removal, the lift
+    // and the plate read with select 0; --move-feather W: the lift's alpha is that mask feathered W pixels inwards (rtdd_lift_layer_matte)
+    int select_op = -1, select_r2 = 0;                              // RTDD_REFINE_GROW or RTDD_REFINE_SHRINK; -1: the code plane as it is
+    float move_feather = 0.0f;                                      // 0: a hard lift
 };
+// The mask --remove-region / --move-region / --plate-region read: the region's code plane under the region id, or (--select-grow /
+// --select-shrink) that plane refined into `refined` (device, cols bytes a row), read under select 0.
+static int region_mask(rtdd_ctx *ctx, const Job &job, unsigned char *refined, int rows, int cols, const uint8_t **mask, size_t *pitch, rtdd_removal *removal) {
+    void *p_code; size_t pi_code;
+    int rc = rtdd_pyramid_image(ctx, RTDD_IMG_REGION_CODE, 0, &p_code, &pi_code, nullptr, nullptr);
+    if (rc != RTDD_OK) return rc;
+    *mask = (const uint8_t *)p_code; *pitch = pi_code; *removal = job.removal;
+    if (job.select_op < 0) return RTDD_OK;
+    const rtdd_mask_refine r = {job.removal.select, job.select_op, job.select_r2, job.select_r2, 0.0f, 0.0f};
+    rc = rtdd_refine_mask(ctx, (const uint8_t *)p_code, pi_code, rows, cols, &r, refined, (size_t)cols);
+    *mask = refined; *pitch = (size_t)cols; removal->select = 0;
+    return rc;
+}
 // what --parallax-depth-out and --parallax-coverage write: device 0's last view
 struct ParallaxFiles { std::vector<unsigned char> depth_u8, coverage; };
 
@@ -566,6 +588,7 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
         unsigned char *d_sprite = nullptr, *d_lart = nullptr; float *d_lz = nullptr;      // --layer: the sprite, the composite and its depth map
         unsigned char *d_rart = nullptr, *d_msprite = nullptr, *d_mart = nullptr; float *d_rz = nullptr, *d_mz = nullptr;     // --remove-region / --move-region
         unsigned char *d_part = nullptr, *d_pz8 = nullptr, *d_pcov = nullptr; float *d_pplz = nullptr, *d_pz = nullptr;          // --plate-region: the plate; the view's depth map (f32, u8) and coverage
+        unsigned char *d_sel = nullptr, *d_alpha = nullptr;                                  // --select-grow / --select-shrink: the refined mask; --move-feather: the lift's alpha
         ~Owned() {
             if (d_bgr) (void)hipFree(d_bgr);
             if (d_ann) (void)hipFree(d_ann);
@@ -582,6 +605,8 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
             if (d_pz) (void)hipFree(d_pz);
             if (d_pz8) (void)hipFree(d_pz8);
             if (d_pcov) (void)hipFree(d_pcov);
+            if (d_sel) (void)hipFree(d_sel);
+            if (d_alpha) (void)hipFree(d_alpha);
             if (ctx) rtdd_ctx_destroy(ctx);           // synchronises the stream first
             if (stream) (void)hipStreamDestroy(stream);
         }
@@ -663,6 +688,8 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
         if (ok && job.has_move) ok = hipMalloc((void **)&own.d_msprite, px * 4) == hipSuccess && hipMalloc((void **)&own.d_mart, px * 3) == hipSuccess && hipMalloc((void **)&own.d_mz, px * 4) == hipSuccess;
         if (!ok) { std::printf("device %d: out of memory\n", device); return RTDD_ERR_NOMEM; }
     }
+    if (job.select_op >= 0 && hipMalloc((void **)&own.d_sel, (size_t)rows * cols) != hipSuccess) { std::printf("device %d: out of memory\n", device); return RTDD_ERR_NOMEM; }
+    if (job.move_feather > 0.0f && hipMalloc((void **)&own.d_alpha, (size_t)rows * cols) != hipSuccess) { std::printf("device %d: out of memory\n", device); return RTDD_ERR_NOMEM; }
     const bool want_pz = !job.parallax_depth_out.empty(), want_pcov = !job.parallax_coverage.empty();
     if (job.has_plate || want_pz || want_pcov) {                       // --plate-region, --parallax-depth-out, --parallax-coverage
         const size_t px = (size_t)rows * cols;
@@ -783,14 +810,19 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
         void *r_orig = p_orig, *r_depth = p_depth;
         size_t ri_orig = pi_orig, ri_depth = pi_depth;
         if (job.has_remove || job.has_move) {
-            void *p_code; size_t pi_code;
-            CK(rtdd_pyramid_image(ctx, RTDD_IMG_REGION_CODE, 0, &p_code, &pi_code, nullptr, nullptr));
+            const uint8_t *p_code; size_t pi_code; rtdd_removal removal;    // (--select-grow / --select-shrink: the refined mask, select 0)
+            CK(region_mask(ctx, job, own.d_sel, rows, cols, &p_code, &pi_code, &removal));
             const size_t w3 = (size_t)cols * 3, w4 = (size_t)cols * 4;
-            CK(rtdd_remove_object(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_code, pi_code, own.d_rart, w3, own.d_rz, w4, rows, cols, &job.removal));
+            CK(rtdd_remove_object(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, p_code, pi_code, own.d_rart, w3, own.d_rz, w4, rows, cols, &removal));
             r_orig = own.d_rart; r_depth = own.d_rz; ri_orig = w3; ri_depth = w4;
             if (job.has_move) {
                 // the sprite is the whole image's box, so it covers the region wherever that lies; it lands (dx, dy) away
-                CK(rtdd_lift_layer(ctx, (uint8_t *)p_orig, pi_orig, (uint8_t *)p_code, pi_code, rows, cols, job.removal.select, 0, 0, own.d_msprite, w4, rows, cols));
+                if (job.move_feather > 0.0f) {                          // a soft edge inside the selection: the feathered mask is the sprite's alpha
+                    const rtdd_mask_refine f = {removal.select, RTDD_REFINE_FEATHER, 0, 0, -job.move_feather, 0.0f};
+                    CK(rtdd_refine_mask(ctx, p_code, pi_code, rows, cols, &f, own.d_alpha, (size_t)cols));
+                    CK(rtdd_lift_layer_matte(ctx, (uint8_t *)p_orig, pi_orig, own.d_alpha, (size_t)cols, rows, cols, 0, 0, own.d_msprite, w4, rows, cols));
+                } else
+                CK(rtdd_lift_layer(ctx, (uint8_t *)p_orig, pi_orig, p_code, pi_code, rows, cols, removal.select, 0, 0, own.d_msprite, w4, rows, cols));
                 rtdd_layer L = {rows, cols, job.move_dx, job.move_dy, 256, RTDD_LAYER_NEAREST, 255, 0, 0, 0, 0, job.move_depth, job.move_depth, 0.0f};
                 if (!job.move_has_depth) {
                     // keep the region's own depth, as one constant: the nearest d' of its pixels, read from a download of the map and the codes
@@ -799,7 +831,7 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
                     CK(rtdd_download(ctx, code.data(), cols, p_code, pi_code, cols, rows));
                     float nearest = 255.0f;
                     for (size_t i = 0; i < z.size(); i++)
-                        if (code[i] == job.removal.select) nearest = std::min(nearest, z[i] > 0.0f ? std::min(z[i], 255.0f) : 0.0f);
+                        if (removal.select == 0 ? code[i] != 0 : code[i] == removal.select) nearest = std::min(nearest, z[i] > 0.0f ? std::min(z[i], 255.0f) : 0.0f);
                     L.depth0 = L.depth1 = nearest;
                     if (n == 0) std::printf("move region %d by %d,%d at its own depth %g\n", job.removal.select, job.move_dx, job.move_dy, nearest);
                 }
@@ -838,9 +870,9 @@ static int run_device(int device, const Job &job, int count, bool live, std::vec
             const rtdd_parallax view = {job.shift_x, job.shift_y, job.dolly, job.zero_depth, job.zero_x, job.zero_y};
             const size_t w1 = (size_t)cols, w3 = w1 * 3, w4 = w1 * 4;
             if (job.has_plate) {                                        // the region taken out of the scene into the plate; the scene itself stays
-                void *p_code; size_t pi_code;
-                CK(rtdd_pyramid_image(ctx, RTDD_IMG_REGION_CODE, 0, &p_code, &pi_code, nullptr, nullptr));
-                CK(rtdd_remove_object(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, (uint8_t *)p_code, pi_code, own.d_part, w3, own.d_pplz, w4, rows, cols, &job.removal));
+                const uint8_t *p_code; size_t pi_code; rtdd_removal removal;
+                CK(region_mask(ctx, job, own.d_sel, rows, cols, &p_code, &pi_code, &removal));
+                CK(rtdd_remove_object(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, p_code, pi_code, own.d_part, w3, own.d_pplz, w4, rows, cols, &removal));
             }
             if (job.has_plate || own.d_pz || own.d_pcov)
                 CK(rtdd_simulate_parallax_layered(ctx, (uint8_t *)p_orig, pi_orig, (float *)p_depth, pi_depth, own.d_part, w3, own.d_pplz, w4, (uint8_t *)p_art, pi_art,
@@ -903,6 +935,7 @@ int main(int argc, const char *argv[]) {
                                  "                    [relight's light flags] [--shadows N (256)] [--shadow-bias B] [--shadow-softness S] [--shadow-strength T] [--ao R (16)] [--ao-directions 4|8] [--ao-bias B] [--ao-strength T] (lighting: shade, cast shadows and occlusion in one call)\n"
                                  "                    [--layer sprite.(ppm|png|jpg) [--layer-alpha alpha.(pgm|png)] --layer-at x,y [--layer-scale S (256)] [--layer-filter nearest|bilinear] [--layer-depth z (128) | --layer-plane x0,y0,z0,x1,y1,z1] [--layer-feather f] [--layer-opacity o (255)]]   (a sprite inserted at a depth after the estimate, rtdd_composite_layer: --effect then runs on the composite and its depth map; without --effect ArtisticEffect is the composite)\n"
                                  "                    [--remove-region id [--remove-grow N (0..8)] [--remove-behind D] | --move-region id:dx,dy[:depth] [--remove-grow N] [--remove-behind D]]   (with --regions: the painted region taken out of the scene, rtdd_remove_object, or moved, rtdd_lift_layer + rtdd_remove_object + rtdd_composite_layer; before --layer and --effect, which run on the result and its depth map)\n"
+                                 "                    [--select-grow R2 | --select-shrink R2] [--move-feather W]   (with --remove-region / --move-region / --plate-region: the region grown out to, or shrunk in by, the squared Euclidean distance R2 first, rtdd_refine_mask; with --move-region: a soft edge of W pixels, 0 < W <= 64, inside the moved selection, rtdd_lift_layer_matte)\n"
                                  "                    [--paint x,y,label,radius]... [--live N [--paint-at frame:x,y,label,radius]...] [--devices D --batch B [--sequential] [--write-all]] [--png] [--cold] [--edges gray|color] [--regions cut|smooth|both [--region-fill x,y;...:id]... [--region-wand x,y,tol:id]... [--surface-global] [--region-surface x,y,step[,below,above]:id]... [--segment step[,lo,hi[,minPixels[,maxRegions[,firstCode]]]]]]   (--segment: every surface of the ESTIMATED depth map at once, rtdd_segment_surfaces into the region pair behind the clicks, the largest as regions firstCode, firstCode + 1, ...; --region-surface: a click on the ESTIMATED depth map, rtdd_fill_surface into the region pair after the estimate and before --remove-region / --move-region / --plate-region; --surface-global: the clicks behind it take every pixel in their band; not with --live or --batch)\n"
                                  "                    [--stroke x0,y0,x1,y1,label,radius[,round]]... [--erase x0,y0,x1,y1,radius[,round]]...   (segments, in command-line order, one rtdd_paint_strokes call after --paint)\n"
                                  "                    [--ramp x0,y0,x1,y1,label0,label1,radius[,round]]...   (a depth ramp: label0 at x0,y0 to label1 at x1,y1; in order with --stroke / --erase, all of them one rtdd_paint_ramp_strokes call)\n"
@@ -1062,6 +1095,15 @@ int main(int argc, const char *argv[]) {
             if (got < 3) { std::printf("--move-region wants id:dx,dy or id:dx,dy:depth\n"); return 1; }
             job.move_has_depth = got == 4; job.has_move = true;
         }
+        else if (!std::strcmp(argv[i], "--select-grow") || !std::strcmp(argv[i], "--select-shrink")) {
+            if (job.select_op >= 0) { std::printf("--select-grow and --select-shrink: one at a time\n"); return 1; }
+            job.select_op = argv[i][9] == 'g' ? RTDD_REFINE_GROW : RTDD_REFINE_SHRINK; job.select_r2 = std::atoi(next());
+            if (job.select_r2 < 1 || job.select_r2 > 1024 * 1024) { std::printf("--select-grow and --select-shrink want a squared radius, 1..1048576\n"); return 1; }
+        }
+        else if (!std::strcmp(argv[i], "--move-feather")) {
+            job.move_feather = (float)std::atof(next());
+            if (!(job.move_feather > 0.0f && job.move_feather <= 64.0f)) { std::printf("--move-feather wants a width W, 0 < W <= 64\n"); return 1; }
+        }
         else if (!std::strcmp(argv[i], "--layer")) layer_path = next();
         else if (!std::strcmp(argv[i], "--layer-alpha")) { layer_alpha_path = next(); layer_opt = true; }
         else if (!std::strcmp(argv[i], "--layer-at")) { if (std::sscanf(next(), "%d,%d", &job.layer.x, &job.layer.y) != 2) { std::printf("--layer-at wants x,y\n"); return 1; } layer_at = layer_opt = true; }
@@ -1114,6 +1156,9 @@ int main(int argc, const char *argv[]) {
     if (live > 0 && !layer_path.empty()) { std::printf("--layer is not supported with --live\n"); return 1; }
     // a removal works on a painted region: its flags belong to it, it needs the regions, and one of the two forms at a time
     if (remove_opt && !job.has_remove && !job.has_move && !job.has_plate) { std::printf("--remove-grow and --remove-behind need --remove-region id, --move-region id:dx,dy or --plate-region id\n"); return 1; }
+    if (job.select_op >= 0 && !job.has_remove && !job.has_move && !job.has_plate) { std::printf("--select-grow and --select-shrink need --remove-region id, --move-region id:dx,dy or --plate-region id\n"); return 1; }
+    if (job.move_feather > 0.0f && !job.has_move) { std::printf("--move-feather needs --move-region id:dx,dy\n"); return 1; }
+    if ((job.select_op >= 0 || job.move_feather > 0.0f) && (live > 0 || batch > 1)) { std::printf("--select-grow, --select-shrink and --move-feather are not supported with --live or --batch\n"); return 1; }
     // the two-layer parallax view: a plate is a painted region removed for --effect parallax alone; one removal per run
     const bool parallax_out = !job.parallax_depth_out.empty() || !job.parallax_coverage.empty();
     if (live > 0 && (job.has_plate || parallax_out)) { std::printf("--plate-region, --parallax-depth-out and --parallax-coverage are not supported with --live\n"); return 1; }

@@ -1138,6 +1138,70 @@ int rtdd_lift_layer(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch
                     uint8_t *sprite, size_t spritePitch,                /* DEVICE, u8 x 4, written */
                     int spriteRows, int spriteCols                      /* 1 .. 16384 each */);
 
+/* Refine a mask: the exact Euclidean distance transform of a selection, and the four things it is wanted for -- grow, shrink, outline and
+ * feather -- between the selecting calls (the wands, the lasso, rtdd_segment_surfaces) and the calls that use a selection
+ * (rtdd_remove_object, rtdd_lift_layer, a plate).  A MASK is u8, rows x cols, on the DEVICE.  Everything is exact in 32-bit integers
+ * (rows^2 + cols^2 < 2^31, rtdd_lift_layer's image rule); E is a minimum of integers, so the result cannot depend on the schedule.
+ *   SELECTED: rtdd_removal.select's rule -- select == 0: the mask byte != 0;  select 1..255: the mask byte == select.
+ *   E(p), for a pixel p = (px, py): the minimum over the image's pixels q of the OTHER class (the unselected ones for a selected p, the
+ *     selected ones for an unselected p) of (px - qx)^2 + (py - qy)^2.  No pixels exist outside the image: an object that touches the
+ *     border has no boundary there.  E >= 1 whenever it exists; where the other class is empty E is infinite.
+ * rtdd_mask_distance, reach in 1..1024:
+ *     dist2(p) = -E if p is selected, +E if not, wherever E <= reach * reach;  -RTDD_DISTANCE_FAR or +RTDD_DISTANCE_FAR otherwise.
+ *   It is never 0.  The cut-off is the Euclidean one: around a single selected pixel the finite values are exactly the disc
+ *   dx^2 + dy^2 <= reach^2, and the corners of its (2 reach + 1)^2 box are FAR.  Every pixel of dist2 is stored exactly once.  dist2
+ *   follows the f32 image alignment rule (pointer and pitch multiples of 4), dist2Pitch >= 4 * cols.
+ * rtdd_refine_mask writes one byte per pixel, by refine->op:
+ *   RTDD_REFINE_GROW:     out = (selected || E <= outer2) ? 255 : 0                     outer2 in 1..1024^2 (inner2 is not read)
+ *   RTDD_REFINE_SHRINK:   out = (selected && E > inner2) ? 255 : 0                      inner2 in 1..1024^2 (outer2 is not read)
+ *   RTDD_REFINE_OUTLINE:  out = ((selected && E <= inner2) || (!selected && E <= outer2)) ? 255 : 0
+ *                         inner2, outer2 each in 0..1024^2 and not both 0; 0: that side of the outline is empty
+ *   RTDD_REFINE_FEATHER:  lo < hi, both finite, in [-1023.5, 1023.5].  Every f32 operation is one operation, rounded once, NONE fused;
+ *                         sqrtf and / are IEEE correctly rounded:
+ *       t = sqrtf((float)E)                              (E <= 2^20 whenever it matters: the conversion is exact)
+ *       s = selected ? 0.5f - t : t - 0.5f               (the boundary runs midway between pixel centres: s <= -0.5 inside, >= 0.5 outside)
+ *       u = (hi - s) / (hi - lo);  u = fminf(fmaxf(u, 0), 1);  out = (int)(u * 255.0f + 0.5f)
+ *                         E infinite: 255 if selected, 0 if not.  lo = -w, hi = 0 is an inner feather of w pixels that never reaches
+ *                         beyond the selection; lo = -w / 2, hi = w / 2 straddles the boundary.
+ *   (lo, hi are not read by the first three, inner2 and outer2 not by the feather.)  The reach is derived on the host and never shown:
+ *   the smallest R with R^2 >= max(inner2, outer2), or for the feather the smallest integer R >= max(|lo|, |hi|) + 0.5; R <= 1024 by the
+ *   ranges above.  With that R a pixel whose E lies beyond the reach saturates to the byte the rule gives it with its true E -- for the
+ *   thresholds because E > R^2 >= the threshold; for the feather because rounding is monotone: t >= R gives s <= 0.5 - R <= lo inside
+ *   (u >= 1) and s >= R - 0.5 >= hi outside (u <= 0), in f32 as in the reals.  So THE OUTPUT IS THE RULE APPLIED TO THE UNBOUNDED E.
+ *   The distance map is never stored for this call.
+ * rtdd_lift_layer_matte is rtdd_lift_layer with an ALPHA image (u8, rows x cols, e.g. a feathered mask) in place of mask and select:
+ *   texel (u, v) is (B, G, R, a), a the alpha byte of image pixel (x + u, y + v); (0, 0, 0, 0) where a == 0 or the pixel lies outside the
+ *   image.  With an alpha of only 0 and 255 it writes rtdd_lift_layer(select = 0)'s bytes.  For ANY alpha, rtdd_composite_layer of the
+ *   sprite onto `original` itself (scale 256, RTDD_LAYER_NEAREST, opacity 255, depth0 = 0 with (x0, y0) == (x1, y1), feather 0) gives
+ *   `original` byte for byte: (o e + o (E - e) + E / 2) div E = o.  A soft edge carries the colour it had, not a halo.
+ * All three: asynchronous, stream-ordered, deterministic, independent of RTDD_OPT_FP_CONTRACT; not in place (a healed time-out runs the
+ * call again, and the second run must read what the first one read).  The first two keep their column pass in the context's table
+ * buffer.  RTDD_VERSION is unchanged: a host finds the symbols by name.
+ * Refused on the host (RTDD_ERR_INVALID), before any launch: rtdd_lift_layer's image rules (null pointers, negative sizes, the image
+ * size, maskPitch, outPitch, alphaPitch >= cols, dist2Pitch >= 4 * cols, the f32 alignment rule for dist2, the sprite's rules);
+ * out == mask; dist2 == mask; sprite == original; select outside [0, 255]; reach outside [1, 1024]; a null refine; an unknown op; any
+ * field the op reads outside its range; lo >= hi; a non-finite lo or hi. */
+#define RTDD_DISTANCE_FAR 0x7fffffff
+enum rtdd_refine_op { RTDD_REFINE_GROW = 0, RTDD_REFINE_SHRINK = 1, RTDD_REFINE_OUTLINE = 2, RTDD_REFINE_FEATHER = 3 };
+typedef struct rtdd_mask_refine {
+    int   select;               /* 0: a pixel is selected iff its mask byte != 0;  1 .. 255: iff its mask byte == select (a region code) */
+    int   op;                   /* enum rtdd_refine_op */
+    int   inner2, outer2;       /* squared distances: how far the rule reaches into the selection, and out of it */
+    float lo, hi;               /* the feather's ramp, in pixels from the boundary (negative: inside): 255 at s <= lo, 0 at s >= hi */
+} rtdd_mask_refine;             /* 24 bytes, ints and floats only */
+int rtdd_mask_distance(rtdd_ctx *ctx, const uint8_t *mask, size_t maskPitch,        /* DEVICE, u8, rows x cols */
+                       int rows, int cols, int select /* 0 .. 255 */, int reach /* 1 .. 1024 */,
+                       int32_t *dist2, size_t dist2Pitch                            /* DEVICE, i32, rows x cols, written */);
+int rtdd_refine_mask(rtdd_ctx *ctx, const uint8_t *mask, size_t maskPitch,          /* DEVICE, u8, rows x cols */
+                     int rows, int cols, const rtdd_mask_refine *refine /* HOST, read before the call returns */,
+                     uint8_t *out, size_t outPitch                                  /* DEVICE, u8, rows x cols, written */);
+int rtdd_lift_layer_matte(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch,
+                          const uint8_t *alpha, size_t alphaPitch,                  /* DEVICE, u8, rows x cols */
+                          int rows, int cols,
+                          int x, int y,                                             /* the sprite's corner in the image, each in [-16384, 16383] */
+                          uint8_t *sprite, size_t spritePitch,                      /* DEVICE, u8 x 4, written */
+                          int spriteRows, int spriteCols                            /* 1 .. 16384 each */);
+
 /* ---- whole-estimate driver ------------------------------------------------
  * One depth estimate = the loop body of src/main.cpp:232-295, run as a single stream-ordered launch
  * sequence with the gray pyramid, f32 pyrUp and u8 conversion ON THE DEVICE (the reference round-trips

@@ -55,7 +55,7 @@ C_ABI_SYMBOLS = [
     "rtdd_paint_strokes", "rtdd_pyramid_annotation_rebuild", "rtdd_paint_ramp_strokes", "rtdd_ramp_polyline", "rtdd_fill_polygon", "rtdd_fill_similar", "rtdd_fill_surface", "rtdd_segment_surfaces",
     "rtdd_simulate_relight", "rtdd_simulate_relight_shadowed", "rtdd_simulate_parallax", "rtdd_simulate_ambient_occlusion",
     "rtdd_simulate_lighting", "rtdd_simulate_bokeh", "rtdd_composite_layer", "rtdd_remove_object", "rtdd_lift_layer",
-    "rtdd_simulate_parallax_layered",
+    "rtdd_simulate_parallax_layered", "rtdd_mask_distance", "rtdd_refine_mask", "rtdd_lift_layer_matte",
     "rtdd_solve_guided", "rtdd_index_to_weight_guided", "rtdd_pyrdown_bgr", "rtdd_pyramid_set_guide", "rtdd_pyramid_guide",
     "rtdd_solve_regions", "rtdd_index_to_weight_regions", "rtdd_region_codes", "rtdd_pyramid_set_regions", "rtdd_pyramid_regions",
     "rtdd_pyramid_regions_changed",
@@ -102,6 +102,33 @@ def remove_plan(rows, cols):
         plan.append((g, r, c))
         if r * c <= REMOVE_APEX and chain(r, c) <= REMOVE_APEX_CHAIN:
             return plan
+
+
+# rtdd_mask_distance / rtdd_refine_mask (csrc/rtdd_internal.hpp: kEdtTileW, kEdtTileH, kEdtBand, kEdtLdsReach): the column pass works on
+# words of EDT_BAND rows of a column and flags blocks of EDT_TILE_W columns; a workgroup of the row pass owns EDT_TILE_W x EDT_TILE_H
+# pixels and stages a row segment with its halo in LDS up to a reach of EDT_LDS_REACH
+EDT_TILE_W, EDT_TILE_H, EDT_BAND, EDT_LDS_REACH = 64, 4, 64, 224
+REFINE_GROW, REFINE_SHRINK, REFINE_OUTLINE, REFINE_FEATHER = range(4)    # rtdd_mask_refine.op
+DISTANCE_FAR = 0x7FFFFFFF                     # rtdd_mask_distance: |dist2| of a pixel whose E lies beyond the reach
+
+
+def mask_distance_plan(rows, cols, reach):
+    """What rtdd_mask_distance does for a rows x cols mask at `reach` (csrc/mask_distance.hip edt_plan and launch_rows): the row pass's
+    path ("lds": the halo is staged; "l2": read through the caches), the bands of the column pass and how many neighbouring words a carry
+    may read each way, the blocks of columns, the row pass's grid and the u32 words of the table buffer."""
+    bands, blocks = (rows + EDT_BAND - 1) // EDT_BAND, (cols + EDT_TILE_W - 1) // EDT_TILE_W
+    return dict(path="lds" if reach <= EDT_LDS_REACH else "l2", bands=bands, blocks=blocks, carry_words=(reach + EDT_BAND - 1) // EDT_BAND,
+                grid=(blocks, (rows + EDT_TILE_H - 1) // EDT_TILE_H), words=2 * bands * cols + rows * cols + rows * blocks)
+
+
+def refine_reach(op, inner2=0, outer2=0, lo=0.0, hi=0.0):
+    """The reach rtdd_refine_mask derives on the host (include/rtdd.h): the smallest R with R^2 >= the largest threshold the op reads, or
+    for the feather the smallest integer R >= max(|lo|, |hi|) + 0.5."""
+    import math
+    if op == REFINE_FEATHER:
+        return math.ceil(max(abs(lo), abs(hi)) + 0.5)
+    most = {REFINE_GROW: outer2, REFINE_SHRINK: inner2}.get(op, max(inner2, outer2))
+    return max(1, math.isqrt(max(most - 1, 0)) + 1 if most > 0 else 1)
 
 
 # Itanium-mangled names of the reference's ten free functions (SURVEY.md 8b)
@@ -266,6 +293,16 @@ class Removal(C.Structure):
 
     def __init__(self, select=0, grow=0, sourceMinDepth=0.0):
         super().__init__(select, grow, sourceMinDepth)
+
+
+class MaskRefine(C.Structure):
+    """rtdd_mask_refine: `select` as Removal's; REFINE_GROW (out to squared distance outer2), REFINE_SHRINK (in by inner2),
+    REFINE_OUTLINE (the selected pixels within inner2 of the boundary and the unselected ones within outer2; 0: that side is empty) or
+    REFINE_FEATHER (255 at `lo` pixels from the boundary, 0 at `hi`, linear between; negative is inside)."""
+    _fields_ = [("select", C.c_int), ("op", C.c_int), ("inner2", C.c_int), ("outer2", C.c_int), ("lo", C.c_float), ("hi", C.c_float)]
+
+    def __init__(self, select=0, op=REFINE_GROW, inner2=0, outer2=0, lo=0.0, hi=0.0):
+        super().__init__(select, op, inner2, outer2, lo, hi)
 
 
 class Profile(C.Structure):
@@ -708,6 +745,28 @@ class Context:
         o, op = _img(originalImage); m, mp = _img(maskImage); s, sp = _img(spriteImage)
         self._check(lib().rtdd_lift_layer(self._h, o, op, m, mp, C.c_int(rows), C.c_int(cols), C.c_int(select), C.c_int(x), C.c_int(y),
                                           s, sp, C.c_int(spriteRows), C.c_int(spriteCols)))
+
+    def mask_distance(self, maskImage, rows, cols, select, reach, dist2Image):
+        """The exact squared Euclidean distance of every pixel of `maskImage` (u8, rows x cols; selected: byte != 0, or == select) to the
+        nearest pixel of the other class, into dist2Image (int32, rows x cols): negative inside the selection, positive outside, never 0;
+        +-DISTANCE_FAR where it exceeds reach * reach (reach 1..1024) or the other class is empty."""
+        m, mp = _img(maskImage) if maskImage is not None else (None, C.c_size_t(0))
+        d, dp = _img(dist2Image) if dist2Image is not None else (None, C.c_size_t(0))
+        self._check(lib().rtdd_mask_distance(self._h, m, mp, C.c_int(rows), C.c_int(cols), C.c_int(select), C.c_int(reach), d, dp))
+
+    def refine_mask(self, maskImage, rows, cols, refine, outImage):
+        """`maskImage` grown, shrunk, outlined or feathered as `refine` (a MaskRefine, or None for the C call's null pointer) says, by the
+        exact Euclidean distance, into outImage (u8, rows x cols): 0 / 255, or the feather's ramp."""
+        m, mp = _img(maskImage) if maskImage is not None else (None, C.c_size_t(0))
+        o, op = _img(outImage) if outImage is not None else (None, C.c_size_t(0))
+        self._check(lib().rtdd_refine_mask(self._h, m, mp, C.c_int(rows), C.c_int(cols), C.byref(refine) if refine is not None else None, o, op))
+
+    def lift_layer_matte(self, originalImage, alphaImage, rows, cols, x, y, spriteImage, spriteRows, spriteCols):
+        """lift_layer with an alpha image (u8, rows x cols, e.g. a feathered mask) in place of the mask: texel (B, G, R, alpha) where
+        alpha != 0, everything else 0, 0, 0, 0.  Composited back where it came from it gives the original byte for byte."""
+        o, op = _img(originalImage); m, mp = _img(alphaImage); s, sp = _img(spriteImage)
+        self._check(lib().rtdd_lift_layer_matte(self._h, o, op, m, mp, C.c_int(rows), C.c_int(cols), C.c_int(x), C.c_int(y),
+                                                s, sp, C.c_int(spriteRows), C.c_int(spriteCols)))
 
     # ---- whole-estimate driver (src/main.cpp:92-155, 232-295)
     def pyramid_create(self, rows, cols):

@@ -860,7 +860,10 @@ int launch_effect(rtdd_ctx *ctx, const Effect &e) {
         case Effect::kBokeh: return launch_bokeh(ctx, e);              // bokeh.hip
         case Effect::kComposite: return launch_composite(ctx, e);      // composite.hip
         case Effect::kRemove: return launch_remove(ctx, e);            // remove.hip
-        case Effect::kLift: return launch_lift(ctx, e);                // remove.hip
+        case Effect::kLift:
+        case Effect::kLiftMatte: return launch_lift(ctx, e);           // remove.hip
+        case Effect::kMaskDistance:
+        case Effect::kRefineMask: return launch_mask_distance(ctx, e); // mask_distance.hip
         case RTDD_EFFECT_DESATURATION:
             return launch_blend<0>(ctx, e.original, e.originalPitch, e.gray, e.grayPitch, e.depth, e.depthPitch, e.artistic, e.artisticPitch,
                                    e.rows, e.cols);

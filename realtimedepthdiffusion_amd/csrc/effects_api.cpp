@@ -426,5 +426,85 @@ int rtdd_lift_layer(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch
     return simulate(ctx, e);
 }
 
+// rtdd_lift_layer's image rules for a mask-sized u8 image and its size (rtdd_mask_distance, rtdd_refine_mask)
+static int check_mask(rtdd_ctx *ctx, const void *mask, size_t maskPitch, const void *out, int rows, int cols) {
+    REQUIRE(ctx, mask && out, "null image pointer");
+    REQUIRE(ctx, rows >= 0 && cols >= 0, "negative size");
+    REQUIRE(ctx, (long long)rows * rows + (long long)cols * cols < 2147483647LL, "image too large");
+    REQUIRE(ctx, maskPitch >= (size_t)cols, "pitch smaller than a row");
+    REQUIRE(ctx, mask != out, "a mask cannot be refined in place");
+    return RTDD_OK;
+}
+
+int rtdd_mask_distance(rtdd_ctx *ctx, const uint8_t *mask, size_t maskPitch, int rows, int cols, int select, int reach, int32_t *dist2,
+                       size_t dist2Pitch) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    int rc = check_mask(ctx, mask, maskPitch, dist2, rows, cols);
+    if (rc != RTDD_OK) return rc;
+    REQUIRE(ctx, dist2Pitch >= (size_t)cols * 4, "pitch smaller than a row");
+    REQUIRE(ctx, f32_image_aligned(dist2, dist2Pitch), kF32AlignText);
+    REQUIRE(ctx, select >= 0 && select <= 255, "select outside [0, 255]");
+    REQUIRE(ctx, reach >= 1 && reach <= kEdtMaxReach, "reach outside [1, 1024]");
+    if (rows == 0 || cols == 0) return RTDD_OK;
+    Effect e{Effect::kMaskDistance, nullptr, 0, nullptr, 0, nullptr, 0, rows, cols};
+    Effect::MaskOp &k = e.maskop;
+    k.mask = mask; k.maskPitch = maskPitch; k.select = select; k.reach = reach; k.dist2 = dist2; k.dist2Pitch = dist2Pitch;
+    return simulate(ctx, e);
+}
+
+int rtdd_refine_mask(rtdd_ctx *ctx, const uint8_t *mask, size_t maskPitch, int rows, int cols, const rtdd_mask_refine *refine, uint8_t *out,
+                     size_t outPitch) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    int rc = check_mask(ctx, mask, maskPitch, out, rows, cols);
+    if (rc != RTDD_OK) return rc;
+    REQUIRE(ctx, outPitch >= (size_t)cols, "pitch smaller than a row");
+    REQUIRE(ctx, refine, "null refine");
+    const rtdd_mask_refine &q = *refine;
+    REQUIRE(ctx, q.select >= 0 && q.select <= 255, "select outside [0, 255]");
+    constexpr int kMax2 = kEdtMaxReach * kEdtMaxReach;
+    // the reach: the smallest R with R^2 >= the largest threshold, or with R >= max(|lo|, |hi|) + 0.5 (include/rtdd.h: a pixel beyond it
+    // saturates to the byte its true E gives it)
+    int reach = 1;
+    if (q.op == RTDD_REFINE_FEATHER) {
+        REQUIRE(ctx, std::isfinite(q.lo) && std::isfinite(q.hi), "a non-finite value in the refine");
+        REQUIRE(ctx, q.lo >= -1023.5f && q.hi <= 1023.5f && q.lo < q.hi, "the feather needs -1023.5 <= lo < hi <= 1023.5");
+        reach = (int)std::ceil(std::max(std::fabs((double)q.lo), std::fabs((double)q.hi)) + 0.5);
+    } else {
+        int most = 0;
+        if (q.op == RTDD_REFINE_GROW) { REQUIRE(ctx, q.outer2 >= 1 && q.outer2 <= kMax2, "outer2 outside [1, 1024^2]"); most = q.outer2; }
+        else if (q.op == RTDD_REFINE_SHRINK) { REQUIRE(ctx, q.inner2 >= 1 && q.inner2 <= kMax2, "inner2 outside [1, 1024^2]"); most = q.inner2; }
+        else if (q.op == RTDD_REFINE_OUTLINE) {
+            REQUIRE(ctx, q.inner2 >= 0 && q.inner2 <= kMax2 && q.outer2 >= 0 && q.outer2 <= kMax2, "inner2 or outer2 outside [0, 1024^2]");
+            REQUIRE(ctx, q.inner2 != 0 || q.outer2 != 0, "an outline needs inner2 or outer2");
+            most = std::max(q.inner2, q.outer2);
+        } else return fail(ctx, RTDD_ERR_INVALID, "op must be RTDD_REFINE_GROW, _SHRINK, _OUTLINE or _FEATHER");
+        while (reach * reach < most) reach++;
+    }
+    REQUIRE(ctx, reach >= 1 && reach <= kEdtMaxReach, "the refine reaches beyond 1024 pixels");
+    if (rows == 0 || cols == 0) return RTDD_OK;
+    Effect e{Effect::kRefineMask, nullptr, 0, nullptr, 0, nullptr, 0, rows, cols};
+    Effect::MaskOp &k = e.maskop;
+    k.mask = mask; k.maskPitch = maskPitch; k.select = q.select; k.reach = reach; k.refine = q; k.out = out; k.outPitch = outPitch;
+    return simulate(ctx, e);
+}
+
+int rtdd_lift_layer_matte(rtdd_ctx *ctx, const uint8_t *original, size_t originalPitch, const uint8_t *alpha, size_t alphaPitch, int rows, int cols,
+                          int x, int y, uint8_t *sprite, size_t spritePitch, int spriteRows, int spriteCols) {
+    if (!ctx) return RTDD_ERR_INVALID;
+    REQUIRE(ctx, original && alpha && sprite, "null image pointer");
+    REQUIRE(ctx, rows >= 0 && cols >= 0, "negative size");
+    REQUIRE(ctx, (long long)rows * rows + (long long)cols * cols < 2147483647LL, "image too large");
+    REQUIRE(ctx, originalPitch >= (size_t)cols * 3 && alphaPitch >= (size_t)cols, "pitch smaller than a row");
+    REQUIRE(ctx, original != sprite, "a sprite cannot be lifted in place");
+    REQUIRE(ctx, spriteRows >= 1 && spriteRows <= 16384 && spriteCols >= 1 && spriteCols <= 16384, "the sprite's rows or cols outside [1, 16384]");
+    REQUIRE(ctx, spritePitch >= (size_t)spriteCols * 4, "pitch smaller than a row");
+    REQUIRE(ctx, x >= -16384 && x <= 16383 && y >= -16384 && y <= 16383, "a sprite coordinate outside [-16384, 16383]");
+    Effect e{Effect::kLiftMatte, original, originalPitch, nullptr, 0, nullptr, 0, rows, cols};  // (an empty image: a transparent sprite)
+    Effect::Lift &k = e.lift;
+    k.mask = alpha; k.maskPitch = alphaPitch; k.select = 0; k.x = x; k.y = y;
+    k.sprite = sprite; k.spritePitch = spritePitch; k.spriteRows = spriteRows; k.spriteCols = spriteCols;
+    return simulate(ctx, e);
+}
+
 }  // extern "C"
 #pragma GCC visibility pop

@@ -522,8 +522,10 @@ int launch_remove(rtdd_ctx *ctx, const Effect &e) {
 }
 
 // ---- k_lift_layer: four texels per lane, a wave 256 texels of a sprite row, a workgroup four rows.  ALIGNED: the sprite's rows are
-// 16-byte aligned (one store per lane); else a texel is one dword (4-byte aligned rows) or four bytes.
-template <bool ALIGNED>
+// 16-byte aligned (one store per lane); else a texel is one dword (4-byte aligned rows) or four bytes.  MATTE (rtdd_lift_layer_matte): the
+// mask is an alpha image, select is 0, and a texel's alpha is its byte; the other instantiations are instruction for instruction what
+// they were.
+template <bool ALIGNED, bool MATTE = false>
 __global__ __launch_bounds__(256) void k_lift_layer(const uint8_t *__restrict__ orig, size_t op, const uint8_t *__restrict__ mask, size_t mp, int rows, int cols,
                                                     Effect::Lift k, bool dwords) {
     const int v = blockIdx.y * 4 + wave_id();
@@ -537,7 +539,10 @@ __global__ __launch_bounds__(256) void k_lift_layer(const uint8_t *__restrict__ 
     for (int i = 0; i < 4; i++) {
         const int x = k.x + u0 + i;
         t[i] = 0u;
-        if (row_in && u0 + i < k.spriteCols && x >= 0 && x < cols && is_selected(mask[(size_t)y * mp + x], k.select)) {
+        if (MATTE) {
+            const uint32_t a = row_in && u0 + i < k.spriteCols && x >= 0 && x < cols ? mask[(size_t)y * mp + x] : 0u;
+            if (a != 0u) t[i] = load_bgr(orig + (size_t)y * op + 3 * (size_t)x) | (a << 24);
+        } else if (row_in && u0 + i < k.spriteCols && x >= 0 && x < cols && is_selected(mask[(size_t)y * mp + x], k.select)) {
             t[i] = load_bgr(orig + (size_t)y * op + 3 * (size_t)x) | 0xff000000u;
         }
     }
@@ -551,12 +556,15 @@ __global__ __launch_bounds__(256) void k_lift_layer(const uint8_t *__restrict__ 
     }
 }
 
-// rtdd_lift_layer (arguments checked by effects_api.cpp): one launch.
+// rtdd_lift_layer and rtdd_lift_layer_matte (arguments checked by effects_api.cpp): one launch.
 int launch_lift(rtdd_ctx *ctx, const Effect &e) {
     const Effect::Lift &k = e.lift;
     const dim3 g((k.spriteCols + 255) / 256, (k.spriteRows + 3) / 4);
     const bool dwords = rows_aligned(k.sprite, k.spritePitch);
-    if (rows_aligned(k.sprite, k.spritePitch, 16)) hipLaunchKernelGGL((k_lift_layer<true>), g, dim3(256), 0, ctx->stream, e.original, e.originalPitch, k.mask, k.maskPitch, e.rows, e.cols, k, dwords);
+    if (e.kind == Effect::kLiftMatte) {
+        if (rows_aligned(k.sprite, k.spritePitch, 16)) hipLaunchKernelGGL((k_lift_layer<true, true>), g, dim3(256), 0, ctx->stream, e.original, e.originalPitch, k.mask, k.maskPitch, e.rows, e.cols, k, dwords);
+        else hipLaunchKernelGGL((k_lift_layer<false, true>), g, dim3(256), 0, ctx->stream, e.original, e.originalPitch, k.mask, k.maskPitch, e.rows, e.cols, k, dwords);
+    } else if (rows_aligned(k.sprite, k.spritePitch, 16)) hipLaunchKernelGGL((k_lift_layer<true>), g, dim3(256), 0, ctx->stream, e.original, e.originalPitch, k.mask, k.maskPitch, e.rows, e.cols, k, dwords);
     else hipLaunchKernelGGL((k_lift_layer<false>), g, dim3(256), 0, ctx->stream, e.original, e.originalPitch, k.mask, k.maskPitch, e.rows, e.cols, k, dwords);
     RTDD_LAUNCH_CHECK(ctx, "k_lift_layer");
     return RTDD_OK;

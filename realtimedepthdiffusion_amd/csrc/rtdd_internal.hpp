@@ -101,8 +101,8 @@ struct LiveTargets {
 // One depth effect, arguments checked: what to render, on which images, with which parameters.  Built by the rtdd_simulate_* entry
 // points (effects_api.cpp) and by a live frame (live_effect), launched by launch_effect, and logged by value (PendingOp) to be launched again.
 struct Effect {
-    enum : int { kRefocus = RTDD_EFFECT_HAZE + 1, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow, kParallax, kAmbientOcclusion, kLighting, kBokeh, kComposite, kRemove, kLift, kParallaxLayered };   // the extensions, after the public kinds
-    int kind = RTDD_EFFECT_NONE;                    // RTDD_EFFECT_DEFOCUS / _DESATURATION / _HAZE, kRefocus, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow, kParallax, kAmbientOcclusion, kLighting, kBokeh, kComposite, kRemove, kLift, kParallaxLayered
+    enum : int { kRefocus = RTDD_EFFECT_HAZE + 1, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow, kParallax, kAmbientOcclusion, kLighting, kBokeh, kComposite, kRemove, kLift, kParallaxLayered, kMaskDistance, kRefineMask, kLiftMatte };   // the extensions, after the public kinds
+    int kind = RTDD_EFFECT_NONE;                    // RTDD_EFFECT_DEFOCUS / _DESATURATION / _HAZE, kRefocus, kHazeEx, kStereo, kLensBlur, kRelight, kRelightShadow, kParallax, kAmbientOcclusion, kLighting, kBokeh, kComposite, kRemove, kLift, kParallaxLayered, kMaskDistance, kRefineMask, kLiftMatte
     const uint8_t *original = nullptr; size_t originalPitch = 0;
     const float *depth = nullptr; size_t depthPitch = 0;
     uint8_t *artistic = nullptr; size_t artisticPitch = 0;
@@ -172,12 +172,22 @@ struct Effect {
         float *depthOut = nullptr; size_t depthOutPitch = 0;       // null: no depth is written
     } remove = {};
     // a lifted sprite (kLift, rtdd_lift_layer): reads original (rows x cols) and the mask, writes the sprite; depth and artistic are null
+    // (kLiftMatte, rtdd_lift_layer_matte: `mask` is the alpha image, select 0)
     struct Lift {
         const uint8_t *mask = nullptr; size_t maskPitch = 0;
         int select = 0, x = 0, y = 0;
         uint8_t *sprite = nullptr; size_t spritePitch = 0;
         int spriteRows = 0, spriteCols = 0;
     } lift = {};
+    // a mask's distance transform (kMaskDistance, rtdd_mask_distance: writes dist2) or a refined mask (kRefineMask, rtdd_refine_mask:
+    // `refine` as the entry point checked it, by value, `reach` derived from it; writes out); original, depth and artistic are null
+    struct MaskOp {
+        const uint8_t *mask = nullptr; size_t maskPitch = 0;
+        int select = 0, reach = 0;
+        int32_t *dist2 = nullptr; size_t dist2Pitch = 0;
+        rtdd_mask_refine refine = {};
+        uint8_t *out = nullptr; size_t outPitch = 0;
+    } maskop = {};
 };
 
 // The defocus window scale K of src/GPUDepthEffect.cu:42, (int)(aperture * diagonal) -- double * float and the int products as there,
@@ -484,7 +494,14 @@ int launch_composite(rtdd_ctx *ctx, const Effect &e);
 // one workgroup takes a level of at most kRemoveApex samples to 1 x 1 and back, its whole chain (at most kRemoveApexChain samples) in LDS.
 constexpr int kRemoveTile = 64, kRemoveGroup = 3, kRemoveApex = 8192, kRemoveApexChain = kRemoveApex + kRemoveApex / 2 + 64;
 int launch_remove(rtdd_ctx *ctx, const Effect &e);
-int launch_lift(rtdd_ctx *ctx, const Effect &e);
+int launch_lift(rtdd_ctx *ctx, const Effect &e);                   // (Effect::kLiftMatte too)
+// ---- mask_distance.hip: Effect::kMaskDistance and Effect::kRefineMask (called by launch_effect) ------
+// The distance transform's geometry (DESIGN.md section 4 "Mask distance"), mirrored by EDT_TILE_W, EDT_TILE_H, EDT_BAND, EDT_LDS_REACH
+// and mask_distance_plan() of realtimedepthdiffusion_amd/__init__.py: the column pass works on words of kEdtBand rows of a column and
+// flags blocks of kEdtTileW columns; a workgroup of the row pass owns kEdtTileW x kEdtTileH pixels, a wave a row of them, and stages its
+// row segment with a halo of the reach in LDS up to a reach of kEdtLdsReach (beyond it the neighbours come through the caches).
+constexpr int kEdtTileW = 64, kEdtTileH = 4, kEdtBand = 64, kEdtLdsReach = 224, kEdtMaxReach = 1024;
+int launch_mask_distance(rtdd_ctx *ctx, const Effect &e);
 
 // ---- cascade.hip -------------------------------------------------------------------------------
 int launch_bgr2gray(rtdd_ctx *ctx, const uint8_t *bgr, size_t bp, uint8_t *gray, size_t gp, int rows, int cols);
